@@ -37,7 +37,13 @@ the last exchange joined.  The process holds ONE RCCL user: the native communica
 process already mapped); torch.distributed runs over gloo and carries host-side rendezvous, barriers and the max-over-ranks
 only.  Rank 0 writes the synthetic model directory once; `per_rank_ms_per_step` carries every rank's own time.
 
-Rank 0 prints ONE JSON line with, besides the contract fields:
+A plain run sets up, warms up, times the K steps and prints ONE JSON line: the contract fields (`value`, `ms_per_step` of the K
+uninstrumented steps, `dtype`, ...) with `config`, `split`, `per_rank_ms_per_step` and `gpu_busy` (GPU seconds of the predicts
+inside the timed region, from HIP events on the model's stream, one pair per predict, next to the region's wall clock), which the
+timed steps give at no extra cost.  `--dump-outputs DIR` writes what the last timed step computed (DIR/detections.npy,
+DIR/masks.npy and, at N > 1, the all-gathered DIR/all_detections.npy, DIR/all_masks.npy; float32, at most 64 MB in all).
+Every other measurement runs only under `--full`, which adds to the line:
+  stage_ms_last_step — per-stage ms of the last instrumented step (see roofline)
   roofline     — dominant conv kernel (the tile class with the largest share of the step): its ALGORITHMIC flops per
                  launch ÷ its average launch duration, both measured live with HIP events on the launching stream
                  in --event-steps further steps of the same batch run RIGHT BEHIND the timed region (round 6: every timed
@@ -51,8 +57,6 @@ Rank 0 prints ONE JSON line with, besides the contract fields:
                  protocol: 1 warm-up + 5 timed images
   parity_e2e   — HIP predict vs the oracle's predict on 16 images, per compute mode: share of detections with the
                  same class id and a box within 1e-4
-  gpu_busy     — GPU seconds of the predicts inside the timed region, from HIP events on the model's stream (one pair per
-                 predict), next to the wall clock of the region: measured in THIS run
   h2d_included — the same step with the batch in pinned HOST memory (25 MB H2D + 2.5 MB D2H per step inside the timing):
                  what the reference's per-image timing (EvaluateCommand.swift:167-179) would include; never `value`
   profiles_ref — constants read from committed files under profiles/ (PMC traffic, the matrix cores' sustained rate):
@@ -64,6 +68,7 @@ import argparse
 import importlib
 import json
 import os
+import shutil
 import socket
 import subprocess
 import sys
@@ -100,6 +105,13 @@ def main():
                          "(profiles/r03_fp64_trunk_parity.json), 99.97 %% of 25 600 detections matched end to end with the CPU oracle (profiles/r03_parity_e2e_256.json); "
                          "f32: v_mfma_f32_32x32x2_f32 (round-1 headline, now under other_modes); f32s: two-part split; "
                          "f16: fp16 tensors + fp16 MFMA (BASELINE configs[3])")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: instrumented steps (roofline, stage_ms_last_step), the live MFMA probe, "
+                         "other_modes, h2d_included, cpu_baseline and parity_e2e; the --no-* / --cpu-images / --e2e-images / --event-steps "
+                         "options below shape these legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the detections and masks of the last timed step as float32 DIR/<name>.npy (a fixed seeded sample of "
+                         "the images when they would exceed 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-live-probe", action="store_true", help="skip the in-process MFMA probe and the clock / power sampler (roofline.sustained_peak_live, clock_mhz)")
     ap.add_argument("--no-calibrate", action="store_true",
@@ -120,6 +132,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus))
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
@@ -238,31 +252,39 @@ def main():
     elapsed = time.perf_counter() - t0
     busy_s = (m.get_int("gpu_busy_us") - busy0) * 1e-6
     busy_calls = m.get_int("predict_calls") - calls0
-    # The instrumented steps: the SAME step a few more times right behind the timed region, with every conv launch
-    # bracketed by HIP events and the stage timer on — `roofline` and `stage_ms_last_step` come from these, `value` from none of them.
-    ev_steps = 0 if args.no_kernel_events else (args.event_steps if args.event_steps > 0 else args.steps)
-    m.enable_timing(True)
-    if not args.no_kernel_events:
-        m.conv_profile_enable(True)
-    torch.cuda.synchronize()
-    t_ev = time.perf_counter()
-    for i in range(max(ev_steps, 1)):
-        step()
-    drain()
-    torch.cuda.synchronize()
-    ev_elapsed = time.perf_counter() - t_ev            # wall time of the instrumented steps: what the shares below are taken against
-    if not args.no_kernel_events:
-        m.conv_profile_enable(False)                   # window closed, totals kept
+    # what the last timed step handed its caller, copied before any further step overwrites it
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        outputs = {"detections": det.cpu().numpy(), "masks": mask.cpu().numpy()}
+        if gather is not None:
+            outputs.update(all_detections=all_det.cpu().numpy(), all_masks=all_mask.cpu().numpy())
+    prof = None
+    if args.full:
+        # The instrumented steps: the SAME step a few more times right behind the timed region, with every conv launch
+        # bracketed by HIP events and the stage timer on — `roofline` and `stage_ms_last_step` come from these, `value` from none of them.
+        ev_steps = 0 if args.no_kernel_events else (args.event_steps if args.event_steps > 0 else args.steps)
+        m.enable_timing(True)
+        if not args.no_kernel_events:
+            m.conv_profile_enable(True)
+        torch.cuda.synchronize()
+        t_ev = time.perf_counter()
+        for i in range(max(ev_steps, 1)):
+            step()
+        drain()
+        torch.cuda.synchronize()
+        ev_elapsed = time.perf_counter() - t_ev            # wall time of the instrumented steps: what the shares below are taken against
+        if not args.no_kernel_events:
+            m.conv_profile_enable(False)                   # window closed, totals kept
+            prof = m.conv_profile()
+            prof_groups = m.conv_profile_groups()
+            prof_bytes = m.conv_profile_bytes()
+        stages = m.stage_ms()
     if use_dist:
         dist.barrier()
     every = gather_elapsed(elapsed, world) if use_dist else [elapsed]
     per_rank_ms = [1e3 * e / args.steps for e in every]
     elapsed = max(every)                                        # the job is as slow as its slowest rank
 
-    prof = m.conv_profile() if not args.no_kernel_events else None
-    prof_groups = m.conv_profile_groups() if not args.no_kernel_events else None
-    prof_bytes = m.conv_profile_bytes() if not args.no_kernel_events else None
-    stages = m.stage_ms()
     n_prop = int(m.read_tensor("keep_count", 0)[0])
     n_det = int((det[0, :, 5] > 0).sum().item())
     # Same-run box normaliser, OUTSIDE the timed region (a sampler thread beside the timed loop cost 16 % of it: the
@@ -270,7 +292,7 @@ def main():
     # while a host thread samples the shader clock / socket power through librocm_smi64; then 1.5 s of back-to-back MFMAs on changing
     # register operands, no operand traffic (mrcnn_bench_mfma_probe), give what the matrix cores of THIS box sustain right now.
     smi, live_probe = None, None
-    if rank == 0 and not args.no_live_probe:
+    if rank == 0 and args.full and not args.no_live_probe:
         m.enable_timing(False)
         sampler = SmiSampler(local_rank)
         sampler.start()
@@ -301,12 +323,13 @@ def main():
                        "model_loaded_by": loaded_by,
                        "global_batch": n_gpus * B, "parallelism": f"dp{n_gpus}" if n_gpus > 1 else "single",
                        "proposals_kept_image0": n_prop, "detections_image0": n_det},
-            "stage_ms_last_step": {k: round(v, 3) for k, v in stages.items()},
             "per_rank_ms_per_step": {"min": round(min(per_rank_ms), 3), "max": round(max(per_rank_ms), 3), "ranks": [round(v, 3) for v in per_rank_ms]},
             "gpu_busy": {"gpu_seconds": round(busy_s, 4), "wall_seconds": round(elapsed, 4), "frac": round(busy_s / elapsed, 4),
                          "predicts": int(busy_calls),
                          "how": "HIP events on the model's stream around every predict of the timed region (rank 0), this run"},
         }
+        if args.full:
+            out["stage_ms_last_step"] = {k: round(v, 3) for k, v in stages.items()}
         if split_info is not None:
             out["split"] = dict(split_info, note="scale-aware split: power-of-two exponent per tensor group from one calibration predict "
                                 "(max |a| * 2^e in [2^11, 2^12)); small / inexact = non-zero stored inputs below 2^-8 of their tensor's maximum / "
@@ -382,8 +405,8 @@ def main():
                     "traffic_bytes_per_launch_dominant_kernel": pmc_traffic(args.dtype, dom), "traffic_source": pmc_traffic_source(args.dtype),
                     "sustained_peak": sustained_peak(args.dtype, parts, achieved)}
         # images of the end-to-end parity leg (the oracle sees the same ones): seed 1 stream, after this rank's bench batch
-        n_e2e = 0 if (n_gpus != 1 or args.no_cpu_baseline) else max(args.e2e_images, 0)
-        e2e_imgs = rng.integers(0, 256, (max(n_e2e, 1 + args.cpu_images), args.size, args.size, 3), dtype=np.uint8)
+        n_e2e = 0 if (n_gpus != 1 or args.no_cpu_baseline or not args.full) else max(args.e2e_images, 0)
+        e2e_imgs = rng.integers(0, 256, (max(n_e2e, 1 + args.cpu_images), args.size, args.size, 3), dtype=np.uint8) if args.full else None
         e2e_pred = {}
 
         def hip_predict_all(model):
@@ -395,7 +418,7 @@ def main():
 
         if n_e2e:
             e2e_pred[args.dtype] = hip_predict_all(m)
-        if n_gpus == 1 and not args.no_other_modes:
+        if n_gpus == 1 and args.full and not args.no_other_modes:
             # the same workload in the engine's other compute modes (same images, same weights): not the headline value
             out["other_modes"] = {}
             for mode in ("f32", "f32x3", "f32s", "f16"):
@@ -439,7 +462,7 @@ def main():
                                                      "f32x3": "fp32 tensors, three fp16 MFMA passes over a three-part split of the "
                                                               "activations (exact for 0.5 <= |a| < 65504, 2^-25 absolute below)"}[mode]}
                 del mm
-        if n_gpus == 1:
+        if n_gpus == 1 and args.full:
             # the same step with the batch in pinned host memory: H2D of the images and D2H of the records inside the timing
             himg = images.cpu().pin_memory()
             hdet = torch.empty(det.shape, dtype=torch.float32).pin_memory()
@@ -470,15 +493,19 @@ def main():
                                            f"{(hdet.numel() + hmask.numel()) * 4 / 1e6:.1f} MB D2H per step inside the timing, through the pipelined "
                                            f"host entry (mrcnn_maskrcnn_submit / _collect: the copy of the next batch under the predict of this one); "
                                            f"synchronous_entry = mrcnn_maskrcnn_predict with host buffers, copy and compute back to back; never `value`"}
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if n_gpus == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"], oracle_pred = cpu_baseline(model_dir, cfg, args, e2e_imgs)
             if n_e2e:
                 out["parity_e2e"] = parity_e2e(e2e_pred, oracle_pred, n_e2e)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
+    if rank == 0:
+        shutil.rmtree(model_dir, ignore_errors=True)           # this run's synthetic artefacts (~130 MB at the headline size)
 
 
 # ---- the host-side group of an N > 1 run (gloo: rendezvous, barriers, the max-over-ranks of a float — never a GPU communicator) ----
@@ -512,6 +539,22 @@ def tile_class_entry(v, nbytes, ev_steps, ev_elapsed, peak_tflops):
             "tflops": round(tflops, 1), "frac_of_mfma": round(tflops / peak_tflops, 4),
             "algorithmic_bytes_per_launch": int(nbytes / launches), "gbps": round(gbps, 1),
             "frac_of_hbm": round(gbps / PEAK_HBM_GBPS, 4), "frac_of_hbm_measured": round(gbps / HBM_MEASURED_GBPS, 4)}
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as float32 out_dir/<name>.npy.  Should they exceed DUMP_LIMIT_BYTES in all, every array keeps the same
+    share of its images (axis 0), drawn by a fixed seed, so that two runs of the same arguments write the same sample."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.size * 4 for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, a.shape[0] * DUMP_LIMIT_BYTES // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def shared_model_dir(rank, use_dist, write):

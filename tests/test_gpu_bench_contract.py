@@ -1,16 +1,18 @@
 """bench.py's output contract, on a reduced workload so it runs in seconds: exactly one JSON line on stdout carrying the
-driver's fields plus the `roofline` and `cpu_baseline` objects (and `other_modes`), also through torch.distributed.run with the
-RCCL leg forced at world size 1."""
+driver's fields plus, under --full, the `roofline` and `cpu_baseline` objects (and `other_modes`), also through torch.distributed.run
+with the RCCL leg forced at world size 1; a plain run carries the driver's fields alone and dumps its outputs on request."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--arch", "resnet50", "--size", "256", "--batch", "2", "--steps", "3", "--warmup", "1", "--cpu-images", "1", "--e2e-images", "2"]
+PLAIN = ["--arch", "resnet50", "--size", "256", "--batch", "2", "--steps", "3", "--warmup", "1"]
+SMALL = ["--full", "--cpu-images", "1", "--e2e-images", "2"] + PLAIN
 
 
 def _check(line, n_gpus=1, steps=3, warmup=1):
@@ -85,6 +87,33 @@ def test_bench_gpus_1_without_torchrun_prints_n_gpus_1():
     assert len(lines) == 1
     j = _check(lines[0])
     assert j["config"]["parallelism"] == "single"
+
+
+def test_plain_run_prints_the_headline_alone_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) is set-up, warm-up, the timed steps and the line: the driver's fields, none of the --full records.
+    --dump-outputs writes what the last timed step handed its caller, and two runs of the same arguments write the same arrays."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dump-outputs", str(d)] + PLAIN,
+                           capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout
+        j = json.loads(lines[0])
+        assert j["metric"].startswith("images/sec") and j["unit"] == "images/s" and j["higher_is_better"] is True and j["dtype"] == "f32x3"
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["gpu_busy"]["predicts"] == 3                # exactly --steps timed steps
+        assert abs(j["value"] - 2 * 1e3 / j["ms_per_step"]) / j["value"] < 1e-2
+        for k in ("roofline", "stage_ms_last_step", "profiles_ref", "other_modes", "h2d_included", "cpu_baseline", "parity_e2e"):
+            assert k not in j, k
+        assert sorted(os.listdir(d)) == ["detections.npy", "masks.npy"]
+        det, mask = np.load(d / "detections.npy"), np.load(d / "masks.npy")
+        assert det.dtype == mask.dtype == np.float32 and det.shape[0] == mask.shape[0] == 2 and det.shape[2] == 6
+        assert mask.shape[1] == det.shape[1] and int((det[0, :, 5] > 0).sum()) == j["config"]["detections_image0"] > 0
+        dumps.append((det, mask))
+    np.testing.assert_array_equal(dumps[0][0], dumps[1][0])
+    np.testing.assert_array_equal(dumps[0][1], dumps[1][1])
 
 
 def test_bench_self_launch_covers_the_visible_gpus():

@@ -483,6 +483,31 @@ def test_bench_host_core_count():
     assert 1 <= physical <= logical == os.cpu_count()
 
 
+def test_bench_dump_outputs_stays_under_its_limit_with_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 files named after the arrays; above the size limit every array keeps the same share of its
+    images, the same images from run to run; under it the arrays are written whole."""
+    import bench
+    rng = np.random.default_rng(3)
+    arrays = {"detections": rng.random((8, 10, 6)), "masks": rng.random((8, 10, 4, 4)).astype(np.float32)}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    for k, a in arrays.items():
+        got = np.load(tmp_path / "whole" / f"{k}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, a.astype(np.float32)), k
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8 * 10 * (6 + 16) * 4 // 2)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    total = 0
+    for k, a in arrays.items():
+        got, again = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert got.shape == (4,) + a.shape[1:] and np.array_equal(got, again), k
+        assert all(any(np.array_equal(g, r) for r in a.astype(np.float32)) for g in got), k
+        total += got.nbytes
+    assert total <= bench.DUMP_LIMIT_BYTES
+    det, mask = np.load(tmp_path / "a" / "detections.npy"), np.load(tmp_path / "a" / "masks.npy")
+    rows = [int(np.flatnonzero((arrays["detections"].astype(np.float32) == d).all(axis=(1, 2)))[0]) for d in det]
+    assert rows == sorted(rows) and np.array_equal(mask, arrays["masks"][rows])          # the same images in every array
+
+
 def test_native_dist_shard_matches_the_torch_twin(pkg):
     """mrcnn_dist_shard (C ABI, host arithmetic) = dist.shard_bounds for every (batch, world, rank): contiguous blocks that
     differ by at most one image and cover the batch exactly; record geometry = 316 000 B at the defaults."""

@@ -12,7 +12,7 @@ OUT=$R/gpurun_out/profiles_$RND
 mkdir -p $OUT
 export TMPDIR=/tmp
 for dt in $MODES; do
-  [ $dt = f32x3 ] || python bench.py --steps 10 --warmup 3 --dtype $dt --no-cpu-baseline --no-other-modes > $OUT/${RND}_bench_n1_$dt.json 2> $OUT/bench_$dt.err
+  [ $dt = f32x3 ] || python bench.py --full --steps 10 --warmup 3 --dtype $dt --no-cpu-baseline --no-other-modes > $OUT/${RND}_bench_n1_$dt.json 2> $OUT/bench_$dt.err
   python tools/conv_layer_table.py $dt 3 8 > $OUT/${RND}_conv_shapes_$dt.txt 2>/dev/null
 done
 python tools/conv_layer_table.py f32x3 5 1 > $OUT/${RND}_conv_shapes_f32x3_batch1.txt 2>/dev/null
@@ -20,7 +20,7 @@ cd /tmp
 BENCH="python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-modes --no-kernel-events --no-live-probe"
 for dt in $MODES; do
   rm -rf /tmp/prof_$dt
-  timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_$dt -o p -- python $R/bench.py --steps 5 --warmup 2 --dtype $dt --no-cpu-baseline --no-other-modes --no-live-probe > $OUT/stats_$dt.json 2> $OUT/stats_$dt.err
+  timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_$dt -o p -- python $R/bench.py --full --steps 5 --warmup 2 --dtype $dt --no-cpu-baseline --no-other-modes --no-live-probe > $OUT/stats_$dt.json 2> $OUT/stats_$dt.err
   db=$(find /tmp/prof_$dt -name "*.db" | head -1)
   python $R/tools/rocpd_summary.py $db $OUT/${RND}_kernel_stats_$dt.csv
   i=0
@@ -91,16 +91,16 @@ timeout 400 python tools/fp64_trunk_parity.py --out $OUT/${RND}_fp64_trunk_parit
   { echo "# batch 1"; python $R/tools/trace_gaps.py /tmp/tr1; echo "# batch 8"; python $R/tools/trace_gaps.py /tmp/tr8; } > $OUT/${RND}_trace_gaps_f32x3.txt
   python $R/tools/trace_gaps.py /tmp/tr1 --list > $OUT/${RND}_trace_b1_kernels_f32x3.txt )
 # per-GPU slices of the other BASELINE configs (configs[2]: ResNet50; configs[3]: fp16; configs[4]: 1536², 2 classes, pre_nms 12000) and the batch sweep
-python bench.py --steps 10 --warmup 3 --arch resnet50 --no-cpu-baseline --no-other-modes > $OUT/${RND}_bench_n1_resnet50.json 2>/dev/null
-python bench.py --steps 10 --warmup 3 --arch resnet50 --dtype f16 --no-cpu-baseline --no-other-modes > $OUT/${RND}_bench_n1_resnet50_f16.json 2>/dev/null
-python bench.py --steps 5 --warmup 2 --size 1536 --num-classes 2 --pre-nms 12000 --no-cpu-baseline --no-other-modes > $OUT/${RND}_bench_n1_config5_1536.json 2>/dev/null
-for b in 1 2 4 16 32; do python bench.py --steps 10 --warmup 3 --batch $b --no-cpu-baseline --no-other-modes --no-kernel-events > $OUT/${RND}_bench_n1_batch$b.json 2>/dev/null; done
+python bench.py --full --steps 10 --warmup 3 --arch resnet50 --no-cpu-baseline --no-other-modes > $OUT/${RND}_bench_n1_resnet50.json 2>/dev/null
+python bench.py --full --steps 10 --warmup 3 --arch resnet50 --dtype f16 --no-cpu-baseline --no-other-modes > $OUT/${RND}_bench_n1_resnet50_f16.json 2>/dev/null
+python bench.py --full --steps 5 --warmup 2 --size 1536 --num-classes 2 --pre-nms 12000 --no-cpu-baseline --no-other-modes > $OUT/${RND}_bench_n1_config5_1536.json 2>/dev/null
+for b in 1 2 4 16 32; do python bench.py --full --steps 10 --warmup 3 --batch $b --no-cpu-baseline --no-other-modes --no-kernel-events > $OUT/${RND}_bench_n1_batch$b.json 2>/dev/null; done
 # 64-image end-to-end agreement with the CPU oracle (about 6 minutes of host time)
-python bench.py --steps 5 --warmup 2 --e2e-images 64 --no-kernel-events 2>/dev/null | python -c "import json,sys; print(json.dumps(json.loads(sys.stdin.read())['parity_e2e'], indent=1))" > $OUT/${RND}_parity_e2e_64.json
+python bench.py --full --steps 5 --warmup 2 --e2e-images 64 --no-kernel-events 2>/dev/null | python -c "import json,sys; print(json.dumps(json.loads(sys.stdin.read())['parity_e2e'], indent=1))" > $OUT/${RND}_parity_e2e_64.json
 timeout 900 python tools/soak_determinism.py 200 > $OUT/${RND}_soak_determinism.txt 2>&1
 # the default bench line last: it reports the counters / probe figures of THIS refresh (bench.py reads them from profiles/)
 cp $OUT/${RND}_pmc_traffic_*.json $OUT/${RND}_mfma_power.txt $R/profiles/ 2>/dev/null
-python bench.py --steps 10 --warmup 3 > $OUT/${RND}_bench_n1.json 2> $OUT/bench_default.err
+python bench.py --full --steps 10 --warmup 3 > $OUT/${RND}_bench_n1.json 2> $OUT/bench_default.err
 head -5 $OUT/${RND}_kernel_stats_f32x3.csv | cut -c1-160
 cut -c1-300 $OUT/${RND}_bench_n1.json
 cat $OUT/${RND}_pmc_kernels_f32x3.txt
