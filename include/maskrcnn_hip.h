@@ -309,7 +309,8 @@ MRCNN_API int mrcnn_model_get_int(mrcnn_model* model, const char* key, int64_t* 
 
 /* Debug taps for parity tests: copies a named intermediate of the last predict (image b) to a host
  * buffer of `capacity` floats and reports its element count.  Names: "rpn_probs" (A,2),
- * "rpn_deltas" (A,4), "P2".."P5" (H,W,256 NHWC), "topk_idx" (int32 stored as float-exact values),
+ * "rpn_deltas" (A,4), "C1" (H/4,W/4,64 NHWC: the pooled stem output), "C2".."C5" (the backbone stages' outputs, NHWC,
+ * 256 / 512 / 1024 / 2048 channels), "P2".."P5" (H,W,256 NHWC), "topk_idx" (int32 stored as float-exact values),
  * "boxes_sorted" (n,4), "rois" (maxProposals,4), "pooled" (maxProposals,7,7,256 NHWC),
  * "cls_probs" (maxProposals,nc), "cls_bbox" (maxProposals,nc*4), "cls6" (maxProposals,6),
  * "detections" (maxDetections,6), "pooled_mask" (maxDetections,14,14,256 NHWC), "mask" (maxDetections,784),

@@ -927,6 +927,10 @@ void Model::build_maskrcnn()
             });
             x_after_stem = xo;
         }
+        // trunk taps C1..C5 (parity tests): the arena only grows, so these buffers are not reused by a later layer and still hold
+        // their values after predict — C1 the pooled stem output; C{st} the last block output of stage st, which in the fp16 mode's
+        // fused stages is stage_main or stage_alt (whichever the last block wrote)
+        taps["C1"] = {x_after_stem.p, x_after_stem.sB(), dt, g_c1};
         Tensor4 x = x_after_stem;
         Tensor4 Cf[6];
         const int f1s[6] = {0, 0, 64, 128, 256, 512}, f3s[6] = {0, 0, 256, 512, 1024, 2048};
@@ -997,6 +1001,7 @@ void Model::build_maskrcnn()
             bneck_stage_flush((x.H / (f1s[st] == 256 ? 8 : 16)) * (x.W / 16));
             Cf[st] = x;
             g_C[st] = g_stage;
+            taps["C" + std::to_string(st)] = {x.p, x.sB(), dt, g_stage};
         }
         // FPN: lateral 1×1 (+ nearest 2× upsample of the level above, fused as a shifted residual), then 3×3
         Tensor4 L5 = T(Cf[5].H, Cf[5].W, 256), L4 = T(Cf[4].H, Cf[4].W, 256), L3 = T(Cf[3].H, Cf[3].W, 256), L2 = T(Cf[2].H, Cf[2].W, 256);

@@ -190,6 +190,10 @@ class MaskRCNN(_Model):
 
     # -- parity / profiling hooks -------------------------------------------------------------------
     def read_tensor(self, name: str, image_index: int = 0) -> np.ndarray:
+        """A named intermediate of the last predict for one image, flat fp32 (include/maskrcnn_hip.h: mrcnn_model_read_tensor).
+        Trunk: "C1" (the pooled stem output, NHWC 64 channels), "C2".."C5" (the backbone stages), "P2".."P5" (NHWC 256 channels),
+        "rpn_probs", "rpn_deltas"; then "topk_idx", "boxes_sorted", "keep_count", "rois", "pooled", "cls_probs", "cls_bbox", "cls6",
+        "detections", "pooled_mask", "mask_row_flags", "mask".  Split-mode tensors come back without their stored exponent."""
         cnt = C.c_int64(0)
         L = _lib.lib()
         st = L.mrcnn_model_read_tensor(self._h, name.encode(), image_index, None, 0, C.byref(cnt))
