@@ -213,6 +213,20 @@ MRCNN_API int mrcnn_maskrcnn_predict(mrcnn_model* model, const uint8_t* rgb, int
 MRCNN_API int mrcnn_maskrcnn_predict_scalefit(mrcnn_model* model, const uint8_t* rgb, int batch, int height, int width, int memspace,
                                               float* detections, float* masks);
 MRCNN_API int mrcnn_unletterbox_boxes(float* detections, int64_t n, int64_t stride, int src_h, int src_w, int model_h, int model_w);
+/* One predict over images of DIFFERENT sizes — what a host walking a directory of photos has (EvaluateCommand.swift:159-200: no two
+ * consecutive COCO images share a size).  images[b] is RGB8 interleaved (height, width, 3), any size 1..32767 per side; every image
+ * is letterboxed into the model's input with its OWN geometry inside ONE pre-processing launch (a per-image descriptor table on the
+ * device; the letterboxed images are never materialised), so record b equals mrcnn_maskrcnn_predict_scalefit on image b alone, bit
+ * for bit.  Outputs as predict_scalefit's: detections (batch, maxDetections, 6) normalized in the LETTERBOXED frame, masks (batch,
+ * maxDetections, 28, 28), zero-padded.  memspace holds for every rgb pointer and both outputs; the table itself is host memory.
+ * The images are copied to the device inside the call: the caller's buffers (and the table) only have to stay valid until it
+ * returns.  Synchronous; never replayed from a captured graph; range recovery of the split modes works as in predict.
+ * Errors: null table / null rgb -> MRCNN_ERR_INVALID; batch outside 1..max_batch or a side outside 1..32767 -> MRCNN_ERR_SHAPE;
+ * the message names the index of the offending image.  mrcnn_paste_masks_source (below) turns the result into boxes and binary
+ * masks in each image's own pixels. */
+typedef struct { const uint8_t* rgb; int32_t height, width; } mrcnn_image;
+MRCNN_API int mrcnn_maskrcnn_predict_images(mrcnn_model* model, const mrcnn_image* images, int batch, int memspace,
+                                            float* detections, float* masks);
 /* Pipelined host entry — the evaluate loop of EvaluateCommand.swift:167-179 (images handed over one call after the other, the
  * hand-over inside the per-image time) with the hand-over of batch i + 1 OVERLAPPED with the computation of batch i:
  *   mrcnn_maskrcnn_submit   copies a batch of host images (pinned memory makes the copy asynchronous) on the handle's copy
@@ -423,6 +437,19 @@ MRCNN_API int mrcnn_letterbox_rgb(const uint8_t* src, int h, int w, int memspace
  * with half-pixel centres, `>= threshold`; rows with score <= 0 give empty masks. image_w % 4 == 0. */
 MRCNN_API int mrcnn_paste_masks(const float* detections, int64_t det_stride, const float* masks, int n, int mask_size,
                                 int image_h, int image_w, float threshold, int memspace, uint8_t* out);
+/* The same for a batch of images of DIFFERENT sizes, in each image's own pixels — the way back from mrcnn_maskrcnn_predict_images.
+ * detections (batch, rows, 6) / masks (batch, rows, mask_size, mask_size) are what that call returned (rows = maxDetections), heights
+ * / widths the sizes of the source images, model_h / model_w the model's input size.  For image b, row i:
+ *   detections_src (batch, rows, 6)  the row with its box mapped to the SOURCE frame exactly as mrcnn_unletterbox_boxes(..., heights[b],
+ *                                    widths[b], model_h, model_w) maps it (all-zero rows stay all-zero; class id and score copied)
+ *   out + out_offsets[b] + i*h_b*w_b the h_b × w_b uint8 {0,1} mask mrcnn_paste_masks gives for that mapped box at image_h = h_b,
+ *                                    image_w = w_b.  ANY width (no `% 4` rule here).
+ * out_offsets: batch byte offsets, each a multiple of 16 (the planes of different images must not overlap); bytes of `out` that no
+ * plane covers are left untouched.  memspace holds for detections, masks, detections_src and out; heights, widths and out_offsets
+ * are host arrays.  The un-letterbox runs on the device and one launch pastes the whole batch. */
+MRCNN_API int mrcnn_paste_masks_source(const float* detections, const float* masks, int batch, int rows, int mask_size,
+                                       const int32_t* heights, const int32_t* widths, int model_h, int model_w, float threshold,
+                                       int memspace, float* detections_src, uint8_t* out, const int64_t* out_offsets);
 /* 28×28 mask → 8-bit: UInt8(255 - v/2*255) (Detection.swift:83-85). */
 MRCNN_API int mrcnn_mask_to_u8(const float* mask, int64_t n, uint8_t* out);
 /* The same on Double input — the type Core ML hands maskFromFeatureValue (Detection.swift:77); for hosts that widen the fp32

@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = [
     "mrcnn_dist_all_gather_records", "mrcnn_maskrcnn_predict_sharded", "mrcnn_mask_to_u8_f64",
     "mrcnn_dist_all_gather_records_async", "mrcnn_dist_wait", "mrcnn_dist_recovered", "mrcnn_dist_rccl_shared", "mrcnn_dist_plan", "mrcnn_dist_simulate_host",
     "mrcnn_maskrcnn_predict_scalefit", "mrcnn_unletterbox_boxes",
+    "mrcnn_maskrcnn_predict_images", "mrcnn_paste_masks_source",
 ]
 # declared in include/maskrcnn_hip_test.h (test / measurement entry points of the same library)
 TEST_SYMBOLS = [
@@ -70,6 +71,10 @@ class SplitGroupStat(C.Structure):   # mrcnn_split_group_stat
 class DetectionRecord(C.Structure):  # mrcnn_detection
     _fields_ = [("index", C.c_int64), ("x", C.c_double), ("y", C.c_double), ("w", C.c_double), ("h", C.c_double),
                 ("class_id", C.c_int64), ("score", C.c_double)]
+
+
+class Image(C.Structure):           # mrcnn_image
+    _fields_ = [("rgb", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32)]
 
 
 _lib = None
@@ -120,6 +125,8 @@ def lib():
     L.mrcnn_maskrcnn_predict.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     L.mrcnn_maskrcnn_predict_scalefit.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     L.mrcnn_unletterbox_boxes.argtypes = [vp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.mrcnn_maskrcnn_predict_images.argtypes = [vp, C.POINTER(Image), C.c_int, C.c_int, vp, vp]
+    L.mrcnn_paste_masks_source.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp]
     L.mrcnn_maskrcnn_predict_async.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.mrcnn_maskrcnn_submit.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
     L.mrcnn_maskrcnn_collect.argtypes = [vp, vp, vp, C.POINTER(C.c_int)]

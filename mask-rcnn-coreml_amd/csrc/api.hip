@@ -548,6 +548,14 @@ extern "C" int mrcnn_maskrcnn_predict_scalefit(mrcnn_model* model, const uint8_t
         model->m.predict(rgb, batch, height, width, memspace, detections, masks, true, true);
     });
 }
+extern "C" int mrcnn_maskrcnn_predict_images(mrcnn_model* model, const mrcnn_image* images, int batch, int memspace, float* detections,
+                                             float* masks)
+{
+    return guarded([&] {
+        MRCNN_REQUIRE(model, MRCNN_ERR_INVALID, "null model");
+        model->m.predict_images(images, batch, memspace, detections, masks);
+    });
+}
 extern "C" int mrcnn_unletterbox_boxes(float* detections, int64_t n, int64_t stride, int h, int w, int H, int W)
 {
     return guarded([&] {
@@ -1384,6 +1392,65 @@ extern "C" int mrcnn_paste_masks(const float* detections, int64_t det_stride, co
         paste_masks_forward(st.s, d, det_stride, m, n, mask_size, image_h, image_w, threshold, o);
         HIP_CHECK(hipStreamSynchronize(st.s));
         if (memspace != MRCNN_DEVICE) HIP_CHECK(hipMemcpy(out, to.p, bytes, hipMemcpyDeviceToHost));
+    });
+}
+
+extern "C" int mrcnn_paste_masks_source(const float* detections, const float* masks, int batch, int rows, int mask_size,
+                                        const int32_t* heights, const int32_t* widths, int model_h, int model_w, float threshold,
+                                        int memspace, float* detections_src, uint8_t* out, const int64_t* out_offsets)
+{
+    return guarded([&] {
+        require_gpu();
+        MRCNN_REQUIRE(detections && masks && heights && widths && detections_src && out && out_offsets, MRCNN_ERR_INVALID, "null paste_masks_source argument");
+        MRCNN_REQUIRE(batch >= 0 && rows >= 0 && mask_size >= 2 && model_h > 0 && model_w > 0, MRCNN_ERR_INVALID, "bad paste_masks_source argument");
+        MRCNN_REQUIRE((long)batch * rows < (1L << 31), MRCNN_ERR_SHAPE, "paste_masks_source: %d x %d rows are too many", batch, rows);
+        if (batch == 0 || rows == 0) return;
+        std::vector<ImageGeom> geom((size_t)batch);
+        long max_bytes = 0;
+        int64_t extent = 0;
+        for (int b = 0; b < batch; ++b) {
+            ImageGeom& g = geom[(size_t)b];
+            g.h = heights[b]; g.w = widths[b]; g.offset = out_offsets[b];
+            MRCNN_REQUIRE(g.h >= 1 && g.h <= 32767 && g.w >= 1 && g.w <= 32767, MRCNN_ERR_SHAPE,
+                          "image %d of the batch is %dx%d: height and width must lie in 1..32767", b, g.h, g.w);
+            MRCNN_REQUIRE(g.offset >= 0 && g.offset % 16 == 0, MRCNN_ERR_INVALID, "image %d of the batch: out_offsets[%d] = %lld is not a non-negative multiple of 16",
+                          b, b, (long long)g.offset);
+            MRCNN_REQUIRE(mrcnn_letterbox_geometry(g.h, g.w, model_h, model_w, &g.nh, &g.nw, &g.py, &g.px) == MRCNN_OK, MRCNN_ERR_INVALID,
+                          "image %d of the batch: bad letterbox geometry", b);
+            const long bytes = (long)rows * g.h * g.w;
+            max_bytes = bytes > max_bytes ? bytes : max_bytes;
+            extent = g.offset + bytes > extent ? g.offset + bytes : extent;
+        }
+        for (int a = 0; a < batch; ++a)
+            for (int b = a + 1; b < batch; ++b) {
+                const int64_t a0 = geom[(size_t)a].offset, a1 = a0 + (int64_t)rows * geom[(size_t)a].h * geom[(size_t)a].w;
+                const int64_t b0 = geom[(size_t)b].offset, b1 = b0 + (int64_t)rows * geom[(size_t)b].h * geom[(size_t)b].w;
+                MRCNN_REQUIRE(a1 <= b0 || b1 <= a0, MRCNN_ERR_INVALID, "paste_masks_source: the planes of images %d and %d overlap in out", a, b);
+            }
+        Stream st;
+        DevBuf td, tm, ts, to, tt, tb;
+        const size_t n = (size_t)batch * rows;
+        const float* d = stage_rows(detections, memspace, (long)n, 6, 6, td);
+        const float* m = stage_rows(masks, memspace, (long)n, (long)mask_size * mask_size, (long)mask_size * mask_size, tm);
+        float* ds = detections_src;
+        uint8_t* o = out;
+        if (memspace != MRCNN_DEVICE) {
+            ts.alloc(n * 6 * sizeof(float)); ds = ts.as<float>();
+            to.alloc((size_t)extent); o = to.as<uint8_t>();     // (same offsets as the caller's buffer: only the planes are copied back)
+        }
+        tt.alloc((size_t)batch * sizeof(ImageGeom));
+        tb.alloc(n * sizeof(int4));
+        HIP_CHECK(hipMemcpy(tt.p, geom.data(), (size_t)batch * sizeof(ImageGeom), hipMemcpyHostToDevice));
+        paste_masks_source_forward(st.s, d, m, static_cast<const ImageGeom*>(tt.p), batch, rows, mask_size, model_h, model_w, max_bytes, threshold, ds,
+                                   static_cast<int4*>(tb.p), o);
+        HIP_CHECK(hipStreamSynchronize(st.s));
+        if (memspace != MRCNN_DEVICE) {
+            HIP_CHECK(hipMemcpy(detections_src, ts.p, n * 6 * sizeof(float), hipMemcpyDeviceToHost));
+            for (int b = 0; b < batch; ++b) {
+                const ImageGeom& g = geom[(size_t)b];
+                HIP_CHECK(hipMemcpy(out + g.offset, to.as<uint8_t>() + g.offset, (size_t)rows * g.h * g.w, hipMemcpyDeviceToHost));
+            }
+        }
     });
 }
 

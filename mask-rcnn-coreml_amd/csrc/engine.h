@@ -183,7 +183,15 @@ struct Model {
     std::map<std::string, Tap> taps;    // name → (base, per-image elements, element type)
     uint8_t* d_rgb = nullptr;
     void* stem_in = nullptr;          // the stem's zero-padded NHWC4 / NHWC8 staging tensor (written by the pre-processing op = trunk_ops[0])
-    DevBuf fit_src;                   // predict_scalefit: the source images on the device
+    DevBuf fit_src;                   // predict_scalefit / predict_images: the source images on the device (back to back)
+    // predict_images: fit_src holds the images back to back and, behind them, one ImageGeom per image (offset into fit_src, size,
+    // letterbox geometry) at fit_table_off.  The table is uploaded from a small pinned buffer of the HANDLE (fit_pack), never from
+    // the caller's array, and both stay resident until the call returns: a range recovery recomputes the batch from them.
+    // fit_mixed is set for the duration of such a call only.
+    size_t fit_table_off = 0;
+    uint8_t* fit_pack = nullptr;      // hipHostMalloc: max_batch table entries
+    size_t fit_pack_bytes = 0;
+    bool fit_mixed = false;
     float *rpn_logits = nullptr, *rpn_probs = nullptr, *rpn_deltas = nullptr, *rois = nullptr;
     float *cls6 = nullptr, *detections = nullptr, *mask_out = nullptr;
     void *pooled = nullptr, *pooled_mask = nullptr;     // compute dtype
@@ -265,7 +273,10 @@ struct Model {
     // det / masks may be nullptr for internal passes (calibration, recovery measurement): nothing is copied out;
     // resident: the images already sit in d_rgb / fit_src (no input copy)
     void predict(const uint8_t* rgb, int batch, int h, int w, int memspace, float* det, float* masks, bool sync, bool fit = false, bool resident = false);
-    // d_rgb (or, with fit geometry, fit_src) → detections / mask_out, launches only
+    // One predict over `batch` images of DIFFERENT sizes (mrcnn_maskrcnn_predict_images): every image is staged into fit_src and
+    // letterboxed with its own geometry by the pre-processing kernel; synchronous, never replayed from a captured graph.
+    void predict_images(const mrcnn_image* images, int batch, int memspace, float* det, float* masks);
+    // d_rgb (or, with fit geometry, fit_src — and, while fit_mixed is set, the geometry table instead of `fit`) → detections / mask_out, launches only
     void enqueue_pipeline(hipStream_t s, int batch, const int* fit = nullptr);
     void drop_graphs();
     void read_tensor(const std::string& name, int image, float* dst, int64_t cap, int64_t* count);

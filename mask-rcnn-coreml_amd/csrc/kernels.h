@@ -79,9 +79,24 @@ void letterbox_forward(hipStream_t s, const uint8_t* src, int h, int w, uint8_t*
 // The same resampling fused with the mean subtraction, straight into the stem's padded staging tensor (B images of h×w).
 void preprocess_scalefit_forward(hipStream_t s, const uint8_t* src, int B, int h, int w, int H, int W, int nh, int nw, int py, int px, int pad,
                                  const float mean[3], void* out, int dtype);
+// One image of a mixed-size batch: where its bytes start in the buffer the kernel is given (the h×w×3 source pixels for the
+// pre-processing, the pasted planes for paste_masks_source_forward) and its letterbox geometry
+// (mrcnn_letterbox_geometry at the model's input size).  The table lives on the device, one entry per image.
+struct ImageGeom {
+    long long offset;
+    int h, w, nh, nw, py, px;
+};
+void preprocess_images_forward(hipStream_t s, const uint8_t* src, const ImageGeom* tab, int B, int H, int W, int pad, const float mean[3],
+                               void* out, int dtype);
 // Full-resolution binary instance masks from the 28×28 sigmoid masks (resize to box + threshold).
 void paste_masks_forward(hipStream_t s, const float* det, long det_stride, const float* masks, int n, int S, int H, int W,
                          float thr, uint8_t* out);
+// The same in every image's own frame, for a batch of images of different sizes: entry b (an ImageGeom, above) says where image
+// b's `rows` planes of h×w bytes start in `out` (bytes) and how it was letterboxed.  det (batch, rows, 6) in the letterboxed H×W frame → det_src in the
+// source frame (mrcnn_unletterbox_boxes' arithmetic) and the pasted planes; `boxes` is scratch of batch * rows int4,
+// max_bytes = the largest rows*h*w of the batch (sizes the grid).  Two launches in all.
+void paste_masks_source_forward(hipStream_t s, const float* det, const float* masks, const ImageGeom* tab, int batch, int rows, int S,
+                                int H, int W, long max_bytes, float thr, float* det_src, int4* boxes, uint8_t* out);
 
 // ================================================================================================
 // Convolution family + element-wise helpers (kernels_conv.hip)

@@ -307,6 +307,142 @@ void paste_masks_forward(hipStream_t s, const float* det, long det_stride, const
 }
 
 // ------------------------------------------------------------------------------------------------
+// Mask paste in each image's OWN pixels, for a batch of images of different sizes (mrcnn_paste_masks_source).
+//   k_unletterbox_boxes  one thread per detection row: the box mapped from the letterboxed frame to the source frame — the double
+//                        arithmetic of mrcnn_unletterbox_boxes, operation for operation — written to det_src, and its pixel box at
+//                        the source size (k_paste_masks' denorm_boxes; (0,0,0,0) for a row that pastes nothing) to a side table
+//   k_paste_masks_ragged the planes of image b — rows × h_b × w_b bytes from byte offset off_b — addressed as ONE flat byte stream:
+//                        h_b·w_b need not be a multiple of 4, so a plane starts wherever the last one ended.  A lane owns one
+//                        16-byte aligned chunk (one 16-B store), walks its 16 pixels across row / plane boundaries and recomputes
+//                        the row set-up only when the row changes; bytes before the first and after the last whole chunk of an
+//                        image go out one by one.  Nothing outside [off_b, off_b + rows·h_b·w_b) is written.
+// Pure write stream (Σ rows·h·w bytes); the 3 KB masks and the 16-B box entries come through L1.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_unletterbox_boxes(const float* __restrict__ det, const ImageGeom* __restrict__ tab, int rows, int total,
+                                                           int H, int W, float* __restrict__ det_src, int4* __restrict__ boxes)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const ImageGeom im = tab[i / rows];
+    const float* d = det + (size_t)i * 6;
+    float r[6] = {d[0], d[1], d[2], d[3], d[4], d[5]};
+    if (!(r[0] == 0.f && r[1] == 0.f && r[2] == 0.f && r[3] == 0.f)) {
+        const int h = im.h, w = im.w;
+        const double sy = (double)h / im.nh, sx = (double)w / im.nw, hy = h > 1 ? h - 1 : 1, wx = w > 1 ? w - 1 : 1;
+        const double y1 = ((double)r[0] * (H - 1) - im.py) * sy, x1 = ((double)r[1] * (W - 1) - im.px) * sx;
+        const double y2 = ((double)r[2] * (H - 1) + 1.0 - im.py) * sy, x2 = ((double)r[3] * (W - 1) + 1.0 - im.px) * sx;
+        auto clip = [](double v) { return v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v); };
+        r[0] = (float)clip(y1 / hy); r[1] = (float)clip(x1 / wx); r[2] = (float)clip((y2 - 1.0) / hy); r[3] = (float)clip((x2 - 1.0) / wx);
+    }
+    float* o = det_src + (size_t)i * 6;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) o[k] = r[k];
+    // denorm_boxes at the source size, as k_paste_masks computes it
+    const int by1 = (int)rint((double)r[0] * (double)(im.h - 1));
+    const int bx1 = (int)rint((double)r[1] * (double)(im.w - 1));
+    const int by2 = (int)rint((double)r[2] * (double)(im.h - 1) + 1.0);
+    const int bx2 = (int)rint((double)r[3] * (double)(im.w - 1) + 1.0);
+    const bool empty = by2 - by1 <= 0 || bx2 - bx1 <= 0 || !(r[5] > 0.0f);
+    boxes[i] = empty ? make_int4(0, 0, 0, 0) : make_int4(by1, bx1, by2, bx2);
+}
+
+// the pixels of one row of one instance plane: what k_paste_masks derives from (instance, y) before its x loop
+struct PasteRow {
+    const float *ra, *rb;      // the two mask rows the bilinear sample mixes
+    float fy, sx_scale;
+    int x1, x2;                // columns outside [x1, x2) are 0; x1 = x2 = 0: nothing on this row
+};
+__device__ __forceinline__ PasteRow paste_row(const int4* __restrict__ boxes, const float* __restrict__ masks, int S, int inst, int y)
+{
+    PasteRow r;
+    const int4 bx = boxes[inst];           // (y1, x1, y2, x2)
+    r.x1 = r.x2 = 0; r.ra = r.rb = masks; r.fy = 0.f; r.sx_scale = 0.f;
+    if (y >= bx.x && y < bx.z) {           // (an empty box is (0,0,0,0): no y passes)
+        const float* m = masks + (size_t)inst * S * S;
+        float sy = ((float)(y - bx.x) + 0.5f) * ((float)S / (float)(bx.z - bx.x)) - 0.5f;
+        sy = fminf(fmaxf(sy, 0.0f), (float)(S - 1));
+        const int ya = (int)floorf(sy), yb = min(ya + 1, S - 1);
+        r.fy = sy - (float)ya;
+        r.ra = m + ya * S; r.rb = m + yb * S;
+        r.sx_scale = (float)S / (float)(bx.w - bx.y);
+        r.x1 = bx.y; r.x2 = bx.w;
+    }
+    return r;
+}
+__device__ __forceinline__ uint32_t paste_pixel(const PasteRow& r, int S, int x, float thr)
+{
+    if (x < r.x1 || x >= r.x2) return 0u;
+    float sx = ((float)(x - r.x1) + 0.5f) * r.sx_scale - 0.5f;
+    sx = fminf(fmaxf(sx, 0.0f), (float)(S - 1));
+    const int xa = (int)floorf(sx), xc = min(xa + 1, S - 1);
+    const float fx = sx - (float)xa;
+    const float a = r.ra[xa], b = r.ra[xc], c = r.rb[xa], dd = r.rb[xc];
+    const float top = a + (b - a) * fx;
+    const float bot = c + (dd - c) * fx;
+    const float v = top + (bot - top) * r.fy;
+    return v >= thr ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void k_paste_masks_ragged(const ImageGeom* __restrict__ tab, const int4* __restrict__ boxes,
+                                                            const float* __restrict__ masks, int rows, int S, float thr, uint8_t* __restrict__ out)
+{
+    const int b = blockIdx.y;
+    const ImageGeom im = tab[b];
+    const int h = im.h, w = im.w;
+    const long plane = (long)h * w, len = plane * rows;
+    uint8_t* const o = out + im.offset;
+    const int4* const bx = boxes + (size_t)b * rows;
+    const float* const m = masks + (size_t)b * rows * S * S;
+    // [0, head) single bytes | whole 16-byte aligned chunks | [head + 16 * chunks, len) single bytes
+    const long mis = (long)(reinterpret_cast<uintptr_t>(o) & 15);
+    const long head = mis ? (16 - mis < len ? 16 - mis : len) : 0;
+    const long chunks = (len - head) >> 4;
+    for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < chunks; c += (long)gridDim.x * 256) {
+        const long p0 = head + (c << 4);
+        int inst = (int)(p0 / plane);
+        const long rem = p0 - (long)inst * plane;
+        int y = (int)(rem / w), x = (int)(rem - (long)y * w);
+        PasteRow r = paste_row(bx, m, S, inst, y);
+        uint32_t q[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            q[k >> 2] |= paste_pixel(r, S, x, thr) << (8 * (k & 3));
+            if (++x == w && k < 15) {                 // next row, possibly of the next plane (p0 + 16 <= len: inst stays < rows)
+                x = 0;
+                if (++y == h) { y = 0; ++inst; }
+                r = paste_row(bx, m, S, inst, y);
+            }
+        }
+        *reinterpret_cast<uint4*>(o + p0) = make_uint4(q[0], q[1], q[2], q[3]);
+    }
+    if (blockIdx.x == 0) {
+        const long tail0 = head + (chunks << 4);
+        const long loose = head + (len - tail0);      // < 32
+        if ((long)threadIdx.x < loose) {
+            const long p = (long)threadIdx.x < head ? (long)threadIdx.x : tail0 + ((long)threadIdx.x - head);
+            const int inst = (int)(p / plane);
+            const long rem = p - (long)inst * plane;
+            const int y = (int)(rem / w), x = (int)(rem - (long)y * w);
+            const PasteRow r = paste_row(bx, m, S, inst, y);
+            o[p] = (uint8_t)paste_pixel(r, S, x, thr);
+        }
+    }
+}
+
+void paste_masks_source_forward(hipStream_t s, const float* det, const float* masks, const ImageGeom* tab, int batch, int rows, int S,
+                                int H, int W, long max_bytes, float thr, float* det_src, int4* boxes, uint8_t* out)
+{
+    if (batch <= 0 || rows <= 0) return;
+    const int total = batch * rows;
+    hipLaunchKernelGGL(k_unletterbox_boxes, dim3((total + 255) / 256), dim3(256), 0, s, det, tab, rows, total, H, W, det_src, boxes);
+    HIP_CHECK(hipGetLastError());
+    const long blocks = (max_bytes / 16 + 255) / 256;
+    const int gx = (int)(blocks < 1 ? 1 : (blocks < 4096 ? blocks : 4096));
+    hipLaunchKernelGGL(k_paste_masks_ragged, dim3(gx, batch), dim3(256), 0, s, tab, boxes, masks, rows, S, thr, out);
+    HIP_CHECK(hipGetLastError());
+}
+
+// ------------------------------------------------------------------------------------------------
 // Letterbox: the host's `.scaleFit` step (VNCoreMLRequest.imageCropAndScaleOption,
 // EvaluateCommand.swift:157, ViewController.swift:45) on the GPU: aspect-preserving bilinear resize
 // (half-pixel centres, edge clamp, round-half-up to 8 bit) centred in an H×W canvas, black borders.
@@ -391,6 +527,53 @@ void preprocess_scalefit_forward(hipStream_t s, const uint8_t* src, int B, int h
         hipLaunchKernelGGL(k_preprocess_scalefit<_Float16>, dim3(grid), dim3(256), 0, s, src, B, h, w, H, W, nh, nw, py, px, pad, mean[0], mean[1], mean[2], out);
     else
         hipLaunchKernelGGL(k_preprocess_scalefit<float>, dim3(grid), dim3(256), 0, s, src, B, h, w, H, W, nh, nw, py, px, pad, mean[0], mean[1], mean[2], out);
+    HIP_CHECK(hipGetLastError());
+}
+
+// The same for a batch of images of DIFFERENT sizes (mrcnn_maskrcnn_predict_images): image b = blockIdx.y reads its own geometry
+// from a descriptor table on the device and its pixels from `src + offset`; every pixel is letterbox_pixel's, so each image's
+// slice of the stem input holds the bits k_preprocess_scalefit writes for that image alone.  One launch for the whole batch.
+template <typename T>
+__global__ __launch_bounds__(256) void k_preprocess_images(const uint8_t* __restrict__ src, const ImageGeom* __restrict__ tab, int H, int W, int pad,
+                                                           float mr, float mg, float mb, void* __restrict__ out)
+{
+    const int Hp = H + 2 * pad, Wp = W + 2 * pad;
+    const int per = Hp * Wp;
+    const ImageGeom im = tab[blockIdx.y];
+    const uint8_t* const sp = src + im.offset;
+    const float ry = (float)im.h / (float)im.nh, rx = (float)im.w / (float)im.nw;
+    const long base = (long)blockIdx.y * per;
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < per; e += gridDim.x * 256) {
+        const int yp = e / Wp;
+        const int X = e - yp * Wp - pad, Y = yp - pad;
+        float r = 0.f, g = 0.f, bl = 0.f;
+        if ((unsigned)Y < (unsigned)H && (unsigned)X < (unsigned)W) {
+            uint8_t v[3];
+            letterbox_pixel(sp, im.h, im.w, im.nh, im.nw, ry, rx, Y - im.py, X - im.px, v);
+            r = (float)v[0] - mr; g = (float)v[1] - mg; bl = (float)v[2] - mb;
+        }
+        if constexpr (sizeof(T) == 4) {
+            reinterpret_cast<float4*>(out)[base + e] = make_float4(r, g, bl, 0.f);
+        } else {
+            typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+            h8 hv;
+            hv[0] = (_Float16)r; hv[1] = (_Float16)g; hv[2] = (_Float16)bl;
+            hv[3] = hv[4] = hv[5] = hv[6] = hv[7] = (_Float16)0.f;
+            reinterpret_cast<h8*>(out)[base + e] = hv;
+        }
+    }
+}
+
+void preprocess_images_forward(hipStream_t s, const uint8_t* src, const ImageGeom* tab, int B, int H, int W, int pad, const float mean[3],
+                               void* out, int dtype)
+{
+    const long per = (long)(H + 2 * pad) * (W + 2 * pad);
+    const long want = (per + 255) / 256, cap = 8192 / B > 0 ? 8192 / B : 1;
+    const int gx = (int)(want < cap ? want : cap);
+    if (dtype == MRCNN_F16)
+        hipLaunchKernelGGL(k_preprocess_images<_Float16>, dim3(gx, B), dim3(256), 0, s, src, tab, H, W, pad, mean[0], mean[1], mean[2], out);
+    else
+        hipLaunchKernelGGL(k_preprocess_images<float>, dim3(gx, B), dim3(256), 0, s, src, tab, H, W, pad, mean[0], mean[1], mean[2], out);
     HIP_CHECK(hipGetLastError());
 }
 

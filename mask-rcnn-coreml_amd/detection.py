@@ -74,3 +74,27 @@ def paste_masks(detections: np.ndarray, masks: np.ndarray, image_h: int, image_w
     _lib.check(_lib.lib().mrcnn_paste_masks(det.ctypes.data, det.shape[1], m.ctypes.data, n, m.shape[1], image_h, image_w,
                                             C.c_float(threshold), _lib.HOST, out.ctypes.data))
     return out
+
+
+def paste_masks_source(detections: np.ndarray, masks: np.ndarray, sizes, model_h: int, model_w: int, threshold: float = 0.5):
+    """The way back from ``MaskRCNN.predict_images``: detections (B,rows,6) / masks (B,rows,S,S) of a batch of images of sizes
+    ``sizes`` = [(h_b, w_b)] → (det_src, [ (rows, h_b, w_b) uint8 per image ]).  det_src holds the boxes normalized in each SOURCE
+    image (``mrcnn_unletterbox_boxes``' mapping, done on the GPU), the masks are pasted in each image's own pixels — any width —
+    by one launch over the ragged buffer (``mrcnn_paste_masks_source``)."""
+    det = np.ascontiguousarray(detections, dtype=np.float32)
+    m = np.ascontiguousarray(masks, dtype=np.float32)
+    B, rows = det.shape[0], det.shape[1]
+    if len(sizes) != B or m.shape[0] != B or m.shape[1] != rows or det.shape[2] != 6:
+        raise ValueError("paste_masks_source: detections (B,rows,6), masks (B,rows,S,S) and B sizes expected")
+    hs = np.array([int(s[0]) for s in sizes], dtype=np.int32)
+    ws = np.array([int(s[1]) for s in sizes], dtype=np.int32)
+    nbytes = rows * hs.astype(np.int64) * ws.astype(np.int64)
+    padded = (nbytes + 15) // 16 * 16                      # every image's planes start on a 16-byte boundary
+    offs = np.concatenate(([0], np.cumsum(padded)[:-1])).astype(np.int64) if B else np.zeros(0, np.int64)
+    out = np.empty(int(padded.sum()), dtype=np.uint8)
+    det_src = np.empty_like(det)
+    _lib.check(_lib.lib().mrcnn_paste_masks_source(det.ctypes.data, m.ctypes.data, B, rows, m.shape[2], hs.ctypes.data, ws.ctypes.data,
+                                                   model_h, model_w, C.c_float(threshold), _lib.HOST, det_src.ctypes.data,
+                                                   out.ctypes.data, offs.ctypes.data))
+    planes = [out[int(offs[b]):int(offs[b] + nbytes[b])].reshape(rows, int(hs[b]), int(ws[b])) for b in range(B)]
+    return det_src, planes

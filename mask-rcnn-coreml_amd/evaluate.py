@@ -173,8 +173,12 @@ def mask_flip_causes(det_a: np.ndarray, det_b: np.ndarray, pooled_a: np.ndarray,
 
 
 def evaluate(model: MaskRCNN, images: Iterable[Tuple[int, np.ndarray]], dataset_id: str = "coco",
-             limit: Optional[int] = 5, verbose: bool = True, calibrate: bool = False):
+             limit: Optional[int] = 5, verbose: bool = True, calibrate: bool = False, batch: int = 1):
     """images: (image_id, HxWx3 uint8).  Returns (results.proto bytes, [seconds per image], [PBResult]).
+    batch: 1 — the reference's loop, one image per call (letterbox, then predict).  k > 1 (at most the model's max_batch): the
+    images, after the sort and the limit, go through MaskRCNN.predict_images k at a time whatever their sizes, the last group
+    smaller; the seconds reported for an image are then its GROUP's wall time divided by the group's size.  The results.proto
+    bytes do not depend on `batch`.
     calibrate: split modes only — one calibration predict on the first image before the timed loop (model set-up, like the load
     the reference keeps outside its timing, EvaluateCommand.swift:146-156): mrcnn_model_calibrate_split."""
     items = sorted(images, key=lambda it: it[0])           # sortById:true
@@ -185,6 +189,20 @@ def evaluate(model: MaskRCNN, images: Iterable[Tuple[int, np.ndarray]], dataset_
         model.calibrate_split(letterbox(items[0][1], H, W)[None])
     out: List[PBResult] = []
     secs: List[float] = []
+    if batch != 1:
+        if batch < 1 or batch > model.max_batch:
+            raise ValueError(f"batch {batch} outside 1..{model.max_batch} (the model's max_batch)")
+        for g0 in range(0, len(items), batch):
+            group = items[g0:g0 + batch]
+            t0 = time.perf_counter()
+            det, _ = model.predict_images([img for _, img in group])
+            t1 = time.perf_counter()
+            for b, (image_id, img) in enumerate(group):
+                out.append(PBResult(dataset_id, str(image_id), int(img.shape[1]), int(img.shape[0]), detections_to_pb(det[b])))
+                secs.append((t1 - t0) / len(group))
+                if verbose:
+                    print((t1 - t0) / len(group))
+        return encode_results(out), secs, out
     for image_id, img in items:
         t0 = time.perf_counter()
         lb = letterbox(img, H, W)

@@ -116,6 +116,40 @@ class MaskRCNN(_Model):
         _lib.check(_lib.lib().mrcnn_maskrcnn_predict_scalefit(self._h, imgs.ctypes.data, B, h, w, _lib.HOST, det.ctypes.data, mask.ctypes.data))
         return det, mask
 
+    def predict_images(self, images):
+        """One predict over images of DIFFERENT sizes (mrcnn_maskrcnn_predict_images): a list of (h_i, w_i, 3) uint8 numpy arrays —
+        or of uint8 CUDA tensors, in which case the results stay on the device.  Every image is letterboxed with its own geometry
+        inside the one pre-processing launch; row b equals predict_scalefit(images[b][None]).  Returns (det, mask) like
+        predict_scalefit: boxes normalized in the letterboxed frame (detection.paste_masks_source maps them back)."""
+        images = list(images)
+        B = len(images)
+        table = (_lib.Image * max(1, B))()
+        on_host = B == 0 or isinstance(images[0], np.ndarray)
+        keep = []
+        for b, im in enumerate(images):
+            if on_host:
+                im = np.ascontiguousarray(im, dtype=np.uint8)
+                ptr = im.ctypes.data
+            else:
+                import torch
+                assert im.is_cuda and im.dtype == torch.uint8 and im.is_contiguous()
+                ptr = im.data_ptr()
+            if im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError(f"image {b} has shape {tuple(im.shape)}, expected (h, w, 3)")
+            keep.append(im)
+            table[b].rgb, table[b].height, table[b].width = ptr, int(im.shape[0]), int(im.shape[1])
+        shape_d = (B, self.max_detections, 6)
+        shape_m = (B, self.max_detections, self.mask_size, self.mask_size)
+        if on_host:
+            det, mask = np.empty(shape_d, dtype=np.float32), np.empty(shape_m, dtype=np.float32)
+            _lib.check(_lib.lib().mrcnn_maskrcnn_predict_images(self._h, table, B, _lib.HOST, det.ctypes.data, mask.ctypes.data))
+        else:
+            import torch
+            det = torch.empty(shape_d, dtype=torch.float32, device=images[0].device)
+            mask = torch.empty(shape_m, dtype=torch.float32, device=images[0].device)
+            _lib.check(_lib.lib().mrcnn_maskrcnn_predict_images(self._h, table, B, _lib.DEVICE, det.data_ptr(), mask.data_ptr()))
+        return det, mask
+
     def predict_into(self, images, det, mask, sync: bool = True):
         """Device tensors in, pre-allocated device tensors out (bench loop: no allocation, optional no sync)."""
         B, H, W, _ = images.shape
