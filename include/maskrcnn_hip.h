@@ -450,6 +450,24 @@ MRCNN_API int mrcnn_paste_masks(const float* detections, int64_t det_stride, con
 MRCNN_API int mrcnn_paste_masks_source(const float* detections, const float* masks, int batch, int rows, int mask_size,
                                        const int32_t* heights, const int32_t* widths, int model_h, int model_w, float threshold,
                                        int memspace, float* detections_src, uint8_t* out, const int64_t* out_offsets);
+/* COCO run-length encoding (RLE) of the masks mrcnn_paste_masks_source would paste, without pasting them: the same arguments up to
+ * detections_src, and for image b, row i (k = b*rows + i) the h_b x w_b plane of that call encoded as COCO does — pixels in
+ * column-major order (p = x*h + y), counts[0] = the number of leading zeros (0 when pixel (0,0) is set), then alternating lengths of
+ * runs of ones and zeros, summing to h*w; a row that pastes nothing is the single run [h*w].
+ *   counts + run_offsets[k] .. counts + run_offsets[k+1]   the run lengths of row k (all rows back to back)
+ *   run_offsets (batch*rows + 1), areas (batch*rows: the number of set pixels), bboxes_xywh (batch*rows*4: the tight box x, y, w, h of
+ *   the set pixels, 0,0,0,0 for an empty mask) and detections_src are ALWAYS written; areas / bboxes_xywh may be NULL.
+ * If run_offsets[batch*rows] > capacity the call returns MRCNN_ERR_SHAPE, the message names the capacity needed and counts is not
+ * written (capacity = 0 with counts = NULL is the size query).  memspace holds for detections, masks, detections_src, counts,
+ * run_offsets, areas and bboxes_xywh; heights and widths are host arrays.  With MRCNN_HOST only the used part of counts is copied. */
+MRCNN_API int mrcnn_masks_rle_source(const float* detections, const float* masks, int batch, int rows, int mask_size,
+                                     const int32_t* heights, const int32_t* widths, int model_h, int model_w, float threshold,
+                                     int memspace, float* detections_src, uint32_t* counts, int64_t capacity, int64_t* run_offsets,
+                                     uint32_t* areas, int32_t* bboxes_xywh);
+/* Host only, no GPU: COCO's compressed string of one RLE (pycocotools rleToString / rleFrString), not NUL-terminated.  *length / *n is
+ * always the size needed; with out / counts = NULL the call only measures, a buffer that is too small gives MRCNN_ERR_SHAPE. */
+MRCNN_API int mrcnn_rle_to_string(const uint32_t* counts, int64_t n, char* out, int64_t capacity, int64_t* length);
+MRCNN_API int mrcnn_rle_from_string(const char* s, int64_t length, uint32_t* counts, int64_t capacity, int64_t* n);
 /* 28×28 mask → 8-bit: UInt8(255 - v/2*255) (Detection.swift:83-85). */
 MRCNN_API int mrcnn_mask_to_u8(const float* mask, int64_t n, uint8_t* out);
 /* The same on Double input — the type Core ML hands maskFromFeatureValue (Detection.swift:77); for hosts that widen the fp32

@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "mrcnn_dist_all_gather_records_async", "mrcnn_dist_wait", "mrcnn_dist_recovered", "mrcnn_dist_rccl_shared", "mrcnn_dist_plan", "mrcnn_dist_simulate_host",
     "mrcnn_maskrcnn_predict_scalefit", "mrcnn_unletterbox_boxes",
     "mrcnn_maskrcnn_predict_images", "mrcnn_paste_masks_source",
+    "mrcnn_masks_rle_source", "mrcnn_rle_to_string", "mrcnn_rle_from_string",
 ]
 # declared in include/maskrcnn_hip_test.h (test / measurement entry points of the same library)
 TEST_SYMBOLS = [
@@ -127,6 +128,9 @@ def lib():
     L.mrcnn_unletterbox_boxes.argtypes = [vp, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]
     L.mrcnn_maskrcnn_predict_images.argtypes = [vp, C.POINTER(Image), C.c_int, C.c_int, vp, vp]
     L.mrcnn_paste_masks_source.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp]
+    L.mrcnn_masks_rle_source.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, C.c_int64, vp, vp, vp]
+    L.mrcnn_rle_to_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
+    L.mrcnn_rle_from_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_maskrcnn_predict_async.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.mrcnn_maskrcnn_submit.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
     L.mrcnn_maskrcnn_collect.argtypes = [vp, vp, vp, C.POINTER(C.c_int)]

@@ -97,6 +97,18 @@ void paste_masks_forward(hipStream_t s, const float* det, long det_stride, const
 // max_bytes = the largest rows*h*w of the batch (sizes the grid).  Two launches in all.
 void paste_masks_source_forward(hipStream_t s, const float* det, const float* masks, const ImageGeom* tab, int batch, int rows, int S,
                                 int H, int W, long max_bytes, float thr, float* det_src, int4* boxes, uint8_t* out);
+// COCO run-length encoding of the same planes without pasting them (mrcnn_masks_rle_source), in two steps with the capacity check
+// between them.  _count: det_src and `boxes` as above, then per instance its number of runs, area and tight box (areas / bboxes may be
+// nullptr) and run_offsets (batch * rows + 1 entries; the last = the runs of the whole batch).  segs (batch * rows * RLE_SEGS) and
+// nruns (batch * rows) are scratch the second step reads.  _write: the run lengths of instance k at counts[run_offsets[k] ..
+// run_offsets[k + 1]); counts must hold run_offsets[batch * rows] entries.
+constexpr int RLE_SEGS = 16;                 // an instance's positions are walked as 16 contiguous segments, one per wave of its block
+struct RleSeg { uint32_t count, last; };     // one segment: its transitions and the position of the last one
+void masks_rle_count_forward(hipStream_t s, const float* det, const float* masks, const ImageGeom* tab, int batch, int rows, int S, int H, int W,
+                             float thr, float* det_src, int4* boxes, RleSeg* segs, uint32_t* nruns, long long* run_offsets, uint32_t* areas,
+                             int32_t* bboxes);
+void masks_rle_write_forward(hipStream_t s, const float* masks, const ImageGeom* tab, int batch, int rows, int S, float thr, const int4* boxes,
+                             const RleSeg* segs, const long long* run_offsets, uint32_t* counts);
 
 // ================================================================================================
 // Convolution family + element-wise helpers (kernels_conv.hip)

@@ -346,6 +346,27 @@ __global__ __launch_bounds__(256) void k_unletterbox_boxes(const float* __restri
     boxes[i] = empty ? make_int4(0, 0, 0, 0) : make_int4(by1, bx1, by2, bx2);
 }
 
+// One axis of the paste's bilinear sample (the set-up k_paste_masks does per y and per x): pixel i of a box that starts at `lo`,
+// scale = S / the box's extent → the two mask cells it mixes and the weight of the second.  Shared by the paste and the RLE kernels:
+// the same float operations in the same order (-ffp-contract=off), so both see the same bits.
+struct PasteTap { int a, b; float f; };
+__device__ __forceinline__ PasteTap paste_tap(int i, int lo, float scale, int S)
+{
+    float s = ((float)(i - lo) + 0.5f) * scale - 0.5f;
+    s = fminf(fmaxf(s, 0.0f), (float)(S - 1));
+    PasteTap t;
+    t.a = (int)floorf(s); t.b = min(t.a + 1, S - 1);
+    t.f = s - (float)t.a;
+    return t;
+}
+// the sample itself: a, b = the upper mask row at the two columns, c, dd = the lower one
+__device__ __forceinline__ float paste_lerp(float a, float b, float c, float dd, float fx, float fy)
+{
+    const float top = a + (b - a) * fx;
+    const float bot = c + (dd - c) * fx;
+    return top + (bot - top) * fy;
+}
+
 // the pixels of one row of one instance plane: what k_paste_masks derives from (instance, y) before its x loop
 struct PasteRow {
     const float *ra, *rb;      // the two mask rows the bilinear sample mixes
@@ -359,11 +380,9 @@ __device__ __forceinline__ PasteRow paste_row(const int4* __restrict__ boxes, co
     r.x1 = r.x2 = 0; r.ra = r.rb = masks; r.fy = 0.f; r.sx_scale = 0.f;
     if (y >= bx.x && y < bx.z) {           // (an empty box is (0,0,0,0): no y passes)
         const float* m = masks + (size_t)inst * S * S;
-        float sy = ((float)(y - bx.x) + 0.5f) * ((float)S / (float)(bx.z - bx.x)) - 0.5f;
-        sy = fminf(fmaxf(sy, 0.0f), (float)(S - 1));
-        const int ya = (int)floorf(sy), yb = min(ya + 1, S - 1);
-        r.fy = sy - (float)ya;
-        r.ra = m + ya * S; r.rb = m + yb * S;
+        const PasteTap ty = paste_tap(y, bx.x, (float)S / (float)(bx.z - bx.x), S);
+        r.fy = ty.f;
+        r.ra = m + ty.a * S; r.rb = m + ty.b * S;
         r.sx_scale = (float)S / (float)(bx.w - bx.y);
         r.x1 = bx.y; r.x2 = bx.w;
     }
@@ -372,14 +391,8 @@ __device__ __forceinline__ PasteRow paste_row(const int4* __restrict__ boxes, co
 __device__ __forceinline__ uint32_t paste_pixel(const PasteRow& r, int S, int x, float thr)
 {
     if (x < r.x1 || x >= r.x2) return 0u;
-    float sx = ((float)(x - r.x1) + 0.5f) * r.sx_scale - 0.5f;
-    sx = fminf(fmaxf(sx, 0.0f), (float)(S - 1));
-    const int xa = (int)floorf(sx), xc = min(xa + 1, S - 1);
-    const float fx = sx - (float)xa;
-    const float a = r.ra[xa], b = r.ra[xc], c = r.rb[xa], dd = r.rb[xc];
-    const float top = a + (b - a) * fx;
-    const float bot = c + (dd - c) * fx;
-    const float v = top + (bot - top) * r.fy;
+    const PasteTap tx = paste_tap(x, r.x1, r.sx_scale, S);
+    const float v = paste_lerp(r.ra[tx.a], r.ra[tx.b], r.rb[tx.a], r.rb[tx.b], tx.f, r.fy);
     return v >= thr ? 1u : 0u;
 }
 
@@ -439,6 +452,190 @@ void paste_masks_source_forward(hipStream_t s, const float* det, const float* ma
     const long blocks = (max_bytes / 16 + 255) / 256;
     const int gx = (int)(blocks < 1 ? 1 : (blocks < 4096 ? blocks : 4096));
     hipLaunchKernelGGL(k_paste_masks_ragged, dim3(gx, batch), dim3(256), 0, s, tab, boxes, masks, rows, S, thr, out);
+    HIP_CHECK(hipGetLastError());
+}
+
+// ------------------------------------------------------------------------------------------------
+// COCO run-length encoding of the planes k_paste_masks_ragged would write, without writing them (mrcnn_masks_rle_source).
+// COCO walks a plane column by column: position p = x·h + y.  A TRANSITION is a p with bit(p) != bit(p - 1), bit(-1) = 0; with the
+// transitions p_1 < … < p_T of a plane its counts are p_1, p_2 - p_1, …, h·w - p_T: T + 1 runs, [h·w] for an empty plane, a leading 0
+// when pixel (0,0) is set.  Only positions inside the box, and the one right behind each box column, can be transitions.
+//   One block of 16 waves per instance.  The box's columns are cut into chunks of 63 consecutive positions; a wave looks at one chunk
+//   at a time: lane l evaluates position p0 + l (lane 0 only supplies its neighbour's predecessor — the pixel above, or the last pixel
+//   of the column before: positions are linear, so a run that leaves a column at the bottom edge and enters the next at the top is ONE
+//   run), `ballot ^ (ballot << 1)` marks the transitions.  The chunks of an instance, in position order, are dealt to the 16 waves as
+//   16 contiguous SEGMENTS, so a wave needs nothing from the others while it walks.
+//   k_rle_count    per segment: number of transitions and the position of the last one; per instance: runs, area, tight box
+//   k_rle_offsets  exclusive scan of the runs per instance → run_offsets (one block; batch·rows is a few hundred)
+//   k_rle_write    the same walk; a wave starts at its instance's offset + the transitions of the segments before its own, with the
+//                  last transition before its segment as predecessor, and stores p_k - p_(k-1) per transition; the last wave adds h·w - p_T.
+// Every bit is paste_pixel's: paste_tap / paste_lerp with the same operands.  No run count is assumed anywhere.
+// ------------------------------------------------------------------------------------------------
+static_assert(sizeof(RleSeg) == 8, "RleSeg is two uint32");
+
+__device__ __forceinline__ bool rle_bit(const int4 bx, const float* __restrict__ m, int S, int h, int x, int y, float thr)
+{
+    if (y < 0) { --x; y = h - 1; } else if (y >= h) { ++x; y = 0; }        // the position before a column's first / behind its last pixel
+    if (x < bx.y || x >= bx.w || y < bx.x || y >= bx.z) return false;
+    const PasteTap ty = paste_tap(y, bx.x, (float)S / (float)(bx.z - bx.x), S);
+    const PasteTap tx = paste_tap(x, bx.y, (float)S / (float)(bx.w - bx.y), S);
+    const float *ra = m + ty.a * S, *rb = m + ty.b * S;
+    return paste_lerp(ra[tx.a], ra[tx.b], rb[tx.a], rb[tx.b], tx.f, ty.f) >= thr;
+}
+
+// One chunk: lane l stands for position p0 + l (p0 may be "-1" for the chunk that starts the plane: lane 0 is never a candidate).
+struct RleChunk {
+    unsigned long long set;     // candidate lanes whose pixel is 1 (every pixel of the box is a candidate of exactly one chunk)
+    unsigned long long trans;   // candidate lanes that are transitions
+    uint32_t p0;
+    int x, y0;                  // lane l: column x, row y0 + l
+};
+struct RleWalk {
+    int4 bx; const float* m; int S, h, w, nchunk; long items; float thr;
+};
+__device__ __forceinline__ RleWalk rle_walk(const ImageGeom* __restrict__ tab, const int4* __restrict__ boxes, const float* __restrict__ masks,
+                                            int rows, int S, float thr, int inst)
+{
+    RleWalk k;
+    const ImageGeom im = tab[inst / rows];
+    k.bx = boxes[inst]; k.m = masks + (size_t)inst * S * S; k.S = S; k.h = im.h; k.w = im.w; k.thr = thr;
+    k.nchunk = (k.bx.z - k.bx.x + 1 + 62) / 63;                            // candidates per column: rows y1 .. y2 (y2 = the position behind)
+    k.items = (long)(k.bx.w - k.bx.y) * k.nchunk;                          // (an empty box is (0,0,0,0): no items)
+    return k;
+}
+__device__ __forceinline__ RleChunk rle_chunk(const RleWalk& k, long item, int lane)
+{
+    RleChunk c;
+    c.x = k.bx.y + (int)(item / k.nchunk);
+    c.y0 = k.bx.x - 1 + 63 * (int)(item % k.nchunk);
+    const int y = c.y0 + lane;
+    // the last candidate of this column: the position behind the box's last row — unless that position is the first candidate of the
+    // next column (a box of the plane's full height) or lies behind the plane's end (no transition there: the last run just ends)
+    int hi = k.bx.z;
+    if (k.bx.z == k.h && ((k.bx.x == 0 && c.x < k.bx.w - 1) || c.x == k.w - 1)) hi = k.h - 1;
+    const bool valid = y <= hi;
+    const bool cur = valid && rle_bit(k.bx, k.m, k.S, k.h, c.x, y, k.thr);
+    const unsigned long long bal = __ballot(cur);
+    const unsigned long long cand = __ballot(valid && lane >= 1);
+    c.set = bal & cand;
+    c.trans = (bal ^ (bal << 1)) & cand;
+    c.p0 = (uint32_t)c.x * (uint32_t)k.h + (uint32_t)c.y0;
+    return c;
+}
+
+__global__ __launch_bounds__(1024) void k_rle_count(const ImageGeom* __restrict__ tab, const int4* __restrict__ boxes, const float* __restrict__ masks,
+                                                    int rows, int S, float thr, RleSeg* __restrict__ segs, uint32_t* __restrict__ nruns,
+                                                    uint32_t* __restrict__ areas, int32_t* __restrict__ bboxes)
+{
+    const int inst = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const RleWalk k = rle_walk(tab, boxes, masks, rows, S, thr, inst);
+    uint32_t count = 0, last = 0, area = 0;
+    int xmin = 0x7fffffff, ymin = 0x7fffffff, xmax = -1, ymax = -1;
+    for (long it = k.items * wave / RLE_SEGS, end = k.items * (wave + 1) / RLE_SEGS; it < end; ++it) {
+        const RleChunk c = rle_chunk(k, it, lane);
+        if (c.trans) { count += __popcll(c.trans); last = c.p0 + (63 - __clzll(c.trans)); }
+        if (c.set) {
+            area += __popcll(c.set);
+            xmin = min(xmin, c.x); xmax = max(xmax, c.x);
+            ymin = min(ymin, c.y0 + (__ffsll(c.set) - 1)); ymax = max(ymax, c.y0 + 63 - __clzll(c.set));
+        }
+    }
+    __shared__ uint32_t s_count[RLE_SEGS], s_area[RLE_SEGS];
+    __shared__ int s_box[RLE_SEGS][4];
+    if (lane == 0) {
+        segs[(size_t)inst * RLE_SEGS + wave] = RleSeg{count, last};
+        s_count[wave] = count; s_area[wave] = area;
+        s_box[wave][0] = xmin; s_box[wave][1] = ymin; s_box[wave][2] = xmax; s_box[wave][3] = ymax;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int s = 1; s < RLE_SEGS; ++s) {
+            count += s_count[s]; area += s_area[s];
+            xmin = min(xmin, s_box[s][0]); ymin = min(ymin, s_box[s][1]); xmax = max(xmax, s_box[s][2]); ymax = max(ymax, s_box[s][3]);
+        }
+        nruns[inst] = count + 1;
+        if (areas) areas[inst] = area;
+        if (bboxes) {
+            int* o = bboxes + (size_t)inst * 4;
+            const bool any = area > 0;
+            o[0] = any ? xmin : 0; o[1] = any ? ymin : 0; o[2] = any ? xmax - xmin + 1 : 0; o[3] = any ? ymax - ymin + 1 : 0;
+        }
+    }
+}
+
+// run_offsets[k] = Σ nruns[0 .. k), run_offsets[total] = the sum; one block of 1024 threads, 1024 instances per step
+__global__ __launch_bounds__(1024) void k_rle_offsets(const uint32_t* __restrict__ nruns, int total, long long* __restrict__ run_offsets)
+{
+    __shared__ long long buf[2][1024];
+    const int t = threadIdx.x;
+    long long carry = 0;
+    for (long base = 0; base < total; base += 1024) {                      // (long: total may be close to 2^31)
+        const long long mine = base + t < total ? (long long)nruns[base + t] : 0;
+        int cur = 0;
+        buf[0][t] = mine;
+        __syncthreads();
+        for (int d = 1; d < 1024; d <<= 1) {                               // inclusive scan, double-buffered
+            buf[cur ^ 1][t] = buf[cur][t] + (t >= d ? buf[cur][t - d] : 0);
+            cur ^= 1;
+            __syncthreads();
+        }
+        if (base + t < total) run_offsets[base + t] = carry + buf[cur][t] - mine;
+        carry += buf[cur][1023];
+        __syncthreads();                                                   // (buf is written again by the next step)
+    }
+    if (t == 0) run_offsets[total] = carry;
+}
+
+__global__ __launch_bounds__(1024) void k_rle_write(const ImageGeom* __restrict__ tab, const int4* __restrict__ boxes, const float* __restrict__ masks,
+                                                    int rows, int S, float thr, const RleSeg* __restrict__ segs,
+                                                    const long long* __restrict__ run_offsets, uint32_t* __restrict__ counts)
+{
+    const int inst = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const RleWalk k = rle_walk(tab, boxes, masks, rows, S, thr, inst);
+    long long off = run_offsets[inst];
+    const long long stop = run_offsets[inst + 1];                          // nothing of this instance is stored at or behind it
+    uint32_t prev = 0;                                                     // the transition before this wave's first; 0 = the plane's start
+    for (int s = 0; s < wave; ++s) {
+        const RleSeg g = segs[(size_t)inst * RLE_SEGS + s];
+        if (g.count) { off += g.count; prev = g.last; }
+    }
+    for (long it = k.items * wave / RLE_SEGS, end = k.items * (wave + 1) / RLE_SEGS; it < end; ++it) {
+        const RleChunk c = rle_chunk(k, it, lane);
+        if (!c.trans) continue;
+        if ((c.trans >> lane) & 1ull) {
+            const unsigned long long below = c.trans & ((1ull << lane) - 1ull);
+            const long long at = off + __popcll(below);
+            // the transition before mine: the nearest one below me in this chunk (lanes are consecutive positions), else `prev`
+            const uint32_t run = below ? (uint32_t)(lane - (63 - __clzll(below))) : c.p0 + (uint32_t)lane - prev;
+            if (at < stop) counts[at] = run;
+        }
+        off += __popcll(c.trans);
+        prev = c.p0 + (63 - __clzll(c.trans));
+    }
+    if (wave == RLE_SEGS - 1 && lane == 0 && off < stop) counts[off] = (uint32_t)k.h * (uint32_t)k.w - prev;
+}
+
+void masks_rle_count_forward(hipStream_t s, const float* det, const float* masks, const ImageGeom* tab, int batch, int rows, int S, int H, int W,
+                             float thr, float* det_src, int4* boxes, RleSeg* segs, uint32_t* nruns, long long* run_offsets, uint32_t* areas,
+                             int32_t* bboxes)
+{
+    const int total = batch * rows;
+    if (total > 0) {
+        hipLaunchKernelGGL(k_unletterbox_boxes, dim3((total + 255) / 256), dim3(256), 0, s, det, tab, rows, total, H, W, det_src, boxes);
+        HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_rle_count, dim3(total), dim3(64 * RLE_SEGS), 0, s, tab, boxes, masks, rows, S, thr, segs, nruns, areas, bboxes);
+        HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_rle_offsets, dim3(1), dim3(1024), 0, s, nruns, total, run_offsets);
+    HIP_CHECK(hipGetLastError());
+}
+
+void masks_rle_write_forward(hipStream_t s, const float* masks, const ImageGeom* tab, int batch, int rows, int S, float thr, const int4* boxes,
+                             const RleSeg* segs, const long long* run_offsets, uint32_t* counts)
+{
+    const int total = batch * rows;
+    if (total <= 0) return;
+    hipLaunchKernelGGL(k_rle_write, dim3(total), dim3(64 * RLE_SEGS), 0, s, tab, boxes, masks, rows, S, thr, segs, run_offsets, counts);
     HIP_CHECK(hipGetLastError());
 }
 

@@ -98,3 +98,60 @@ def paste_masks_source(detections: np.ndarray, masks: np.ndarray, sizes, model_h
                                                    out.ctypes.data, offs.ctypes.data))
     planes = [out[int(offs[b]):int(offs[b] + nbytes[b])].reshape(rows, int(hs[b]), int(ws[b])) for b in range(B)]
     return det_src, planes
+
+
+def masks_rle_source(detections, masks, sizes, model_h: int, model_w: int, threshold: float = 0.5):
+    """The masks ``paste_masks_source`` would paste, as COCO run-length encodings straight from the GPU — the planes never exist
+    (``mrcnn_masks_rle_source``).  Same arguments; returns (det_src, rles, areas, bboxes): ``rles[b][i] = {"size": [h_b, w_b],
+    "counts": uint32 array}`` (column-major runs, coco_results.rle_decode gives the plane back), areas (B, rows) the set pixels,
+    bboxes (B, rows, 4) their tight box x, y, w, h.  numpy in → numpy out.  torch CUDA tensors in → the device buffers are used in
+    place, det_src / areas / bboxes stay on the device (int32 tensors) and only the run offsets and the used part of the run
+    lengths come to the host.  A first attempt is sized from the image widths; if the batch needs more, one more call with the
+    capacity the library reported."""
+    on_host = isinstance(detections, np.ndarray)
+    if on_host:
+        det = np.ascontiguousarray(detections, dtype=np.float32)
+        m = np.ascontiguousarray(masks, dtype=np.float32)
+    else:
+        import torch
+        det, m = detections, masks
+        assert det.is_cuda and m.is_cuda and det.dtype == torch.float32 and m.dtype == torch.float32 and det.is_contiguous() and m.is_contiguous()
+    B, rows = int(det.shape[0]), int(det.shape[1])
+    if len(sizes) != B or m.shape[0] != B or m.shape[1] != rows or det.shape[2] != 6:
+        raise ValueError("masks_rle_source: detections (B,rows,6), masks (B,rows,S,S) and B sizes expected")
+    hs = np.array([int(s[0]) for s in sizes], dtype=np.int32)
+    ws = np.array([int(s[1]) for s in sizes], dtype=np.int32)
+    n = B * rows
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    if on_host:
+        det_src, areas, bboxes = np.empty_like(det), np.empty((B, rows), np.uint32), np.empty((B, rows, 4), np.int32)
+        ptr = lambda a: a.ctypes.data
+        new_counts = lambda k: np.empty(max(1, k), np.uint32)
+        offs_buf = offsets
+    else:
+        det_src = torch.empty_like(det)
+        areas = torch.empty((B, rows), dtype=torch.int32, device=det.device)
+        bboxes = torch.empty((B, rows, 4), dtype=torch.int32, device=det.device)
+        ptr = lambda a: a.data_ptr()
+        new_counts = lambda k: torch.empty(max(1, k), dtype=torch.int32, device=det.device)
+        offs_buf = torch.empty(n + 1, dtype=torch.int64, device=det.device)
+
+    def call(capacity):
+        counts = new_counts(capacity)
+        st = _lib.lib().mrcnn_masks_rle_source(ptr(det), ptr(m), B, rows, int(m.shape[2]), hs.ctypes.data, ws.ctypes.data, model_h, model_w,
+                                               C.c_float(threshold), _lib.HOST if on_host else _lib.DEVICE, ptr(det_src), ptr(counts), capacity,
+                                               ptr(offs_buf), ptr(areas), ptr(bboxes))
+        return st, counts
+    # a mask with one run of ones per column of its image has 2 w + 1 runs: enough for the masks a network draws, not for noise
+    capacity = int(rows * (2 * ws.astype(np.int64) + 2).sum())
+    st, counts = call(capacity)
+    if not on_host:
+        offsets[:] = offs_buf.cpu().numpy()
+    if st == 4 and int(offsets[n]) > capacity:                 # MRCNN_ERR_SHAPE with the offsets complete: the capacity was the reason
+        st, counts = call(int(offsets[n]))
+    _lib.check(st)
+    used = int(offsets[n])
+    host = counts[:used] if on_host else counts[:used].cpu().numpy().view(np.uint32)
+    rles = [[{"size": [int(hs[b]), int(ws[b])], "counts": host[int(offsets[b * rows + i]):int(offsets[b * rows + i + 1])]}
+             for i in range(rows)] for b in range(B)]
+    return det_src, rles, areas, bboxes

@@ -215,6 +215,44 @@ def evaluate(model: MaskRCNN, images: Iterable[Tuple[int, np.ndarray]], dataset_
     return encode_results(out), secs, out
 
 
+def evaluate_segm(model: MaskRCNN, images: Iterable[Tuple[int, np.ndarray]], dataset_id: str = "coco", limit: Optional[int] = 5,
+                  verbose: bool = True, batch: int = 1, threshold: float = 0.5, class_to_category=None, score_threshold: float = 0.0):
+    """``evaluate(..., batch=k)`` that also hands the masks on: returns (results.proto bytes, [seconds per image], [PBResult],
+    COCO results list).  The first three are evaluate's — the same bytes.  The fourth is what a COCO scorer reads
+    (coco_results.coco_results: image_id, category_id, bbox in source pixels, score, segmentation as a compressed RLE), one record
+    per detection row with score > score_threshold.  Per group of `batch` images everything stays on the device — the images go up
+    once, predict_images and detection.masks_rle_source run on device tensors — and only the detection rows and the run lengths come
+    back: no full-resolution plane exists anywhere.  The seconds of an image are its group's wall time (predict and encoding) / size."""
+    import torch
+    from .coco_results import coco_results
+    from .detection import masks_rle_source
+    items = sorted(images, key=lambda it: it[0])
+    if limit is not None:
+        items = items[:limit]
+    if batch < 1 or batch > model.max_batch:
+        raise ValueError(f"batch {batch} outside 1..{model.max_batch} (the model's max_batch)")
+    H, W = model.image_height, model.image_width
+    out: List[PBResult] = []
+    secs: List[float] = []
+    coco: List[dict] = []
+    for g0 in range(0, len(items), batch):
+        group = items[g0:g0 + batch]
+        sizes = [(int(img.shape[0]), int(img.shape[1])) for _, img in group]
+        t0 = time.perf_counter()
+        dev = [torch.from_numpy(np.ascontiguousarray(img, dtype=np.uint8)).cuda() for _, img in group]
+        det_g, mask_g = model.predict_images(dev)
+        src_g, rles, _, _ = masks_rle_source(det_g, mask_g, sizes, H, W, threshold)
+        det, det_src = det_g.cpu().numpy(), src_g.cpu().numpy()
+        t1 = time.perf_counter()
+        coco += coco_results([image_id for image_id, _ in group], det_src, rles, sizes, class_to_category, score_threshold)
+        for b, (image_id, img) in enumerate(group):
+            out.append(PBResult(dataset_id, str(image_id), int(img.shape[1]), int(img.shape[0]), detections_to_pb(det[b])))
+            secs.append((t1 - t0) / len(group))
+            if verbose:
+                print((t1 - t0) / len(group))
+    return encode_results(out), secs, out, coco
+
+
 def evaluate_from_dir(model_dir: str, images, **kw):
     return evaluate(load_maskrcnn(model_dir, max_batch=1), images, **kw)
 

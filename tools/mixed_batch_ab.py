@@ -13,7 +13,18 @@
       multiple of 4 — the same kernel against mrcnn_paste_masks (one launch per image), device buffers.  Run it under
       `rocprofv3 --kernel-trace --stats -d DIR -- python tools/mixed_batch_ab.py --paste`, then
   mixed_batch_ab.py --digest DIR [--out ...]
-      reads the kernel trace and adds µs and bytes written / µs of both kernels to the JSON file."""
+      reads the kernel trace and adds µs and bytes written / µs of both kernels to the JSON file.
+  mixed_batch_ab.py --rle [--steps 20] [--warmup 5]
+      What it costs a host to GET the masks of batch 8 x 100 rows at the eight sizes, detections and masks resident on the device,
+      the legs interleaved in one process after a warm-up:
+        A  mrcnn_paste_masks_source on device buffers, then the copy of the planes to (pinned) host memory — transport only: the
+           run-length encoding a consumer then does on the host is left out, which favours A
+        B  mrcnn_masks_rle_source on device buffers, then the copy of run_offsets and of the used run lengths
+      on uniform-random masks (many runs per column: the worst case for B) and, for B, on smooth blobs (what a network draws).
+      min / median / max of each and the bytes each moves go to the JSON file ("rle").  Under
+      `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/mixed_batch_ab.py --rle`, then
+  mixed_batch_ab.py --digest-rle DIR
+      adds the µs of k_rle_count / k_rle_offsets / k_rle_write beside k_paste_masks_ragged's ("rle_kernels")."""
 import argparse, csv, ctypes as C, glob, importlib, json, os, subprocess, sys, tempfile, time
 
 import numpy as np
@@ -127,6 +138,92 @@ def run_paste(args):
     torch.cuda.synchronize()
 
 
+def smooth_masks(batch, rng):
+    yy, xx = np.mgrid[0:28, 0:28].astype(np.float32)
+    cy = rng.uniform(8, 20, (batch, ROWS, 1, 1)); cx = rng.uniform(8, 20, (batch, ROWS, 1, 1))
+    sy = rng.uniform(4, 12, (batch, ROWS, 1, 1)); sx = rng.uniform(4, 12, (batch, ROWS, 1, 1))
+    return np.exp(-(((yy - cy) / sy) ** 2 + ((xx - cx) / sx) ** 2)).astype(np.float32)
+
+
+def run_rle(args):
+    import torch
+    lib = importlib.import_module("mask-rcnn-coreml_amd._lib")
+    L = lib.lib()
+    rng = np.random.default_rng(5)
+    B, n = len(SIZES), len(SIZES) * ROWS
+    det, random_masks = synthetic_records(B, rng)
+    hs = np.array([s[0] for s in SIZES], np.int32); ws = np.array([s[1] for s in SIZES], np.int32)
+    nbytes = ROWS * hs.astype(np.int64) * ws
+    padded = (nbytes + 15) // 16 * 16
+    offs = np.concatenate(([0], np.cumsum(padded)[:-1])).astype(np.int64)
+    det_g = torch.from_numpy(det).cuda()
+    masks_g = {"random": torch.from_numpy(random_masks).cuda(), "smooth": torch.from_numpy(smooth_masks(B, rng)).cuda()}
+    src_g = torch.empty_like(det_g)
+    planes_g = torch.empty(int(padded.sum()), dtype=torch.uint8, device="cuda")
+    planes_h = torch.empty(int(padded.sum()), dtype=torch.uint8).pin_memory()
+    ro_g = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+    ro_h = torch.empty(n + 1, dtype=torch.int64).pin_memory()
+    areas_g = torch.empty(n, dtype=torch.int32, device="cuda"); boxes_g = torch.empty(4 * n, dtype=torch.int32, device="cuda")
+    used = {}
+
+    def rle(kind, counts_g, capacity):
+        return L.mrcnn_masks_rle_source(det_g.data_ptr(), masks_g[kind].data_ptr(), B, ROWS, 28, hs.ctypes.data, ws.ctypes.data, 1024, 1024, C.c_float(0.5),
+                                        lib.DEVICE, src_g.data_ptr(), counts_g.data_ptr() if counts_g is not None else None, capacity, ro_g.data_ptr(),
+                                        areas_g.data_ptr(), boxes_g.data_ptr())
+    counts_g, counts_h = {}, {}
+    for kind in masks_g:                                                    # the size query, once, outside the timing
+        assert rle(kind, None, 0) == 4
+        used[kind] = int(ro_g[n].item())
+        counts_g[kind] = torch.empty(used[kind], dtype=torch.int32, device="cuda")
+        counts_h[kind] = torch.empty(used[kind], dtype=torch.int32).pin_memory()
+
+    def leg_a():
+        lib.check(L.mrcnn_paste_masks_source(det_g.data_ptr(), masks_g["random"].data_ptr(), B, ROWS, 28, hs.ctypes.data, ws.ctypes.data, 1024, 1024,
+                                             C.c_float(0.5), lib.DEVICE, src_g.data_ptr(), planes_g.data_ptr(), offs.ctypes.data))
+        planes_h.copy_(planes_g)
+        torch.cuda.synchronize()
+
+    def leg_b(kind):
+        lib.check(rle(kind, counts_g[kind], used[kind]))
+        ro_h.copy_(ro_g)
+        counts_h[kind].copy_(counts_g[kind])                                # (sized to the used part by the query above)
+        torch.cuda.synchronize()
+    legs = {"A": leg_a, "B": lambda: leg_b("random"), "B_smooth": lambda: leg_b("smooth")}
+    times = {k: [] for k in legs}
+    for step in range(args.warmup + args.steps):
+        for k, leg in legs.items():
+            t0 = time.perf_counter()
+            leg()
+            if step >= args.warmup:
+                times[k].append(time.perf_counter() - t0)
+
+    def ms(ts):
+        ts = sorted(ts)
+        return {"min": ts[0] * 1e3, "median": ts[len(ts) // 2] * 1e3, "max": ts[-1] * 1e3}
+    rec = {k: {"ms": ms(v)} for k, v in times.items()}
+    rec["A"]["bytes_to_host"] = int(nbytes.sum())
+    for k, kind in (("B", "random"), ("B_smooth", "smooth")):
+        rec[k]["runs"] = used[kind]
+        rec[k]["bytes_to_host"] = 4 * used[kind] + 8 * (n + 1)
+    a = rec["A"]["ms"]
+    rec["A_spread_ms"] = a["max"] - a["min"]
+    rec["B_below_A_by_more_than_A_spread"] = bool(a["median"] - rec["B"]["ms"]["median"] > rec["A_spread_ms"])
+    rec["B_smooth_below_A_by_more_than_A_spread"] = bool(a["median"] - rec["B_smooth"]["ms"]["median"] > rec["A_spread_ms"])
+    merge(args.out, {"git_head": git_head(), "rle": dict(rec, rows=ROWS, sizes_hw=SIZES, steps=args.steps, warmup=args.warmup, host_memory="pinned")})
+
+
+def run_digest_rle(args):
+    rows = []
+    for f in glob.glob(os.path.join(args.digest_rle, "**", "*kernel_trace.csv"), recursive=True):
+        rows += list(csv.DictReader(open(f)))
+    us = lambda r: (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
+
+    def stat(name):
+        v = sorted(us(r) for r in rows if name in r["Kernel_Name"])
+        return {"launches": len(v), "us": {"min": v[0], "median": v[len(v) // 2], "max": v[-1]}} if v else {"launches": 0}
+    merge(args.out, {"rle_kernels": {k: stat(k) for k in ("k_unletterbox_boxes", "k_paste_masks_ragged", "k_rle_count", "k_rle_offsets", "k_rle_write")}})
+
+
 def run_digest(args):
     rows = []
     for f in glob.glob(os.path.join(args.digest, "**", "*kernel_trace.csv"), recursive=True):
@@ -164,7 +261,14 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--paste", action="store_true")
+    ap.add_argument("--rle", action="store_true")
     ap.add_argument("--digest", metavar="DIR")
+    ap.add_argument("--digest-rle", metavar="DIR")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mixed_batch_ab.json"))
     a = ap.parse_args()
-    run_digest(a) if a.digest else (run_paste(a) if a.paste else run_ab(a))
+    if a.digest_rle:
+        run_digest_rle(a)
+    elif a.rle:
+        run_rle(a)
+    else:
+        run_digest(a) if a.digest else (run_paste(a) if a.paste else run_ab(a))
