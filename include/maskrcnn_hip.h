@@ -474,6 +474,62 @@ MRCNN_API int mrcnn_mask_to_u8(const float* mask, int64_t n, uint8_t* out);
  * mask of mrcnn_maskrcnn_predict first the result is identical (float → double is exact). */
 MRCNN_API int mrcnn_mask_to_u8_f64(const double* mask, int64_t n, uint8_t* out);
 
+/* ---------------------------------------------------------------------------------------------
+ * COCO scoring — the second half of `maskrcnn evaluate` (Sources/maskrcnn/Python/COCOEval/task.py:93-98,
+ * coco_dataset.evaluate_results: COCOeval's evaluate step).  The IoU of every detection with every ground truth of its image and the
+ * greedy matching per (image, category, area range, IoU threshold) run on the GPU; accumulate / summarize are left to the host
+ * (coco_eval.py).  RLE sets are in the layout of mrcnn_masks_rle_source: RLE k = counts[run_offsets[k] .. run_offsets[k+1]),
+ * uint32 run lengths, column-major, counts[0] = leading zeros; n + 1 offsets, non-decreasing, run_offsets[0] >= 0.
+ *
+ * mrcnn_iou_group — one image: detections [d0, d1) of the detection set against ground truths [g0, g1) of the ground-truth set; the
+ * (d1-d0) x (g1-g0) results, row-major (detection-major), start at out_offset of the outputs, which hold n_pairs entries; blocks of
+ * different groups must not overlap, entries no block covers are left untouched.
+ *
+ * mrcnn_rle_iou: inter = the intersection in pixels (exact), iou = inter / (area_d + area_g - inter) as IEEE double division of those
+ * integers; for a ground truth with g_iscrowd != 0: inter / area_d (COCO's crowd rule); 0 / 0 = 0.  A pair whose two RLEs do not sum to
+ * the same number of pixels makes the call fail with MRCNN_ERR_SHAPE (the message names the pair) before anything is written.
+ * memspace holds for the counts, the run offsets, inter and iou (with MRCNN_DEVICE the buffers mrcnn_masks_rle_source wrote are read in
+ * place); g_iscrowd (n_g, may be NULL = none) and groups are host arrays.  inter / iou may be NULL.
+ * mrcnn_box_iou_xywh: the same for boxes (x, y, w, h as double): iw = min(xd+wd, xg+wg) - max(xd, xg), ih likewise, 0 unless both are
+ * positive, else iw*ih / (wd*hd + wg*hg - iw*ih), crowd: / (wd*hd).  memspace holds for the boxes and iou.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct { int64_t d0, d1, g0, g1, out_offset; } mrcnn_iou_group;
+MRCNN_API int mrcnn_rle_iou(const uint32_t* d_counts, const int64_t* d_run_offsets, int64_t n_d, const uint32_t* g_counts,
+                            const int64_t* g_run_offsets, int64_t n_g, const uint8_t* g_iscrowd, const mrcnn_iou_group* groups, int n_groups,
+                            int memspace, uint32_t* inter, double* iou, int64_t n_pairs);
+MRCNN_API int mrcnn_box_iou_xywh(const double* d_boxes, int64_t n_d, const double* g_boxes, int64_t n_g, const uint8_t* g_iscrowd,
+                                 const mrcnn_iou_group* groups, int n_groups, int memspace, double* iou, int64_t n_pairs);
+/* COCOeval.evaluateImg for many (image, category) groups at once.  iou (n_iou doubles, memspace) holds the images' IoU blocks as the two
+ * calls above wrote them.  Group k: its image's block starts at iou_offset and has iou_stride columns (the image's ground truths);
+ * its detections are entries [dt0, dt1) of the flat lists dt_idx (row of the block) / dt_area, ALREADY sorted by score descending
+ * (stable) and cut to maxDet; its ground truths entries [gt0, gt1) of gt_idx (column of the block) / gt_area / gt_iscrowd in annotation
+ * order.  The groups tile the flat lists: dt0 of group 0 is 0, dt0 of group k+1 = dt1 of group k, the last dt1 = n_dt; likewise gt.
+ * For every area range a (area_ranges[2a] <= area <= area_ranges[2a+1] is inside) and threshold t:
+ *   a ground truth is IGNORED when it is a crowd or its area is outside the range; COCOeval's order "non-ignored first, stable" is taken
+ *   inside the kernel (it depends on a); each detection in turn takes, among the ground truths with iou >= min(t, 1 - 1e-10) that are
+ *   not yet taken (a crowd can be taken again), the non-ignored one of highest IoU — the later of equals — and only if there is none
+ *   the ignored one of highest IoU; a matched detection inherits the ignore flag, an unmatched one is ignored when its own area is
+ *   outside the range.  "Taken" is tested as such (pycocotools tests the annotation id for > 0 instead).
+ * Outputs (memspace; any may be NULL), with A = n_ranges, T = n_thresholds, nd = dt1-dt0, ng = gt1-gt0 of the group:
+ *   dt_match [A*T*dt0 + (a*T + t)*nd + i]  the position in the group's ground-truth list (0..ng-1) detection i took, or -1
+ *   dt_ignore[the same index]              1 / 0
+ *   gt_match [A*T*gt0 + (a*T + t)*ng + j]  the position in the group's detection list that took ground truth j (the last, for a crowd), or -1
+ * All tables but iou are host arrays.  Inconsistent tables (ranges out of order, an index outside its block, a block outside iou) give
+ * MRCNN_ERR_SHAPE. */
+typedef struct { int64_t iou_offset; int32_t iou_stride, dt0, dt1, gt0, gt1, reserved; } mrcnn_match_group;
+MRCNN_API int mrcnn_coco_match(const double* iou, int64_t n_iou, int memspace, const mrcnn_match_group* groups, int n_groups,
+                               const int32_t* dt_idx, const double* dt_area, int64_t n_dt, const int32_t* gt_idx, const double* gt_area,
+                               const uint8_t* gt_iscrowd, int64_t n_gt, const double* area_ranges, int n_ranges,
+                               const double* iou_thresholds, int n_thresholds, int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match);
+/* Host only, no GPU: the union of n_polys COCO polygons (polygon p = the points xy[2*poly_offsets[p]] .. xy[2*poly_offsets[p+1]), x
+ * then y, in pixels) on an h x w plane as ONE RLE, by COCO's published procedure (pycocotools rleFrPoly): vertices scaled by 5 and
+ * rounded, the edges walked on that fine grid, the crossings of pixel-column centres reduced to column-major run boundaries (clipped
+ * to the plane), the polygons of one annotation united.  *n is always the number of runs; counts = NULL with capacity = 0 only
+ * measures, a buffer that is too small gives MRCNN_ERR_SHAPE.  Polygons partly or wholly outside the plane are clipped; a polygon of fewer than 3 points
+ * or of no area still gives a valid RLE (its crossings cancel in pairs). */
+MRCNN_API int mrcnn_rle_from_polygons(const double* xy, const int64_t* poly_offsets, int n_polys, int h, int w, uint32_t* counts,
+                                      int64_t capacity, int64_t* n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "mrcnn_maskrcnn_predict_scalefit", "mrcnn_unletterbox_boxes",
     "mrcnn_maskrcnn_predict_images", "mrcnn_paste_masks_source",
     "mrcnn_masks_rle_source", "mrcnn_rle_to_string", "mrcnn_rle_from_string",
+    "mrcnn_rle_iou", "mrcnn_box_iou_xywh", "mrcnn_coco_match", "mrcnn_rle_from_polygons",
 ]
 # declared in include/maskrcnn_hip_test.h (test / measurement entry points of the same library)
 TEST_SYMBOLS = [
@@ -72,6 +73,15 @@ class SplitGroupStat(C.Structure):   # mrcnn_split_group_stat
 class DetectionRecord(C.Structure):  # mrcnn_detection
     _fields_ = [("index", C.c_int64), ("x", C.c_double), ("y", C.c_double), ("w", C.c_double), ("h", C.c_double),
                 ("class_id", C.c_int64), ("score", C.c_double)]
+
+
+class IouGroup(C.Structure):        # mrcnn_iou_group
+    _fields_ = [("d0", C.c_int64), ("d1", C.c_int64), ("g0", C.c_int64), ("g1", C.c_int64), ("out_offset", C.c_int64)]
+
+
+class MatchGroup(C.Structure):      # mrcnn_match_group
+    _fields_ = [("iou_offset", C.c_int64), ("iou_stride", C.c_int32), ("dt0", C.c_int32), ("dt1", C.c_int32), ("gt0", C.c_int32),
+                ("gt1", C.c_int32), ("reserved", C.c_int32)]
 
 
 class Image(C.Structure):           # mrcnn_image
@@ -131,6 +141,10 @@ def lib():
     L.mrcnn_masks_rle_source.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, C.c_int64, vp, vp, vp]
     L.mrcnn_rle_to_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_from_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
+    L.mrcnn_rle_iou.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int64]
+    L.mrcnn_box_iou_xywh.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int, C.c_int, vp, C.c_int64]
+    L.mrcnn_coco_match.argtypes = [vp, C.c_int64, C.c_int, vp, C.c_int, vp, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, C.c_int, vp, C.c_int, vp, vp, vp]
+    L.mrcnn_rle_from_polygons.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int64, i64p]
     L.mrcnn_maskrcnn_predict_async.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.mrcnn_maskrcnn_submit.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
     L.mrcnn_maskrcnn_collect.argtypes = [vp, vp, vp, C.POINTER(C.c_int)]

@@ -359,4 +359,26 @@ void mask_select_from_full_forward(hipStream_t s, const float* masks, long masks
                                    const float* det, long det_sB, long det_stride, int D, int B,
                                    const MaskSelectWorkspace& ws, float* out, long out_sB, long out_stride);
 
+// ================================================================================================
+// COCO scoring (kernels_coco.hip): RLE x RLE intersection, box IoU, COCOeval's greedy matching.  -ffp-contract=off.
+// ================================================================================================
+using IouGroup = mrcnn_iou_group;          // one image: detections [d0, d1) x ground truths [g0, g1), block at out_offset
+using MatchGroup = mrcnn_match_group;      // one (image, category): ranges of the flat detection / ground-truth lists
+// Per RLE k (counts[run_offsets[k] .. run_offsets[k+1])): pre_b = exclusive prefix of the counts, pre_o = exclusive prefix of the odd
+// (ones) runs, both indexed like counts (either may be nullptr); totals[k] = the pixels, areas[k] = the set pixels.  One block per RLE.
+void rle_prefix_forward(hipStream_t s, const uint32_t* counts, const long long* run_offsets, long n_rle, uint32_t* pre_b, uint32_t* pre_o,
+                        unsigned long long* totals, uint32_t* areas);
+// inter / iou of every pair of every group.  block_starts (n_groups + 1, device): prefix of ceil(nd / 4) * ng per group = the grid.
+// The caller has checked that the two RLEs of every pair have the same total.  inter / iou may be nullptr.
+void rle_iou_forward(hipStream_t s, const uint32_t* d_b, const long long* d_off, const unsigned long long* d_total, const uint32_t* d_area,
+                     const uint32_t* g_b, const uint32_t* g_o, const long long* g_off, const uint32_t* g_area, const uint8_t* g_crowd,
+                     const IouGroup* groups, const long long* block_starts, int n_groups, long long n_blocks, uint32_t* inter, double* iou);
+// pair_starts (n_groups + 1, device): prefix of nd * ng per group; one thread per pair
+void box_iou_xywh_forward(hipStream_t s, const double* db, const double* gb, const uint8_t* g_crowd, const IouGroup* groups,
+                          const long long* pair_starts, int n_groups, long long n_pairs, double* iou);
+// one wave per (group, area range, threshold); outputs laid out as mrcnn_coco_match documents
+void coco_match_forward(hipStream_t s, const double* iou, const MatchGroup* groups, int n_groups, const int32_t* dt_idx, const double* dt_area,
+                        const int32_t* gt_idx, const double* gt_area, const uint8_t* gt_crowd, const double* ranges, int A, const double* thrs, int T,
+                        int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match);
+
 }  // namespace mrcnn

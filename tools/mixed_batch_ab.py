@@ -24,7 +24,19 @@
       min / median / max of each and the bytes each moves go to the JSON file ("rle").  Under
       `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/mixed_batch_ab.py --rle`, then
   mixed_batch_ab.py --digest-rle DIR
-      adds the µs of k_rle_count / k_rle_offsets / k_rle_write beside k_paste_masks_ragged's ("rle_kernels")."""
+      adds the µs of k_rle_count / k_rle_offsets / k_rle_write beside k_paste_masks_ragged's ("rle_kernels").
+  mixed_batch_ab.py --score [--steps 20] [--warmup 5]
+      The mask IoU of COCO scoring: batch 8 x 100 detection rows at the eight sizes against 16 synthetic ground truths per image
+      (smooth blobs, rows of a second synthetic batch), everything resident on the device, legs interleaved:
+        A  what the library could do before mrcnn_rle_iou: mrcnn_paste_masks_source for both sets, then the dense intersection in
+           torch on the device, (d & g).sum per ground truth — the arithmetic of (d[:, None] & g[None]).sum without materialising
+           the 100 x 16 x h x w intermediate, which does not fit for the larger images
+        B  mrcnn_masks_rle_source for both sets, then mrcnn_rle_iou on the run-length buffers   (B_iou: mrcnn_rle_iou alone)
+        M  mrcnn_coco_match on B's IoU blocks (4 categories per image, 4 area ranges x 10 thresholds) — reported, no leg to compare
+      A's and B's intersections are compared once, outside the timing.  min / median / max go to the JSON file ("score").  Under
+      `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/mixed_batch_ab.py --score`, then
+  mixed_batch_ab.py --digest-score DIR
+      adds the µs of k_rle_prefix / k_rle_iou / k_coco_match ("score_kernels")."""
 import argparse, csv, ctypes as C, glob, importlib, json, os, subprocess, sys, tempfile, time
 
 import numpy as np
@@ -212,6 +224,135 @@ def run_rle(args):
     merge(args.out, {"git_head": git_head(), "rle": dict(rec, rows=ROWS, sizes_hw=SIZES, steps=args.steps, warmup=args.warmup, host_memory="pinned")})
 
 
+def run_score(args):
+    import torch
+    lib = importlib.import_module("mask-rcnn-coreml_amd._lib")
+    L = lib.lib()
+    rng = np.random.default_rng(7)
+    B, NG = len(SIZES), 16
+    hs = np.array([s[0] for s in SIZES], np.int32); ws = np.array([s[1] for s in SIZES], np.int32)
+
+    class Set:
+        def __init__(self, rows):
+            global ROWS
+            keep, ROWS = ROWS, rows                                          # (synthetic_records / smooth_masks size by the module's ROWS)
+            det, _ = synthetic_records(B, rng)
+            masks = smooth_masks(B, rng)
+            ROWS = keep
+            self.rows, self.n = rows, B * rows
+            self.det, self.masks = torch.from_numpy(det).cuda(), torch.from_numpy(masks).cuda()
+            self.src = torch.empty_like(self.det)
+            nbytes = rows * hs.astype(np.int64) * ws
+            padded = (nbytes + 15) // 16 * 16
+            self.offs = np.concatenate(([0], np.cumsum(padded)[:-1])).astype(np.int64)
+            self.planes = torch.empty(int(padded.sum()), dtype=torch.uint8, device="cuda")
+            self.ro = torch.empty(self.n + 1, dtype=torch.int64, device="cuda")
+            self.areas = torch.empty(self.n, dtype=torch.int32, device="cuda")
+            assert self.rle(None, 0) == 4                                    # the size query, outside the timing
+            self.used = int(self.ro[self.n].item())
+            self.counts = torch.empty(self.used, dtype=torch.int32, device="cuda")
+
+        def rle(self, counts, capacity):
+            return L.mrcnn_masks_rle_source(self.det.data_ptr(), self.masks.data_ptr(), B, self.rows, 28, hs.ctypes.data, ws.ctypes.data, 1024, 1024,
+                                            C.c_float(0.5), lib.DEVICE, self.src.data_ptr(), counts.data_ptr() if counts is not None else None, capacity,
+                                            self.ro.data_ptr(), self.areas.data_ptr(), None)
+
+        def paste(self):
+            lib.check(L.mrcnn_paste_masks_source(self.det.data_ptr(), self.masks.data_ptr(), B, self.rows, 28, hs.ctypes.data, ws.ctypes.data, 1024, 1024,
+                                                 C.c_float(0.5), lib.DEVICE, self.src.data_ptr(), self.planes.data_ptr(), self.offs.ctypes.data))
+
+        def image(self, b):
+            h, w = SIZES[b]
+            o = int(self.offs[b])
+            return self.planes[o:o + self.rows * h * w].view(self.rows, h, w)
+    D, G = Set(ROWS), Set(NG)
+    n_pairs = B * ROWS * NG
+    groups = (lib.IouGroup * B)()
+    for b in range(B):
+        groups[b].d0, groups[b].d1, groups[b].g0, groups[b].g1, groups[b].out_offset = b * ROWS, (b + 1) * ROWS, b * NG, (b + 1) * NG, b * ROWS * NG
+    crowd = np.zeros(B * NG, np.uint8)
+    inter_a = torch.empty(n_pairs, dtype=torch.int64, device="cuda")
+    inter_b = torch.empty(n_pairs, dtype=torch.int32, device="cuda")
+    iou_b = torch.empty(n_pairs, dtype=torch.float64, device="cuda")
+
+    def leg_a():
+        D.paste(); G.paste()
+        for b in range(B):
+            d, g = D.image(b), G.image(b)
+            out = inter_a[b * ROWS * NG:(b + 1) * ROWS * NG].view(ROWS, NG)
+            for j in range(NG):
+                out[:, j] = (d & g[j]).sum((1, 2))
+        torch.cuda.synchronize()
+
+    def iou_only():
+        lib.check(L.mrcnn_rle_iou(D.counts.data_ptr(), D.ro.data_ptr(), D.n, G.counts.data_ptr(), G.ro.data_ptr(), G.n, crowd.ctypes.data, groups, B,
+                                  lib.DEVICE, inter_b.data_ptr(), iou_b.data_ptr(), n_pairs))
+
+    def leg_b():
+        lib.check(D.rle(D.counts, D.used)); lib.check(G.rle(G.counts, G.used))
+        iou_only()
+    # the match tables: per image 4 categories (class id % 4), detections by score, ground truths in row order
+    det_h, gdet_h = D.det.cpu().numpy(), G.det.cpu().numpy()
+    area_d, area_g = D.areas.cpu().numpy().astype(np.float64), G.areas.cpu().numpy().astype(np.float64)
+    mg, dt_idx, gt_idx = [], [], []
+    for b in range(B):
+        for cat in range(4):
+            di = [i for i in range(ROWS) if int(det_h[b, i, 4]) % 4 == cat]
+            di = [di[i] for i in np.argsort([-det_h[b, i, 5] for i in di], kind="mergesort")]
+            gi = [j for j in range(NG) if int(gdet_h[b, j, 4]) % 4 == cat]
+            mg.append((b * ROWS * NG, NG, len(dt_idx), len(dt_idx) + len(di), len(gt_idx), len(gt_idx) + len(gi), b))
+            dt_idx += [(b, i) for i in di]; gt_idx += [(b, j) for j in gi]
+    marr = (lib.MatchGroup * len(mg))()
+    for k, g in enumerate(mg):
+        marr[k].iou_offset, marr[k].iou_stride, marr[k].dt0, marr[k].dt1, marr[k].gt0, marr[k].gt1 = g[:6]
+    dti = np.array([i for _, i in dt_idx], np.int32); gti = np.array([j for _, j in gt_idx], np.int32)
+    dta = np.array([area_d[b * ROWS + i] for b, i in dt_idx]); gta = np.array([area_g[b * NG + j] for b, j in gt_idx])
+    gtc = np.zeros(gti.size, np.uint8)
+    rngs = np.array([[0, 1e10], [0, 1024], [1024, 9216], [9216, 1e10]], np.float64); thrs = np.linspace(.5, .95, 10)
+    dm = torch.empty(40 * dti.size, dtype=torch.int32, device="cuda"); dg = torch.empty(40 * dti.size, dtype=torch.uint8, device="cuda")
+    gm = torch.empty(40 * gti.size, dtype=torch.int32, device="cuda")
+
+    def leg_m():
+        lib.check(L.mrcnn_coco_match(iou_b.data_ptr(), n_pairs, lib.DEVICE, marr, len(mg), dti.ctypes.data, dta.ctypes.data, dti.size, gti.ctypes.data,
+                                     gta.ctypes.data, gtc.ctypes.data, gti.size, rngs.ctypes.data, 4, thrs.ctypes.data, 10, dm.data_ptr(), dg.data_ptr(),
+                                     gm.data_ptr()))
+    legs = {"A": leg_a, "B": leg_b, "B_iou": iou_only, "M": leg_m}
+    times = {k: [] for k in legs}
+    for step in range(args.warmup + args.steps):
+        for k, leg in legs.items():
+            t0 = time.perf_counter()
+            leg()
+            if step >= args.warmup:
+                times[k].append(time.perf_counter() - t0)
+    equal = bool(torch.equal(inter_a, inter_b.to(torch.int64)))
+
+    def ms(ts):
+        ts = sorted(ts)
+        return {"min": ts[0] * 1e3, "median": ts[len(ts) // 2] * 1e3, "max": ts[-1] * 1e3}
+    rec = {k: {"ms": ms(v)} for k, v in times.items()}
+    a = rec["A"]["ms"]
+    rec["A_spread_ms"] = a["max"] - a["min"]
+    rec["B_below_A_by_more_than_A_spread"] = bool(a["median"] - rec["B"]["ms"]["median"] > rec["A_spread_ms"])
+    rec["intersections_equal"] = equal
+    rec["A"]["plane_bytes"] = int(D.planes.numel() + G.planes.numel())
+    rec["B"]["run_bytes"] = 4 * (D.used + G.used)
+    rec["M"]["groups"] = len(mg)
+    merge(args.out, {"git_head": git_head(), "score": dict(rec, rows=ROWS, ground_truths_per_image=NG, pairs=n_pairs, sizes_hw=SIZES, steps=args.steps,
+                                                           warmup=args.warmup)})
+
+
+def run_digest_score(args):
+    rows = []
+    for f in glob.glob(os.path.join(args.digest_score, "**", "*kernel_trace.csv"), recursive=True):
+        rows += list(csv.DictReader(open(f)))
+    us = lambda r: (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
+
+    def stat(name):
+        v = sorted(us(r) for r in rows if name in r["Kernel_Name"])
+        return {"launches": len(v), "us": {"min": v[0], "median": v[len(v) // 2], "max": v[-1]}} if v else {"launches": 0}
+    merge(args.out, {"score_kernels": {k: stat(k) for k in ("k_rle_prefix", "k_rle_iou", "k_coco_match")}})
+
+
 def run_digest_rle(args):
     rows = []
     for f in glob.glob(os.path.join(args.digest_rle, "**", "*kernel_trace.csv"), recursive=True):
@@ -264,9 +405,15 @@ if __name__ == "__main__":
     ap.add_argument("--rle", action="store_true")
     ap.add_argument("--digest", metavar="DIR")
     ap.add_argument("--digest-rle", metavar="DIR")
+    ap.add_argument("--score", action="store_true")
+    ap.add_argument("--digest-score", metavar="DIR")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mixed_batch_ab.json"))
     a = ap.parse_args()
-    if a.digest_rle:
+    if a.digest_score:
+        run_digest_score(a)
+    elif a.score:
+        run_score(a)
+    elif a.digest_rle:
         run_digest_rle(a)
     elif a.rle:
         run_rle(a)
