@@ -1,0 +1,427 @@
+// api_test.hip — the C ABI of include/maskrcnn_hip_test.h that is not in probe.hip: the debug knobs, the convolution
+// micro-benchmark, single kernels and bottleneck blocks on caller data, the live convolution profile of a model.
+#include <string.h>
+
+#include <random>
+
+#include "api_util.h"
+
+using namespace mrcnn;
+
+// ================================================================================================
+// scaffolding of the entries on caller (host) data
+// ================================================================================================
+namespace {
+
+// host floats -> a device buffer of n_alloc (default n) fp16 / fp32 elements, zero beyond the first n
+void upload_f16(DevBuf& d, const float* src, size_t n, size_t n_alloc = 0)
+{
+    std::vector<_Float16> t(n_alloc > n ? n_alloc : n, (_Float16)0.f);
+    for (size_t i = 0; i < n; ++i) t[i] = (_Float16)src[i];
+    d.alloc(t.size() * 2);
+    HIP_CHECK(hipMemcpy(d.p, t.data(), t.size() * 2, hipMemcpyHostToDevice));
+}
+void upload_f32(DevBuf& d, const float* src, size_t n, size_t n_alloc = 0)
+{
+    d.alloc((n_alloc > n ? n_alloc : n) * 4);
+    if (n_alloc > n) HIP_CHECK(hipMemset(d.p, 0, n_alloc * 4));
+    HIP_CHECK(hipMemcpy(d.p, src, n * 4, hipMemcpyHostToDevice));
+}
+void download_f16_as_f32(const void* dev, size_t n, float* out)
+{
+    std::vector<_Float16> t(n);
+    HIP_CHECK(hipMemcpy(t.data(), dev, n * 2, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) out[i] = (float)t[i];
+}
+
+// A K x K convolution (padding K / 2) over dense NHWC tensors; dtype / wdtype / out_f32 are the caller's to set.
+ConvDesc dense_nhwc_desc(const void* in, int B, int H, int W, int Cin, const void* wgt, int K, int stride, const float* scale, const float* shift,
+                         void* out, int Cout, int Npad, int act)
+{
+    ConvDesc d;
+    d.in = in; d.B = B; d.H = H; d.W = W; d.Cin = Cin;
+    d.in_sW = Cin; d.in_sH = (long)W * Cin; d.in_sB = (long)H * W * Cin;
+    d.wgt = wgt; d.KH = d.KW = K; d.stride = stride; d.padH = d.padW = K / 2;
+    d.scale = scale; d.shift = shift;
+    d.OH = (H + 2 * d.padH - K) / stride + 1; d.OW = (W + 2 * d.padW - K) / stride + 1; d.Cout = Cout; d.Npad = Npad;
+    d.out = out; d.out_sP = Cout; d.out_sB = (long)d.OH * d.OW * Cout; d.act = act;
+    return d;
+}
+// a dense residual of the output's shape
+void set_dense_residual(ConvDesc& d, const void* res)
+{
+    d.res = res; d.res_sW = d.Cout; d.res_sH = (long)d.OW * d.Cout; d.res_sB = d.out_sB;
+}
+
+// A pair of events: the average milliseconds of `iters` calls of run() on a stream.  The events go with the scope, also when a launch throws.
+struct EventTimer {
+    struct Event {
+        hipEvent_t e = nullptr;
+        Event() { HIP_CHECK(hipEventCreate(&e)); }
+        ~Event() { (void)hipEventDestroy(e); }
+    } e0, e1;
+    template <class F>
+    float avg_ms(hipStream_t s, int iters, F&& run)
+    {
+        HIP_CHECK(hipEventRecord(e0.e, s));
+        for (int i = 0; i < iters; ++i) run();
+        HIP_CHECK(hipEventRecord(e1.e, s));
+        HIP_CHECK(hipEventSynchronize(e1.e));
+        float ms = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms, e0.e, e1.e));
+        return ms / iters;
+    }
+};
+
+// One short-lived ConvScratch for the call (kernels.h), handed to the calling thread's launches until the scope ends
+struct ScopedConvScratch {
+    ConvScratch scratch;
+    explicit ScopedConvScratch(bool wanted) { if (wanted) { scratch.alloc(); conv_set_scratch(&scratch); } }
+    ~ScopedConvScratch() { conv_set_scratch(nullptr); }
+};
+
+}  // namespace
+
+// ================================================================================================
+// convolution micro-benchmark (bench.py roofline leg)
+// ================================================================================================
+extern "C" int mrcnn_bench_conv(int batch, int h, int w, int cin, int cout, int ksize, int stride, int iters, float* avg_ms,
+                                double* flops)
+{
+    return mrcnn_bench_conv_dtype(batch, h, w, cin, cout, ksize, stride, iters, MRCNN_F32, avg_ms, flops);
+}
+
+extern "C" int mrcnn_bench_conv_dtype(int batch, int h, int w, int cin, int cout, int ksize, int stride, int iters, int dtype,
+                                      float* avg_ms, double* flops)
+{
+    return guarded([&] {
+        require_gpu();
+        MRCNN_REQUIRE(avg_ms && flops && iters >= 1 && (ksize == 1 || ksize == 3) && cin % 64 == 0, MRCNN_ERR_INVALID, "bad bench_conv arguments");
+        MRCNN_REQUIRE(dtype == MRCNN_F32 || dtype == MRCNN_F16 || dtype == MRCNN_F32S || dtype == MRCNN_F32X3, MRCNN_ERR_UNSUPPORTED, "bench_conv: dtype %d", dtype);
+        const size_t es = dtype == MRCNN_F16 ? 2 : 4;             // activations
+        const size_t ws = dtype == MRCNN_F32 ? 4 : 2;             // filters
+        const int pad = ksize / 2;
+        const int oh = (h + 2 * pad - ksize) / stride + 1, ow = (w + 2 * pad - ksize) / stride + 1;
+        const int bn = conv_n_tile(cout), npad = (cout + bn - 1) / bn * bn;
+        const size_t n_in = (size_t)batch * h * w * cin, n_w = (size_t)npad * ksize * ksize * cin, n_out = (size_t)batch * oh * ow * cout;
+        std::mt19937 rng(7);
+        std::uniform_real_distribution<float> U(-1.f, 1.f);
+        const std::vector<float> hs(npad, 1.f), hb(npad, 0.f);
+        // random operands in [-1,1) (weights scaled); for fp16 the bit patterns are generated directly
+        const size_t pat = 1 << 20;
+        std::vector<unsigned char> hin(pat * es), hw(n_w * ws);
+        auto fill = [&](unsigned char* dst, size_t n, float scale, size_t esz) {
+            for (size_t i = 0; i < n; ++i) {
+                const float v = U(rng) * scale;
+                if (esz == 4) memcpy(dst + i * 4, &v, 4);
+                else { const _Float16 hv = (_Float16)v; memcpy(dst + i * 2, &hv, 2); }
+            }
+        };
+        fill(hin.data(), pat, 1.f, es);
+        fill(hw.data(), n_w, 0.05f, ws);
+        DevBuf din(n_in * es), dw(n_w * ws), ds, db, dout(n_out * es);
+        for (size_t off = 0; off < n_in; off += pat) {
+            const size_t c = n_in - off < pat ? n_in - off : pat;
+            HIP_CHECK(hipMemcpy((char*)din.p + off * es, hin.data(), c * es, hipMemcpyHostToDevice));
+        }
+        HIP_CHECK(hipMemcpy(dw.p, hw.data(), n_w * ws, hipMemcpyHostToDevice));
+        upload_f32(ds, hs.data(), npad);
+        upload_f32(db, hb.data(), npad);
+        ConvDesc d = dense_nhwc_desc(din.p, batch, h, w, cin, dw.p, ksize, stride, ds.as<float>(), db.as<float>(), dout.p, cout, npad, ACT_RELU);
+        d.dtype = (dtype == MRCNN_F32S || dtype == MRCNN_F32X3) ? MRCNN_F32 : dtype;
+        d.wdtype = dtype == MRCNN_F32 ? MRCNN_F32 : (dtype == MRCNN_F32X3 ? MRCNN_F32X3 : MRCNN_F16);
+        DevBuf dres;
+        if (knob_env("MRCNN_BENCH_RESIDUAL") && atoi(knob_env("MRCNN_BENCH_RESIDUAL"))) {        // the bottleneck blocks' branch2c shape
+            dres.alloc(n_out * es);
+            HIP_CHECK(hipMemset(dres.p, 0, n_out * es));
+            set_dense_residual(d, dres.p);
+        }
+        Stream st;
+        DevBuf dwh;
+        if (ksize == 3 && ws == 2 && es == 4 && conv_halo_packable(ksize, ksize, cin, npad)) {
+            conv_halo_pack(st.s, dw.p, npad, cin, dwh);
+            d.wgt_halo = dwh.p;
+        }
+        DevBuf dw3h;
+        if (ws == 2 && es == 2 && stride == 1 && conv3x3h_packable(ksize, ksize, cin, cout, npad)) { conv3x3h_pack(st.s, dw.p, cout, cin, dw3h); d.wgt_c3h = dw3h.p; }
+        ScopedConvScratch scratch(ws == 2 && es == 4);      // the split modes' shared-tile K chunks measure as the engine runs them
+        EventTimer timer;
+        for (int i = 0; i < 2; ++i) conv_forward(st.s, d);   // warm-up, outside the timed region
+        *avg_ms = timer.avg_ms(st.s, iters, [&] { conv_forward(st.s, d); });
+        *flops = 2.0 * (double)batch * oh * ow * (double)cout * ksize * ksize * cin;
+    });
+}
+
+// ================================================================================================
+// One convolution of the engine's kernel family on caller data (parity tests of the kernels themselves: every tile
+// shape / pipeline variant must give bit-identical results, since the choice depends on the batch size)
+// ================================================================================================
+static int g_conv2d_alias_res = 0;      // mrcnn_conv2d_nhwc writes its output in place over the residual (tests of the in-place contract)
+extern "C" int mrcnn_debug_set(const char* key, int value)
+{
+    return guarded([&] {
+        MRCNN_REQUIRE(key, MRCNN_ERR_INVALID, "null key");
+        MRCNN_REQUIRE(test_knobs_armed(), MRCNN_ERR_UNSUPPORTED, "mrcnn_debug_set('%s'): the test / measurement knobs are armed only in a process started with "
+                      "MRCNN_TEST_KNOBS=1 (include/maskrcnn_hip_test.h); a production host runs the shipped policy", key);
+        if (strcmp(key, "conv2d_alias_res") == 0) { g_conv2d_alias_res = value; return; }
+        MRCNN_REQUIRE(conv_debug_set(key, value) || boxes_debug_set(key, value) || engine_debug_set(key, value), MRCNN_ERR_INVALID, "unknown debug key '%s'", key);
+    });
+}
+
+extern "C" int mrcnn_conv2d_nhwc(const float* in, int batch, int h, int w, int cin, const float* filters, int cout, int ksize, int stride,
+                                 const float* scale, const float* shift, const float* residual, int act, int dtype, float* out)
+{
+    return guarded([&] {
+        require_gpu();
+        MRCNN_REQUIRE(in && filters && out && batch >= 1 && h >= 1 && w >= 1 && cout >= 1 && (ksize == 1 || ksize == 3) && stride >= 1,
+                      MRCNN_ERR_INVALID, "bad conv2d_nhwc argument");
+        MRCNN_REQUIRE(dtype == MRCNN_F32 || dtype == MRCNN_F16 || dtype == MRCNN_F32S || dtype == MRCNN_F32X3, MRCNN_ERR_UNSUPPORTED, "conv2d_nhwc: dtype %d", dtype);
+        const int adt = dtype == MRCNN_F16 ? MRCNN_F16 : MRCNN_F32;
+        const int wdt = dtype == MRCNN_F32 ? MRCNN_F32 : (dtype == MRCNN_F32X3 ? MRCNN_F32X3 : MRCNN_F16);
+        MRCNN_REQUIRE(cin % (adt == MRCNN_F16 ? 64 : 32) == 0, MRCNN_ERR_SHAPE, "conv2d_nhwc: Cin %d not a multiple of the K tile", cin);
+        const int pad = ksize / 2;
+        const int oh = (h + 2 * pad - ksize) / stride + 1, ow = (w + 2 * pad - ksize) / stride + 1;
+        const int bn = conv_n_tile(cout), npad = (cout + bn - 1) / bn * bn;
+        const size_t n_in = (size_t)batch * h * w * cin, kk = (size_t)ksize * ksize * cin, n_out = (size_t)batch * oh * ow * cout;
+        auto* const upload_act = adt == MRCNN_F16 ? upload_f16 : upload_f32;
+        DevBuf din, dw, ds, db, dres, dout;
+        upload_act(din, in, n_in, n_in);
+        (wdt != MRCNN_F32 ? upload_f16 : upload_f32)(dw, filters, (size_t)cout * kk, (size_t)npad * kk);      // the filter rows up to Npad are zero
+        std::vector<float> hs(npad, 0.f), hb(npad, 0.f);
+        for (int o = 0; o < cout; ++o) { hs[o] = scale ? scale[o] : 1.f; hb[o] = shift ? shift[o] : 0.f; }
+        upload_f32(ds, hs.data(), npad);
+        upload_f32(db, hb.data(), npad);
+        if (residual) upload_act(dres, residual, n_out, n_out);
+        dout.alloc(n_out * 4);
+        ConvDesc d = dense_nhwc_desc(din.p, batch, h, w, cin, dw.p, ksize, stride, ds.as<float>(), db.as<float>(), dout.p, cout, npad, act);
+        d.dtype = adt; d.wdtype = wdt; d.out_f32 = 0;      // fp16 mode stores fp16 (the path the engine's layers take), widened below
+        if (residual) set_dense_residual(d, dres.p);
+        // mrcnn_debug_set("conv2d_alias_res", 1): the output is written IN PLACE over the residual, the way the engine runs every
+        // bottleneck block's branch2c (engine.hip: `to = sc`).  The contract every epilogue must keep (ConvDesc::res in kernels.h):
+        // a residual element is loaded by the thread that stores the output element at the same address, before that store.
+        if (residual && g_conv2d_alias_res) d.out = dres.p;
+        Stream st;
+        DevBuf dwh;
+        if (ksize == 3 && wdt != MRCNN_F32 && adt == MRCNN_F32 && conv_halo_packable(ksize, ksize, cin, npad)) {
+            conv_halo_pack(st.s, dw.p, npad, cin, dwh);
+            d.wgt_halo = dwh.p;
+        }
+        DevBuf dw3h;
+        if (adt == MRCNN_F16 && conv3x3h_packable(ksize, ksize, cin, cout, npad)) { conv3x3h_pack(st.s, dw.p, cout, cin, dw3h); d.wgt_c3h = dw3h.p; }
+        ScopedConvScratch scratch(wdt != MRCNN_F32 && adt == MRCNN_F32);      // the shared-tile K chunks need it
+        conv_forward(st.s, d);
+        HIP_CHECK(hipStreamSynchronize(st.s));
+        if (adt == MRCNN_F16) download_f16_as_f32(d.out, n_out, out);
+        else HIP_CHECK(hipMemcpy(out, d.out, n_out * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+// An identity bottleneck block of the fp16 mode on caller (host) data — the unit tests/test_gpu_bneck.py compares bit for bit:
+// fused = 1: the single persistent launch (kernels_bneck.hip); 0: the three launches of the 128-row / ping-pong kernels.
+extern "C" int mrcnn_bottleneck_nhwc(const float* x, int batch, int h, int w, int cmid, const float* w1, const float* w2, const float* w3,
+                                     const float* s1, const float* h1, const float* s2, const float* h2, const float* s3, const float* h3,
+                                     int fused, int iters, float* out, float* avg_ms)
+{
+    return guarded([&] {
+        require_gpu();
+        MRCNN_REQUIRE(x && w1 && w2 && w3 && s1 && h1 && s2 && h2 && s3 && h3 && out && batch >= 1 && h >= 1 && w >= 1 && cmid >= 64 && cmid % 64 == 0,
+                      MRCNN_ERR_INVALID, "bad bottleneck_nhwc argument");
+        const int C = cmid, C4 = 4 * cmid;
+        const size_t npix = (size_t)batch * h * w;
+        DevBuf dx, dy, dt1, dt2, dw1, dw2, dw3, ds1, dh1, ds2, dh2, ds3, dh3;
+        upload_f16(dx, x, npix * C4);
+        upload_f16(dw1, w1, (size_t)C * C4);
+        upload_f16(dw2, w2, (size_t)C * 9 * C);
+        upload_f16(dw3, w3, (size_t)C4 * C);
+        upload_f32(ds1, s1, C); upload_f32(dh1, h1, C); upload_f32(ds2, s2, C); upload_f32(dh2, h2, C); upload_f32(ds3, s3, C4); upload_f32(dh3, h3, C4);
+        dy.alloc(npix * C4 * 2); dt1.alloc(npix * C * 2); dt2.alloc(npix * C * 2);
+        HIP_CHECK(hipMemset(dy.p, 0xff, npix * C4 * 2));
+        auto desc = [&](const void* in, int cin, const void* wgt, int k, const float* sc, const float* sh, void* o, int cout) {
+            ConvDesc d = dense_nhwc_desc(in, batch, h, w, cin, wgt, k, 1, sc, sh, o, cout, cout, ACT_RELU);
+            d.dtype = d.wdtype = MRCNN_F16;
+            return d;
+        };
+        ConvDesc da = desc(dx.p, C4, dw1.p, 1, ds1.as<float>(), dh1.as<float>(), dt1.p, C);
+        ConvDesc db = desc(dt1.p, C, dw2.p, 3, ds2.as<float>(), dh2.as<float>(), dt2.p, C);
+        ConvDesc dc = desc(dt2.p, C, dw3.p, 1, ds3.as<float>(), dh3.as<float>(), dy.p, C4);
+        set_dense_residual(dc, dx.p);
+        Stream st;
+        DevBuf dw1f, dw2f, dw3f;
+        if (bneck_frag_wanted(1, 1, C4, C)) { bneck_pack_frag(st.s, dw1.p, C, C4, dw1f); da.wgt_frag = dw1f.p; }
+        if (bneck_frag_wanted(3, 3, C, C)) { bneck_pack_frag(st.s, dw2.p, C, 9 * C, dw2f); db.wgt_frag = dw2f.p; }
+        if (bneck_frag_wanted(1, 1, C, C4)) { bneck_pack_frag(st.s, dw3.p, C4, C, dw3f); dc.wgt_frag = dw3f.p; }
+        MRCNN_REQUIRE(!fused || conv_bneck_fusable(da, db, dc), MRCNN_ERR_UNSUPPORTED, "bottleneck_nhwc: C %d at %dx%d does not qualify for the fused launch", C, h, w);
+        auto run = [&] {
+            if (fused) {        // the fused launch whatever the grid size (conv_bneck_forward sends under-filled grids to the three launches)
+                bneck_launch(st.s, C, da.in, dc.out, batch, h, w, da.wgt, db.wgt, dc.wgt, da.scale, da.shift, db.scale, db.shift, dc.scale, dc.shift, nullptr, device_cu_count(),
+                             fused == 2 ? nullptr : db.wgt_frag, fused == 2 ? nullptr : dc.wgt_frag, fused == 2 ? nullptr : da.wgt_frag);
+            }
+            else { conv_forward(st.s, da); conv_forward(st.s, db); conv_forward(st.s, dc); }
+        };
+        run();
+        HIP_CHECK(hipStreamSynchronize(st.s));
+        if (iters > 0 && avg_ms) *avg_ms = EventTimer().avg_ms(st.s, iters, run);
+        download_f16_as_f32(dy.p, npix * C4, out);
+    });
+}
+
+// The stage-entry block (res2a of the fp16 mode: x (B,H,W,C) -> (B,H,W,4C), shortcut = the 1x1 convolution ws of x) — fused = 1: one launch
+// (kernels_bneck.hip, FIRST form); 0: the four launches.  tests/test_gpu_bneck.py compares them bit for bit.
+extern "C" int mrcnn_bottleneck_first_nhwc(const float* x, int batch, int h, int w, int cmid, const float* w1, const float* w2, const float* w3, const float* ws,
+                                           const float* const bn[8], int fused, int iters, float* out, float* avg_ms)
+{
+    return guarded([&] {
+        require_gpu();
+        MRCNN_REQUIRE(x && w1 && w2 && w3 && ws && bn && out && batch >= 1 && h >= 1 && w >= 1 && cmid >= 64 && cmid % 64 == 0, MRCNN_ERR_INVALID, "bad bottleneck_first_nhwc argument");
+        const int C = cmid, C4 = 4 * cmid;
+        const size_t npix = (size_t)batch * h * w;
+        DevBuf dx, dy, dsc, dt1, dt2, dw1, dw2, dw3, dws, dbn[8];
+        upload_f16(dx, x, npix * C);
+        upload_f16(dw1, w1, (size_t)C * C); upload_f16(dw2, w2, (size_t)C * 9 * C); upload_f16(dw3, w3, (size_t)C4 * C); upload_f16(dws, ws, (size_t)C4 * C);
+        const int bn_n[8] = {C, C, C, C, C4, C4, C4, C4};
+        for (int i = 0; i < 8; ++i) upload_f32(dbn[i], bn[i], (size_t)bn_n[i]);
+        dy.alloc(npix * C4 * 2); dsc.alloc(npix * C4 * 2); dt1.alloc(npix * C * 2); dt2.alloc(npix * C * 2);
+        HIP_CHECK(hipMemset(dy.p, 0xff, npix * C4 * 2));
+        auto desc = [&](const void* in, int cin, const void* wgt, int k, int bi, void* o, int cout, int act) {
+            ConvDesc d = dense_nhwc_desc(in, batch, h, w, cin, wgt, k, 1, dbn[bi].as<float>(), dbn[bi + 1].as<float>(), o, cout, cout, act);
+            d.dtype = d.wdtype = MRCNN_F16;
+            return d;
+        };
+        ConvDesc da = desc(dx.p, C, dw1.p, 1, 0, dt1.p, C, ACT_RELU);
+        ConvDesc db = desc(dt1.p, C, dw2.p, 3, 2, dt2.p, C, ACT_RELU);
+        ConvDesc dc = desc(dt2.p, C, dw3.p, 1, 4, dy.p, C4, ACT_RELU);
+        ConvDesc ds = desc(dx.p, C, dws.p, 1, 6, dsc.p, C4, ACT_NONE);
+        set_dense_residual(dc, dsc.p);
+        MRCNN_REQUIRE(!fused || conv_bneck_first_fusable(da, db, dc, ds), MRCNN_ERR_UNSUPPORTED, "bottleneck_first_nhwc: C %d at %dx%d does not qualify for the fused launch", C, h, w);
+        Stream st;
+        auto run = [&] {
+            if (fused) bneck_launch(st.s, C, da.in, dc.out, batch, h, w, da.wgt, db.wgt, dc.wgt, da.scale, da.shift, db.scale, db.shift, dc.scale, dc.shift, nullptr, device_cu_count(),
+                                    nullptr, nullptr, nullptr, ds.wgt, ds.scale, ds.shift);
+            else { conv_forward(st.s, da); conv_forward(st.s, ds); conv_forward(st.s, db); conv_forward(st.s, dc); }
+        };
+        run();
+        HIP_CHECK(hipStreamSynchronize(st.s));
+        if (iters > 0 && avg_ms) *avg_ms = EventTimer().avg_ms(st.s, iters, run);
+        download_f16_as_f32(dy.p, npix * C4, out);
+    });
+}
+
+// The identity blocks of a C = 256 stage on caller data (tests/test_gpu_bneck.py): nlayers blocks with stacked operands — w1 (n,C,4C), w2 (n,C,3,3,C),
+// w3 (n,4C,C), bn[6] = s1,h1,s2,h2 (n,C) and s3,h3 (n,4C).  form 1: ONE launch (kernels_bneck.hip, STAGE form: tiles wait for their neighbours' previous
+// block); form 0: one fused launch per block.  out = the last block's output.  status_flag (optional) receives the launch's flag word (bit 1: no progress).
+extern "C" int mrcnn_bottleneck_stage_nhwc(const float* x, int batch, int h, int w, int nlayers, const float* w1, const float* w2, const float* w3,
+                                           const float* const bn[6], int form, int iters, float* out, float* avg_ms, int* status_flag)
+{
+    return guarded([&] {
+        require_gpu();
+        MRCNN_REQUIRE(x && w1 && w2 && w3 && bn && out && batch >= 1 && h >= 1 && w >= 1 && nlayers >= 1, MRCNN_ERR_INVALID, "bad bottleneck_stage_nhwc argument");
+        const int C = 256, C4 = 1024;
+        MRCNN_REQUIRE(bneck_geometry_ok(C, h, w), MRCNN_ERR_UNSUPPORTED, "bottleneck_stage_nhwc: %dx%d does not qualify", h, w);
+        const size_t npix = (size_t)batch * h * w;
+        DevBuf dx, dx0, dy, dbn[6], flag;
+        upload_f16(dx0, x, npix * C4);
+        dx.alloc(npix * C4 * 2); dy.alloc(npix * C4 * 2);
+        flag.alloc(sizeof(int));
+        const size_t bn_n[6] = {(size_t)C, (size_t)C, (size_t)C, (size_t)C, (size_t)C4, (size_t)C4};
+        for (int i = 0; i < 6; ++i) upload_f32(dbn[i], bn[i], bn_n[i] * nlayers);
+        Stream st;
+        std::vector<DevBuf> dw(3 * (size_t)nlayers), df(3 * (size_t)nlayers);
+        const size_t rb = bneck_layer_record_bytes();
+        std::vector<unsigned char> recs(rb * nlayers);
+        for (int l = 0; l < nlayers; ++l) {
+            upload_f16(dw[3 * l], w1 + (size_t)l * C * C4, (size_t)C * C4);
+            upload_f16(dw[3 * l + 1], w2 + (size_t)l * C * 9 * C, (size_t)C * 9 * C);
+            upload_f16(dw[3 * l + 2], w3 + (size_t)l * C4 * C, (size_t)C4 * C);
+            bneck_pack_frag(st.s, dw[3 * l].p, C, C4, df[3 * l]);
+            bneck_pack_frag(st.s, dw[3 * l + 1].p, C, 9 * C, df[3 * l + 1]);
+            bneck_pack_frag(st.s, dw[3 * l + 2].p, C4, C, df[3 * l + 2]);
+            bneck_layer_record(recs.data() + l * rb, df[3 * l].p, df[3 * l + 1].p, df[3 * l + 2].p, dbn[0].as<float>() + (size_t)l * C, dbn[1].as<float>() + (size_t)l * C,
+                               dbn[2].as<float>() + (size_t)l * C, dbn[3].as<float>() + (size_t)l * C, dbn[4].as<float>() + (size_t)l * C4, dbn[5].as<float>() + (size_t)l * C4);
+        }
+        const int ntiles = batch * (h / 8) * (w / 16);
+        DevBuf tab(recs.size() + (size_t)ntiles * sizeof(unsigned));
+        HIP_CHECK(hipMemcpy(tab.p, recs.data(), recs.size(), hipMemcpyHostToDevice));
+        unsigned* const done = reinterpret_cast<unsigned*>(static_cast<unsigned char*>(tab.p) + recs.size());
+        const int n_cus = device_cu_count();
+        auto run = [&] {
+            HIP_CHECK(hipMemcpyAsync(dx.p, dx0.p, npix * C4 * 2, hipMemcpyDeviceToDevice, st.s));      // (the blocks overwrite the input tensor from the second one on)
+            HIP_CHECK(hipMemsetAsync(flag.p, 0, sizeof(int), st.s));
+            if (form == 1) bneck_stage_launch(st.s, tab.p, nlayers, dx.p, dy.p, batch, h, w, done, flag.as<int>(), n_cus);
+            else
+                for (int l = 0; l < nlayers; ++l) {
+                    void* const pi = (l & 1) ? dy.p : dx.p;
+                    void* const po = (l & 1) ? dx.p : dy.p;
+                    bneck_launch(st.s, C, pi, po, batch, h, w, dw[3 * l].p, dw[3 * l + 1].p, dw[3 * l + 2].p, dbn[0].as<float>() + (size_t)l * C, dbn[1].as<float>() + (size_t)l * C,
+                                 dbn[2].as<float>() + (size_t)l * C, dbn[3].as<float>() + (size_t)l * C, dbn[4].as<float>() + (size_t)l * C4, dbn[5].as<float>() + (size_t)l * C4,
+                                 flag.as<int>(), n_cus, df[3 * l + 1].p, df[3 * l + 2].p, df[3 * l].p);
+                }
+        };
+        run();
+        HIP_CHECK(hipStreamSynchronize(st.s));
+        if (status_flag) HIP_CHECK(hipMemcpy(status_flag, flag.p, sizeof(int), hipMemcpyDeviceToHost));
+        if (iters > 0 && avg_ms) *avg_ms = EventTimer().avg_ms(st.s, iters, run);      // (includes the input copy and the two memsets of a run: the same for both forms)
+        download_f16_as_f32((nlayers & 1) ? dy.p : dx.p, npix * C4, out);
+    });
+}
+
+extern "C" int mrcnn_model_conv_profile_enable(mrcnn_model* model, int on)
+{
+    return guarded([&] {
+        MRCNN_REQUIRE(model, MRCNN_ERR_INVALID, "null model");
+        ConvProfile& cp = model->m.conv_profile;
+        if (on) {
+            cp.reset();                                  // a new measurement window
+        } else if (cp.active) {
+            HIP_CHECK(hipStreamSynchronize(model->m.stream));
+            cp.collect();                                // keep the totals readable after the window closes
+        }
+        cp.active = on != 0;
+    });
+}
+extern "C" int mrcnn_model_conv_profile_get(mrcnn_model* model, int tile, int64_t* launches, double* total_ms, double* total_flops)
+{
+    return guarded([&] {
+        MRCNN_REQUIRE(model && launches && total_ms && total_flops && tile >= 0 && tile < 9, MRCNN_ERR_INVALID, "bad argument");
+        HIP_CHECK(hipStreamSynchronize(model->m.stream));
+        model->m.conv_profile.collect();
+        const auto& sl = model->m.conv_profile.by_tile[tile];
+        *launches = sl.launches; *total_ms = sl.ms; *total_flops = sl.flops;
+    });
+}
+
+extern "C" int mrcnn_model_conv_profile_bytes(mrcnn_model* model, int tile, double* total_bytes)
+{
+    return guarded([&] {
+        MRCNN_REQUIRE(model && total_bytes && tile >= 0 && tile < 9, MRCNN_ERR_INVALID, "bad argument");
+        HIP_CHECK(hipStreamSynchronize(model->m.stream));
+        model->m.conv_profile.collect();
+        *total_bytes = model->m.conv_profile.by_tile[tile].bytes;
+    });
+}
+
+extern "C" int mrcnn_model_conv_profile_group(mrcnn_model* model, int group, int64_t* launches, double* total_ms, double* total_flops)
+{
+    return guarded([&] {
+        MRCNN_REQUIRE(model && launches && total_ms && total_flops && (group == 0 || group == 1), MRCNN_ERR_INVALID, "bad argument");
+        // (the totals are complete only once the pending launches' events have been read — as in _get)
+        HIP_CHECK(hipStreamSynchronize(model->m.stream));
+        model->m.conv_profile.collect();
+        const auto& sl = model->m.conv_profile.by_group[group];
+        *launches = sl.launches; *total_ms = sl.ms; *total_flops = sl.flops;
+    });
+}
+extern "C" int mrcnn_model_conv_profile_shapes(mrcnn_model* model, mrcnn_conv_shape_stat* out, int capacity, int* count)
+{
+    return guarded([&] {
+        MRCNN_REQUIRE(model && count && (out || capacity == 0) && capacity >= 0, MRCNN_ERR_INVALID, "bad argument");
+        HIP_CHECK(hipStreamSynchronize(model->m.stream));
+        model->m.conv_profile.collect();
+        const auto& shapes = model->m.conv_profile.by_shape;
+        *count = (int)shapes.size();
+        int i = 0;
+        for (const auto& kv : shapes) {
+            if (i >= capacity) break;
+            out[i++] = {kv.first.M, kv.first.N, kv.first.K, kv.first.tile, (int64_t)kv.second.launches, kv.second.ms, kv.second.flops, kv.second.bytes};
+        }
+    });
+}

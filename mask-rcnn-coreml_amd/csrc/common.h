@@ -113,4 +113,11 @@ struct DevBuf {
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// Compute units of the current device, read once per process; 256 when the query fails.
+inline int device_cu_count()
+{
+    static const int n = [] { int dev = 0; hipDeviceProp_t p; (void)hipGetDevice(&dev); return hipGetDeviceProperties(&p, dev) == hipSuccess ? p.multiProcessorCount : 256; }();
+    return n;
+}
+
 }  // namespace mrcnn

@@ -820,7 +820,7 @@ void conv_forward(hipStream_t s, const ConvDesc& d_in, const ConvDesc* sc)
     const bool half = d.dtype == MRCNN_F16;
     const int wdtype = d.wdtype < 0 ? d.dtype : d.wdtype;
     if (half && g_c3h && (d.head_w || d.prefer_c3h || g_c3h == 2) && conv3x3h_eligible(d)) {
-        static int n_cus_c3h = [] { int dev = 0; hipDeviceProp_t p; (void)hipGetDevice(&dev); return hipGetDeviceProperties(&p, dev) == hipSuccess ? p.multiProcessorCount : 256; }();
+        const int n_cus_c3h = device_cu_count();
         ConvProfile* prof = (g_prof && g_prof->active) ? g_prof : nullptr;
         const int e0 = prof ? prof_event(prof, s) : 0;
         conv3x3h_launch(s, d, g_range_flag, n_cus_c3h);
@@ -907,7 +907,7 @@ void conv_forward(hipStream_t s, const ConvDesc& d_in, const ConvDesc* sc)
     const bool halo = g_halo && d.wgt_halo && a.vec_ok && conv_halo_eligible(d);
     MRCNN_REQUIRE(!d.head_w || (halo && conv_halo_head_eligible(d)), MRCNN_ERR_INVALID, "conv: a fused head needs the halo kernel (layer not eligible, or switched off)");
     if (halo) {
-        static int n_cus = [] { int dev = 0; hipDeviceProp_t p; (void)hipGetDevice(&dev); return hipGetDeviceProperties(&p, dev) == hipSuccess ? p.multiProcessorCount : 256; }();
+        const int n_cus = device_cu_count();
         pp_bn = 0;
         (void)conv_halo_forward(s, a, d, wdtype == MRCNN_F32X3 ? 3 : 2, n_cus);
     } else
@@ -943,7 +943,7 @@ bool conv_stem_eligible(const ConvDesc& d)
 void conv_stem_forward(hipStream_t s, const ConvDesc& d, void* pooled, int PH, int PW)
 {
     MRCNN_REQUIRE(conv_stem_eligible(d) && pooled && PH == (d.OH + 1) / 2 && PW == (d.OW + 1) / 2, MRCNN_ERR_INVALID, "conv_stem_forward: not the stem layer");
-    static int n_cus = [] { int dev = 0; hipDeviceProp_t p; (void)hipGetDevice(&dev); return hipGetDeviceProperties(&p, dev) == hipSuccess ? p.multiProcessorCount : 256; }();
+    const int n_cus = device_cu_count();
     ConvProfile* prof = (g_prof && g_prof->active) ? g_prof : nullptr;
     const int e0 = prof ? prof_event(prof, s) : 0;
     const int wdtype = d.wdtype < 0 ? d.dtype : d.wdtype;
@@ -979,7 +979,7 @@ bool conv_tail_fusable(const ConvDesc& d3, const ConvDesc& d1)
 
 void conv_forward_tail(hipStream_t s, const ConvDesc& d3, const ConvDesc& d1, const ConvDesc* sc)
 {
-    static int n_cus = [] { int dev = 0; hipDeviceProp_t p; (void)hipGetDevice(&dev); return hipGetDeviceProperties(&p, dev) == hipSuccess ? p.multiProcessorCount : 256; }();
+    const int n_cus = device_cu_count();
     const long tiles = ((long)d3.B * d3.OH * d3.OW + 127) / 128;
     ConvArgs a3, a1;
     bool fuse = g_tail && g_halo && g_scratch && conv_tail_fusable(d3, d1) && tiles * 8 >= (long)n_cus * 7;       // a grid that fills the chip: one 128 x 256 tile per block (and an owner for the parking buffer)
@@ -1036,7 +1036,7 @@ bool conv_bneck_fusable(const ConvDesc& da, const ConvDesc& db, const ConvDesc& 
 
 void conv_bneck_forward(hipStream_t s, const ConvDesc& da, const ConvDesc& db, const ConvDesc& dc)
 {
-    static int n_cus = [] { int dev = 0; hipDeviceProp_t p; (void)hipGetDevice(&dev); return hipGetDeviceProperties(&p, dev) == hipSuccess ? p.multiProcessorCount : 256; }();
+    const int n_cus = device_cu_count();
     // One tile per block: a grid that leaves the chip under-filled (single images: 32 tiles at C4) runs the three launches, whose narrower
     // tiles spread over more CUs — the two forms agree bit for bit, so the choice may follow the batch (measured at batch 1, fp16 mode:
     // 2.66 ms per image with the three launches, 3.59 fused everywhere; batch 8: 9.87 -> 9.52 ms fused)
@@ -1061,7 +1061,7 @@ void conv_bneck_forward(hipStream_t s, const ConvDesc& da, const ConvDesc& db, c
 
 void conv_bneck_stage_forward(hipStream_t s, const BneckTriple* blocks, int n, const void* layers_dev, unsigned* done)
 {
-    static int n_cus = [] { int dev = 0; hipDeviceProp_t p; (void)hipGetDevice(&dev); return hipGetDeviceProperties(&p, dev) == hipSuccess ? p.multiProcessorCount : 256; }();
+    const int n_cus = device_cu_count();
     bool stage = n >= 2 && g_bneck == 1 && g_bneck_stage && layers_dev && done && g_range_flag;
     if (stage) {
         const ConvDesc& a0 = blocks[0].a;
@@ -1112,7 +1112,7 @@ bool conv_bneck_first_fusable(const ConvDesc& da, const ConvDesc& db, const Conv
 
 void conv_bneck_first_forward(hipStream_t s, const ConvDesc& da, const ConvDesc& db, const ConvDesc& dc, const ConvDesc& ds)
 {
-    static int n_cus = [] { int dev = 0; hipDeviceProp_t p; (void)hipGetDevice(&dev); return hipGetDeviceProperties(&p, dev) == hipSuccess ? p.multiProcessorCount : 256; }();
+    const int n_cus = device_cu_count();
     const long ntiles = (long)da.B * (da.H / 16) * (da.W / 16);
     if (!g_bneck || !conv_bneck_first_fusable(da, db, dc, ds) || (g_bneck < 3 && ntiles * 8 < (long)n_cus * 7)) {
         conv_forward(s, da);
