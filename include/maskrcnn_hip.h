@@ -464,6 +464,50 @@ MRCNN_API int mrcnn_masks_rle_source(const float* detections, const float* masks
                                      const int32_t* heights, const int32_t* widths, int model_h, int model_w, float threshold,
                                      int memspace, float* detections_src, uint32_t* counts, int64_t capacity, int64_t* run_offsets,
                                      uint32_t* areas, int32_t* bboxes_xywh);
+/* Drawing (Example/Source/DetectionRenderer.swift:13-88: each 28×28 mask stretched over its box and filled in one of four colours,
+ * the box stroked three pixels wide, everything over the photo) — for a batch of images of DIFFERENT sizes, in each image's own
+ * pixels, straight from the 28×28 masks: the rows × h × w planes of mrcnn_paste_masks_source are never written.  Both entries are
+ * defined by that call and nothing else.  For image b (h_b × w_b) and row i: box_i = (y1, x1, y2, x2), the pixel box of the mapped
+ * row (round-half-even of y*(h_b-1), +1 on the far edge, which is exclusive; empty for a row that pastes nothing), P_i = the plane
+ * mrcnn_paste_masks_source pastes for the row at `threshold`.  Row i is DRAWN if its score > min_score and box_i is not empty;
+ * padding rows and rows with score <= 0 are never drawn, whatever min_score is.
+ *
+ * mrcnn_instance_map_source — DetectionRenderer.swift:13-24 without the colours: which detection owns a pixel.
+ *   map + map_offsets[b] (bytes)     h_b × w_b int16, row-major: the LOWEST drawn i with P_i[y,x] = 1, or -1.  Rows leave the
+ *                                    detection layer in descending score, so the most confident instance owns a contested pixel.
+ *                                    This departs from the reference on purpose: DetectionRenderer.swift:26-41 paints row after row,
+ *                                    so there the LAST — least confident — row covers the others.
+ *   visible_areas (batch, rows)      uint32, may be NULL: the number of pixels of image b whose map value is i.
+ *   detections_src                   written exactly as mrcnn_paste_masks_source writes it.
+ * rows <= 32767 (the map is int16).
+ *
+ * mrcnn_render_detections_source — DetectionRenderer.swift:26-88: the detections drawn over the source images, RGB8 interleaved.
+ *   images[b]                        the source image, as given to mrcnn_maskrcnn_predict_images (read, never written)
+ *   out_rgb + out_offsets[b]         h_b × w_b × 3 bytes.  Row i has colour palette[i % 4], palette = red (255,0,0), blue (0,0,255),
+ *                                    green (0,255,0), yellow (255,255,0) (DetectionRenderer.swift:53).  The stroke of row i, `stroke`
+ *                                    pixels wide, is the part of OUTER that is not in INNER: OUTER = box_i grown by stroke/2 (integer
+ *                                    division) on every side and clipped to the image, INNER = box_i shrunk by stroke - stroke/2 on
+ *                                    every side (stroke = 3, the reference's lineWidth: one pixel outside the box, two inside); an
+ *                                    empty or inverted INNER leaves the whole OUTER; stroke = 0 draws none.  Per pixel and channel c:
+ *                                      under the stroke of a drawn row: the colour of the lowest such row, opaque;
+ *                                      else, map[y,x] >= 0:            (src_c * (256 - alpha) + colour_c * alpha + 128) >> 8
+ *                                                                      (alpha 256 = the reference's opaque fill);
+ *                                      else:                           src_c.
+ *   detections_src                   as above; may be NULL.
+ * alpha in 0..256, stroke in 0..65534.  out_rgb must not overlap the source images.
+ *
+ * Conventions of both, as mrcnn_paste_masks_source: memspace holds for every data pointer (and for the rgb pointers of `images`);
+ * heights, widths, the offsets and the image table are host memory.  Offsets are BYTE offsets, each a multiple of 16; the images'
+ * ranges must not overlap, bytes no image covers are left untouched.  One launch per call for the whole batch, after the box mapping.
+ * Errors (the message names the index of the offending image): null pointer, bad offsets -> MRCNN_ERR_INVALID; a side outside
+ * 1..32767, rows > 32767, alpha or stroke out of range -> MRCNN_ERR_SHAPE; no gfx950 device -> MRCNN_ERR_HIP (no CPU fallback). */
+MRCNN_API int mrcnn_instance_map_source(const float* detections, const float* masks, int batch, int rows, int mask_size,
+                                        const int32_t* heights, const int32_t* widths, int model_h, int model_w, float threshold,
+                                        float min_score, int memspace, float* detections_src, int16_t* map, const int64_t* map_offsets,
+                                        uint32_t* visible_areas);
+MRCNN_API int mrcnn_render_detections_source(const mrcnn_image* images, const float* detections, const float* masks, int batch, int rows,
+                                             int mask_size, int model_h, int model_w, float threshold, float min_score, int alpha, int stroke,
+                                             int memspace, float* detections_src, uint8_t* out_rgb, const int64_t* out_offsets);
 /* Host only, no GPU: COCO's compressed string of one RLE (pycocotools rleToString / rleFrString), not NUL-terminated.  *length / *n is
  * always the size needed; with out / counts = NULL the call only measures, a buffer that is too small gives MRCNN_ERR_SHAPE. */
 MRCNN_API int mrcnn_rle_to_string(const uint32_t* counts, int64_t n, char* out, int64_t capacity, int64_t* length);

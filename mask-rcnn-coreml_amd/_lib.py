@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "mrcnn_maskrcnn_predict_scalefit", "mrcnn_unletterbox_boxes",
     "mrcnn_maskrcnn_predict_images", "mrcnn_paste_masks_source",
     "mrcnn_masks_rle_source", "mrcnn_rle_to_string", "mrcnn_rle_from_string",
+    "mrcnn_instance_map_source", "mrcnn_render_detections_source",
     "mrcnn_rle_iou", "mrcnn_box_iou_xywh", "mrcnn_coco_match", "mrcnn_rle_from_polygons",
 ]
 # declared in include/maskrcnn_hip_test.h (test / measurement entry points of the same library)
@@ -139,6 +140,9 @@ def lib():
     L.mrcnn_maskrcnn_predict_images.argtypes = [vp, C.POINTER(Image), C.c_int, C.c_int, vp, vp]
     L.mrcnn_paste_masks_source.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp]
     L.mrcnn_masks_rle_source.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, C.c_int64, vp, vp, vp]
+    L.mrcnn_instance_map_source.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp, vp, vp]
+    L.mrcnn_render_detections_source.argtypes = [C.POINTER(Image), vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
+                                                 C.c_int, vp, vp, vp]
     L.mrcnn_rle_to_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_from_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_iou.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int64]

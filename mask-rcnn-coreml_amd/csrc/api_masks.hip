@@ -158,6 +158,148 @@ extern "C" int mrcnn_masks_rle_source(const float* detections, const float* mask
     });
 }
 
+// ================================================================================================
+// drawing (DetectionRenderer.swift:13-88): the instance-id map and the rendered overlay
+// ================================================================================================
+// out_offsets of a ragged output with `unit` bytes per pixel, as mrcnn_paste_masks_source checks them: written into geom, the
+// extent of the buffer and the largest h*w returned
+static void ragged_offsets(std::vector<ImageGeom>& geom, const int64_t* offsets, int unit, const char* entry, int64_t& extent, long& max_pixels)
+{
+    const int batch = (int)geom.size();
+    extent = 0; max_pixels = 0;
+    auto bytes_of = [&](const ImageGeom& g) { return (int64_t)unit * g.h * g.w; };
+    for (int b = 0; b < batch; ++b) {
+        ImageGeom& g = geom[(size_t)b];
+        g.offset = offsets[b];
+        MRCNN_REQUIRE(g.offset >= 0 && g.offset % 16 == 0, MRCNN_ERR_INVALID, "image %d of the batch: out_offsets[%d] = %lld is not a non-negative multiple of 16",
+                      b, b, (long long)g.offset);
+        const long pixels = (long)g.h * g.w;
+        max_pixels = pixels > max_pixels ? pixels : max_pixels;
+        extent = g.offset + bytes_of(g) > extent ? g.offset + bytes_of(g) : extent;
+    }
+    for (int a = 0; a < batch; ++a)
+        for (int b = a + 1; b < batch; ++b) {
+            const int64_t a0 = geom[(size_t)a].offset, a1 = a0 + bytes_of(geom[(size_t)a]);
+            const int64_t b0 = geom[(size_t)b].offset, b1 = b0 + bytes_of(geom[(size_t)b]);
+            MRCNN_REQUIRE(a1 <= b0 || b1 <= a0, MRCNN_ERR_INVALID, "%s: images %d and %d overlap in the output", entry, a, b);
+        }
+}
+
+extern "C" int mrcnn_instance_map_source(const float* detections, const float* masks, int batch, int rows, int mask_size,
+                                         const int32_t* heights, const int32_t* widths, int model_h, int model_w, float threshold,
+                                         float min_score, int memspace, float* detections_src, int16_t* map, const int64_t* map_offsets,
+                                         uint32_t* visible_areas)
+{
+    return guarded([&] {
+        require_gpu();
+        MRCNN_REQUIRE(detections && masks && heights && widths && detections_src && map && map_offsets, MRCNN_ERR_INVALID, "null instance_map_source argument");
+        MRCNN_REQUIRE(batch >= 0 && rows >= 0 && mask_size >= 2 && model_h > 0 && model_w > 0, MRCNN_ERR_INVALID, "bad instance_map_source argument");
+        MRCNN_REQUIRE(rows <= 32767, MRCNN_ERR_SHAPE, "instance_map_source: %d rows do not fit the int16 map (at most 32767)", rows);
+        MRCNN_REQUIRE((long)batch * rows < (1L << 31), MRCNN_ERR_SHAPE, "instance_map_source: %d x %d rows are too many", batch, rows);
+        MRCNN_REQUIRE(reinterpret_cast<uintptr_t>(map) % 2 == 0, MRCNN_ERR_INVALID, "instance_map_source: map is not aligned for int16");
+        if (batch == 0) return;
+        std::vector<ImageGeom> geom = image_geometry(heights, widths, batch, model_h, model_w);
+        int64_t extent = 0;
+        long max_pixels = 0;
+        ragged_offsets(geom, map_offsets, 2, "instance_map_source", extent, max_pixels);
+        const bool dev = memspace == MRCNN_DEVICE;
+        Stream st;
+        DevBuf td, tm, ts, to, tv, tt;
+        const size_t n = (size_t)batch * rows;
+        const float* d = stage_rows(detections, memspace, (long)n, 6, 6, td);
+        const float* m = stage_rows(masks, memspace, (long)n, (long)mask_size * mask_size, (long)mask_size * mask_size, tm);
+        float* ds = detections_src;
+        uint8_t* o = reinterpret_cast<uint8_t*>(map);
+        uint32_t* va = visible_areas;
+        if (!dev) {
+            ts.alloc((n ? n : 1) * 6 * sizeof(float)); ds = ts.as<float>();
+            to.alloc((size_t)extent); o = to.as<uint8_t>();     // (same offsets as the caller's buffer: only the maps are copied back)
+            if (visible_areas) { tv.alloc((n ? n : 1) * sizeof(uint32_t)); va = tv.as<uint32_t>(); }
+        }
+        // one scratch allocation: the geometry table | the pixel boxes
+        const size_t o_box = ((size_t)batch * sizeof(ImageGeom) + 15) / 16 * 16;
+        tt.alloc(o_box + (n ? n : 1) * sizeof(int4));
+        HIP_CHECK(hipMemcpy(tt.p, geom.data(), (size_t)batch * sizeof(ImageGeom), hipMemcpyHostToDevice));
+        instance_map_forward(st.s, d, m, tt.as<ImageGeom>(), batch, rows, mask_size, model_h, model_w, max_pixels, threshold, min_score, ds,
+                             reinterpret_cast<int4*>(tt.as<char>() + o_box), reinterpret_cast<int16_t*>(o), va);
+        HIP_CHECK(hipStreamSynchronize(st.s));
+        if (!dev) {
+            if (n) HIP_CHECK(hipMemcpy(detections_src, ts.p, n * 6 * sizeof(float), hipMemcpyDeviceToHost));
+            if (visible_areas && n) HIP_CHECK(hipMemcpy(visible_areas, tv.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            for (int b = 0; b < batch; ++b) {
+                const ImageGeom& g = geom[(size_t)b];
+                HIP_CHECK(hipMemcpy(reinterpret_cast<uint8_t*>(map) + g.offset, to.as<uint8_t>() + g.offset, (size_t)2 * g.h * g.w, hipMemcpyDeviceToHost));
+            }
+        }
+    });
+}
+
+extern "C" int mrcnn_render_detections_source(const mrcnn_image* images, const float* detections, const float* masks, int batch, int rows,
+                                              int mask_size, int model_h, int model_w, float threshold, float min_score, int alpha, int stroke,
+                                              int memspace, float* detections_src, uint8_t* out_rgb, const int64_t* out_offsets)
+{
+    return guarded([&] {
+        require_gpu();
+        MRCNN_REQUIRE(images && detections && masks && out_rgb && out_offsets, MRCNN_ERR_INVALID, "null render_detections_source argument");
+        MRCNN_REQUIRE(batch >= 0 && rows >= 0 && mask_size >= 2 && model_h > 0 && model_w > 0, MRCNN_ERR_INVALID, "bad render_detections_source argument");
+        MRCNN_REQUIRE(rows <= 32767, MRCNN_ERR_SHAPE, "render_detections_source: %d rows are too many (at most 32767)", rows);
+        MRCNN_REQUIRE((long)batch * rows < (1L << 31), MRCNN_ERR_SHAPE, "render_detections_source: %d x %d rows are too many", batch, rows);
+        MRCNN_REQUIRE(alpha >= 0 && alpha <= 256, MRCNN_ERR_SHAPE, "render_detections_source: alpha %d outside 0..256", alpha);
+        MRCNN_REQUIRE(stroke >= 0 && stroke <= 65534, MRCNN_ERR_SHAPE, "render_detections_source: stroke %d outside 0..65534", stroke);
+        if (batch == 0) return;
+        std::vector<int32_t> hs((size_t)batch), ws((size_t)batch);
+        for (int b = 0; b < batch; ++b) {
+            MRCNN_REQUIRE(images[b].rgb, MRCNN_ERR_INVALID, "image %d of the batch has a null rgb pointer", b);
+            hs[(size_t)b] = images[b].height; ws[(size_t)b] = images[b].width;
+        }
+        std::vector<ImageGeom> geom = image_geometry(hs.data(), ws.data(), batch, model_h, model_w);
+        int64_t extent = 0;
+        long max_pixels = 0;
+        ragged_offsets(geom, out_offsets, 3, "render_detections_source", extent, max_pixels);
+        const bool dev = memspace == MRCNN_DEVICE;
+        Stream st;
+        DevBuf td, tm, ts, to, ti, tt;
+        const size_t n = (size_t)batch * rows;
+        const float* d = stage_rows(detections, memspace, (long)n, 6, 6, td);
+        const float* m = stage_rows(masks, memspace, (long)n, (long)mask_size * mask_size, (long)mask_size * mask_size, tm);
+        float* ds = detections_src;
+        uint8_t* o = out_rgb;
+        std::vector<const uint8_t*> srcs((size_t)batch);
+        if (!dev || !detections_src) { ts.alloc((n ? n : 1) * 6 * sizeof(float)); ds = ts.as<float>(); }
+        if (!dev) {
+            to.alloc((size_t)extent); o = to.as<uint8_t>();
+            size_t total = 0;                                           // the sources back to back, each from a 16-byte boundary
+            for (int b = 0; b < batch; ++b) total += ((size_t)3 * geom[(size_t)b].h * geom[(size_t)b].w + 15) / 16 * 16;
+            ti.alloc(total);
+            size_t at = 0;
+            for (int b = 0; b < batch; ++b) {
+                const size_t bytes = (size_t)3 * geom[(size_t)b].h * geom[(size_t)b].w;
+                HIP_CHECK(hipMemcpy(ti.as<uint8_t>() + at, images[b].rgb, bytes, hipMemcpyHostToDevice));
+                srcs[(size_t)b] = ti.as<uint8_t>() + at;
+                at += (bytes + 15) / 16 * 16;
+            }
+        } else {
+            for (int b = 0; b < batch; ++b) srcs[(size_t)b] = images[b].rgb;
+        }
+        // one scratch allocation: the geometry table | the source pointers | the pixel boxes
+        auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
+        const size_t o_src = up16((size_t)batch * sizeof(ImageGeom)), o_box = o_src + up16((size_t)batch * sizeof(const uint8_t*));
+        tt.alloc(o_box + (n ? n : 1) * sizeof(int4));
+        HIP_CHECK(hipMemcpy(tt.p, geom.data(), (size_t)batch * sizeof(ImageGeom), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(tt.as<char>() + o_src, srcs.data(), (size_t)batch * sizeof(const uint8_t*), hipMemcpyHostToDevice));
+        render_detections_forward(st.s, d, m, tt.as<ImageGeom>(), reinterpret_cast<const uint8_t* const*>(tt.as<char>() + o_src), batch, rows, mask_size,
+                                  model_h, model_w, max_pixels, threshold, min_score, alpha, stroke, ds, reinterpret_cast<int4*>(tt.as<char>() + o_box), o);
+        HIP_CHECK(hipStreamSynchronize(st.s));
+        if (!dev) {
+            if (detections_src && n) HIP_CHECK(hipMemcpy(detections_src, ts.p, n * 6 * sizeof(float), hipMemcpyDeviceToHost));
+            for (int b = 0; b < batch; ++b) {
+                const ImageGeom& g = geom[(size_t)b];
+                HIP_CHECK(hipMemcpy(out_rgb + g.offset, to.as<uint8_t>() + g.offset, (size_t)3 * g.h * g.w, hipMemcpyDeviceToHost));
+            }
+        }
+    });
+}
+
 // COCO's compressed RLE string (pycocotools maskApi.c: rleToString / rleFrString) — host arithmetic, no GPU.  Counts from the fourth
 // on go out as their difference to the count two places before; a value is written in 5-bit groups, low group first, 0x20 = more
 // follows (until the rest is only the sign extension of the group's bit 0x10), character = group + 48.

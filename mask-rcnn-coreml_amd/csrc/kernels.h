@@ -109,6 +109,22 @@ void masks_rle_count_forward(hipStream_t s, const float* det, const float* masks
                              int32_t* bboxes);
 void masks_rle_write_forward(hipStream_t s, const float* masks, const ImageGeom* tab, int batch, int rows, int S, float thr, const int4* boxes,
                              const RleSeg* segs, const long long* run_offsets, uint32_t* counts);
+// The box-mapping launch the three entries above start with, on its own: det → det_src and the pixel boxes (batch * rows int4).
+void unletterbox_boxes_forward(hipStream_t s, const float* det, const ImageGeom* tab, int batch, int rows, int H, int W, float* det_src, int4* boxes);
+
+// ================================================================================================
+// Drawing (kernels_render.hip; DetectionRenderer.swift:13-88): one launch per entry for the whole ragged batch, after the box mapping
+// ================================================================================================
+// Instance-id map: entry b of `tab` says where image b's h×w int16 start in `map` (byte offset).  map[y,x] = the lowest row with
+// score > min_score whose pasted plane is set there, -1 for none; visible (batch * rows, may be nullptr) = the pixels each row owns.
+// max_pixels = the largest h*w of the batch (sizes the grid).  det_src and boxes as in paste_masks_source_forward.
+void instance_map_forward(hipStream_t s, const float* det, const float* masks, const ImageGeom* tab, int batch, int rows, int S, int H, int W,
+                          long max_pixels, float thr, float min_score, float* det_src, int4* boxes, int16_t* map, uint32_t* visible);
+// Rendered overlay: srcs[b] = image b's RGB8 source (a device table of device pointers), tab[b].offset = where its h×w×3 bytes start in
+// `out`.  Stroke ring of the lowest drawn row opaque, else the fill of the lowest drawn row blended with alpha/256, else the source.
+void render_detections_forward(hipStream_t s, const float* det, const float* masks, const ImageGeom* tab, const uint8_t* const* srcs, int batch,
+                               int rows, int S, int H, int W, long max_pixels, float thr, float min_score, int alpha, int stroke, float* det_src,
+                               int4* boxes, uint8_t* out);
 
 // ================================================================================================
 // Convolution family + element-wise helpers (kernels_conv.hip)

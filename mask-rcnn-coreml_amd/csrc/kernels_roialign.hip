@@ -14,6 +14,7 @@
 // in HBM (no staging copy at all).  Compiled with -ffp-contract=off.
 #include "device_math.h"
 #include "kernels.h"
+#include "paste_device.h"
 
 namespace mrcnn {
 
@@ -346,56 +347,7 @@ __global__ __launch_bounds__(256) void k_unletterbox_boxes(const float* __restri
     boxes[i] = empty ? make_int4(0, 0, 0, 0) : make_int4(by1, bx1, by2, bx2);
 }
 
-// One axis of the paste's bilinear sample (the set-up k_paste_masks does per y and per x): pixel i of a box that starts at `lo`,
-// scale = S / the box's extent → the two mask cells it mixes and the weight of the second.  Shared by the paste and the RLE kernels:
-// the same float operations in the same order (-ffp-contract=off), so both see the same bits.
-struct PasteTap { int a, b; float f; };
-__device__ __forceinline__ PasteTap paste_tap(int i, int lo, float scale, int S)
-{
-    float s = ((float)(i - lo) + 0.5f) * scale - 0.5f;
-    s = fminf(fmaxf(s, 0.0f), (float)(S - 1));
-    PasteTap t;
-    t.a = (int)floorf(s); t.b = min(t.a + 1, S - 1);
-    t.f = s - (float)t.a;
-    return t;
-}
-// the sample itself: a, b = the upper mask row at the two columns, c, dd = the lower one
-__device__ __forceinline__ float paste_lerp(float a, float b, float c, float dd, float fx, float fy)
-{
-    const float top = a + (b - a) * fx;
-    const float bot = c + (dd - c) * fx;
-    return top + (bot - top) * fy;
-}
-
-// the pixels of one row of one instance plane: what k_paste_masks derives from (instance, y) before its x loop
-struct PasteRow {
-    const float *ra, *rb;      // the two mask rows the bilinear sample mixes
-    float fy, sx_scale;
-    int x1, x2;                // columns outside [x1, x2) are 0; x1 = x2 = 0: nothing on this row
-};
-__device__ __forceinline__ PasteRow paste_row(const int4* __restrict__ boxes, const float* __restrict__ masks, int S, int inst, int y)
-{
-    PasteRow r;
-    const int4 bx = boxes[inst];           // (y1, x1, y2, x2)
-    r.x1 = r.x2 = 0; r.ra = r.rb = masks; r.fy = 0.f; r.sx_scale = 0.f;
-    if (y >= bx.x && y < bx.z) {           // (an empty box is (0,0,0,0): no y passes)
-        const float* m = masks + (size_t)inst * S * S;
-        const PasteTap ty = paste_tap(y, bx.x, (float)S / (float)(bx.z - bx.x), S);
-        r.fy = ty.f;
-        r.ra = m + ty.a * S; r.rb = m + ty.b * S;
-        r.sx_scale = (float)S / (float)(bx.w - bx.y);
-        r.x1 = bx.y; r.x2 = bx.w;
-    }
-    return r;
-}
-__device__ __forceinline__ uint32_t paste_pixel(const PasteRow& r, int S, int x, float thr)
-{
-    if (x < r.x1 || x >= r.x2) return 0u;
-    const PasteTap tx = paste_tap(x, r.x1, r.sx_scale, S);
-    const float v = paste_lerp(r.ra[tx.a], r.ra[tx.b], r.rb[tx.a], r.rb[tx.b], tx.f, r.fy);
-    return v >= thr ? 1u : 0u;
-}
-
+// (paste_tap / paste_lerp / paste_row / paste_pixel — the per-pixel arithmetic — live in paste_device.h, shared with kernels_render.hip)
 __global__ __launch_bounds__(256) void k_paste_masks_ragged(const ImageGeom* __restrict__ tab, const int4* __restrict__ boxes,
                                                             const float* __restrict__ masks, int rows, int S, float thr, uint8_t* __restrict__ out)
 {
@@ -442,13 +394,19 @@ __global__ __launch_bounds__(256) void k_paste_masks_ragged(const ImageGeom* __r
     }
 }
 
+void unletterbox_boxes_forward(hipStream_t s, const float* det, const ImageGeom* tab, int batch, int rows, int H, int W, float* det_src, int4* boxes)
+{
+    const int total = batch * rows;
+    if (total <= 0) return;
+    hipLaunchKernelGGL(k_unletterbox_boxes, dim3((total + 255) / 256), dim3(256), 0, s, det, tab, rows, total, H, W, det_src, boxes);
+    HIP_CHECK(hipGetLastError());
+}
+
 void paste_masks_source_forward(hipStream_t s, const float* det, const float* masks, const ImageGeom* tab, int batch, int rows, int S,
                                 int H, int W, long max_bytes, float thr, float* det_src, int4* boxes, uint8_t* out)
 {
     if (batch <= 0 || rows <= 0) return;
-    const int total = batch * rows;
-    hipLaunchKernelGGL(k_unletterbox_boxes, dim3((total + 255) / 256), dim3(256), 0, s, det, tab, rows, total, H, W, det_src, boxes);
-    HIP_CHECK(hipGetLastError());
+    unletterbox_boxes_forward(s, det, tab, batch, rows, H, W, det_src, boxes);
     const long blocks = (max_bytes / 16 + 255) / 256;
     const int gx = (int)(blocks < 1 ? 1 : (blocks < 4096 ? blocks : 4096));
     hipLaunchKernelGGL(k_paste_masks_ragged, dim3(gx, batch), dim3(256), 0, s, tab, boxes, masks, rows, S, thr, out);

@@ -155,3 +155,88 @@ def masks_rle_source(detections, masks, sizes, model_h: int, model_w: int, thres
     rles = [[{"size": [int(hs[b]), int(ws[b])], "counts": host[int(offsets[b * rows + i]):int(offsets[b * rows + i + 1])]}
              for i in range(rows)] for b in range(B)]
     return det_src, rles, areas, bboxes
+
+
+def _ragged_layout(hs, ws, unit):
+    """Byte offsets of a ragged output with ``unit`` bytes per pixel: every image starts on a 16-byte boundary."""
+    nbytes = unit * hs.astype(np.int64) * ws.astype(np.int64)
+    padded = (nbytes + 15) // 16 * 16
+    offs = np.concatenate(([0], np.cumsum(padded)[:-1])).astype(np.int64) if len(hs) else np.zeros(0, np.int64)
+    return nbytes, offs, int(padded.sum())
+
+
+def _batch_inputs(name, detections, masks, B_expected):
+    """(on_host, det, masks, B, rows, ptr): numpy arrays made contiguous float32, or contiguous float32 CUDA tensors used in place."""
+    on_host = isinstance(detections, np.ndarray)
+    if on_host:
+        det = np.ascontiguousarray(detections, dtype=np.float32)
+        m = np.ascontiguousarray(masks, dtype=np.float32)
+        ptr = lambda a: a.ctypes.data
+    else:
+        import torch
+        det, m = detections, masks
+        assert det.is_cuda and m.is_cuda and det.dtype == torch.float32 and m.dtype == torch.float32 and det.is_contiguous() and m.is_contiguous()
+        ptr = lambda a: a.data_ptr()
+    if det.ndim != 3 or m.ndim != 4 or det.shape[2] != 6 or m.shape[0] != det.shape[0] or m.shape[1] != det.shape[1] or B_expected != det.shape[0]:
+        raise ValueError(f"{name}: detections (B,rows,6), masks (B,rows,S,S) and B images / sizes expected")
+    return on_host, det, m, int(det.shape[0]), int(det.shape[1]), ptr
+
+
+def instance_map_source(detections, masks, sizes, model_h: int, model_w: int, threshold: float = 0.5, min_score: float = 0.0):
+    """Which detection owns a pixel (``mrcnn_instance_map_source``): for a batch of images of sizes ``sizes`` = [(h_b, w_b)] returns
+    (det_src, [ (h_b, w_b) int16 per image ], visible (B, rows) uint32).  ``map[y, x]`` is the lowest row with score > min_score whose
+    pasted mask (``paste_masks_source`` at ``threshold``) is set at the pixel, -1 where there is none; ``visible[b, i]`` counts the
+    pixels row i owns.  The planes are never pasted.  numpy in → numpy out; torch CUDA tensors in → the device buffers are used in
+    place and torch tensors come back (visible as int32)."""
+    sizes = list(sizes)
+    on_host, det, m, B, rows, ptr = _batch_inputs("instance_map_source", detections, masks, len(sizes))
+    hs = np.array([int(s[0]) for s in sizes], dtype=np.int32)
+    ws = np.array([int(s[1]) for s in sizes], dtype=np.int32)
+    nbytes, offs, total = _ragged_layout(hs, ws, 2)
+    if on_host:
+        det_src, out, visible = np.empty_like(det), np.empty(max(1, total // 2), np.int16), np.zeros((B, rows), np.uint32)
+    else:
+        import torch
+        det_src = torch.empty_like(det)
+        out = torch.empty(max(1, total // 2), dtype=torch.int16, device=det.device)
+        visible = torch.zeros((B, rows), dtype=torch.int32, device=det.device)
+    _lib.check(_lib.lib().mrcnn_instance_map_source(ptr(det), ptr(m), B, rows, int(m.shape[2]), hs.ctypes.data, ws.ctypes.data, model_h, model_w,
+                                                    C.c_float(threshold), C.c_float(min_score), _lib.HOST if on_host else _lib.DEVICE,
+                                                    ptr(det_src), ptr(out), offs.ctypes.data, ptr(visible)))
+    maps = [out[int(offs[b]) // 2:int(offs[b] + nbytes[b]) // 2].reshape(int(hs[b]), int(ws[b])) for b in range(B)]
+    return det_src, maps, visible
+
+
+def render_detections_source(images, detections, masks, model_h: int, model_w: int, threshold: float = 0.5, min_score: float = 0.7,
+                             alpha: int = 128, stroke: int = 3):
+    """The detections drawn over their source images (``mrcnn_render_detections_source``; DetectionRenderer.swift:26-88): a list of
+    (h_b, w_b, 3) uint8 images and the (det, mask) ``MaskRCNN.predict_images`` returned for them → [ (h_b, w_b, 3) uint8 ].  Rows with
+    score > min_score (0.7: the cut Detection.swift:38 applies before drawing) are drawn in palette[i % 4] = red, blue, green, yellow:
+    the box stroked ``stroke`` pixels wide, opaque, the mask blended in with ``alpha``/256 (256 = the reference's opaque fill); the
+    lowest row wins a contested pixel.  numpy in → numpy out; torch CUDA tensors in → used in place, torch tensors returned."""
+    images = list(images)
+    on_host, det, m, B, rows, ptr = _batch_inputs("render_detections_source", detections, masks, len(images))
+    table = (_lib.Image * max(1, B))()
+    keep = []
+    for b, im in enumerate(images):
+        if on_host:
+            im = np.ascontiguousarray(im, dtype=np.uint8)
+        else:
+            import torch
+            assert im.is_cuda and im.dtype == torch.uint8 and im.is_contiguous()
+        if im.ndim != 3 or im.shape[2] != 3:
+            raise ValueError(f"image {b} has shape {tuple(im.shape)}, expected (h, w, 3)")
+        keep.append(im)
+        table[b].rgb, table[b].height, table[b].width = ptr(im), int(im.shape[0]), int(im.shape[1])
+    hs = np.array([int(im.shape[0]) for im in keep], dtype=np.int32)
+    ws = np.array([int(im.shape[1]) for im in keep], dtype=np.int32)
+    nbytes, offs, total = _ragged_layout(hs, ws, 3)
+    if on_host:
+        out = np.empty(max(1, total), np.uint8)
+    else:
+        import torch
+        out = torch.empty(max(1, total), dtype=torch.uint8, device=det.device)
+    _lib.check(_lib.lib().mrcnn_render_detections_source(table, ptr(det), ptr(m), B, rows, int(m.shape[2]), model_h, model_w, C.c_float(threshold),
+                                                         C.c_float(min_score), int(alpha), int(stroke), _lib.HOST if on_host else _lib.DEVICE,
+                                                         None, ptr(out), offs.ctypes.data))
+    return [out[int(offs[b]):int(offs[b] + nbytes[b])].reshape(int(hs[b]), int(ws[b]), 3) for b in range(B)]

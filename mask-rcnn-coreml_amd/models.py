@@ -150,6 +150,15 @@ class MaskRCNN(_Model):
             _lib.check(_lib.lib().mrcnn_maskrcnn_predict_images(self._h, table, B, _lib.DEVICE, det.data_ptr(), mask.data_ptr()))
         return det, mask
 
+    def render_images(self, images, **kw):
+        """predict_images followed by detection.render_detections_source at this handle's model size: the images with their
+        detections drawn on them (DetectionRenderer.swift:26-88).  Keyword arguments go to the render (threshold, min_score, alpha,
+        stroke).  A convenience: no device work of its own."""
+        from .detection import render_detections_source
+        images = list(images)
+        det, mask = self.predict_images(images)
+        return render_detections_source(images, det, mask, self.image_height, self.image_width, **kw)
+
     def predict_into(self, images, det, mask, sync: bool = True):
         """Device tensors in, pre-allocated device tensors out (bench loop: no allocation, optional no sync)."""
         B, H, W, _ = images.shape

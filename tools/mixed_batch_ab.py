@@ -36,7 +36,20 @@
       A's and B's intersections are compared once, outside the timing.  min / median / max go to the JSON file ("score").  Under
       `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/mixed_batch_ab.py --score`, then
   mixed_batch_ab.py --digest-score DIR
-      adds the µs of k_rle_prefix / k_rle_iou / k_coco_match ("score_kernels")."""
+      adds the µs of k_rle_prefix / k_rle_iou / k_coco_match ("score_kernels").
+  mixed_batch_ab.py --render [--steps 20] [--warmup 5]
+      What it costs to LOOK at the detections of batch 8 x 100 rows at the eight sizes (smooth blobs, every row drawn: min_score 0),
+      detections, masks and source images resident on the device, the legs interleaved in one process after a warm-up:
+        A_map     what the library could do before: mrcnn_paste_masks_source on device buffers, then per image the first set plane
+                  per pixel in torch on the device (argmax over the planes, -1 where none is set)
+        B_map     mrcnn_instance_map_source (with visible_areas)
+        A_render  A_map, then the palette colour gathered per pixel and blended into the source in torch; no strokes, which favours A
+        B_render  mrcnn_render_detections_source, alpha 128, stroke 3
+      A's and B's maps, and A's picture and B's at stroke 0, are compared once outside the timing.  min / median / max go to the JSON
+      file ("render").  Under `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/mixed_batch_ab.py --render`, then
+  mixed_batch_ab.py --digest-render DIR
+      adds the µs of k_instance_map / k_render_detections beside k_paste_masks_ragged's and their GB/s of algorithmic bytes
+      ("render_kernels")."""
 import argparse, csv, ctypes as C, glob, importlib, json, os, subprocess, sys, tempfile, time
 
 import numpy as np
@@ -341,6 +354,114 @@ def run_score(args):
                                                            warmup=args.warmup)})
 
 
+def run_render(args):
+    import torch
+    lib = importlib.import_module("mask-rcnn-coreml_amd._lib")
+    L = lib.lib()
+    rng = np.random.default_rng(9)
+    B = len(SIZES)
+    det, _ = synthetic_records(B, rng)
+    det[..., 5] = -np.sort(-det[..., 5], axis=1)                            # rows leave the detection layer in descending score
+    masks = smooth_masks(B, rng)
+    hs = np.array([s[0] for s in SIZES], np.int32); ws = np.array([s[1] for s in SIZES], np.int32)
+    pixels = hs.astype(np.int64) * ws
+
+    def layout(unit):
+        padded = (unit * pixels + 15) // 16 * 16
+        return np.concatenate(([0], np.cumsum(padded)[:-1])).astype(np.int64), int(padded.sum())
+    p_offs, p_total = layout(ROWS); m_offs, m_total = layout(2); r_offs, r_total = layout(3)
+    det_g, masks_g = torch.from_numpy(det).cuda(), torch.from_numpy(masks).cuda()
+    src_g = torch.empty_like(det_g)
+    images = [torch.from_numpy(rng.integers(0, 256, (h, w, 3), dtype=np.uint8)).cuda() for h, w in SIZES]
+    table = (lib.Image * B)()
+    for b, t in enumerate(images):
+        table[b].rgb, table[b].height, table[b].width = t.data_ptr(), SIZES[b][0], SIZES[b][1]
+    planes_g = torch.empty(p_total, dtype=torch.uint8, device="cuda")
+    map_g = torch.empty(m_total // 2, dtype=torch.int16, device="cuda")
+    vis_g = torch.empty(B * ROWS, dtype=torch.int32, device="cuda")
+    rgb_g = torch.empty(r_total, dtype=torch.uint8, device="cuda")
+    palette = torch.tensor([[255, 0, 0], [0, 0, 255], [0, 255, 0], [255, 255, 0]], dtype=torch.int32, device="cuda")
+    a_maps, a_rgb = [None] * B, [None] * B
+
+    def a_map():
+        lib.check(L.mrcnn_paste_masks_source(det_g.data_ptr(), masks_g.data_ptr(), B, ROWS, 28, hs.ctypes.data, ws.ctypes.data, 1024, 1024,
+                                             C.c_float(0.5), lib.DEVICE, src_g.data_ptr(), planes_g.data_ptr(), p_offs.ctypes.data))
+        for b, (h, w) in enumerate(SIZES):
+            p = planes_g[int(p_offs[b]):int(p_offs[b]) + ROWS * h * w].view(ROWS, h, w)
+            top, idx = p.max(0)                                             # (the first of several maxima: the lowest set plane)
+            a_maps[b] = torch.where(top > 0, idx, -1).to(torch.int16)
+
+    def leg_a_map():
+        a_map()
+        torch.cuda.synchronize()
+
+    def leg_a_render():
+        a_map()
+        for b in range(B):
+            m = a_maps[b].to(torch.int64)
+            col = palette[m % 4]
+            s = images[b].to(torch.int32)
+            a_rgb[b] = torch.where((m >= 0)[..., None], (s * 128 + col * 128 + 128) >> 8, s).to(torch.uint8)
+        torch.cuda.synchronize()
+
+    def leg_b_map():
+        lib.check(L.mrcnn_instance_map_source(det_g.data_ptr(), masks_g.data_ptr(), B, ROWS, 28, hs.ctypes.data, ws.ctypes.data, 1024, 1024, C.c_float(0.5),
+                                              C.c_float(0.0), lib.DEVICE, src_g.data_ptr(), map_g.data_ptr(), m_offs.ctypes.data, vis_g.data_ptr()))
+
+    def b_render(stroke):
+        lib.check(L.mrcnn_render_detections_source(table, det_g.data_ptr(), masks_g.data_ptr(), B, ROWS, 28, 1024, 1024, C.c_float(0.5), C.c_float(0.0), 128,
+                                                   stroke, lib.DEVICE, src_g.data_ptr(), rgb_g.data_ptr(), r_offs.ctypes.data))
+    legs = {"A_map": leg_a_map, "B_map": leg_b_map, "A_render": leg_a_render, "B_render": lambda: b_render(3)}
+    times = {k: [] for k in legs}
+    for step in range(args.warmup + args.steps):
+        for k, leg in legs.items():
+            t0 = time.perf_counter()
+            leg()
+            if step >= args.warmup:
+                times[k].append(time.perf_counter() - t0)
+    b_render(0)
+    maps_equal = rgb_equal = True
+    for b, (h, w) in enumerate(SIZES):
+        maps_equal &= bool(torch.equal(a_maps[b], map_g[int(m_offs[b]) // 2:int(m_offs[b]) // 2 + h * w].view(h, w)))
+        rgb_equal &= bool(torch.equal(a_rgb[b], rgb_g[int(r_offs[b]):int(r_offs[b]) + 3 * h * w].view(h, w, 3)))
+    b_render(3)                                                             # (leave the real picture behind, and one more launch for the trace)
+
+    def ms(ts):
+        ts = sorted(ts)
+        return {"min": ts[0] * 1e3, "median": ts[len(ts) // 2] * 1e3, "max": ts[-1] * 1e3}
+    rec = {k: {"ms": ms(v)} for k, v in times.items()}
+    for kind in ("map", "render"):
+        a = rec["A_" + kind]["ms"]
+        rec[f"A_{kind}_spread_ms"] = a["max"] - a["min"]
+        rec[f"B_{kind}_below_A_by_more_than_A_spread"] = bool(a["median"] - rec["B_" + kind]["ms"]["median"] > a["max"] - a["min"])
+    rec["maps_equal"], rec["pictures_equal_at_stroke_0"] = maps_equal, rgb_equal
+    rec["A_map"]["plane_bytes"] = int(ROWS * pixels.sum())
+    rec["B_map"]["bytes_written"] = int(2 * pixels.sum())
+    rec["B_render"]["bytes_read_and_written"] = int(6 * pixels.sum())
+    rec["visible_pixels"] = int(vis_g.sum().item())
+    merge(args.out, {"git_head": git_head(), "render": dict(rec, rows=ROWS, sizes_hw=SIZES, steps=args.steps, warmup=args.warmup, masks="smooth", min_score=0.0)})
+
+
+def run_digest_render(args):
+    rows = []
+    for f in glob.glob(os.path.join(args.digest_render, "**", "*kernel_trace.csv"), recursive=True):
+        rows += list(csv.DictReader(open(f)))
+    us = lambda r: (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
+    pixels = sum(h * w for h, w in SIZES)
+    algo = {"k_paste_masks_ragged": ROWS * pixels, "k_instance_map": 2 * pixels, "k_render_detections": 6 * pixels}
+
+    def stat(name):
+        v = sorted(us(r) for r in rows if name in r["Kernel_Name"])
+        if not v:
+            return {"launches": 0}
+        rec = {"launches": len(v), "us": {"min": v[0], "median": v[len(v) // 2], "max": v[-1]}}
+        if name in algo:
+            rec["algorithmic_bytes"] = algo[name]
+            rec["gb_per_s_at_median"] = algo[name] / v[len(v) // 2] / 1e3
+        return rec
+    merge(args.out, {"render_kernels": {k: stat(k) for k in ("k_unletterbox_boxes", "k_paste_masks_ragged", "k_instance_map", "k_render_detections")}})
+
+
 def run_digest_score(args):
     rows = []
     for f in glob.glob(os.path.join(args.digest_score, "**", "*kernel_trace.csv"), recursive=True):
@@ -407,9 +528,15 @@ if __name__ == "__main__":
     ap.add_argument("--digest-rle", metavar="DIR")
     ap.add_argument("--score", action="store_true")
     ap.add_argument("--digest-score", metavar="DIR")
+    ap.add_argument("--render", action="store_true")
+    ap.add_argument("--digest-render", metavar="DIR")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mixed_batch_ab.json"))
     a = ap.parse_args()
-    if a.digest_score:
+    if a.digest_render:
+        run_digest_render(a)
+    elif a.render:
+        run_render(a)
+    elif a.digest_score:
         run_digest_score(a)
     elif a.score:
         run_score(a)
