@@ -573,6 +573,26 @@ MRCNN_API int mrcnn_coco_match(const double* iou, int64_t n_iou, int memspace, c
  * or of no area still gives a valid RLE (its crossings cancel in pairs). */
 MRCNN_API int mrcnn_rle_from_polygons(const double* xy, const int64_t* poly_offsets, int n_polys, int h, int w, uint32_t* counts,
                                       int64_t capacity, int64_t* n);
+/* The same for a whole annotation file in one call, on the GPU.  xy / poly_offsets as above (all points; polygon p = the points
+ * [poly_offsets[p], poly_offsets[p+1])); annotation k = the polygons [ann_offsets[k], ann_offsets[k+1]) on the heights[k] x widths[k]
+ * plane of its image.  RLE k is, word for word, what mrcnn_rle_from_polygons returns for annotation k's polygons on that plane — that
+ * function is the definition; an annotation without a polygon is the single run [h*w].  The result is an RLE set in the layout and
+ * with the capacity protocol of mrcnn_masks_rle_source, ready for mrcnn_rle_iou:
+ *   counts + run_offsets[k] .. counts + run_offsets[k+1]   the run lengths of annotation k (all annotations back to back)
+ *   run_offsets (n_anns + 1), areas (n_anns: the set pixels = the sum of the odd runs) and bboxes_xywh (n_anns*4: the tight box x, y, w,
+ *   h of the set pixels, 0,0,0,0 for none) are ALWAYS written; areas / bboxes_xywh may be NULL.
+ * If run_offsets[n_anns] > capacity the call returns MRCNN_ERR_SHAPE, the message names the capacity needed and counts is not written
+ * (capacity = 0 with counts = NULL is the size query).  memspace holds for counts, run_offsets, areas and bboxes_xywh; xy, poly_offsets,
+ * ann_offsets, heights and widths are host arrays.  With MRCNN_HOST only the used part of counts is copied.
+ * An annotation crossing at most MRCNN_POLY_LDS_TOGGLES pixel-column centres with its outlines is sorted in LDS, one with more in global
+ * memory; there is no size limit beyond that of mrcnn_rle_from_polygons, and the number of launches does not depend on n_anns.
+ * Errors (the message names the annotation, and the polygon inside it): null pointer, decreasing offsets -> MRCNN_ERR_INVALID; a side
+ * outside 1..32767 -> MRCNN_ERR_SHAPE; a coordinate that is not finite or has |c| >= 1e6 -> MRCNN_ERR_INVALID; all of these before the
+ * device is touched.  No gfx950 device -> MRCNN_ERR_HIP (no CPU fallback). */
+#define MRCNN_POLY_LDS_TOGGLES 4096
+MRCNN_API int mrcnn_rle_from_polygons_batch(const double* xy, const int64_t* poly_offsets, const int64_t* ann_offsets, int64_t n_anns,
+                                            const int32_t* heights, const int32_t* widths, int memspace, uint32_t* counts, int64_t capacity,
+                                            int64_t* run_offsets, uint32_t* areas, int32_t* bboxes_xywh);
 
 #ifdef __cplusplus
 }

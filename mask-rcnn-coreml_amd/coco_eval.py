@@ -42,6 +42,61 @@ def rle_from_polygons(polygons: Sequence[Sequence[float]], h: int, w: int) -> np
     return out
 
 
+LDS_TOGGLES = 4096     # MRCNN_POLY_LDS_TOGGLES: an annotation whose outlines cross more pixel-column centres is sorted in global memory
+
+
+def rle_from_polygons_batch(annotations_polygons, sizes, device=None):
+    """The polygons of many annotations -> one ragged RLE set, encoded on the GPU in one call (mrcnn_rle_from_polygons_batch):
+    annotations_polygons[k] = the COCO polygons of annotation k, sizes[k] = (h, w) of its image.  Returns (counts, run_offsets, areas,
+    bboxes_xywh): RLE k = counts[run_offsets[k]:run_offsets[k + 1]], word for word what ``rle_from_polygons`` gives.  device=None:
+    numpy arrays (uint32, int64, uint32, int32 (n, 4)); a torch device: tensors that stay there (int32, int64, int32, int32)."""
+    polys, ann_offs = [], np.zeros(len(annotations_polygons) + 1, dtype=np.int64)
+    for k, ann in enumerate(annotations_polygons):
+        for p in ann:
+            p = np.asarray(p, dtype=np.float64).reshape(-1)
+            if p.size % 2:
+                raise ValueError("rle_from_polygons_batch: a polygon is a flat list of x, y pairs")
+            polys.append(p)
+        ann_offs[k + 1] = len(polys)
+    if len(sizes) != len(annotations_polygons):
+        raise ValueError("rle_from_polygons_batch: one (h, w) per annotation")
+    xy = np.ascontiguousarray(np.concatenate(polys) if polys else np.zeros(0), dtype=np.float64)
+    offs = np.zeros(len(polys) + 1, dtype=np.int64)
+    if polys:
+        offs[1:] = np.cumsum([p.size // 2 for p in polys])
+    n = len(annotations_polygons)
+    hs = np.array([int(s[0]) for s in sizes], dtype=np.int32)
+    ws = np.array([int(s[1]) for s in sizes], dtype=np.int32)
+    L = _lib.lib()
+    if device is None:
+        ro = np.zeros(n + 1, dtype=np.int64)
+        areas = np.zeros(n, dtype=np.uint32)
+        boxes = np.zeros((n, 4), dtype=np.int32)
+        ptr = lambda a: a.ctypes.data
+        new = lambda c: np.empty(max(1, c), dtype=np.uint32)
+        space, last = _lib.HOST, lambda: int(ro[n])
+    else:
+        import torch
+        ro = torch.zeros(n + 1, dtype=torch.int64, device=device)
+        areas = torch.zeros(n, dtype=torch.int32, device=device)
+        boxes = torch.zeros((n, 4), dtype=torch.int32, device=device)
+        ptr = lambda a: a.data_ptr()
+        new = lambda c: torch.empty(max(1, c), dtype=torch.int32, device=device)
+        space, last = _lib.DEVICE, lambda: int(ro[n].item())
+
+    def call(capacity):
+        counts = new(capacity)
+        st = L.mrcnn_rle_from_polygons_batch(xy.ctypes.data, offs.ctypes.data, ann_offs.ctypes.data, n, hs.ctypes.data, ws.ctypes.data, space,
+                                             ptr(counts), capacity, ptr(ro), ptr(areas), ptr(boxes))
+        return st, counts
+    capacity = 256 * n + 1024                                    # a guess; the call names what it needs
+    st, counts = call(capacity)
+    if st == 4 and last() > capacity:
+        st, counts = call(last())
+    _lib.check(st)
+    return counts[:last()], ro, areas, boxes
+
+
 def segmentation_to_counts(seg, h: int, w: int) -> np.ndarray:
     """Any of COCO's three segmentation forms -> uint32 run lengths on the h x w plane."""
     if isinstance(seg, dict):
@@ -92,7 +147,97 @@ class COCOGroundTruth:
         return ann["_counts"]
 
     def area(self, ann: dict) -> float:
-        return float(ann["area"]) if ann["area"] is not None else float(_area(self.counts(ann)))
+        if ann["area"] is not None:
+            return float(ann["area"])
+        if "_area" in ann:                                       # set pixels counted on the device (to_device)
+            return ann["_area"]
+        return float(_area(self.counts(ann)))
+
+    def to_device(self, device="cuda") -> "DeviceGroundTruth":
+        """Every annotation encoded once and kept on `device` for scoring (``score(..., device_gt=...)``): polygon annotations in one
+        call of mrcnn_rle_from_polygons_batch, RLE-form annotations (crowds) decoded on the host and spliced in.  The order is that of
+        ``by_image``, so the ground truths of an image are one contiguous range."""
+        import torch
+        order, ranges = [], {}
+        for image_id, anns in self.by_image.items():
+            ranges[image_id] = (len(order), len(order) + len(anns))
+            order += anns
+        n = len(order)
+        sizes = [self.images[a["image_id"]] for a in order]
+        is_poly = [not isinstance(a["segmentation"], dict) for a in order]
+        poly_idx = [k for k in range(n) if is_poly[k]]
+        pc, po, pa, _ = rle_from_polygons_batch([order[k]["segmentation"] for k in poly_idx], [sizes[k] for k in poly_idx], device=device)
+        po_h = po.cpu().numpy()
+        pa_h = pa.cpu().numpy()
+        lengths = np.zeros(n, dtype=np.int64)
+        host = {}
+        for j, k in enumerate(poly_idx):
+            lengths[k] = po_h[j + 1] - po_h[j]
+        for k in range(n):
+            if not is_poly[k]:
+                host[k] = segmentation_to_counts(order[k]["segmentation"], *sizes[k])
+                lengths[k] = host[k].size
+        offs = np.zeros(n + 1, dtype=np.int64)
+        offs[1:] = np.cumsum(lengths)
+        if host:
+            counts = torch.empty(max(1, int(offs[n])), dtype=torch.int32, device=device)
+            areas_h = np.zeros(n, dtype=np.int64)
+            j = 0                                                # polygon annotations between two RLE-form ones move as one slice
+            k = 0
+            while k < n:
+                if is_poly[k]:
+                    k1 = k
+                    while k1 < n and is_poly[k1]:
+                        k1 += 1
+                    m = k1 - k
+                    counts[int(offs[k]):int(offs[k1])] = pc[int(po_h[j]):int(po_h[j + m])]
+                    areas_h[k:k1] = pa_h[j:j + m]
+                    j += m
+                    k = k1
+                else:
+                    counts[int(offs[k]):int(offs[k + 1])] = torch.from_numpy(host[k].view(np.int32)).to(device)
+                    areas_h[k] = _area(host[k])
+                    k += 1
+        else:
+            counts, areas_h = pc, pa_h.astype(np.int64)
+        run_offsets = torch.from_numpy(offs).to(device)
+        areas = torch.from_numpy(areas_h.astype(np.int32)).to(device)
+        # every RLE sums to the pixels of its image
+        if n:
+            csum = torch.zeros(int(offs[n]) + 1, dtype=torch.int64, device=device)
+            csum[1:] = torch.cumsum(counts[:int(offs[n])].to(torch.int64) & 0xFFFFFFFF, 0)
+            sums = (csum[run_offsets[1:]] - csum[run_offsets[:-1]]).cpu().numpy()
+            want = np.array([h * w for h, w in sizes], dtype=np.int64)
+            bad = np.nonzero(sums != want)[0]
+            if bad.size:
+                k = int(bad[0])
+                raise ValueError(f"segmentation sums to {int(sums[k])} pixels, the image has {int(want[k])}")
+        for k, a in enumerate(order):
+            if a["area"] is None:
+                a["_area"] = float(areas_h[k])
+        return DeviceGroundTruth(self, counts, run_offsets, areas, offs, {id(a): k for k, a in enumerate(order)}, ranges,
+                                 np.array([a["iscrowd"] for a in order], dtype=np.uint8))
+
+
+class DeviceGroundTruth:
+    """The masks of a COCOGroundTruth as one RLE set resident on the device, in the layout mrcnn_rle_iou reads: ``counts`` (int32),
+    ``run_offsets`` (int64, n + 1) and ``areas`` (int32) are device tensors; annotation ``a`` is RLE ``index[id(a)]``, the annotations of
+    an image are the range ``image_range[image_id]``.  ``COCOGroundTruth.to_device`` makes one."""
+
+    def __init__(self, gt, counts, run_offsets, areas, host_offsets, index, image_range, iscrowd):
+        self.gt, self.counts, self.run_offsets, self.areas = gt, counts, run_offsets, areas
+        self.host_offsets, self.index, self.image_range, self.iscrowd = host_offsets, index, image_range, iscrowd
+        self.n = len(index)
+
+    def gather(self, anns):
+        """The RLEs of `anns` as a set of their own on the device (counts, run_offsets): when a filter breaks an image's range."""
+        import torch
+        ks = [self.index[id(a)] for a in anns]
+        offs = np.zeros(len(ks) + 1, dtype=np.int64)
+        offs[1:] = np.cumsum([self.host_offsets[k + 1] - self.host_offsets[k] for k in ks])
+        parts = [self.counts[int(self.host_offsets[k]):int(self.host_offsets[k + 1])] for k in ks]
+        counts = torch.cat(parts) if parts else torch.zeros(1, dtype=torch.int32, device=self.counts.device)
+        return counts, torch.from_numpy(offs).to(self.counts.device)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -170,12 +315,16 @@ def _group_array(groups):
 
 
 def _evaluate_set(gt: COCOGroundTruth, img_order: List, per_image: Dict, iou_type: str, max_det: int, device: Optional[DeviceDetections],
-                  cat_set, area_rng, iou_thrs):
+                  cat_set, area_rng, iou_thrs, resident: Optional["DeviceGroundTruth"] = None):
     """IoU + matching for the images of one detection set.  per_image[image_id] = list of records (with ``_local`` = the row of the
     image's IoU block, ``area``, ``score``, ``category_id`` and — host sets — ``_counts``).  Returns {(image_id, category_id): eval}."""
     L = _lib.lib()
     A, T = len(area_rng), len(iou_thrs)
     on_device = device is not None
+    if resident is not None and (iou_type != "segm" or resident.gt is not gt):
+        resident = None                                          # boxes are host tables; another file's set is not this one's
+    iou_dev = on_device or resident is not None                  # where the IoU blocks live
+    in_place = resident is not None                              # the images' ranges of the resident set, unless a filter breaks one
     imgs = [i for i in img_order if i in per_image]
     # --- the two sets and the IoU groups -----------------------------------------------------------------------------------------
     g_anns, groups, blocks = [], [], {}
@@ -201,21 +350,52 @@ def _evaluate_set(gt: COCOGroundTruth, img_order: List, per_image: Dict, iou_typ
                 d_boxes.append(np.array([r["bbox"] for r in recs], dtype=np.float64).reshape(-1, 4))
         g0 = len(g_anns)
         g_anns += ganns
+        if in_place and ganns:
+            r0, r1 = resident.image_range[image_id]
+            in_place = r1 - r0 == len(ganns)
+            g0 = r0
         groups.append((d0, d0 + nd, g0, g0 + len(ganns), out_at))
         blocks[image_id] = (out_at, len(ganns), ganns)
         out_at += nd * len(ganns)
     n_pairs, n_g = out_at, len(g_anns)
     crowd = np.array([a["iscrowd"] for a in g_anns], dtype=np.uint8)
+    if resident is not None and not in_place:                    # the gather fallback: the groups name the gathered set
+        at = 0
+        for k, (image_id, g) in enumerate(zip(imgs, groups)):
+            ng = g[3] - g[2]
+            groups[k] = (g[0], g[1], at, at + ng, g[4])
+            at += ng
+    g_lo = 0
+    if resident is not None and in_place:                        # only the stretch of the resident set this batch's images span is named
+        used = [g for g in groups if g[3] > g[2]]
+        g_lo, g_hi = (min(g[2] for g in used), max(g[3] for g in used)) if used else (0, 0)
+        groups = [(g[0], g[1], g[2] - g_lo, g[3] - g_lo, g[4]) if g[3] > g[2] else (g[0], g[1], 0, 0, g[4]) for g in groups]
     garr = _group_array(groups)
-    if on_device:
+    if iou_dev:
         import torch
-        iou = torch.zeros(max(1, n_pairs), dtype=torch.float64, device=device.counts.device)
+        dev_of = device.counts.device if on_device else resident.counts.device
+        iou = torch.zeros(max(1, n_pairs), dtype=torch.float64, device=dev_of)
         iou_ptr, space = iou.data_ptr(), _lib.DEVICE
     else:
         iou = np.zeros(max(1, n_pairs), dtype=np.float64)
         iou_ptr, space = iou.ctypes.data, _lib.HOST
     if n_pairs:
-        if iou_type == "segm":
+        if iou_type == "segm" and resident is not None:
+            # the ground truth never leaves the device: its resident buffers, or a gather of them on the device
+            if in_place:
+                gc, go, n_g = resident.counts, resident.run_offsets[g_lo:g_hi + 1], g_hi - g_lo      # (the offsets index the whole counts)
+                crowd = np.ascontiguousarray(resident.iscrowd[g_lo:g_hi])
+            else:
+                gc, go = resident.gather(g_anns)
+            if on_device:
+                dc, do, n_d = device.counts, device.run_offsets, len(device.image_ids) * device.rows
+            else:
+                d_counts, d_offs = _concat_rles(d_rles)
+                dc = torch.from_numpy(d_counts.view(np.int32)).to(dev_of) if d_counts.size else torch.zeros(1, dtype=torch.int32, device=dev_of)
+                do, n_d = torch.from_numpy(d_offs).to(dev_of), len(d_rles)
+            _lib.check(L.mrcnn_rle_iou(dc.data_ptr(), do.data_ptr(), n_d, gc.data_ptr(), go.data_ptr(), n_g, crowd.ctypes.data, garr, len(groups),
+                                       space, None, iou_ptr, n_pairs))
+        elif iou_type == "segm":
             g_counts, g_offs = _concat_rles([gt.counts(a) for a in g_anns])
             if on_device:
                 gc = torch.from_numpy(g_counts.view(np.int32)).to(device.counts.device)
@@ -274,7 +454,7 @@ def _evaluate_set(gt: COCOGroundTruth, img_order: List, per_image: Dict, iou_typ
     n_dt, n_gt = dt_idx_a.size, gt_idx_a.size
     dt_match = np.full(max(1, A * T * n_dt), -1, dtype=np.int32)
     dt_ignore = np.zeros(max(1, A * T * n_dt), dtype=np.uint8)
-    if on_device:
+    if iou_dev:
         dm = torch.empty(max(1, A * T * n_dt), dtype=torch.int32, device=iou.device)
         di = torch.empty(max(1, A * T * n_dt), dtype=torch.uint8, device=iou.device)
         _lib.check(L.mrcnn_coco_match(iou_ptr, n_pairs, space, marr, len(mgroups), dt_idx_a.ctypes.data, dt_area_a.ctypes.data, n_dt, gt_idx_a.ctypes.data,
@@ -409,12 +589,14 @@ def _finish(gt: COCOGroundTruth, ev: Dict, img_ids: List, cat_ids: List, max_det
     return {"stats": stats, "precision": precision, "recall": recall, "summary": lines, "img_ids": list(img_ids), "cat_ids": list(cat_ids)}
 
 
-def score(gt: COCOGroundTruth, results, iou_type: str = "segm", img_ids=None, max_dets=(1, 10, 100), device_batches=None) -> dict:
+def score(gt: COCOGroundTruth, results, iou_type: str = "segm", img_ids=None, max_dets=(1, 10, 100), device_batches=None, device_gt=None) -> dict:
     """COCO's twelve numbers for `results` (the list coco_results.coco_results returns, or that list loaded from JSON) against `gt`.
     Returns ``stats`` (12, -1 where COCO prints -1), ``precision`` (T, R, K, A, M), ``recall`` (T, K, A, M) and ``summary`` (the twelve
     lines in COCOeval's wording).  img_ids: the images scored (default: all of the annotation file).
     device_batches: a list of DeviceDetections — the fast path: `results` may then be None; the run lengths of those batches are read
-    on the device where mrcnn_masks_rle_source left them (see score_batch)."""
+    on the device where mrcnn_masks_rle_source left them (see score_batch).
+    device_gt: ``gt.to_device()`` — for ``segm`` the ground truth is then read where it is resident, for every batch, and no run length
+    of it crosses to the device again; the numbers are the same."""
     if iou_type not in ("segm", "bbox"):
         raise ValueError("iou_type must be 'segm' or 'bbox'")
     if len(max_dets) != 3:
@@ -433,13 +615,15 @@ def score(gt: COCOGroundTruth, results, iou_type: str = "segm", img_ids=None, ma
                     if iou_type == "bbox":
                         rec["area"] = r["bbox"][2] * r["bbox"][3]
                     per_image.setdefault(r["image_id"], []).append(rec)
-            ev.update(_evaluate_set(gt, img_ids, per_image, iou_type, max_dets[-1], batch, cat_set, AREA_RNG, IOU_THRS))
+            ev.update(_evaluate_set(gt, img_ids, per_image, iou_type, max_dets[-1], batch, cat_set, AREA_RNG, IOU_THRS, device_gt))
     else:
         per_image = _records(gt, results or [], iou_type, img_set, cat_set)
-        ev.update(_evaluate_set(gt, img_ids, per_image, iou_type, max_dets[-1], None, cat_set, AREA_RNG, IOU_THRS))
+        ev.update(_evaluate_set(gt, img_ids, per_image, iou_type, max_dets[-1], None, cat_set, AREA_RNG, IOU_THRS, device_gt))
     return _finish(gt, ev, img_ids, cat_ids, max_dets)
 
 
-def score_batch(gt: COCOGroundTruth, batches: Sequence[DeviceDetections], iou_type: str = "segm", img_ids=None, max_dets=(1, 10, 100)) -> dict:
-    """``score`` over detections that never left the device (device_detections): the same arrays as the path through strings."""
-    return score(gt, None, iou_type, img_ids, max_dets, device_batches=list(batches))
+def score_batch(gt: COCOGroundTruth, batches: Sequence[DeviceDetections], iou_type: str = "segm", img_ids=None, max_dets=(1, 10, 100),
+                device_gt=None) -> dict:
+    """``score`` over detections that never left the device (device_detections): the same arrays as the path through strings.  With
+    device_gt = ``gt.to_device()`` neither side of the mask IoU is uploaded per batch."""
+    return score(gt, None, iou_type, img_ids, max_dets, device_batches=list(batches), device_gt=device_gt)

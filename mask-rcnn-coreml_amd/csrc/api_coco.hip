@@ -1,5 +1,5 @@
 // api_coco.hip — the C ABI of include/maskrcnn_hip.h, COCO scoring: mask / box IoU per image, COCOeval's matching
-// (kernels_coco.hip) and polygons to run-length masks on the host.
+// (kernels_coco.hip) and polygons to run-length masks: one annotation on the host, a whole annotation file on the device.
 #include <math.h>
 #include <string.h>
 
@@ -333,5 +333,123 @@ extern "C" int mrcnn_rle_from_polygons(const double* xy, const int64_t* poly_off
         *n = (int64_t)runs.size();
         MRCNN_REQUIRE(*n <= capacity || !counts, MRCNN_ERR_SHAPE, "rle_from_polygons: the mask has %lld runs, counts holds %lld", (long long)*n, (long long)capacity);
         if (counts) memcpy(counts, runs.data(), runs.size() * sizeof(uint32_t));
+    });
+}
+
+// The same for a whole annotation file at once, on the device (kernels_coco.hip, poly_device.h).  Every argument check comes before
+// the device is touched.
+extern "C" int mrcnn_rle_from_polygons_batch(const double* xy, const int64_t* poly_offsets, const int64_t* ann_offsets, int64_t n_anns,
+                                             const int32_t* heights, const int32_t* widths, int memspace, uint32_t* counts, int64_t capacity,
+                                             int64_t* run_offsets, uint32_t* areas, int32_t* bboxes_xywh)
+{
+    return guarded([&] {
+        MRCNN_REQUIRE(n_anns >= 0 && ann_offsets && run_offsets && ((heights && widths) || n_anns == 0), MRCNN_ERR_INVALID,
+                      "rle_from_polygons_batch: null table or negative number of annotations");
+        MRCNN_REQUIRE(memspace == MRCNN_HOST || memspace == MRCNN_DEVICE, MRCNN_ERR_INVALID, "rle_from_polygons_batch: memspace %d", memspace);
+        MRCNN_REQUIRE(capacity >= 0 && (counts || capacity == 0), MRCNN_ERR_INVALID, "rle_from_polygons_batch: null counts with capacity %lld",
+                      (long long)capacity);
+        MRCNN_REQUIRE(n_anns < (1LL << 31), MRCNN_ERR_SHAPE, "rle_from_polygons_batch: %lld annotations are too many for one call", (long long)n_anns);
+        MRCNN_REQUIRE(ann_offsets[0] >= 0, MRCNN_ERR_INVALID, "rle_from_polygons_batch: ann_offsets[0] = %lld is negative", (long long)ann_offsets[0]);
+        for (int64_t k = 0; k < n_anns; ++k) {
+            MRCNN_REQUIRE(ann_offsets[k + 1] >= ann_offsets[k], MRCNN_ERR_INVALID, "rle_from_polygons_batch: annotation %lld has the polygon range [%lld, %lld)",
+                          (long long)k, (long long)ann_offsets[k], (long long)ann_offsets[k + 1]);
+            MRCNN_REQUIRE(heights[k] >= 1 && heights[k] <= 32767 && widths[k] >= 1 && widths[k] <= 32767, MRCNN_ERR_SHAPE,
+                          "rle_from_polygons_batch: the plane of annotation %lld is %dx%d: height and width must lie in 1..32767", (long long)k, heights[k],
+                          widths[k]);
+        }
+        const int64_t p0 = ann_offsets[0], p1 = ann_offsets[n_anns];
+        MRCNN_REQUIRE(poly_offsets || p1 == p0, MRCNN_ERR_INVALID, "rle_from_polygons_batch: null poly_offsets");
+        MRCNN_REQUIRE(p1 - p0 < (1LL << 31), MRCNN_ERR_SHAPE, "rle_from_polygons_batch: %lld polygons are too many for one call", (long long)(p1 - p0));
+        const int64_t pt_base = p1 > p0 ? poly_offsets[p0] : 0;
+        MRCNN_REQUIRE(pt_base >= 0, MRCNN_ERR_INVALID, "rle_from_polygons_batch: poly_offsets[%lld] = %lld is negative", (long long)p0, (long long)pt_base);
+        std::vector<PolyRec> polys((size_t)(p1 - p0));
+        std::vector<PolyAnn> anns((size_t)n_anns);
+        for (int64_t k = 0; k < n_anns; ++k) {
+            for (int64_t p = ann_offsets[k]; p < ann_offsets[k + 1]; ++p) {
+                const long long q = (long long)(p - ann_offsets[k]);
+                const int64_t a = poly_offsets[p], b = poly_offsets[p + 1];
+                MRCNN_REQUIRE(b >= a && b - pt_base < (1LL << 31), b >= a ? MRCNN_ERR_SHAPE : MRCNN_ERR_INVALID,
+                              "rle_from_polygons_batch: polygon %lld of annotation %lld has the point range [%lld, %lld)", q, (long long)k, (long long)a, (long long)b);
+                MRCNN_REQUIRE(xy || b == a, MRCNN_ERR_INVALID, "rle_from_polygons_batch: null xy");
+                for (int64_t i = 2 * a; i < 2 * b; ++i)
+                    MRCNN_REQUIRE(fabs(xy[i]) < 1e6, MRCNN_ERR_INVALID,
+                                  "rle_from_polygons_batch: coordinate %lld of polygon %lld of annotation %lld is not a finite pixel position", (long long)(i - 2 * a), q,
+                                  (long long)k);
+                polys[(size_t)(p - p0)] = PolyRec{(long long)(a - pt_base), (int)(b - a), (int)k};
+            }
+            const long long f = ann_offsets[k] < p1 ? poly_offsets[ann_offsets[k]] - pt_base : (p1 > p0 ? poly_offsets[p1] - pt_base : 0);
+            anns[(size_t)k] = PolyAnn{f, 0, (int)(ann_offsets[k] - p0), heights[k], widths[k], 0};
+        }
+        const long n_pts = p1 > p0 ? (long)(poly_offsets[p1] - pt_base) : 0;
+        for (int64_t k = 0; k < n_anns; ++k) anns[(size_t)k].pt1 = k + 1 < n_anns ? anns[(size_t)k + 1].pt0 : n_pts;
+        std::vector<int32_t> pt_poly((size_t)n_pts);
+        for (size_t p = 0; p < polys.size(); ++p)
+            for (int j = 0; j < polys[p].npts; ++j) pt_poly[(size_t)polys[p].pt0 + (size_t)j] = (int32_t)p;
+
+        require_gpu();
+        const bool dev = memspace == MRCNN_DEVICE;
+        const size_t n = (size_t)n_anns;
+        Stream st;
+        auto up = [](DevBuf& b, const void* src, size_t bytes) { b.alloc(bytes ? bytes : 16); if (bytes) HIP_CHECK(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice)); };
+        DevBuf t_xy, t_pp, t_pr, t_an, t_ec, t_es, t_to, t_bnd, t_nb, t_nr, t_ro, t_ar, t_bb, t_big, t_keys, t_cov, t_c;
+        up(t_xy, xy ? xy + 2 * pt_base : nullptr, (size_t)n_pts * 16);
+        up(t_pp, pt_poly.data(), (size_t)n_pts * 4);
+        up(t_pr, polys.data(), polys.size() * sizeof(PolyRec));
+        up(t_an, anns.data(), n * sizeof(PolyAnn));
+        t_ec.alloc((size_t)n_pts * 4 + 16); t_es.alloc(((size_t)n_pts + 1) * 8); t_to.alloc((n + 1) * 8);
+        poly_count_forward(st.s, t_xy.as<double>(), t_pp.as<int32_t>(), t_pr.as<PolyRec>(), t_an.as<PolyAnn>(), n_pts, (long)n_anns, t_ec.as<uint32_t>(),
+                           t_es.as<long long>(), t_to.as<long long>());
+        std::vector<long long> tog((size_t)n + 1, 0);
+        HIP_CHECK(hipMemcpyAsync(tog.data(), t_to.p, (n + 1) * 8, hipMemcpyDeviceToHost, st.s));
+        HIP_CHECK(hipStreamSynchronize(st.s));
+        // the annotations whose toggles do not fit LDS are sorted in global memory, each in a power-of-two slice of one scratch
+        std::vector<PolyBig> big;
+        long long scratch = 0;
+        for (size_t k = 0; k < n; ++k) {
+            const long long m = tog[k + 1] - tog[k];
+            if (m <= POLY_LDS_TOGGLES) continue;
+            long long padded = 1;
+            while (padded < m) padded <<= 1;
+            big.push_back(PolyBig{(long long)k, scratch, padded});
+            scratch += padded;
+        }
+        MRCNN_REQUIRE(big.size() < (1u << 31), MRCNN_ERR_SHAPE, "rle_from_polygons_batch: too many large annotations for one call");
+        long long* ro = reinterpret_cast<long long*>(run_offsets);
+        uint32_t* ar = areas;
+        int32_t* bb = bboxes_xywh;
+        if (!dev) {
+            t_ro.alloc((n + 1) * 8); ro = t_ro.as<long long>();
+            if (areas) { t_ar.alloc(n * 4 + 16); ar = t_ar.as<uint32_t>(); }
+            if (bboxes_xywh) { t_bb.alloc(n * 16 + 16); bb = t_bb.as<int32_t>(); }
+        }
+        t_bnd.alloc((size_t)tog[n] * 4 + 16); t_nb.alloc(n * 4 + 16); t_nr.alloc(n * 4 + 16);
+        poly_encode_lds_forward(st.s, t_xy.as<double>(), t_pp.as<int32_t>(), t_pr.as<PolyRec>(), t_an.as<PolyAnn>(), (long)n_anns, t_es.as<long long>(),
+                                t_bnd.as<uint32_t>(), t_nb.as<uint32_t>(), t_nr.as<uint32_t>(), ar, bb);
+        if (!big.empty()) {
+            up(t_big, big.data(), big.size() * sizeof(PolyBig));
+            t_keys.alloc((size_t)scratch * 8); t_cov.alloc((size_t)scratch * 4);
+            poly_encode_big_forward(st.s, t_xy.as<double>(), t_pp.as<int32_t>(), t_pr.as<PolyRec>(), t_an.as<PolyAnn>(), t_es.as<long long>(),
+                                    t_big.as<PolyBig>(), big.data(), (int)big.size(), t_keys.as<unsigned long long>(), t_cov.as<int32_t>(),
+                                    t_bnd.as<uint32_t>(), t_nb.as<uint32_t>(), t_nr.as<uint32_t>(), ar, bb);
+        }
+        poly_offsets_forward(st.s, t_nr.as<uint32_t>(), (long)n_anns, ro);
+        long long need = 0;
+        HIP_CHECK(hipMemcpyAsync(&need, ro + n, sizeof(need), hipMemcpyDeviceToHost, st.s));
+        HIP_CHECK(hipStreamSynchronize(st.s));
+        if (!dev) {
+            HIP_CHECK(hipMemcpy(run_offsets, t_ro.p, (n + 1) * 8, hipMemcpyDeviceToHost));
+            if (areas && n) HIP_CHECK(hipMemcpy(areas, t_ar.p, n * 4, hipMemcpyDeviceToHost));
+            if (bboxes_xywh && n) HIP_CHECK(hipMemcpy(bboxes_xywh, t_bb.p, n * 16, hipMemcpyDeviceToHost));
+        }
+        // everything but the runs is written by now; the runs only when all of them fit
+        MRCNN_REQUIRE(need <= (long long)capacity, MRCNN_ERR_SHAPE,
+                      "rle_from_polygons_batch: the annotations encode to %lld runs, counts holds %lld: call again with capacity >= %lld", need,
+                      (long long)capacity, need);
+        if (n == 0) return;
+        uint32_t* c = counts;
+        if (!dev) { t_c.alloc((size_t)need * 4); c = t_c.as<uint32_t>(); }
+        poly_write_forward(st.s, t_an.as<PolyAnn>(), (long)n_anns, t_to.as<long long>(), t_bnd.as<uint32_t>(), t_nb.as<uint32_t>(), ro, c);
+        HIP_CHECK(hipStreamSynchronize(st.s));
+        if (!dev) HIP_CHECK(hipMemcpy(counts, t_c.p, (size_t)need * 4, hipMemcpyDeviceToHost));
     });
 }

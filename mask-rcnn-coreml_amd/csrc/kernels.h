@@ -397,4 +397,30 @@ void coco_match_forward(hipStream_t s, const double* iou, const MatchGroup* grou
                         const int32_t* gt_idx, const double* gt_area, const uint8_t* gt_crowd, const double* ranges, int A, const double* thrs, int T,
                         int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match);
 
+// Polygon ground truth -> RLE (mrcnn_rle_from_polygons_batch; the arithmetic is poly_device.h).  All tables are device arrays.
+// An EDGE is a point of the concatenated point list together with its successor in its polygon; its toggles are the pixel-column
+// centres it crosses.  The toggles of an annotation are contiguous in edge order: toggle q of the batch belongs to the edge e with
+// edge_start[e] <= q < edge_start[e + 1].
+struct PolyRec { long long pt0; int npts, ann; };                 // one polygon: its points [pt0, pt0 + npts) and its annotation
+struct PolyAnn { long long pt0, pt1; int poly0, h, w, pad; };     // one annotation: its points, its first polygon, its plane
+struct PolyBig { long long ann, offset, padded; };               // an annotation on the global sort path: its slice of the scratch, a power of two
+constexpr int POLY_LDS_TOGGLES = MRCNN_POLY_LDS_TOGGLES;                           // toggles an annotation may have to be sorted in LDS (8 B keys + 4 B coverage = 48 KiB)
+// edge_cnt[e] = the toggles of edge e, edge_start = its exclusive prefix (n_pts + 1), tog_off[k] = edge_start[anns[k].pt0] (n_anns + 1)
+void poly_count_forward(hipStream_t s, const double* xy, const int32_t* pt_poly, const PolyRec* polys, const PolyAnn* anns, long n_pts, long n_anns,
+                        uint32_t* edge_cnt, long long* edge_start, long long* tog_off);
+// Annotations of at most POLY_LDS_TOGGLES toggles, one block each: generate, sort per polygon, pair, sort per annotation, unite.  The run
+// boundaries of annotation k land at bnd[tog_off[k] ..], their number in nb[k]; nruns[k], areas[k], bboxes[4k ..] (may be nullptr) follow.
+void poly_encode_lds_forward(hipStream_t s, const double* xy, const int32_t* pt_poly, const PolyRec* polys, const PolyAnn* anns, long n_anns,
+                             const long long* edge_start, uint32_t* bnd, uint32_t* nb, uint32_t* nruns, uint32_t* areas, int32_t* bboxes);
+// The same for the annotations listed in `big` (host copy: h_big), sorted in global memory: keys (8 B) and cov (4 B) hold the sum of the
+// padded sizes.  The number of launches grows with the logarithm of the largest padded size, not with the number of annotations.
+void poly_encode_big_forward(hipStream_t s, const double* xy, const int32_t* pt_poly, const PolyRec* polys, const PolyAnn* anns,
+                             const long long* edge_start, const PolyBig* big, const PolyBig* h_big, int n_big, unsigned long long* keys, int32_t* cov,
+                             uint32_t* bnd, uint32_t* nb, uint32_t* nruns, uint32_t* areas, int32_t* bboxes);
+// run_offsets = the exclusive prefix of nruns (n + 1 entries)
+void poly_offsets_forward(hipStream_t s, const uint32_t* nruns, long n, long long* run_offsets);
+// counts[run_offsets[k] ..] = the differences of annotation k's boundaries, closed by the run to h*w
+void poly_write_forward(hipStream_t s, const PolyAnn* anns, long n_anns, const long long* tog_off, const uint32_t* bnd, const uint32_t* nb,
+                        const long long* run_offsets, uint32_t* counts);
+
 }  // namespace mrcnn
