@@ -521,8 +521,8 @@ MRCNN_API int mrcnn_mask_to_u8_f64(const double* mask, int64_t n, uint8_t* out);
 /* ---------------------------------------------------------------------------------------------
  * COCO scoring — the second half of `maskrcnn evaluate` (Sources/maskrcnn/Python/COCOEval/task.py:93-98,
  * coco_dataset.evaluate_results: COCOeval's evaluate step).  The IoU of every detection with every ground truth of its image and the
- * greedy matching per (image, category, area range, IoU threshold) run on the GPU; accumulate / summarize are left to the host
- * (coco_eval.py).  RLE sets are in the layout of mrcnn_masks_rle_source: RLE k = counts[run_offsets[k] .. run_offsets[k+1]),
+ * greedy matching per (image, category, area range, IoU threshold) run on the GPU, and so does accumulate (mrcnn_coco_accumulate);
+ * summarize — twelve means — is left to the host (coco_eval.py).  RLE sets are in the layout of mrcnn_masks_rle_source: RLE k = counts[run_offsets[k] .. run_offsets[k+1]),
  * uint32 run lengths, column-major, counts[0] = leading zeros; n + 1 offsets, non-decreasing, run_offsets[0] >= 0.
  *
  * mrcnn_iou_group — one image: detections [d0, d1) of the detection set against ground truths [g0, g1) of the ground-truth set; the
@@ -565,6 +565,39 @@ MRCNN_API int mrcnn_coco_match(const double* iou, int64_t n_iou, int memspace, c
                                const int32_t* dt_idx, const double* dt_area, int64_t n_dt, const int32_t* gt_idx, const double* gt_area,
                                const uint8_t* gt_iscrowd, int64_t n_gt, const double* area_ranges, int n_ranges,
                                const double* iou_thresholds, int n_thresholds, int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match);
+/* COCOeval.accumulate on the GPU: the precision / recall tables from the matching's flags.  coco_eval.accumulate (numpy) is the
+ * definition; the two outputs are what it returns, bit for bit.
+ * Inputs.  The detection entries are ONE flat list of n_dt entries, category-major; inside a category the images in image order; inside an
+ * image the entries in descending score — the order in which accumulate concatenates its per-image records.  Category k owns the
+ * entries [cat_offsets[k], cat_offsets[k+1]) (n_cats + 1 offsets, cat_offsets[0] = 0, non-decreasing, cat_offsets[n_cats] = n_dt).
+ *   scores[i]                      the score of entry i
+ *   ranks[i]                       the position of entry i in the list of its own (image, category): the entry TAKES PART under
+ *                                  max_dets[m] iff ranks[i] < max_dets[m] (accumulate's [:maxDet] slices)
+ *   dt_matched[(a*T + t)*n_dt + i] and dt_ignore[the same index]: 0 or 1, A = n_ranges, T = n_thresholds
+ *   npig[k*A + a]                  the non-ignored ground truths of category k in area range a, over all images
+ * memspace holds for scores, ranks, dt_matched, dt_ignore, precision and recall; cat_offsets, npig, max_dets (n_max_dets = M) and rec_thrs
+ * (n_rec = R, non-decreasing) are host arrays.
+ * Outputs, row-major doubles, every entry overwritten: precision (T, R, K, A, M), recall (T, K, A, M), K = n_cats.  Per (k, a, m):
+ *   the entries of category k that take part, ordered as np.argsort(-scores, kind="mergesort") orders them: descending and stable, -0.0
+ *   and 0.0 equal, a NaN after every number (the order under a smaller max_dets is a subsequence of the order under a larger one);
+ *   per t: tp = cumsum(matched & !ignore), fp = cumsum(!matched & !ignore), counted as integers and converted to double;
+ *   rc = tp / npig; pr = tp / ((fp + tp) + 2.220446049250313e-16), in exactly that association, both IEEE double divisions;
+ *   pr is replaced by its maximum over the entries from it to the end; precision[t, r] = pr[the first i with rc[i] >= rec_thrs[r]], 0
+ *   where there is none; recall[t] = rc[last], 0 when no entry takes part.
+ *   npig == 0: the whole (k, a, m) cell is -1 in both outputs — a category without any record is this case.
+ * A category is sorted in chunks of MRCNN_COCO_ACC_CHUNK entries in LDS which are then merged pairwise in global memory, and scanned
+ * in chunks of the same size with a carry; there is no limit on the size of a category (n_dt < 2^31), and the number of launches grows
+ * with the logarithm of the largest category, not with n_cats.  The flag planes are permuted into sorted order once.
+ * Errors, all before the device is touched: a null pointer (scores, ranks, dt_matched, dt_ignore only when n_dt > 0; npig, precision,
+ * recall only when n_cats > 0), negative n_dt / n_cats, an unknown memspace, cat_offsets that decrease, do not start at 0 or do not end at
+ * n_dt, a negative npig -> MRCNN_ERR_INVALID; n_ranges, n_thresholds, n_max_dets or n_rec below 1, rec_thrs that decrease (or hold a NaN),
+ * tables too large for one call (n_dt >= 2^31, K*A*M*T >= 2^31) -> MRCNN_ERR_SHAPE.  No gfx950 device -> MRCNN_ERR_HIP (no CPU fallback).
+ * n_dt = 0 and n_cats = 0 are valid. */
+#define MRCNN_COCO_ACC_CHUNK 1024
+MRCNN_API int mrcnn_coco_accumulate(const double* scores, const int32_t* ranks, const uint8_t* dt_matched, const uint8_t* dt_ignore,
+                                    int64_t n_dt, const int64_t* cat_offsets, int n_cats, const int64_t* npig, int n_ranges, int n_thresholds,
+                                    const int32_t* max_dets, int n_max_dets, const double* rec_thrs, int n_rec, int memspace, double* precision,
+                                    double* recall);
 /* Host only, no GPU: the union of n_polys COCO polygons (polygon p = the points xy[2*poly_offsets[p]] .. xy[2*poly_offsets[p+1]), x
  * then y, in pixels) on an h x w plane as ONE RLE, by COCO's published procedure (pycocotools rleFrPoly): vertices scaled by 5 and
  * rounded, the edges walked on that fine grid, the crossings of pixel-column centres reduced to column-major run boundaries (clipped

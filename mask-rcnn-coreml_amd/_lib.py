@@ -39,7 +39,7 @@ EXPORTED_SYMBOLS = [
     "mrcnn_masks_rle_source", "mrcnn_rle_to_string", "mrcnn_rle_from_string",
     "mrcnn_instance_map_source", "mrcnn_render_detections_source",
     "mrcnn_rle_iou", "mrcnn_box_iou_xywh", "mrcnn_coco_match", "mrcnn_rle_from_polygons",
-    "mrcnn_rle_from_polygons_batch",
+    "mrcnn_rle_from_polygons_batch", "mrcnn_coco_accumulate",
 ]
 # declared in include/maskrcnn_hip_test.h (test / measurement entry points of the same library)
 TEST_SYMBOLS = [
@@ -151,6 +151,7 @@ def lib():
     L.mrcnn_coco_match.argtypes = [vp, C.c_int64, C.c_int, vp, C.c_int, vp, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, C.c_int, vp, C.c_int, vp, vp, vp]
     L.mrcnn_rle_from_polygons.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int64, i64p]
     L.mrcnn_rle_from_polygons_batch.argtypes = [vp, vp, vp, C.c_int64, vp, vp, C.c_int, vp, C.c_int64, vp, vp, vp]
+    L.mrcnn_coco_accumulate.argtypes = [vp, vp, vp, vp, C.c_int64, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
     L.mrcnn_maskrcnn_predict_async.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.mrcnn_maskrcnn_submit.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
     L.mrcnn_maskrcnn_collect.argtypes = [vp, vp, vp, C.POINTER(C.c_int)]

@@ -4,8 +4,9 @@
 The procedure is COCO's published one (COCOeval: evaluate -> accumulate -> summarize).  Its hot half runs on the GPU through the C
 ABI: the IoU of every detection with every ground truth of its image straight from the run lengths (``mrcnn_rle_iou``, or
 ``mrcnn_box_iou_xywh`` for ``bbox``) and the greedy matching for every (image, category, area range, threshold)
-(``mrcnn_coco_match``).  The host sorts, builds the group tables and runs ``accumulate`` / ``summarize`` in numpy; those two, and
-``COCOGroundTruth``, need no GPU.  One deliberate difference to pycocotools: a detection counts as matched when it is matched, not
+(``mrcnn_coco_match``), and COCOeval's accumulate (``mrcnn_coco_accumulate`` through ``accumulate_device``).  The host sorts each image's
+detections, builds the group tables and runs ``summarize``; ``accumulate`` in numpy stays the definition of the device entry and the path
+of a host without a device.  ``accumulate``, ``summarize`` and ``COCOGroundTruth`` need no GPU.  One deliberate difference to pycocotools: a detection counts as matched when it is matched, not
 when the id of its ground truth is > 0.
 """
 from __future__ import annotations
@@ -528,6 +529,96 @@ def accumulate(evals: List[List[dict]], max_dets=(1, 10, 100), n_thrs: int = len
     return precision, recall
 
 
+ACC_CHUNK = 1024       # MRCNN_COCO_ACC_CHUNK: mrcnn_coco_accumulate sorts and scans a category in chunks of this many entries
+
+
+def pack_evals(evals: List[List[dict]], max_dets=(1, 10, 100), n_thrs: int = len(IOU_THRS), n_areas: int = len(AREA_RNG)) -> dict:
+    """The per-category lists of per-image records ``accumulate`` takes -> the flat tables of mrcnn_coco_accumulate: ``scores`` (n,
+    float64), ``ranks`` (n, int32: the position in the record), ``matched`` / ``ignore`` (A, T, n) uint8, ``cat_offsets`` (K + 1, int64) and
+    ``npig`` (K, A) int64.  The entries are accumulate's concatenation for the largest of max_dets: category after category, record after
+    record, each record cut to that many entries."""
+    K, A, T, cap = len(evals), int(n_areas), int(n_thrs), int(max(max_dets))
+    recs = [e for E in evals for e in E]
+    rec_bounds = np.zeros(K + 1, dtype=np.int64)
+    rec_bounds[1:] = np.cumsum(np.fromiter((len(E) for E in evals), dtype=np.int64, count=K))
+    lens = np.fromiter((len(e["scores"]) for e in recs), dtype=np.int64, count=len(recs))
+    ngs = np.fromiter((np.shape(e["gt_ignore"])[1] for e in recs), dtype=np.int64, count=len(recs))
+    if recs:
+        scores = np.concatenate([e["scores"] for e in recs]).astype(np.float64, copy=False)
+        matched = np.concatenate([e["matched"] for e in recs], axis=2)
+        ignore = np.concatenate([e["ignore"] for e in recs], axis=2)
+        gt_ignore = np.concatenate([e["gt_ignore"] for e in recs], axis=1)
+    else:
+        scores, matched, ignore, gt_ignore = np.zeros(0), np.zeros((A, T, 0), bool), np.zeros((A, T, 0), bool), np.zeros((A, 0), bool)
+    n = int(lens.sum())
+    if matched.shape != (A, T, n) or ignore.shape != (A, T, n) or gt_ignore.shape[0] != A or scores.shape != (n,):
+        raise ValueError(f"pack_evals: records of {n} entries with flags of shape {matched.shape} / {ignore.shape} and ground-truth flags "
+                         f"{gt_ignore.shape}: expected ({A}, {T}, {n}) and ({A}, ng)")
+    ranks = np.arange(n, dtype=np.int64) - np.repeat(np.cumsum(lens) - lens, lens)
+    if n and int(lens.max()) > cap:                              # accumulate's [:max_det] for the largest max_det
+        keep = ranks < cap
+        scores, ranks, matched, ignore = scores[keep], ranks[keep], matched[:, :, keep], ignore[:, :, keep]
+        lens = np.minimum(lens, cap)
+    ends = np.zeros(len(recs) + 1, dtype=np.int64)
+    ends[1:] = np.cumsum(lens)
+    g_ends = np.zeros(len(recs) + 1, dtype=np.int64)
+    g_ends[1:] = np.cumsum(ngs)
+    found = np.zeros((A, gt_ignore.shape[1] + 1), dtype=np.int64)
+    found[:, 1:] = np.cumsum(gt_ignore == 0, axis=1)
+    g_bounds = g_ends[rec_bounds]
+    npig = (found[:, g_bounds[1:]] - found[:, g_bounds[:-1]]).T
+    return {"scores": np.ascontiguousarray(scores, dtype=np.float64), "ranks": np.ascontiguousarray(ranks, dtype=np.int32),
+            "matched": np.ascontiguousarray(matched != 0, dtype=np.uint8), "ignore": np.ascontiguousarray(ignore != 0, dtype=np.uint8),
+            "cat_offsets": np.ascontiguousarray(ends[rec_bounds]), "npig": np.ascontiguousarray(npig, dtype=np.int64)}
+
+
+def accumulate_packed(packed: dict, max_dets=(1, 10, 100), rec_thrs=REC_THRS, device=None):
+    """mrcnn_coco_accumulate over the tables of ``pack_evals``.  device=None: the tables stay numpy arrays and the library stages them;
+    a torch device: they are uploaded as tensors and read in place.  Returns precision (T, R, K, A, M), recall (T, K, A, M) as numpy."""
+    A, T, n = packed["matched"].shape
+    K, M = packed["cat_offsets"].size - 1, len(max_dets)
+    md = np.ascontiguousarray(max_dets, dtype=np.int32)
+    thr = np.ascontiguousarray(rec_thrs, dtype=np.float64)
+    R = thr.size
+    L = _lib.lib()
+    tables = [packed["scores"], packed["ranks"], packed["matched"], packed["ignore"]]
+    if device is None:
+        precision, recall = np.empty((T, R, K, A, M)), np.empty((T, K, A, M))
+        ptr, space = (lambda a: a.ctypes.data), _lib.HOST
+    else:
+        import torch
+        tables = [torch.from_numpy(a).to(device) for a in tables]
+        precision = torch.empty((T, R, K, A, M), dtype=torch.float64, device=device)
+        recall = torch.empty((T, K, A, M), dtype=torch.float64, device=device)
+        ptr, space = (lambda a: a.data_ptr()), _lib.DEVICE
+    _lib.check(L.mrcnn_coco_accumulate(ptr(tables[0]), ptr(tables[1]), ptr(tables[2]), ptr(tables[3]), n, packed["cat_offsets"].ctypes.data, K,
+                                       packed["npig"].ctypes.data, A, T, md.ctypes.data, M, thr.ctypes.data, R, space, ptr(precision), ptr(recall)))
+    if device is not None:
+        precision, recall = precision.cpu().numpy(), recall.cpu().numpy()
+    return precision, recall
+
+
+def accumulate_device(evals: List[List[dict]], max_dets=(1, 10, 100), n_thrs: int = len(IOU_THRS), n_areas: int = len(AREA_RNG), rec_thrs=REC_THRS,
+                      device="cuda"):
+    """``accumulate`` on the GPU (mrcnn_coco_accumulate): the same arguments, the same two arrays bit for bit.  device: where the packed
+    tables are uploaded as torch tensors, or None to hand the library host arrays."""
+    return accumulate_packed(pack_evals(evals, max_dets, n_thrs, n_areas), max_dets, rec_thrs, device)
+
+
+# What accumulate_on=None means.  The device entry has not been timed against numpy's accumulate on an MI355X yet (DESIGN.md §5
+# "Scoring"; tools/coco_accumulate_ab.py takes the measurement), so the default stays with the definition; "device" is for the asking.
+DEFAULT_ACCUMULATE_ON = "host"
+
+
+def _accumulate_where(accumulate_on):
+    """None: DEFAULT_ACCUMULATE_ON — and the host in any case when there is no device."""
+    if accumulate_on is None:
+        return "device" if DEFAULT_ACCUMULATE_ON == "device" and _lib.lib().mrcnn_device_count() > 0 else "host"
+    if accumulate_on not in ("host", "device"):
+        raise ValueError("accumulate_on must be None, 'host' or 'device'")
+    return accumulate_on
+
+
 def summarize(precision: np.ndarray, recall: np.ndarray, max_dets=(1, 10, 100), iou_thrs=IOU_THRS, area_lbl=AREA_LBL):
     """COCOeval.summarize: (stats (12,), the twelve lines)."""
     lines = []
@@ -571,7 +662,8 @@ def _records(gt: COCOGroundTruth, results, iou_type: str, img_set, cat_set):
     return per_image
 
 
-def _finish(gt: COCOGroundTruth, ev: Dict, img_ids: List, cat_ids: List, max_dets):
+def _finish(gt: COCOGroundTruth, ev: Dict, img_ids: List, cat_ids: List, max_dets, accumulate_on=None):
+    where = _accumulate_where(accumulate_on)
     cat_set = set(cat_ids)
     for image_id in img_ids:                                  # images with ground truth and no detection at all still count their objects
         by_cat: Dict = {}
@@ -584,19 +676,23 @@ def _finish(gt: COCOGroundTruth, ev: Dict, img_ids: List, cat_ids: List, max_det
                 ev[(image_id, cat)] = {"scores": np.zeros(0), "matched": np.zeros((A, T, 0), bool), "ignore": np.zeros((A, T, 0), bool),
                                        "gt_ignore": gt_ignore_flags(gts, gt, AREA_RNG)}
     evals = [[ev[(i, c)] for i in img_ids if (i, c) in ev] for c in cat_ids]
-    precision, recall = accumulate(evals, max_dets)
+    precision, recall = accumulate_device(evals, max_dets, device=None) if where == "device" else accumulate(evals, max_dets)
     stats, lines = summarize(precision, recall, max_dets)
     return {"stats": stats, "precision": precision, "recall": recall, "summary": lines, "img_ids": list(img_ids), "cat_ids": list(cat_ids)}
 
 
-def score(gt: COCOGroundTruth, results, iou_type: str = "segm", img_ids=None, max_dets=(1, 10, 100), device_batches=None, device_gt=None) -> dict:
+def score(gt: COCOGroundTruth, results, iou_type: str = "segm", img_ids=None, max_dets=(1, 10, 100), device_batches=None, device_gt=None,
+          accumulate_on=None) -> dict:
     """COCO's twelve numbers for `results` (the list coco_results.coco_results returns, or that list loaded from JSON) against `gt`.
     Returns ``stats`` (12, -1 where COCO prints -1), ``precision`` (T, R, K, A, M), ``recall`` (T, K, A, M) and ``summary`` (the twelve
     lines in COCOeval's wording).  img_ids: the images scored (default: all of the annotation file).
     device_batches: a list of DeviceDetections — the fast path: `results` may then be None; the run lengths of those batches are read
     on the device where mrcnn_masks_rle_source left them (see score_batch).
     device_gt: ``gt.to_device()`` — for ``segm`` the ground truth is then read where it is resident, for every batch, and no run length
-    of it crosses to the device again; the numbers are the same."""
+    of it crosses to the device again; the numbers are the same.
+    accumulate_on: "device" — COCOeval's accumulate through mrcnn_coco_accumulate, "host" — in numpy, None — DEFAULT_ACCUMULATE_ON; the
+    arrays are identical either way."""
+    _accumulate_where(accumulate_on)
     if iou_type not in ("segm", "bbox"):
         raise ValueError("iou_type must be 'segm' or 'bbox'")
     if len(max_dets) != 3:
@@ -619,11 +715,11 @@ def score(gt: COCOGroundTruth, results, iou_type: str = "segm", img_ids=None, ma
     else:
         per_image = _records(gt, results or [], iou_type, img_set, cat_set)
         ev.update(_evaluate_set(gt, img_ids, per_image, iou_type, max_dets[-1], None, cat_set, AREA_RNG, IOU_THRS, device_gt))
-    return _finish(gt, ev, img_ids, cat_ids, max_dets)
+    return _finish(gt, ev, img_ids, cat_ids, max_dets, accumulate_on)
 
 
 def score_batch(gt: COCOGroundTruth, batches: Sequence[DeviceDetections], iou_type: str = "segm", img_ids=None, max_dets=(1, 10, 100),
-                device_gt=None) -> dict:
+                device_gt=None, accumulate_on=None) -> dict:
     """``score`` over detections that never left the device (device_detections): the same arrays as the path through strings.  With
     device_gt = ``gt.to_device()`` neither side of the mask IoU is uploaded per batch."""
-    return score(gt, None, iou_type, img_ids, max_dets, device_batches=list(batches), device_gt=device_gt)
+    return score(gt, None, iou_type, img_ids, max_dets, device_batches=list(batches), device_gt=device_gt, accumulate_on=accumulate_on)

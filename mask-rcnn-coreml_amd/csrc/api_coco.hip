@@ -1,5 +1,6 @@
 // api_coco.hip — the C ABI of include/maskrcnn_hip.h, COCO scoring: mask / box IoU per image, COCOeval's matching
-// (kernels_coco.hip) and polygons to run-length masks: one annotation on the host, a whole annotation file on the device.
+// (kernels_coco.hip), its accumulate (kernels_coco_acc.hip) and polygons to run-length masks: one annotation on the host, a whole
+// annotation file on the device.
 #include <math.h>
 #include <string.h>
 
@@ -243,6 +244,78 @@ extern "C" int mrcnn_coco_match(const double* iou, int64_t n_iou, int memspace, 
             if (dt_match && n_dt) HIP_CHECK(hipMemcpy(dt_match, dm, AT * (size_t)n_dt * 4, hipMemcpyDeviceToHost));
             if (dt_ignore && n_dt) HIP_CHECK(hipMemcpy(dt_ignore, di, AT * (size_t)n_dt, hipMemcpyDeviceToHost));
             if (gt_match && n_gt) HIP_CHECK(hipMemcpy(gt_match, gm, AT * (size_t)n_gt * 4, hipMemcpyDeviceToHost));
+        }
+    });
+}
+
+// COCOeval.accumulate (kernels_coco_acc.hip).  Every argument check comes before the device is touched.
+extern "C" int mrcnn_coco_accumulate(const double* scores, const int32_t* ranks, const uint8_t* dt_matched, const uint8_t* dt_ignore, int64_t n_dt,
+                                     const int64_t* cat_offsets, int n_cats, const int64_t* npig, int n_ranges, int n_thresholds,
+                                     const int32_t* max_dets, int n_max_dets, const double* rec_thrs, int n_rec, int memspace, double* precision,
+                                     double* recall)
+{
+    return guarded([&] {
+        MRCNN_REQUIRE(n_dt >= 0 && n_cats >= 0, MRCNN_ERR_INVALID, "coco_accumulate: %lld entries in %d categories", (long long)n_dt, n_cats);
+        MRCNN_REQUIRE(memspace == MRCNN_HOST || memspace == MRCNN_DEVICE, MRCNN_ERR_INVALID, "coco_accumulate: memspace %d", memspace);
+        MRCNN_REQUIRE(cat_offsets && max_dets && rec_thrs, MRCNN_ERR_INVALID, "coco_accumulate: null cat_offsets, max_dets or rec_thrs");
+        MRCNN_REQUIRE((scores && ranks && dt_matched && dt_ignore) || n_dt == 0, MRCNN_ERR_INVALID, "coco_accumulate: null scores, ranks, dt_matched or dt_ignore");
+        MRCNN_REQUIRE((npig && precision && recall) || n_cats == 0, MRCNN_ERR_INVALID, "coco_accumulate: null npig, precision or recall");
+        MRCNN_REQUIRE(n_ranges >= 1 && n_thresholds >= 1 && n_max_dets >= 1 && n_rec >= 1, MRCNN_ERR_SHAPE,
+                      "coco_accumulate: %d area ranges, %d thresholds, %d max_dets, %d recall thresholds: each must be at least 1", n_ranges, n_thresholds,
+                      n_max_dets, n_rec);
+        MRCNN_REQUIRE(cat_offsets[0] == 0, MRCNN_ERR_INVALID, "coco_accumulate: cat_offsets[0] = %lld, not 0", (long long)cat_offsets[0]);
+        for (int k = 0; k < n_cats; ++k)
+            MRCNN_REQUIRE(cat_offsets[k + 1] >= cat_offsets[k], MRCNN_ERR_INVALID, "coco_accumulate: cat_offsets decrease at category %d: [%lld, %lld)", k,
+                          (long long)cat_offsets[k], (long long)cat_offsets[k + 1]);
+        MRCNN_REQUIRE(cat_offsets[n_cats] == n_dt, MRCNN_ERR_INVALID, "coco_accumulate: cat_offsets end at %lld, the list has %lld entries",
+                      (long long)cat_offsets[n_cats], (long long)n_dt);
+        for (long long i = 0; i < (long long)n_cats * n_ranges; ++i)
+            MRCNN_REQUIRE(npig[i] >= 0, MRCNN_ERR_INVALID, "coco_accumulate: npig of category %lld, area range %lld is %lld", i / n_ranges, i % n_ranges,
+                          (long long)npig[i]);
+        for (int r = 0; r + 1 < n_rec; ++r)
+            MRCNN_REQUIRE(rec_thrs[r + 1] >= rec_thrs[r], MRCNN_ERR_SHAPE, "coco_accumulate: rec_thrs decrease at %d (%g, then %g)", r, rec_thrs[r], rec_thrs[r + 1]);
+        MRCNN_REQUIRE(rec_thrs[n_rec - 1] == rec_thrs[n_rec - 1], MRCNN_ERR_SHAPE, "coco_accumulate: rec_thrs[%d] is not a number", n_rec - 1);
+        const long long cells = (long long)n_ranges * n_max_dets * n_thresholds;
+        MRCNN_REQUIRE(n_dt < (1LL << 31) && cells < (1LL << 31) && (n_cats == 0 || cells < (1LL << 31) / n_cats) &&
+                      (long long)n_ranges * n_thresholds < (1LL << 31), MRCNN_ERR_SHAPE, "coco_accumulate: the tables are too large for one call");
+        // the chunks of the segments: the grid of the sort
+        std::vector<AccChunk> chunks;
+        long long longest = 0;
+        for (int k = 0; k < n_cats; ++k) {
+            const long long len = cat_offsets[k + 1] - cat_offsets[k];
+            longest = std::max(longest, len);
+            for (long long at = 0; at < len; at += COCO_ACC_CHUNK) chunks.push_back(AccChunk{(long long)cat_offsets[k], (int)len, (int)at});
+        }
+
+        require_gpu();
+        if (n_cats == 0) return;
+        const bool dev = memspace == MRCNN_DEVICE;
+        const size_t n = (size_t)n_dt, K = (size_t)n_cats, A = (size_t)n_ranges, T = (size_t)n_thresholds, M = (size_t)n_max_dets, R = (size_t)n_rec;
+        Stream st;
+        auto up = [](DevBuf& b, const void* src, size_t bytes) { b.alloc(bytes); if (bytes) HIP_CHECK(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice)); };
+        DevBuf t_sc, t_rk, t_dm, t_di, t_ch, t_off, t_np, t_md, t_th, t_ka, t_kb, t_pa, t_pb, t_code, t_srank, t_pr, t_rc;
+        const double* d_sc = scores;
+        const int32_t* d_rk = ranks;
+        const uint8_t *d_dm = dt_matched, *d_di = dt_ignore;
+        double *d_pr = precision, *d_rc = recall;
+        if (!dev) {
+            up(t_sc, scores, n * 8); up(t_rk, ranks, n * 4); up(t_dm, dt_matched, A * T * n); up(t_di, dt_ignore, A * T * n);
+            t_pr.alloc(T * R * K * A * M * 8); t_rc.alloc(T * K * A * M * 8);
+            d_sc = t_sc.as<double>(); d_rk = t_rk.as<int32_t>(); d_dm = t_dm.as<uint8_t>(); d_di = t_di.as<uint8_t>();
+            d_pr = t_pr.as<double>(); d_rc = t_rc.as<double>();
+        }
+        up(t_ch, chunks.data(), chunks.size() * sizeof(AccChunk));
+        up(t_off, cat_offsets, (K + 1) * 8); up(t_np, npig, K * A * 8); up(t_md, max_dets, M * 4); up(t_th, rec_thrs, R * 8);
+        t_ka.alloc(n * 8); t_kb.alloc(n * 8); t_pa.alloc(n * 4); t_pb.alloc(n * 4); t_code.alloc(A * T * n); t_srank.alloc(n * 4);
+        const uint32_t* perm = coco_acc_sort_forward(st.s, d_sc, t_ch.as<AccChunk>(), (long)chunks.size(), longest, t_ka.as<unsigned long long>(),
+                                                     t_pa.as<uint32_t>(), t_kb.as<unsigned long long>(), t_pb.as<uint32_t>());
+        coco_acc_permute_forward(st.s, perm, d_rk, d_dm, d_di, (long long)n_dt, (int)(A * T), t_code.as<uint8_t>(), t_srank.as<int32_t>());
+        coco_acc_scan_forward(st.s, t_code.as<uint8_t>(), t_srank.as<int32_t>(), t_off.as<long long>(), t_np.as<long long>(), t_md.as<int32_t>(),
+                              t_th.as<double>(), (long long)n_dt, n_cats, n_ranges, n_max_dets, n_thresholds, n_rec, d_pr, d_rc);
+        HIP_CHECK(hipStreamSynchronize(st.s));
+        if (!dev) {
+            HIP_CHECK(hipMemcpy(precision, d_pr, T * R * K * A * M * 8, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(recall, d_rc, T * K * A * M * 8, hipMemcpyDeviceToHost));
         }
     });
 }

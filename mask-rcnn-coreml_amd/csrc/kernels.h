@@ -1,5 +1,6 @@
 // kernels.h — host-side launchers of the gfx950 kernels (one namespace, no torch, no templates in the API).
 #pragma once
+#include <algorithm>
 #include <map>
 #include <tuple>
 #include <vector>
@@ -422,5 +423,23 @@ void poly_offsets_forward(hipStream_t s, const uint32_t* nruns, long n, long lon
 // counts[run_offsets[k] ..] = the differences of annotation k's boundaries, closed by the run to h*w
 void poly_write_forward(hipStream_t s, const PolyAnn* anns, long n_anns, const long long* tog_off, const uint32_t* bnd, const uint32_t* nb,
                         const long long* run_offsets, uint32_t* counts);
+
+// COCOeval.accumulate (mrcnn_coco_accumulate; kernels_coco_acc.hip).  -ffp-contract=off.  All tables are device arrays.
+// A chunk is COCO_ACC_CHUNK consecutive entries of one category's segment [seg0, seg0 + seg_len) of the flat detection list, starting
+// `at` entries into it (a multiple of the chunk); the chunks of all segments, in order, are the grid of the sort kernels.
+constexpr int COCO_ACC_CHUNK = MRCNN_COCO_ACC_CHUNK;
+struct AccChunk { long long seg0; int seg_len, at; };
+// Stable sort of every segment by descending score (-0 = 0, NaN last).  `longest` = the longest segment.  keys / perm a and b hold n_dt
+// entries each; returns the one of perm_a / perm_b that holds the result: perm[i] = the entry that stands at sorted position i.
+// 1 + ceil(log2(longest / COCO_ACC_CHUNK)) launches.
+const uint32_t* coco_acc_sort_forward(hipStream_t s, const double* scores, const AccChunk* chunks, long n_chunks, long long longest,
+                                      unsigned long long* keys_a, uint32_t* perm_a, unsigned long long* keys_b, uint32_t* perm_b);
+// code[pl * n_dt + i] = 2 if ignore else matched, of the entry at sorted position i, for each of the `planes` = A * T planes; srank[i] = its rank
+void coco_acc_permute_forward(hipStream_t s, const uint32_t* perm, const int32_t* ranks, const uint8_t* matched, const uint8_t* ignore, long long n_dt,
+                              int planes, uint8_t* code, int32_t* srank);
+// precision (T, R, K, A, M) and recall (T, K, A, M), every entry written; one block per (k, a, m, t)
+void coco_acc_scan_forward(hipStream_t s, const uint8_t* code, const int32_t* srank, const long long* cat_off, const long long* npig,
+                           const int32_t* max_dets, const double* rec_thrs, long long n_dt, int K, int A, int M, int T, int R, double* precision,
+                           double* recall);
 
 }  // namespace mrcnn
