@@ -430,6 +430,36 @@ MRCNN_API int mrcnn_generate_anchors(int image_h, int image_w, float* out, int64
 MRCNN_API int mrcnn_letterbox_geometry(int h, int w, int H, int W, int* nh, int* nw, int* pad_y, int* pad_x);
 MRCNN_API int mrcnn_letterbox_rgb(const uint8_t* src, int h, int w, int memspace, uint8_t* dst, int H, int W);
 
+/* JPEG: compressed bytes in (the reference reads `<dataset dir>/<file_name>`, EvaluateCommand.swift:159-200, and every COCO file is a
+ * JPEG).  The serial part — marker parsing, Huffman decoding — runs on the host; dequantisation, the 8x8 inverse DCT, chroma
+ * upsampling and YCbCr -> RGB run in two launches for the whole batch, and the decoded RGB8 never exists in host memory.
+ * The output is DEFINED as what libjpeg / libjpeg-turbo produce with their defaults (JDCT_ISLOW, fancy upsampling), byte for byte.
+ *   decoded:     baseline sequential DCT (SOF0), 8-bit, Huffman, one interleaved scan; 1 component (grey, replicated to RGB) or 3
+ *                (YCbCr) sampled 4:4:4, 4:2:2 (h2v1) or 4:2:0 (h2v2); 8- and 16-bit quantisation tables; any DHT; restart intervals;
+ *                APPn / COM are skipped; sides 1..32767
+ *   refused:     progressive, arithmetic, lossless, 12-bit, 4 components, an Adobe transform other than YCbCr, other sampling
+ *                factors, multi-scan sequential files -> MRCNN_ERR_UNSUPPORTED, the message names what was found
+ *   damaged or truncated stream -> MRCNN_ERR_IO.  No input, however malformed, is read or written out of bounds.
+ * A file is ALWAYS host memory.  _info and _decode_host are host code and need no GPU; _decode_host is the whole pipeline in scalar C++,
+ * the definition the device entry is held to (rgb: height*width*3 bytes; capacity too small -> MRCNN_ERR_SHAPE).
+ * _decode_batch: files of different sizes; image b's height*width*3 bytes go to out_rgb + out_offsets[b] (`memspace` is out_rgb's;
+ * offsets are bytes, multiples of 16, the ranges must not overlap, bytes no image covers are left untouched — the conventions of
+ * mrcnn_render_detections_source); heights / widths (host, `batch` entries) are outputs.  Every file is validated first, before anything
+ * is written; an error names the index of the offending file.  Entropy decoding runs on min(batch, 8) threads of the call.
+ * Errors: null pointer, bad offset -> MRCNN_ERR_INVALID; batch outside 1..MRCNN_JPEG_MAX_BATCH -> MRCNN_ERR_SHAPE; no gfx950 device
+ * -> MRCNN_ERR_HIP from the two device entries (no CPU fallback).
+ * mrcnn_maskrcnn_predict_jpegs = _decode_batch into staging the model owns + mrcnn_maskrcnn_predict_images on it, bit for bit
+ * (`memspace` is that of detections and masks; batch 1..max_batch). */
+#define MRCNN_JPEG_MAX_BATCH 1024
+typedef struct { const uint8_t* data; int64_t length; } mrcnn_jpeg;
+MRCNN_API int mrcnn_jpeg_info(const uint8_t* data, int64_t length, int32_t* height, int32_t* width, int32_t* components, int32_t* h_samp,
+                              int32_t* v_samp);
+MRCNN_API int mrcnn_jpeg_decode_host(const uint8_t* data, int64_t length, uint8_t* rgb, int64_t capacity);
+MRCNN_API int mrcnn_jpeg_decode_batch(const mrcnn_jpeg* files, int batch, int memspace, uint8_t* out_rgb, const int64_t* out_offsets,
+                                      int32_t* heights, int32_t* widths);
+MRCNN_API int mrcnn_maskrcnn_predict_jpegs(mrcnn_model* model, const mrcnn_jpeg* files, int batch, int memspace, float* detections,
+                                           float* masks, int32_t* heights, int32_t* widths);
+
 /* Mask paste: per-instance 28×28 sigmoid masks → full-resolution binary masks
  * (n, image_h, image_w) uint8 {0,1}: resize to the detection's box and threshold.  Replaces what the
  * example app does with CoreGraphics when drawing (Example/Source/DetectionRenderer.swift:13-24).

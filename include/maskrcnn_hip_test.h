@@ -132,6 +132,10 @@ MRCNN_API int mrcnn_bottleneck_first_nhwc(const float* x, int batch, int h, int 
 MRCNN_API int mrcnn_bottleneck_stage_nhwc(const float* x, int batch, int h, int w, int nlayers, const float* w1, const float* w2, const float* w3,
                                           const float* const bn[6], int form, int iters, float* out, float* avg_ms, int* status_flag);
 
+/* Measurement (tools/jpeg_ab.py): the wall time of the two stages of the calling thread's last mrcnn_jpeg_decode_batch /
+ * mrcnn_maskrcnn_predict_jpegs — host_ms: header parsing + the entropy threads; device_ms: from the upload of the coefficients to the end
+ * of the second launch (decode_batch only, where the call waits for it; 0 after predict_jpegs, whose launches run ahead of the predict). */
+MRCNN_API int mrcnn_jpeg_last_stage_ms(float* host_ms, float* device_ms);
 
 #ifdef __cplusplus
 }

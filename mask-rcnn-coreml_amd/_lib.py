@@ -40,11 +40,13 @@ EXPORTED_SYMBOLS = [
     "mrcnn_instance_map_source", "mrcnn_render_detections_source",
     "mrcnn_rle_iou", "mrcnn_box_iou_xywh", "mrcnn_coco_match", "mrcnn_rle_from_polygons",
     "mrcnn_rle_from_polygons_batch", "mrcnn_coco_accumulate",
+    "mrcnn_jpeg_info", "mrcnn_jpeg_decode_host", "mrcnn_jpeg_decode_batch", "mrcnn_maskrcnn_predict_jpegs",
 ]
 # declared in include/maskrcnn_hip_test.h (test / measurement entry points of the same library)
 TEST_SYMBOLS = [
     "mrcnn_bench_conv", "mrcnn_bench_conv_dtype", "mrcnn_model_conv_profile_enable", "mrcnn_model_conv_profile_get",
     "mrcnn_model_conv_profile_shapes", "mrcnn_conv2d_nhwc", "mrcnn_debug_set", "mrcnn_bottleneck_nhwc", "mrcnn_bench_mfma_probe", "mrcnn_model_conv_profile_group", "mrcnn_bottleneck_first_nhwc", "mrcnn_bottleneck_stage_nhwc", "mrcnn_model_conv_profile_bytes",
+    "mrcnn_jpeg_last_stage_ms",
 ]
 
 
@@ -84,6 +86,10 @@ class IouGroup(C.Structure):        # mrcnn_iou_group
 class MatchGroup(C.Structure):      # mrcnn_match_group
     _fields_ = [("iou_offset", C.c_int64), ("iou_stride", C.c_int32), ("dt0", C.c_int32), ("dt1", C.c_int32), ("gt0", C.c_int32),
                 ("gt1", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Jpeg(C.Structure):            # mrcnn_jpeg
+    _fields_ = [("data", C.c_void_p), ("length", C.c_int64)]
 
 
 class Image(C.Structure):           # mrcnn_image
@@ -152,6 +158,12 @@ def lib():
     L.mrcnn_rle_from_polygons.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int64, i64p]
     L.mrcnn_rle_from_polygons_batch.argtypes = [vp, vp, vp, C.c_int64, vp, vp, C.c_int, vp, C.c_int64, vp, vp, vp]
     L.mrcnn_coco_accumulate.argtypes = [vp, vp, vp, vp, C.c_int64, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
+    i32p = C.POINTER(C.c_int32)
+    L.mrcnn_jpeg_info.argtypes = [vp, C.c_int64, i32p, i32p, i32p, i32p, i32p]
+    L.mrcnn_jpeg_decode_host.argtypes = [vp, C.c_int64, vp, C.c_int64]
+    L.mrcnn_jpeg_decode_batch.argtypes = [C.POINTER(Jpeg), C.c_int, C.c_int, vp, vp, vp, vp]
+    L.mrcnn_maskrcnn_predict_jpegs.argtypes = [vp, C.POINTER(Jpeg), C.c_int, C.c_int, vp, vp, vp, vp]
+    L.mrcnn_jpeg_last_stage_ms.argtypes = [f32p, f32p]
     L.mrcnn_maskrcnn_predict_async.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.mrcnn_maskrcnn_submit.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
     L.mrcnn_maskrcnn_collect.argtypes = [vp, vp, vp, C.POINTER(C.c_int)]

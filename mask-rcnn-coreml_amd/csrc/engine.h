@@ -152,6 +152,18 @@ struct StageTimer {
     ~StageTimer();
 };
 
+// Staging of a JPEG batch (api_jpeg.hip): one pinned host buffer the entropy threads fill — the descriptor table, then the coefficient
+// blocks — its device twin, the sample planes between the two launches, and (predict_jpegs) the decoded RGB8 images.  Grows, never shrinks.
+struct JpegScratch {
+    uint8_t* pinned = nullptr;        // hipHostMalloc
+    size_t pinned_bytes = 0;
+    DevBuf staged, planes, rgb;
+    JpegScratch() = default;
+    JpegScratch(const JpegScratch&) = delete;
+    JpegScratch& operator=(const JpegScratch&) = delete;
+    ~JpegScratch() { if (pinned) (void)hipHostFree(pinned); }
+};
+
 struct Model {
     int kind = 0;
     int max_batch = 1;
@@ -192,6 +204,7 @@ struct Model {
     uint8_t* fit_pack = nullptr;      // hipHostMalloc: max_batch table entries
     size_t fit_pack_bytes = 0;
     bool fit_mixed = false;
+    JpegScratch jpeg;                 // predict_jpegs: the decode's staging; jpeg.rgb holds the decoded batch predict_images then reads
     float *rpn_logits = nullptr, *rpn_probs = nullptr, *rpn_deltas = nullptr, *rois = nullptr;
     float *cls6 = nullptr, *detections = nullptr, *mask_out = nullptr;
     void *pooled = nullptr, *pooled_mask = nullptr;     // compute dtype

@@ -1,5 +1,6 @@
 // kernels.h — host-side launchers of the gfx950 kernels (one namespace, no torch, no templates in the API).
 #pragma once
+#include <stddef.h>
 #include <algorithm>
 #include <map>
 #include <tuple>
@@ -126,6 +127,33 @@ void instance_map_forward(hipStream_t s, const float* det, const float* masks, c
 void render_detections_forward(hipStream_t s, const float* det, const float* masks, const ImageGeom* tab, const uint8_t* const* srcs, int batch,
                                int rows, int S, int H, int W, long max_pixels, float thr, float min_score, int alpha, int stroke, float* det_src,
                                int4* boxes, uint8_t* out);
+
+// ================================================================================================
+// JPEG decode behind the entropy decoder (kernels_jpeg.hip; the arithmetic is jpeg_math.h's, shared with the host definition)
+// ================================================================================================
+// One image of a ragged batch.  Its coefficient blocks (64 int16 each, natural order) are blocks [block0, block0 + sum of the grids) of
+// the batch's coefficient array, component after component, row-major over each component's MCU-padded grid; its sample planes sit at
+// comp[c].plane0 (bytes, multiple of 16) of the batch's plane buffer with a row pitch of blocks_w * 8.
+struct JpegComp {
+    long long block0;          // first block of the component, counted over the whole batch
+    long long plane0;
+    int blocks_w, blocks_h;
+    int width, height;         // the component's real samples
+};
+struct JpegDesc {
+    long long out_offset;      // byte offset of the h*w*3 RGB8 bytes in `out`
+    long long block0;          // = comp[0].block0
+    long long chunk0;          // first 16-pixel output chunk of the image, counted over the whole batch
+    int h, w, ncomp, mode;     // mode: jpeg_math.h MODE_*
+    int reserved[2];           // (keeps quant, and the next entry of a table, on 16-byte boundaries: the kernels load rows of it as uint4)
+    JpegComp comp[3];
+    uint16_t quant[3][64];     // per component, natural order
+};
+static_assert(sizeof(JpegDesc) % 16 == 0 && offsetof(JpegDesc, quant) % 16 == 0, "JpegDesc: quant rows are loaded 16 bytes at a time");
+// Launch 1: dequantise + islow IDCT of every block of every component of every image -> planes.  Launch 2: chroma upsampling and
+// YCbCr -> RGB per output pixel -> out + tab[b].out_offset.  total_blocks / total_chunks: the sums over the batch.
+void jpeg_decode_forward(hipStream_t s, const JpegDesc* tab, int batch, const int16_t* coef, long long total_blocks, uint8_t* planes,
+                         long long total_chunks, uint8_t* out);
 
 // ================================================================================================
 // Convolution family + element-wise helpers (kernels_conv.hip)

@@ -222,7 +222,8 @@ def evaluate_segm(model: MaskRCNN, images: Iterable[Tuple[int, np.ndarray]], dat
     (coco_results.coco_results: image_id, category_id, bbox in source pixels, score, segmentation as a compressed RLE), one record
     per detection row with score > score_threshold.  Per group of `batch` images everything stays on the device — the images go up
     once, predict_images and detection.masks_rle_source run on device tensors — and only the detection rows and the run lengths come
-    back: no full-resolution plane exists anywhere.  The seconds of an image are its group's wall time (predict and encoding) / size."""
+    back: no full-resolution plane exists anywhere.  The seconds of an image are its group's wall time (predict and encoding) / size.
+    An item's image may also be the ``bytes`` of a JPEG file: such groups go through MaskRCNN.predict_jpegs (jpeg.py), results unchanged."""
     import torch
     from .coco_results import coco_results
     from .detection import masks_rle_source
@@ -235,18 +236,27 @@ def evaluate_segm(model: MaskRCNN, images: Iterable[Tuple[int, np.ndarray]], dat
     out: List[PBResult] = []
     secs: List[float] = []
     coco: List[dict] = []
+    def is_file(img):
+        return isinstance(img, (bytes, bytearray, memoryview))
+
     for g0 in range(0, len(items), batch):
         group = items[g0:g0 + batch]
-        sizes = [(int(img.shape[0]), int(img.shape[1])) for _, img in group]
+        files = [is_file(img) for _, img in group]
+        if any(files) and not all(files):
+            raise ValueError(f"images {group[0][0]}..{group[-1][0]} mix JPEG files and decoded arrays in one group of {batch}")
         t0 = time.perf_counter()
-        dev = [torch.from_numpy(np.ascontiguousarray(img, dtype=np.uint8)).cuda() for _, img in group]
-        det_g, mask_g = model.predict_images(dev)
+        if files[0]:             # compressed bytes: the decode runs on the device too, the decoded images never exist on the host
+            det_g, mask_g, sizes = model.predict_jpegs([img for _, img in group])
+        else:
+            sizes = [(int(img.shape[0]), int(img.shape[1])) for _, img in group]
+            dev = [torch.from_numpy(np.ascontiguousarray(img, dtype=np.uint8)).cuda() for _, img in group]
+            det_g, mask_g = model.predict_images(dev)
         src_g, rles, _, _ = masks_rle_source(det_g, mask_g, sizes, H, W, threshold)
         det, det_src = det_g.cpu().numpy(), src_g.cpu().numpy()
         t1 = time.perf_counter()
         coco += coco_results([image_id for image_id, _ in group], det_src, rles, sizes, class_to_category, score_threshold)
         for b, (image_id, img) in enumerate(group):
-            out.append(PBResult(dataset_id, str(image_id), int(img.shape[1]), int(img.shape[0]), detections_to_pb(det[b])))
+            out.append(PBResult(dataset_id, str(image_id), sizes[b][1], sizes[b][0], detections_to_pb(det[b])))
             secs.append((t1 - t0) / len(group))
             if verbose:
                 print((t1 - t0) / len(group))
@@ -260,7 +270,8 @@ def evaluate_from_dir(model_dir: str, images, **kw):
 def evaluate_coco(model: MaskRCNN, annotations_json: str, load_image, dataset_id: str = "coco", limit: Optional[int] = 5, verbose: bool = True):
     """`maskrcnn evaluate` over a COCO annotation file (EvaluateCommand.swift:159-200): the first `limit` images sorted by id
     (`coco.makeImageIterator(limit: 5, sortById: true)`, :165), each loaded by `load_image(COCOImage) -> (h,w,3) uint8` (the
-    reference reads `<dataset dir>/<file_name>`; decoding image files is left to the host — no codec ships here)."""
+    reference reads `<dataset dir>/<file_name>`; this entry takes decoded arrays — evaluate_segm / evaluate_coco_scored also take the
+    bytes of JPEG files and decode them on the GPU, jpeg.py)."""
     from .coco import COCO
     coco = COCO(annotations_json)
     items = [(im.id, load_image(im)) for im, _ in coco.makeImageIterator(limit=limit, sortById=True)]

@@ -150,6 +150,24 @@ class MaskRCNN(_Model):
             _lib.check(_lib.lib().mrcnn_maskrcnn_predict_images(self._h, table, B, _lib.DEVICE, det.data_ptr(), mask.data_ptr()))
         return det, mask
 
+    def predict_jpegs(self, files):
+        """predict_images straight from JPEG files (mrcnn_maskrcnn_predict_jpegs): a list of bytes.  The entropy decoders run on the
+        host, everything after them on the GPU, and the decoded images stay in staging the handle owns; the results equal
+        ``predict_images([jpeg.decode_host(f) for f in files])`` bit for bit.  Returns (det, mask, [(h_b, w_b)]) with det and mask
+        CUDA tensors, like predict_images on CUDA tensors."""
+        import torch
+        from .jpeg import file_table
+        files = list(files)
+        B = len(files)
+        table, keep = file_table(files)
+        hs, ws = np.zeros(max(1, B), np.int32), np.zeros(max(1, B), np.int32)
+        det = torch.empty((B, self.max_detections, 6), dtype=torch.float32, device="cuda")
+        mask = torch.empty((B, self.max_detections, self.mask_size, self.mask_size), dtype=torch.float32, device="cuda")
+        _lib.check(_lib.lib().mrcnn_maskrcnn_predict_jpegs(self._h, table, B, _lib.DEVICE, det.data_ptr(), mask.data_ptr(), hs.ctypes.data,
+                                                           ws.ctypes.data))
+        del keep
+        return det, mask, [(int(hs[b]), int(ws[b])) for b in range(B)]
+
     def render_images(self, images, **kw):
         """predict_images followed by detection.render_detections_source at this handle's model size: the images with their
         detections drawn on them (DetectionRenderer.swift:26-88).  Keyword arguments go to the render (threshold, min_score, alpha,
