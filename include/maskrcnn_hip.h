@@ -460,6 +460,34 @@ MRCNN_API int mrcnn_jpeg_decode_batch(const mrcnn_jpeg* files, int batch, int me
 MRCNN_API int mrcnn_maskrcnn_predict_jpegs(mrcnn_model* model, const mrcnn_jpeg* files, int batch, int memspace, float* detections,
                                            float* masks, int32_t* heights, int32_t* widths);
 
+/* JPEG: files out — the rendered overlays of mrcnn_render_detections_source (or any RGB8 image) leave as baseline JPEG files, and the
+ * whole encoder runs on the device: colour conversion, chroma downsampling, forward DCT, quantisation, Huffman coding (code lengths
+ * counted per block and scanned, then every block's bits written at once) and byte stuffing.  Only the files' bytes cross back.
+ *   the file:    baseline sequential (SOF0), 8-bit, one interleaved scan; SOI, JFIF APP0 (1.1, density 1:1, no units), DQT, SOF0, DHT,
+ *                SOS, scan, EOI.  Quantisation: Annex K's tables scaled by libjpeg's quality rule (scale = 5000/q below 50, else
+ *                200 - 2q; entry = (base*scale + 50)/100 clamped to 1..255).  Huffman: the four standard Annex K tables.
+ *   left out:    restart markers, optimised Huffman tables, progressive scans.
+ *   the samples: libjpeg's default compressor in integers — 16-bit fixed-point RGB -> YCbCr, box chroma downsampling with libjpeg's
+ *                alternating bias, edges replicated, level shift -128, the jfdctint (ISLOW) forward DCT, round-half-away division by 8q.
+ *                Blocks that exist only as MCU padding are ordinary blocks of replicated samples (libjpeg writes DC-only dummies), so the
+ *                bytes differ from libjpeg's while every visible pixel decodes to the same value.
+ * sampling: MRCNN_JPEG_444 / _422 (h2v1) / _420 (h2v2) / _GREY (one component: the Y above).  quality 1..100.  sides 1..32767.
+ * _encode_host is plain scalar C++, needs no GPU and is the DEFINITION: _encode_batch returns the same bytes, byte for byte.  *length is
+ * always the size needed; out = NULL with capacity = 0 measures; capacity too small -> MRCNN_ERR_SHAPE and nothing is written.
+ * _encode_batch: images of different sizes, as given to mrcnn_maskrcnn_predict_images or left by mrcnn_render_detections_source;
+ * `memspace` is that of the rgb pointers (any alignment); the files are ALWAYS host memory: file b is out[file_offsets[b] ..
+ * file_offsets[b + 1]), back to back.  file_offsets (host, batch + 1 entries) is always written.  file_offsets[batch] > capacity ->
+ * MRCNN_ERR_SHAPE naming the capacity needed, with out untouched; capacity 0 with out = NULL is the size query.  Only the used bytes
+ * are copied from the device, and the number of launches does not depend on batch.
+ * Errors (the message names the index of the offending image), all raised before the device is touched: null pointer, unknown sampling
+ * or memspace -> MRCNN_ERR_INVALID; a side outside 1..32767, quality outside 1..100, batch outside 1..MRCNN_JPEG_MAX_BATCH ->
+ * MRCNN_ERR_SHAPE.  No gfx950 device -> MRCNN_ERR_HIP (no CPU fallback). */
+enum { MRCNN_JPEG_444 = 0, MRCNN_JPEG_422 = 1, MRCNN_JPEG_420 = 2, MRCNN_JPEG_GREY = 3 };
+MRCNN_API int mrcnn_jpeg_encode_host(const uint8_t* rgb, int height, int width, int quality, int sampling, uint8_t* out, int64_t capacity,
+                                     int64_t* length);
+MRCNN_API int mrcnn_jpeg_encode_batch(const mrcnn_image* images, int batch, int memspace, int quality, int sampling, uint8_t* out,
+                                      int64_t capacity, int64_t* file_offsets /* batch + 1 */);
+
 /* Mask paste: per-instance 28×28 sigmoid masks → full-resolution binary masks
  * (n, image_h, image_w) uint8 {0,1}: resize to the detection's box and threshold.  Replaces what the
  * example app does with CoreGraphics when drawing (Example/Source/DetectionRenderer.swift:13-24).

@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = [
     "mrcnn_rle_iou", "mrcnn_box_iou_xywh", "mrcnn_coco_match", "mrcnn_rle_from_polygons",
     "mrcnn_rle_from_polygons_batch", "mrcnn_coco_accumulate",
     "mrcnn_jpeg_info", "mrcnn_jpeg_decode_host", "mrcnn_jpeg_decode_batch", "mrcnn_maskrcnn_predict_jpegs",
+    "mrcnn_jpeg_encode_host", "mrcnn_jpeg_encode_batch",
 ]
 # declared in include/maskrcnn_hip_test.h (test / measurement entry points of the same library)
 TEST_SYMBOLS = [
@@ -163,6 +164,8 @@ def lib():
     L.mrcnn_jpeg_decode_host.argtypes = [vp, C.c_int64, vp, C.c_int64]
     L.mrcnn_jpeg_decode_batch.argtypes = [C.POINTER(Jpeg), C.c_int, C.c_int, vp, vp, vp, vp]
     L.mrcnn_maskrcnn_predict_jpegs.argtypes = [vp, C.POINTER(Jpeg), C.c_int, C.c_int, vp, vp, vp, vp]
+    L.mrcnn_jpeg_encode_host.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.mrcnn_jpeg_encode_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp]
     L.mrcnn_jpeg_last_stage_ms.argtypes = [f32p, f32p]
     L.mrcnn_maskrcnn_predict_async.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.mrcnn_maskrcnn_submit.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]

@@ -1,6 +1,7 @@
 // jpeg_math.h — the per-sample arithmetic of the JPEG decoder, written once for the host definition (jpeg_host.cpp, plain C++) and for
 // the kernels (kernels_jpeg.hip): libjpeg's default pipeline — the "islow" inverse DCT, fancy (triangle) chroma upsampling, the 16-bit
 // fixed-point YCbCr -> RGB — all in integers, so both sides produce the same bytes by construction.  No HIP header is included here.
+// The second half is the encoder's (jpeg_enc_host.cpp, kernels_jpeg_enc.hip): libjpeg's default compressor, shared the same way.
 #pragma once
 #include <stdint.h>
 
@@ -120,6 +121,119 @@ MRCNN_JPEG_HD uint32_t pixel_rgb(const Planes& p, int x, int y)
     if (p.ncomp == 1) return (uint32_t)yy * 0x010101u;
     return ycc_to_rgb(yy, chroma_at(p.plane[1], p.pitch[1], p.cw, p.ch, x, y, p.mode), chroma_at(p.plane[2], p.pitch[2], p.cw, p.ch, x, y, p.mode));
 }
+
+// ================================================================================================
+// The forward path (jpeg_enc_host.cpp, kernels_jpeg_enc.hip): libjpeg's default compressor in integers — 16-bit fixed-point
+// RGB -> YCbCr, box chroma downsampling with the alternating bias, edge replication, the "islow" forward DCT, division by 8q.
+// Samples are 0..255, so nothing here leaves int32.
+// ================================================================================================
+enum { ENC_444 = 0, ENC_422 = 1, ENC_420 = 2, ENC_GREY = 3 };      // = MRCNN_JPEG_444 ..
+
+MRCNN_JPEG_HD int32_t rgb_to_y(int32_t r, int32_t g, int32_t b) { return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16; }
+MRCNN_JPEG_HD int32_t rgb_to_cb(int32_t r, int32_t g, int32_t b) { return (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16; }
+MRCNN_JPEG_HD int32_t rgb_to_cr(int32_t r, int32_t g, int32_t b) { return (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16; }
+
+// component c (0 = Y, 1 = Cb, 2 = Cr) of the pixel at (x, y), both clamped into the image: the edge replication
+MRCNN_JPEG_HD int32_t enc_pixel(const uint8_t* rgb, int h, int w, int c, int x, int y)
+{
+    x = x < w - 1 ? x : w - 1;
+    y = y < h - 1 ? y : h - 1;
+    const uint8_t* p = rgb + ((int64_t)y * w + x) * 3;
+    return c == 0 ? rgb_to_y(p[0], p[1], p[2]) : (c == 1 ? rgb_to_cb(p[0], p[1], p[2]) : rgb_to_cr(p[0], p[1], p[2]));
+}
+
+// sample (sx, sy) of component c on its own (downsampled) grid, any sx, sy >= 0: the bias of a chroma box alternates along a row,
+// 0,1,.. for two samples (h2v1) and 1,2,.. for four (h2v2)
+MRCNN_JPEG_HD int32_t enc_sample(const uint8_t* rgb, int h, int w, int sampling, int c, int sx, int sy)
+{
+    if (c == 0 || sampling == ENC_444 || sampling == ENC_GREY) return enc_pixel(rgb, h, w, c, sx, sy);
+    if (sampling == ENC_422) return (enc_pixel(rgb, h, w, c, 2 * sx, sy) + enc_pixel(rgb, h, w, c, 2 * sx + 1, sy) + (sx & 1)) >> 1;
+    // libjpeg replicates columns BEFORE downsampling but rows of a component AFTER it: below the image a chroma row repeats the last
+    // real chroma row (rows h-2 and h-1 when h is even), which clamping the two source rows alone would not give
+    const int last = (h + 1) / 2 - 1;
+    sy = sy < last ? sy : last;
+    return (enc_pixel(rgb, h, w, c, 2 * sx, 2 * sy) + enc_pixel(rgb, h, w, c, 2 * sx + 1, 2 * sy) + enc_pixel(rgb, h, w, c, 2 * sx, 2 * sy + 1) +
+            enc_pixel(rgb, h, w, c, 2 * sx + 1, 2 * sy + 1) + 1 + (sx & 1)) >> 2;
+}
+
+MRCNN_JPEG_HD int32_t fdescale(int32_t x, int n) { return (x + (1 << (n - 1))) >> n; }
+
+// One 1-D pass of jfdctint over eight values, in place.  first = true: the pass over a row of level-shifted samples (results scaled
+// up by 2^PASS1_BITS); false: the pass over a column of the workspace (that scaling removed; the output stays 8x the true DCT).
+MRCNN_JPEG_HD void fdct_1d(int32_t v[8], bool first)
+{
+    int32_t tmp0 = v[0] + v[7], tmp7 = v[0] - v[7], tmp1 = v[1] + v[6], tmp6 = v[1] - v[6];
+    int32_t tmp2 = v[2] + v[5], tmp5 = v[2] - v[5], tmp3 = v[3] + v[4], tmp4 = v[3] - v[4];
+    const int32_t tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+    const int shift = first ? CONST_BITS - PASS1_BITS : CONST_BITS + PASS1_BITS;
+    if (first) {
+        v[0] = (tmp10 + tmp11) * (1 << PASS1_BITS);
+        v[4] = (tmp10 - tmp11) * (1 << PASS1_BITS);
+    } else {
+        v[0] = fdescale(tmp10 + tmp11, PASS1_BITS);
+        v[4] = fdescale(tmp10 - tmp11, PASS1_BITS);
+    }
+    int32_t z1 = (tmp12 + tmp13) * (int32_t)MRCNN_JPEG_FIX_0_541196100;
+    v[2] = fdescale(z1 + tmp13 * (int32_t)MRCNN_JPEG_FIX_0_765366865, shift);
+    v[6] = fdescale(z1 - tmp12 * (int32_t)MRCNN_JPEG_FIX_1_847759065, shift);
+    z1 = tmp4 + tmp7;
+    int32_t z2 = tmp5 + tmp6, z3 = tmp4 + tmp6, z4 = tmp5 + tmp7;
+    const int32_t z5 = (z3 + z4) * (int32_t)MRCNN_JPEG_FIX_1_175875602;
+    tmp4 *= (int32_t)MRCNN_JPEG_FIX_0_298631336;
+    tmp5 *= (int32_t)MRCNN_JPEG_FIX_2_053119869;
+    tmp6 *= (int32_t)MRCNN_JPEG_FIX_3_072711026;
+    tmp7 *= (int32_t)MRCNN_JPEG_FIX_1_501321110;
+    z1 *= -(int32_t)MRCNN_JPEG_FIX_0_899976223;
+    z2 *= -(int32_t)MRCNN_JPEG_FIX_2_562915447;
+    z3 *= -(int32_t)MRCNN_JPEG_FIX_1_961570560;
+    z4 *= -(int32_t)MRCNN_JPEG_FIX_0_390180644;
+    z3 += z5; z4 += z5;
+    v[7] = fdescale(tmp4 + z1 + z3, shift);
+    v[5] = fdescale(tmp5 + z2 + z4, shift);
+    v[3] = fdescale(tmp6 + z2 + z3, shift);
+    v[1] = fdescale(tmp7 + z1 + z4, shift);
+}
+
+// a DCT output (8x scaled) over quantiser q: division by 8q, halves rounded away from zero
+MRCNN_JPEG_HD int32_t quantise(int32_t v, int32_t q)
+{
+    const int32_t d = q << 3;
+    return v < 0 ? -((-v + (d >> 1)) / d) : (v + (d >> 1)) / d;
+}
+
+// ---- entropy coding of one coefficient: what it appends to the scan, as (bits, their count) ----
+struct Code { uint64_t bits; int len; };              // len <= 59, the bits right-aligned
+
+MRCNN_JPEG_HD int size_category(int32_t v)            // bits of |v|: 0 for 0, 11 at most (a DC difference)
+{
+    uint32_t a = (uint32_t)(v < 0 ? -v : v);
+    int n = 0;
+    while (a) { ++n; a >>= 1; }
+    return n;
+}
+MRCNN_JPEG_HD void code_append(Code& c, uint32_t bits, int len) { c.bits = (c.bits << len) | bits; c.len += len; }
+
+// A Huffman table as the encoder reads it: entry[symbol] = length << 16 | code.  dc: 12 symbols; ac: 256 (run << 4 | size).
+// The DC difference `diff` of a block: its size's code, then the size's low bits of diff (of diff - 1 when negative).
+MRCNN_JPEG_HD Code code_dc(const uint32_t* dc, int32_t diff)
+{
+    Code c = {0, 0};
+    const int s = size_category(diff);
+    code_append(c, dc[s] & 0xFFFFu, (int)(dc[s] >> 16));
+    if (s) code_append(c, (uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << s) - 1), s);
+    return c;
+}
+// A non-zero AC coefficient v after `run` zeros (0..62): run / 16 ZRL codes, the code of (run % 16, size), the size's low bits.
+MRCNN_JPEG_HD Code code_ac(const uint32_t* ac, int run, int32_t v)
+{
+    Code c = {0, 0};
+    for (int i = run >> 4; i > 0; --i) code_append(c, ac[0xF0] & 0xFFFFu, (int)(ac[0xF0] >> 16));
+    const int s = size_category(v), sym = ((run & 15) << 4) | s;
+    code_append(c, ac[sym] & 0xFFFFu, (int)(ac[sym] >> 16));
+    code_append(c, (uint32_t)(v < 0 ? v - 1 : v) & ((1u << s) - 1), s);
+    return c;
+}
+MRCNN_JPEG_HD Code code_eob(const uint32_t* ac) { Code c = {ac[0] & 0xFFFFu, (int)(ac[0] >> 16)}; return c; }
 
 }  // namespace jpeg
 }  // namespace mrcnn

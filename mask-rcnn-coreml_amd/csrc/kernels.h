@@ -156,6 +156,50 @@ void jpeg_decode_forward(hipStream_t s, const JpegDesc* tab, int batch, const in
                          long long total_chunks, uint8_t* out);
 
 // ================================================================================================
+// JPEG encode, all of it (kernels_jpeg_enc.hip; the arithmetic and the code words are jpeg_math.h's, shared with the host definition)
+// ================================================================================================
+// One image of a ragged batch.  Its blocks are [block0, block0 + blocks) of the batch in SCAN order: MCU after MCU, in an MCU the
+// hs * vs luma blocks row-major, then Cb, then Cr (a grey image: one block per MCU).
+struct JpegEncDesc {
+    const uint8_t* rgb;        // device, h*w*3, any alignment
+    long long block0, blocks;
+    int h, w, sampling, ncomp; // sampling: jpeg_math.h ENC_*
+    int hs, vs, mcus_x, blocks_per_mcu;
+    int header0, header_len;   // the file's bytes before the scan, in the batch's header blob
+    int reserved[4];           // (the size stays a multiple of 16)
+    uint16_t quant[2][64];     // luma, chroma; natural order
+};
+static_assert(sizeof(JpegEncDesc) % 16 == 0, "JpegEncDesc: a table of them keeps 16-byte alignment");
+// entry[symbol] = length << 16 | code, [0] luma, [1] chroma — jpeg_enc_host.h's EncHuffman, as the device reads it
+struct JpegEncHuffman {
+    uint32_t dc[2][16];
+    uint32_t ac[2][256];
+    uint8_t zigzag_of[64];     // natural index -> zigzag position
+};
+constexpr int JPEG_ENC_CHUNK = 128;            // bytes of unstuffed scan per stuffing thread; an image's scan starts on a chunk boundary
+constexpr int JPEG_ENC_BLOCK_BYTES = 208;      // >= the 1660 bits a block can cost: DC 11 + 11, 63 x (16 + 10)
+// The device buffers of one call, all but `tab`, `huff` and `headers` written by the launches.  max_chunks = the chunks the scans of all
+// images can need at JPEG_ENC_BLOCK_BYTES a block; stream holds max_chunks * JPEG_ENC_CHUNK bytes (cleared by jpeg_encode_forward).
+struct JpegEncBuffers {
+    const JpegEncDesc* tab;
+    const JpegEncHuffman* huff;
+    const uint8_t* headers;
+    int16_t* coef;                   // total_blocks * 64, zigzag order within a block
+    uint32_t* block_bits;            // total_blocks
+    unsigned long long* block_scan;  // total_blocks + 1: exclusive sum of block_bits over the whole batch
+    long long* image_chunk0;         // batch + 1: first chunk of each image's scan in `stream`
+    long long* image_bytes;          // batch: bytes of each image's unstuffed scan
+    uint32_t* stream;                // words, most significant bit first
+    uint32_t* chunk_ff;              // max_chunks: FF bytes per chunk
+    unsigned long long* chunk_scan;  // max_chunks + 1
+    long long* file_offsets;         // batch + 1: the result, bytes into `files`
+    uint8_t* files;                  // files_capacity bytes
+    long long max_chunks, files_capacity;
+};
+// One fill and eight launches whatever the batch: forward DCT, code lengths, their scan, the bits, FF counts, their scan, stuffing, headers + EOI.
+void jpeg_encode_forward(hipStream_t s, const JpegEncBuffers& b, int batch, long long total_blocks);
+
+// ================================================================================================
 // Convolution family + element-wise helpers (kernels_conv.hip)
 // ================================================================================================
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_SIGMOID = 2 };

@@ -2,7 +2,11 @@
 
 Baseline JPEG (grey or YCbCr, 4:4:4 / 4:2:2 / 4:2:0) decoded to libjpeg's bytes: the entropy decoder on the host, dequantisation,
 inverse DCT, chroma upsampling and colour conversion on the GPU.  ``info`` and ``decode_host`` need no GPU; ``decode_host`` is the
-scalar definition ``decode_batch`` is held to.  No codec is imported here."""
+scalar definition ``decode_batch`` is held to.
+
+JPEG files out: ``encode_host`` is the scalar definition of the encoder (libjpeg's default compressor: Annex K tables at a quality,
+the standard Huffman tables), ``encode_batch`` the same files from the GPU, where every stage of the encoder runs; only the files'
+bytes come back.  No codec is imported here."""
 from __future__ import annotations
 
 import ctypes as C
@@ -75,3 +79,76 @@ def decode_batch(files: Sequence[bytes], device: bool = True) -> Tuple[list, Lis
     got = [(int(hs[b]), int(ws[b])) for b in range(B)]
     images = [buf[int(offsets[b]):int(offsets[b]) + h * w * 3].reshape(h, w, 3) for b, (h, w) in enumerate(got)]
     return images, got
+
+
+SAMPLING = {"444": 0, "422": 1, "420": 2, "grey": 3, "gray": 3}
+
+
+def _sampling(sampling) -> int:
+    if isinstance(sampling, str):
+        if sampling not in SAMPLING:
+            raise ValueError(f"sampling {sampling!r}: expected one of {sorted(SAMPLING)}")
+        return SAMPLING[sampling]
+    return int(sampling)
+
+
+def encode_host(rgb, quality: int = 90, sampling="420") -> bytes:
+    """An (h, w, 3) uint8 RGB image → the bytes of a baseline JPEG file, the whole encoder on the host (``mrcnn_jpeg_encode_host``):
+    the definition ``encode_batch`` is held to.  sampling: "444", "422", "420" or "grey" (one component, the luma)."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError(f"the image has shape {tuple(rgb.shape)}, expected (h, w, 3)")
+    h, w, s = int(rgb.shape[0]), int(rgb.shape[1]), _sampling(sampling)
+    n = C.c_int64(0)
+    _lib.check(_lib.lib().mrcnn_jpeg_encode_host(rgb.ctypes.data, h, w, int(quality), s, None, 0, C.byref(n)))
+    out = np.empty(int(n.value), dtype=np.uint8)
+    _lib.check(_lib.lib().mrcnn_jpeg_encode_host(rgb.ctypes.data, h, w, int(quality), s, out.ctypes.data, out.size, C.byref(n)))
+    return out.tobytes()
+
+
+def image_table(images):
+    """list of (h, w, 3) uint8 numpy arrays or CUDA tensors → (mrcnn_image table, memspace, what keeps the pixels alive)."""
+    images = list(images)
+    table = (_lib.Image * max(1, len(images)))()
+    on_host = len(images) == 0 or isinstance(images[0], np.ndarray)
+    keep = []
+    for b, im in enumerate(images):
+        if on_host:
+            im = np.ascontiguousarray(im, dtype=np.uint8)
+            ptr = im.ctypes.data
+        else:
+            import torch
+            if not (im.is_cuda and im.dtype == torch.uint8):
+                raise ValueError(f"image {b}: expected a uint8 CUDA tensor")
+            im = im.contiguous()
+            ptr = im.data_ptr()
+        if im.ndim != 3 or im.shape[2] != 3:
+            raise ValueError(f"image {b} has shape {tuple(im.shape)}, expected (h, w, 3)")
+        keep.append(im)
+        table[b].rgb, table[b].height, table[b].width = ptr, int(im.shape[0]), int(im.shape[1])
+    return table, (_lib.HOST if on_host else _lib.DEVICE), keep
+
+
+def encode_batch(images, quality: int = 90, sampling="420") -> List[bytes]:
+    """A batch of images of any sizes → their JPEG files in one call (``mrcnn_jpeg_encode_batch``), byte for byte what
+    ``encode_host`` writes for each.  images: numpy arrays (copied up) or uint8 CUDA tensors (read in place, e.g. what
+    ``detection.render_detections_source`` left on the device).  The buffer is sized from the call's own answer: a first attempt
+    at one byte per pixel, and when that is too small, a second at the size the first one reported."""
+    table, space, keep = image_table(images)
+    B = len(keep)
+    if B == 0:
+        return []
+    offsets = np.zeros(B + 1, dtype=np.int64)
+    capacity = max(4096, sum(int(im.shape[0]) * int(im.shape[1]) for im in keep) + 1024 * B)
+    for _ in range(2):
+        out = np.empty(capacity, dtype=np.uint8)
+        code = _lib.lib().mrcnn_jpeg_encode_batch(table, B, space, int(quality), _sampling(sampling), out.ctypes.data, out.size, offsets.ctypes.data)
+        if code == 4 and int(offsets[B]) > capacity:        # MRCNN_ERR_SHAPE from the capacity check: offsets[B] is the size needed
+            capacity = int(offsets[B])
+            continue
+        _lib.check(code)
+        break
+    else:
+        _lib.check(code)
+    del keep
+    return [out[int(offsets[b]):int(offsets[b + 1])].tobytes() for b in range(B)]

@@ -177,6 +177,12 @@ class MaskRCNN(_Model):
         det, mask = self.predict_images(images)
         return render_detections_source(images, det, mask, self.image_height, self.image_width, **kw)
 
+    def render_jpegs(self, images, quality: int = 90, sampling="420", **kw):
+        """render_images followed by jpeg.encode_batch on the device result: the overlays as JPEG files, a list of bytes.  For CUDA
+        images the rendered pixels never exist in host memory — only the files cross back.  A convenience: no device work of its own."""
+        from .jpeg import encode_batch
+        return encode_batch(self.render_images(images, **kw), quality=quality, sampling=sampling)
+
     def predict_into(self, images, det, mask, sync: bool = True):
         """Device tensors in, pre-allocated device tensors out (bench loop: no allocation, optional no sync)."""
         B, H, W, _ = images.shape
