@@ -6,7 +6,10 @@
  *
  *   cc -std=c99 -Iinclude examples/maskrcnn_predict_jpeg.c -Lmask-rcnn-coreml_amd -lmaskrcnn_hip \
  *      -Wl,-rpath,$PWD/mask-rcnn-coreml_amd -Wl,-rpath-link,/opt/rocm/lib -o maskrcnn_predict_jpeg
- *   ./maskrcnn_predict_jpeg <artefact dir> <file.jpg> [more.jpg ...]
+ *   ./maskrcnn_predict_jpeg <artefact dir> <file.jpg> [more.jpg ...] [device-entropy]
+ *
+ * A trailing word `device-entropy` decodes the Huffman streams on the GPU as well (mrcnn_maskrcnn_predict_jpegs_on with
+ * MRCNN_JPEG_ENTROPY_DEVICE, opt-in): the output is the same.
  *
  * Prints `seconds`, then per file `image <k> <height> <width> detections <n>` and one line per detection with
  * score > 0.7: row, class, score, the box normalized in the letterboxed frame (mrcnn_unletterbox_boxes maps it
@@ -59,7 +62,8 @@ int main(int argc, char** argv)
         return 64;
     }
     const char* dir = argv[1];
-    const int batch = argc - 2;
+    const int entropy = argc > 3 && strcmp(argv[argc - 1], "device-entropy") == 0 ? MRCNN_JPEG_ENTROPY_DEVICE : MRCNN_JPEG_ENTROPY_HOST;
+    const int batch = argc - 2 - (entropy == MRCNN_JPEG_ENTROPY_DEVICE ? 1 : 0);
     const int mask_size = 28;
     char path[4][4096];
     snprintf(path[0], sizeof path[0], "%s/anchors.bin", dir);
@@ -92,7 +96,7 @@ int main(int argc, char** argv)
     if (!det || !masks || !recs) { fprintf(stderr, "out of memory\n"); return 70; }
 
     const double t0 = now_s();
-    CHECK(mrcnn_maskrcnn_predict_jpegs(model, files, batch, MRCNN_HOST, det, masks, heights, widths));
+    CHECK(mrcnn_maskrcnn_predict_jpegs_on(model, files, batch, MRCNN_HOST, entropy, det, masks, heights, widths));
     const double t1 = now_s();
 
     printf("seconds %.6f\n", t1 - t0);

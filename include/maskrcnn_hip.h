@@ -459,6 +459,19 @@ MRCNN_API int mrcnn_jpeg_decode_batch(const mrcnn_jpeg* files, int batch, int me
                                       int32_t* heights, int32_t* widths);
 MRCNN_API int mrcnn_maskrcnn_predict_jpegs(mrcnn_model* model, const mrcnn_jpeg* files, int batch, int memspace, float* detections,
                                            float* masks, int32_t* heights, int32_t* widths);
+/* The same two entries with the ENTROPY stage chosen by the caller.  MRCNN_JPEG_ENTROPY_HOST is what the entries above run.
+ * MRCNN_JPEG_ENTROPY_DEVICE (opt-in) decodes the Huffman streams on the device too — self-synchronising parallel decoding
+ * (kernels_jpeg_entropy.hip): the files' bytes, not their coefficients, are uploaded, and the host does a marker scan only.  A file the
+ * device's verdict does not call clean (a damaged stream, fill bytes before a marker, a stream that does not resynchronise within the
+ * round cap) goes through the host decoder after all, whose coefficients, status and message are then the call's: for every input the
+ * bytes, the status and the message equal MRCNN_JPEG_ENTROPY_HOST's.  LIMIT: the number of synchronisation launches is set from the files'
+ * sizes and capped (4 with the 128-byte units): an intact file in which a wrong decoder state survives more than 64 KB of stream is
+ * given to the host decoder too — same result, the host's speed.  Any other `entropy` -> MRCNN_ERR_INVALID. */
+enum { MRCNN_JPEG_ENTROPY_HOST = 0, MRCNN_JPEG_ENTROPY_DEVICE = 1 };
+MRCNN_API int mrcnn_jpeg_decode_batch_on(const mrcnn_jpeg* files, int batch, int memspace, int entropy, uint8_t* out_rgb,
+                                         const int64_t* out_offsets, int32_t* heights, int32_t* widths);
+MRCNN_API int mrcnn_maskrcnn_predict_jpegs_on(mrcnn_model* model, const mrcnn_jpeg* files, int batch, int memspace, int entropy,
+                                              float* detections, float* masks, int32_t* heights, int32_t* widths);
 
 /* JPEG: files out — the rendered overlays of mrcnn_render_detections_source (or any RGB8 image) leave as baseline JPEG files, and the
  * whole encoder runs on the device: colour conversion, chroma downsampling, forward DCT, quantisation, Huffman coding (code lengths

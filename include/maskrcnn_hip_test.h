@@ -134,8 +134,24 @@ MRCNN_API int mrcnn_bottleneck_stage_nhwc(const float* x, int batch, int h, int 
 
 /* Measurement (tools/jpeg_ab.py): the wall time of the two stages of the calling thread's last mrcnn_jpeg_decode_batch /
  * mrcnn_maskrcnn_predict_jpegs — host_ms: header parsing + the entropy threads; device_ms: from the upload of the coefficients to the end
- * of the second launch (decode_batch only, where the call waits for it; 0 after predict_jpegs, whose launches run ahead of the predict). */
+ * of the second launch (decode_batch only, where the call waits for it; 0 after predict_jpegs, whose launches run ahead of the predict).
+ * With MRCNN_JPEG_ENTROPY_DEVICE host_ms runs from the headers to the verdict words: marker scan, upload of the bytes, the entropy launches, their synchronise
+ * and any fallback; device_ms is the inverse DCT and the colour conversion as before. */
 MRCNN_API int mrcnn_jpeg_last_stage_ms(float* host_ms, float* device_ms);
+
+/* The quantised coefficients of a batch of JPEG files — what the entropy stage hands to the inverse DCT — from the host decoder
+ * (entropy MRCNN_JPEG_ENTROPY_HOST), the device stage (MRCNN_JPEG_ENTROPY_DEVICE) or the sequential host MODEL of the device stage (2:
+ * csrc/jpeg_entropy_host.cpp, the same step function phase for phase); HOST and the model need no GPU.  coef (host, `capacity` int16):
+ * file b's blocks of 64 (natural order, component after component over the MCU-padded grids) start at block0[b]; block0[batch] = the
+ * batch's blocks, written before capacity is checked (too small -> MRCNN_ERR_SHAPE).  Device and model include the fallback: a file they
+ * do not call clean is decoded by the host decoder, and a file that one refuses fails the call as "file N of the batch: ...".
+ * stats[4] = {files decoded clean on the device / model, files that fell back, most rounds a workgroup needed, units in the batch}.
+ * unit_bytes: EVERY per-thread partition of the scan bytes, a power of two in 4..1024 (0 = production, 128); max_rounds: cap of the
+ * rounds inside a synchronisation launch and of the launches (0 = production; 1 leaves no round to confirm a state, so every file of
+ * more than one unit falls back).  Non-zero knobs work only under MRCNN_TEST_KNOBS=1 (else MRCNN_ERR_UNSUPPORTED); bad values ->
+ * MRCNN_ERR_INVALID. */
+MRCNN_API int mrcnn_jpeg_coefficients(const mrcnn_jpeg* files, int batch, int entropy, int unit_bytes, int max_rounds, int16_t* coef,
+                                      int64_t capacity, int64_t* block0, int32_t* stats);
 
 #ifdef __cplusplus
 }

@@ -41,13 +41,14 @@ EXPORTED_SYMBOLS = [
     "mrcnn_rle_iou", "mrcnn_box_iou_xywh", "mrcnn_coco_match", "mrcnn_rle_from_polygons",
     "mrcnn_rle_from_polygons_batch", "mrcnn_coco_accumulate",
     "mrcnn_jpeg_info", "mrcnn_jpeg_decode_host", "mrcnn_jpeg_decode_batch", "mrcnn_maskrcnn_predict_jpegs",
+    "mrcnn_jpeg_decode_batch_on", "mrcnn_maskrcnn_predict_jpegs_on",
     "mrcnn_jpeg_encode_host", "mrcnn_jpeg_encode_batch",
 ]
 # declared in include/maskrcnn_hip_test.h (test / measurement entry points of the same library)
 TEST_SYMBOLS = [
     "mrcnn_bench_conv", "mrcnn_bench_conv_dtype", "mrcnn_model_conv_profile_enable", "mrcnn_model_conv_profile_get",
     "mrcnn_model_conv_profile_shapes", "mrcnn_conv2d_nhwc", "mrcnn_debug_set", "mrcnn_bottleneck_nhwc", "mrcnn_bench_mfma_probe", "mrcnn_model_conv_profile_group", "mrcnn_bottleneck_first_nhwc", "mrcnn_bottleneck_stage_nhwc", "mrcnn_model_conv_profile_bytes",
-    "mrcnn_jpeg_last_stage_ms",
+    "mrcnn_jpeg_last_stage_ms", "mrcnn_jpeg_coefficients",
 ]
 
 
@@ -167,6 +168,9 @@ def lib():
     L.mrcnn_jpeg_encode_host.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]
     L.mrcnn_jpeg_encode_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp]
     L.mrcnn_jpeg_last_stage_ms.argtypes = [f32p, f32p]
+    L.mrcnn_jpeg_decode_batch_on.argtypes = [C.POINTER(Jpeg), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.mrcnn_maskrcnn_predict_jpegs_on.argtypes = [vp, C.POINTER(Jpeg), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.mrcnn_jpeg_coefficients.argtypes = [C.POINTER(Jpeg), C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp, vp]
     L.mrcnn_maskrcnn_predict_async.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.mrcnn_maskrcnn_submit.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
     L.mrcnn_maskrcnn_collect.argtypes = [vp, vp, vp, C.POINTER(C.c_int)]

@@ -158,6 +158,7 @@ struct JpegScratch {
     uint8_t* pinned = nullptr;        // hipHostMalloc
     size_t pinned_bytes = 0;
     DevBuf staged, planes, rgb;
+    DevBuf ent_work;                  // MRCNN_JPEG_ENTROPY_DEVICE: the states, counts and verdict words of the entropy launches
     JpegScratch() = default;
     JpegScratch(const JpegScratch&) = delete;
     JpegScratch& operator=(const JpegScratch&) = delete;

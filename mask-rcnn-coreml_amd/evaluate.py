@@ -216,14 +216,16 @@ def evaluate(model: MaskRCNN, images: Iterable[Tuple[int, np.ndarray]], dataset_
 
 
 def evaluate_segm(model: MaskRCNN, images: Iterable[Tuple[int, np.ndarray]], dataset_id: str = "coco", limit: Optional[int] = 5,
-                  verbose: bool = True, batch: int = 1, threshold: float = 0.5, class_to_category=None, score_threshold: float = 0.0):
+                  verbose: bool = True, batch: int = 1, threshold: float = 0.5, class_to_category=None, score_threshold: float = 0.0,
+                  jpeg_entropy: str = "host"):
     """``evaluate(..., batch=k)`` that also hands the masks on: returns (results.proto bytes, [seconds per image], [PBResult],
     COCO results list).  The first three are evaluate's — the same bytes.  The fourth is what a COCO scorer reads
     (coco_results.coco_results: image_id, category_id, bbox in source pixels, score, segmentation as a compressed RLE), one record
     per detection row with score > score_threshold.  Per group of `batch` images everything stays on the device — the images go up
     once, predict_images and detection.masks_rle_source run on device tensors — and only the detection rows and the run lengths come
     back: no full-resolution plane exists anywhere.  The seconds of an image are its group's wall time (predict and encoding) / size.
-    An item's image may also be the ``bytes`` of a JPEG file: such groups go through MaskRCNN.predict_jpegs (jpeg.py), results unchanged."""
+    An item's image may also be the ``bytes`` of a JPEG file: such groups go through MaskRCNN.predict_jpegs (jpeg.py), results unchanged;
+    jpeg_entropy ("host" | "device") is its ``entropy``: where their Huffman streams are decoded — the results are the same."""
     import torch
     from .coco_results import coco_results
     from .detection import masks_rle_source
@@ -246,7 +248,7 @@ def evaluate_segm(model: MaskRCNN, images: Iterable[Tuple[int, np.ndarray]], dat
             raise ValueError(f"images {group[0][0]}..{group[-1][0]} mix JPEG files and decoded arrays in one group of {batch}")
         t0 = time.perf_counter()
         if files[0]:             # compressed bytes: the decode runs on the device too, the decoded images never exist on the host
-            det_g, mask_g, sizes = model.predict_jpegs([img for _, img in group])
+            det_g, mask_g, sizes = model.predict_jpegs([img for _, img in group], entropy=jpeg_entropy)
         else:
             sizes = [(int(img.shape[0]), int(img.shape[1])) for _, img in group]
             dev = [torch.from_numpy(np.ascontiguousarray(img, dtype=np.uint8)).cuda() for _, img in group]
@@ -280,19 +282,19 @@ def evaluate_coco(model: MaskRCNN, annotations_json: str, load_image, dataset_id
 
 def evaluate_coco_scored(model: MaskRCNN, annotations_json: str, load_image, dataset_id: str = "coco", limit: Optional[int] = 5, verbose: bool = True,
                          batch: int = 1, iou_types=("bbox", "segm"), threshold: float = 0.5, class_to_category=None, score_threshold: float = 0.0,
-                         device_gt: bool = False, accumulate_on=None):
+                         device_gt: bool = False, accumulate_on=None, jpeg_entropy: str = "host"):
     """`maskrcnn evaluate` to its end (EvaluateCommand.swift:159-200, then COCOEval/task.py:93-98): evaluate_segm over the first `limit`
     images of the annotation file sorted by id, then coco_eval.score of those results against the same file, restricted to the images
     that were run.  Returns evaluate_segm's four values plus {iou_type: score dict} (``stats``, ``precision``, ``recall``, ``summary``);
     with verbose the twelve lines of every type are printed the way COCOeval prints them.  device_gt: encode the annotation file's masks
     once on the GPU and score against them where they are resident (COCOGroundTruth.to_device); the numbers are the same.  accumulate_on:
-    where COCOeval's accumulate runs ("host", "device", None = coco_eval.DEFAULT_ACCUMULATE_ON), as coco_eval.score takes it."""
+    where COCOeval's accumulate runs ("host", "device", None = coco_eval.DEFAULT_ACCUMULATE_ON), as coco_eval.score takes it.  jpeg_entropy: evaluate_segm's."""
     from .coco import COCO
     from .coco_eval import COCOGroundTruth, score
     coco = COCO(annotations_json)
     items = [(im.id, load_image(im)) for im, _ in coco.makeImageIterator(limit=limit, sortById=True)]
     pb, secs, out, results = evaluate_segm(model, items, dataset_id=dataset_id, limit=None, verbose=verbose, batch=batch, threshold=threshold,
-                                           class_to_category=class_to_category, score_threshold=score_threshold)
+                                           class_to_category=class_to_category, score_threshold=score_threshold, jpeg_entropy=jpeg_entropy)
     gt = COCOGroundTruth(annotations_json)
     scores = {}
     resident = gt.to_device() if device_gt else None

@@ -51,11 +51,27 @@ def decode_host(data) -> np.ndarray:
     return rgb
 
 
-def decode_batch(files: Sequence[bytes], device: bool = True) -> Tuple[list, List[Tuple[int, int]]]:
-    """A batch of JPEG files of any sizes in one call (``mrcnn_jpeg_decode_batch``) → ([ (h_b, w_b, 3) uint8 ], [(h_b, w_b)]).
-    device=True: CUDA tensors, views of one allocation (the decoded images never exist in host memory); False: numpy arrays."""
+ENTROPY = {"host": 0, "device": 1}
+
+
+def entropy_code(entropy) -> int:
+    """"host" | "device" → MRCNN_JPEG_ENTROPY_*; an integer goes through as it is (the library refuses what it does not know)."""
+    if isinstance(entropy, str):
+        if entropy not in ENTROPY:
+            raise ValueError(f"entropy {entropy!r}: expected one of {sorted(ENTROPY)}")
+        return ENTROPY[entropy]
+    return int(entropy)
+
+
+def decode_batch(files: Sequence[bytes], device: bool = True, entropy="host") -> Tuple[list, List[Tuple[int, int]]]:
+    """A batch of JPEG files of any sizes in one call (``mrcnn_jpeg_decode_batch_on``) → ([ (h_b, w_b, 3) uint8 ], [(h_b, w_b)]).
+    device=True: CUDA tensors, views of one allocation (the decoded images never exist in host memory); False: numpy arrays.
+    entropy: "host" (the default) decodes the Huffman streams on the host; "device" (opt-in) on the GPU — self-synchronising parallel
+    decoding: the files' bytes go up instead of their coefficients, and a file the device's verdict does not call clean is decoded by
+    the host after all, so the bytes, and the error for a damaged file, are the same either way."""
     files = list(files)
     B = len(files)
+    entropy = entropy_code(entropy)
     sizes = []
     for f in files:
         i = info(f)
@@ -74,11 +90,31 @@ def decode_batch(files: Sequence[bytes], device: bool = True) -> Tuple[list, Lis
     else:
         buf = np.empty(max(total, 16), dtype=np.uint8)
         ptr, space = buf.ctypes.data, _lib.HOST
-    _lib.check(_lib.lib().mrcnn_jpeg_decode_batch(table, B, space, ptr, offsets.ctypes.data, hs.ctypes.data, ws.ctypes.data))
+    _lib.check(_lib.lib().mrcnn_jpeg_decode_batch_on(table, B, space, entropy, ptr, offsets.ctypes.data, hs.ctypes.data, ws.ctypes.data))
     del keep
     got = [(int(hs[b]), int(ws[b])) for b in range(B)]
     images = [buf[int(offsets[b]):int(offsets[b]) + h * w * 3].reshape(h, w, 3) for b, (h, w) in enumerate(got)]
     return images, got
+
+
+def coefficients(files: Sequence[bytes], entropy=0, unit_bytes: int = 0, max_rounds: int = 0):
+    """Test entry ``mrcnn_jpeg_coefficients`` (include/maskrcnn_hip_test.h): the quantised coefficients of a batch from the host decoder
+    (entropy 0), the device entropy stage (1) or its sequential host model (2) → (coef int16 (blocks, 64), block0 int64 (B + 1),
+    stats = [clean, fell back, rounds, units]).  unit_bytes / max_rounds: its knobs (0 = production)."""
+    files = list(files)
+    B = len(files)
+    table, keep = file_table(files)
+    block0 = np.zeros(B + 1, np.int64)
+    stats = np.zeros(4, np.int32)
+    e = entropy_code(entropy)
+    code = _lib.lib().mrcnn_jpeg_coefficients(table, B, e, int(unit_bytes), int(max_rounds), None, 0, block0.ctypes.data, stats.ctypes.data)
+    if code != 4 or int(block0[B]) <= 0:            # MRCNN_ERR_SHAPE from the capacity check is the sizing answer
+        _lib.check(code)
+    coef = np.zeros((int(block0[B]), 64), np.int16)
+    _lib.check(_lib.lib().mrcnn_jpeg_coefficients(table, B, e, int(unit_bytes), int(max_rounds), coef.ctypes.data, coef.size, block0.ctypes.data,
+                                                  stats.ctypes.data))
+    del keep
+    return coef, block0, stats
 
 
 SAMPLING = {"444": 0, "422": 1, "420": 2, "grey": 3, "gray": 3}

@@ -150,21 +150,22 @@ class MaskRCNN(_Model):
             _lib.check(_lib.lib().mrcnn_maskrcnn_predict_images(self._h, table, B, _lib.DEVICE, det.data_ptr(), mask.data_ptr()))
         return det, mask
 
-    def predict_jpegs(self, files):
-        """predict_images straight from JPEG files (mrcnn_maskrcnn_predict_jpegs): a list of bytes.  The entropy decoders run on the
+    def predict_jpegs(self, files, entropy="host"):
+        """predict_images straight from JPEG files (mrcnn_maskrcnn_predict_jpegs_on): a list of bytes.  The entropy decoders run on the
         host, everything after them on the GPU, and the decoded images stay in staging the handle owns; the results equal
         ``predict_images([jpeg.decode_host(f) for f in files])`` bit for bit.  Returns (det, mask, [(h_b, w_b)]) with det and mask
-        CUDA tensors, like predict_images on CUDA tensors."""
+        CUDA tensors, like predict_images on CUDA tensors.  entropy="device" (opt-in) decodes the Huffman streams on the GPU as well
+        (jpeg.decode_batch explains it); the results are the same."""
         import torch
-        from .jpeg import file_table
+        from .jpeg import entropy_code, file_table
         files = list(files)
         B = len(files)
         table, keep = file_table(files)
         hs, ws = np.zeros(max(1, B), np.int32), np.zeros(max(1, B), np.int32)
         det = torch.empty((B, self.max_detections, 6), dtype=torch.float32, device="cuda")
         mask = torch.empty((B, self.max_detections, self.mask_size, self.mask_size), dtype=torch.float32, device="cuda")
-        _lib.check(_lib.lib().mrcnn_maskrcnn_predict_jpegs(self._h, table, B, _lib.DEVICE, det.data_ptr(), mask.data_ptr(), hs.ctypes.data,
-                                                           ws.ctypes.data))
+        _lib.check(_lib.lib().mrcnn_maskrcnn_predict_jpegs_on(self._h, table, B, _lib.DEVICE, entropy_code(entropy), det.data_ptr(), mask.data_ptr(),
+                                                              hs.ctypes.data, ws.ctypes.data))
         del keep
         return det, mask, [(int(hs[b]), int(ws[b])) for b in range(B)]
 
