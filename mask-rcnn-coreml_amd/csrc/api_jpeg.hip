@@ -59,8 +59,6 @@ struct JpegPlan {
     size_t plane_bytes = 0;
 };
 
-size_t up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // step 1: every file parsed and checked against the decoder's scope; the layout of the batch on the device
 void plan_batch(const char* entry, const mrcnn_jpeg* files, int batch, JpegPlan& plan)
 {
@@ -127,6 +125,24 @@ template <class CoefOf> void decode_on_host(const char* entry, const mrcnn_jpeg*
         if (status[(size_t)i] != MRCNN_OK) fail(status[(size_t)i], "%s: file %d of the batch: %s", entry, which[(size_t)i], errs[(size_t)i].c_str());
 }
 
+// every file of the batch through the host decoder, file b to its place in the batch's coefficient array at `coef`
+void decode_all_on_host(const char* entry, const mrcnn_jpeg* files, const JpegPlan& plan, int16_t* coef)
+{
+    std::vector<int> all(plan.desc.size());
+    for (size_t b = 0; b < all.size(); ++b) all[b] = (int)b;
+    decode_on_host(entry, files, plan, all, [&](int b) { return coef + plan.desc[(size_t)b].block0 * 64; });
+}
+
+// the marker scan of the batch (jpeg_entropy_host.h), for the device stage and for its host model
+jpeg::EntropyPlan entropy_plan(const mrcnn_jpeg* files, int batch, const JpegPlan& plan, int unit_bytes)
+{
+    std::vector<long long> block0((size_t)batch);
+    for (int b = 0; b < batch; ++b) block0[(size_t)b] = plan.desc[(size_t)b].block0;
+    jpeg::EntropyPlan ep;
+    jpeg::plan_entropy(files, plan.hdr.data(), block0.data(), batch, unit_bytes, ep);
+    return ep;
+}
+
 // the knobs of mrcnn_jpeg_coefficients (0 = production) and what it reports
 struct EntropyKnobs {
     int unit_bytes = 0, max_rounds = 0;
@@ -138,12 +154,7 @@ struct EntropyKnobs {
 // is not clean to the host decoder, whose coefficients are uploaded over the device's.  Returns the offset of the coefficients in sc.staged.
 size_t entropy_on_device(const char* entry, hipStream_t s, JpegScratch& sc, const mrcnn_jpeg* files, int batch, JpegPlan& plan, EntropyKnobs& knobs)
 {
-    std::vector<const uint8_t*> data((size_t)batch);
-    std::vector<int64_t> length((size_t)batch);
-    std::vector<long long> block0((size_t)batch);
-    for (int b = 0; b < batch; ++b) { data[(size_t)b] = files[b].data; length[(size_t)b] = files[b].length; block0[(size_t)b] = plan.desc[(size_t)b].block0; }
-    jpeg::EntropyPlan ep;
-    jpeg::plan_entropy(data.data(), length.data(), plan.hdr.data(), block0.data(), batch, knobs.unit_bytes, ep);
+    const jpeg::EntropyPlan ep = entropy_plan(files, batch, plan, knobs.unit_bytes);
     const int nsegs = (int)ep.segs.size(), nunits = (int)ep.unit_seg.size(), nwg = (int)ep.wgs.size();
     // the upload: descriptors | files | segments | unit -> segment | workgroups | bytes ; behind it on the device: the coefficients
     const size_t o_files = up((size_t)batch * sizeof(JpegDesc), 256), o_segs = o_files + up((size_t)batch * sizeof(jpeg::EntFile), 256),
@@ -222,10 +233,7 @@ void decode_on_device(const char* entry, hipStream_t s, JpegScratch& sc, const m
     if (sc.staged.bytes < total) sc.staged.alloc(total);
     if (sc.planes.bytes < plan.plane_bytes) sc.planes.alloc(plan.plane_bytes);
     memcpy(sc.pinned, plan.desc.data(), (size_t)batch * sizeof(JpegDesc));
-    int16_t* const coef = reinterpret_cast<int16_t*>(sc.pinned + table_bytes);
-    std::vector<int> all((size_t)batch);
-    for (int b = 0; b < batch; ++b) all[(size_t)b] = b;
-    decode_on_host(entry, files, plan, all, [&](int b) { return coef + plan.desc[(size_t)b].block0 * 64; });
+    decode_all_on_host(entry, files, plan, reinterpret_cast<int16_t*>(sc.pinned + table_bytes));
 
     HIP_CHECK(hipMemcpyAsync(sc.staged.p, sc.pinned, total, hipMemcpyHostToDevice, s));
     jpeg_decode_forward(s, sc.staged.as<JpegDesc>(), batch, reinterpret_cast<const int16_t*>(sc.staged.as<uint8_t>() + table_bytes), plan.total_blocks,
@@ -286,10 +294,7 @@ extern "C" int mrcnn_jpeg_decode_batch_on(const mrcnn_jpeg* files, int batch, in
             if (sc.rgb.bytes < (size_t)extent) sc.rgb.alloc((size_t)extent);
             o = sc.rgb.as<uint8_t>();
         }
-        struct Drain {          // an error after the upload was queued must not leave it reading the staging the next call rewrites
-            hipStream_t s;
-            ~Drain() { (void)hipStreamSynchronize(s); }
-        } drain{st.s};
+        Drain drain{st.s};
         decode_on_device("jpeg_decode_batch", st.s, sc, files, batch, plan, entropy, o);
         t_host_ms = (float)ms_since(t0);
         const auto t1 = std::chrono::steady_clock::now();
@@ -330,10 +335,7 @@ extern "C" int mrcnn_maskrcnn_predict_jpegs_on(mrcnn_model* model, const mrcnn_j
         }
         JpegScratch& sc = m.jpeg;
         if (sc.rgb.bytes < total) { HIP_CHECK(hipStreamSynchronize(m.stream)); sc.rgb.alloc(total); }
-        struct Drain {
-            hipStream_t s;
-            ~Drain() { (void)hipStreamSynchronize(s); }
-        } drain{m.stream};
+        Drain drain{m.stream};
         decode_on_device("predict_jpegs", m.stream, sc, files, batch, plan, entropy, sc.rgb.as<uint8_t>());
         t_host_ms = (float)ms_since(t0);
         t_device_ms = 0;
@@ -381,29 +383,19 @@ extern "C" int mrcnn_jpeg_coefficients(const mrcnn_jpeg* files, int batch, int e
         EntropyKnobs knobs;
         knobs.unit_bytes = unit_bytes; knobs.max_rounds = max_rounds;
         if (entropy == MRCNN_JPEG_ENTROPY_HOST) {
-            std::vector<int> all((size_t)batch);
-            for (int b = 0; b < batch; ++b) all[(size_t)b] = b;
-            decode_on_host("jpeg_coefficients", files, plan, all, [&](int b) { return coef + plan.desc[(size_t)b].block0 * 64; });
+            decode_all_on_host("jpeg_coefficients", files, plan, coef);
         } else if (entropy == MRCNN_JPEG_ENTROPY_DEVICE) {
             std::lock_guard<std::mutex> lock(g_scratch_mutex);
             JpegScratch& sc = shared_scratch();
             Stream st;
-            struct Drain {
-                hipStream_t s;
-                ~Drain() { (void)hipStreamSynchronize(s); }
-            } drain{st.s};
+            Drain drain{st.s};
             const size_t o_coef = entropy_on_device("jpeg_coefficients", st.s, sc, files, batch, plan, knobs);
             HIP_CHECK(hipMemcpyAsync(coef, sc.staged.as<uint8_t>() + o_coef, (size_t)plan.total_blocks * 64 * sizeof(int16_t), hipMemcpyDeviceToHost, st.s));
             HIP_CHECK(hipStreamSynchronize(st.s));
         } else {
-            std::vector<const uint8_t*> data((size_t)batch);
-            std::vector<int64_t> length((size_t)batch);
-            std::vector<long long> first((size_t)batch);
-            for (int b = 0; b < batch; ++b) { data[(size_t)b] = files[b].data; length[(size_t)b] = files[b].length; first[(size_t)b] = plan.desc[(size_t)b].block0; }
-            jpeg::EntropyPlan ep;
-            jpeg::plan_entropy(data.data(), length.data(), plan.hdr.data(), first.data(), batch, unit_bytes, ep);
+            const jpeg::EntropyPlan ep = entropy_plan(files, batch, plan, unit_bytes);
             std::vector<char> clean;
-            jpeg::entropy_model(ep, data.data(), max_rounds, coef, plan.total_blocks, clean, &knobs.rounds);
+            jpeg::entropy_model(ep, files, max_rounds, coef, plan.total_blocks, clean, &knobs.rounds);
             std::vector<int> fallback;
             for (int b = 0; b < batch; ++b)
                 if (!clean[(size_t)b]) fallback.push_back(b);

@@ -22,8 +22,6 @@ extern "C" int mrcnn_jpeg_encode_host(const uint8_t* rgb, int height, int width,
 
 namespace {
 
-size_t up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // mrcnn_jpeg_encode_batch has no handle to keep its scratch in: one grow-only allocation per process, handed to one call at a time.
 // Never freed — at process exit the HIP runtime may be gone before a static destructor would run.
 DevBuf& shared_scratch() { static DevBuf* b = new DevBuf; return *b; }
@@ -102,15 +100,12 @@ extern "C" int mrcnn_jpeg_encode_batch(const mrcnn_image* images, int batch, int
         memcpy(staged.data() + o_tab, desc.data(), (size_t)batch * sizeof(JpegEncDesc));
         JpegEncHuffman huff;
         memcpy(&huff, &jpeg::enc_huffman(), sizeof(jpeg::EncHuffman));
-        for (int k = 0; k < 64; ++k) huff.zigzag_of[jpeg::kZigzagOrder[k]] = (uint8_t)k;
+        for (int k = 0; k < 64; ++k) huff.zigzag_of[jpeg::kZigzag[k]] = (uint8_t)k;
         memcpy(staged.data() + o_huff, &huff, sizeof huff);
         memcpy(staged.data() + o_hdr, headers.data(), headers.size());
 
         Stream st;
-        struct Drain {          // an error after work was queued must not leave it running on scratch the next call rewrites
-            hipStream_t s;
-            ~Drain() { (void)hipStreamSynchronize(s); }
-        } drain{st.s};
+        Drain drain{st.s};
         HIP_CHECK(hipMemcpyAsync(base, staged.data(), upload, hipMemcpyHostToDevice, st.s));
         if (memspace == MRCNN_HOST)
             for (int b = 0; b < batch; ++b)

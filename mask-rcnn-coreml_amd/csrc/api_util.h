@@ -1,5 +1,5 @@
 // api_util.h — what more than one api*.hip translation unit needs: row staging between the caller's memory space and
-// dense device buffers, and an owned stream.  Header-only; internal linkage, nothing here is exported.
+// dense device buffers, an owned stream and the guard that drains one, and rounding up.  Header-only; internal linkage, nothing here is exported.
 #pragma once
 #include "engine.h"
 
@@ -29,5 +29,14 @@ struct Stream {
     Stream() { require_gpu(); HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
     ~Stream() { if (s) (void)hipStreamDestroy(s); }
 };
+
+// Synchronises `s` when the scope ends, however it ends: an error after work was queued must not leave it running on staging or scratch
+// that the next call rewrites.
+struct Drain {
+    hipStream_t s;
+    ~Drain() { (void)hipStreamSynchronize(s); }
+};
+
+static size_t up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 }  // namespace mrcnn

@@ -11,10 +11,6 @@
 namespace mrcnn {
 namespace jpeg {
 
-const uint8_t kZigzagOrder[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                  41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                  30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
 namespace {
 
 // ITU-T T.81 Annex K.1, natural order
@@ -144,7 +140,7 @@ std::vector<uint8_t> enc_header(int height, int width, int quality, int sampling
     put16(o, 0xFFDB); put16(o, 2 + 65 * tables);
     for (int t = 0; t < tables; ++t) {
         o.push_back((uint8_t)t);
-        for (int k = 0; k < 64; ++k) o.push_back((uint8_t)quant[t][kZigzagOrder[k]]);
+        for (int k = 0; k < 64; ++k) o.push_back((uint8_t)quant[t][kZigzag[k]]);
     }
     put16(o, 0xFFC0); put16(o, 8 + 3 * g.ncomp);
     o.push_back(8); put16(o, height); put16(o, width); o.push_back((uint8_t)g.ncomp);
@@ -212,7 +208,7 @@ int encode_host(const uint8_t* rgb, int height, int width, int quality, int samp
                     pred[c] = ws[0];
                     int run = 0;
                     for (int z = 1; z < 64; ++z) {
-                        const int32_t v = ws[kZigzagOrder[z]];
+                        const int32_t v = ws[kZigzag[z]];
                         if (v == 0) { ++run; continue; }
                         bw.put(code_ac(huff.ac[t], run, v));
                         run = 0;

@@ -10,11 +10,10 @@
 #include <vector>
 
 #include "../../include/maskrcnn_hip.h"
+#include "jpeg_huff.h"
 
 namespace mrcnn {
 namespace jpeg {
-
-extern const uint8_t kZigzagOrder[64];          // zigzag position -> natural (row-major) index
 
 struct EncGeometry {
     int ncomp;                  // 1 (grey) or 3

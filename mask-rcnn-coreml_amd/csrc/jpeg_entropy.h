@@ -1,5 +1,6 @@
-// jpeg_entropy.h — the Huffman decoding step of the self-synchronising entropy stage, written once for both sides: the kernels of
-// kernels_jpeg_entropy.hip and the sequential model of jpeg_entropy_host.cpp run these functions.  Plain C++ (g++ builds it alone).
+// jpeg_entropy.h — the Huffman decoding step of the self-synchronising entropy stage and one unit's turn around it (its bytes, its
+// context, its sink, the writing pass's verdict), written once for both sides: the kernels of kernels_jpeg_entropy.hip and the
+// sequential model of jpeg_entropy_host.cpp run these functions.  Plain C++ (g++ builds it alone).
 //
 // The scan of a file is cut at its markers into SEGMENTS (a restart interval, or the whole scan): each starts on an MCU boundary with
 // zeroed predictors.  A segment is cut into UNITS of unit_bytes raw bytes (stuffed zeros included).  A decoder state is
@@ -10,13 +11,7 @@
 // above 15, a zero run that leaves the block, bits consumed past the end of the segment, a block outside the image.  The one place where
 // an anomaly is not one: in the last 7 bits of a segment it only says that those bits are padding and no further block.
 #pragma once
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define MRCNN_ENT_HD __host__ __device__ inline
-#else
-#define MRCNN_ENT_HD inline
-#endif
+#include "jpeg_huff.h"
 
 namespace mrcnn {
 namespace jpeg {
@@ -25,16 +20,6 @@ constexpr int ENT_UNIT_BYTES = 128;        // production unit
 constexpr int ENT_WG_UNITS = 256;          // units (= threads) of a workgroup; a workgroup serves ONE file
 constexpr int ENT_SYNC_BYTES = 65536;      // a wrong state may survive this much stream before the file is given to the host decoder
 constexpr int ENT_MAX_BPM = 6;             // blocks per MCU of the sampling modes the parser admits (4:2:0)
-
-// jpeg_host.cpp's HuffTable, self-contained (the symbols inside): what a workgroup copies into LDS, 356 words
-struct EntTable {
-    uint16_t look[512];         // 9 leading bits -> (length << 8) | symbol, 0 = longer than 9 bits (or no such code)
-    int32_t maxcode[18];        // largest code of each length, -1 = none
-    int32_t valoff[17];         // index of a length's first symbol minus its first code
-    int32_t count;
-    uint8_t vals[256];
-};
-static_assert(sizeof(EntTable) == 1424, "EntTable is copied as 356 words");
 
 struct EntFile {
     long long byte0;            // the file's first byte in the batch's byte blob (multiple of 16)
@@ -46,7 +31,7 @@ struct EntFile {
     int wg0, nwg;
     int bpm, nluma, hs, vs;     // blocks per MCU; of them luma (hs * vs)
     int mcus_x, mcus_y, ncomp, reserved;
-    EntTable tab[6];            // DC of components 0..2, then AC of components 0..2
+    HuffTable tab[6];           // DC of components 0..2, then AC of components 0..2
 };
 struct EntSeg {
     long long b0, b1;           // raw bytes [b0, b1) of the file; b1 is the FF of the marker that ends the segment
@@ -64,14 +49,14 @@ enum { ENT_BAD_WRITE = 1,      // an anomaly in the writing pass, or a unit that
 
 typedef unsigned long long ent_state;
 constexpr ent_state ENT_INVALID = ~0ull;
-MRCNN_ENT_HD ent_state ent_pack(long long bitpos, int blk, int zz) { return (ent_state)bitpos | ((ent_state)blk << 32) | ((ent_state)zz << 40); }
-MRCNN_ENT_HD long long ent_pos(ent_state s) { return (long long)(s & 0xFFFFFFFFull); }
-MRCNN_ENT_HD int ent_blk(ent_state s) { return (int)((s >> 32) & 0xFF); }
-MRCNN_ENT_HD int ent_zz(ent_state s) { return (int)((s >> 40) & 0xFF); }
+MRCNN_HUFF_HD ent_state ent_pack(long long bitpos, int blk, int zz) { return (ent_state)bitpos | ((ent_state)blk << 32) | ((ent_state)zz << 40); }
+MRCNN_HUFF_HD long long ent_pos(ent_state s) { return (long long)(s & 0xFFFFFFFFull); }
+MRCNN_HUFF_HD int ent_blk(ent_state s) { return (int)((s >> 32) & 0xFF); }
+MRCNN_HUFF_HD int ent_zz(ent_state s) { return (int)((s >> 40) & 0xFF); }
 
 struct EntCtx {
     const uint8_t* data;        // the file's bytes
-    const EntTable* tab;        // EntFile::tab (the kernels: its copy in LDS)
+    const HuffTable* tab;       // EntFile::tab (the kernels: its copy in LDS)
     const uint8_t* zigzag;      // zigzag position -> natural index
     long long b0, b1;           // the segment: raw bytes [b0, b1)
     int bpm, nluma;
@@ -92,7 +77,7 @@ struct EntResult {
 };
 
 // scan-order number -> block of the batch's coefficient array (seq < mcus * bpm: inside the component grids)
-MRCNN_ENT_HD long long ent_block_index(const EntSink& k, long long seq, int bpm, int nluma)
+MRCNN_HUFF_HD long long ent_block_index(const EntSink& k, long long seq, int bpm, int nluma)
 {
     const long long m = seq / bpm;
     const int b = (int)(seq - m * bpm);
@@ -105,7 +90,7 @@ MRCNN_ENT_HD long long ent_block_index(const EntSink& k, long long seq, int bpm,
 }
 
 // the state a unit starts from when nothing better is known: a block starting at its first byte that is not a stuffed zero
-MRCNN_ENT_HD ent_state ent_guess(const uint8_t* data, long long seg_b0, long long unit_b0)
+MRCNN_HUFF_HD ent_state ent_guess(const uint8_t* data, long long seg_b0, long long unit_b0)
 {
     const bool stuffed = unit_b0 > seg_b0 && data[unit_b0 - 1] == 0xFF;
     return ent_pack((unit_b0 + (stuffed ? 1 : 0)) * 8, 0, 0);
@@ -113,7 +98,7 @@ MRCNN_ENT_HD ent_state ent_guess(const uint8_t* data, long long seg_b0, long lon
 
 // DATA bits between position P and the marker that ends segment [b0, b1): the bytes are not unstuffed, so when the segment's last data
 // byte is an FF, its stuffed 00 stands in front of the marker and holds no bits (P never rests inside it).
-MRCNN_ENT_HD long long ent_bits_left(const uint8_t* data, long long b0, long long b1, long long P)
+MRCNN_HUFF_HD long long ent_bits_left(const uint8_t* data, long long b0, long long b1, long long P)
 {
     const long long raw = b1 * 8 - P;
     if (raw < 8 || raw >= 16) return raw < 0 ? 0 : raw;          // behind the pair (or at the end) | too far to matter
@@ -122,7 +107,7 @@ MRCNN_ENT_HD long long ent_bits_left(const uint8_t* data, long long b0, long lon
 
 // Decodes the symbols that start in raw bytes [unit_b0, unit_b1) of the segment from state `in`; sink != nullptr: writes them (the DC
 // as its difference).  Every read is below c.b1; the loop runs once per symbol, at most once per bit of the unit.
-MRCNN_ENT_HD EntResult decode_unit(const EntCtx& c, long long unit_b0, long long unit_b1, ent_state in, const EntSink* sink)
+MRCNN_HUFF_HD EntResult decode_unit(const EntCtx& c, long long unit_b0, long long unit_b1, ent_state in, const EntSink* sink)
 {
     EntResult r;
     r.state = ENT_INVALID; r.blocks = 0; r.anomaly = 1;
@@ -160,23 +145,10 @@ MRCNN_ENT_HD EntResult decode_unit(const EntCtx& c, long long unit_b0, long long
         const int sh = (int)(P & 7);
         const uint32_t w = (uint32_t)((acc << (16 + sh)) >> 32);       // the next 32 bits (41 are loaded)
         const int comp = blk < c.nluma ? 0 : blk - c.nluma + 1;
-        const EntTable& t = c.tab[(zz == 0 ? 0 : 3) + comp];
-        int len = 0, sym = 0;
-        const int e = t.look[w >> 23];
-        if (e) {
-            len = e >> 8; sym = e & 255;
-        } else {
-            for (int l = 10; l <= 16; ++l) {
-                const int code = (int)(w >> (32 - l));
-                if (code <= t.maxcode[l]) {
-                    const int idx = code + t.valoff[l];
-                    if (idx < 0 || idx >= t.count) { if (trial) goto padding; return r; }
-                    len = l; sym = t.vals[idx];
-                    break;
-                }
-            }
-            if (!len) { if (trial) goto padding; return r; }                          // no such code
-        }
+        const HuffTable& t = c.tab[(zz == 0 ? 0 : 3) + comp];
+        const int e = huff_lookup(t, w);
+        if (!e) { if (trial) goto padding; return r; }                                // no such code
+        const int len = e >> 8, sym = e & 255;
         int s, run = 0;
         if (zz == 0) {
             if (sym > 15) { if (trial) goto padding; return r; }                      // DC category
@@ -227,15 +199,71 @@ padding:
     return r;
 }
 
+// One unit's turn, the same on both sides: where it lies, what it decodes with, where it writes, and what the writing pass says of it.
+struct EntUnit {
+    long long ub, ue;           // raw bytes [ub, ue) of the file
+    bool first;                 // of its segment: it starts from the segment's own state, never from a neighbour's
+};
+MRCNN_HUFF_HD EntUnit ent_unit(const EntSeg& s, int u, int unit_bytes)
+{
+    EntUnit q;
+    q.ub = s.b0 + (long long)(u - s.unit0) * unit_bytes;
+    q.ue = q.ub + unit_bytes < s.b1 ? q.ub + unit_bytes : s.b1;
+    q.first = u == s.unit0;
+    return q;
+}
+
+// data: the file's bytes; tab: EntFile::tab or a copy of it.  Two clamps keep a plan that is not plan_entropy's from reading or writing
+// outside the file: b1 to the file's length here, seq_end to the MCU grid in ent_write_unit.  Both are no-ops for every plan that
+// plan_entropy makes: it accepts a segment only with end + 1 < length, and its segments' nblocks sum to mcus * bpm.
+MRCNN_HUFF_HD EntCtx ent_ctx(const EntFile& f, const EntSeg& s, const uint8_t* data, const HuffTable* tab, const uint8_t* zigzag)
+{
+    EntCtx c;
+    c.data = data; c.tab = tab; c.zigzag = zigzag;
+    c.b0 = s.b0; c.b1 = s.b1 < f.length ? s.b1 : f.length; c.bpm = f.bpm; c.nluma = f.nluma;
+    return c;
+}
+
+MRCNN_HUFF_HD EntSink ent_sink(const EntFile& f, int16_t* coef)
+{
+    EntSink k;
+    k.coef = coef; k.seq0 = 0; k.seq_end = 0;
+    for (int i = 0; i < 3; ++i) { k.block0[i] = f.comp_block0[i]; k.blocks_w[i] = f.comp_blocks_w[i]; }
+    k.hs = f.hs; k.vs = f.vs; k.mcus_x = f.mcus_x;
+    return k;
+}
+
+// The writing pass of unit u of segment s: decodes it from the state its predecessor recorded into coef (the DC as its difference) and
+// returns the status bits.  state: the recorded states, by unit; before / through: the blocks the synchronisation phase counted in the
+// segment's units in front of u / up to and including u (their difference is the count recorded for u).
+MRCNN_HUFF_HD int ent_write_unit(const EntCtx& c, const EntFile& f, const EntSeg& s, int u, int unit_bytes, const ent_state* state, long long before,
+                                 long long through, int16_t* coef)
+{
+    const EntUnit q = ent_unit(s, u, unit_bytes);
+    EntSink k = ent_sink(f, coef);
+    const long long mcu_blocks = (long long)f.mcus_x * f.mcus_y * f.bpm;
+    k.seq0 = s.first_block + before;
+    k.seq_end = s.first_block + s.nblocks < mcu_blocks ? s.first_block + s.nblocks : mcu_blocks;       // (never behind the component grids)
+    const EntResult r = decode_unit(c, q.ub, q.ue, q.first ? ent_pack(s.b0 * 8, 0, 0) : state[u - 1], &k);
+    int bad = 0;
+    if (r.anomaly || r.state != state[u] || r.blocks != through - before) bad |= ENT_BAD_WRITE;
+    if (u == s.unit0 + s.nunits - 1) {
+        const bool whole = !r.anomaly && ent_zz(r.state) == 0 && ent_blk(r.state) == 0 && ent_bits_left(c.data, c.b0, c.b1, ent_pos(r.state)) < 8 &&
+                           through == s.nblocks;
+        if (!whole) bad |= ENT_BAD_COUNT;
+    }
+    return bad;
+}
+
 // the launches of the synchronisation phase and the rounds inside one, from the knobs (0 = production)
-MRCNN_ENT_HD int ent_launches(int unit_bytes, int max_file_wgs, int max_rounds)
+MRCNN_HUFF_HD int ent_launches(int unit_bytes, int max_file_wgs, int max_rounds)
 {
     int n = 2 + (ENT_SYNC_BYTES + ENT_WG_UNITS * unit_bytes - 1) / (ENT_WG_UNITS * unit_bytes);
     if (n > max_file_wgs + 1) n = max_file_wgs + 1;
     if (max_rounds > 0 && n > max_rounds) n = max_rounds;
     return n < 1 ? 1 : n;
 }
-MRCNN_ENT_HD int ent_inner_rounds(int max_rounds) { return max_rounds > 0 ? max_rounds : ENT_WG_UNITS + 1; }
+MRCNN_HUFF_HD int ent_inner_rounds(int max_rounds) { return max_rounds > 0 ? max_rounds : ENT_WG_UNITS + 1; }
 
 }  // namespace jpeg
 }  // namespace mrcnn

@@ -6,32 +6,6 @@
 namespace mrcnn {
 namespace jpeg {
 
-const uint8_t kEntZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-// (jpeg_host.cpp's build_table, with the symbols copied in)
-void build_ent_table(const HuffSpec& s, EntTable& t)
-{
-    memset(&t, 0, sizeof t);
-    memcpy(t.vals, s.vals, sizeof t.vals);
-    t.count = s.count;
-    int32_t code = 0;
-    int k = 0;
-    for (int l = 1; l <= 16; ++l) {
-        t.valoff[l] = k - code;
-        for (int i = 0; i < s.bits[l]; ++i, ++k, ++code) {
-            if (l <= 9) {
-                const int first = code << (9 - l), span = 1 << (9 - l);
-                for (int j = 0; j < span; ++j) t.look[first + j] = (uint16_t)((l << 8) | s.vals[k]);
-            }
-        }
-        t.maxcode[l] = s.bits[l] ? code - 1 : -1;
-        code <<= 1;
-    }
-    t.maxcode[17] = 0x7FFFFFFF;
-}
-
 namespace {
 
 // the FF that ends the entropy data starting at `from`: the first one not followed by 00; -1 = none before the end of the data
@@ -50,7 +24,7 @@ int64_t segment_end(const uint8_t* data, int64_t length, int64_t from)
 
 }  // namespace
 
-void plan_entropy(const uint8_t* const* data, const int64_t* length, const Header* hdr, const long long* block0, int batch, int unit_bytes, EntropyPlan& plan)
+void plan_entropy(const mrcnn_jpeg* files, const Header* hdr, const long long* block0, int batch, int unit_bytes, EntropyPlan& plan)
 {
     plan.unit_bytes = unit_bytes > 0 ? unit_bytes : ENT_UNIT_BYTES;
     const int U = plan.unit_bytes;
@@ -59,11 +33,13 @@ void plan_entropy(const uint8_t* const* data, const int64_t* length, const Heade
     plan.blob_bytes = 0; plan.max_file_wgs = 0;
     for (int b = 0; b < batch; ++b) {
         const Header& h = hdr[b];
+        const uint8_t* const data = files[b].data;
+        const int64_t length = files[b].length;
         EntFile& f = plan.files[(size_t)b];
         memset(&f, 0, sizeof f);
         f.byte0 = plan.blob_bytes;
-        f.length = length[b];
-        plan.blob_bytes += (length[b] + 15) / 16 * 16;
+        f.length = length;
+        plan.blob_bytes += (length + 15) / 16 * 16;
         f.ncomp = h.components;
         f.hs = h.h_samp; f.vs = h.v_samp;
         f.nluma = h.components == 1 ? 1 : h.h_samp * h.v_samp;
@@ -72,8 +48,8 @@ void plan_entropy(const uint8_t* const* data, const int64_t* length, const Heade
         for (int c = 0; c < h.components; ++c) {
             f.comp_block0[c] = block0[b] + h.comp[c].block0;
             f.comp_blocks_w[c] = h.comp[c].blocks_w;
-            build_ent_table(h.dc[h.comp[c].td], f.tab[c]);
-            build_ent_table(h.ac[h.comp[c].ta], f.tab[3 + c]);
+            build_huff_table(h.dc[h.comp[c].td], f.tab[c]);
+            build_huff_table(h.ac[h.comp[c].ta], f.tab[3 + c]);
         }
         f.seg0 = (int)plan.segs.size();
         f.unit0 = (int)plan.unit_seg.size();
@@ -81,14 +57,14 @@ void plan_entropy(const uint8_t* const* data, const int64_t* length, const Heade
         // the marker scan
         const int64_t mcus = (int64_t)h.mcus_x * h.mcus_y, R = h.restart_interval ? h.restart_interval : mcus;
         const int64_t nseg = (mcus + R - 1) / R;
-        bool ok = f.bpm <= ENT_MAX_BPM && length[b] < ((int64_t)1 << 28) && nseg < ((int64_t)1 << 24) &&
-                  (int64_t)plan.unit_seg.size() + length[b] / U + nseg < ((int64_t)1 << 30);
+        bool ok = f.bpm <= ENT_MAX_BPM && length < ((int64_t)1 << 28) && nseg < ((int64_t)1 << 24) &&
+                  (int64_t)plan.unit_seg.size() + length / U + nseg < ((int64_t)1 << 30);
         int64_t pos = h.scan_offset;
         for (int64_t k = 0; ok && k < nseg; ++k) {
-            const int64_t end = segment_end(data[b], length[b], pos);
-            if (end <= pos || end + 1 >= length[b]) { ok = false; break; }       // no marker, or no entropy data in front of it
+            const int64_t end = segment_end(data, length, pos);
+            if (end <= pos || end + 1 >= length) { ok = false; break; }          // no marker, or no entropy data in front of it
             const int want = k + 1 == nseg ? 0xD9 : 0xD0 + (int)(k & 7);
-            if (data[b][end + 1] != want) { ok = false; break; }                // (a fill byte FF included)
+            if (data[end + 1] != want) { ok = false; break; }                    // (a fill byte FF included)
             EntSeg s;
             memset(&s, 0, sizeof s);
             s.b0 = pos; s.b1 = end;
@@ -118,7 +94,7 @@ void plan_entropy(const uint8_t* const* data, const int64_t* length, const Heade
     }
 }
 
-void entropy_model(const EntropyPlan& plan, const uint8_t* const* data, int max_rounds, int16_t* coef, long long total_blocks, std::vector<char>& clean,
+void entropy_model(const EntropyPlan& plan, const mrcnn_jpeg* files, int max_rounds, int16_t* coef, long long total_blocks, std::vector<char>& clean,
                    int* rounds)
 {
     const int batch = (int)plan.files.size(), U = plan.unit_bytes;
@@ -127,11 +103,6 @@ void entropy_model(const EntropyPlan& plan, const uint8_t* const* data, int max_
     std::vector<ent_state> state(nunits, ENT_INVALID), wg_exit[2], wg_entry(nwg, ENT_INVALID);
     wg_exit[0].assign(nwg, ENT_INVALID); wg_exit[1].assign(nwg, ENT_INVALID);
     std::vector<int> count(nunits, 0), wg_done(nwg, 0), wg_rounds(nwg, 0), status((size_t)batch, 0), last_change((size_t)batch, 0);
-    auto ctx_of = [&](const EntFile& f, int b, const EntSeg& s) {
-        EntCtx c;
-        c.data = data[b]; c.tab = f.tab; c.zigzag = kEntZigzag; c.b0 = s.b0; c.b1 = s.b1; c.bpm = f.bpm; c.nluma = f.nluma;
-        return c;
-    };
     // phase 1: synchronisation
     for (int launch = 0; launch < launches; ++launch) {
         const int cur = launch & 1, prev = cur ^ 1;
@@ -152,13 +123,13 @@ void entropy_model(const EntropyPlan& plan, const uint8_t* const* data, int max_
                 for (int t = 0; t < g.count; ++t) {
                     const int u = g.unit0 + t;
                     const EntSeg& s = plan.segs[(size_t)plan.unit_seg[(size_t)u]];
-                    const long long ub = s.b0 + (long long)(u - s.unit0) * U, ue = ub + U < s.b1 ? ub + U : s.b1;
-                    ent_state in = u == s.unit0 ? ent_pack(s.b0 * 8, 0, 0) : (t == 0 ? entry : st[at][(size_t)t - 1]);
-                    if (in == ENT_INVALID) in = ent_guess(data[g.file], s.b0, ub);
+                    const EntUnit q = ent_unit(s, u, U);
+                    const EntCtx c = ent_ctx(f, s, files[g.file].data, f.tab, kZigzag);
+                    ent_state in = q.first ? ent_pack(c.b0 * 8, 0, 0) : (t == 0 ? entry : st[at][(size_t)t - 1]);
+                    if (in == ENT_INVALID) in = ent_guess(c.data, c.b0, q.ub);
                     if (n > 0 && in == last_in[(size_t)t]) { st[at ^ 1][(size_t)t] = st[at][(size_t)t]; continue; }
                     last_in[(size_t)t] = in;
-                    const EntCtx c = ctx_of(f, g.file, s);
-                    const EntResult r = decode_unit(c, ub, ue, in, nullptr);
+                    const EntResult r = decode_unit(c, q.ub, q.ue, in, nullptr);
                     if (r.state != st[at][(size_t)t] || r.blocks != cnt[(size_t)t]) any = 1;
                     st[at ^ 1][(size_t)t] = r.state;
                     cnt[(size_t)t] = r.blocks;
@@ -181,30 +152,14 @@ void entropy_model(const EntropyPlan& plan, const uint8_t* const* data, int max_
     for (size_t u = 0; u < nunits; ++u) {
         const EntSeg& s = plan.segs[(size_t)plan.unit_seg[u]];
         const EntFile& f = plan.files[(size_t)s.file];
-        const long long ub = s.b0 + (long long)((int)u - s.unit0) * U, ue = ub + U < s.b1 ? ub + U : s.b1;
-        const ent_state in = (int)u == s.unit0 ? ent_pack(s.b0 * 8, 0, 0) : state[u - 1];
-        const EntCtx c = ctx_of(f, s.file, s);
-        EntSink k;
-        k.coef = coef;
-        k.seq0 = s.first_block + (prefix[u] - prefix[(size_t)s.unit0]);
-        k.seq_end = s.first_block + s.nblocks;
-        for (int i = 0; i < 3; ++i) { k.block0[i] = f.comp_block0[i]; k.blocks_w[i] = f.comp_blocks_w[i]; }
-        k.hs = f.hs; k.vs = f.vs; k.mcus_x = f.mcus_x;
-        const EntResult r = decode_unit(c, ub, ue, in, &k);
-        if (r.anomaly || r.state != state[u] || r.blocks != count[u]) status[(size_t)s.file] |= ENT_BAD_WRITE;
-        if ((int)u == s.unit0 + s.nunits - 1) {
-            const bool whole = !r.anomaly && ent_zz(r.state) == 0 && ent_blk(r.state) == 0 && ent_bits_left(c.data, s.b0, s.b1, ent_pos(r.state)) < 8 &&
-                               prefix[u + 1] - prefix[(size_t)s.unit0] == s.nblocks;
-            if (!whole) status[(size_t)s.file] |= ENT_BAD_COUNT;
-        }
+        const EntCtx c = ent_ctx(f, s, files[s.file].data, f.tab, kZigzag);
+        const long long p0 = prefix[(size_t)s.unit0];
+        status[(size_t)s.file] |= ent_write_unit(c, f, s, (int)u, U, state.data(), prefix[u] - p0, prefix[u + 1] - p0, coef);
     }
     // phase 4: the DC predictors, per component inside each segment, modulo 2^16
     for (const EntSeg& s : plan.segs) {
         const EntFile& f = plan.files[(size_t)s.file];
-        EntSink k;
-        k.coef = coef; k.seq0 = 0; k.seq_end = 0;
-        for (int i = 0; i < 3; ++i) { k.block0[i] = f.comp_block0[i]; k.blocks_w[i] = f.comp_blocks_w[i]; }
-        k.hs = f.hs; k.vs = f.vs; k.mcus_x = f.mcus_x;
+        const EntSink k = ent_sink(f, coef);
         uint16_t pred[3] = {0, 0, 0};
         for (long long q = s.first_block; q < s.first_block + s.nblocks; ++q) {
             const int b = (int)(q % f.bpm), comp = b < f.nluma ? 0 : b - f.nluma + 1;

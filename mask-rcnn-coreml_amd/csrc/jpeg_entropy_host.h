@@ -20,14 +20,9 @@ struct EntropyPlan {
     int max_file_wgs = 0;
 };
 
-extern const uint8_t kEntZigzag[64];
-
-void build_ent_table(const HuffSpec& s, EntTable& t);
-
 // The marker scan.  block0[b]: the file's first block in the batch's coefficient array.  A file whose scan is not "segments of entropy
 // data, RST0..7 in order between them, EOI behind the last" gets nseg = 0: the host decoder decides about it.
-void plan_entropy(const uint8_t* const* data, const int64_t* length, const Header* hdr, const long long* block0, int batch, int unit_bytes,
-                  EntropyPlan& plan);
+void plan_entropy(const mrcnn_jpeg* files, const Header* hdr, const long long* block0, int batch, int unit_bytes, EntropyPlan& plan);
 
 // clean = the verdict: the coefficients of the file are what decode_coefficients writes (and it accepts the file)
 inline bool ent_clean(const EntFile& f, int status, int last_change, int launches)
@@ -37,7 +32,7 @@ inline bool ent_clean(const EntFile& f, int status, int last_change, int launche
 
 // The model: coef (the batch's array, total_blocks * 64) is cleared and written like the device does; clean[b] as above; *rounds = the
 // most rounds a workgroup ran over all launches.
-void entropy_model(const EntropyPlan& plan, const uint8_t* const* data, int max_rounds, int16_t* coef, long long total_blocks, std::vector<char>& clean,
+void entropy_model(const EntropyPlan& plan, const mrcnn_jpeg* files, int max_rounds, int16_t* coef, long long total_blocks, std::vector<char>& clean,
                    int* rounds);
 
 }  // namespace jpeg

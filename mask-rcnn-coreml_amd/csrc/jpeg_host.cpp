@@ -29,10 +29,6 @@ int fail(std::string* err, int code, const char* fmt, ...)
     return code;
 }
 
-const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
 const char* sof_name(int m)
 {
     switch (m) {
@@ -223,20 +219,10 @@ int parse(const uint8_t* data, int64_t length, Header* out, std::string* err)
     return MRCNN_OK;
 }
 
-namespace {
-
-struct HuffTable {
-    uint16_t look[512];         // 9 leading bits -> (length << 8) | symbol, 0 = longer than 9 bits (or no such code)
-    int32_t maxcode[18];        // largest code of each length, -1 = none
-    int32_t valoff[17];         // index of a length's first symbol minus its first code
-    const uint8_t* vals;
-    int count;
-};
-
-void build_table(const HuffSpec& s, HuffTable& t)
+void build_huff_table(const HuffSpec& s, HuffTable& t)
 {
-    memset(t.look, 0, sizeof t.look);
-    t.vals = s.vals;
+    memset(&t, 0, sizeof t);
+    memcpy(t.vals, s.vals, sizeof t.vals);
     t.count = s.count;
     int32_t code = 0;
     int k = 0;
@@ -253,6 +239,8 @@ void build_table(const HuffSpec& s, HuffTable& t)
     }
     t.maxcode[17] = 0x7FFFFFFF;
 }
+
+namespace {
 
 // MSB-first bit reader over the entropy-coded segment.  It stops at the first marker (or at the end of the data) and supplies zero
 // bits from there on, counting them: consuming one of those is the error `overrun`, checked by the caller once per block.
@@ -297,18 +285,10 @@ struct BitReader {
 inline int decode_symbol(BitReader& br, const HuffTable& t)
 {
     br.fill();
-    const int e = t.look[br.peek(9)];
-    if (e) { br.consume(e >> 8); return e & 255; }
-    for (int l = 10; l <= 16; ++l) {
-        const int code = br.peek(l);
-        if (code <= t.maxcode[l]) {
-            const int idx = code + t.valoff[l];
-            if (idx < 0 || idx >= t.count) return -1;
-            br.consume(l);
-            return t.vals[idx];
-        }
-    }
-    return -1;
+    const int e = huff_lookup(t, (uint32_t)(br.buf >> 32));
+    if (!e) return -1;
+    br.consume(e >> 8);
+    return e & 255;
 }
 
 inline int receive_extend(BitReader& br, int s)     // 1 <= s <= 15
@@ -339,8 +319,8 @@ int decode_coefficients(const uint8_t* data, int64_t length, const Header& h, in
     memset(coef, 0, (size_t)h.total_blocks * 64 * sizeof(int16_t));
     HuffTable dc[4], ac[4];
     for (int i = 0; i < 4; ++i) {
-        if (h.dc[i].defined) build_table(h.dc[i], dc[i]);
-        if (h.ac[i].defined) build_table(h.ac[i], ac[i]);
+        if (h.dc[i].defined) build_huff_table(h.dc[i], dc[i]);
+        if (h.ac[i].defined) build_huff_table(h.ac[i], ac[i]);
     }
     BitReader br;
     br.p = data + h.scan_offset;

@@ -10,6 +10,7 @@
 #include <string>
 
 #include "../../include/maskrcnn_hip.h"
+#include "jpeg_huff.h"
 
 namespace mrcnn {
 namespace jpeg {
@@ -43,6 +44,9 @@ struct Header {
 
 // Parses every segment up to and including SOS and validates the file against the scope above.  Reads nothing behind the SOS header.
 int parse(const uint8_t* data, int64_t length, Header* out, std::string* err);
+
+// The decoding table of a DHT table the parser accepted: for decode_coefficients and for the entropy stage's plan (jpeg_entropy_host.h).
+void build_huff_table(const HuffSpec& s, HuffTable& t);
 
 // Entropy-decodes the scan into coef[total_blocks * 64] (natural order within a block; component c's blocks start at comp[c].block0,
 // row-major over its padded grid).  The array is cleared here.  The scan must be followed by EOI.

@@ -1,6 +1,7 @@
 // kernels_jpeg_entropy.hip — the entropy stage of the JPEG decoder on the device: self-synchronising parallel Huffman decoding
-// (Weissenberger & Schmidt, ICPP 2018) over a ragged batch.  The decoding step is jpeg_entropy.h's, shared with the host model
-// (jpeg_entropy_host.cpp), which runs these phases launch for launch:
+// (Weissenberger & Schmidt, ICPP 2018) over a ragged batch.  The decoding step and one unit's turn around it (byte range, context, sink,
+// the writing pass's verdict) are jpeg_entropy.h's, shared with the host model (jpeg_entropy_host.cpp), which runs these phases launch
+// for launch:
 //   k_ent_sync  x launches   one thread per unit, one workgroup per 256 units of ONE file, the file's Huffman tables in LDS.  A round
 //                            decodes every unit from the state its predecessor left in the round before (LDS, one barrier a round)
 //                            until nothing in the workgroup changes; a workgroup's first unit takes the state the workgroup before it
@@ -19,30 +20,12 @@ using namespace jpeg;
 
 namespace {
 
-__device__ const uint8_t d_zigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                         41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                         30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-constexpr int TAB_WORDS = 6 * (int)sizeof(EntTable) / 4;
+constexpr int TAB_WORDS = 6 * (int)sizeof(HuffTable) / 4;
 
 __device__ inline void stage_tables(const EntFile& f, uint32_t* s_tab)
 {
     const uint32_t* src = reinterpret_cast<const uint32_t*>(f.tab);
     for (int i = threadIdx.x; i < TAB_WORDS; i += ENT_WG_UNITS) s_tab[i] = src[i];
-}
-
-struct UnitGeom {
-    long long b0, b1, ub, ue;
-    bool first;
-};
-__device__ inline UnitGeom unit_geom(const EntSeg& s, int u, int unit_bytes)
-{
-    UnitGeom g;
-    g.b0 = s.b0; g.b1 = s.b1;
-    g.ub = s.b0 + (long long)(u - s.unit0) * unit_bytes;
-    g.ue = g.ub + unit_bytes < s.b1 ? g.ub + unit_bytes : s.b1;
-    g.first = u == s.unit0;
-    return g;
 }
 
 }  // namespace
@@ -63,16 +46,15 @@ __global__ __launch_bounds__(ENT_WG_UNITS) void k_ent_sync(JpegEntBuffers b, int
     stage_tables(f, s_tab);
     const bool live = t < g.count;
     const int u = g.unit0 + t;
-    UnitGeom q = {};
+    EntUnit q = {};
     EntCtx c = {};
     ent_state guess = ENT_INVALID;
     int cnt = 0;
     if (live) {
         const EntSeg s = b.segs[b.unit_seg[u]];
-        q = unit_geom(s, u, b.unit_bytes);
-        c.data = b.bytes + f.byte0; c.tab = reinterpret_cast<const EntTable*>(s_tab); c.zigzag = d_zigzag;
-        c.b0 = s.b0; c.b1 = s.b1 < f.length ? s.b1 : f.length; c.bpm = f.bpm; c.nluma = f.nluma;
-        guess = ent_guess(c.data, q.b0, q.ub);
+        q = ent_unit(s, u, b.unit_bytes);
+        c = ent_ctx(f, s, b.bytes + f.byte0, reinterpret_cast<const HuffTable*>(s_tab), kZigzag);
+        guess = ent_guess(c.data, c.b0, q.ub);
         cnt = (int)b.count[u];
     }
     s_st[0][t] = live ? b.state[u] : ENT_INVALID;
@@ -82,7 +64,7 @@ __global__ __launch_bounds__(ENT_WG_UNITS) void k_ent_sync(JpegEntBuffers b, int
     while (n < b.inner_rounds && any) {
         int changed = 0;
         if (live) {
-            ent_state in = q.first ? ent_pack(q.b0 * 8, 0, 0) : (t == 0 ? entry : s_st[at][t - 1]);
+            ent_state in = q.first ? ent_pack(c.b0 * 8, 0, 0) : (t == 0 ? entry : s_st[at][t - 1]);
             if (in == ENT_INVALID) in = guess;
             if (n > 0 && in == last_in) {                  // the same question as in the round before: the same answer
                 s_st[at ^ 1][t] = s_st[at][t];
@@ -147,16 +129,7 @@ __global__ __launch_bounds__(1024) void k_ent_scan(const uint32_t* __restrict__ 
     if (t == 0) prefix[n] = carry;
 }
 
-__device__ inline EntSink sink_of(const EntFile& f, int16_t* coef)
-{
-    EntSink k;
-    k.coef = coef; k.seq0 = 0; k.seq_end = 0;
-    for (int i = 0; i < 3; ++i) { k.block0[i] = f.comp_block0[i]; k.blocks_w[i] = f.comp_blocks_w[i]; }
-    k.hs = f.hs; k.vs = f.vs; k.mcus_x = f.mcus_x;
-    return k;
-}
-
-__global__ __launch_bounds__(ENT_WG_UNITS) void k_ent_write(JpegEntBuffers b, int16_t* __restrict__ coef, long long total_blocks)
+__global__ __launch_bounds__(ENT_WG_UNITS) void k_ent_write(JpegEntBuffers b, int16_t* __restrict__ coef)
 {
     __shared__ uint32_t s_tab[TAB_WORDS];
     __shared__ uint8_t s_zz[64];
@@ -164,30 +137,15 @@ __global__ __launch_bounds__(ENT_WG_UNITS) void k_ent_write(JpegEntBuffers b, in
     const EntWg g = b.wgs[w];
     const EntFile& f = b.files[g.file];
     stage_tables(f, s_tab);
-    if (t < 64) s_zz[t] = d_zigzag[t];
+    if (t < 64) s_zz[t] = kZigzag[t];
     __syncthreads();
     if (t >= g.count) return;
     const int u = g.unit0 + t;
     const EntSeg s = b.segs[b.unit_seg[u]];
-    const UnitGeom q = unit_geom(s, u, b.unit_bytes);
-    EntCtx c;
-    c.data = b.bytes + f.byte0; c.tab = reinterpret_cast<const EntTable*>(s_tab); c.zigzag = s_zz;
-    c.b0 = s.b0; c.b1 = s.b1 < f.length ? s.b1 : f.length; c.bpm = f.bpm; c.nluma = f.nluma;
-    EntSink k = sink_of(f, coef);
-    const long long mcu_blocks = (long long)f.mcus_x * f.mcus_y * f.bpm;
-    k.seq0 = s.first_block + (long long)(b.prefix[u] - b.prefix[s.unit0]);
-    k.seq_end = s.first_block + s.nblocks < mcu_blocks ? s.first_block + s.nblocks : mcu_blocks;       // (never behind the component grids)
-    const ent_state in = q.first ? ent_pack(q.b0 * 8, 0, 0) : b.state[u - 1];
-    const EntResult r = decode_unit(c, q.ub, q.ue, in, &k);
-    int bad = 0;
-    if (r.anomaly || r.state != b.state[u] || (uint32_t)r.blocks != b.count[u]) bad |= ENT_BAD_WRITE;
-    if (u == s.unit0 + s.nunits - 1) {
-        const bool whole = !r.anomaly && ent_zz(r.state) == 0 && ent_blk(r.state) == 0 && ent_bits_left(c.data, c.b0, c.b1, ent_pos(r.state)) < 8 &&
-                           b.prefix[u + 1] - b.prefix[s.unit0] == (uint32_t)s.nblocks;
-        if (!whole) bad |= ENT_BAD_COUNT;
-    }
+    const EntCtx c = ent_ctx(f, s, b.bytes + f.byte0, reinterpret_cast<const HuffTable*>(s_tab), s_zz);
+    const uint32_t p0 = b.prefix[s.unit0];
+    const int bad = ent_write_unit(c, f, s, u, b.unit_bytes, b.state, b.prefix[u] - p0, b.prefix[u + 1] - p0, coef);
     if (bad) atomicOr(&b.verdict[2 * g.file], bad);
-    (void)total_blocks;
 }
 
 __global__ __launch_bounds__(256) void k_ent_dc(JpegEntBuffers b, int16_t* __restrict__ coef)
@@ -198,7 +156,7 @@ __global__ __launch_bounds__(256) void k_ent_dc(JpegEntBuffers b, int16_t* __res
     const EntSeg s = b.segs[si];
     const EntFile& f = b.files[s.file];
     if (comp >= f.ncomp) return;
-    const EntSink k = sink_of(f, coef);
+    const EntSink k = ent_sink(f, coef);
     const int per = comp == 0 ? f.nluma : 1;
     const long long first_mcu = s.first_block / f.bpm, mcu_blocks = (long long)f.mcus_x * f.mcus_y * f.bpm;
     const int total = s.nblocks / f.bpm * per;
@@ -235,7 +193,7 @@ void jpeg_entropy_forward(hipStream_t s, const JpegEntBuffers& b, int16_t* coef,
     }
     hipLaunchKernelGGL(k_ent_scan, dim3(1), dim3(1024), 0, s, b.count, b.nunits, b.prefix);
     HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_ent_write, dim3(b.nwg), dim3(ENT_WG_UNITS), 0, s, b, coef, total_blocks);
+    hipLaunchKernelGGL(k_ent_write, dim3(b.nwg), dim3(ENT_WG_UNITS), 0, s, b, coef);
     HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(k_ent_dc, dim3((b.nsegs * 3 + 3) / 4), dim3(256), 0, s, b, coef);
     HIP_CHECK(hipGetLastError());

@@ -162,6 +162,30 @@ def test_the_parser_is_clean_under_the_sanitizers(tmp_path):
     assert " 0 findings" in r.stdout
 
 
+def test_the_host_decoder_answers_what_it_always_answered(L):
+    """tests/golden/jpeg_host_answers_v1.npz (make_jpeg_host_answers.py): status, message and the CRC32 of the coefficients that
+    mrcnn_jpeg_coefficients(entropy = HOST) gave on the 25 files of jpeg_entropy_cases.py, intact and in their 25 damaged variants
+    each, recorded from the commit before the decoder's tables and lookup were shared.  650 answers, equal case by case."""
+    import sys
+    import jpeg_entropy_cases as K
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    try:
+        maker = importlib.import_module("make_jpeg_host_answers")
+    finally:
+        sys.path.pop(0)
+    path = os.path.join(ROOT, "tests", "golden", "jpeg_host_answers_v1.npz")
+    gold = np.load(path)
+    assert os.path.getsize(path) < 64 * 1024 and gold["status"].shape == (25, 26) and len(gold["messages"]) == 168
+    rows = maker.answers(K)
+    assert [n for n, _ in rows] == gold["names"].tolist()
+    for i, (name, row) in enumerate(rows):
+        assert len(row) == 26
+        for j, (label, st, msg, crc) in enumerate(row):
+            want_st, want_msg, want_crc = int(gold["status"][i, j]), str(gold["messages"][gold["message"][i, j]]), int(gold["crc"][i, j])
+            assert (st, msg, crc) == (want_st, want_msg, want_crc), \
+                f"{name}, {label}: status {st} {msg!r} crc {crc:08x}; recorded: status {want_st} {want_msg!r} crc {want_crc:08x}"
+
+
 def test_the_fixture_is_still_what_pil_decodes():
     Image = pytest.importorskip("PIL.Image")
     for name in DECODABLE:

@@ -35,12 +35,11 @@ static int check(const std::vector<uint8_t>& bytes, size_t length, bool must_be_
     *host_status = st;
     if (st != MRCNN_OK) return 0;                                  // (no entropy stage runs on a refused header)
     if (h.total_blocks > (int64_t)1 << 20) return 0;               // (a corrupted size field: not this program's business)
-    const uint8_t* ptr = data.data();
-    const int64_t len = (int64_t)data.size();
+    const mrcnn_jpeg file = {data.data(), (int64_t)data.size()};
     const long long block0 = 0;
     if (!must_be_clean) {           // a file the marker scan hands to the host decoder IS the host decoder's answer: nothing to compare
         jpeg::EntropyPlan probe;
-        jpeg::plan_entropy(&ptr, &len, &h, &block0, 1, 128, probe);
+        jpeg::plan_entropy(&file, &h, &block0, 1, 128, probe);
         ++g_scans;
         if (probe.files[0].nseg == 0) return 0;
     }
@@ -50,10 +49,10 @@ static int check(const std::vector<uint8_t>& bytes, size_t length, bool must_be_
     int bad = 0;
     for (int unit : {4, 16, 128}) {
         jpeg::EntropyPlan plan;
-        jpeg::plan_entropy(&ptr, &len, &h, &block0, 1, unit, plan);
+        jpeg::plan_entropy(&file, &h, &block0, 1, unit, plan);
         std::vector<char> clean;
         int rounds = 0;
-        jpeg::entropy_model(plan, &ptr, 0, got.data(), h.total_blocks, clean, &rounds);
+        jpeg::entropy_model(plan, &file, 0, got.data(), h.total_blocks, clean, &rounds);
         ++g_models;
         if (clean[0]) {
             ++g_clean;
