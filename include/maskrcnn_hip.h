@@ -501,6 +501,42 @@ MRCNN_API int mrcnn_jpeg_encode_host(const uint8_t* rgb, int height, int width, 
 MRCNN_API int mrcnn_jpeg_encode_batch(const mrcnn_image* images, int batch, int memspace, int quality, int sampling, uint8_t* out,
                                       int64_t capacity, int64_t* file_offsets /* batch + 1 */);
 
+/* PNG: files out — the label images leave as lossless files: the int16 maps of mrcnn_instance_map_source and the uint8 mask planes of
+ * mrcnn_paste_masks_source (JPEG cannot carry an id).  The deflate stream is made on the device: the bits of every token counted per
+ * block and scanned, then every token written at once; only the files' bytes cross back, and no codec is linked.
+ *   the formats: MRCNN_PNG_GREY8     pixels = uint8, height x width, row-major -> colour type 0, depth 8, the values as they are.
+ *                MRCNN_PNG_INSTANCE  pixels = int16, height x width (what mrcnn_instance_map_source leaves) -> colour type 3 (palette),
+ *                                    depth 8: index = v + 1 for v in -1 .. rows - 1, any other value index 0.  rows in 1..255.  PLTE has
+ *                                    rows + 1 entries: entry 0 is (0,0,0), entry k >= 1 palette[(k-1) % 4] of mrcnn_render_detections_source
+ *                                    (red, blue, green, yellow); tRNS is one byte, 0: "no detection" is transparent.  The file is the
+ *                                    exact id map (index - 1) and a coloured overlay any viewer shows.
+ *   the file:    signature, IHDR, [PLTE, tRNS], ONE IDAT, IEND.  Raw stream R: per scanline a filter byte 0 and the width sample
+ *                bytes, N = height (width + 1).  IDAT = 78 01, a deflate stream, Adler-32 of R.  R is cut into blocks of
+ *                MRCNN_PNG_BLOCK_BYTES raw bytes, each one fixed-Huffman block (BFINAL on the last), bit-contiguous, the last byte
+ *                zero-padded.  Tokens (zlib's Z_RLE matcher, distance 1 only), for a block [b0, b1) and p from b0: n = the number of
+ *                k >= 0 with R[p+k] == R[p+k-1], counted up to min(258, b1 - p), 0 at p = 0; n >= 3 -> (length n, distance 1), p += n;
+ *                else the literal R[p], p += 1.
+ *   left out:    RGB8, 16-bit samples, row filters other than 0 (they gain nothing on label data under this matcher), dynamic Huffman
+ *                tables, interlacing, decoding.  Photographs come out larger than raw with fixed codes: pictures have the JPEG entries.
+ * _encode_host is plain sequential C++, needs no GPU and is the DEFINITION: _encode_batch returns the same bytes, byte for byte.  *length
+ * is always the size needed; out = NULL with capacity = 0 measures; capacity too small -> MRCNN_ERR_SHAPE and nothing is written.
+ * _encode_batch: images of different sizes, all of one format; `memspace` is that of the pixel pointers (natural alignment of the sample
+ * type); the files are ALWAYS host memory: file b is out[file_offsets[b] .. file_offsets[b + 1]), back to back.  file_offsets (host,
+ * batch + 1 entries) is always written.  file_offsets[batch] > capacity -> MRCNN_ERR_SHAPE naming the capacity needed, with out
+ * untouched; capacity 0 with out = NULL is the size query.  Only the used bytes are copied from the device (IDAT's CRC-32 is the host's,
+ * filled in after the copy), and the number of launches does not depend on batch.  rows is ignored for MRCNN_PNG_GREY8.
+ * Errors (the message names the index of the offending image), all raised before the device is touched: null pointer, unknown format
+ * or memspace -> MRCNN_ERR_INVALID; a side outside 1..32767, rows outside 1..255 for MRCNN_PNG_INSTANCE, batch outside
+ * 1..MRCNN_PNG_MAX_BATCH -> MRCNN_ERR_SHAPE.  No gfx950 device -> MRCNN_ERR_HIP from _encode_batch (no CPU fallback). */
+enum { MRCNN_PNG_GREY8 = 0, MRCNN_PNG_INSTANCE = 1 };
+#define MRCNN_PNG_BLOCK_BYTES 4096
+#define MRCNN_PNG_MAX_BATCH 1024 /* the 100 mask planes of several images fit one call */
+typedef struct { const void* pixels; int32_t height, width; } mrcnn_png_source;
+MRCNN_API int mrcnn_png_encode_host(const void* pixels, int height, int width, int format, int rows, uint8_t* out, int64_t capacity,
+                                    int64_t* length);
+MRCNN_API int mrcnn_png_encode_batch(const mrcnn_png_source* images, int batch, int memspace, int format, int rows, uint8_t* out,
+                                     int64_t capacity, int64_t* file_offsets /* batch + 1 */);
+
 /* Mask paste: per-instance 28×28 sigmoid masks → full-resolution binary masks
  * (n, image_h, image_w) uint8 {0,1}: resize to the detection's box and threshold.  Replaces what the
  * example app does with CoreGraphics when drawing (Example/Source/DetectionRenderer.swift:13-24).

@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = [
     "mrcnn_jpeg_info", "mrcnn_jpeg_decode_host", "mrcnn_jpeg_decode_batch", "mrcnn_maskrcnn_predict_jpegs",
     "mrcnn_jpeg_decode_batch_on", "mrcnn_maskrcnn_predict_jpegs_on",
     "mrcnn_jpeg_encode_host", "mrcnn_jpeg_encode_batch",
+    "mrcnn_png_encode_host", "mrcnn_png_encode_batch",
 ]
 # declared in include/maskrcnn_hip_test.h (test / measurement entry points of the same library)
 TEST_SYMBOLS = [
@@ -96,6 +97,10 @@ class Jpeg(C.Structure):            # mrcnn_jpeg
 
 class Image(C.Structure):           # mrcnn_image
     _fields_ = [("rgb", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32)]
+
+
+class PngSource(C.Structure):       # mrcnn_png_source
+    _fields_ = [("pixels", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32)]
 
 
 _lib = None
@@ -167,6 +172,8 @@ def lib():
     L.mrcnn_maskrcnn_predict_jpegs.argtypes = [vp, C.POINTER(Jpeg), C.c_int, C.c_int, vp, vp, vp, vp]
     L.mrcnn_jpeg_encode_host.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]
     L.mrcnn_jpeg_encode_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp]
+    L.mrcnn_png_encode_host.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.mrcnn_png_encode_batch.argtypes = [C.POINTER(PngSource), C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp]
     L.mrcnn_jpeg_last_stage_ms.argtypes = [f32p, f32p]
     L.mrcnn_jpeg_decode_batch_on.argtypes = [C.POINTER(Jpeg), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.mrcnn_maskrcnn_predict_jpegs_on.argtypes = [vp, C.POINTER(Jpeg), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]

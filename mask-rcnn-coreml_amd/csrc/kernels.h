@@ -200,6 +200,33 @@ struct JpegEncBuffers {
 void jpeg_encode_forward(hipStream_t s, const JpegEncBuffers& b, int batch, long long total_blocks);
 
 // ================================================================================================
+// PNG encode of label images (kernels_png.hip; the format is png_format.h's)
+// ================================================================================================
+// One image of a ragged batch.  Its deflate blocks (4096 raw bytes each, the last shorter) are [block0, block0 + blocks) of the batch.
+struct PngDesc {
+    const void* pixels;        // device; uint8 (GREY8) or int16 (INSTANCE), h*w, naturally aligned
+    long long block0, blocks;
+    long long n;               // raw bytes: h * (w + 1)
+    int h, w;
+    int header0, header_len;   // its host-built chunks (signature .. the last chunk before IDAT) in `headers`
+};
+static_assert(sizeof(PngDesc) % 16 == 0, "PngDesc: a table of them keeps 16-byte alignment");
+// The device buffers of one call, all but `tab` and `headers` written by the launches.  files holds files_capacity bytes (a multiple of
+// 4, at least the sum of png_host.h's max_file_bytes) and is cleared by png_encode_forward, as is adler.
+struct PngBuffers {
+    const PngDesc* tab;
+    const uint8_t* headers;
+    uint32_t* block_bits;            // total_blocks: header + tokens + end of block
+    unsigned long long* block_scan;  // total_blocks + 1
+    unsigned long long* adler;       // batch x 2: the blocks' reduced contributions to a and b
+    long long* file_offsets;         // batch + 1
+    uint32_t* files;                 // the files back to back, IDAT's CRC-32 left zero for the host
+    long long files_capacity;
+};
+// Two fills and four launches whatever the batch: token bits + Adler sums, their scan + file offsets, the bits, the framing.
+void png_encode_forward(hipStream_t s, const PngBuffers& b, int batch, long long total_blocks, int format, int rows);
+
+// ================================================================================================
 // Convolution family + element-wise helpers (kernels_conv.hip)
 // ================================================================================================
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_SIGMOID = 2 };

@@ -184,6 +184,18 @@ class MaskRCNN(_Model):
         from .jpeg import encode_batch
         return encode_batch(self.render_images(images, **kw), quality=quality, sampling=sampling)
 
+    def instance_pngs(self, images, **kw):
+        """predict_images followed by detection.instance_map_source at this handle's model size and png.encode_batch on the device
+        result: which detection owns each pixel, as PNG files (index = row + 1, 0 and transparent where there is none; coloured
+        like render_images), a list of bytes.  Keyword arguments go to the map (threshold, min_score).  For CUDA images the maps
+        never exist in host memory — only the files cross back.  A convenience: no device work of its own."""
+        from .detection import instance_map_source
+        from .png import encode_batch
+        images = list(images)
+        det, mask = self.predict_images(images)
+        _, maps, _ = instance_map_source(det, mask, [(int(im.shape[0]), int(im.shape[1])) for im in images], self.image_height, self.image_width, **kw)
+        return encode_batch(maps, rows=self.max_detections)
+
     def predict_into(self, images, det, mask, sync: bool = True):
         """Device tensors in, pre-allocated device tensors out (bench loop: no allocation, optional no sync)."""
         B, H, W, _ = images.shape
