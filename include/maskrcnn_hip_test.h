@@ -132,6 +132,20 @@ MRCNN_API int mrcnn_bottleneck_first_nhwc(const float* x, int batch, int h, int 
 MRCNN_API int mrcnn_bottleneck_stage_nhwc(const float* x, int batch, int h, int w, int nlayers, const float* w1, const float* w2, const float* w3,
                                           const float* const bn[6], int form, int iters, float* out, float* avg_ms, int* status_flag);
 
+/* The fp16-range watchdog word of the calling thread's last mrcnn_conv2d_nhwc / mrcnn_bottleneck_nhwc / mrcnn_bottleneck_first_nhwc (each of them
+ * gives its launches a zeroed 4-byte device flag, the way the engine does for a predict, and reads it back when they have finished):
+ * bit 0: some stored output has !(|v| < 65504) after scale, shift, residual and activation (NaN included) — what makes MRCNN_F16 refuse a predict and
+ * MRCNN_F32S / MRCNN_F32X3 recompute it.  Padded columns, rows beyond M and the on-chip lanes of no real output never set it; in the fused bottlenecks
+ * the two mid tensors count as stored outputs.  MRCNN_F32 (exact fp32: no fp16 hand-over) leaves the word 0; so does an entry that failed.
+ * mrcnn_bottleneck_stage_nhwc returns its word through status_flag.  tests/test_gpu_range_watch.py pins every epilogue form with it. */
+MRCNN_API int mrcnn_test_last_range_flag(int* flag);
+
+/* The classifier head behind its last inner product, on caller (host) rows: logits (n rows at stride ld >= nc, the first nc entries of a row are read),
+ * bbox (n, nc*4) -> probs_out (n, nc) = the row softmax, cls6_out (n, 6) = (dy, dx, dh, dw, class id, score) of the arg-max class (ties -> lowest index).
+ * NaN entries never win; a row with no comparable entry (all probabilities NaN: one logit +Inf or NaN, or all -Inf) yields class 0, its score the
+ * row's probability at index 0 (the NaN as it is) and class 0's deltas: DetectionLayer drops such a row (score >= threshold is false). */
+MRCNN_API int mrcnn_classifier_rows(const float* logits, int64_t ld, const float* bbox, int nc, int64_t n, float* probs_out, float* cls6_out);
+
 /* Measurement (tools/jpeg_ab.py): the wall time of the two stages of the calling thread's last mrcnn_jpeg_decode_batch /
  * mrcnn_maskrcnn_predict_jpegs — host_ms: header parsing + the entropy threads; device_ms: from the upload of the coefficients to the end
  * of the second launch (decode_batch only, where the call waits for it; 0 after predict_jpegs, whose launches run ahead of the predict).

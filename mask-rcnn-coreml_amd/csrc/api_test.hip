@@ -80,6 +80,24 @@ struct ScopedConvScratch {
     ~ScopedConvScratch() { conv_set_scratch(nullptr); }
 };
 
+// The fp16-range watchdog word of one entry on caller data (include/maskrcnn_hip_test.h: mrcnn_test_last_range_flag): a 4-byte device flag, zeroed on the
+// launch stream, handed to the calling thread's conv_forward launches (watch_conv_family) and, through dev(), to bneck_launch; taken away again however the
+// scope ends.  keep() reads the word back into the thread-local the getter returns (0 from the entry's start, so a failed entry never reports a stale word).
+thread_local int t_last_range_flag = 0;
+struct ScopedRangeFlag {
+    DevBuf flag;
+    ScopedRangeFlag(hipStream_t s, bool watch_conv_family)
+    {
+        t_last_range_flag = 0;
+        flag.alloc(sizeof(int));
+        HIP_CHECK(hipMemsetAsync(flag.p, 0, sizeof(int), s));
+        if (watch_conv_family) conv_set_range_flag(flag.as<int>());
+    }
+    ~ScopedRangeFlag() { conv_set_range_flag(nullptr); }
+    int* dev() { return flag.as<int>(); }
+    void keep() { HIP_CHECK(hipMemcpy(&t_last_range_flag, flag.p, sizeof(int), hipMemcpyDeviceToHost)); }      // (after the stream has been synchronised)
+};
+
 }  // namespace
 
 // ================================================================================================
@@ -187,7 +205,9 @@ extern "C" int mrcnn_conv2d_nhwc(const float* in, int batch, int h, int w, int c
         DevBuf din, dw, ds, db, dres, dout;
         upload_act(din, in, n_in, n_in);
         (wdt != MRCNN_F32 ? upload_f16 : upload_f32)(dw, filters, (size_t)cout * kk, (size_t)npad * kk);      // the filter rows up to Npad are zero
-        std::vector<float> hs(npad, 0.f), hb(npad, 0.f);
+        // the padded columns cout..Npad-1 (zero filters) carry a shift far beyond the fp16 range: no epilogue stores them, and one whose watchdog
+        // forgot to gate them reports it (tests/test_gpu_range_watch.py)
+        std::vector<float> hs(npad, 0.f), hb(npad, 1.0e30f);
         for (int o = 0; o < cout; ++o) { hs[o] = scale ? scale[o] : 1.f; hb[o] = shift ? shift[o] : 0.f; }
         upload_f32(ds, hs.data(), npad);
         upload_f32(db, hb.data(), npad);
@@ -209,8 +229,10 @@ extern "C" int mrcnn_conv2d_nhwc(const float* in, int batch, int h, int w, int c
         DevBuf dw3h;
         if (adt == MRCNN_F16 && conv3x3h_packable(ksize, ksize, cin, cout, npad)) { conv3x3h_pack(st.s, dw.p, cout, cin, dw3h); d.wgt_c3h = dw3h.p; }
         ScopedConvScratch scratch(wdt != MRCNN_F32 && adt == MRCNN_F32);      // the shared-tile K chunks need it
+        ScopedRangeFlag range(st.s, dtype != MRCNN_F32);      // as the engine: the exact-fp32 mode has no fp16 hand-over to watch, its word stays 0
         conv_forward(st.s, d);
         HIP_CHECK(hipStreamSynchronize(st.s));
+        range.keep();
         if (adt == MRCNN_F16) download_f16_as_f32(d.out, n_out, out);
         else HIP_CHECK(hipMemcpy(out, d.out, n_out * 4, hipMemcpyDeviceToHost));
     });
@@ -251,15 +273,17 @@ extern "C" int mrcnn_bottleneck_nhwc(const float* x, int batch, int h, int w, in
         if (bneck_frag_wanted(3, 3, C, C)) { bneck_pack_frag(st.s, dw2.p, C, 9 * C, dw2f); db.wgt_frag = dw2f.p; }
         if (bneck_frag_wanted(1, 1, C, C4)) { bneck_pack_frag(st.s, dw3.p, C4, C, dw3f); dc.wgt_frag = dw3f.p; }
         MRCNN_REQUIRE(!fused || conv_bneck_fusable(da, db, dc), MRCNN_ERR_UNSUPPORTED, "bottleneck_nhwc: C %d at %dx%d does not qualify for the fused launch", C, h, w);
+        ScopedRangeFlag range(st.s, true);
         auto run = [&] {
             if (fused) {        // the fused launch whatever the grid size (conv_bneck_forward sends under-filled grids to the three launches)
-                bneck_launch(st.s, C, da.in, dc.out, batch, h, w, da.wgt, db.wgt, dc.wgt, da.scale, da.shift, db.scale, db.shift, dc.scale, dc.shift, nullptr, device_cu_count(),
+                bneck_launch(st.s, C, da.in, dc.out, batch, h, w, da.wgt, db.wgt, dc.wgt, da.scale, da.shift, db.scale, db.shift, dc.scale, dc.shift, range.dev(), device_cu_count(),
                              fused == 2 ? nullptr : db.wgt_frag, fused == 2 ? nullptr : dc.wgt_frag, fused == 2 ? nullptr : da.wgt_frag);
             }
             else { conv_forward(st.s, da); conv_forward(st.s, db); conv_forward(st.s, dc); }
         };
         run();
         HIP_CHECK(hipStreamSynchronize(st.s));
+        range.keep();      // the word of the first run (the timed repeats below see the same data)
         if (iters > 0 && avg_ms) *avg_ms = EventTimer().avg_ms(st.s, iters, run);
         download_f16_as_f32(dy.p, npix * C4, out);
     });
@@ -294,13 +318,15 @@ extern "C" int mrcnn_bottleneck_first_nhwc(const float* x, int batch, int h, int
         set_dense_residual(dc, dsc.p);
         MRCNN_REQUIRE(!fused || conv_bneck_first_fusable(da, db, dc, ds), MRCNN_ERR_UNSUPPORTED, "bottleneck_first_nhwc: C %d at %dx%d does not qualify for the fused launch", C, h, w);
         Stream st;
+        ScopedRangeFlag range(st.s, true);
         auto run = [&] {
-            if (fused) bneck_launch(st.s, C, da.in, dc.out, batch, h, w, da.wgt, db.wgt, dc.wgt, da.scale, da.shift, db.scale, db.shift, dc.scale, dc.shift, nullptr, device_cu_count(),
+            if (fused) bneck_launch(st.s, C, da.in, dc.out, batch, h, w, da.wgt, db.wgt, dc.wgt, da.scale, da.shift, db.scale, db.shift, dc.scale, dc.shift, range.dev(), device_cu_count(),
                                     nullptr, nullptr, nullptr, ds.wgt, ds.scale, ds.shift);
             else { conv_forward(st.s, da); conv_forward(st.s, ds); conv_forward(st.s, db); conv_forward(st.s, dc); }
         };
         run();
         HIP_CHECK(hipStreamSynchronize(st.s));
+        range.keep();
         if (iters > 0 && avg_ms) *avg_ms = EventTimer().avg_ms(st.s, iters, run);
         download_f16_as_f32(dy.p, npix * C4, out);
     });
@@ -361,6 +387,35 @@ extern "C" int mrcnn_bottleneck_stage_nhwc(const float* x, int batch, int h, int
         if (status_flag) HIP_CHECK(hipMemcpy(status_flag, flag.p, sizeof(int), hipMemcpyDeviceToHost));
         if (iters > 0 && avg_ms) *avg_ms = EventTimer().avg_ms(st.s, iters, run);      // (includes the input copy and the two memsets of a run: the same for both forms)
         download_f16_as_f32((nlayers & 1) ? dy.p : dx.p, npix * C4, out);
+    });
+}
+
+extern "C" int mrcnn_test_last_range_flag(int* flag)
+{
+    return guarded([&] {
+        MRCNN_REQUIRE(flag, MRCNN_ERR_INVALID, "null flag");
+        *flag = t_last_range_flag;
+    });
+}
+
+// softmax_rows_forward + classifier_postprocess_forward on caller rows: what ClassifierHead::forward runs behind its last inner product
+// (logits at the padded row stride ld of the stacked logits + deltas tensor).
+extern "C" int mrcnn_classifier_rows(const float* logits, int64_t ld, const float* bbox, int nc, int64_t n, float* probs_out, float* cls6_out)
+{
+    return guarded([&] {
+        require_gpu();
+        MRCNN_REQUIRE(logits && bbox && probs_out && cls6_out && nc >= 1 && ld >= nc && n >= 1, MRCNN_ERR_INVALID, "bad classifier_rows argument");
+        DevBuf dl, db, dp, dc;
+        upload_f32(dl, logits, (size_t)n * ld);
+        upload_f32(db, bbox, (size_t)n * nc * 4);
+        dp.alloc((size_t)n * nc * 4);
+        dc.alloc((size_t)n * 6 * 4);
+        Stream st;
+        softmax_rows_forward(st.s, dl.as<float>(), ld, nc, n, dp.as<float>());
+        classifier_postprocess_forward(st.s, dp.as<float>(), db.as<float>(), nc, n, dc.as<float>(), 6);
+        HIP_CHECK(hipStreamSynchronize(st.s));
+        HIP_CHECK(hipMemcpy(probs_out, dp.p, (size_t)n * nc * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(cls6_out, dc.p, (size_t)n * 6 * 4, hipMemcpyDeviceToHost));
     });
 }
 

@@ -1272,6 +1272,10 @@ void copy_columns_forward(hipStream_t s, const float* src, long ld, int c0, int 
 
 // TimeDistributedClassifierLayer.swift:65-86: argmax over all classes (ties → lowest index), score,
 // the four deltas of the arg-max class.  One wave per ROI.
+// Non-finite rows (a local fp16-range overflow reaches this kernel before the watchdog word is read): NaN entries never win — no comparison
+// with a NaN succeeds; a row with no comparable entry (every probability NaN: softmax of a row with a +Inf or NaN logit, or of all -Inf)
+// yields class 0, score = the row's probability at index 0 (the NaN as it is) and class 0's deltas, so DetectionLayer drops it
+// (score >= threshold is false).  The class index is therefore always inside [0, nc): `bbox` is never read outside the row.
 __global__ __launch_bounds__(256) void k_classifier_post(const float* __restrict__ probs, const float* __restrict__ bbox,
                                                          int nc, long n, float* __restrict__ out, long out_row_stride)
 {
@@ -1285,12 +1289,12 @@ __global__ __launch_bounds__(256) void k_classifier_post(const float* __restrict
         const float v = p[c];
         if (v > bv || (v == bv && c < bi)) { bv = v; bi = c; }
     }
-    if (bi == 0x7fffffff) { bv = -INFINITY; }
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_xor(bv, o);
         const int oi = __shfl_xor(bi, o);
         if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
     }
+    if (bi == 0x7fffffff) { bi = 0; bv = p[0]; }      // no lane met a comparable entry
     float* o = out + row * out_row_stride;
     if (lane < 4) o[lane] = bbox[row * nc * 4 + (long)bi * 4 + lane];
     else if (lane == 4) o[4] = (float)bi;

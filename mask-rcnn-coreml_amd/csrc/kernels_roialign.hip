@@ -55,7 +55,8 @@ __device__ __forceinline__ Sample make_sample(const RoiGeom& g, int H, int W, in
     const float ws = (P > 1) ? (g.x2 - g.x1) * (float)(W - 1) / (float)(P - 1) : 0.0f;
     const float in_y = (P > 1) ? g.y1 * (float)(H - 1) + (float)py * hs : 0.5f * (g.y1 + g.y2) * (float)(H - 1);
     const float in_x = (P > 1) ? g.x1 * (float)(W - 1) + (float)px * ws : 0.5f * (g.x1 + g.x2) * (float)(W - 1);
-    s.ok = !(in_y < 0 || in_y > (float)(H - 1)) && !(in_x < 0 || in_x > (float)(W - 1));
+    // (written so that a NaN coordinate — 0 * inf of an ROI beyond any image — is OUTSIDE: its corner indices below are never used)
+    s.ok = in_y >= 0 && in_y <= (float)(H - 1) && in_x >= 0 && in_x <= (float)(W - 1);
     const float fy = floorf(in_y), cy = ceilf(in_y), fx = floorf(in_x), cx = ceilf(in_x);
     s.ly = in_y - fy;
     s.lx = in_x - fx;

@@ -292,13 +292,13 @@ static void orc_crop_and_resize_chw(const float* fmap, int64_t C, int64_t H, int
     for (int64_t py = 0; py < P; ++py) {
         float in_y = (P > 1) ? y1 * (float)(H - 1) + (float)py * hs
                              : 0.5f * (y1 + y2) * (float)(H - 1);
-        int y_ok = !(in_y < 0 || in_y > (float)(H - 1));
+        int y_ok = in_y >= 0 && in_y <= (float)(H - 1);               /* (a NaN coordinate is outside: extrapolation 0) */
         float fy = floorf(in_y), cy = ceilf(in_y);
         float ly = in_y - fy;
         for (int64_t px = 0; px < P; ++px) {
             float in_x = (P > 1) ? x1 * (float)(W - 1) + (float)px * ws
                                  : 0.5f * (x1 + x2) * (float)(W - 1);
-            int x_ok = !(in_x < 0 || in_x > (float)(W - 1));
+            int x_ok = in_x >= 0 && in_x <= (float)(W - 1);
             if (!y_ok || !x_ok) {
                 for (int64_t c = 0; c < C; ++c) out[(c * P + py) * P + px] = 0.0f;
                 continue;
@@ -341,17 +341,22 @@ ORC_API void orc_pyramid_roi_align(const float* rois, int64_t n, int64_t roi_str
  * probs (n, nc) and bbox (n, nc*4) as emitted by Classifier.mlmodel (Double in the reference;
  * the Double→Float cast at :69-71 is the identity on values that are already floats).
  * out row i = (dy,dx,dh,dw, classId, score), row stride out_stride.
+ * Non-finite rows (this project's definition; the reference is silent): NaN entries never win; a row with
+ * no comparable entry yields class 0, score = the row's probability at index 0 (the NaN as it is) and
+ * class 0's deltas, so orc_detection_layer drops it (score >= thr is false).
  * ---------------------------------------------------------------------------------------- */
 ORC_API void orc_classifier_postprocess(const double* probs, const double* bbox, int64_t n,
                                         int64_t nc, float* out, int64_t out_stride)
 {
     for (int64_t i = 0; i < n; ++i) {
-        int64_t best = 0;
-        float bestv = (float)probs[i * nc];
-        for (int64_t c = 1; c < nc; ++c) {                           /* maximumValueWithIndex :177-192, Q12 */
+        int64_t best = -1;
+        float bestv = 0.0f;
+        for (int64_t c = 0; c < nc; ++c) {                           /* maximumValueWithIndex :177-192, Q12 */
             float v = (float)probs[i * nc + c];
-            if (v > bestv) { bestv = v; best = c; }
+            if (v != v) continue;                                    /* a NaN entry never wins (the reference never meets one) */
+            if (best < 0 || v > bestv) { bestv = v; best = c; }
         }
+        if (best < 0) { best = 0; bestv = (float)probs[i * nc]; }    /* no comparable entry: class 0, its NaN as the score */
         float* o = out + i * out_stride;
         o[4] = (float)best;                                          /* :79 */
         o[5] = bestv;                                                /* :80 */

@@ -157,7 +157,8 @@ def pyramid_roi_align(rois, fmaps, pool: int, image_w: float, image_h: float) ->
 
 
 def classifier_postprocess(probs, bbox) -> np.ndarray:
-    """probs (n, nc), bbox (n, nc*4) → (n, 6) rows (dy,dx,dh,dw,classId,score)."""
+    """probs (n, nc), bbox (n, nc*4) → (n, 6) rows (dy,dx,dh,dw,classId,score).  NaN entries never win; a row with no
+    comparable entry yields class 0, score = its probability at index 0 (the NaN as it is) and class 0's deltas."""
     p = np.ascontiguousarray(probs, dtype=np.float64)
     b = np.ascontiguousarray(bbox, dtype=np.float64).reshape(p.shape[0], -1)
     out = np.empty((p.shape[0], 6), dtype=np.float32)

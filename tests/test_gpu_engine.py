@@ -422,6 +422,411 @@ def test_engine_fp16_range_watchdog(pkg, small_model, weights_mod, tmp_path):
     pkg.MaskRCNNConfig.defaultConfig().anchorsURL = os.path.join(d, "anchors.bin")
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# LOCAL overflows: the first tensor to leave the fp16 range lies past the stem, so Inf / NaN run through the rest of the
+# pipeline (ROI align, softmax, the classifier's arg-max, DetectionLayer, the mask select) before the watchdog word is read
+# ---------------------------------------------------------------------------------------------------------------------
+FP16_LIMIT = 65504.0
+TRUNK_TAPS = ["C1", "C2", "C3", "C4", "C5", "P2", "P3", "P4", "P5"]
+# (the tap compared after a recovery is the deepest one that is a CONTINUOUS function of the image — a trunk tap or the RPN's deltas: behind the
+#  proposal and detection stages two engines that differ by 1e-5 may pick other rows, and no norm compares those; the heads' depths therefore
+#  compare P2, as test_engine_fp16_range_watchdog does, and the heads' own tensors only where the discrete stages agreed bit for bit)
+LOCAL_OVERFLOWS = {  # depth: (file, convolution, its BatchNorm, the first tensor out of range, taps that must stay in range, tap compared after a recovery,
+    #         the next layer whose kernel takes 2^-k so that only the named tensor grows | None: everything behind it grows with it)
+    "c5_last_block": ("MaskRCNN", "res5c_branch2c", "bn5c_branch2c", "C5", ["C1", "C2", "C3", "C4"], "C5", None),
+    "c5_entry_shortcut": ("MaskRCNN", "res5a_branch1", "bn5a_branch1", "C5", ["C1", "C2", "C3", "C4"], "C5", None),
+    "fpn_p3_alone": ("MaskRCNN", "fpn_p3", None, "P3", ["C1", "C2", "C3", "C4", "C5", "P2", "P4", "P5"], "P3", None),
+    "rpn_shared_3x3": ("MaskRCNN", "rpn_conv_shared", None, "rpn_feat", TRUNK_TAPS, "rpn_deltas", None),
+    "box_head_fc1": ("Classifier", "mrcnn_class_conv1", "mrcnn_class_bn1", "cls_h1", TRUNK_TAPS + ["pooled"], "P2", "mrcnn_class_conv2"),
+    "mask_head_conv1": ("Mask", "mrcnn_mask_conv1", "mrcnn_mask_bn1", "mask_t1", TRUNK_TAPS + ["pooled", "pooled_mask"], "P2", "mrcnn_mask_conv2"),
+    "box_head_fc1_to_the_logits": ("Classifier", "mrcnn_class_conv1", "mrcnn_class_bn1", "cls_h1", TRUNK_TAPS + ["pooled"], "P2", None),
+    "mask_head_conv1_to_the_deconvolution": ("Mask", "mrcnn_mask_conv1", "mrcnn_mask_bn1", "mask_t1", TRUNK_TAPS + ["pooled", "pooled_mask"], "P2", None),
+}
+# Unrecoverable BY DESIGN in the split modes: behind these edits the heads' last tensors (logits and box deltas; the mask deconvolution's output) grow
+# by the same 2^k.  They belong to the FIXED group "outputs" (exponent 0: their consumers are fp32 arithmetic), which a recovery cannot rescale, and
+# the epilogues that store them are watched like every other: once they pass 65504 the recomputed batch trips again and the documented error stands.
+FIXED_GROUP_DEPTHS = ("box_head_fc1_to_the_logits", "mask_head_conv1_to_the_deconvolution")
+
+
+def _scaled_layer(tensors, conv, bn, k, comp=None):
+    """The layer's output before its activation times 2^k, exactly: kernel, bias (and the BatchNorm mean) carry 2^a, gamma 2^(k-a), beta 2^k —
+    every tensor stays fp16-representable (asserted).  comp: the next layer's kernel times 2^-k, rounded to fp16 (its small entries become
+    subnormal: the same file feeds every engine compared)."""
+    t = dict(tensors)
+    if comp:
+        t[f"{comp}/kernel"] = np.ldexp(t[f"{comp}/kernel"].astype(np.float32), -k).astype(np.float16)
+    a = k // 2 if bn else k
+    mul = {f"{conv}/kernel": a, f"{conv}/bias": a}
+    if bn:
+        mul.update({f"{bn}/mean": a, f"{bn}/gamma": k - a, f"{bn}/beta": k})
+    for name, e in mul.items():
+        v = np.ldexp(t[name].astype(np.float32), e)
+        h = v.astype(np.float16)
+        assert np.isfinite(h).all() and np.array_equal(h.astype(np.float32), v), name
+        t[name] = h
+    return t
+
+
+def _write_model(weights_mod, src, dst, cfg, edits):
+    os.makedirs(dst)
+    for kind in ("MaskRCNN", "Classifier", "Mask"):
+        meta, tensors = weights_mod.read_mrcw(os.path.join(src, f"{kind}.mrcw"))
+        weights_mod.write_mrcw(os.path.join(dst, f"{kind}.mrcw"), meta, edits[kind](tensors) if kind in edits else tensors)
+    __import__("importlib").import_module("mask-rcnn-coreml_amd.anchors").write_anchors_bin(os.path.join(dst, "anchors.bin"), cfg)
+    return dst
+
+
+def _bn_fold(tensors, meta, conv, bn):
+    f = lambda n: tensors[n].astype(np.float64)
+    if not bn:
+        return np.ones_like(f(f"{conv}/bias")), f(f"{conv}/bias")
+    sc = f(f"{bn}/gamma") / np.sqrt(f(f"{bn}/variance") + float(meta.get("bn_eps", 1e-3)))
+    return sc, (f(f"{conv}/bias") - f(f"{bn}/mean")) * sc + f(f"{bn}/beta")
+
+
+def _first_hot_tensor_absmax(m32, cfg, weights_mod, model_dir, depth, batch):
+    """max |v| of the depth's target tensor in the exact-fp32 engine: its tap where it has one; otherwise the layer evaluated in float64 on the
+    engine's tap of its INPUT (P2 for the RPN's shared layer — the first level it runs on; the pooled ROI rows for the heads)."""
+    import torch
+    import torch.nn.functional as F
+    kind, conv, bn, target = LOCAL_OVERFLOWS[depth][:4]
+    if target in TRUNK_TAPS:
+        return max(float(np.abs(m32.read_tensor(target, b)).max()) for b in range(batch))
+    meta, tensors = weights_mod.read_mrcw(os.path.join(model_dir, f"{kind}.mrcw"))
+    sc, sh = _bn_fold(tensors, meta, conv, bn)
+    w = torch.from_numpy(tensors[f"{conv}/kernel"].astype(np.float64))                 # (O, I, kh, kw)
+    best = 0.0
+    for b in range(batch):
+        if target == "rpn_feat":
+            h, wd = cfg.feature_shapes()[0]
+            x = m32.read_tensor("P2", b).reshape(1, h, wd, 256)
+            y = F.conv2d(torch.from_numpy(x.astype(np.float64)).permute(0, 3, 1, 2), w, padding=1)
+        elif target == "cls_h1":
+            x = m32.read_tensor("pooled", b).reshape(cfg.max_proposals, 7, 7, 256)
+            y = F.conv2d(torch.from_numpy(x.astype(np.float64)).permute(0, 3, 1, 2), w)
+        else:
+            x = m32.read_tensor("pooled_mask", b).reshape(cfg.max_detections, 14, 14, 256)
+            y = F.conv2d(torch.from_numpy(x.astype(np.float64)).permute(0, 3, 1, 2), w, padding=1)
+        y = torch.relu(y * torch.from_numpy(sc)[None, :, None, None] + torch.from_numpy(sh)[None, :, None, None])
+        best = max(best, float(y.abs().max()))
+    return best
+
+
+@pytest.fixture(scope="module")
+def local_overflow_models(small_model, weights_mod, tmp_path_factory):
+    """depth -> (directory of the edited model, the fp32 engine's tap it is compared on): one weight group times 2^k per depth, k the smallest
+    power for which the exact-fp32 engine shows the target tensor beyond TWICE the fp16 range while every tap upstream stays below HALF of it."""
+    models = __import__("importlib").import_module("mask-rcnn-coreml_amd.models")
+    d, cfg = small_model
+    images = rand_images(1, cfg.image_height, cfg.image_width, seed=2)
+    base = models.load_maskrcnn(d, max_batch=1)
+    base.predict(images)
+    root = str(tmp_path_factory.mktemp("local_overflow"))
+    out = {}
+    for depth, (kind, conv, bn, target, upstream, tap, comp) in LOCAL_OVERFLOWS.items():
+        k = int(np.ceil(np.log2(2.2 * FP16_LIMIT / _first_hot_tensor_absmax(base, cfg, weights_mod, d, depth, 1))))
+        for attempt in range(4):          # (C5 = relu(2^k branch + shortcut) is not homogeneous in k: one or two more steps may be needed)
+            hot = _write_model(weights_mod, d, os.path.join(root, f"{depth}_{k}"), cfg, {kind: lambda t: _scaled_layer(t, conv, bn, k, comp)})
+            m32 = models.load_maskrcnn(hot, max_batch=1)
+            det32, mask32 = m32.predict(images)
+            top = _first_hot_tensor_absmax(m32, cfg, weights_mod, hot, depth, 1)
+            if top > 2 * FP16_LIMIT:
+                break
+            k += 1
+        below = {n: float(np.abs(m32.read_tensor(n, 0)).max()) for n in upstream}
+        print(f"{depth}: 2^{k}, {target} reaches {top:.4g}, upstream {below}")
+        assert top > 2 * FP16_LIMIT, (depth, k, top)
+        assert max(below.values()) < FP16_LIMIT / 2, (depth, below)
+        assert m32.get_int("range_overflows") == 0
+        heads32 = {n: m32.read_tensor(n, 0).copy() for n in ("rois", "cls_bbox", "detections", "pooled_mask")}
+        out[depth] = (hot, m32.read_tensor(tap, 0).copy(), det32, heads32)
+    __import__("importlib").import_module("mask-rcnn-coreml_amd").MaskRCNNConfig.defaultConfig().anchorsURL = os.path.join(d, "anchors.bin")
+    return out, images
+
+
+def cfg_of(model_fixture):
+    return model_fixture[1]
+
+
+def _good_model_still_predicts(models, small_model, images, mode):
+    d, cfg = small_model
+    ok = models.load_maskrcnn(d, max_batch=1, compute_dtype=mode)
+    det, _ = ok.predict(images)
+    assert ok.get_int("range_overflows") == 0 and np.isfinite(det).all() and (det[..., 5] > 0).any()
+
+
+@pytest.mark.parametrize("mode", ["f16", "f32s", "f32x3"])
+@pytest.mark.parametrize("depth", list(LOCAL_OVERFLOWS))
+def test_engine_local_overflow_is_refused_or_recovered(pkg, small_model, weights_mod, local_overflow_models, depth, mode):
+    """One tensor past the stem leaves the fp16 range: MRCNN_F16 refuses the predict, the split modes recompute it with lowered exponents and
+    agree with the exact-fp32 engine — at EVERY depth, although everything behind the hot tensor has run on Inf / NaN by the time the word is read.
+    Records with range_overflows == 0 are never accepted; no depth may fault; a good model loaded afterwards still predicts."""
+    models = __import__("importlib").import_module("mask-rcnn-coreml_amd.models")
+    table, images = local_overflow_models
+    hot, tap32, det32, heads32 = table[depth]
+    tap = LOCAL_OVERFLOWS[depth][5]
+    m = models.load_maskrcnn(hot, max_batch=1, compute_dtype=mode)
+    try:
+        if mode == "f16":
+            with pytest.raises(Exception, match="left the fp16 range"):
+                m.predict(images)
+            assert m.get_int("range_overflows") == 1 and m.get_int("range_recoveries") == 0
+        else:
+            if depth in FIXED_GROUP_DEPTHS:              # the documented error after ONE attempted recovery, never records
+                with pytest.raises(Exception, match="left the fp16 range"):
+                    m.predict(images)
+                assert m.get_int("range_overflows") == 1 and m.get_int("range_recoveries") == 1
+            else:
+                got, gmask = m.predict(images)           # trips, recovers, returns valid records
+                assert m.get_int("range_overflows") == 1 and m.get_int("range_recoveries") == 1
+                assert _rel(m.read_tensor(tap, 0), tap32) < 5e-5, (depth, mode)
+                assert np.isfinite(got).all() and np.isfinite(gmask).all()
+                # The recomputed HEAD itself, against float64 on this engine's OWN tap of the head's input (two engines' proposals and detections
+                # differ in their last bits, so the fp32 engine's head tensors are no reference): the same 5e-5 bar on the box deltas; on the
+                # masks the bar applied to the selected class's logits and carried through the sigmoid, whose slope is at most 1/4.
+                cfg = cfg_of(small_model)
+                if LOCAL_OVERFLOWS[depth][0] == "Classifier":
+                    want = _box_head_deltas64(m.read_tensor("pooled", 0), weights_mod, hot, cfg)
+                    assert _rel(m.read_tensor("cls_bbox", 0).reshape(want.shape), want) < 5e-5, (depth, mode)
+                if LOCAL_OVERFLOWS[depth][0] == "Mask":
+                    # (rows in front of the first one the removeZeros rule drops — a pooled row holding an exact zero — keep compact index = row)
+                    flags = np.asarray(m.read_tensor("mask_row_flags", 0)).reshape(-1)[:cfg.max_detections]
+                    n = int(np.argmin(flags != 0)) if (flags == 0).any() else cfg.max_detections
+                    assert n >= 1 and (got[0][:n, 5] > 0).all()
+                    logits = _mask_head_maxima(m, weights_mod, hot, cfg, logits_of=got[0][:, 4].astype(np.int64))[:n]
+                    want = 1.0 / (1.0 + np.exp(-logits))
+                    assert np.abs(gmask[0].reshape(cfg.max_detections, -1)[:n] - want).max() <= 0.25 * 5e-5 * np.abs(logits).max() + 1e-6, (depth, mode)
+                m.predict(images)
+                assert m.get_int("range_recoveries") == 1   # the lowered exponents hold
+    finally:
+        pkg.MaskRCNNConfig.defaultConfig().anchorsURL = os.path.join(small_model[0], "anchors.bin")
+    _good_model_still_predicts(models, small_model, images, mode)
+
+
+FUSED_FORM_CASES = [  # knob, values, depth (None: the stem's BatchNorm times 2^12, as test_engine_fp16_range_watchdog), modes
+    ("conv_stem", (0, 1, 2), None, ("f16", "f32s", "f32x3"), 1),
+    ("mask_fused", (0, 1), "mask_head_conv1", ("f16", "f32s", "f32x3"), 1),
+    ("mask_fused", (0, 1), "mask_head_conv1_to_the_deconvolution", ("f16",), 1),
+]
+
+
+@pytest.mark.parametrize("knob,values,depth,modes,default", FUSED_FORM_CASES, ids=[c[0] + ("" if c[2] in (None, "mask_head_conv1") else "-" + c[2]) for c in FUSED_FORM_CASES])
+def test_engine_overflow_in_the_engine_only_fused_forms(pkg, small_model, weights_mod, local_overflow_models, tmp_path, knob, values, depth, modes, default):
+    """The fused stem (kernels_conv_stem.hip) and both forms of the mask head's tail report the same as the launches they replace (the forms that
+    need larger levels — fused shortcut, fused RPN heads, the selected-class epilogue as the FIRST site — have tests of their own below)."""
+    L = __import__("importlib").import_module("mask-rcnn-coreml_amd._lib")
+    models = __import__("importlib").import_module("mask-rcnn-coreml_amd.models")
+    d, cfg = small_model
+    table, images = local_overflow_models
+    if depth is None:
+        scale = lambda t: {**t, "bn_conv1/gamma": (t["bn_conv1/gamma"].astype(np.float32) * 4096).astype(np.float16)}
+        hot = _write_model(weights_mod, d, str(tmp_path / "hot_stem"), cfg, {"MaskRCNN": scale})
+    else:
+        hot = table[depth][0]
+    try:
+        for v in values:
+            L.check(L.lib().mrcnn_debug_set(knob.encode(), v))
+            for mode in modes:
+                m = models.load_maskrcnn(hot, max_batch=1, compute_dtype=mode)
+                if mode == "f16":
+                    with pytest.raises(Exception, match="left the fp16 range"):
+                        m.predict(images)
+                    assert m.get_int("range_overflows") == 1, (knob, v)
+                else:
+                    got, _ = m.predict(images)
+                    assert m.get_int("range_overflows") == 1 and m.get_int("range_recoveries") == 1, (knob, v, mode)
+                    assert np.isfinite(got).all()
+    finally:
+        L.check(L.lib().mrcnn_debug_set(knob.encode(), default))
+        pkg.MaskRCNNConfig.defaultConfig().anchorsURL = os.path.join(d, "anchors.bin")
+    _good_model_still_predicts(models, small_model, images, "f16")
+
+
+def _launch_shapes(m, images):
+    """{(M, N, K): launches} and the total of one profiled predict"""
+    m.conv_profile_enable(True)
+    m.predict(images)
+    m.conv_profile_enable(False)
+    shapes = {}
+    for (M, N, K, tile, n, *_) in m.conv_profile_shapes():
+        shapes[(M, N, K)] = shapes.get((M, N, K), 0) + n
+    return shapes, sum(shapes.values())
+
+
+@pytest.mark.parametrize("mode", ["f32s", "f32x3"])
+def test_engine_overflow_inside_the_fused_shortcut_launch(pkg, weights_mod, tmp_path_factory, tmp_path, mode):
+    """The shortcut computed INSIDE branch2c's launch (conv_device.h: conv_epilogue_wave with the second accumulator set) is a stored tensor of the
+    two-launch form, watched there by its own launch; the fused launch must report it as well.  A 320 x 448 model at batch 3, where C2's entry fuses
+    (210 M tiles x 2 column tiles; asserted on the launch counts).  bn2a_branch1 gets mean 60000 and four times its gamma: EVERY shortcut value lies
+    below -2 x 65504 (float64 on the fp32 engine's C1 tap), so res2a's output is relu(branch + shortcut) = 0 and nothing else in the network
+    leaves the range — the shortcut's check is the only site that can trip."""
+    import importlib
+    L = importlib.import_module("mask-rcnn-coreml_amd._lib")
+    models = importlib.import_module("mask-rcnn-coreml_amd.models")
+    d, cfg = make_model_dir(tmp_path_factory, pkg, weights_mod, "scfuse_hot" + mode, architecture="resnet50", input_image_shape=(320, 448, 3),
+                            num_classes=21, pre_nms_max_proposals=1000, max_proposals=128, max_detections=32)
+    B = 3
+    images = rand_images(B, 320, 448, seed=11)
+
+    def edit(t):
+        t = dict(t)
+        t["bn2a_branch1/mean"] = np.full_like(t["bn2a_branch1/mean"], 60000.0)
+        t["bn2a_branch1/gamma"] = (t["bn2a_branch1/gamma"].astype(np.float32) * 4).astype(np.float16)
+        return t
+    hot = _write_model(weights_mod, d, str(tmp_path / "hot"), cfg, {"MaskRCNN": edit})
+    try:
+        m32 = models.load_maskrcnn(hot, max_batch=B)
+        det32, _ = m32.predict(images)
+        meta, tensors = weights_mod.read_mrcw(os.path.join(hot, "MaskRCNN.mrcw"))
+        sc, sh = _bn_fold(tensors, meta, "res2a_branch1", "bn2a_branch1")
+        kern = tensors["res2a_branch1/kernel"].astype(np.float64).reshape(256, 64)
+        for b in range(B):
+            short = m32.read_tensor("C1", b).reshape(-1, 64).astype(np.float64) @ kern.T * sc + sh
+            assert short.max() < -2 * FP16_LIMIT, short.max()
+            assert max(float(np.abs(m32.read_tensor(n, b)).max()) for n in TRUNK_TAPS) < FP16_LIMIT / 2
+        assert m32.get_int("range_overflows") == 0 and np.isfinite(det32).all()
+        p2 = m32.read_tensor("P2", 1).copy()
+        c2_shape = (B * 80 * 112, 256, 64)          # res2a_branch2c, res2a_branch1 and the branch2c of res2b / res2c
+        counts = {}
+        for knob in (1, 0):
+            L.check(L.lib().mrcnn_debug_set(b"conv_scfuse", knob))
+            counts[knob] = _launch_shapes(models.load_maskrcnn(d, max_batch=B, compute_dtype=mode), images)
+            m = models.load_maskrcnn(hot, max_batch=B, compute_dtype=mode)
+            got, gmask = m.predict(images)
+            assert m.get_int("range_overflows") == 1 and m.get_int("range_recoveries") == 1, (knob, mode)
+            assert np.isfinite(got).all() and np.isfinite(gmask).all()
+            assert _rel(m.read_tensor("P2", 1), p2) < 5e-5, (knob, mode)
+        # the fused form ran at C2 with the knob on: its shortcut is no launch of its own
+        assert counts[1][0].get(c2_shape, 0) == 3 and counts[0][0].get(c2_shape, 0) == 4, (counts[1][0].get(c2_shape), counts[0][0].get(c2_shape))
+        assert counts[1][1] < counts[0][1]
+    finally:
+        L.check(L.lib().mrcnn_debug_set(b"conv_scfuse", 1))
+        pkg.MaskRCNNConfig.defaultConfig().anchorsURL = None
+
+
+@pytest.mark.parametrize("mode", ["f16", "f32s", "f32x3"])
+def test_engine_overflow_under_the_fused_rpn_heads(pkg, weights_mod, tmp_path_factory, tmp_path, mode):
+    """The RPN's shared 3x3 layer with the two heads in its epilogue (split modes: kernels_conv_halo.hip, HEAD; fp16: kernels_conv3x3_h.hip, HEAD)
+    never stores the 512-channel tensor it watches.  A 512^2 model: P2 is 128 x 128 = 16384 pixels, fused in every mode (asserted on the launch
+    counts).  rpn_conv_shared times 2^k: the fp32 engine's taps stay below half the range, the shared layer's output on P2 (float64 on a 34 x 34
+    crop of the P2 tap: its 32 x 32 interior) passes twice the range.  Fused and unfused forms report the same."""
+    import importlib
+    import torch
+    import torch.nn.functional as F
+    L = importlib.import_module("mask-rcnn-coreml_amd._lib")
+    models = importlib.import_module("mask-rcnn-coreml_amd.models")
+    d, cfg = make_model_dir(tmp_path_factory, pkg, weights_mod, "rpnhot" + mode, architecture="resnet50", input_image_shape=(512, 512, 3),
+                            num_classes=21, pre_nms_max_proposals=1000, max_proposals=128, max_detections=32)
+    B = 2
+    images = rand_images(B, 512, 512, seed=5)
+
+    def shared_layer_max(m32, model_dir):
+        meta, tensors = weights_mod.read_mrcw(os.path.join(model_dir, "MaskRCNN.mrcw"))
+        w = torch.from_numpy(tensors["rpn_conv_shared/kernel"].astype(np.float64))
+        bias = torch.from_numpy(tensors["rpn_conv_shared/bias"].astype(np.float64))
+        x = m32.read_tensor("P2", 0).reshape(128, 128, 256)[:34, :34].astype(np.float64)
+        y = F.conv2d(torch.from_numpy(x).permute(2, 0, 1)[None], w) + bias[None, :, None, None]
+        return float(torch.relu(y).max())
+    knob_name, on, offs = ("conv_c3h", 1, (3, 0)) if mode == "f16" else ("conv_halo", 1, (0,))
+    try:
+        base = models.load_maskrcnn(d, max_batch=B)
+        base.predict(images)
+        k = int(np.ceil(np.log2(2.2 * FP16_LIMIT / shared_layer_max(base, d))))
+        hot = _write_model(weights_mod, d, str(tmp_path / "hot"), cfg, {"MaskRCNN": lambda t: _scaled_layer(t, "rpn_conv_shared", None, k)})
+        m32 = models.load_maskrcnn(hot, max_batch=B)
+        m32.predict(images)
+        assert shared_layer_max(m32, hot) > 2 * FP16_LIMIT
+        for b in range(B):
+            assert max(float(np.abs(m32.read_tensor(n, b)).max()) for n in TRUNK_TAPS) < FP16_LIMIT / 2
+        deltas32 = m32.read_tensor("rpn_deltas", 0).copy()
+        totals = {}
+        for v in (on,) + offs:
+            L.check(L.lib().mrcnn_debug_set(knob_name.encode(), v))
+            totals[v] = _launch_shapes(models.load_maskrcnn(d, max_batch=B, compute_dtype=mode), images)[1]
+            m = models.load_maskrcnn(hot, max_batch=B, compute_dtype=mode)
+            if mode == "f16":
+                with pytest.raises(Exception, match="left the fp16 range"):
+                    m.predict(images)
+                assert m.get_int("range_overflows") == 1 and m.get_int("range_recoveries") == 0, (knob_name, v)
+            else:
+                got, gmask = m.predict(images)
+                assert m.get_int("range_overflows") == 1 and m.get_int("range_recoveries") == 1, (knob_name, v)
+                assert np.isfinite(got).all() and np.isfinite(gmask).all()
+                assert _rel(m.read_tensor("rpn_deltas", 0), deltas32) < 5e-5, (knob_name, v)
+        # with the knob on, fused levels have no head launch of their own
+        assert all(totals[on] < totals[v] for v in offs), totals
+    finally:
+        L.check(L.lib().mrcnn_debug_set(knob_name.encode(), 1))
+        pkg.MaskRCNNConfig.defaultConfig().anchorsURL = None
+
+
+def _box_head_deltas64(pooled, weights_mod, model_dir, cfg):
+    """the box head's deltas (rows, nc * 4) in float64 from an engine's pooled tap (rows of 7 x 7 x 256, NHWC)"""
+    meta, t = weights_mod.read_mrcw(os.path.join(model_dir, "Classifier.mrcw"))
+    x = pooled.reshape(cfg.max_proposals, -1).astype(np.float64)
+    for conv, bn in (("mrcnn_class_conv1", "mrcnn_class_bn1"), ("mrcnn_class_conv2", "mrcnn_class_bn2")):
+        k = t[f"{conv}/kernel"].astype(np.float64)
+        sc, sh = _bn_fold(t, meta, conv, bn)
+        x = np.maximum(x @ k.transpose(0, 2, 3, 1).reshape(k.shape[0], -1).T * sc + sh, 0.0)
+    return x @ t["mrcnn_bbox_fc/kernel"].astype(np.float64).T + t["mrcnn_bbox_fc/bias"].astype(np.float64)
+
+
+def _mask_head_maxima(m32, weights_mod, model_dir, cfg, logits_of=None):
+    """max |v| of the mask head's five stored tensors (four 3x3 layers, the deconvolution) in float64 on an engine's pooled_mask tap;
+    logits_of = class ids per row: instead, the (rows, 28 * 28) logits of those classes"""
+    import torch
+    import torch.nn.functional as F
+    meta, t = weights_mod.read_mrcw(os.path.join(model_dir, "Mask.mrcw"))
+    x = torch.from_numpy(m32.read_tensor("pooled_mask", 0).reshape(cfg.max_detections, 14, 14, 256).astype(np.float64)).permute(0, 3, 1, 2)
+    out = []
+    for i in range(1, 5):
+        sc, sh = _bn_fold(t, meta, f"mrcnn_mask_conv{i}", f"mrcnn_mask_bn{i}")
+        x = F.conv2d(x, torch.from_numpy(t[f"mrcnn_mask_conv{i}/kernel"].astype(np.float64)), padding=1)
+        x = torch.relu(x * torch.from_numpy(sc)[None, :, None, None] + torch.from_numpy(sh)[None, :, None, None])
+        out.append(float(x.abs().max()))
+    y = F.conv_transpose2d(x, torch.from_numpy(t["mrcnn_mask_deconv/kernel"].astype(np.float64)), stride=2)
+    y = torch.relu(y + torch.from_numpy(t["mrcnn_mask_deconv/bias"].astype(np.float64))[None, :, None, None])
+    if logits_of is not None:
+        z = F.conv2d(y, torch.from_numpy(t["mrcnn_mask/kernel"].astype(np.float64))) + torch.from_numpy(t["mrcnn_mask/bias"].astype(np.float64))[None, :, None, None]
+        return z.numpy()[np.arange(z.shape[0]), logits_of].reshape(z.shape[0], -1)
+    return out + [float(y.abs().max())]
+
+
+@pytest.mark.parametrize("mode", ["f16", "f32s", "f32x3"])
+def test_engine_overflow_first_in_the_mask_deconvolution(pkg, small_model, weights_mod, tmp_path, mode):
+    """The mask head's last stored tensor: with "mask_fused" 1 it exists only inside the deconvolution's selected-class epilogue
+    (conv_device.h: conv_epilogue_sel_wave), which therefore carries the watch; with 0 the tensor is stored and selected from.  mrcnn_mask_deconv
+    times 2^k: the four layers in front stay below half the range, the deconvolution's output passes twice the range (float64 on the fp32 engine's
+    pooled_mask tap).  It belongs to the fixed group `outputs` (FIXED_GROUP_DEPTHS): fp16 refuses, the split modes end in the documented error after
+    one attempted recovery — the same with either form."""
+    import importlib
+    L = importlib.import_module("mask-rcnn-coreml_amd._lib")
+    models = importlib.import_module("mask-rcnn-coreml_amd.models")
+    d, cfg = small_model
+    images = rand_images(1, cfg.image_height, cfg.image_width, seed=2)
+    try:
+        base = models.load_maskrcnn(d, max_batch=1)
+        base.predict(images)
+        k = int(np.ceil(np.log2(2.2 * FP16_LIMIT / _mask_head_maxima(base, weights_mod, d, cfg)[4])))
+        hot = _write_model(weights_mod, d, str(tmp_path / "hot"), cfg, {"Mask": lambda t: _scaled_layer(t, "mrcnn_mask_deconv", None, k)})
+        m32 = models.load_maskrcnn(hot, max_batch=1)
+        det32, mask32 = m32.predict(images)
+        mx = _mask_head_maxima(m32, weights_mod, hot, cfg)
+        assert max(mx[:4]) < FP16_LIMIT / 2 and mx[4] > 2 * FP16_LIMIT, mx
+        assert max(float(np.abs(m32.read_tensor(n, 0)).max()) for n in TRUNK_TAPS + ["pooled", "pooled_mask"]) < FP16_LIMIT / 2
+        assert np.isfinite(det32).all() and np.isfinite(mask32).all() and m32.get_int("range_overflows") == 0
+        for fused in (1, 0):
+            L.check(L.lib().mrcnn_debug_set(b"mask_fused", fused))
+            m = models.load_maskrcnn(hot, max_batch=1, compute_dtype=mode)
+            with pytest.raises(Exception, match="left the fp16 range"):
+                m.predict(images)
+            assert m.get_int("range_overflows") == 1 and m.get_int("range_recoveries") == (0 if mode == "f16" else 1), (fused, mode)
+    finally:
+        L.check(L.lib().mrcnn_debug_set(b"mask_fused", 1))
+        pkg.MaskRCNNConfig.defaultConfig().anchorsURL = os.path.join(d, "anchors.bin")
+    _good_model_still_predicts(models, small_model, images, mode)
+
+
 @pytest.mark.parametrize("mode", ["f32s", "f32x3"])
 def test_engine_f32s_full_size(pkg, orc, tmp_path_factory, weights_mod, mode):
     """BASELINE configs[1] shapes (R101, 1024², 81 classes) in the split modes, batch 2: staged parity at fp32 tolerances."""

@@ -306,3 +306,40 @@ def test_roi_align_fp16_tiny_samples_keep_their_rows(pkg, orc):
     # the fixture really exercises the hazard: fp32 says "keep" where the rounded row would have been dropped
     assert want_flags[0] == 1 and want_flags[1] == 0
     assert 0 not in valid16, "fixture does not produce a sample that rounds to zero in fp16"
+
+
+def test_overflow_inside_the_fused_bottleneck_tail(pkg, weights_mod, full_model, full_images, tmp_path):
+    """The fused bottleneck tail ("conv_tail" 1: a 3x3 `branch2b` and the 1x1 `branch2c` behind it in one launch where the grid fills the chip —
+    C4 at 1024^2, batch 8) keeps branch2b's output on chip and watches it there (kernels_conv_halo.hip, TAIL).  res4c_branch2b's output times
+    2^17 (exactly: _scaled_layer) with branch2c's kernel times 2^-17, so that ONLY that tensor grows — behind a hot C4 the RPN's logits, a fixed
+    group, would leave the range too and no recovery could succeed.  The tensor has no tap: every tap of the exact-fp32 engine stays below half
+    the range (asserted), and the hot tensor is 2^17 times a post-ReLU tensor of a unit-variance layer over 8 x 4096 x 256 elements, whose maximum
+    exceeds 1, i.e. more than 2 x 65504 = 2^17 (reasoned; the trip itself, with every tap in range, shows it).  The fused launch and the two
+    launches must both trip once and recover."""
+    import os
+    from test_gpu_engine import _write_model, _scaled_layer, _rel, FP16_LIMIT
+    L = __import__("importlib").import_module("mask-rcnn-coreml_amd._lib")
+    models = __import__("importlib").import_module("mask-rcnn-coreml_amd.models")
+    d, cfg = full_model
+    k = 17
+    hot = _write_model(weights_mod, d, str(tmp_path / "hot"), cfg, {"MaskRCNN": lambda t: _scaled_layer(t, "res4c_branch2b", "bn4c_branch2b", k, comp="res4c_branch2c")})
+    try:
+        m32 = models.load_maskrcnn(hot, max_batch=8)
+        m32.predict(full_images)
+        for b in (0, 7):
+            assert max(float(np.abs(m32.read_tensor(n, b)).max()) for n in ("C1", "C2", "C3", "C4", "C5", "P2", "P3", "P4", "P5")) < FP16_LIMIT / 2
+        p4 = m32.read_tensor("P4", 7).copy()
+        for tail in (1, 0):
+            L.check(L.lib().mrcnn_debug_set(b"conv_tail", tail))
+            m = models.load_maskrcnn(hot, max_batch=8, compute_dtype="f32x3")
+            m.conv_profile_enable(True)
+            got, _ = m.predict(full_images)
+            m.conv_profile_enable(False)
+            assert m.get_int("range_overflows") == 1 and m.get_int("range_recoveries") == 1, tail
+            assert (m.conv_profile()["128x256tail"][0] > 0) == bool(tail)          # the fused form ran / did not
+            assert np.isfinite(got).all()
+            assert _rel(m.read_tensor("P4", 7), p4) < 5e-5, tail
+    finally:
+        L.check(L.lib().mrcnn_debug_set(b"conv_tail", 0))
+        pkg.MaskRCNNConfig.defaultConfig().anchorsURL = None
+
