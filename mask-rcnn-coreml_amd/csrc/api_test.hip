@@ -5,6 +5,7 @@
 #include <random>
 
 #include "api_util.h"
+#include "knobs.h"
 
 using namespace mrcnn;
 
@@ -174,15 +175,14 @@ extern "C" int mrcnn_bench_conv_dtype(int batch, int h, int w, int cin, int cout
 // One convolution of the engine's kernel family on caller data (parity tests of the kernels themselves: every tile
 // shape / pipeline variant must give bit-identical results, since the choice depends on the batch size)
 // ================================================================================================
-static int g_conv2d_alias_res = 0;      // mrcnn_conv2d_nhwc writes its output in place over the residual (tests of the in-place contract)
+static int& g_conv2d_alias_res = knob("conv2d_alias_res", nullptr, 0);      // mrcnn_conv2d_nhwc writes its output in place over the residual (tests of the in-place contract)
 extern "C" int mrcnn_debug_set(const char* key, int value)
 {
     return guarded([&] {
         MRCNN_REQUIRE(key, MRCNN_ERR_INVALID, "null key");
         MRCNN_REQUIRE(test_knobs_armed(), MRCNN_ERR_UNSUPPORTED, "mrcnn_debug_set('%s'): the test / measurement knobs are armed only in a process started with "
                       "MRCNN_TEST_KNOBS=1 (include/maskrcnn_hip_test.h); a production host runs the shipped policy", key);
-        if (strcmp(key, "conv2d_alias_res") == 0) { g_conv2d_alias_res = value; return; }
-        MRCNN_REQUIRE(conv_debug_set(key, value) || boxes_debug_set(key, value) || engine_debug_set(key, value), MRCNN_ERR_INVALID, "unknown debug key '%s'", key);
+        MRCNN_REQUIRE(knob_set(key, value), MRCNN_ERR_INVALID, "unknown debug key '%s'", key);
     });
 }
 
@@ -436,7 +436,7 @@ extern "C" int mrcnn_model_conv_profile_enable(mrcnn_model* model, int on)
 extern "C" int mrcnn_model_conv_profile_get(mrcnn_model* model, int tile, int64_t* launches, double* total_ms, double* total_flops)
 {
     return guarded([&] {
-        MRCNN_REQUIRE(model && launches && total_ms && total_flops && tile >= 0 && tile < 9, MRCNN_ERR_INVALID, "bad argument");
+        MRCNN_REQUIRE(model && launches && total_ms && total_flops && tile >= 0 && tile < TILE_CLASSES, MRCNN_ERR_INVALID, "bad argument");
         HIP_CHECK(hipStreamSynchronize(model->m.stream));
         model->m.conv_profile.collect();
         const auto& sl = model->m.conv_profile.by_tile[tile];
@@ -447,7 +447,7 @@ extern "C" int mrcnn_model_conv_profile_get(mrcnn_model* model, int tile, int64_
 extern "C" int mrcnn_model_conv_profile_bytes(mrcnn_model* model, int tile, double* total_bytes)
 {
     return guarded([&] {
-        MRCNN_REQUIRE(model && total_bytes && tile >= 0 && tile < 9, MRCNN_ERR_INVALID, "bad argument");
+        MRCNN_REQUIRE(model && total_bytes && tile >= 0 && tile < TILE_CLASSES, MRCNN_ERR_INVALID, "bad argument");
         HIP_CHECK(hipStreamSynchronize(model->m.stream));
         model->m.conv_profile.collect();
         *total_bytes = model->m.conv_profile.by_tile[tile].bytes;

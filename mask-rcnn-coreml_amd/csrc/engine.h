@@ -139,7 +139,6 @@ struct MaskHead {
     void forward_full(hipStream_t s, int n);
 };
 
-bool engine_debug_set(const char* key, int value);     // "mask_fused"
 
 struct StageTimer {
     bool enabled = false;

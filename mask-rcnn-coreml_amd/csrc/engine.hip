@@ -11,6 +11,7 @@
 #include <dlfcn.h>
 
 #include "engine.h"
+#include "knobs.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -508,12 +509,7 @@ void MaskHead::load(const MrcwFile& f, int capacity_rows, int dtype_)
 }
 
 // process-wide A/B switch of the fused mask tail (tests, tools/e2e_ab.py): mrcnn_debug_set("mask_fused", 0 | 1)
-static int g_fuse_mask_tail = 1;
-bool engine_debug_set(const char* key, int value)
-{
-    if (std::string(key) == "mask_fused") { g_fuse_mask_tail = value; return true; }
-    return false;
-}
+static int& g_fuse_mask_tail = knob("mask_fused", nullptr, 1);
 
 void MaskHead::forward_features(hipStream_t s, const void* pooled_nhwc, int n, const int32_t* sel_cid, float* sel_partial)
 {

@@ -227,7 +227,8 @@ struct PngBuffers {
 void png_encode_forward(hipStream_t s, const PngBuffers& b, int batch, long long total_blocks, int format, int rows);
 
 // ================================================================================================
-// Convolution family + element-wise helpers (kernels_conv.hip)
+// Convolution family + element-wise helpers (kernels_conv.hip: the 128-row kernel; conv_dispatch.hip: which kernel runs a layer;
+// kernels_elementwise.hip: the helpers)
 // ================================================================================================
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_SIGMOID = 2 };
 
@@ -300,10 +301,22 @@ struct ConvDesc {
 // Live per-kernel profile of the conv family: when a profiler is active on the calling thread every
 // conv_forward launch is bracketed by HIP events on its own stream; collect() (after the stream
 // has been synchronised) folds the elapsed times into per-tile-shape totals.
+// The tile classes of the profile (the index of ConvProfile::by_tile, the `tile` of a shape key; bench.py reads the numbers)
+enum ConvTileClass {
+    TILE_128x128 = 0,
+    TILE_128x64 = 1,
+    TILE_128x32 = 2,
+    TILE_128x128_4WAVE = 3,      // 128x128 run by 4 waves of 32x128 (split modes, long K)
+    TILE_PP_256x256 = 4,         // 256x256 ping-pong
+    TILE_HALO = 5,               // persistent halo tiles (3x3 stride 1, split modes)
+    TILE_HALO_TAIL = 6,          // halo tiles with the fused bottleneck tail (3x3 + 1x1)
+    TILE_BNECK = 7,              // a whole identity bottleneck of the fp16 mode in one launch (kernels_bneck.hip; flops of its three layers)
+    TILE_C3H = 8,                // 16 x 16 halo tiles x 256 columns of the fp16 mode's 3x3 layers (kernels_conv3x3_h.hip)
+    TILE_CLASSES
+};
 struct ConvProfile {
     struct Slot { long launches = 0; double ms = 0, flops = 0, bytes = 0; };       // bytes: ALGORITHMIC bytes (conv_algorithmic_bytes: every operand once)
-    Slot by_tile[9];                 // 8: 16 x 16 halo tiles x 256 columns of the fp16 mode's 3x3 layers (kernels_conv3x3_h.hip); 7: a whole identity bottleneck of the fp16 mode in one launch (kernels_bneck.hip; flops of its three layers); 0: 128x128, 1: 128x64, 2: 128x32, 3: 128x128 run by 4 waves of 32x128 (split modes, long K), 4: 256x256 ping-pong,
-                                     // 5: persistent halo tiles (3x3 stride 1, split modes), 6: halo tiles with the fused bottleneck tail (3x3 + 1x1)
+    Slot by_tile[TILE_CLASSES];      // per ConvTileClass
     std::vector<hipEvent_t> pool;
     struct Shape { int M, N, K, tile; bool operator<(const Shape& o) const { return std::tie(M, N, K, tile) < std::tie(o.M, o.N, o.K, o.tile); } };
     std::map<Shape, Slot> by_shape;  // per GEMM shape (M = images·OH·OW, N = output columns, K = taps·Cin)
@@ -338,10 +351,6 @@ int conv_n_tile(int Cout);
 // sc != nullptr: `sc` is the 1x1 convolution whose output is d's residual (a ResNet stage's shortcut): computed inside d's launch where the pair
 // qualifies (bit-identical to the two launches; the shortcut tensor is then not written), as its own launch before d otherwise
 void conv_forward(hipStream_t s, const ConvDesc& d, const ConvDesc* sc = nullptr);
-// Test / measurement switches of the kernel choice ("conv_pp" 0|1, "conv_pp_split" 0|1, "conv_pp_min_tiles", "conv_pp_min_kt",
-// "conv_pp_min_fill" percent, "conv_pp_dbg" ablation bits); false = unknown key.
-bool conv_debug_set(const char* key, int value);
-bool boxes_debug_set(const char* key, int value);    // kernels_boxes.hip: "proposal_rank_sort", "nms_col_splits", "nms_class_fast" (no output bit depends on them)
 // Halo kernel (kernels_conv_halo.hip): 3x3 stride-1 layers of the split modes.  conv_halo_pack re-tiles [Npad][9][Cin] fp16
 // filters (device) into its granule layout; conv_halo_eligible says whether a layer can run on it (a property of the layer's
 // geometry and mode only — never of the batch: the K order of the kernel differs from the 128-row kernel's).
@@ -351,7 +360,6 @@ void conv_halo_pack_head(hipStream_t s, const void* wgt_std, int Npad, int Cin, 
 bool conv_halo_eligible(const ConvDesc& d);
 bool conv_halo_head_eligible(const ConvDesc& d);
 bool conv_halo_enabled();                   // the run-time switch mrcnn_debug_set("conv_halo") / MRCNN_HALO
-bool conv_halo_debug_set(const char* key, int value);     // "halo_geo" 0 = the round-3 tile geometries (A/B, bit-identity tests) | 1
 bool conv_halo_packable(int KH, int KW, int Cin, int Npad);   // the filter shapes conv_halo_eligible can accept (re-tile only those)
 int conv_halo_forward(hipStream_t s, ConvArgs a, const ConvDesc& d, int parts, int n_cus, const ConvArgs* tail = nullptr, const void* tail_w = nullptr);
 bool conv_halo_tail_packable(int KH, int KW, int Cin, int Npad);       // the 1x1 filters the fused bottleneck tail accepts (re-tiled with one tap)

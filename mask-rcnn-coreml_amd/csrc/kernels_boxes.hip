@@ -22,26 +22,17 @@
 
 #include "device_math.h"
 #include "kernels.h"
+#include "knobs.h"
 
 namespace mrcnn {
 
 static constexpr int CHUNK = 1024;   // scores per block in the select passes (256 threads × 4)
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-static int boxes_env_int(const char* name, int dflt) { const char* e = knob_env(name); return e && *e ? atoi(e) : dflt; }      // (honoured only with MRCNN_TEST_KNOBS=1)
 // Run-time switches (A/B and bit-identity tests; mrcnn_debug_set): none of them changes an output bit
-static int g_rank_sort = boxes_env_int("MRCNN_RANK_SORT", 1);       // "proposal_rank_sort": 1 rank counting over the chip (k_rank_decode), 0 the one-block bitonic sort
-static int g_nms_splits = boxes_env_int("MRCNN_NMS_SPLITS", 0);     // "nms_col_splits": column splits of k_nms_mask's grid; 0 = by policy (nms_col_splits)
-static int g_nms_fast = boxes_env_int("MRCNN_NMS_FAST", 1);         // "nms_class_fast": 1 the per-class limit test on the chunk's own candidates, 0 the round-4 test (count + 64)
-bool boxes_debug_set(const char* key, int value)
-{
-    const std::string k = key;
-    if (k == "proposal_rank_sort") g_rank_sort = value;
-    else if (k == "nms_col_splits") g_nms_splits = value;
-    else if (k == "nms_class_fast") g_nms_fast = value;
-    else return false;
-    return true;
-}
+static int& g_rank_sort = knob("proposal_rank_sort", "MRCNN_RANK_SORT", 1);       // 1 rank counting over the chip (k_rank_decode), 0 the one-block bitonic sort
+static int& g_nms_splits = knob("nms_col_splits", "MRCNN_NMS_SPLITS", 0);     // column splits of k_nms_mask's grid; 0 = by policy (nms_col_splits)
+static int& g_nms_fast = knob("nms_class_fast", "MRCNN_NMS_FAST", 1);         // 1 the per-class limit test on the chunk's own candidates, 0 the round-4 test (count + 64)
 // Column splits of the suppression-matrix launch.  Row block rb owns the column chunks rb .. W-1, so with a fixed split the blocks
 // of row 0 walk W / 16 chunks one after the other while the chip idles (single image, W = 94: six rounds, 79 us): as many splits as
 // keep the launch within the chip's wave slots — every wave at most one chunk on a single image (22 us) — and never fewer than four.

@@ -32,6 +32,7 @@
 // Epilogue: conv_epilogue_wave (conv_device.h) — wave-private LDS transpose, full-line stores — the same arithmetic, in the
 // same order, as every other kernel of the family.
 #include "conv_device.h"
+#include "knobs.h"
 
 #include <stdlib.h>
 #include <map>
@@ -41,9 +42,7 @@
 
 namespace mrcnn {
 
-ConvScratch* conv_current_scratch();      // kernels_conv.hip: the calling thread's scratch (conv_set_scratch)
-
-static int env_int_halo(const char* name, int dflt) { const char* e = knob_env(name); return e ? atoi(e) : dflt; }      // (honoured only with MRCNN_TEST_KNOBS=1)
+ConvScratch* conv_current_scratch();      // conv_dispatch.hip: the calling thread's scratch (conv_set_scratch)
 
 static constexpr int HALO_MAX_SLOT = 640;        // LDS pixel slots of one plane (region rows x LDS pitch <= this)
 static constexpr unsigned HALO_OOB = 0xC0000000u;
@@ -948,10 +947,10 @@ static int halo_linear_rows(int H, int W, int bm)
     return rows_touched + 2 * boundaries + 2;
 }
 
-static int g_halo_lat = env_int_halo("MRCNN_HALO_LAT", 1);     // grids under 3/4 of the chip even at 64 x 128: 64 x 64 tiles in the latency form (k_conv_halo_lat; bit-identical)
-static int g_halo_rounds = env_int_halo("MRCNN_HALO_ROUNDS", 1);     // 64-row tiles where they shorten the last round of a 128 x 128 grid
-static int g_halo_n64 = env_int_halo("MRCNN_HALO_N64", 2);     // 64-column 3x3 layers on the halo kernel: 1 as 128 x 64 tiles, 2 also 256 x 64 where the level allows
-static int g_halo_geo = env_int_halo("MRCNN_HALO_GEO", 1);     // 0: the round-3 geometries (one-row 3 x 130 regions, five staging pieces, pitch W + 2) — A/B and bit-identity tests
+static int& g_halo_lat = knob("halo_lat", "MRCNN_HALO_LAT", 1);     // grids under 3/4 of the chip even at 64 x 128: 64 x 64 tiles in the latency form (k_conv_halo_lat; bit-identical)
+static int& g_halo_rounds = knob("halo_rounds", "MRCNN_HALO_ROUNDS", 1);     // 64-row tiles where they shorten the last round of a 128 x 128 grid
+static int& g_halo_n64 = knob("halo_n64", "MRCNN_HALO_N64", 2);     // 64-column 3x3 layers on the halo kernel: 1 as 128 x 64 tiles, 2 also 256 x 64 where the level allows
+static int& g_halo_geo = knob("halo_geo", "MRCNN_HALO_GEO", 1);     // 0: the round-3 geometries (one-row 3 x 130 regions, five staging pieces, pitch W + 2) — A/B and bit-identity tests
 
 struct HaloGeo { int geo, ecols, pitch, img_skew, tiles_row, tiles_img, rows, maxpc, slots; bool ok; };
 
@@ -1063,15 +1062,6 @@ static void halo_launch(hipStream_t s, const HaloArgs& ha, int bm, int bn, int m
 
 // the filter shapes conv_halo_eligible can accept: only those are re-tiled at load (engine.hip: pack_conv_oihw)
 bool conv_halo_packable(int KH, int KW, int Cin, int Npad) { return KH == 3 && KW == 3 && Cin % 64 == 0 && (Npad % 128 == 0 || Npad == 64); }
-
-bool conv_halo_debug_set(const char* key, int value)
-{
-    if (std::string(key) == "halo_geo") { g_halo_geo = value; return true; }
-    if (std::string(key) == "halo_lat") { g_halo_lat = value; return true; }
-    if (std::string(key) == "halo_n64") { g_halo_n64 = value; return true; }
-    if (std::string(key) == "halo_rounds") { g_halo_rounds = value; return true; }
-    return false;
-}
 
 // A fused head needs 256-column tiles (the head's K groups are walked per wave column) and enough M tiles to occupy the chip
 // at ANY batch the layer may see — a property of the layer, not of the call: at least 32 M tiles per image.

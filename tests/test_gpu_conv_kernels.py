@@ -132,7 +132,7 @@ def test_wide_wave_variant_equals_the_eight_wave_tile_bitwise(shape, dtype):
     np.testing.assert_array_equal(y1, y0)
 
 
-DIRECT_DEFAULT = 3      # MRCNN_DIRECT of kernels_conv.hip
+DIRECT_DEFAULT = 3      # MRCNN_DIRECT of conv_dispatch.hip
 
 
 @pytest.mark.parametrize("dtype", ["f16", "f32", "f32s", "f32x3"])

@@ -375,6 +375,40 @@ def test_the_knobs_are_out_of_a_production_hosts_reach():
     assert int(rc) == 5 and "MRCNN_TEST_KNOBS=1" in msg and "conv_bneck" in msg        # MRCNN_ERR_UNSUPPORTED
 
 
+KNOB_KEYS = [
+    # csrc/conv_dispatch.hip
+    "conv_pp", "conv_pp_min_tiles", "conv_pp_min_kt", "conv_pp_dbg", "conv_pp_min_fill", "conv_pp_split", "conv_tn4", "conv_halo", "conv_direct",
+    "conv_min_blocks", "conv_min_blocks_split", "conv_scfuse", "mask_sel_wave", "conv_kchunk", "conv_ksplit", "conv_ksplit_below", "conv_tail",
+    "conv_stem", "conv_tail_dbg", "conv_bneck", "conv_bneck_stage", "conv_c3h",
+    # csrc/kernels_conv_halo.hip
+    "halo_geo", "halo_lat", "halo_n64", "halo_rounds",
+    # csrc/kernels_boxes.hip
+    "proposal_rank_sort", "nms_col_splits", "nms_class_fast",
+    # csrc/engine.hip, csrc/api_test.hip
+    "mask_fused", "conv2d_alias_res",
+]
+
+
+def test_every_knob_is_in_the_one_table():
+    """csrc/knobs.h: a knob is declared once, beside the code it steers, and mrcnn_debug_set looks its key up in the one table the
+    declarations fill.  Every key the tests and tools use is there — whichever translation unit declares it — and a key nobody declared
+    still fails with the 'unknown debug key' message.  In a child process of its own (armed; some overrides set, one of them empty =
+    the default), so that no switch of this test process moves.  No GPU needed: no knob has a read that would not need one, so the
+    values are pinned by the GPU tests that switch forms, not here."""
+    import subprocess
+    assert len(KNOB_KEYS) == 31 and len(set(KNOB_KEYS)) == 31
+    code = ("import importlib, sys; sys.path.insert(0, %r); L = importlib.import_module('mask-rcnn-coreml_amd._lib'); lib = L.lib()\n"
+            "for k in %r: print(k, lib.mrcnn_debug_set(k.encode(), 1))\n"
+            "print('no_such_knob', lib.mrcnn_debug_set(b'no_such_knob', 1), lib.mrcnn_last_error().decode())" % (ROOT, KNOB_KEYS))
+    env = dict(os.environ, MRCNN_TEST_KNOBS="1", MRCNN_C3H="2", MRCNN_HALO_GEO="", MRCNN_NMS_FAST="0")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.strip().splitlines()
+    assert [ln.split() for ln in lines[:-1]] == [[k, "0"] for k in KNOB_KEYS], r.stdout
+    name, rc, msg = lines[-1].split(" ", 2)
+    assert name == "no_such_knob" and int(rc) == 1 and msg == "unknown debug key 'no_such_knob'"        # MRCNN_ERR_INVALID
+
+
 def test_unletterbox_boxes_follow_the_norm_boxes_convention(pkg):
     """normalized coordinates are Matterport's norm_boxes (pixel = n*(size-1), far edge +1) — the convention
     of anchors.py and the mask paste — so a box covering exactly the letterboxed content maps back to the full
