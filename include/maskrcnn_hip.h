@@ -384,7 +384,9 @@ MRCNN_API int mrcnn_model_set_split_exponents(mrcnn_model* model, const int32_t*
  * in the maps' dtype.  row_flags (optional, n_rois int32): the removeZeros predicate the mask layer applies to a
  * pooled row (TimeDistributedClassifierLayer.swift:116-127: kept iff every element != 0) evaluated on the fp32
  * samples BEFORE the store rounds them — in fp16 a tiny non-zero sample would otherwise flush to zero and drop a
- * valid detection.  This is what the fused engine uses; the stand-alone MLCustomLayer entry takes CHW fp32. */
+ * valid detection.  This is what the fused engine uses; the stand-alone MLCustomLayer entry takes CHW fp32.
+ * channels % 4 == 0.  MRCNN_DEVICE: the kernel reads the maps and writes `out` where they lie with 16-byte vector accesses — maps and out
+ * 16-byte aligned (any allocation is; a slice must start on a multiple of 16 bytes). */
 MRCNN_API int mrcnn_roi_align_nhwc(const void* const maps[4], const int heights[4], const int widths[4], int channels,
                                    int dtype, const float* rois, int64_t roi_stride, int n_rois, int pool,
                                    double image_w, double image_h, int memspace, void* out, int32_t* row_flags);

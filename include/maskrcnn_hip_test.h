@@ -146,6 +146,17 @@ MRCNN_API int mrcnn_test_last_range_flag(int* flag);
  * row's probability at index 0 (the NaN as it is) and class 0's deltas: DetectionLayer drops such a row (score >= threshold is false). */
 MRCNN_API int mrcnn_classifier_rows(const float* logits, int64_t ld, const float* bbox, int nc, int64_t n, float* probs_out, float* cls6_out);
 
+/* The NHWC ROIAlign sampler as the fused engine launches it — a BATCH of images in one launch, every pyramid level with its own power-of-two
+ * multiplier — on caller (host) data; mrcnn_roi_align_nhwc reaches neither (one image, multipliers 1).  maps[l] (batch, H_l, W_l, channels) fp32,
+ * converted on the host to `dtype` (MRCNN_F32 | MRCNN_F16, round-to-nearest: pass fp16-representable values for MRCNN_F16); level_mul[l]: every
+ * sample of level l is multiplied by it in fp32 before the predicate and the store; rois (batch, n_rois, roi_stride) rows (y1,x1,y2,x2,...);
+ * out (batch, n_rois, pool, pool, channels) fp32 (MRCNN_F16: the fp16 values the kernel stores, widened); row_flags (optional, batch x n_rois
+ * int32): 1 iff every fp32 sample times multiplier of the row != 0.  channels % 4 == 0, roi_stride >= 4, n_rois >= 1, batch >= 1
+ * (tests/test_gpu_roi_align_nhwc.py). */
+MRCNN_API int mrcnn_test_roi_align_nhwc_batch(const float* const maps[4], const int heights[4], const int widths[4], int channels, int dtype,
+                                              const float level_mul[4], const float* rois, int64_t roi_stride, int n_rois, int batch, int pool,
+                                              double image_w, double image_h, float* out, int32_t* row_flags);
+
 /* Measurement (tools/jpeg_ab.py): the wall time of the two stages of the calling thread's last mrcnn_jpeg_decode_batch /
  * mrcnn_maskrcnn_predict_jpegs — host_ms: header parsing + the entropy threads; device_ms: from the upload of the coefficients to the end
  * of the second launch (decode_batch only, where the call waits for it; 0 after predict_jpegs, whose launches run ahead of the predict).

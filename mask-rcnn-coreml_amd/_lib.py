@@ -49,7 +49,7 @@ EXPORTED_SYMBOLS = [
 TEST_SYMBOLS = [
     "mrcnn_bench_conv", "mrcnn_bench_conv_dtype", "mrcnn_model_conv_profile_enable", "mrcnn_model_conv_profile_get",
     "mrcnn_model_conv_profile_shapes", "mrcnn_conv2d_nhwc", "mrcnn_debug_set", "mrcnn_bottleneck_nhwc", "mrcnn_bench_mfma_probe", "mrcnn_model_conv_profile_group", "mrcnn_bottleneck_first_nhwc", "mrcnn_bottleneck_stage_nhwc", "mrcnn_model_conv_profile_bytes",
-    "mrcnn_jpeg_last_stage_ms", "mrcnn_jpeg_coefficients", "mrcnn_test_last_range_flag", "mrcnn_classifier_rows",
+    "mrcnn_jpeg_last_stage_ms", "mrcnn_jpeg_coefficients", "mrcnn_test_last_range_flag", "mrcnn_classifier_rows", "mrcnn_test_roi_align_nhwc_batch",
 ]
 
 
@@ -234,6 +234,8 @@ def lib():
     L.mrcnn_dist_simulate_host.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp]
     L.mrcnn_roi_align_nhwc.argtypes = [C.POINTER(vp), ip, ip, C.c_int, C.c_int, vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double,
                                        C.c_int, vp, vp]
+    L.mrcnn_test_roi_align_nhwc_batch.argtypes = [C.POINTER(vp), ip, ip, C.c_int, C.c_int, f32p, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double,
+                                                  C.c_double, vp, vp]
     _lib = L
     return L
 

@@ -419,6 +419,47 @@ extern "C" int mrcnn_classifier_rows(const float* logits, int64_t ld, const floa
     });
 }
 
+// roi_align_forward (NHWC) on a BATCH of caller (host) data with per-level multipliers — the two things mrcnn_roi_align_nhwc cannot reach: the batch strides
+// of the maps, the ROIs, the output and the flags, and PyramidMaps::mul (tests/test_gpu_roi_align_nhwc.py).
+extern "C" int mrcnn_test_roi_align_nhwc_batch(const float* const maps[4], const int heights[4], const int widths[4], int channels, int dtype,
+                                               const float level_mul[4], const float* rois, int64_t roi_stride, int n_rois, int batch, int pool,
+                                               double image_w, double image_h, float* out, int32_t* row_flags)
+{
+    return guarded([&] {
+        require_gpu();
+        MRCNN_REQUIRE(maps && heights && widths && level_mul && rois && out, MRCNN_ERR_INVALID, "null argument");
+        MRCNN_REQUIRE(dtype == MRCNN_F32 || dtype == MRCNN_F16, MRCNN_ERR_UNSUPPORTED, "test_roi_align_nhwc_batch: dtype %d", dtype);
+        MRCNN_REQUIRE(n_rois >= 1 && batch >= 1 && pool >= 1 && channels >= 4 && channels % 4 == 0 && roi_stride >= 4, MRCNN_ERR_INVALID,
+                      "bad test_roi_align_nhwc_batch argument");
+        const bool f16 = dtype == MRCNN_F16;
+        auto* const upload_map = f16 ? upload_f16 : upload_f32;
+        DevBuf dm[4], dr, dout, dflags;
+        PyramidMaps pm;
+        for (int l = 0; l < 4; ++l) {
+            MRCNN_REQUIRE(maps[l] && heights[l] > 0 && widths[l] > 0, MRCNN_ERR_INVALID, "test_roi_align_nhwc_batch: level %d missing", l);
+            const size_t per = (size_t)heights[l] * widths[l] * channels;
+            upload_map(dm[l], maps[l], per * batch, 0);
+            pm.data[l] = dm[l].p; pm.H[l] = heights[l]; pm.W[l] = widths[l]; pm.sB[l] = (long)per; pm.mul[l] = level_mul[l];
+        }
+        const long rois_sB = (long)n_rois * roi_stride, row = (long)pool * pool * channels, out_sB = (long)n_rois * row;
+        upload_f32(dr, rois, (size_t)batch * rois_sB);
+        const size_t n_out = (size_t)batch * out_sB;
+        dout.alloc(n_out * (f16 ? 2 : 4));
+        HIP_CHECK(hipMemset(dout.p, 0xff, n_out * (f16 ? 2 : 4)));      // an element the kernel skips comes back as NaN
+        if (row_flags) {
+            dflags.alloc((size_t)batch * n_rois * 4);
+            HIP_CHECK(hipMemset(dflags.p, 0xff, (size_t)batch * n_rois * 4));
+        }
+        Stream st;
+        roi_align_forward(st.s, pm, channels, 1, dr.as<float>(), rois_sB, roi_stride, n_rois, batch, pool, image_w, image_h, dout.p, out_sB, row, dtype,
+                          row_flags ? dflags.as<int32_t>() : nullptr);
+        HIP_CHECK(hipStreamSynchronize(st.s));
+        if (f16) download_f16_as_f32(dout.p, n_out, out);
+        else HIP_CHECK(hipMemcpy(out, dout.p, n_out * 4, hipMemcpyDeviceToHost));
+        if (row_flags) HIP_CHECK(hipMemcpy(row_flags, dflags.p, (size_t)batch * n_rois * 4, hipMemcpyDeviceToHost));
+    });
+}
+
 extern "C" int mrcnn_model_conv_profile_enable(mrcnn_model* model, int on)
 {
     return guarded([&] {

@@ -95,7 +95,8 @@ template <> __device__ __forceinline__ void st4<_Float16>(_Float16* p, float4 v)
 // ceil, the range test) and four run-time integer divisions per element: ~150 VALU instructions around four loads, 125 us for 200 MB
 // of fp16 output.  Now the (at most 256) points of a pass are sampled ONCE, one per thread, into an LDS table (corner offsets, weights),
 // and the element loop reads its point's entry (wave-uniform address when C >= 256: a broadcast) and indexes by shift / mask.
-// The arithmetic per sample and per element is unchanged: the same bits (tests/test_gpu_layers.py against the oracle).
+// The arithmetic per sample and per element is unchanged: the same bits (tests/test_gpu_roi_align_nhwc.py against the oracle: both item widths, the shift and
+// the divide index, one to four passes, multipliers, flags, batch strides).
 template <typename T>
 __global__ __launch_bounds__(256) void k_roi_align_nhwc(PyramidMaps maps, int C, const float* __restrict__ rois,
                                                         long rois_sB, long roi_stride, int P, double ratio,

@@ -117,6 +117,36 @@ def test_calibrated_engine_keeps_every_staged_parity(pkg, orc, small_model):
         m2.split_exponents = bad
 
 
+def test_pyramid_levels_at_four_different_exponents_keep_the_roi_align_parity(pkg, orc, small_model):
+    """The ROIAlign sampler's per-level multiplier (PyramidMaps::mul = 2^(output's exponent - level's exponent)) with four DIFFERENT values, set by
+    hand — a calibration gives the four levels different exponents only if the checkpoint happens to.  P2..P5 (the groups `g_P[l]` of engine.hip,
+    named after their taps) at 3, 1, -2, 2, every other group at 0: `pooled` and `pooled_mask` stay bit-exact against the oracle on the GPU's own
+    taps, for every image of a batch, and every other stage keeps its parity."""
+    from oracle.network import load_oracle_model
+    d, cfg = small_model
+    om = load_oracle_model(d)
+    B = 2
+    m = _models().load_maskrcnn(d, max_batch=B, compute_dtype="f32x3")
+    images = rand_images(B, cfg.image_height, cfg.image_width, seed=1)
+    names = [g["name"] for g in m.split_report()]
+    level_groups = [names.index(f"P{l + 2}") for l in range(4)]
+    assert len(set(level_groups)) == 4 and all(names.count(f"P{l + 2}") == 1 for l in range(4))
+    assert not any(m.split_report()[i]["fixed"] for i in level_groups)
+    exps = np.zeros(len(names), np.int32)
+    exps[level_groups] = [3, 1, -2, 2]
+    m.split_exponents = exps
+    det, mask = m.predict(images)
+    back = m.split_exponents
+    np.testing.assert_array_equal(back, exps)                               # no range recovery moved them
+    assert m.get_int("range_recoveries") == 0
+    assert len({int(back[i]) for i in level_groups}) == 4                  # four distinct multipliers reached the sampler
+    trunk = om.trunk(images)
+    for b in range(B):
+        d_b, m_b = _check_stages(pkg, orc, om, m, cfg, images, b, True, trunk)
+        np.testing.assert_array_equal(det[b], d_b)
+        np.testing.assert_array_equal(mask[b].reshape(cfg.max_detections, -1), m_b)
+
+
 def test_calibration_is_refused_where_it_means_nothing(small_model):
     d, cfg = small_model
     images = rand_images(1, cfg.image_height, cfg.image_width, seed=1)
