@@ -217,7 +217,7 @@ extern "C" int mrcnn_conv2d_nhwc(const float* in, int batch, int h, int w, int c
         d.dtype = adt; d.wdtype = wdt; d.out_f32 = 0;      // fp16 mode stores fp16 (the path the engine's layers take), widened below
         if (residual) set_dense_residual(d, dres.p);
         // mrcnn_debug_set("conv2d_alias_res", 1): the output is written IN PLACE over the residual, the way the engine runs every
-        // bottleneck block's branch2c (engine.hip: `to = sc`).  The contract every epilogue must keep (ConvDesc::res in kernels.h):
+        // bottleneck block's branch2c (engine_plan.hip: `to = sc`).  The contract every epilogue must keep (ConvDesc::res in kernels.h):
         // a residual element is loaded by the thread that stores the output element at the same address, before that store.
         if (residual && g_conv2d_alias_res) d.out = dres.p;
         Stream st;

@@ -1,4 +1,5 @@
-// engine.h — model artefacts (.mrcw), weight packing and the static execution plans.
+// engine.h — model artefacts (.mrcw), weight packing and the static execution plans: the one header of the engine that the api_*.hip
+// files and dist.hip see (what only the engine's own files share is in engine_internal.h).
 #pragma once
 #include <functional>
 #include <map>
@@ -294,12 +295,6 @@ struct Model {
     void drop_graphs();
     void read_tensor(const std::string& name, int image, float* dst, int64_t cap, int64_t* count);
 };
-
-// Helpers shared with api.hip
-PackedConv pack_conv_oihw(const MrcwFile& f, const std::string& conv, const std::string& bn, int dtype);
-void run_conv_dense(hipStream_t s, const PackedConv& pc, const void* in, int B, int H, int W, void* out, int stride,
-                    int pad, int act, const void* res = nullptr, int out_f32 = 0, const ScaledOp* sop = nullptr);
-void init_scaled_op(ScaledOp& op, const PackedConv* pc, int g_in, int g_out);      // allocates the copies = the base scale / shift
 
 }  // namespace mrcnn
 

@@ -1060,7 +1060,7 @@ static void halo_launch(hipStream_t s, const HaloArgs& ha, int bm, int bn, int m
     else halo_launch_pc<PARTS, 1, false, 1>(s, ha, maxpc, grid);
 }
 
-// the filter shapes conv_halo_eligible can accept: only those are re-tiled at load (engine.hip: pack_conv_oihw)
+// the filter shapes conv_halo_eligible can accept: only those are re-tiled at load (engine_weights.hip: pack_conv_oihw)
 bool conv_halo_packable(int KH, int KW, int Cin, int Npad) { return KH == 3 && KW == 3 && Cin % 64 == 0 && (Npad % 128 == 0 || Npad == 64); }
 
 // A fused head needs 256-column tiles (the head's K groups are walked per wave column) and enough M tiles to occupy the chip

@@ -50,7 +50,7 @@ def _bn_of(conv: str):
 
 
 def fold_bn_f32(tensors, conv: str, eps: float = BN_EPS):
-    """(scale, shift) of conv(+bias)(+BN) as the engine folds them (csrc/engine.hip fold_bn): float32 arithmetic,
+    """(scale, shift) of conv(+bias)(+BN) as the engine folds them (csrc/engine_weights.hip fold_bn): float32 arithmetic,
     y = acc * scale + shift with scale = gamma / sqrt(var + eps), shift = (bias - mean) * scale + beta."""
     f32 = lambda k: np.asarray(tensors[k], dtype=np.float32)
     bias = f32(f"{conv}/bias")
@@ -193,7 +193,7 @@ class OracleMaskRCNN:
     # scale / shift the engine folds (fold_bn_f32), means are the config's float32 values.  What remains between a stage's output
     # and an engine's tap of it is then the engine's convolution arithmetic (summation order, operand split) and its stores.
     #
-    # round_f16=True: every tensor the fp16 compute mode STORES is rounded to fp16 where the engine stores it (csrc/engine.hip):
+    # round_f16=True: every tensor the fp16 compute mode STORES is rounded to fp16 where the engine stores it (csrc/engine_plan.hip, csrc/engine_heads.hip):
     #   stem: the mean-subtracted input (the fp16 staging tensor), conv1's output (max-pooled after rounding: max commutes with it);
     #   each bottleneck: branch2a's and branch2b's outputs, the first block's shortcut (branch1) output, the block output;
     #   FPN: the lateral sums L5..L2 (the upsampled level above is added to the fp32 sum, then stored), P2..P5;

@@ -198,7 +198,7 @@ def test_convert_command_end_to_end(pkg, weights_mod, anchors_mod, conv, hdf5, t
 
 def test_stored_split_exponents_ride_in_the_artefact_metadata(weights_mod, conv, tmp_path):
     """`convert --calibrate` (round 5): the exponent vector of the scale-aware split goes into MaskRCNN.mrcw as `split_exp.<group>` integer
-    metadata — what mrcnn_model_load applies (engine.hip) — leaving every tensor and every other key untouched; storing again replaces the old
+    metadata — what mrcnn_model_load applies (engine_plan.hip) — leaving every tensor and every other key untouched; storing again replaces the old
     vector instead of accumulating keys; the image loader of the flag takes uint8 (N,H,W,3) .npy files and refuses anything else."""
     d = tmp_path / "products"
     d.mkdir()

@@ -555,7 +555,7 @@ ALIAS_SHAPES = [  # B, H, W, Cin, Cout, k — one per epilogue form a residual l
 @pytest.mark.parametrize("dtype", ["f32", "f16", "f32s", "f32x3"])
 @pytest.mark.parametrize("shape", ALIAS_SHAPES)
 def test_every_epilogue_is_safe_in_place_over_its_residual(shape, dtype):
-    """The engine writes every bottleneck block's output IN PLACE over its shortcut (engine.hip: `to = sc`, res == out).  That
+    """The engine writes every bottleneck block's output IN PLACE over its shortcut (engine_plan.hip: `to = sc`, res == out).  That
     rests on a contract of every epilogue form — a residual element is loaded by the thread that stores the output element at the
     same address, before the store (ConvDesc::res) — which nothing pinned (ADVICE r3): here each form runs with the output aliased
     onto the residual (mrcnn_debug_set("conv2d_alias_res", 1)) and must give the bits of the separate-buffer run, for every

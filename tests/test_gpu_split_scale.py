@@ -68,6 +68,22 @@ def _models():
     return importlib.import_module("mask-rcnn-coreml_amd.models")
 
 
+def test_split_groups_keep_their_names_and_order(small_model):
+    """The order of the split groups is visible: mrcnn_model_get_split_exponents / _set_split_exponents address groups by index, a sharded
+    job sends the vector between ranks, and convert --calibrate stores exponents under the names.  tests/golden/split_groups_resnet50.txt is the
+    list ("name fixed" per line, in index order) of the ResNet-50 plan as read from the library BEFORE the plan builder was split out of
+    engine.hip; the names depend on the architecture only, not on the input size.  A load only: no predict."""
+    d, _ = small_model
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "split_groups_resnet50.txt")
+    want = open(golden).read().splitlines()
+    assert len(want) == 57
+    for mode in ("f32x3", "f16"):                                         # (the groups exist in every mode; only the split modes move their exponents)
+        m = _models().load_maskrcnn(d, max_batch=1, compute_dtype=mode)
+        got = [f"{g['name']} {int(g['fixed'])}" for g in m.split_report()]
+        assert got == want, mode
+        assert len(m.split_exponents) == len(want)
+
+
 def test_calibrated_engine_keeps_every_staged_parity(pkg, orc, small_model):
     """After calibration the tensors in HBM are scaled — taps hand out true values, the ROIAlign sampler brings pyramid levels
     at different exponents to its output's, the fused heads undo theirs: every stage still equals the oracle on the GPU's own
@@ -119,7 +135,7 @@ def test_calibrated_engine_keeps_every_staged_parity(pkg, orc, small_model):
 
 def test_pyramid_levels_at_four_different_exponents_keep_the_roi_align_parity(pkg, orc, small_model):
     """The ROIAlign sampler's per-level multiplier (PyramidMaps::mul = 2^(output's exponent - level's exponent)) with four DIFFERENT values, set by
-    hand — a calibration gives the four levels different exponents only if the checkpoint happens to.  P2..P5 (the groups `g_P[l]` of engine.hip,
+    hand — a calibration gives the four levels different exponents only if the checkpoint happens to.  P2..P5 (the groups `g_P[l]` of engine_plan.hip,
     named after their taps) at 3, 1, -2, 2, every other group at 0: `pooled` and `pooled_mask` stay bit-exact against the oracle on the GPU's own
     taps, for every image of a batch, and every other stage keeps its parity."""
     from oracle.network import load_oracle_model
