@@ -617,6 +617,76 @@ MRCNN_API int mrcnn_instance_map_source(const float* detections, const float* ma
 MRCNN_API int mrcnn_render_detections_source(const mrcnn_image* images, const float* detections, const float* masks, int batch, int rows,
                                              int mask_size, int model_h, int model_w, float threshold, float min_score, int alpha, int stroke,
                                              int memspace, float* detections_src, uint8_t* out_rgb, const int64_t* out_offsets);
+
+/* Tiled prediction: large images (aerial scenes, slides, 4K/8K frames) predicted as overlapping windows at native resolution, the
+ * duplicates of the overlaps removed on the GPU.  Letterboxing such an image into the model's input shrinks its objects below the
+ * RPN's smallest anchors; a window is letterboxed with its OWN geometry, exactly as an image of the window's size would be.
+ *
+ * mrcnn_tile_plan — host only, no GPU.  Per axis with length L, tile T and overlap O (0 <= O < T): L <= T gives the one window
+ *   [0, L); otherwise the stride is s = T - O, there are ceil((L - T) / s) + 1 windows and window k starts at min(k*s, L - T): every
+ *   window is exactly T long, the last one is shifted inward instead of being cut.  Tiles are listed row-major (y outer, x inner) with
+ *   .image = image.  *count is always the number needed; out = NULL (capacity 0) is the size query; a capacity that is too small, a bad
+ *   overlap or a side outside 1..32767 -> MRCNN_ERR_SHAPE.
+ *
+ * mrcnn_maskrcnn_predict_tiles — record t (detections (n_tiles, maxDetections, 6), masks (n_tiles, maxDetections, S, S)) equals
+ *   mrcnn_maskrcnn_predict_images on a contiguous copy of window t alone, bit for bit, in every compute mode.  Any window size is
+ *   allowed.  n_tiles may exceed max_batch: the call runs ceil(n_tiles / max_batch) predicts of up to max_batch tiles each (range
+ *   recovery of the split modes works per predict).  Every source image is copied to the device ONCE (MRCNN_DEVICE: read in place);
+ *   the windows are never materialised on either side — the pre-processing addresses a window through its image's row pitch.
+ *   memspace holds for the rgb pointers and both outputs; the two tables are host memory.  Synchronous; never replayed from a captured
+ *   graph.  Errors (the message names the tile): null pointer -> MRCNN_ERR_INVALID; n_tiles < 1, tile.image outside 0..n_images-1, an
+ *   empty window or one not inside its image -> MRCNN_ERR_SHAPE.
+ *
+ * mrcnn_merge_tiles (device) / mrcnn_merge_tiles_host (the definition: sequential plain C++, no GPU) — the records of predict_tiles
+ *   in the frame of the images the windows were cut from, cross-tile duplicates dropped.  The device entry equals the host entry bit
+ *   for bit.  Candidate k = t*rows + i is row i of tile t:
+ *     box      its pixel box (y1, x1, y2, x2) in the tile (what mrcnn_paste_masks_source derives for an image of the tile's size)
+ *              plus (y0, x0, y0, x0) of the tile;
+ *     plane    P_k, h_img x w_img: zero outside the window, inside it the plane mrcnn_paste_masks_source pastes for the tile alone;
+ *     row      (y1 / max(h-1,1), x1 / max(w-1,1), (y2-1) / max(h-1,1), (x2-1) / max(w-1,1), class, score) of the full-frame box,
+ *              each quotient computed in double and rounded to float once.  For sides <= 32767 the rounding error is at most
+ *              32767 * 2^-24 (0.002 pixel), so denorm_boxes of the row returns the full-frame pixel box again: handed these rows
+ *              (as `detections`, with heights/widths = model_h/model_w = the image's size, i.e. an identity letterbox, one image
+ *              at a time) mrcnn_paste_masks_source and the renderers give P_k.
+ *   A candidate is ELIGIBLE if its score is > 0 and its box is not empty.  Per image the eligible candidates are walked by score
+ *   descending, ties by k ascending; candidate c is DROPPED if an earlier KEPT candidate q of the same image has the same class id,
+ *   tile(q) != tile(c) and m(q, c) >= match_threshold, where inter = |P_q & P_c| (an exact integer), a = the planes' areas and
+ *     MRCNN_MATCH_IOU: m = inter / (a_q + a_c - inter)        MRCNN_MATCH_IOS: m = inter / min(a_q, a_c)
+ *   as IEEE double divisions of those integers, 0/0 = 0.  A dropped candidate suppresses nothing; rows of one tile are never compared
+ *   (the detection layer's own NMS ran there).  Candidates are only dropped, masks are never united: an object is recovered whole
+ *   only if some window contains it whole, so the overlap should be at least the largest object of interest; IoS is the metric that
+ *   removes a cut copy of an object in favour of its whole copy.
+ *   Outputs, per image the first max_out kept candidates in that order:
+ *     detections_src (n_images, max_out, 6)   the rows above, zero-padded
+ *     source (n_images, max_out)              the candidate index k, -1 for padding
+ *     n_kept (n_images)                       the number kept BEFORE the cap (n_kept > max_out: the output was truncated)
+ *     counts / run_offsets (n_images*max_out + 1) / areas / bboxes_xywh   the kept planes as COCO RLE in mrcnn_masks_rle_source's
+ *                                             layout and capacity protocol (padding = the single run [h*w]; capacity 0 with counts
+ *                                             NULL = the size query, everything but counts is written; too small -> MRCNN_ERR_SHAPE
+ *                                             with the size needed in the message); areas / bboxes_xywh may be NULL.
+ *   memspace holds for detections, masks and every output; the tile table and the sizes are host arrays.  match_threshold > 0.
+ *   An image may have at most MRCNN_TILES_MAX_CANDIDATES candidates (its tiles x rows: 81 tiles of 100 rows), beyond ->
+ *   MRCNN_ERR_SHAPE.  Argument errors as predict_tiles'; unknown metric, match_threshold <= 0 -> MRCNN_ERR_INVALID; rows, n_images or
+ *   max_out < 1 -> MRCNN_ERR_SHAPE.  Every argument error is answered before a device is looked for.
+ * examples/maskrcnn_predict_tiled.c is the whole flow as a C99 host. */
+typedef struct { int32_t image, y0, x0, height, width; } mrcnn_tile;   /* a window of images[image] */
+enum { MRCNN_MATCH_IOU = 0, MRCNN_MATCH_IOS = 1 };
+#define MRCNN_TILES_MAX_CANDIDATES 8192
+MRCNN_API int mrcnn_tile_plan(int height, int width, int tile_h, int tile_w, int overlap_y, int overlap_x, int image, mrcnn_tile* out,
+                              int capacity, int* count);
+MRCNN_API int mrcnn_maskrcnn_predict_tiles(mrcnn_model* model, const mrcnn_image* images, int n_images, const mrcnn_tile* tiles,
+                                           int n_tiles, int memspace, float* detections, float* masks);
+MRCNN_API int mrcnn_merge_tiles(const float* detections, const float* masks, const mrcnn_tile* tiles, int n_tiles, int rows, int mask_size,
+                                const int32_t* heights, const int32_t* widths, int n_images, int model_h, int model_w, float threshold,
+                                int metric, double match_threshold, int max_out, int memspace, float* detections_src, int32_t* source,
+                                int32_t* n_kept, uint32_t* counts, int64_t capacity, int64_t* run_offsets, uint32_t* areas,
+                                int32_t* bboxes_xywh);
+MRCNN_API int mrcnn_merge_tiles_host(const float* detections, const float* masks, const mrcnn_tile* tiles, int n_tiles, int rows,
+                                     int mask_size, const int32_t* heights, const int32_t* widths, int n_images, int model_h, int model_w,
+                                     float threshold, int metric, double match_threshold, int max_out, float* detections_src,
+                                     int32_t* source, int32_t* n_kept, uint32_t* counts, int64_t capacity, int64_t* run_offsets,
+                                     uint32_t* areas, int32_t* bboxes_xywh);
+
 /* Host only, no GPU: COCO's compressed string of one RLE (pycocotools rleToString / rleFrString), not NUL-terminated.  *length / *n is
  * always the size needed; with out / counts = NULL the call only measures, a buffer that is too small gives MRCNN_ERR_SHAPE. */
 MRCNN_API int mrcnn_rle_to_string(const uint32_t* counts, int64_t n, char* out, int64_t capacity, int64_t* length);

@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = [
     "mrcnn_jpeg_decode_batch_on", "mrcnn_maskrcnn_predict_jpegs_on",
     "mrcnn_jpeg_encode_host", "mrcnn_jpeg_encode_batch",
     "mrcnn_png_encode_host", "mrcnn_png_encode_batch",
+    "mrcnn_tile_plan", "mrcnn_maskrcnn_predict_tiles", "mrcnn_merge_tiles", "mrcnn_merge_tiles_host",
 ]
 # declared in include/maskrcnn_hip_test.h (test / measurement entry points of the same library)
 TEST_SYMBOLS = [
@@ -97,6 +98,14 @@ class Jpeg(C.Structure):            # mrcnn_jpeg
 
 class Image(C.Structure):           # mrcnn_image
     _fields_ = [("rgb", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32)]
+
+
+class Tile(C.Structure):            # mrcnn_tile
+    _fields_ = [("image", C.c_int32), ("y0", C.c_int32), ("x0", C.c_int32), ("height", C.c_int32), ("width", C.c_int32)]
+
+
+MATCH_IOU, MATCH_IOS = 0, 1
+TILES_MAX_CANDIDATES = 8192
 
 
 class PngSource(C.Structure):       # mrcnn_png_source
@@ -157,6 +166,11 @@ def lib():
     L.mrcnn_instance_map_source.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp, vp, vp]
     L.mrcnn_render_detections_source.argtypes = [C.POINTER(Image), vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
                                                  C.c_int, vp, vp, vp]
+    L.mrcnn_tile_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Tile), C.c_int, C.POINTER(C.c_int)]
+    L.mrcnn_maskrcnn_predict_tiles.argtypes = [vp, C.POINTER(Image), C.c_int, C.POINTER(Tile), C.c_int, C.c_int, vp, vp]
+    _merge = [vp, vp, C.POINTER(Tile), C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_double, C.c_int]
+    L.mrcnn_merge_tiles.argtypes = _merge + [C.c_int, vp, vp, vp, vp, C.c_int64, vp, vp, vp]
+    L.mrcnn_merge_tiles_host.argtypes = _merge + [vp, vp, vp, vp, C.c_int64, vp, vp, vp]
     L.mrcnn_rle_to_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_from_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_iou.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int64]

@@ -34,7 +34,7 @@ static std::vector<ImageGeom> image_geometry(const int32_t* heights, const int32
     std::vector<ImageGeom> geom((size_t)batch);
     for (int b = 0; b < batch; ++b) {
         ImageGeom& g = geom[(size_t)b];
-        g.h = heights[b]; g.w = widths[b]; g.offset = 0;
+        g.h = heights[b]; g.w = widths[b]; g.offset = 0; g.pitch = g.w;
         MRCNN_REQUIRE(g.h >= 1 && g.h <= 32767 && g.w >= 1 && g.w <= 32767, MRCNN_ERR_SHAPE,
                       "image %d of the batch is %dx%d: height and width must lie in 1..32767", b, g.h, g.w);
         MRCNN_REQUIRE(mrcnn_letterbox_geometry(g.h, g.w, model_h, model_w, &g.nh, &g.nw, &g.py, &g.px) == MRCNN_OK, MRCNN_ERR_INVALID,

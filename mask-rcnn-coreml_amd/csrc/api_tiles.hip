@@ -1,0 +1,179 @@
+// api_tiles.hip — the C ABI of include/maskrcnn_hip.h, tiled prediction: the planner and the host merge (tiles_host.cpp behind them),
+// the predict over windows (Model::predict_tiles) and the device merge (kernels_tiles.hip).  Every argument error is answered before a
+// device is looked for.
+#include "api_util.h"
+#include "kernels_tiles.h"
+#include "tiles_host.h"
+
+using namespace mrcnn;
+
+extern "C" int mrcnn_tile_plan(int height, int width, int tile_h, int tile_w, int overlap_y, int overlap_x, int image, mrcnn_tile* out,
+                               int capacity, int* count)
+{
+    return guarded([&] {
+        std::string err;
+        const int st = tiles::plan(height, width, tile_h, tile_w, overlap_y, overlap_x, image, out, capacity, count, &err);
+        if (st != MRCNN_OK) fail(st, "%s", err.c_str());
+    });
+}
+
+extern "C" int mrcnn_maskrcnn_predict_tiles(mrcnn_model* model, const mrcnn_image* images, int n_images, const mrcnn_tile* tiles, int n_tiles,
+                                            int memspace, float* detections, float* masks)
+{
+    return guarded([&] {
+        MRCNN_REQUIRE(model && images && tiles && detections && masks, MRCNN_ERR_INVALID, "predict_tiles: null argument");
+        MRCNN_REQUIRE(n_tiles >= 1, MRCNN_ERR_SHAPE, "predict_tiles: n_tiles %d < 1", n_tiles);
+        MRCNN_REQUIRE(n_images >= 1, MRCNN_ERR_SHAPE, "predict_tiles: n_images %d < 1", n_images);
+        std::vector<int32_t> hs((size_t)n_images), ws((size_t)n_images);
+        for (int b = 0; b < n_images; ++b) {
+            MRCNN_REQUIRE(images[b].rgb, MRCNN_ERR_INVALID, "predict_tiles: image %d has a null rgb pointer", b);
+            hs[(size_t)b] = images[b].height; ws[(size_t)b] = images[b].width;
+        }
+        std::string err;
+        const int st = tiles::check_tiles(tiles, n_tiles, hs.data(), ws.data(), n_images, "predict_tiles", &err);
+        if (st != MRCNN_OK) fail(st, "%s", err.c_str());
+        model->m.predict_tiles(images, n_images, tiles, n_tiles, memspace, detections, masks);
+    });
+}
+
+static tiles::MergeArgs merge_args(const float* detections, const float* masks, const mrcnn_tile* tiles, int n_tiles, int rows, int mask_size,
+                                   const int32_t* heights, const int32_t* widths, int n_images, int model_h, int model_w, float threshold, int metric,
+                                   double match_threshold, int max_out, float* detections_src, int32_t* source, int32_t* n_kept, uint32_t* counts,
+                                   int64_t capacity, int64_t* run_offsets, uint32_t* areas, int32_t* bboxes_xywh)
+{
+    return tiles::MergeArgs{detections, masks, tiles, n_tiles, rows, mask_size, heights, widths, n_images, model_h, model_w, threshold, metric,
+                            match_threshold, max_out, detections_src, source, n_kept, counts, capacity, run_offsets, areas, bboxes_xywh};
+}
+
+extern "C" int mrcnn_merge_tiles_host(const float* detections, const float* masks, const mrcnn_tile* tiles, int n_tiles, int rows, int mask_size,
+                                      const int32_t* heights, const int32_t* widths, int n_images, int model_h, int model_w, float threshold,
+                                      int metric, double match_threshold, int max_out, float* detections_src, int32_t* source, int32_t* n_kept,
+                                      uint32_t* counts, int64_t capacity, int64_t* run_offsets, uint32_t* areas, int32_t* bboxes_xywh)
+{
+    return guarded([&] {
+        std::string err;
+        const int st = tiles::merge_host(merge_args(detections, masks, tiles, n_tiles, rows, mask_size, heights, widths, n_images, model_h, model_w,
+                                                    threshold, metric, match_threshold, max_out, detections_src, source, n_kept, counts, capacity,
+                                                    run_offsets, areas, bboxes_xywh), &err);
+        if (st != MRCNN_OK) fail(st, "%s", err.c_str());
+    });
+}
+
+extern "C" int mrcnn_merge_tiles(const float* detections, const float* masks, const mrcnn_tile* tiles, int n_tiles, int rows, int mask_size,
+                                 const int32_t* heights, const int32_t* widths, int n_images, int model_h, int model_w, float threshold, int metric,
+                                 double match_threshold, int max_out, int memspace, float* detections_src, int32_t* source, int32_t* n_kept,
+                                 uint32_t* counts, int64_t capacity, int64_t* run_offsets, uint32_t* areas, int32_t* bboxes_xywh)
+{
+    return guarded([&] {
+        std::string err;
+        const int st = tiles::check_merge(merge_args(detections, masks, tiles, n_tiles, rows, mask_size, heights, widths, n_images, model_h, model_w,
+                                                     threshold, metric, match_threshold, max_out, detections_src, source, n_kept, counts, capacity,
+                                                     run_offsets, areas, bboxes_xywh), "merge_tiles", &err);
+        if (st != MRCNN_OK) fail(st, "%s", err.c_str());
+        require_gpu();
+        const bool dev = memspace == MRCNN_DEVICE;
+        const size_t n = (size_t)n_tiles * rows, slots = (size_t)n_images * max_out;
+        // the host tables: per tile its own letterbox geometry (the box map), its image's size (the RLE kernels) and its place; per image its tiles
+        std::vector<ImageGeom> tab((size_t)2 * n_tiles);
+        std::vector<TileGeom> tg((size_t)n_tiles);
+        std::vector<int> toff((size_t)n_images + 1, 0), tlist((size_t)n_tiles);
+        std::vector<int2> imgsz((size_t)n_images);
+        for (int b = 0; b < n_images; ++b) imgsz[(size_t)b] = make_int2(heights[b], widths[b]);
+        for (int t = 0; t < n_tiles; ++t) {
+            const mrcnn_tile& w = tiles[t];
+            ImageGeom& g = tab[(size_t)t];
+            g = ImageGeom{};
+            g.h = w.height; g.w = w.width; g.pitch = w.width;
+            MRCNN_REQUIRE(mrcnn_letterbox_geometry(g.h, g.w, model_h, model_w, &g.nh, &g.nw, &g.py, &g.px) == MRCNN_OK, MRCNN_ERR_INVALID,
+                          "merge_tiles: tile %d: bad letterbox geometry", t);
+            ImageGeom& f = tab[(size_t)n_tiles + t];
+            f = ImageGeom{};
+            f.h = heights[w.image]; f.w = widths[w.image]; f.pitch = f.w;
+            tg[(size_t)t] = TileGeom{w.image, w.y0, w.x0, f.h, f.w};
+            ++toff[(size_t)w.image + 1];
+        }
+        int most = 0;
+        for (int b = 0; b < n_images; ++b) { most = std::max(most, toff[(size_t)b + 1] * rows); toff[(size_t)b + 1] += toff[(size_t)b]; }
+        {
+            std::vector<int> fill(toff.begin(), toff.end() - 1);
+            for (int t = 0; t < n_tiles; ++t) tlist[(size_t)fill[(size_t)tiles[t].image]++] = t;           // ascending t within an image
+        }
+        Stream st_;
+        hipStream_t s = st_.s;
+        DevBuf td, tm, tt, tw, tc, toc;
+        Drain drain{s};                                          // (declared behind the buffers: the stream drains before they are freed)
+        TilesMerge m{};
+        m.n_tiles = n_tiles; m.rows = rows; m.S = mask_size; m.n_images = n_images; m.max_out = max_out; m.W = (most + 63) / 64;
+        m.thr = threshold; m.metric = metric; m.match_thr = match_threshold;
+        m.det = stage_rows(detections, memspace, (long)n, 6, 6, td);
+        m.masks = stage_rows(masks, memspace, (long)n, (long)mask_size * mask_size, (long)mask_size * mask_size, tm);
+        // one allocation for the tables, one for the scratch
+        size_t o = 0;
+        auto take = [&](size_t bytes) { const size_t at = o; o = up(o + bytes, 16); return at; };
+        const size_t o_tab = take(tab.size() * sizeof(ImageGeom)), o_tg = take(tg.size() * sizeof(TileGeom)), o_toff = take(toff.size() * sizeof(int)),
+                     o_tl = take(tlist.size() * sizeof(int)), o_sz = take(imgsz.size() * sizeof(int2));
+        tt.alloc(o);
+        HIP_CHECK(hipMemcpyAsync(tt.as<char>() + o_tab, tab.data(), tab.size() * sizeof(ImageGeom), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(tt.as<char>() + o_tg, tg.data(), tg.size() * sizeof(TileGeom), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(tt.as<char>() + o_toff, toff.data(), toff.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(tt.as<char>() + o_tl, tlist.data(), tlist.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(tt.as<char>() + o_sz, imgsz.data(), imgsz.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipStreamSynchronize(s));                      // (the vectors above are pageable: the copies have read them now)
+        const ImageGeom* tab_tile = reinterpret_cast<const ImageGeom*>(tt.as<char>() + o_tab);
+        m.tab_full = tab_tile + n_tiles;
+        m.tiles = reinterpret_cast<const TileGeom*>(tt.as<char>() + o_tg);
+        m.toff = reinterpret_cast<const int*>(tt.as<char>() + o_toff);
+        m.tlist = reinterpret_cast<const int*>(tt.as<char>() + o_tl);
+        m.imgsz = reinterpret_cast<const int2*>(tt.as<char>() + o_sz);
+        o = 0;
+        const size_t w_box = take(n * sizeof(int4)), w_rows = take(n * 6 * sizeof(float)), w_tile = take(n * 6 * sizeof(float)),
+                     w_seg = take(n * RLE_SEGS * sizeof(RleSeg)), w_nr = take(n * sizeof(uint32_t)), w_ro = take((n + 1) * sizeof(long long)),
+                     w_ar = take(n * sizeof(uint32_t)), w_bb = take(n * 4 * sizeof(int32_t)), w_ord = take(n * sizeof(int)), w_pos = take(n * sizeof(int)),
+                     w_ne = take((size_t)n_images * sizeof(int)), w_sup = take(n * (size_t)m.W * sizeof(unsigned long long)),
+                     w_onr = take(slots * sizeof(uint32_t));
+        // the outputs: the caller's device arrays, or a staging copy of each
+        const size_t w_ds = take(slots * 6 * sizeof(float)), w_src = take(slots * sizeof(int32_t)), w_nk = take((size_t)n_images * sizeof(int32_t)),
+                     w_oro = take((slots + 1) * sizeof(long long)), w_oar = take(slots * sizeof(uint32_t)), w_obb = take(slots * 4 * sizeof(int32_t));
+        tw.alloc(o);
+        char* const wb = tw.as<char>();
+        m.boxes = reinterpret_cast<int4*>(wb + w_box); m.rows_src = reinterpret_cast<float*>(wb + w_rows);
+        m.segs = reinterpret_cast<RleSeg*>(wb + w_seg); m.nruns = reinterpret_cast<uint32_t*>(wb + w_nr); m.ro = reinterpret_cast<long long*>(wb + w_ro);
+        m.areas = reinterpret_cast<uint32_t*>(wb + w_ar); m.bboxes = reinterpret_cast<int32_t*>(wb + w_bb);
+        m.order = reinterpret_cast<int*>(wb + w_ord); m.pos = reinterpret_cast<int*>(wb + w_pos); m.nelig = reinterpret_cast<int*>(wb + w_ne);
+        m.supp = reinterpret_cast<unsigned long long*>(wb + w_sup); m.out_nruns = reinterpret_cast<uint32_t*>(wb + w_onr);
+        m.det_src = dev ? detections_src : reinterpret_cast<float*>(wb + w_ds);
+        m.source = dev ? source : reinterpret_cast<int32_t*>(wb + w_src);
+        m.n_kept = dev ? n_kept : reinterpret_cast<int32_t*>(wb + w_nk);
+        m.out_ro = dev ? reinterpret_cast<long long*>(run_offsets) : reinterpret_cast<long long*>(wb + w_oro);
+        m.out_areas = dev && areas ? areas : reinterpret_cast<uint32_t*>(wb + w_oar);
+        m.out_bboxes = dev && bboxes_xywh ? bboxes_xywh : reinterpret_cast<int32_t*>(wb + w_obb);
+        // 1. the boxes, 2. the candidates' runs counted
+        unletterbox_boxes_forward(s, m.det, tab_tile, n_tiles, rows, model_h, model_w, reinterpret_cast<float*>(wb + w_tile), m.boxes);
+        tiles_rle_count_forward(s, m);
+        long long need = 0;
+        HIP_CHECK(hipMemcpyAsync(&need, m.ro + n, sizeof need, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        tc.alloc((size_t)need * sizeof(uint32_t));
+        m.counts = tc.as<uint32_t>();
+        // 3. .. 5. runs, order, suppression bits, greedy scan, the size of the output
+        tiles_select_forward(s, m);
+        long long out_need = 0;
+        HIP_CHECK(hipMemcpyAsync(&out_need, m.out_ro + slots, sizeof out_need, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (!dev) {
+            HIP_CHECK(hipMemcpy(detections_src, m.det_src, slots * 6 * sizeof(float), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(source, m.source, slots * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(n_kept, m.n_kept, (size_t)n_images * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(run_offsets, m.out_ro, (slots + 1) * sizeof(long long), hipMemcpyDeviceToHost));
+            if (areas) HIP_CHECK(hipMemcpy(areas, m.out_areas, slots * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            if (bboxes_xywh) HIP_CHECK(hipMemcpy(bboxes_xywh, m.out_bboxes, slots * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
+        }
+        MRCNN_REQUIRE(out_need <= (long long)capacity, MRCNN_ERR_SHAPE, "merge_tiles: the kept masks encode to %lld runs, counts holds %lld: call again with capacity >= %lld",
+                      out_need, (long long)capacity, out_need);
+        m.out_counts = counts;
+        if (!dev) { toc.alloc((size_t)out_need * sizeof(uint32_t)); m.out_counts = toc.as<uint32_t>(); }
+        tiles_gather_forward(s, m);
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (!dev) HIP_CHECK(hipMemcpy(counts, toc.p, (size_t)out_need * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    });
+}

@@ -290,6 +290,10 @@ struct Model {
     // One predict over `batch` images of DIFFERENT sizes (mrcnn_maskrcnn_predict_images): every image is staged into fit_src and
     // letterboxed with its own geometry by the pre-processing kernel; synchronous, never replayed from a captured graph.
     void predict_images(const mrcnn_image* images, int batch, int memspace, float* det, float* masks);
+    // The same over WINDOWS of the images (mrcnn_maskrcnn_predict_tiles; the table was checked by the caller): every image is staged
+    // once (MRCNN_DEVICE: read where it lies), a tile's table entry is its origin pixel, the window's size and its image's row pitch;
+    // ceil(n_tiles / max_batch) predicts of up to max_batch tiles each.
+    void predict_tiles(const mrcnn_image* images, int n_images, const mrcnn_tile* tiles, int n_tiles, int memspace, float* det, float* masks);
     // d_rgb (or, with fit geometry, fit_src — and, while fit_mixed is set, the geometry table instead of `fit`) → detections / mask_out, launches only
     void enqueue_pipeline(hipStream_t s, int batch, const int* fit = nullptr);
     void drop_graphs();

@@ -263,7 +263,7 @@ void Model::predict_images(const mrcnn_image* images, int batch, int memspace, f
         MRCNN_REQUIRE(im.height >= 1 && im.height <= 32767 && im.width >= 1 && im.width <= 32767, MRCNN_ERR_SHAPE,
                       "image %d of the batch is %dx%d: height and width must lie in 1..32767", b, im.height, im.width);
         ImageGeom& g = geom[(size_t)b];
-        g.offset = (long long)need; g.h = im.height; g.w = im.width;
+        g.offset = (long long)need; g.h = im.height; g.w = im.width; g.pitch = g.w;
         MRCNN_REQUIRE(mrcnn_letterbox_geometry(g.h, g.w, H, W, &g.nh, &g.nw, &g.py, &g.px) == MRCNN_OK, MRCNN_ERR_INVALID,
                       "image %d of the batch: bad letterbox geometry", b);
         need += (size_t)g.h * g.w * 3;
@@ -295,6 +295,55 @@ void Model::predict_images(const mrcnn_image* images, int batch, int memspace, f
     for (int b = 0; b < batch; ++b)
         HIP_CHECK(hipMemcpyAsync(dst + geom[(size_t)b].offset, images[b].rgb, (size_t)geom[(size_t)b].h * geom[(size_t)b].w * 3, in, s));
     predict(nullptr, batch, H, W, MRCNN_DEVICE, det_out, masks_out, true, true, true);
+}
+
+void Model::predict_tiles(const mrcnn_image* images, int n_images, const mrcnn_tile* tiles, int n_tiles, int memspace, float* det_out, float* masks_out)
+{
+    MRCNN_REQUIRE(kind == MRCNN_MODEL_MASKRCNN, MRCNN_ERR_INVALID, "predict_tiles called on a non-MaskRCNN model");
+    MRCNN_REQUIRE(images && tiles && det_out && masks_out, MRCNN_ERR_INVALID, "null buffer");
+    const bool dev = memspace == MRCNN_DEVICE;
+    // host images: back to back in fit_src, each from a 16-byte boundary; device images are read where they lie — an entry's offset
+    // is then the distance of its first byte from fit_src (one flat address space: k_preprocess_images only adds it to that base)
+    std::vector<size_t> at((size_t)n_images, 0);
+    size_t need = 0;
+    if (!dev)
+        for (int b = 0; b < n_images; ++b) { at[(size_t)b] = need; need += ((size_t)images[b].height * images[b].width * 3 + 15) & ~(size_t)15; }
+    hipStream_t s = stream;
+    const size_t table_off = (need + 15) & ~(size_t)15, cap = (size_t)max_batch * sizeof(ImageGeom), total = table_off + cap;
+    if (fit_src.bytes < total) { HIP_CHECK(hipStreamSynchronize(s)); fit_src.alloc(total); drop_graphs(); }
+    if (fit_pack_bytes < cap) {
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (fit_pack) { (void)hipHostFree(fit_pack); fit_pack = nullptr; fit_pack_bytes = 0; }
+        HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&fit_pack), cap, hipHostMallocDefault));
+        fit_pack_bytes = cap;
+    }
+    struct Leave {
+        Model* m;
+        ~Leave() { (void)hipStreamSynchronize(m->stream); m->fit_mixed = false; }
+    } leave{this};
+    fit_table_off = table_off;
+    fit_mixed = true;
+    uint8_t* const dst = fit_src.as<uint8_t>();
+    if (!dev)
+        for (int b = 0; b < n_images; ++b)
+            HIP_CHECK(hipMemcpyAsync(dst + at[(size_t)b], images[b].rgb, (size_t)images[b].height * images[b].width * 3, hipMemcpyHostToDevice, s));
+    const int HW = 4 * mask_pool * mask_pool;
+    for (int t0 = 0; t0 < n_tiles; t0 += max_batch) {
+        const int n = n_tiles - t0 < max_batch ? n_tiles - t0 : max_batch;
+        ImageGeom* const geom = reinterpret_cast<ImageGeom*>(fit_pack);       // (the predict before this one has drained the stream)
+        for (int i = 0; i < n; ++i) {
+            const mrcnn_tile& w = tiles[t0 + i];
+            const mrcnn_image& im = images[w.image];
+            ImageGeom& g = geom[i];
+            const long long first = ((long long)w.y0 * im.width + w.x0) * 3;
+            g.offset = dev ? (long long)(reinterpret_cast<intptr_t>(im.rgb) - reinterpret_cast<intptr_t>(dst)) + first : (long long)at[(size_t)w.image] + first;
+            g.h = w.height; g.w = w.width; g.pitch = im.width;
+            MRCNN_REQUIRE(mrcnn_letterbox_geometry(g.h, g.w, H, W, &g.nh, &g.nw, &g.py, &g.px) == MRCNN_OK, MRCNN_ERR_INVALID,
+                          "tile %d: bad letterbox geometry", t0 + i);
+        }
+        HIP_CHECK(hipMemcpyAsync(dst + table_off, fit_pack, (size_t)n * sizeof(ImageGeom), hipMemcpyHostToDevice, s));
+        predict(nullptr, n, H, W, MRCNN_DEVICE, det_out + (size_t)t0 * max_det * 6, masks_out + (size_t)t0 * max_det * HW, true, true, true);
+    }
 }
 
 // ---- pipelined host entry ------------------------------------------------------------------------------------------------

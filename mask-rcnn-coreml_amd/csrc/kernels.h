@@ -84,9 +84,12 @@ void preprocess_scalefit_forward(hipStream_t s, const uint8_t* src, int B, int h
 // One image of a mixed-size batch: where its bytes start in the buffer the kernel is given (the h×w×3 source pixels for the
 // pre-processing, the pasted planes for paste_masks_source_forward) and its letterbox geometry
 // (mrcnn_letterbox_geometry at the model's input size).  The table lives on the device, one entry per image.
+// pitch = the distance between two source rows in PIXELS, read by the pre-processing alone: w for a whole image, the image's width
+// for a window cut from it (mrcnn_maskrcnn_predict_tiles: offset = the window's origin pixel, h / w = the window's size).
 struct ImageGeom {
     long long offset;
     int h, w, nh, nw, py, px;
+    int pitch;
 };
 void preprocess_images_forward(hipStream_t s, const uint8_t* src, const ImageGeom* tab, int B, int H, int W, int pad, const float mean[3],
                                void* out, int dtype);

@@ -605,8 +605,10 @@ void masks_rle_write_forward(hipStream_t s, const float* masks, const ImageGeom*
 // (half-pixel centres, edge clamp, round-half-up to 8 bit) centred in an H×W canvas, black borders.
 // Vision's resampler is closed source → convention unpinned.
 // ------------------------------------------------------------------------------------------------
-// One letterboxed pixel (the arithmetic k_letterbox and the fused pre-processing share: the two must agree to the bit)
-__device__ __forceinline__ void letterbox_pixel(const uint8_t* __restrict__ src, int h, int w, int nh, int nw, float ry, float rx, int y, int x,
+// One letterboxed pixel (the arithmetic k_letterbox and the fused pre-processing share: the two must agree to the bit).  `pitch` is
+// the distance between two source rows in pixels — only the addresses use it; the clamps stay at h and w, so a window of a larger
+// image reads what a contiguous copy of it would
+__device__ __forceinline__ void letterbox_pixel(const uint8_t* __restrict__ src, int h, int w, int pitch, int nh, int nw, float ry, float rx, int y, int x,
                                                 uint8_t (&r)[3])
 {
     r[0] = r[1] = r[2] = 0;
@@ -616,10 +618,10 @@ __device__ __forceinline__ void letterbox_pixel(const uint8_t* __restrict__ src,
         sx = fminf(fmaxf(sx, 0.0f), (float)(w - 1));
         const int ya = (int)floorf(sy), yb = min(ya + 1, h - 1), xa = (int)floorf(sx), xb = min(xa + 1, w - 1);
         const float fy = sy - (float)ya, fx = sx - (float)xa;
-        const uint8_t* a = src + ((long)ya * w + xa) * 3;
-        const uint8_t* b = src + ((long)ya * w + xb) * 3;
-        const uint8_t* c = src + ((long)yb * w + xa) * 3;
-        const uint8_t* d = src + ((long)yb * w + xb) * 3;
+        const uint8_t* a = src + ((long)ya * pitch + xa) * 3;
+        const uint8_t* b = src + ((long)ya * pitch + xb) * 3;
+        const uint8_t* c = src + ((long)yb * pitch + xa) * 3;
+        const uint8_t* d = src + ((long)yb * pitch + xb) * 3;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const float top = (float)a[k] + ((float)b[k] - (float)a[k]) * fx;
@@ -638,7 +640,7 @@ __global__ __launch_bounds__(256) void k_letterbox(const uint8_t* __restrict__ s
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
         const int Y = (int)(e / W), X = (int)(e - (long)Y * W);
         uint8_t r[3];
-        letterbox_pixel(src, h, w, nh, nw, ry, rx, Y - py, X - px, r);
+        letterbox_pixel(src, h, w, w, nh, nw, ry, rx, Y - py, X - px, r);
         dst[e * 3 + 0] = r[0]; dst[e * 3 + 1] = r[1]; dst[e * 3 + 2] = r[2];
     }
 }
@@ -660,7 +662,7 @@ __global__ __launch_bounds__(256) void k_preprocess_scalefit(const uint8_t* __re
         float r = 0.f, g = 0.f, bl = 0.f;
         if ((unsigned)Y < (unsigned)H && (unsigned)X < (unsigned)W) {
             uint8_t v[3];
-            letterbox_pixel(src + (long)b * h * w * 3, h, w, nh, nw, ry, rx, Y - py, X - px, v);
+            letterbox_pixel(src + (long)b * h * w * 3, h, w, w, nh, nw, ry, rx, Y - py, X - px, v);
             r = (float)v[0] - mr; g = (float)v[1] - mg; bl = (float)v[2] - mb;
         }
         if constexpr (sizeof(T) == 4) {
@@ -706,7 +708,7 @@ __global__ __launch_bounds__(256) void k_preprocess_images(const uint8_t* __rest
         float r = 0.f, g = 0.f, bl = 0.f;
         if ((unsigned)Y < (unsigned)H && (unsigned)X < (unsigned)W) {
             uint8_t v[3];
-            letterbox_pixel(sp, im.h, im.w, im.nh, im.nw, ry, rx, Y - im.py, X - im.px, v);
+            letterbox_pixel(sp, im.h, im.w, im.pitch, im.nh, im.nw, ry, rx, Y - im.py, X - im.px, v);
             r = (float)v[0] - mr; g = (float)v[1] - mg; bl = (float)v[2] - mb;
         }
         if constexpr (sizeof(T) == 4) {

@@ -1,0 +1,277 @@
+// tiles_host.cpp — see tiles_host.h.  Sequential and plain on purpose: this file is what the merge kernels are compared with.
+#include "tiles_host.h"
+
+#include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
+
+#include <algorithm>
+#include <vector>
+
+namespace mrcnn {
+namespace tiles {
+
+static int bad(std::string* err, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
+static int bad(std::string* err, int code, const char* fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (err) *err = buf;
+    return code;
+}
+
+// ---- the planner: one axis ---------------------------------------------------------------------
+static int axis_count(int L, int T, int O) { return L <= T ? 1 : (L - T + (T - O) - 1) / (T - O) + 1; }
+static int axis_origin(int L, int T, int O, int k) { return L <= T ? 0 : std::min(k * (T - O), L - T); }
+
+int plan(int height, int width, int tile_h, int tile_w, int overlap_y, int overlap_x, int image, mrcnn_tile* out, int capacity, int* count,
+         std::string* err)
+{
+    if (!count) return bad(err, MRCNN_ERR_INVALID, "tile_plan: null count");
+    if (capacity < 0 || (!out && capacity != 0)) return bad(err, MRCNN_ERR_INVALID, "tile_plan: null out with capacity %d", capacity);
+    if (height < 1 || height > 32767 || width < 1 || width > 32767)
+        return bad(err, MRCNN_ERR_SHAPE, "tile_plan: the image is %dx%d: height and width must lie in 1..32767", height, width);
+    if (tile_h < 1 || tile_h > 32767 || tile_w < 1 || tile_w > 32767)
+        return bad(err, MRCNN_ERR_SHAPE, "tile_plan: the tile is %dx%d: height and width must lie in 1..32767", tile_h, tile_w);
+    if (overlap_y < 0 || overlap_y >= tile_h || overlap_x < 0 || overlap_x >= tile_w)
+        return bad(err, MRCNN_ERR_SHAPE, "tile_plan: overlap (%d, %d) must lie in 0..tile-1 of a %dx%d tile", overlap_y, overlap_x, tile_h, tile_w);
+    const int ny = axis_count(height, tile_h, overlap_y), nx = axis_count(width, tile_w, overlap_x);
+    const long need = (long)ny * nx;
+    if (need > 0x7fffffffL) return bad(err, MRCNN_ERR_SHAPE, "tile_plan: %ld tiles are too many", need);
+    *count = (int)need;
+    if (!out) return MRCNN_OK;                                  // the size query
+    if (need > capacity) return bad(err, MRCNN_ERR_SHAPE, "tile_plan: the plan has %ld tiles, out holds %d", need, capacity);
+    for (int j = 0; j < ny; ++j)
+        for (int i = 0; i < nx; ++i) {
+            mrcnn_tile& t = out[(size_t)j * nx + i];
+            t.image = image;
+            t.y0 = axis_origin(height, tile_h, overlap_y, j); t.x0 = axis_origin(width, tile_w, overlap_x, i);
+            t.height = std::min(tile_h, height); t.width = std::min(tile_w, width);
+        }
+    return MRCNN_OK;
+}
+
+// ---- argument checks -----------------------------------------------------------------------------
+int check_tiles(const mrcnn_tile* tiles, int n_tiles, const int32_t* heights, const int32_t* widths, int n_images, const char* who, std::string* err)
+{
+    for (int b = 0; b < n_images; ++b)
+        if (heights[b] < 1 || heights[b] > 32767 || widths[b] < 1 || widths[b] > 32767)
+            return bad(err, MRCNN_ERR_SHAPE, "%s: image %d is %dx%d: height and width must lie in 1..32767", who, b, heights[b], widths[b]);
+    for (int t = 0; t < n_tiles; ++t) {
+        const mrcnn_tile& w = tiles[t];
+        if (w.image < 0 || w.image >= n_images) return bad(err, MRCNN_ERR_SHAPE, "%s: tile %d names image %d of %d", who, t, w.image, n_images);
+        if (w.height < 1 || w.width < 1) return bad(err, MRCNN_ERR_SHAPE, "%s: tile %d is an empty window (%dx%d)", who, t, w.height, w.width);
+        const int h = heights[w.image], wd = widths[w.image];
+        if (w.y0 < 0 || w.x0 < 0 || w.y0 > h - w.height || w.x0 > wd - w.width)
+            return bad(err, MRCNN_ERR_SHAPE, "%s: tile %d (%dx%d at %d,%d) is not inside image %d (%dx%d)", who, t, w.height, w.width, w.y0, w.x0,
+                       w.image, h, wd);
+    }
+    return MRCNN_OK;
+}
+
+int check_merge(const MergeArgs& a, const char* who, std::string* err)
+{
+    if (!a.detections || !a.masks || !a.tiles || !a.heights || !a.widths || !a.detections_src || !a.source || !a.n_kept || !a.run_offsets)
+        return bad(err, MRCNN_ERR_INVALID, "%s: null argument", who);
+    if (a.capacity < 0 || (!a.counts && a.capacity != 0)) return bad(err, MRCNN_ERR_INVALID, "%s: null counts with capacity %lld", who, (long long)a.capacity);
+    if (a.mask_size < 2 || a.model_h < 1 || a.model_w < 1) return bad(err, MRCNN_ERR_INVALID, "%s: bad mask or model size", who);
+    if (a.metric != MRCNN_MATCH_IOU && a.metric != MRCNN_MATCH_IOS) return bad(err, MRCNN_ERR_INVALID, "%s: metric %d is neither MRCNN_MATCH_IOU nor MRCNN_MATCH_IOS", who, a.metric);
+    if (!(a.match_threshold > 0.0)) return bad(err, MRCNN_ERR_INVALID, "%s: match_threshold %g must be > 0", who, a.match_threshold);
+    if (a.n_tiles < 1) return bad(err, MRCNN_ERR_SHAPE, "%s: n_tiles %d < 1", who, a.n_tiles);
+    if (a.n_images < 1 || a.rows < 1 || a.max_out < 1) return bad(err, MRCNN_ERR_SHAPE, "%s: n_images %d, rows %d and max_out %d must be >= 1", who, a.n_images, a.rows, a.max_out);
+    if ((long)a.n_tiles * a.rows >= (1L << 31) || (long)a.n_images * a.max_out >= (1L << 31)) return bad(err, MRCNN_ERR_SHAPE, "%s: too many rows", who);
+    const int st = check_tiles(a.tiles, a.n_tiles, a.heights, a.widths, a.n_images, who, err);
+    if (st != MRCNN_OK) return st;
+    std::vector<long> per((size_t)a.n_images, 0);
+    for (int t = 0; t < a.n_tiles; ++t) per[(size_t)a.tiles[t].image] += a.rows;
+    for (int b = 0; b < a.n_images; ++b)
+        if (per[(size_t)b] > MRCNN_TILES_MAX_CANDIDATES)
+            return bad(err, MRCNN_ERR_SHAPE, "%s: image %d has %ld candidates (tiles x rows), at most %d can be merged", who, b, per[(size_t)b], MRCNN_TILES_MAX_CANDIDATES);
+    return MRCNN_OK;
+}
+
+// ---- the merge -----------------------------------------------------------------------------------
+namespace {
+
+struct Candidate {
+    int box[4];                      // (y1, x1, y2, x2) in the full frame, far edges exclusive; all 0 = not eligible
+    bool eligible;
+    float row[6];                    // the source-frame row
+    std::vector<uint32_t> counts;    // COCO RLE of the plane in the full frame
+    uint32_t area;
+    int bbox[4];
+};
+
+// paste_device.h's paste_tap / paste_lerp, operation for operation
+struct Tap { int a, b; float f; };
+Tap tap(int i, int lo, float scale, int S)
+{
+    float s = ((float)(i - lo) + 0.5f) * scale - 0.5f;
+    s = fminf(fmaxf(s, 0.0f), (float)(S - 1));
+    Tap t;
+    t.a = (int)floorf(s); t.b = std::min(t.a + 1, S - 1);
+    t.f = s - (float)t.a;
+    return t;
+}
+float lerp2(float a, float b, float c, float dd, float fx, float fy)
+{
+    const float top = a + (b - a) * fx;
+    const float bot = c + (dd - c) * fx;
+    return top + (bot - top) * fy;
+}
+
+// the candidate's box: mrcnn_unletterbox_boxes on the tile's own size, denorm_boxes at that size, then the shift by the origin
+void map_box(const float* d, const mrcnn_tile& t, int H, int W, int img_h, int img_w, Candidate& c)
+{
+    int nh = 0, nw = 0, py = 0, px = 0;
+    mrcnn_letterbox_geometry(t.height, t.width, H, W, &nh, &nw, &py, &px);
+    float r[4] = {d[0], d[1], d[2], d[3]};
+    const int h = t.height, w = t.width;
+    if (!(r[0] == 0.f && r[1] == 0.f && r[2] == 0.f && r[3] == 0.f)) {
+        const double sy = (double)h / nh, sx = (double)w / nw, hy = h > 1 ? h - 1 : 1, wx = w > 1 ? w - 1 : 1;
+        const double y1 = ((double)r[0] * (H - 1) - py) * sy, x1 = ((double)r[1] * (W - 1) - px) * sx;
+        const double y2 = ((double)r[2] * (H - 1) + 1.0 - py) * sy, x2 = ((double)r[3] * (W - 1) + 1.0 - px) * sx;
+        auto clip = [](double v) { return v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v); };
+        r[0] = (float)clip(y1 / hy); r[1] = (float)clip(x1 / wx); r[2] = (float)clip((y2 - 1.0) / hy); r[3] = (float)clip((x2 - 1.0) / wx);
+    }
+    const int by1 = (int)rint((double)r[0] * (double)(h - 1)), bx1 = (int)rint((double)r[1] * (double)(w - 1));
+    const int by2 = (int)rint((double)r[2] * (double)(h - 1) + 1.0), bx2 = (int)rint((double)r[3] * (double)(w - 1) + 1.0);
+    c.eligible = !(by2 - by1 <= 0 || bx2 - bx1 <= 0 || !(d[5] > 0.0f));
+    for (int k = 0; k < 6; ++k) c.row[k] = 0.f;
+    c.box[0] = c.box[1] = c.box[2] = c.box[3] = 0;
+    if (!c.eligible) return;
+    c.box[0] = by1 + t.y0; c.box[1] = bx1 + t.x0; c.box[2] = by2 + t.y0; c.box[3] = bx2 + t.x0;
+    const double hy = img_h > 1 ? img_h - 1 : 1, wx = img_w > 1 ? img_w - 1 : 1;
+    c.row[0] = (float)((double)c.box[0] / hy); c.row[1] = (float)((double)c.box[1] / wx);
+    c.row[2] = (float)((double)(c.box[2] - 1) / hy); c.row[3] = (float)((double)(c.box[3] - 1) / wx);
+    c.row[4] = d[4]; c.row[5] = d[5];
+}
+
+// the plane in the full frame as COCO runs: positions p = x*h + y in increasing order, only the box can hold set pixels
+void encode(const float* m, int S, float thr, int h, int w, Candidate& c)
+{
+    c.counts.clear(); c.area = 0;
+    c.bbox[0] = c.bbox[1] = c.bbox[2] = c.bbox[3] = 0;
+    const long total = (long)h * w;
+    long cursor = 0, start = -1, end = -1;         // [start, end): the run of ones being grown
+    int xmin = w, ymin = h, xmax = -1, ymax = -1;
+    auto close = [&] {
+        if (start < 0) return;
+        c.counts.push_back((uint32_t)(start - cursor)); c.counts.push_back((uint32_t)(end - start));
+        cursor = end; start = -1;
+    };
+    if (c.eligible) {
+        const int y1 = c.box[0], x1 = c.box[1], y2 = c.box[2], x2 = c.box[3];
+        const float sy = (float)S / (float)(y2 - y1), sx = (float)S / (float)(x2 - x1);
+        for (int x = x1; x < x2; ++x) {
+            const Tap tx = tap(x, x1, sx, S);
+            for (int y = y1; y < y2; ++y) {
+                const Tap ty = tap(y, y1, sy, S);
+                const float *ra = m + ty.a * S, *rb = m + ty.b * S;
+                if (!(lerp2(ra[tx.a], ra[tx.b], rb[tx.a], rb[tx.b], tx.f, ty.f) >= thr)) continue;
+                const long p = (long)x * h + y;
+                if (start >= 0 && p == end) ++end; else { close(); start = p; end = p + 1; }
+                ++c.area;
+                xmin = std::min(xmin, x); xmax = std::max(xmax, x); ymin = std::min(ymin, y); ymax = std::max(ymax, y);
+            }
+        }
+    }
+    close();
+    if (c.counts.empty() || cursor < total) c.counts.push_back((uint32_t)(total - cursor));
+    if (c.area) { c.bbox[0] = xmin; c.bbox[1] = ymin; c.bbox[2] = xmax - xmin + 1; c.bbox[3] = ymax - ymin + 1; }
+}
+
+// |A ∧ B| of two RLEs over the same number of pixels
+uint64_t intersection(const std::vector<uint32_t>& a, const std::vector<uint32_t>& b)
+{
+    uint64_t inter = 0, pa = 0, pb = 0;      // the ends of run ia / ib
+    size_t ia = 0, ib = 0;
+    if (a.empty() || b.empty()) return 0;
+    pa = a[0]; pb = b[0];
+    uint64_t at = 0;
+    while (ia < a.size() && ib < b.size()) {
+        const uint64_t to = std::min(pa, pb);
+        if ((ia & 1) && (ib & 1)) inter += to - at;
+        at = to;
+        if (pa == to) { ++ia; if (ia < a.size()) pa += a[ia]; }
+        if (pb == to) { ++ib; if (ib < b.size()) pb += b[ib]; }
+    }
+    return inter;
+}
+
+double measure(uint64_t inter, uint64_t aq, uint64_t ac, int metric)
+{
+    const uint64_t den = metric == MRCNN_MATCH_IOU ? aq + ac - inter : std::min(aq, ac);
+    return den == 0 ? 0.0 : (double)inter / (double)den;
+}
+
+}  // namespace
+
+int merge_host(const MergeArgs& a, std::string* err)
+{
+    const int st = check_merge(a, "merge_tiles_host", err);
+    if (st != MRCNN_OK) return st;
+    const int S = a.mask_size;
+    const long n = (long)a.n_tiles * a.rows;
+    std::vector<Candidate> cand((size_t)n);
+    for (int t = 0; t < a.n_tiles; ++t)
+        for (int i = 0; i < a.rows; ++i) {
+            const long k = (long)t * a.rows + i;
+            const mrcnn_tile& w = a.tiles[t];
+            map_box(a.detections + k * 6, w, a.model_h, a.model_w, a.heights[w.image], a.widths[w.image], cand[(size_t)k]);
+            encode(a.masks + k * S * S, S, a.threshold, a.heights[w.image], a.widths[w.image], cand[(size_t)k]);
+        }
+    const long slots = (long)a.n_images * a.max_out;
+    for (long s = 0; s < slots; ++s) {
+        a.source[s] = -1;
+        for (int k = 0; k < 6; ++k) a.detections_src[s * 6 + k] = 0.f;
+    }
+    for (int b = 0; b < a.n_images; ++b) {
+        std::vector<long> order;
+        for (long k = 0; k < n; ++k)
+            if (a.tiles[k / a.rows].image == b && cand[(size_t)k].eligible) order.push_back(k);
+        std::stable_sort(order.begin(), order.end(), [&](long p, long q) { return cand[(size_t)p].row[5] > cand[(size_t)q].row[5]; });
+        std::vector<long> kept;
+        for (long c : order) {
+            const Candidate& cc = cand[(size_t)c];
+            bool dropped = false;
+            for (long q : kept) {
+                const Candidate& cq = cand[(size_t)q];
+                if (cq.row[4] != cc.row[4] || q / a.rows == c / a.rows) continue;
+                if (measure(intersection(cq.counts, cc.counts), cq.area, cc.area, a.metric) >= a.match_threshold) { dropped = true; break; }
+            }
+            if (!dropped) kept.push_back(c);
+        }
+        a.n_kept[b] = (int32_t)kept.size();
+        for (size_t j = 0; j < kept.size() && j < (size_t)a.max_out; ++j) {
+            const long s = (long)b * a.max_out + (long)j;
+            a.source[s] = (int32_t)kept[j];
+            for (int k = 0; k < 6; ++k) a.detections_src[s * 6 + k] = cand[(size_t)kept[j]].row[k];
+        }
+    }
+    // the kept planes in mrcnn_masks_rle_source's layout; a padding slot is the empty plane of its image
+    int64_t need = 0;
+    for (long s = 0; s < slots; ++s) {
+        a.run_offsets[s] = need;
+        need += a.source[s] >= 0 ? (int64_t)cand[(size_t)a.source[s]].counts.size() : 1;
+        const Candidate* c = a.source[s] >= 0 ? &cand[(size_t)a.source[s]] : nullptr;
+        if (a.areas) a.areas[s] = c ? c->area : 0;
+        if (a.bboxes_xywh) for (int k = 0; k < 4; ++k) a.bboxes_xywh[s * 4 + k] = c ? c->bbox[k] : 0;
+    }
+    a.run_offsets[slots] = need;
+    if (need > a.capacity)
+        return bad(err, MRCNN_ERR_SHAPE, "merge_tiles_host: the kept masks encode to %lld runs, counts holds %lld: call again with capacity >= %lld",
+                   (long long)need, (long long)a.capacity, (long long)need);
+    for (long s = 0; s < slots; ++s) {
+        uint32_t* o = a.counts + a.run_offsets[s];
+        if (a.source[s] >= 0) std::copy(cand[(size_t)a.source[s]].counts.begin(), cand[(size_t)a.source[s]].counts.end(), o);
+        else { const int b = (int)(s / a.max_out); o[0] = (uint32_t)a.heights[b] * (uint32_t)a.widths[b]; }
+    }
+    return MRCNN_OK;
+}
+
+}  // namespace tiles
+}  // namespace mrcnn

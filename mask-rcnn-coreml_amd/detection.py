@@ -157,6 +157,110 @@ def masks_rle_source(detections, masks, sizes, model_h: int, model_w: int, thres
     return det_src, rles, areas, bboxes
 
 
+def tile_plan(height: int, width: int, tile, overlap=(64, 64), image: int = 0) -> np.ndarray:
+    """The windows of one image (``mrcnn_tile_plan``): tile = (tile_h, tile_w), overlap = (overlap_y, overlap_x) → an (n, 5) int32
+    array of (image, y0, x0, height, width), row-major.  Per axis: one window if the image is not longer than the tile, else windows
+    of exactly the tile's length at stride tile - overlap, the last one shifted inward.  The tables of several images are
+    concatenated with np.concatenate."""
+    n = C.c_int(0)
+    args = (int(height), int(width), int(tile[0]), int(tile[1]), int(overlap[0]), int(overlap[1]), int(image))
+    _lib.check(_lib.lib().mrcnn_tile_plan(*args, None, 0, C.byref(n)))
+    out = np.zeros((n.value, 5), dtype=np.int32)
+    _lib.check(_lib.lib().mrcnn_tile_plan(*args, out.ctypes.data_as(C.POINTER(_lib.Tile)), n.value, C.byref(n)))
+    return out
+
+
+def _tile_table(tiles):
+    t = np.ascontiguousarray(tiles, dtype=np.int32)
+    if t.ndim != 2 or t.shape[1] != 5:
+        raise ValueError("tiles: an (n, 5) table of (image, y0, x0, height, width) expected")
+    return t
+
+
+_METRICS = {"iou": _lib.MATCH_IOU, "ios": _lib.MATCH_IOS}
+
+
+def _merge_tiles(host_definition, detections, masks, tiles, sizes, model_h, model_w, threshold, metric, match_threshold, max_out):
+    on_host = isinstance(detections, np.ndarray)
+    if on_host:
+        det = np.ascontiguousarray(detections, dtype=np.float32)
+        m = np.ascontiguousarray(masks, dtype=np.float32)
+    else:
+        import torch
+        det, m = detections, masks
+        assert not host_definition, "merge_tiles_host takes numpy arrays"
+        assert det.is_cuda and m.is_cuda and det.dtype == torch.float32 and m.dtype == torch.float32 and det.is_contiguous() and m.is_contiguous()
+    tab = _tile_table(tiles)
+    T, rows = int(det.shape[0]), int(det.shape[1])
+    if tab.shape[0] != T or m.shape[0] != T or m.shape[1] != rows or det.shape[2] != 6:
+        raise ValueError("merge_tiles: detections (T,rows,6), masks (T,rows,S,S) and T tiles expected")
+    if metric not in _METRICS:
+        raise ValueError(f"merge_tiles: metric {metric!r} is neither 'iou' nor 'ios'")
+    B = len(sizes)
+    hs = np.array([int(s[0]) for s in sizes], dtype=np.int32)
+    ws = np.array([int(s[1]) for s in sizes], dtype=np.int32)
+    if max_out is None:
+        max_out = rows
+    max_out = int(max_out)
+    slots = max(0, B * max_out)
+    offsets = np.zeros(slots + 1, dtype=np.int64)
+    if on_host:
+        det_src, source, n_kept = np.zeros((B, max(0, max_out), 6), np.float32), np.zeros((B, max(0, max_out)), np.int32), np.zeros(B, np.int32)
+        areas, bboxes = np.zeros((B, max(0, max_out)), np.uint32), np.zeros((B, max(0, max_out), 4), np.int32)
+        ptr = lambda a: a.ctypes.data
+        new_counts = lambda k: np.empty(max(1, k), np.uint32)
+        offs_buf = offsets
+    else:
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=det.device)
+        det_src, source, n_kept = z((B, max(0, max_out), 6), torch.float32), z((B, max(0, max_out)), torch.int32), z((B,), torch.int32)
+        areas, bboxes = z((B, max(0, max_out)), torch.int32), z((B, max(0, max_out), 4), torch.int32)
+        ptr = lambda a: a.data_ptr()
+        new_counts = lambda k: torch.empty(max(1, k), dtype=torch.int32, device=det.device)
+        offs_buf = z((slots + 1,), torch.int64)
+    head = (ptr(det), ptr(m), tab.ctypes.data_as(C.POINTER(_lib.Tile)), T, rows, int(m.shape[2]), hs.ctypes.data, ws.ctypes.data, B,
+            int(model_h), int(model_w), C.c_float(threshold), _METRICS[metric], float(match_threshold), max_out)
+
+    def call(capacity):
+        counts = new_counts(capacity)
+        tail = (ptr(det_src), ptr(source), ptr(n_kept), ptr(counts), capacity, ptr(offs_buf), ptr(areas), ptr(bboxes))
+        if host_definition:
+            return _lib.lib().mrcnn_merge_tiles_host(*head, *tail), counts
+        return _lib.lib().mrcnn_merge_tiles(*head, _lib.HOST if on_host else _lib.DEVICE, *tail), counts
+    capacity = int(max(1, max_out) * (2 * ws.astype(np.int64) + 2).sum())      # as masks_rle_source sizes its first attempt
+    st, counts = call(capacity)
+    if not on_host:
+        offsets[:] = offs_buf.cpu().numpy()
+    if st == 4 and int(offsets[slots]) > capacity:             # MRCNN_ERR_SHAPE with the offsets complete: the capacity was the reason
+        st, counts = call(int(offsets[slots]))
+        if not on_host:
+            offsets[:] = offs_buf.cpu().numpy()
+    _lib.check(st)
+    used = int(offsets[slots])
+    host = counts[:used] if on_host else counts[:used].cpu().numpy().view(np.uint32)
+    rles = [[{"size": [int(hs[b]), int(ws[b])], "counts": host[int(offsets[b * max_out + i]):int(offsets[b * max_out + i + 1])]}
+             for i in range(max_out)] for b in range(B)]
+    return det_src, source, n_kept, rles, areas, bboxes
+
+
+def merge_tiles(detections, masks, tiles, sizes, model_h: int, model_w: int, threshold: float = 0.5, metric: str = "ios",
+                match_threshold: float = 0.5, max_out=None):
+    """The records ``MaskRCNN.predict_tiles`` returned for the windows ``tiles`` of images of sizes ``sizes`` = [(h_b, w_b)], in the
+    frame of those images, the duplicates of the overlaps dropped on the GPU (``mrcnn_merge_tiles``; the header states the rule).
+    Returns (det_src (B, max_out, 6), source (B, max_out) — the candidate tile*rows + row, -1 for padding —, n_kept (B) before the
+    cap, rles, areas, bboxes): ``rles[b][j]`` as masks_rle_source returns them, so coco_results.coco_results and
+    coco_eval.score_batch take them with det_src as they are.  metric "ios" (intersection over the smaller area: removes the cut
+    copy of an object in favour of its whole copy) or "iou"; max_out = None keeps `rows` per image.  numpy in → numpy out; torch
+    CUDA tensors in → the outputs stay on the device, only the run lengths come to the host."""
+    return _merge_tiles(False, detections, masks, tiles, sizes, model_h, model_w, threshold, metric, match_threshold, max_out)
+
+
+def merge_tiles_host(detections, masks, tiles, sizes, model_h: int, model_w: int, threshold: float = 0.5, metric: str = "ios",
+                     match_threshold: float = 0.5, max_out=None):
+    """The definition of merge_tiles: the same arguments (numpy) and results from the sequential host code
+    (``mrcnn_merge_tiles_host``), no GPU."""
+    return _merge_tiles(True, detections, masks, tiles, sizes, model_h, model_w, threshold, metric, match_threshold, max_out)
+
+
 def _ragged_layout(hs, ws, unit):
     """Byte offsets of a ragged output with ``unit`` bytes per pixel: every image starts on a 16-byte boundary."""
     nbytes = unit * hs.astype(np.int64) * ws.astype(np.int64)

@@ -150,6 +150,56 @@ class MaskRCNN(_Model):
             _lib.check(_lib.lib().mrcnn_maskrcnn_predict_images(self._h, table, B, _lib.DEVICE, det.data_ptr(), mask.data_ptr()))
         return det, mask
 
+    def predict_tiles(self, images, tiles):
+        """One predict per WINDOW of the images (mrcnn_maskrcnn_predict_tiles): images as predict_images takes them, tiles an (n, 5)
+        int32 table of (image, y0, x0, height, width) (detection.tile_plan).  Record t equals predict_images on a contiguous copy
+        of window t; every image crosses to the device once.  Any number of tiles: the call runs them max_batch at a time."""
+        from .detection import _tile_table
+        images = list(images)
+        tab = _tile_table(tiles)
+        B, T = len(images), int(tab.shape[0])
+        table = (_lib.Image * max(1, B))()
+        on_host = B == 0 or isinstance(images[0], np.ndarray)
+        keep = []
+        for b, im in enumerate(images):
+            if on_host:
+                im = np.ascontiguousarray(im, dtype=np.uint8)
+                ptr = im.ctypes.data
+            else:
+                import torch
+                assert im.is_cuda and im.dtype == torch.uint8 and im.is_contiguous()
+                ptr = im.data_ptr()
+            if im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError(f"image {b} has shape {tuple(im.shape)}, expected (h, w, 3)")
+            keep.append(im)
+            table[b].rgb, table[b].height, table[b].width = ptr, int(im.shape[0]), int(im.shape[1])
+        shape_d = (T, self.max_detections, 6)
+        shape_m = (T, self.max_detections, self.mask_size, self.mask_size)
+        tp = tab.ctypes.data_as(C.POINTER(_lib.Tile))
+        if on_host:
+            det, mask = np.empty(shape_d, dtype=np.float32), np.empty(shape_m, dtype=np.float32)
+            _lib.check(_lib.lib().mrcnn_maskrcnn_predict_tiles(self._h, table, B, tp, T, _lib.HOST, det.ctypes.data, mask.ctypes.data))
+        else:
+            import torch
+            det = torch.empty(shape_d, dtype=torch.float32, device=images[0].device)
+            mask = torch.empty(shape_m, dtype=torch.float32, device=images[0].device)
+            _lib.check(_lib.lib().mrcnn_maskrcnn_predict_tiles(self._h, table, B, tp, T, _lib.DEVICE, det.data_ptr(), mask.data_ptr()))
+        return det, mask
+
+    def predict_tiled(self, images, tile=None, overlap=(64, 64), metric="ios", match_threshold=0.5, max_out=None, threshold=0.5):
+        """Large images as overlapping windows at native resolution: detection.tile_plan per image (tile = None: the model's input
+        size), predict_tiles, detection.merge_tiles.  Returns (det_src, source, n_kept, rles) in the frame of the images, in the
+        form coco_results.coco_results and coco_eval.score_batch take.  An object is found whole only if some window holds it
+        whole: choose the overlap at least as large as the largest object of interest."""
+        from .detection import merge_tiles, tile_plan
+        images = list(images)
+        H, W = self.image_height, self.image_width
+        tile = (H, W) if tile is None else tile
+        sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+        tiles = np.concatenate([tile_plan(h, w, tile, overlap, b) for b, (h, w) in enumerate(sizes)])
+        det, mask = self.predict_tiles(images, tiles)
+        return merge_tiles(det, mask, tiles, sizes, H, W, threshold, metric, match_threshold, max_out)[:4]
+
     def predict_jpegs(self, files, entropy="host"):
         """predict_images straight from JPEG files (mrcnn_maskrcnn_predict_jpegs_on): a list of bytes.  The entropy decoders run on the
         host, everything after them on the GPU, and the decoded images stay in staging the handle owns; the results equal
