@@ -653,9 +653,9 @@ MRCNN_API int mrcnn_render_detections_source(const mrcnn_image* images, const fl
  *   tile(q) != tile(c) and m(q, c) >= match_threshold, where inter = |P_q & P_c| (an exact integer), a = the planes' areas and
  *     MRCNN_MATCH_IOU: m = inter / (a_q + a_c - inter)        MRCNN_MATCH_IOS: m = inter / min(a_q, a_c)
  *   as IEEE double divisions of those integers, 0/0 = 0.  A dropped candidate suppresses nothing; rows of one tile are never compared
- *   (the detection layer's own NMS ran there).  Candidates are only dropped, masks are never united: an object is recovered whole
- *   only if some window contains it whole, so the overlap should be at least the largest object of interest; IoS is the metric that
- *   removes a cut copy of an object in favour of its whole copy.
+ *   (the detection layer's own NMS ran there).  This entry only drops candidates: an object is recovered whole by it only if some
+ *   window contains it whole; IoS is the metric that removes a cut copy of an object in favour of its whole copy.  The cut parts of
+ *   an object that no window holds whole are united into one mask by mrcnn_unite_tiles (below).
  *   Outputs, per image the first max_out kept candidates in that order:
  *     detections_src (n_images, max_out, 6)   the rows above, zero-padded
  *     source (n_images, max_out)              the candidate index k, -1 for padding
@@ -668,6 +668,35 @@ MRCNN_API int mrcnn_render_detections_source(const mrcnn_image* images, const fl
  *   An image may have at most MRCNN_TILES_MAX_CANDIDATES candidates (its tiles x rows: 81 tiles of 100 rows), beyond ->
  *   MRCNN_ERR_SHAPE.  Argument errors as predict_tiles'; unknown metric, match_threshold <= 0 -> MRCNN_ERR_INVALID; rows, n_images or
  *   max_out < 1 -> MRCNN_ERR_SHAPE.  Every argument error is answered before a device is looked for.
+ *
+ * mrcnn_unite_tiles (device) / mrcnn_unite_tiles_host (the definition: sequential plain C++, no GPU) — the same records with the cut
+ *   parts of an object, and its duplicates, united into ONE mask.  The device entry equals the host entry bit for bit.  Candidates,
+ *   eligibility, boxes, planes, rows and the per-image order (score descending, ties by k ascending) are mrcnn_merge_tiles'.
+ *   LINK: two eligible candidates q, c of one image are linked if they have the same class id, tile(q) != tile(c), the two windows
+ *   share a non-empty rectangle R and m_R(q, c) >= link_threshold, where inter = |P_q & P_c| (it lies inside R), a_qR = |P_q & R|,
+ *   a_cR = |P_c & R| and
+ *     MRCNN_MATCH_IOU: m_R = inter / (a_qR + a_cR - inter)    MRCNN_MATCH_IOS: m_R = inter / min(a_qR, a_cR)
+ *   as IEEE double divisions of those integers, 0/0 = 0: the agreement of the two masks where both windows could see the object.  It
+ *   is 1 where a cut part meets its continuation, where a cut copy meets the whole copy and where two whole copies lie inside the
+ *   overlap, so one rule covers fragments and duplicates.  Rows of one tile are never linked.
+ *   COMPONENTS: the connected components of the link graph (transitive: an object crossing three windows in a row is one component
+ *   even if the first and the last window share nothing; a wrongly chained component is not split — link_threshold is the control).
+ *   A component's REPRESENTATIVE is its member earliest in the order; components are listed by their representative's place.
+ *   Outputs, per image the first max_out components, as mrcnn_merge_tiles' with
+ *     plane (counts / areas / bboxes_xywh)    the OR of the members' planes (a run one member ends exactly where another begins is
+ *                                             one run; positions are linear, also across a column boundary); bboxes_xywh is the
+ *                                             tight box of the set pixels
+ *     detections_src                          the row, computed as above, of the hull of the members' full-frame boxes (min y1, x1,
+ *                                             max y2, x2); class and score are the representative's
+ *     source                                  the representative's k
+ *     n_kept                                  the number of components before the cap
+ *     n_parts (n_images, max_out)             the number of members, 0 for padding; may be NULL
+ *     group (n_tiles, rows)                   per candidate the index of its component within its image in the output order (>=
+ *                                             max_out where the output was truncated), -1 if not eligible; may be NULL
+ *   A component of one member is, bit for bit, what mrcnn_merge_tiles outputs for that candidate when kept.  link_threshold > 0;
+ *   limits, errors and the capacity protocol are mrcnn_merge_tiles'.  A united mask is no longer a pasted S x S mask:
+ *   mrcnn_paste_masks_source and the renderers cannot reproduce it from detections_src; the RLE is the result.  Objects are not united
+ *   across images.
  * examples/maskrcnn_predict_tiled.c is the whole flow as a C99 host. */
 typedef struct { int32_t image, y0, x0, height, width; } mrcnn_tile;   /* a window of images[image] */
 enum { MRCNN_MATCH_IOU = 0, MRCNN_MATCH_IOS = 1 };
@@ -686,6 +715,16 @@ MRCNN_API int mrcnn_merge_tiles_host(const float* detections, const float* masks
                                      float threshold, int metric, double match_threshold, int max_out, float* detections_src,
                                      int32_t* source, int32_t* n_kept, uint32_t* counts, int64_t capacity, int64_t* run_offsets,
                                      uint32_t* areas, int32_t* bboxes_xywh);
+MRCNN_API int mrcnn_unite_tiles(const float* detections, const float* masks, const mrcnn_tile* tiles, int n_tiles, int rows, int mask_size,
+                                const int32_t* heights, const int32_t* widths, int n_images, int model_h, int model_w, float threshold,
+                                int metric, double link_threshold, int max_out, int memspace, float* detections_src, int32_t* source,
+                                int32_t* n_kept, int32_t* n_parts, int32_t* group, uint32_t* counts, int64_t capacity,
+                                int64_t* run_offsets, uint32_t* areas, int32_t* bboxes_xywh);
+MRCNN_API int mrcnn_unite_tiles_host(const float* detections, const float* masks, const mrcnn_tile* tiles, int n_tiles, int rows,
+                                     int mask_size, const int32_t* heights, const int32_t* widths, int n_images, int model_h, int model_w,
+                                     float threshold, int metric, double link_threshold, int max_out, float* detections_src,
+                                     int32_t* source, int32_t* n_kept, int32_t* n_parts, int32_t* group, uint32_t* counts,
+                                     int64_t capacity, int64_t* run_offsets, uint32_t* areas, int32_t* bboxes_xywh);
 
 /* Host only, no GPU: COCO's compressed string of one RLE (pycocotools rleToString / rleFrString), not NUL-terminated.  *length / *n is
  * always the size needed; with out / counts = NULL the call only measures, a buffer that is too small gives MRCNN_ERR_SHAPE. */

@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = [
     "mrcnn_jpeg_encode_host", "mrcnn_jpeg_encode_batch",
     "mrcnn_png_encode_host", "mrcnn_png_encode_batch",
     "mrcnn_tile_plan", "mrcnn_maskrcnn_predict_tiles", "mrcnn_merge_tiles", "mrcnn_merge_tiles_host",
+    "mrcnn_unite_tiles", "mrcnn_unite_tiles_host",
 ]
 # declared in include/maskrcnn_hip_test.h (test / measurement entry points of the same library)
 TEST_SYMBOLS = [
@@ -171,6 +172,8 @@ def lib():
     _merge = [vp, vp, C.POINTER(Tile), C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_double, C.c_int]
     L.mrcnn_merge_tiles.argtypes = _merge + [C.c_int, vp, vp, vp, vp, C.c_int64, vp, vp, vp]
     L.mrcnn_merge_tiles_host.argtypes = _merge + [vp, vp, vp, vp, C.c_int64, vp, vp, vp]
+    L.mrcnn_unite_tiles.argtypes = _merge + [C.c_int, vp, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp]
+    L.mrcnn_unite_tiles_host.argtypes = _merge + [vp, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp]
     L.mrcnn_rle_to_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_from_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_iou.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int64]

@@ -1,6 +1,6 @@
-// api_tiles.hip — the C ABI of include/maskrcnn_hip.h, tiled prediction: the planner and the host merge (tiles_host.cpp behind them),
-// the predict over windows (Model::predict_tiles) and the device merge (kernels_tiles.hip).  Every argument error is answered before a
-// device is looked for.
+// api_tiles.hip — the C ABI of include/maskrcnn_hip.h, tiled prediction: the planner, the host merge and the host union (tiles_host.cpp
+// behind them), the predict over windows (Model::predict_tiles), and the device merge and the device union (kernels_tiles.hip), which
+// share one staging (TilesRun).  Every argument error is answered before a device is looked for.
 #include "api_util.h"
 #include "kernels_tiles.h"
 #include "tiles_host.h"
@@ -39,10 +39,11 @@ extern "C" int mrcnn_maskrcnn_predict_tiles(mrcnn_model* model, const mrcnn_imag
 static tiles::MergeArgs merge_args(const float* detections, const float* masks, const mrcnn_tile* tiles, int n_tiles, int rows, int mask_size,
                                    const int32_t* heights, const int32_t* widths, int n_images, int model_h, int model_w, float threshold, int metric,
                                    double match_threshold, int max_out, float* detections_src, int32_t* source, int32_t* n_kept, uint32_t* counts,
-                                   int64_t capacity, int64_t* run_offsets, uint32_t* areas, int32_t* bboxes_xywh)
+                                   int64_t capacity, int64_t* run_offsets, uint32_t* areas, int32_t* bboxes_xywh, int32_t* n_parts = nullptr,
+                                   int32_t* group = nullptr)
 {
     return tiles::MergeArgs{detections, masks, tiles, n_tiles, rows, mask_size, heights, widths, n_images, model_h, model_w, threshold, metric,
-                            match_threshold, max_out, detections_src, source, n_kept, counts, capacity, run_offsets, areas, bboxes_xywh};
+                            match_threshold, max_out, detections_src, source, n_kept, counts, capacity, run_offsets, areas, bboxes_xywh, n_parts, group};
 }
 
 extern "C" int mrcnn_merge_tiles_host(const float* detections, const float* masks, const mrcnn_tile* tiles, int n_tiles, int rows, int mask_size,
@@ -59,54 +60,71 @@ extern "C" int mrcnn_merge_tiles_host(const float* detections, const float* mask
     });
 }
 
-extern "C" int mrcnn_merge_tiles(const float* detections, const float* masks, const mrcnn_tile* tiles, int n_tiles, int rows, int mask_size,
-                                 const int32_t* heights, const int32_t* widths, int n_images, int model_h, int model_w, float threshold, int metric,
-                                 double match_threshold, int max_out, int memspace, float* detections_src, int32_t* source, int32_t* n_kept,
-                                 uint32_t* counts, int64_t capacity, int64_t* run_offsets, uint32_t* areas, int32_t* bboxes_xywh)
+extern "C" int mrcnn_unite_tiles_host(const float* detections, const float* masks, const mrcnn_tile* tiles, int n_tiles, int rows, int mask_size,
+                                      const int32_t* heights, const int32_t* widths, int n_images, int model_h, int model_w, float threshold,
+                                      int metric, double link_threshold, int max_out, float* detections_src, int32_t* source, int32_t* n_kept,
+                                      int32_t* n_parts, int32_t* group, uint32_t* counts, int64_t capacity, int64_t* run_offsets, uint32_t* areas,
+                                      int32_t* bboxes_xywh)
 {
     return guarded([&] {
         std::string err;
-        const int st = tiles::check_merge(merge_args(detections, masks, tiles, n_tiles, rows, mask_size, heights, widths, n_images, model_h, model_w,
-                                                     threshold, metric, match_threshold, max_out, detections_src, source, n_kept, counts, capacity,
-                                                     run_offsets, areas, bboxes_xywh), "merge_tiles", &err);
+        const int st = tiles::unite_host(merge_args(detections, masks, tiles, n_tiles, rows, mask_size, heights, widths, n_images, model_h, model_w,
+                                                    threshold, metric, link_threshold, max_out, detections_src, source, n_kept, counts, capacity,
+                                                    run_offsets, areas, bboxes_xywh, n_parts, group), &err);
         if (st != MRCNN_OK) fail(st, "%s", err.c_str());
-        require_gpu();
-        const bool dev = memspace == MRCNN_DEVICE;
-        const size_t n = (size_t)n_tiles * rows, slots = (size_t)n_images * max_out;
+    });
+}
+
+namespace {
+
+// One merge / unite call on the device.  The constructor stages what both entries share: the tables, the candidates' boxes in the full
+// frame, their planes as runs and the per-image order (steps 1 to 3 of kernels_tiles.hip).  The entry then runs its own selection,
+// deliver() hands out the fixed-size results and checks the capacity, and the entry's write step fills out_counts before done().
+struct TilesRun {
+    const tiles::MergeArgs& a;
+    const char* who;
+    const bool dev, unite;
+    const size_t n, slots;
+    Stream st_;
+    DevBuf td, tm, tt, tw, tc, toc;
+    Drain drain;                                             // (declared behind the buffers: the stream drains before they are freed)
+    TilesMerge m{};
+    hipStream_t s;
+
+    TilesRun(const tiles::MergeArgs& args, int memspace, const char* name, bool uniting)
+        : a(args), who(name), dev(memspace == MRCNN_DEVICE), unite(uniting), n((size_t)args.n_tiles * args.rows),
+          slots((size_t)args.n_images * args.max_out), drain{st_.s}, s(st_.s)
+    {
+        const int n_tiles = a.n_tiles, n_images = a.n_images, rows = a.rows;
         // the host tables: per tile its own letterbox geometry (the box map), its image's size (the RLE kernels) and its place; per image its tiles
         std::vector<ImageGeom> tab((size_t)2 * n_tiles);
         std::vector<TileGeom> tg((size_t)n_tiles);
         std::vector<int> toff((size_t)n_images + 1, 0), tlist((size_t)n_tiles);
         std::vector<int2> imgsz((size_t)n_images);
-        for (int b = 0; b < n_images; ++b) imgsz[(size_t)b] = make_int2(heights[b], widths[b]);
+        for (int b = 0; b < n_images; ++b) imgsz[(size_t)b] = make_int2(a.heights[b], a.widths[b]);
         for (int t = 0; t < n_tiles; ++t) {
-            const mrcnn_tile& w = tiles[t];
+            const mrcnn_tile& w = a.tiles[t];
             ImageGeom& g = tab[(size_t)t];
             g = ImageGeom{};
             g.h = w.height; g.w = w.width; g.pitch = w.width;
-            MRCNN_REQUIRE(mrcnn_letterbox_geometry(g.h, g.w, model_h, model_w, &g.nh, &g.nw, &g.py, &g.px) == MRCNN_OK, MRCNN_ERR_INVALID,
-                          "merge_tiles: tile %d: bad letterbox geometry", t);
+            MRCNN_REQUIRE(mrcnn_letterbox_geometry(g.h, g.w, a.model_h, a.model_w, &g.nh, &g.nw, &g.py, &g.px) == MRCNN_OK, MRCNN_ERR_INVALID,
+                          "%s: tile %d: bad letterbox geometry", who, t);
             ImageGeom& f = tab[(size_t)n_tiles + t];
             f = ImageGeom{};
-            f.h = heights[w.image]; f.w = widths[w.image]; f.pitch = f.w;
-            tg[(size_t)t] = TileGeom{w.image, w.y0, w.x0, f.h, f.w};
+            f.h = a.heights[w.image]; f.w = a.widths[w.image]; f.pitch = f.w;
+            tg[(size_t)t] = TileGeom{w.image, w.y0, w.x0, f.h, f.w, w.height, w.width};
             ++toff[(size_t)w.image + 1];
         }
         int most = 0;
         for (int b = 0; b < n_images; ++b) { most = std::max(most, toff[(size_t)b + 1] * rows); toff[(size_t)b + 1] += toff[(size_t)b]; }
         {
             std::vector<int> fill(toff.begin(), toff.end() - 1);
-            for (int t = 0; t < n_tiles; ++t) tlist[(size_t)fill[(size_t)tiles[t].image]++] = t;           // ascending t within an image
+            for (int t = 0; t < n_tiles; ++t) tlist[(size_t)fill[(size_t)a.tiles[t].image]++] = t;         // ascending t within an image
         }
-        Stream st_;
-        hipStream_t s = st_.s;
-        DevBuf td, tm, tt, tw, tc, toc;
-        Drain drain{s};                                          // (declared behind the buffers: the stream drains before they are freed)
-        TilesMerge m{};
-        m.n_tiles = n_tiles; m.rows = rows; m.S = mask_size; m.n_images = n_images; m.max_out = max_out; m.W = (most + 63) / 64;
-        m.thr = threshold; m.metric = metric; m.match_thr = match_threshold;
-        m.det = stage_rows(detections, memspace, (long)n, 6, 6, td);
-        m.masks = stage_rows(masks, memspace, (long)n, (long)mask_size * mask_size, (long)mask_size * mask_size, tm);
+        m.n_tiles = n_tiles; m.rows = rows; m.S = a.mask_size; m.n_images = n_images; m.max_out = a.max_out; m.W = (most + 63) / 64;
+        m.thr = a.threshold; m.metric = a.metric; m.match_thr = a.match_threshold;
+        m.det = stage_rows(a.detections, memspace, (long)n, 6, 6, td);
+        m.masks = stage_rows(a.masks, memspace, (long)n, (long)a.mask_size * a.mask_size, (long)a.mask_size * a.mask_size, tm);
         // one allocation for the tables, one for the scratch
         size_t o = 0;
         auto take = [&](size_t bytes) { const size_t at = o; o = up(o + bytes, 16); return at; };
@@ -134,6 +152,10 @@ extern "C" int mrcnn_merge_tiles(const float* detections, const float* masks, co
         // the outputs: the caller's device arrays, or a staging copy of each
         const size_t w_ds = take(slots * 6 * sizeof(float)), w_src = take(slots * sizeof(int32_t)), w_nk = take((size_t)n_images * sizeof(int32_t)),
                      w_oro = take((slots + 1) * sizeof(long long)), w_oar = take(slots * sizeof(uint32_t)), w_obb = take(slots * 4 * sizeof(int32_t));
+        // the union's member lists, hulls and segments, and its two outputs
+        const size_t u = unite ? 1 : 0;
+        const size_t w_mem = take(u * n * sizeof(int)), w_span = take(u * slots * sizeof(int2)), w_hull = take(u * slots * sizeof(int4)),
+                     w_oseg = take(u * slots * RLE_SEGS * sizeof(RleSeg)), w_np = take(u * slots * sizeof(int32_t)), w_grp = take(u * n * sizeof(int32_t));
         tw.alloc(o);
         char* const wb = tw.as<char>();
         m.boxes = reinterpret_cast<int4*>(wb + w_box); m.rows_src = reinterpret_cast<float*>(wb + w_rows);
@@ -141,39 +163,104 @@ extern "C" int mrcnn_merge_tiles(const float* detections, const float* masks, co
         m.areas = reinterpret_cast<uint32_t*>(wb + w_ar); m.bboxes = reinterpret_cast<int32_t*>(wb + w_bb);
         m.order = reinterpret_cast<int*>(wb + w_ord); m.pos = reinterpret_cast<int*>(wb + w_pos); m.nelig = reinterpret_cast<int*>(wb + w_ne);
         m.supp = reinterpret_cast<unsigned long long*>(wb + w_sup); m.out_nruns = reinterpret_cast<uint32_t*>(wb + w_onr);
-        m.det_src = dev ? detections_src : reinterpret_cast<float*>(wb + w_ds);
-        m.source = dev ? source : reinterpret_cast<int32_t*>(wb + w_src);
-        m.n_kept = dev ? n_kept : reinterpret_cast<int32_t*>(wb + w_nk);
-        m.out_ro = dev ? reinterpret_cast<long long*>(run_offsets) : reinterpret_cast<long long*>(wb + w_oro);
-        m.out_areas = dev && areas ? areas : reinterpret_cast<uint32_t*>(wb + w_oar);
-        m.out_bboxes = dev && bboxes_xywh ? bboxes_xywh : reinterpret_cast<int32_t*>(wb + w_obb);
+        m.det_src = dev ? a.detections_src : reinterpret_cast<float*>(wb + w_ds);
+        m.source = dev ? a.source : reinterpret_cast<int32_t*>(wb + w_src);
+        m.n_kept = dev ? a.n_kept : reinterpret_cast<int32_t*>(wb + w_nk);
+        m.out_ro = dev ? reinterpret_cast<long long*>(a.run_offsets) : reinterpret_cast<long long*>(wb + w_oro);
+        m.out_areas = dev && a.areas ? a.areas : reinterpret_cast<uint32_t*>(wb + w_oar);
+        m.out_bboxes = dev && a.bboxes_xywh ? a.bboxes_xywh : reinterpret_cast<int32_t*>(wb + w_obb);
+        if (unite) {
+            m.members = reinterpret_cast<int*>(wb + w_mem); m.mspan = reinterpret_cast<int2*>(wb + w_span);
+            m.hull = reinterpret_cast<int4*>(wb + w_hull); m.out_segs = reinterpret_cast<RleSeg*>(wb + w_oseg);
+            m.n_parts = dev && a.n_parts ? a.n_parts : reinterpret_cast<int32_t*>(wb + w_np);
+            m.group = dev && a.group ? a.group : reinterpret_cast<int32_t*>(wb + w_grp);
+        }
         // 1. the boxes, 2. the candidates' runs counted
-        unletterbox_boxes_forward(s, m.det, tab_tile, n_tiles, rows, model_h, model_w, reinterpret_cast<float*>(wb + w_tile), m.boxes);
+        unletterbox_boxes_forward(s, m.det, tab_tile, n_tiles, rows, a.model_h, a.model_w, reinterpret_cast<float*>(wb + w_tile), m.boxes);
         tiles_rle_count_forward(s, m);
         long long need = 0;
         HIP_CHECK(hipMemcpyAsync(&need, m.ro + n, sizeof need, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         tc.alloc((size_t)need * sizeof(uint32_t));
         m.counts = tc.as<uint32_t>();
-        // 3. .. 5. runs, order, suppression bits, greedy scan, the size of the output
-        tiles_select_forward(s, m);
+        // 3. the runs and the per-image order
+        tiles_order_forward(s, m);
+    }
+
+    // the selection has run: the fixed-size results to the caller, the capacity checked, out_counts ready for the write step
+    void deliver()
+    {
         long long out_need = 0;
         HIP_CHECK(hipMemcpyAsync(&out_need, m.out_ro + slots, sizeof out_need, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         if (!dev) {
-            HIP_CHECK(hipMemcpy(detections_src, m.det_src, slots * 6 * sizeof(float), hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(source, m.source, slots * sizeof(int32_t), hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(n_kept, m.n_kept, (size_t)n_images * sizeof(int32_t), hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(run_offsets, m.out_ro, (slots + 1) * sizeof(long long), hipMemcpyDeviceToHost));
-            if (areas) HIP_CHECK(hipMemcpy(areas, m.out_areas, slots * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            if (bboxes_xywh) HIP_CHECK(hipMemcpy(bboxes_xywh, m.out_bboxes, slots * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(a.detections_src, m.det_src, slots * 6 * sizeof(float), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(a.source, m.source, slots * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(a.n_kept, m.n_kept, (size_t)a.n_images * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(a.run_offsets, m.out_ro, (slots + 1) * sizeof(long long), hipMemcpyDeviceToHost));
+            if (a.areas) HIP_CHECK(hipMemcpy(a.areas, m.out_areas, slots * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            if (a.bboxes_xywh) HIP_CHECK(hipMemcpy(a.bboxes_xywh, m.out_bboxes, slots * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
+            if (unite && a.n_parts) HIP_CHECK(hipMemcpy(a.n_parts, m.n_parts, slots * sizeof(int32_t), hipMemcpyDeviceToHost));
+            if (unite && a.group) HIP_CHECK(hipMemcpy(a.group, m.group, n * sizeof(int32_t), hipMemcpyDeviceToHost));
         }
-        MRCNN_REQUIRE(out_need <= (long long)capacity, MRCNN_ERR_SHAPE, "merge_tiles: the kept masks encode to %lld runs, counts holds %lld: call again with capacity >= %lld",
-                      out_need, (long long)capacity, out_need);
-        m.out_counts = counts;
+        MRCNN_REQUIRE(out_need <= (long long)a.capacity, MRCNN_ERR_SHAPE, "%s: the kept masks encode to %lld runs, counts holds %lld: call again with capacity >= %lld",
+                      who, out_need, (long long)a.capacity, out_need);
+        m.out_counts = a.counts;
         if (!dev) { toc.alloc((size_t)out_need * sizeof(uint32_t)); m.out_counts = toc.as<uint32_t>(); }
-        tiles_gather_forward(s, m);
+        used = out_need;
+    }
+
+    // the write step is queued: the runs to the caller
+    void done()
+    {
         HIP_CHECK(hipStreamSynchronize(s));
-        if (!dev) HIP_CHECK(hipMemcpy(counts, toc.p, (size_t)out_need * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (!dev) HIP_CHECK(hipMemcpy(a.counts, toc.p, (size_t)used * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+
+    long long used = 0;
+};
+
+}  // namespace
+
+extern "C" int mrcnn_merge_tiles(const float* detections, const float* masks, const mrcnn_tile* tiles, int n_tiles, int rows, int mask_size,
+                                 const int32_t* heights, const int32_t* widths, int n_images, int model_h, int model_w, float threshold, int metric,
+                                 double match_threshold, int max_out, int memspace, float* detections_src, int32_t* source, int32_t* n_kept,
+                                 uint32_t* counts, int64_t capacity, int64_t* run_offsets, uint32_t* areas, int32_t* bboxes_xywh)
+{
+    return guarded([&] {
+        std::string err;
+        const tiles::MergeArgs a = merge_args(detections, masks, tiles, n_tiles, rows, mask_size, heights, widths, n_images, model_h, model_w, threshold,
+                                              metric, match_threshold, max_out, detections_src, source, n_kept, counts, capacity, run_offsets, areas,
+                                              bboxes_xywh);
+        const int st = tiles::check_merge(a, "merge_tiles", &err);
+        if (st != MRCNN_OK) fail(st, "%s", err.c_str());
+        require_gpu();
+        TilesRun r(a, memspace, "merge_tiles", false);
+        tiles_select_forward(r.s, r.m);                          // 4., 5. suppression bits, greedy scan, the size of the output
+        r.deliver();
+        tiles_gather_forward(r.s, r.m);
+        r.done();
+    });
+}
+
+extern "C" int mrcnn_unite_tiles(const float* detections, const float* masks, const mrcnn_tile* tiles, int n_tiles, int rows, int mask_size,
+                                 const int32_t* heights, const int32_t* widths, int n_images, int model_h, int model_w, float threshold, int metric,
+                                 double link_threshold, int max_out, int memspace, float* detections_src, int32_t* source, int32_t* n_kept,
+                                 int32_t* n_parts, int32_t* group, uint32_t* counts, int64_t capacity, int64_t* run_offsets, uint32_t* areas,
+                                 int32_t* bboxes_xywh)
+{
+    return guarded([&] {
+        std::string err;
+        const tiles::MergeArgs a = merge_args(detections, masks, tiles, n_tiles, rows, mask_size, heights, widths, n_images, model_h, model_w, threshold,
+                                              metric, link_threshold, max_out, detections_src, source, n_kept, counts, capacity, run_offsets, areas,
+                                              bboxes_xywh, n_parts, group);
+        const int st = tiles::check_merge(a, "unite_tiles", &err, "link_threshold");
+        if (st != MRCNN_OK) fail(st, "%s", err.c_str());
+        require_gpu();
+        TilesRun r(a, memspace, "unite_tiles", true);
+        tiles_unite_forward(r.s, r.m);                           // link bits, components, the union planes counted
+        r.deliver();
+        tiles_unite_write_forward(r.s, r.m);
+        r.done();
     });
 }

@@ -15,6 +15,7 @@
 #include "device_math.h"
 #include "kernels.h"
 #include "paste_device.h"
+#include "rle_device.h"
 
 namespace mrcnn {
 
@@ -433,94 +434,15 @@ void paste_masks_source_forward(hipStream_t s, const float* det, const float* ma
 // ------------------------------------------------------------------------------------------------
 static_assert(sizeof(RleSeg) == 8, "RleSeg is two uint32");
 
-__device__ __forceinline__ bool rle_bit(const int4 bx, const float* __restrict__ m, int S, int h, int x, int y, float thr)
-{
-    if (y < 0) { --x; y = h - 1; } else if (y >= h) { ++x; y = 0; }        // the position before a column's first / behind its last pixel
-    if (x < bx.y || x >= bx.w || y < bx.x || y >= bx.z) return false;
-    const PasteTap ty = paste_tap(y, bx.x, (float)S / (float)(bx.z - bx.x), S);
-    const PasteTap tx = paste_tap(x, bx.y, (float)S / (float)(bx.w - bx.y), S);
-    const float *ra = m + ty.a * S, *rb = m + ty.b * S;
-    return paste_lerp(ra[tx.a], ra[tx.b], rb[tx.a], rb[tx.b], tx.f, ty.f) >= thr;
-}
-
-// One chunk: lane l stands for position p0 + l (p0 may be "-1" for the chunk that starts the plane: lane 0 is never a candidate).
-struct RleChunk {
-    unsigned long long set;     // candidate lanes whose pixel is 1 (every pixel of the box is a candidate of exactly one chunk)
-    unsigned long long trans;   // candidate lanes that are transitions
-    uint32_t p0;
-    int x, y0;                  // lane l: column x, row y0 + l
-};
-struct RleWalk {
-    int4 bx; const float* m; int S, h, w, nchunk; long items; float thr;
-};
-__device__ __forceinline__ RleWalk rle_walk(const ImageGeom* __restrict__ tab, const int4* __restrict__ boxes, const float* __restrict__ masks,
-                                            int rows, int S, float thr, int inst)
-{
-    RleWalk k;
-    const ImageGeom im = tab[inst / rows];
-    k.bx = boxes[inst]; k.m = masks + (size_t)inst * S * S; k.S = S; k.h = im.h; k.w = im.w; k.thr = thr;
-    k.nchunk = (k.bx.z - k.bx.x + 1 + 62) / 63;                            // candidates per column: rows y1 .. y2 (y2 = the position behind)
-    k.items = (long)(k.bx.w - k.bx.y) * k.nchunk;                          // (an empty box is (0,0,0,0): no items)
-    return k;
-}
-__device__ __forceinline__ RleChunk rle_chunk(const RleWalk& k, long item, int lane)
-{
-    RleChunk c;
-    c.x = k.bx.y + (int)(item / k.nchunk);
-    c.y0 = k.bx.x - 1 + 63 * (int)(item % k.nchunk);
-    const int y = c.y0 + lane;
-    // the last candidate of this column: the position behind the box's last row — unless that position is the first candidate of the
-    // next column (a box of the plane's full height) or lies behind the plane's end (no transition there: the last run just ends)
-    int hi = k.bx.z;
-    if (k.bx.z == k.h && ((k.bx.x == 0 && c.x < k.bx.w - 1) || c.x == k.w - 1)) hi = k.h - 1;
-    const bool valid = y <= hi;
-    const bool cur = valid && rle_bit(k.bx, k.m, k.S, k.h, c.x, y, k.thr);
-    const unsigned long long bal = __ballot(cur);
-    const unsigned long long cand = __ballot(valid && lane >= 1);
-    c.set = bal & cand;
-    c.trans = (bal ^ (bal << 1)) & cand;
-    c.p0 = (uint32_t)c.x * (uint32_t)k.h + (uint32_t)c.y0;
-    return c;
-}
+// (rle_bit, the chunk and the two passes over a plane — the walk itself — live in rle_device.h, shared with kernels_tiles.hip)
 
 __global__ __launch_bounds__(1024) void k_rle_count(const ImageGeom* __restrict__ tab, const int4* __restrict__ boxes, const float* __restrict__ masks,
                                                     int rows, int S, float thr, RleSeg* __restrict__ segs, uint32_t* __restrict__ nruns,
                                                     uint32_t* __restrict__ areas, int32_t* __restrict__ bboxes)
 {
-    const int inst = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int inst = blockIdx.x;
     const RleWalk k = rle_walk(tab, boxes, masks, rows, S, thr, inst);
-    uint32_t count = 0, last = 0, area = 0;
-    int xmin = 0x7fffffff, ymin = 0x7fffffff, xmax = -1, ymax = -1;
-    for (long it = k.items * wave / RLE_SEGS, end = k.items * (wave + 1) / RLE_SEGS; it < end; ++it) {
-        const RleChunk c = rle_chunk(k, it, lane);
-        if (c.trans) { count += __popcll(c.trans); last = c.p0 + (63 - __clzll(c.trans)); }
-        if (c.set) {
-            area += __popcll(c.set);
-            xmin = min(xmin, c.x); xmax = max(xmax, c.x);
-            ymin = min(ymin, c.y0 + (__ffsll(c.set) - 1)); ymax = max(ymax, c.y0 + 63 - __clzll(c.set));
-        }
-    }
-    __shared__ uint32_t s_count[RLE_SEGS], s_area[RLE_SEGS];
-    __shared__ int s_box[RLE_SEGS][4];
-    if (lane == 0) {
-        segs[(size_t)inst * RLE_SEGS + wave] = RleSeg{count, last};
-        s_count[wave] = count; s_area[wave] = area;
-        s_box[wave][0] = xmin; s_box[wave][1] = ymin; s_box[wave][2] = xmax; s_box[wave][3] = ymax;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int s = 1; s < RLE_SEGS; ++s) {
-            count += s_count[s]; area += s_area[s];
-            xmin = min(xmin, s_box[s][0]); ymin = min(ymin, s_box[s][1]); xmax = max(xmax, s_box[s][2]); ymax = max(ymax, s_box[s][3]);
-        }
-        nruns[inst] = count + 1;
-        if (areas) areas[inst] = area;
-        if (bboxes) {
-            int* o = bboxes + (size_t)inst * 4;
-            const bool any = area > 0;
-            o[0] = any ? xmin : 0; o[1] = any ? ymin : 0; o[2] = any ? xmax - xmin + 1 : 0; o[3] = any ? ymax - ymin + 1 : 0;
-        }
-    }
+    rle_count_plane(k, RleOneMask{k}, (size_t)inst, segs, nruns, areas, bboxes);
 }
 
 // run_offsets[k] = Σ nruns[0 .. k), run_offsets[total] = the sum; one block of 1024 threads, 1024 instances per step
@@ -550,29 +472,9 @@ __global__ __launch_bounds__(1024) void k_rle_write(const ImageGeom* __restrict_
                                                     int rows, int S, float thr, const RleSeg* __restrict__ segs,
                                                     const long long* __restrict__ run_offsets, uint32_t* __restrict__ counts)
 {
-    const int inst = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int inst = blockIdx.x;
     const RleWalk k = rle_walk(tab, boxes, masks, rows, S, thr, inst);
-    long long off = run_offsets[inst];
-    const long long stop = run_offsets[inst + 1];                          // nothing of this instance is stored at or behind it
-    uint32_t prev = 0;                                                     // the transition before this wave's first; 0 = the plane's start
-    for (int s = 0; s < wave; ++s) {
-        const RleSeg g = segs[(size_t)inst * RLE_SEGS + s];
-        if (g.count) { off += g.count; prev = g.last; }
-    }
-    for (long it = k.items * wave / RLE_SEGS, end = k.items * (wave + 1) / RLE_SEGS; it < end; ++it) {
-        const RleChunk c = rle_chunk(k, it, lane);
-        if (!c.trans) continue;
-        if ((c.trans >> lane) & 1ull) {
-            const unsigned long long below = c.trans & ((1ull << lane) - 1ull);
-            const long long at = off + __popcll(below);
-            // the transition before mine: the nearest one below me in this chunk (lanes are consecutive positions), else `prev`
-            const uint32_t run = below ? (uint32_t)(lane - (63 - __clzll(below))) : c.p0 + (uint32_t)lane - prev;
-            if (at < stop) counts[at] = run;
-        }
-        off += __popcll(c.trans);
-        prev = c.p0 + (63 - __clzll(c.trans));
-    }
-    if (wave == RLE_SEGS - 1 && lane == 0 && off < stop) counts[off] = (uint32_t)k.h * (uint32_t)k.w - prev;
+    rle_write_plane(k, RleOneMask{k}, (size_t)inst, segs, run_offsets[inst], run_offsets[inst + 1], counts);
 }
 
 void masks_rle_count_forward(hipStream_t s, const float* det, const float* masks, const ImageGeom* tab, int batch, int rows, int S, int H, int W,

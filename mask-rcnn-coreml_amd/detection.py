@@ -180,7 +180,8 @@ def _tile_table(tiles):
 _METRICS = {"iou": _lib.MATCH_IOU, "ios": _lib.MATCH_IOS}
 
 
-def _merge_tiles(host_definition, detections, masks, tiles, sizes, model_h, model_w, threshold, metric, match_threshold, max_out):
+def _merge_tiles(host_definition, detections, masks, tiles, sizes, model_h, model_w, threshold, metric, match_threshold, max_out, unite=False):
+    name = "unite_tiles" if unite else "merge_tiles"
     on_host = isinstance(detections, np.ndarray)
     if on_host:
         det = np.ascontiguousarray(detections, dtype=np.float32)
@@ -188,14 +189,14 @@ def _merge_tiles(host_definition, detections, masks, tiles, sizes, model_h, mode
     else:
         import torch
         det, m = detections, masks
-        assert not host_definition, "merge_tiles_host takes numpy arrays"
+        assert not host_definition, f"{name}_host takes numpy arrays"
         assert det.is_cuda and m.is_cuda and det.dtype == torch.float32 and m.dtype == torch.float32 and det.is_contiguous() and m.is_contiguous()
     tab = _tile_table(tiles)
     T, rows = int(det.shape[0]), int(det.shape[1])
     if tab.shape[0] != T or m.shape[0] != T or m.shape[1] != rows or det.shape[2] != 6:
-        raise ValueError("merge_tiles: detections (T,rows,6), masks (T,rows,S,S) and T tiles expected")
+        raise ValueError(f"{name}: detections (T,rows,6), masks (T,rows,S,S) and T tiles expected")
     if metric not in _METRICS:
-        raise ValueError(f"merge_tiles: metric {metric!r} is neither 'iou' nor 'ios'")
+        raise ValueError(f"{name}: metric {metric!r} is neither 'iou' nor 'ios'")
     B = len(sizes)
     hs = np.array([int(s[0]) for s in sizes], dtype=np.int32)
     ws = np.array([int(s[1]) for s in sizes], dtype=np.int32)
@@ -207,6 +208,7 @@ def _merge_tiles(host_definition, detections, masks, tiles, sizes, model_h, mode
     if on_host:
         det_src, source, n_kept = np.zeros((B, max(0, max_out), 6), np.float32), np.zeros((B, max(0, max_out)), np.int32), np.zeros(B, np.int32)
         areas, bboxes = np.zeros((B, max(0, max_out)), np.uint32), np.zeros((B, max(0, max_out), 4), np.int32)
+        n_parts, group = np.zeros((B, max(0, max_out)), np.int32), np.zeros((T, rows), np.int32)
         ptr = lambda a: a.ctypes.data
         new_counts = lambda k: np.empty(max(1, k), np.uint32)
         offs_buf = offsets
@@ -214,6 +216,7 @@ def _merge_tiles(host_definition, detections, masks, tiles, sizes, model_h, mode
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=det.device)
         det_src, source, n_kept = z((B, max(0, max_out), 6), torch.float32), z((B, max(0, max_out)), torch.int32), z((B,), torch.int32)
         areas, bboxes = z((B, max(0, max_out)), torch.int32), z((B, max(0, max_out), 4), torch.int32)
+        n_parts, group = z((B, max(0, max_out)), torch.int32), z((T, rows), torch.int32)
         ptr = lambda a: a.data_ptr()
         new_counts = lambda k: torch.empty(max(1, k), dtype=torch.int32, device=det.device)
         offs_buf = z((slots + 1,), torch.int64)
@@ -222,10 +225,11 @@ def _merge_tiles(host_definition, detections, masks, tiles, sizes, model_h, mode
 
     def call(capacity):
         counts = new_counts(capacity)
-        tail = (ptr(det_src), ptr(source), ptr(n_kept), ptr(counts), capacity, ptr(offs_buf), ptr(areas), ptr(bboxes))
+        parts = (ptr(n_parts), ptr(group)) if unite else ()
+        tail = (ptr(det_src), ptr(source), ptr(n_kept), *parts, ptr(counts), capacity, ptr(offs_buf), ptr(areas), ptr(bboxes))
         if host_definition:
-            return _lib.lib().mrcnn_merge_tiles_host(*head, *tail), counts
-        return _lib.lib().mrcnn_merge_tiles(*head, _lib.HOST if on_host else _lib.DEVICE, *tail), counts
+            return getattr(_lib.lib(), f"mrcnn_{name}_host")(*head, *tail), counts
+        return getattr(_lib.lib(), f"mrcnn_{name}")(*head, _lib.HOST if on_host else _lib.DEVICE, *tail), counts
     capacity = int(max(1, max_out) * (2 * ws.astype(np.int64) + 2).sum())      # as masks_rle_source sizes its first attempt
     st, counts = call(capacity)
     if not on_host:
@@ -239,6 +243,8 @@ def _merge_tiles(host_definition, detections, masks, tiles, sizes, model_h, mode
     host = counts[:used] if on_host else counts[:used].cpu().numpy().view(np.uint32)
     rles = [[{"size": [int(hs[b]), int(ws[b])], "counts": host[int(offsets[b * max_out + i]):int(offsets[b * max_out + i + 1])]}
              for i in range(max_out)] for b in range(B)]
+    if unite:
+        return det_src, source, n_kept, rles, areas, bboxes, n_parts, group
     return det_src, source, n_kept, rles, areas, bboxes
 
 
@@ -259,6 +265,26 @@ def merge_tiles_host(detections, masks, tiles, sizes, model_h: int, model_w: int
     """The definition of merge_tiles: the same arguments (numpy) and results from the sequential host code
     (``mrcnn_merge_tiles_host``), no GPU."""
     return _merge_tiles(True, detections, masks, tiles, sizes, model_h, model_w, threshold, metric, match_threshold, max_out)
+
+
+def unite_tiles(detections, masks, tiles, sizes, model_h: int, model_w: int, threshold: float = 0.5, metric: str = "iou",
+                link_threshold: float = 0.5, max_out=None):
+    """merge_tiles' arguments; the cut parts of an object that no window holds whole, and its duplicates, united into one mask on the
+    GPU (``mrcnn_unite_tiles``; the header states the rule).  Candidates of different tiles and one class are LINKED if their planes
+    agree (metric "iou" or "ios" >= link_threshold) inside the rectangle both windows see; every connected component of the links
+    becomes one output: the OR of its members' planes, the row of the hull of their boxes, class and score of its best member.
+    Returns (det_src, source — the best member's candidate index —, n_kept — the components before the cap —, rles, areas, bboxes,
+    n_parts (B, max_out) — the members per output —, group (T, rows) — per candidate its output's index in its image, -1 if not
+    eligible).  ``rles[b][j]`` go to coco_results.coco_results and coco_eval.score_batch with det_src as they are; a united mask is
+    no pasted S x S mask any more, so paste_masks_source and the renderers cannot rebuild it from det_src."""
+    return _merge_tiles(False, detections, masks, tiles, sizes, model_h, model_w, threshold, metric, link_threshold, max_out, unite=True)
+
+
+def unite_tiles_host(detections, masks, tiles, sizes, model_h: int, model_w: int, threshold: float = 0.5, metric: str = "iou",
+                     link_threshold: float = 0.5, max_out=None):
+    """The definition of unite_tiles: the same arguments (numpy) and results from the sequential host code
+    (``mrcnn_unite_tiles_host``), no GPU."""
+    return _merge_tiles(True, detections, masks, tiles, sizes, model_h, model_w, threshold, metric, link_threshold, max_out, unite=True)
 
 
 def _ragged_layout(hs, ws, unit):

@@ -186,18 +186,23 @@ class MaskRCNN(_Model):
             _lib.check(_lib.lib().mrcnn_maskrcnn_predict_tiles(self._h, table, B, tp, T, _lib.DEVICE, det.data_ptr(), mask.data_ptr()))
         return det, mask
 
-    def predict_tiled(self, images, tile=None, overlap=(64, 64), metric="ios", match_threshold=0.5, max_out=None, threshold=0.5):
+    def predict_tiled(self, images, tile=None, overlap=(64, 64), metric="ios", match_threshold=0.5, max_out=None, threshold=0.5,
+                      unite=False, link_threshold=0.5):
         """Large images as overlapping windows at native resolution: detection.tile_plan per image (tile = None: the model's input
         size), predict_tiles, detection.merge_tiles.  Returns (det_src, source, n_kept, rles) in the frame of the images, in the
-        form coco_results.coco_results and coco_eval.score_batch take.  An object is found whole only if some window holds it
-        whole: choose the overlap at least as large as the largest object of interest."""
-        from .detection import merge_tiles, tile_plan
+        form coco_results.coco_results and coco_eval.score_batch take.  By default an object is found whole only if some window
+        holds it whole: choose the overlap at least as large as the largest object of interest.  unite=True replaces the third step
+        by detection.unite_tiles(metric, link_threshold): the cut parts of an object larger than the overlap, and its duplicates,
+        become one mask (match_threshold is not used then)."""
+        from .detection import merge_tiles, tile_plan, unite_tiles
         images = list(images)
         H, W = self.image_height, self.image_width
         tile = (H, W) if tile is None else tile
         sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
         tiles = np.concatenate([tile_plan(h, w, tile, overlap, b) for b, (h, w) in enumerate(sizes)])
         det, mask = self.predict_tiles(images, tiles)
+        if unite:
+            return unite_tiles(det, mask, tiles, sizes, H, W, threshold, metric, link_threshold, max_out)[:4]
         return merge_tiles(det, mask, tiles, sizes, H, W, threshold, metric, match_threshold, max_out)[:4]
 
     def predict_jpegs(self, files, entropy="host"):
