@@ -695,7 +695,7 @@ MRCNN_API int mrcnn_render_detections_source(const mrcnn_image* images, const fl
  *                                             max_out where the output was truncated), -1 if not eligible; may be NULL
  *   A component of one member is, bit for bit, what mrcnn_merge_tiles outputs for that candidate when kept.  link_threshold > 0;
  *   limits, errors and the capacity protocol are mrcnn_merge_tiles'.  A united mask is no longer a pasted S x S mask:
- *   mrcnn_paste_masks_source and the renderers cannot reproduce it from detections_src; the RLE is the result.  Objects are not united
+ *   mrcnn_rle_decode, mrcnn_instance_map_rle and mrcnn_render_detections_rle (below) draw it from its RLE.  Objects are not united
  *   across images.
  * examples/maskrcnn_predict_tiled.c is the whole flow as a C99 host. */
 typedef struct { int32_t image, y0, x0, height, width; } mrcnn_tile;   /* a window of images[image] */
@@ -725,6 +725,44 @@ MRCNN_API int mrcnn_unite_tiles_host(const float* detections, const float* masks
                                      float threshold, int metric, double link_threshold, int max_out, float* detections_src,
                                      int32_t* source, int32_t* n_kept, int32_t* n_parts, int32_t* group, uint32_t* counts,
                                      int64_t capacity, int64_t* run_offsets, uint32_t* areas, int32_t* bboxes_xywh);
+
+/* Drawing run-length masks: dense planes, the instance-id map and the rendered overlay from an RLE SET in the layout mrcnn_masks_rle_source,
+ * mrcnn_merge_tiles, mrcnn_unite_tiles and mrcnn_rle_from_polygons_batch write: counts (uint32, column-major runs, position p = x*h + y,
+ * counts[0] = the leading zeros), run_offsets (int64, n_images*slots + 1 entries); RLE k = b*slots + i belongs to image b, which is
+ * heights[b] x widths[b].  Zero-length runs are legal anywhere.  An RLE whose runs do not sum to exactly h_b*w_b makes the call return
+ * MRCNN_ERR_SHAPE (the message names k) with nothing written to the outputs.  P_k is the h_b x w_b {0,1} plane RLE k encodes.
+ *   mrcnn_rle_decode             out + out_offsets[b] + i*h_b*w_b = P_k, row-major uint8 {0,1}: the layout mrcnn_paste_masks_source writes,
+ *                                so mrcnn_png_encode_batch(MRCNN_PNG_GREY8) takes it unchanged.  A subset of one image: run_offsets + first
+ *                                with a smaller slots.
+ *   mrcnn_instance_map_rle       box_i = the pixel box of row i of detections_src (n_images, slots, 6) in its image's own frame: round-half-
+ *                                even of y*(h_b-1), + 1 on the exclusive far edge.  Row i is DRAWN if score > min_score, score > 0 and
+ *                                box_i is not empty.  map[y,x] (int16) = the lowest drawn i with P_k[y,x] = 1, else -1;
+ *                                visible_areas[b,i] (may be NULL) = the pixels i owns.  slots <= 32767.  The box only decides whether a row
+ *                                is drawn: set pixels outside it count (a united mask's hull box or a user's box need not be tight).
+ *   mrcnn_render_detections_rle  images[b] drawn over: stroke ring, blend, palette i % 4 and the ranges of alpha and stroke in the words of
+ *                                mrcnn_render_detections_source, with P_k in place of the pasted plane.
+ * Conventions are mrcnn_instance_map_source's: memspace holds for every data pointer (run_offsets and the images' rgb pointers too); sizes,
+ * offsets and the image table are host arrays; offsets are byte offsets, multiples of 16, the images' ranges must not overlap and bytes no
+ * image covers are left untouched.  Errors: null pointer, bad output offsets -> MRCNN_ERR_INVALID; a side outside 1..32767, slots > 32767
+ * (map, render), alpha or stroke out of range, decreasing run_offsets -> MRCNN_ERR_SHAPE; argument errors are answered before a device is
+ * looked for; no gfx950 device -> MRCNN_ERR_HIP from the device entries (no CPU fallback).  The _host entries are the definition —
+ * sequential plain C++, no GPU, host pointers — which the device entries equal byte for byte.  examples/maskrcnn_render_tiled.c. */
+MRCNN_API int mrcnn_rle_decode(const uint32_t* counts, const int64_t* run_offsets, int n_images, int slots, const int32_t* heights,
+                               const int32_t* widths, int memspace, uint8_t* out, const int64_t* out_offsets);
+MRCNN_API int mrcnn_rle_decode_host(const uint32_t* counts, const int64_t* run_offsets, int n_images, int slots, const int32_t* heights,
+                                    const int32_t* widths, uint8_t* out, const int64_t* out_offsets);
+MRCNN_API int mrcnn_instance_map_rle(const float* detections_src, const uint32_t* counts, const int64_t* run_offsets, int n_images, int slots,
+                                     const int32_t* heights, const int32_t* widths, float min_score, int memspace, int16_t* map,
+                                     const int64_t* map_offsets, uint32_t* visible_areas);
+MRCNN_API int mrcnn_instance_map_rle_host(const float* detections_src, const uint32_t* counts, const int64_t* run_offsets, int n_images,
+                                          int slots, const int32_t* heights, const int32_t* widths, float min_score, int16_t* map,
+                                          const int64_t* map_offsets, uint32_t* visible_areas);
+MRCNN_API int mrcnn_render_detections_rle(const mrcnn_image* images, const float* detections_src, const uint32_t* counts,
+                                          const int64_t* run_offsets, int n_images, int slots, float min_score, int alpha, int stroke,
+                                          int memspace, uint8_t* out_rgb, const int64_t* out_offsets);
+MRCNN_API int mrcnn_render_detections_rle_host(const mrcnn_image* images, const float* detections_src, const uint32_t* counts,
+                                               const int64_t* run_offsets, int n_images, int slots, float min_score, int alpha, int stroke,
+                                               uint8_t* out_rgb, const int64_t* out_offsets);
 
 /* Host only, no GPU: COCO's compressed string of one RLE (pycocotools rleToString / rleFrString), not NUL-terminated.  *length / *n is
  * always the size needed; with out / counts = NULL the call only measures, a buffer that is too small gives MRCNN_ERR_SHAPE. */

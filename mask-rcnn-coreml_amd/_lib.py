@@ -46,6 +46,8 @@ EXPORTED_SYMBOLS = [
     "mrcnn_png_encode_host", "mrcnn_png_encode_batch",
     "mrcnn_tile_plan", "mrcnn_maskrcnn_predict_tiles", "mrcnn_merge_tiles", "mrcnn_merge_tiles_host",
     "mrcnn_unite_tiles", "mrcnn_unite_tiles_host",
+    "mrcnn_rle_decode", "mrcnn_rle_decode_host", "mrcnn_instance_map_rle", "mrcnn_instance_map_rle_host",
+    "mrcnn_render_detections_rle", "mrcnn_render_detections_rle_host",
 ]
 # declared in include/maskrcnn_hip_test.h (test / measurement entry points of the same library)
 TEST_SYMBOLS = [
@@ -174,6 +176,13 @@ def lib():
     L.mrcnn_merge_tiles_host.argtypes = _merge + [vp, vp, vp, vp, C.c_int64, vp, vp, vp]
     L.mrcnn_unite_tiles.argtypes = _merge + [C.c_int, vp, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp]
     L.mrcnn_unite_tiles_host.argtypes = _merge + [vp, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp]
+    _rles = [vp, vp, C.c_int, C.c_int]                          # counts, run_offsets, n_images, slots
+    L.mrcnn_rle_decode.argtypes = _rles + [vp, vp, C.c_int, vp, vp]
+    L.mrcnn_rle_decode_host.argtypes = _rles + [vp, vp, vp, vp]
+    L.mrcnn_instance_map_rle.argtypes = [vp] + _rles + [vp, vp, C.c_float, C.c_int, vp, vp, vp]
+    L.mrcnn_instance_map_rle_host.argtypes = [vp] + _rles + [vp, vp, C.c_float, vp, vp, vp]
+    L.mrcnn_render_detections_rle.argtypes = [C.POINTER(Image), vp] + _rles + [C.c_float, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.mrcnn_render_detections_rle_host.argtypes = [C.POINTER(Image), vp] + _rles + [C.c_float, C.c_int, C.c_int, vp, vp]
     L.mrcnn_rle_to_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_from_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_iou.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int64]

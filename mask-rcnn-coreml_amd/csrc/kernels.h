@@ -493,8 +493,30 @@ using IouGroup = mrcnn_iou_group;          // one image: detections [d0, d1) x g
 using MatchGroup = mrcnn_match_group;      // one (image, category): ranges of the flat detection / ground-truth lists
 // Per RLE k (counts[run_offsets[k] .. run_offsets[k+1])): pre_b = exclusive prefix of the counts, pre_o = exclusive prefix of the odd
 // (ones) runs, both indexed like counts (either may be nullptr); totals[k] = the pixels, areas[k] = the set pixels.  One block per RLE.
+// extent[k] (may be nullptr) = the positions of the first and the last set pixel, (0xffffffff, 0) for an empty mask.  kernels_rle_prefix.hip.
 void rle_prefix_forward(hipStream_t s, const uint32_t* counts, const long long* run_offsets, long n_rle, uint32_t* pre_b, uint32_t* pre_o,
-                        unsigned long long* totals, uint32_t* areas);
+                        unsigned long long* totals, uint32_t* areas, uint2* extent = nullptr);
+
+// ================================================================================================
+// Drawing run-length masks (kernels_rle_draw.hip): planes, instance maps and overlays of a ragged batch from an RLE set.
+// ================================================================================================
+struct RleDrawImage { int h, w; long long offset; };              // one image: its size and the byte offset of its output
+// One RLE after rle_draw_prepare: its runs, the positions of its first and last set pixel, its row's pixel box, whether it is drawn
+struct RleDrawRec { long long r0; int nruns; uint32_t first, last; int y1, x1, y2, x2; int drawn; };
+struct RleDrawJob {
+    const RleDrawRec* rec;            // n_images * slots
+    const uint32_t* pre_b;            // rle_prefix_forward's B, indexed like counts
+    const RleDrawImage* tab;          // n_images
+    int n_images, slots;
+    int max_h, max_w;                 // the largest sides of the batch: the grid
+};
+// rec[k] from the prefix pass and (det != nullptr) the detection rows; det == nullptr draws every RLE (the decode).  *bad (device, one
+// word) = the lowest k whose total is not its plane's h*w, ~0 if all are right: the caller reads it back before it draws.
+void rle_draw_prepare(hipStream_t s, const long long* run_offsets, const unsigned long long* totals, const uint2* extent, const float* det,
+                      float min_score, const RleDrawJob& job, RleDrawRec* rec, unsigned long long* bad);
+void rle_decode_forward(hipStream_t s, const RleDrawJob& job, uint8_t* out);
+void instance_map_rle_forward(hipStream_t s, const RleDrawJob& job, int16_t* map, uint32_t* visible);
+void render_detections_rle_forward(hipStream_t s, const RleDrawJob& job, const uint8_t* const* srcs, int alpha, int stroke, uint8_t* out);
 // inter / iou of every pair of every group.  block_starts (n_groups + 1, device): prefix of ceil(nd / 4) * ng per group = the grid.
 // The caller has checked that the two RLEs of every pair have the same total.  inter / iou may be nullptr.
 void rle_iou_forward(hipStream_t s, const uint32_t* d_b, const long long* d_off, const unsigned long long* d_total, const uint32_t* d_area,

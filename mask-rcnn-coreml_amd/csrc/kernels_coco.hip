@@ -5,7 +5,8 @@
 // An RLE is a range of `counts` (uint32 run lengths, column-major pixels, counts[0] = leading zeros, then ones / zeros alternating):
 // RLE k owns counts[run_offsets[k] .. run_offsets[k+1]) — the layout mrcnn_masks_rle_source writes.
 //
-// Intersection without walking the two run lists in lockstep.  With B[j] the exclusive prefix sum of an RLE's counts (the pixel
+// Intersection without walking the two run lists in lockstep (the tables: k_rle_prefix, kernels_rle_prefix.hip, shared with the RLE
+// drawing kernels).  With B[j] the exclusive prefix sum of an RLE's counts (the pixel
 // position where run j starts) and O[j] the set pixels before run j, the set pixels before position p are
 //     G(p) = O[j] + (j odd ? p - B[j] : 0),   j = the last run with B[j] <= p            (a binary search in B)
 // and   inter(d, g) = sum over d's ones-runs [s, e) of G_g(e) - G_g(s).   Integer arithmetic: exact in any order of summation.
@@ -27,47 +28,6 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 #pragma unroll
     for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
     return v;
-}
-
-// One block per RLE: B (exclusive prefix of the counts) and O (exclusive prefix of the odd runs) into `pre` (either may be nullptr: only
-// the sums are wanted), the pixel count into totals[k] and the set pixels into areas[k].  Runs are taken 256 at a time with a carry.
-__global__ __launch_bounds__(256) void k_rle_prefix(const uint32_t* __restrict__ counts, const long long* __restrict__ run_offsets, long n_rle,
-                                                    uint32_t* __restrict__ pre_b, uint32_t* __restrict__ pre_o,
-                                                    unsigned long long* __restrict__ totals, uint32_t* __restrict__ areas)
-{
-    const long k = blockIdx.x;
-    if (k >= n_rle) return;
-    const long long r0 = run_offsets[k], r1 = run_offsets[k + 1];
-    __shared__ unsigned long long sh_b[256 / WAVE];
-    __shared__ unsigned long long sh_o[256 / WAVE];
-    const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
-    unsigned long long carry_b = 0, carry_o = 0;
-    for (long long base = r0; base < r1; base += 256) {
-        const long long j = base + threadIdx.x;
-        const unsigned long long c = j < r1 ? counts[j] : 0u;
-        const unsigned long long o = ((j - r0) & 1) ? c : 0u;
-        unsigned long long sb = c, so = o;                      // inclusive scan inside the wave
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) {
-            const unsigned long long tb = __shfl_up(sb, d, WAVE), to = __shfl_up(so, d, WAVE);
-            if (lane >= d) { sb += tb; so += to; }
-        }
-        if (lane == WAVE - 1) { sh_b[wave] = sb; sh_o[wave] = so; }
-        __syncthreads();
-        unsigned long long wb = 0, wo = 0, all_b = 0, all_o = 0;
-#pragma unroll
-        for (int w = 0; w < 256 / WAVE; ++w) {
-            if (w < wave) { wb += sh_b[w]; wo += sh_o[w]; }
-            all_b += sh_b[w]; all_o += sh_o[w];
-        }
-        if (j < r1) {
-            if (pre_b) pre_b[j] = (uint32_t)(carry_b + wb + sb - c);
-            if (pre_o) pre_o[j] = (uint32_t)(carry_o + wo + so - o);
-        }
-        carry_b += all_b; carry_o += all_o;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { totals[k] = carry_b; areas[k] = (uint32_t)carry_o; }
 }
 
 // set pixels of the ground truth before position p: tb / to are its B / O tables (LDS or global), n its number of runs (>= 1)
@@ -594,14 +554,6 @@ void poly_write_forward(hipStream_t s, const PolyAnn* anns, long n_anns, const l
 {
     if (n_anns <= 0) return;
     hipLaunchKernelGGL(k_poly_write, dim3((unsigned)n_anns), dim3(POLY_BLOCK), 0, s, anns, tog_off, bnd, nb, run_offsets, counts);
-    HIP_CHECK(hipGetLastError());
-}
-
-void rle_prefix_forward(hipStream_t s, const uint32_t* counts, const long long* run_offsets, long n_rle, uint32_t* pre_b, uint32_t* pre_o,
-                        unsigned long long* totals, uint32_t* areas)
-{
-    if (n_rle <= 0) return;
-    hipLaunchKernelGGL(k_rle_prefix, dim3((unsigned)n_rle), dim3(256), 0, s, counts, run_offsets, n_rle, pre_b, pre_o, totals, areas);
     HIP_CHECK(hipGetLastError());
 }
 

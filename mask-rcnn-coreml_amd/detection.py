@@ -276,7 +276,7 @@ def unite_tiles(detections, masks, tiles, sizes, model_h: int, model_w: int, thr
     Returns (det_src, source — the best member's candidate index —, n_kept — the components before the cap —, rles, areas, bboxes,
     n_parts (B, max_out) — the members per output —, group (T, rows) — per candidate its output's index in its image, -1 if not
     eligible).  ``rles[b][j]`` go to coco_results.coco_results and coco_eval.score_batch with det_src as they are; a united mask is
-    no pasted S x S mask any more, so paste_masks_source and the renderers cannot rebuild it from det_src."""
+    no pasted S x S mask any more: rle_decode_planes, instance_map_rle and render_detections_rle draw it from its RLE."""
     return _merge_tiles(False, detections, masks, tiles, sizes, model_h, model_w, threshold, metric, link_threshold, max_out, unite=True)
 
 
@@ -370,3 +370,191 @@ def render_detections_source(images, detections, masks, model_h: int, model_w: i
                                                          C.c_float(min_score), int(alpha), int(stroke), _lib.HOST if on_host else _lib.DEVICE,
                                                          None, ptr(out), offs.ctypes.data))
     return [out[int(offs[b]):int(offs[b] + nbytes[b])].reshape(int(hs[b]), int(ws[b]), 3) for b in range(B)]
+
+
+# ---- drawing run-length masks (mrcnn_rle_decode, mrcnn_instance_map_rle, mrcnn_render_detections_rle) ------------------------------------
+def _rle_set(name, rles, sizes, device):
+    """An RLE set for the library: (counts, run_offsets, B, slots, hs, ws).  ``rles`` is either what merge_tiles, unite_tiles and
+    masks_rle_source return — rles[b][i] = {"size": [h_b, w_b], "counts": uint32 runs}, the same number of slots for every image —
+    or a (counts, run_offsets) pair holding B*slots RLEs, numpy arrays or CUDA tensors, which then needs ``sizes`` = [(h_b, w_b)].
+    device = None: numpy arrays (a pair of tensors is copied to the host); else CUDA tensors on that device — a pair of CUDA tensors
+    is used in place, anything else is uploaded (a few MB)."""
+    if isinstance(rles, tuple) and len(rles) == 2 and not isinstance(rles[0], (list, tuple, dict)):
+        counts, offs = rles
+        if sizes is None:
+            raise ValueError(f"{name}: a (counts, run_offsets) pair needs sizes = [(h_b, w_b)]")
+        B = len(sizes)
+        n = int(offs.shape[0]) - 1
+        slots = n // B if B else 0
+        if n != B * slots or n < 0:
+            raise ValueError(f"{name}: run_offsets holds {n} RLEs, not a multiple of the {B} images")
+        if not isinstance(counts, np.ndarray):
+            import torch
+            assert counts.is_cuda and offs.is_cuda and counts.element_size() == 4 and offs.dtype == torch.int64 and counts.is_contiguous() and offs.is_contiguous()
+            if device is None:
+                counts, offs = counts.cpu().numpy().view(np.uint32), offs.cpu().numpy()
+        else:
+            counts, offs = np.ascontiguousarray(counts, dtype=np.uint32), np.ascontiguousarray(offs, dtype=np.int64)
+    else:
+        rows = [list(r) for r in rles]
+        B = len(rows)
+        slots = len(rows[0]) if B else 0
+        if any(len(r) != slots for r in rows):
+            raise ValueError(f"{name}: every image needs the same number of RLEs (pad with empty masks)")
+        if sizes is None:
+            if B and not slots:
+                raise ValueError(f"{name}: images without RLEs need sizes = [(h_b, w_b)]")
+            sizes = [r[0]["size"] for r in rows]
+        if len(sizes) != B:
+            raise ValueError(f"{name}: {len(sizes)} sizes for {B} images")
+        for b, r in enumerate(rows):
+            for i, e in enumerate(r):
+                if [int(e["size"][0]), int(e["size"][1])] != [int(sizes[b][0]), int(sizes[b][1])]:
+                    raise ValueError(f"{name}: RLE {i} of image {b} has size {list(e['size'])}, its image {list(sizes[b])}")
+        runs = [np.ascontiguousarray(e["counts"], dtype=np.uint32).ravel() for r in rows for e in r]
+        counts = np.concatenate(runs) if runs else np.zeros(0, np.uint32)
+        offs = np.concatenate(([0], np.cumsum([len(c) for c in runs]))).astype(np.int64)
+    if device is not None and isinstance(counts, np.ndarray):
+        import torch
+        counts = torch.from_numpy(np.ascontiguousarray(counts).view(np.int32).copy()).to(device)
+        offs = torch.from_numpy(offs.copy()).to(device)
+    if isinstance(counts, np.ndarray) and counts.size == 0:
+        counts = np.zeros(1, np.uint32)
+    hs = np.array([int(s[0]) for s in sizes], dtype=np.int32)
+    ws = np.array([int(s[1]) for s in sizes], dtype=np.int32)
+    return counts, offs, B, slots, hs, ws
+
+
+def _rle_rows(name, det_src, B, slots, host_definition):
+    """(on_host, det_src, ptr) for the (B, slots, 6) source-frame rows that go with an RLE set."""
+    on_host = isinstance(det_src, np.ndarray)
+    if on_host:
+        det = np.ascontiguousarray(det_src, dtype=np.float32)
+        ptr = lambda a: a.ctypes.data
+    else:
+        import torch
+        det = det_src
+        assert not host_definition, f"{name}_host takes numpy arrays"
+        assert det.is_cuda and det.dtype == torch.float32 and det.is_contiguous()
+        ptr = lambda a: a.data_ptr()
+    if det.ndim != 3 or det.shape[0] != B or det.shape[1] != slots or det.shape[2] != 6:
+        raise ValueError(f"{name}: det_src {tuple(det.shape)} does not go with {B} images of {slots} RLEs: ({B}, {slots}, 6) expected")
+    return on_host, det, ptr
+
+
+def _rle_decode_planes(host_definition, rles, sizes, device):
+    name = "rle_decode_planes_host" if host_definition else "rle_decode_planes"
+    if device is None and not host_definition and isinstance(rles, tuple) and len(rles) == 2 and hasattr(rles[0], "is_cuda"):
+        device = rles[0].device                                  # a pair of CUDA tensors: used in place, tensors out
+    counts, offs, B, slots, hs, ws = _rle_set(name, rles, sizes, device)
+    nbytes, out_offs, total = _ragged_layout(hs, ws, max(1, slots))
+    if device is None:
+        out = np.empty(max(1, total), np.uint8)
+        ptr = lambda a: a.ctypes.data
+    else:
+        import torch
+        out = torch.empty(max(1, total), dtype=torch.uint8, device=device)
+        ptr = lambda a: a.data_ptr()
+    head = (ptr(counts), ptr(offs), B, slots, hs.ctypes.data, ws.ctypes.data)
+    if host_definition:
+        _lib.check(_lib.lib().mrcnn_rle_decode_host(*head, ptr(out), out_offs.ctypes.data))
+    else:
+        _lib.check(_lib.lib().mrcnn_rle_decode(*head, _lib.HOST if device is None else _lib.DEVICE, ptr(out), out_offs.ctypes.data))
+    return [out[int(out_offs[b]):int(out_offs[b]) + slots * int(hs[b]) * int(ws[b])].reshape(slots, int(hs[b]), int(ws[b])) for b in range(B)]
+
+
+def rle_decode_planes(rles, sizes=None, device=None):
+    """The dense planes of an RLE set, decoded on the GPU (``mrcnn_rle_decode``): [ (slots, h_b, w_b) uint8 {0,1} per image ], the
+    layout paste_masks_source returns, so png.encode_batch takes them.  ``rles`` as merge_tiles, unite_tiles and masks_rle_source
+    return them — rles[b][i] = {"size", "counts"} — or a (counts, run_offsets) pair with ``sizes`` = [(h_b, w_b)]
+    (coco_eval.DeviceDetections and COCOGroundTruth.to_device() hold such pairs).  numpy arrays come back, unless ``device`` is given
+    or the pair is CUDA tensors (used in place): then the planes stay on the device as tensors."""
+    return _rle_decode_planes(False, rles, sizes, device)
+
+
+def rle_decode_planes_host(rles, sizes=None):
+    """The definition of rle_decode_planes: the sequential host code (``mrcnn_rle_decode_host``), no GPU; numpy out."""
+    return _rle_decode_planes(True, rles, sizes, None)
+
+
+def _instance_map_rle(host_definition, det_src, rles, sizes, min_score):
+    name = "instance_map_rle_host" if host_definition else "instance_map_rle"
+    on_host = isinstance(det_src, np.ndarray)
+    counts, offs, B, slots, hs, ws = _rle_set(name, rles, sizes, None if on_host else det_src.device)
+    on_host, det, ptr = _rle_rows(name, det_src, B, slots, host_definition)
+    nbytes, map_offs, total = _ragged_layout(hs, ws, 2)
+    if on_host:
+        out, visible = np.empty(max(1, total // 2), np.int16), np.zeros((B, slots), np.uint32)
+    else:
+        import torch
+        out = torch.empty(max(1, total // 2), dtype=torch.int16, device=det.device)
+        visible = torch.zeros((B, slots), dtype=torch.int32, device=det.device)
+    head = (ptr(det), ptr(counts), ptr(offs), B, slots, hs.ctypes.data, ws.ctypes.data, C.c_float(min_score))
+    tail = (ptr(out), map_offs.ctypes.data, ptr(visible))
+    if host_definition:
+        _lib.check(_lib.lib().mrcnn_instance_map_rle_host(*head, *tail))
+    else:
+        _lib.check(_lib.lib().mrcnn_instance_map_rle(*head, _lib.HOST if on_host else _lib.DEVICE, *tail))
+    maps = [out[int(map_offs[b]) // 2:int(map_offs[b] + nbytes[b]) // 2].reshape(int(hs[b]), int(ws[b])) for b in range(B)]
+    return maps, visible
+
+
+def instance_map_rle(det_src, rles, sizes=None, min_score: float = 0.0):
+    """Which RLE owns a pixel (``mrcnn_instance_map_rle``): det_src (B, slots, 6) source-frame rows and the RLE set that goes with them
+    (``rles`` as rle_decode_planes takes them — what merge_tiles, unite_tiles or masks_rle_source returned) → ([ (h_b, w_b) int16 per
+    image ], visible (B, slots)).  ``map[y, x]`` is the lowest row with score > min_score, score > 0 and a non-empty box whose mask is
+    set at the pixel, -1 where there is none; the box only decides whether a row is drawn.  numpy det_src → numpy out; a CUDA tensor →
+    the RLEs are uploaded (a pair of CUDA tensors is used in place) and tensors come back (visible as int32)."""
+    return _instance_map_rle(False, det_src, rles, sizes, min_score)
+
+
+def instance_map_rle_host(det_src, rles, sizes=None, min_score: float = 0.0):
+    """The definition of instance_map_rle: the sequential host code (``mrcnn_instance_map_rle_host``), no GPU; numpy in and out."""
+    return _instance_map_rle(True, det_src, rles, sizes, min_score)
+
+
+def _render_detections_rle(host_definition, images, det_src, rles, min_score, alpha, stroke):
+    name = "render_detections_rle_host" if host_definition else "render_detections_rle"
+    images = list(images)
+    on_host = isinstance(det_src, np.ndarray)
+    sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+    counts, offs, B, slots, hs, ws = _rle_set(name, rles, sizes, None if on_host else det_src.device)
+    on_host, det, ptr = _rle_rows(name, det_src, B, slots, host_definition)
+    table = (_lib.Image * max(1, B))()
+    keep = []
+    for b, im in enumerate(images):
+        if on_host:
+            im = np.ascontiguousarray(im, dtype=np.uint8)
+        else:
+            import torch
+            assert im.is_cuda and im.dtype == torch.uint8 and im.is_contiguous()
+        if im.ndim != 3 or im.shape[2] != 3:
+            raise ValueError(f"image {b} has shape {tuple(im.shape)}, expected (h, w, 3)")
+        keep.append(im)
+        table[b].rgb, table[b].height, table[b].width = ptr(im), int(im.shape[0]), int(im.shape[1])
+    nbytes, out_offs, total = _ragged_layout(hs, ws, 3)
+    if on_host:
+        out = np.empty(max(1, total), np.uint8)
+    else:
+        import torch
+        out = torch.empty(max(1, total), dtype=torch.uint8, device=det.device)
+    head = (table, ptr(det), ptr(counts), ptr(offs), B, slots, C.c_float(min_score), int(alpha), int(stroke))
+    if host_definition:
+        _lib.check(_lib.lib().mrcnn_render_detections_rle_host(*head, ptr(out), out_offs.ctypes.data))
+    else:
+        _lib.check(_lib.lib().mrcnn_render_detections_rle(*head, _lib.HOST if on_host else _lib.DEVICE, ptr(out), out_offs.ctypes.data))
+    return [out[int(out_offs[b]):int(out_offs[b] + nbytes[b])].reshape(int(hs[b]), int(ws[b]), 3) for b in range(B)]
+
+
+def render_detections_rle(images, det_src, rles, min_score: float = 0.7, alpha: int = 128, stroke: int = 3):
+    """Run-length masks drawn over their images (``mrcnn_render_detections_rle``): a list of (h_b, w_b, 3) uint8 images, det_src
+    (B, slots, 6) and the RLE set that goes with it → [ (h_b, w_b, 3) uint8 ].  Stroke, blend and palette are
+    render_detections_source's, the mask is the RLE's plane — so the result of predict_tiled, united or not, can be looked at.
+    numpy in → numpy out; CUDA tensors in (images and det_src; the RLEs are uploaded, or a pair of CUDA tensors used in place) →
+    tensors out."""
+    return _render_detections_rle(False, images, det_src, rles, min_score, alpha, stroke)
+
+
+def render_detections_rle_host(images, det_src, rles, min_score: float = 0.7, alpha: int = 128, stroke: int = 3):
+    """The definition of render_detections_rle: the sequential host code (``mrcnn_render_detections_rle_host``), no GPU."""
+    return _render_detections_rle(True, images, det_src, rles, min_score, alpha, stroke)

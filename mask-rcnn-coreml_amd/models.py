@@ -251,6 +251,44 @@ class MaskRCNN(_Model):
         _, maps, _ = instance_map_source(det, mask, [(int(im.shape[0]), int(im.shape[1])) for im in images], self.image_height, self.image_width, **kw)
         return encode_batch(maps, rows=self.max_detections)
 
+    def _tiled_draw_args(self, kw):
+        """Splits the keywords of the tiled renderers: predict_tiled's own (tile, overlap, unite, ...) and the rest for the draw."""
+        names = ("tile", "overlap", "metric", "match_threshold", "max_out", "threshold", "unite", "link_threshold")
+        return {k: kw.pop(k) for k in names if k in kw}, kw
+
+    def render_tiled(self, images, **kw):
+        """predict_tiled followed by detection.render_detections_rle: large images with the detections of their windows drawn on
+        them, the masks taken from the run lengths — united ones (unite=True) included, which no 28x28 mask reproduces.  predict_tiled's
+        keywords (tile, overlap, unite, metric, ...) pass through, the others go to the render (min_score, alpha, stroke).  A
+        convenience: no device work of its own."""
+        from .detection import render_detections_rle
+        images = list(images)
+        tiled, draw = self._tiled_draw_args(dict(kw))
+        det_src, _source, _n_kept, rles = self.predict_tiled(images, **tiled)
+        return render_detections_rle(images, det_src, rles, **draw)
+
+    def render_tiled_jpegs(self, images, quality: int = 90, sampling="420", **kw):
+        """render_tiled followed by jpeg.encode_batch on the device result: the overlays as JPEG files, a list of bytes.  A
+        convenience: no device work of its own."""
+        from .jpeg import encode_batch
+        return encode_batch(self.render_tiled(images, **kw), quality=quality, sampling=sampling)
+
+    def instance_pngs_tiled(self, images, **kw):
+        """predict_tiled followed by detection.instance_map_rle and png.encode_batch on the device result: which detection owns each
+        pixel of a large image, as PNG files (index = row + 1, 0 and transparent where there is none), a list of bytes.  The PNG
+        palette holds 255 rows: max_out (default: the model's rows per window) above 255 raises ValueError.  predict_tiled's keywords
+        pass through, min_score goes to the map.  A convenience: no device work of its own."""
+        from .detection import instance_map_rle
+        from .png import encode_batch
+        images = list(images)
+        tiled, draw = self._tiled_draw_args(dict(kw))
+        max_out = self.max_detections if tiled.get("max_out") is None else int(tiled["max_out"])
+        if not 1 <= max_out <= 255:
+            raise ValueError(f"instance_pngs_tiled: max_out = {max_out} rows do not fit the PNG palette (1..255): pass max_out <= 255")
+        det_src, _source, _n_kept, rles = self.predict_tiled(images, **tiled)
+        maps, _visible = instance_map_rle(det_src, rles, [(int(im.shape[0]), int(im.shape[1])) for im in images], **draw)
+        return encode_batch(maps, rows=max_out)
+
     def predict_into(self, images, det, mask, sync: bool = True):
         """Device tensors in, pre-allocated device tensors out (bench loop: no allocation, optional no sync)."""
         B, H, W, _ = images.shape
