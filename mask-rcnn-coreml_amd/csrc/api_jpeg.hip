@@ -270,21 +270,12 @@ extern "C" int mrcnn_jpeg_decode_batch_on(const mrcnn_jpeg* files, int batch, in
         const auto t0 = std::chrono::steady_clock::now();
         JpegPlan plan;
         plan_batch("jpeg_decode_batch", files, batch, plan);
+        std::vector<int32_t> hs((size_t)batch), ws((size_t)batch);
+        for (int b = 0; b < batch; ++b) { hs[(size_t)b] = plan.desc[(size_t)b].h; ws[(size_t)b] = plan.desc[(size_t)b].w; }
         int64_t extent = 0;
-        auto bytes_of = [&](int b) { return (int64_t)3 * plan.desc[(size_t)b].h * plan.desc[(size_t)b].w; };
-        for (int b = 0; b < batch; ++b) {
-            const int64_t off = out_offsets[b];
-            MRCNN_REQUIRE(off >= 0 && off % 16 == 0, MRCNN_ERR_INVALID, "jpeg_decode_batch: file %d of the batch: out_offsets[%d] = %lld is not a non-negative multiple of 16",
-                          b, b, (long long)off);
-            plan.desc[(size_t)b].out_offset = off;
-            extent = off + bytes_of(b) > extent ? off + bytes_of(b) : extent;
-        }
-        for (int a = 0; a < batch; ++a)
-            for (int b = a + 1; b < batch; ++b) {
-                const int64_t a0 = out_offsets[a], a1 = a0 + bytes_of(a), b0 = out_offsets[b], b1 = b0 + bytes_of(b);
-                MRCNN_REQUIRE(a1 <= b0 || b1 <= a0, MRCNN_ERR_INVALID, "jpeg_decode_batch: files %d and %d overlap in the output", a, b);
-            }
-        for (int b = 0; b < batch; ++b) { heights[b] = plan.desc[(size_t)b].h; widths[b] = plan.desc[(size_t)b].w; }
+        std::string err;
+        answer(check_offsets(hs.data(), ws.data(), batch, out_offsets, 3, "jpeg_decode_batch", &extent, &err), err);
+        for (int b = 0; b < batch; ++b) { plan.desc[(size_t)b].out_offset = out_offsets[b]; heights[b] = hs[(size_t)b]; widths[b] = ws[(size_t)b]; }
         const bool dev = memspace == MRCNN_DEVICE;
         std::lock_guard<std::mutex> lock(g_scratch_mutex);
         JpegScratch& sc = shared_scratch();
@@ -300,9 +291,7 @@ extern "C" int mrcnn_jpeg_decode_batch_on(const mrcnn_jpeg* files, int batch, in
         const auto t1 = std::chrono::steady_clock::now();
         HIP_CHECK(hipStreamSynchronize(st.s));
         t_device_ms = (float)ms_since(t1);
-        if (!dev)
-            for (int b = 0; b < batch; ++b)
-                HIP_CHECK(hipMemcpy(out_rgb + out_offsets[b], o + out_offsets[b], (size_t)bytes_of(b), hipMemcpyDeviceToHost));
+        if (!dev) ragged_to_host(out_rgb, o, out_offsets, hs.data(), ws.data(), batch, 3);
     });
 }
 

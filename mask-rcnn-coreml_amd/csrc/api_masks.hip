@@ -17,6 +17,7 @@ extern "C" int mrcnn_paste_masks(const float* detections, int64_t det_stride, co
         if (n == 0) return;
         Stream st;
         DevBuf td, tm, to;
+        Drain drain{st.s};
         const float* d = stage_rows(detections, memspace, n, det_stride, det_stride, td);
         const float* m = stage_rows(masks, memspace, n, (long)mask_size * mask_size, (long)mask_size * mask_size, tm);
         uint8_t* o = out;
@@ -28,17 +29,22 @@ extern "C" int mrcnn_paste_masks(const float* detections, int64_t det_stride, co
     });
 }
 
-// the geometry table of a mixed-size batch: every image's size checked, its letterbox at the model's input size, offset 0
-static std::vector<ImageGeom> image_geometry(const int32_t* heights, const int32_t* widths, int batch, int model_h, int model_w)
+// the geometry table of a mixed-size batch: every image's size checked (ragged.h), its letterbox at the model's input size, and its place
+// in a ragged output of `unit` bytes per pixel (offsets == nullptr: no such output, offset 0), checked too.  *extent = the output's
+// end, *max_pixels = the largest h*w.
+static std::vector<ImageGeom> image_geometry(const char* who, const int32_t* heights, const int32_t* widths, int batch, int model_h, int model_w,
+                                             const int64_t* offsets = nullptr, int64_t unit = 0, int64_t* extent = nullptr, long* max_pixels = nullptr)
 {
+    std::string err;
+    answer(check_sides(heights, widths, batch, who, &err), err);
+    if (offsets) answer(check_offsets(heights, widths, batch, offsets, unit, who, extent, &err), err);
     std::vector<ImageGeom> geom((size_t)batch);
     for (int b = 0; b < batch; ++b) {
         ImageGeom& g = geom[(size_t)b];
-        g.h = heights[b]; g.w = widths[b]; g.offset = 0; g.pitch = g.w;
-        MRCNN_REQUIRE(g.h >= 1 && g.h <= 32767 && g.w >= 1 && g.w <= 32767, MRCNN_ERR_SHAPE,
-                      "image %d of the batch is %dx%d: height and width must lie in 1..32767", b, g.h, g.w);
+        g.h = heights[b]; g.w = widths[b]; g.offset = offsets ? offsets[b] : 0; g.pitch = g.w;
         MRCNN_REQUIRE(mrcnn_letterbox_geometry(g.h, g.w, model_h, model_w, &g.nh, &g.nw, &g.py, &g.px) == MRCNN_OK, MRCNN_ERR_INVALID,
-                      "image %d of the batch: bad letterbox geometry", b);
+                      "%s: image %d: bad letterbox geometry", who, b);
+        if (max_pixels) *max_pixels = std::max(*max_pixels, (long)g.h * g.w);
     }
     return geom;
 }
@@ -53,48 +59,27 @@ extern "C" int mrcnn_paste_masks_source(const float* detections, const float* ma
         MRCNN_REQUIRE(batch >= 0 && rows >= 0 && mask_size >= 2 && model_h > 0 && model_w > 0, MRCNN_ERR_INVALID, "bad paste_masks_source argument");
         MRCNN_REQUIRE((long)batch * rows < (1L << 31), MRCNN_ERR_SHAPE, "paste_masks_source: %d x %d rows are too many", batch, rows);
         if (batch == 0 || rows == 0) return;
-        std::vector<ImageGeom> geom = image_geometry(heights, widths, batch, model_h, model_w);
-        long max_bytes = 0;
         int64_t extent = 0;
-        for (int b = 0; b < batch; ++b) {
-            ImageGeom& g = geom[(size_t)b];
-            g.offset = out_offsets[b];
-            MRCNN_REQUIRE(g.offset >= 0 && g.offset % 16 == 0, MRCNN_ERR_INVALID, "image %d of the batch: out_offsets[%d] = %lld is not a non-negative multiple of 16",
-                          b, b, (long long)g.offset);
-            const long bytes = (long)rows * g.h * g.w;
-            max_bytes = bytes > max_bytes ? bytes : max_bytes;
-            extent = g.offset + bytes > extent ? g.offset + bytes : extent;
-        }
-        for (int a = 0; a < batch; ++a)
-            for (int b = a + 1; b < batch; ++b) {
-                const int64_t a0 = geom[(size_t)a].offset, a1 = a0 + (int64_t)rows * geom[(size_t)a].h * geom[(size_t)a].w;
-                const int64_t b0 = geom[(size_t)b].offset, b1 = b0 + (int64_t)rows * geom[(size_t)b].h * geom[(size_t)b].w;
-                MRCNN_REQUIRE(a1 <= b0 || b1 <= a0, MRCNN_ERR_INVALID, "paste_masks_source: the planes of images %d and %d overlap in out", a, b);
-            }
+        long max_pixels = 0;
+        const std::vector<ImageGeom> geom = image_geometry("paste_masks_source", heights, widths, batch, model_h, model_w, out_offsets, rows, &extent, &max_pixels);
+        const bool dev = memspace == MRCNN_DEVICE;
         Stream st;
-        DevBuf td, tm, ts, to, tt, tb;
+        DevBuf td, tm, ts;
         const size_t n = (size_t)batch * rows;
         const float* d = stage_rows(detections, memspace, (long)n, 6, 6, td);
         const float* m = stage_rows(masks, memspace, (long)n, (long)mask_size * mask_size, (long)mask_size * mask_size, tm);
         float* ds = detections_src;
-        uint8_t* o = out;
-        if (memspace != MRCNN_DEVICE) {
-            ts.alloc(n * 6 * sizeof(float)); ds = ts.as<float>();
-            to.alloc((size_t)extent); o = to.as<uint8_t>();     // (same offsets as the caller's buffer: only the planes are copied back)
-        }
-        tt.alloc((size_t)batch * sizeof(ImageGeom));
-        tb.alloc(n * sizeof(int4));
-        HIP_CHECK(hipMemcpy(tt.p, geom.data(), (size_t)batch * sizeof(ImageGeom), hipMemcpyHostToDevice));
-        paste_masks_source_forward(st.s, d, m, static_cast<const ImageGeom*>(tt.p), batch, rows, mask_size, model_h, model_w, max_bytes, threshold, ds,
-                                   static_cast<int4*>(tb.p), o);
+        if (!dev) { ts.alloc(n * 6 * sizeof(float)); ds = ts.as<float>(); }
+        Carver sc;                                              // one scratch allocation: the geometry table | the pixel boxes
+        const auto tab = sc.take<ImageGeom>((size_t)batch);
+        const auto box = sc.take<int4>(n);
+        sc.alloc();
+        RaggedOut o(st.s, out, dev, extent);
+        HIP_CHECK(hipMemcpy(sc[tab], geom.data(), (size_t)batch * sizeof(ImageGeom), hipMemcpyHostToDevice));
+        paste_masks_source_forward(st.s, d, m, sc[tab], batch, rows, mask_size, model_h, model_w, rows * max_pixels, threshold, ds, sc[box], o.p);
         HIP_CHECK(hipStreamSynchronize(st.s));
-        if (memspace != MRCNN_DEVICE) {
-            HIP_CHECK(hipMemcpy(detections_src, ts.p, n * 6 * sizeof(float), hipMemcpyDeviceToHost));
-            for (int b = 0; b < batch; ++b) {
-                const ImageGeom& g = geom[(size_t)b];
-                HIP_CHECK(hipMemcpy(out + g.offset, to.as<uint8_t>() + g.offset, (size_t)rows * g.h * g.w, hipMemcpyDeviceToHost));
-            }
-        }
+        if (!dev) HIP_CHECK(hipMemcpy(detections_src, ts.p, n * 6 * sizeof(float), hipMemcpyDeviceToHost));
+        o.deliver(out, out_offsets, heights, widths, batch, rows);
     });
 }
 
@@ -110,11 +95,13 @@ extern "C" int mrcnn_masks_rle_source(const float* detections, const float* mask
         MRCNN_REQUIRE(capacity >= 0 && (counts || capacity == 0), MRCNN_ERR_INVALID, "masks_rle_source: null counts with capacity %lld", (long long)capacity);
         MRCNN_REQUIRE(batch >= 0 && rows >= 0 && mask_size >= 2 && model_h > 0 && model_w > 0, MRCNN_ERR_INVALID, "bad masks_rle_source argument");
         MRCNN_REQUIRE((long)batch * rows < (1L << 31), MRCNN_ERR_SHAPE, "masks_rle_source: %d x %d rows are too many", batch, rows);
-        const std::vector<ImageGeom> geom = image_geometry(heights, widths, batch, model_h, model_w);
+        const std::vector<ImageGeom> geom = image_geometry("masks_rle_source", heights, widths, batch, model_h, model_w);
         const bool dev = memspace == MRCNN_DEVICE;
         const size_t n = (size_t)batch * rows;
         Stream st;
-        DevBuf td, tm, ts, tt, to, ta, tx, tc;
+        DevBuf td, tm, ts, to, ta, tx, tc;
+        Carver sc;                                              // one scratch allocation: the geometry table | the pixel boxes | the segment records | the runs per instance
+        Drain drain{st.s};
         const float* d = stage_rows(detections, memspace, (long)n, 6, 6, td);
         const float* m = stage_rows(masks, memspace, (long)n, (long)mask_size * mask_size, (long)mask_size * mask_size, tm);
         float* ds = detections_src;
@@ -127,15 +114,16 @@ extern "C" int mrcnn_masks_rle_source(const float* detections, const float* mask
             if (areas) { ta.alloc(n * sizeof(uint32_t)); ar = ta.as<uint32_t>(); }
             if (bboxes_xywh) { tx.alloc(n * 4 * sizeof(int32_t)); bb = tx.as<int32_t>(); }
         }
-        // one scratch allocation: the geometry table | the pixel boxes | the segment records | the runs per instance
-        auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
-        const size_t o_box = up16((size_t)batch * sizeof(ImageGeom)), o_seg = o_box + n * sizeof(int4), o_run = o_seg + n * RLE_SEGS * sizeof(RleSeg);
-        tt.alloc(o_run + n * sizeof(uint32_t));
-        const ImageGeom* tab = tt.as<ImageGeom>();
-        int4* boxes = reinterpret_cast<int4*>(tt.as<char>() + o_box);
-        RleSeg* segs = reinterpret_cast<RleSeg*>(tt.as<char>() + o_seg);
-        uint32_t* nruns = reinterpret_cast<uint32_t*>(tt.as<char>() + o_run);
-        if (batch > 0) HIP_CHECK(hipMemcpy(tt.p, geom.data(), (size_t)batch * sizeof(ImageGeom), hipMemcpyHostToDevice));
+        const auto s_tab = sc.take<ImageGeom>((size_t)batch);
+        const auto s_box = sc.take<int4>(n);
+        const auto s_seg = sc.take<RleSeg>(n * RLE_SEGS);
+        const auto s_run = sc.take<uint32_t>(n);
+        sc.alloc();
+        const ImageGeom* tab = sc[s_tab];
+        int4* boxes = sc[s_box];
+        RleSeg* segs = sc[s_seg];
+        uint32_t* nruns = sc[s_run];
+        if (batch > 0) HIP_CHECK(hipMemcpy(sc[s_tab], geom.data(), (size_t)batch * sizeof(ImageGeom), hipMemcpyHostToDevice));
         masks_rle_count_forward(st.s, d, m, tab, batch, rows, mask_size, model_h, model_w, threshold, ds, boxes, segs, nruns, ro, ar, bb);
         long long need = 0;
         HIP_CHECK(hipMemcpyAsync(&need, ro + n, sizeof(need), hipMemcpyDeviceToHost, st.s));
@@ -161,30 +149,6 @@ extern "C" int mrcnn_masks_rle_source(const float* detections, const float* mask
 // ================================================================================================
 // drawing (DetectionRenderer.swift:13-88): the instance-id map and the rendered overlay
 // ================================================================================================
-// out_offsets of a ragged output with `unit` bytes per pixel, as mrcnn_paste_masks_source checks them: written into geom, the
-// extent of the buffer and the largest h*w returned
-static void ragged_offsets(std::vector<ImageGeom>& geom, const int64_t* offsets, int unit, const char* entry, int64_t& extent, long& max_pixels)
-{
-    const int batch = (int)geom.size();
-    extent = 0; max_pixels = 0;
-    auto bytes_of = [&](const ImageGeom& g) { return (int64_t)unit * g.h * g.w; };
-    for (int b = 0; b < batch; ++b) {
-        ImageGeom& g = geom[(size_t)b];
-        g.offset = offsets[b];
-        MRCNN_REQUIRE(g.offset >= 0 && g.offset % 16 == 0, MRCNN_ERR_INVALID, "image %d of the batch: out_offsets[%d] = %lld is not a non-negative multiple of 16",
-                      b, b, (long long)g.offset);
-        const long pixels = (long)g.h * g.w;
-        max_pixels = pixels > max_pixels ? pixels : max_pixels;
-        extent = g.offset + bytes_of(g) > extent ? g.offset + bytes_of(g) : extent;
-    }
-    for (int a = 0; a < batch; ++a)
-        for (int b = a + 1; b < batch; ++b) {
-            const int64_t a0 = geom[(size_t)a].offset, a1 = a0 + bytes_of(geom[(size_t)a]);
-            const int64_t b0 = geom[(size_t)b].offset, b1 = b0 + bytes_of(geom[(size_t)b]);
-            MRCNN_REQUIRE(a1 <= b0 || b1 <= a0, MRCNN_ERR_INVALID, "%s: images %d and %d overlap in the output", entry, a, b);
-        }
-}
-
 extern "C" int mrcnn_instance_map_source(const float* detections, const float* masks, int batch, int rows, int mask_size,
                                          const int32_t* heights, const int32_t* widths, int model_h, int model_w, float threshold,
                                          float min_score, int memspace, float* detections_src, int16_t* map, const int64_t* map_offsets,
@@ -198,39 +162,35 @@ extern "C" int mrcnn_instance_map_source(const float* detections, const float* m
         MRCNN_REQUIRE((long)batch * rows < (1L << 31), MRCNN_ERR_SHAPE, "instance_map_source: %d x %d rows are too many", batch, rows);
         MRCNN_REQUIRE(reinterpret_cast<uintptr_t>(map) % 2 == 0, MRCNN_ERR_INVALID, "instance_map_source: map is not aligned for int16");
         if (batch == 0) return;
-        std::vector<ImageGeom> geom = image_geometry(heights, widths, batch, model_h, model_w);
         int64_t extent = 0;
         long max_pixels = 0;
-        ragged_offsets(geom, map_offsets, 2, "instance_map_source", extent, max_pixels);
+        const std::vector<ImageGeom> geom = image_geometry("instance_map_source", heights, widths, batch, model_h, model_w, map_offsets, 2, &extent, &max_pixels);
         const bool dev = memspace == MRCNN_DEVICE;
         Stream st;
-        DevBuf td, tm, ts, to, tv, tt;
+        DevBuf td, tm, ts, tv;
         const size_t n = (size_t)batch * rows;
         const float* d = stage_rows(detections, memspace, (long)n, 6, 6, td);
         const float* m = stage_rows(masks, memspace, (long)n, (long)mask_size * mask_size, (long)mask_size * mask_size, tm);
         float* ds = detections_src;
-        uint8_t* o = reinterpret_cast<uint8_t*>(map);
         uint32_t* va = visible_areas;
         if (!dev) {
             ts.alloc((n ? n : 1) * 6 * sizeof(float)); ds = ts.as<float>();
-            to.alloc((size_t)extent); o = to.as<uint8_t>();     // (same offsets as the caller's buffer: only the maps are copied back)
             if (visible_areas) { tv.alloc((n ? n : 1) * sizeof(uint32_t)); va = tv.as<uint32_t>(); }
         }
-        // one scratch allocation: the geometry table | the pixel boxes
-        const size_t o_box = ((size_t)batch * sizeof(ImageGeom) + 15) / 16 * 16;
-        tt.alloc(o_box + (n ? n : 1) * sizeof(int4));
-        HIP_CHECK(hipMemcpy(tt.p, geom.data(), (size_t)batch * sizeof(ImageGeom), hipMemcpyHostToDevice));
-        instance_map_forward(st.s, d, m, tt.as<ImageGeom>(), batch, rows, mask_size, model_h, model_w, max_pixels, threshold, min_score, ds,
-                             reinterpret_cast<int4*>(tt.as<char>() + o_box), reinterpret_cast<int16_t*>(o), va);
+        Carver sc;                                              // one scratch allocation: the geometry table | the pixel boxes
+        const auto tab = sc.take<ImageGeom>((size_t)batch);
+        const auto box = sc.take<int4>(n);
+        sc.alloc();
+        RaggedOut o(st.s, map, dev, extent);
+        HIP_CHECK(hipMemcpy(sc[tab], geom.data(), (size_t)batch * sizeof(ImageGeom), hipMemcpyHostToDevice));
+        instance_map_forward(st.s, d, m, sc[tab], batch, rows, mask_size, model_h, model_w, max_pixels, threshold, min_score, ds, sc[box],
+                             reinterpret_cast<int16_t*>(o.p), va);
         HIP_CHECK(hipStreamSynchronize(st.s));
         if (!dev) {
             if (n) HIP_CHECK(hipMemcpy(detections_src, ts.p, n * 6 * sizeof(float), hipMemcpyDeviceToHost));
             if (visible_areas && n) HIP_CHECK(hipMemcpy(visible_areas, tv.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            for (int b = 0; b < batch; ++b) {
-                const ImageGeom& g = geom[(size_t)b];
-                HIP_CHECK(hipMemcpy(reinterpret_cast<uint8_t*>(map) + g.offset, to.as<uint8_t>() + g.offset, (size_t)2 * g.h * g.w, hipMemcpyDeviceToHost));
-            }
         }
+        o.deliver(map, map_offsets, heights, widths, batch, 2);
     });
 }
 
@@ -247,56 +207,32 @@ extern "C" int mrcnn_render_detections_source(const mrcnn_image* images, const f
         MRCNN_REQUIRE(alpha >= 0 && alpha <= 256, MRCNN_ERR_SHAPE, "render_detections_source: alpha %d outside 0..256", alpha);
         MRCNN_REQUIRE(stroke >= 0 && stroke <= 65534, MRCNN_ERR_SHAPE, "render_detections_source: stroke %d outside 0..65534", stroke);
         if (batch == 0) return;
-        std::vector<int32_t> hs((size_t)batch), ws((size_t)batch);
-        for (int b = 0; b < batch; ++b) {
-            MRCNN_REQUIRE(images[b].rgb, MRCNN_ERR_INVALID, "image %d of the batch has a null rgb pointer", b);
-            hs[(size_t)b] = images[b].height; ws[(size_t)b] = images[b].width;
-        }
-        std::vector<ImageGeom> geom = image_geometry(hs.data(), ws.data(), batch, model_h, model_w);
+        std::vector<int32_t> hs, ws;
+        image_sizes(images, batch, "render_detections_source", hs, ws);
         int64_t extent = 0;
         long max_pixels = 0;
-        ragged_offsets(geom, out_offsets, 3, "render_detections_source", extent, max_pixels);
+        const std::vector<ImageGeom> geom = image_geometry("render_detections_source", hs.data(), ws.data(), batch, model_h, model_w, out_offsets, 3, &extent, &max_pixels);
         const bool dev = memspace == MRCNN_DEVICE;
         Stream st;
-        DevBuf td, tm, ts, to, ti, tt;
+        DevBuf td, tm, ts, ti;
         const size_t n = (size_t)batch * rows;
         const float* d = stage_rows(detections, memspace, (long)n, 6, 6, td);
         const float* m = stage_rows(masks, memspace, (long)n, (long)mask_size * mask_size, (long)mask_size * mask_size, tm);
         float* ds = detections_src;
-        uint8_t* o = out_rgb;
-        std::vector<const uint8_t*> srcs((size_t)batch);
         if (!dev || !detections_src) { ts.alloc((n ? n : 1) * 6 * sizeof(float)); ds = ts.as<float>(); }
-        if (!dev) {
-            to.alloc((size_t)extent); o = to.as<uint8_t>();
-            size_t total = 0;                                           // the sources back to back, each from a 16-byte boundary
-            for (int b = 0; b < batch; ++b) total += ((size_t)3 * geom[(size_t)b].h * geom[(size_t)b].w + 15) / 16 * 16;
-            ti.alloc(total);
-            size_t at = 0;
-            for (int b = 0; b < batch; ++b) {
-                const size_t bytes = (size_t)3 * geom[(size_t)b].h * geom[(size_t)b].w;
-                HIP_CHECK(hipMemcpy(ti.as<uint8_t>() + at, images[b].rgb, bytes, hipMemcpyHostToDevice));
-                srcs[(size_t)b] = ti.as<uint8_t>() + at;
-                at += (bytes + 15) / 16 * 16;
-            }
-        } else {
-            for (int b = 0; b < batch; ++b) srcs[(size_t)b] = images[b].rgb;
-        }
-        // one scratch allocation: the geometry table | the source pointers | the pixel boxes
-        auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
-        const size_t o_src = up16((size_t)batch * sizeof(ImageGeom)), o_box = o_src + up16((size_t)batch * sizeof(const uint8_t*));
-        tt.alloc(o_box + (n ? n : 1) * sizeof(int4));
-        HIP_CHECK(hipMemcpy(tt.p, geom.data(), (size_t)batch * sizeof(ImageGeom), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(tt.as<char>() + o_src, srcs.data(), (size_t)batch * sizeof(const uint8_t*), hipMemcpyHostToDevice));
-        render_detections_forward(st.s, d, m, tt.as<ImageGeom>(), reinterpret_cast<const uint8_t* const*>(tt.as<char>() + o_src), batch, rows, mask_size,
-                                  model_h, model_w, max_pixels, threshold, min_score, alpha, stroke, ds, reinterpret_cast<int4*>(tt.as<char>() + o_box), o);
+        Carver sc;                                              // one scratch allocation: the geometry table | the source pointers | the pixel boxes
+        const auto tab = sc.take<ImageGeom>((size_t)batch);
+        const auto src = sc.take<const uint8_t*>((size_t)batch);
+        const auto box = sc.take<int4>(n);
+        sc.alloc();
+        RaggedOut o(st.s, out_rgb, dev, extent);
+        HIP_CHECK(hipMemcpy(sc[tab], geom.data(), (size_t)batch * sizeof(ImageGeom), hipMemcpyHostToDevice));
+        upload_sources(images, batch, dev, ti, sc[src]);
+        render_detections_forward(st.s, d, m, sc[tab], sc[src], batch, rows, mask_size, model_h, model_w, max_pixels, threshold, min_score, alpha, stroke, ds,
+                                  sc[box], o.p);
         HIP_CHECK(hipStreamSynchronize(st.s));
-        if (!dev) {
-            if (detections_src && n) HIP_CHECK(hipMemcpy(detections_src, ts.p, n * 6 * sizeof(float), hipMemcpyDeviceToHost));
-            for (int b = 0; b < batch; ++b) {
-                const ImageGeom& g = geom[(size_t)b];
-                HIP_CHECK(hipMemcpy(out_rgb + g.offset, to.as<uint8_t>() + g.offset, (size_t)3 * g.h * g.w, hipMemcpyDeviceToHost));
-            }
-        }
+        if (!dev && detections_src && n) HIP_CHECK(hipMemcpy(detections_src, ts.p, n * 6 * sizeof(float), hipMemcpyDeviceToHost));
+        o.deliver(out_rgb, out_offsets, hs.data(), ws.data(), batch, 3);
     });
 }
 

@@ -13,23 +13,6 @@ static rle_draw::Set rle_set(const uint32_t* counts, const int64_t* run_offsets,
     return rle_draw::Set{counts, run_offsets, n_images, slots, heights, widths};
 }
 
-static void answer(int st, const std::string& err)
-{
-    if (st != MRCNN_OK) fail(st, "%s", err.c_str());
-}
-
-// the sizes of the images of a table, null pointers refused
-static void image_sizes(const mrcnn_image* images, int n_images, const char* who, std::vector<int32_t>& hs, std::vector<int32_t>& ws)
-{
-    MRCNN_REQUIRE(images, MRCNN_ERR_INVALID, "%s: null images", who);
-    MRCNN_REQUIRE(n_images >= 0, MRCNN_ERR_INVALID, "%s: n_images %d is negative", who, n_images);
-    hs.assign((size_t)n_images, 0); ws.assign((size_t)n_images, 0);
-    for (int b = 0; b < n_images; ++b) {
-        MRCNN_REQUIRE(images[b].rgb, MRCNN_ERR_INVALID, "%s: image %d has a null rgb pointer", who, b);
-        hs[(size_t)b] = images[b].height; ws[(size_t)b] = images[b].width;
-    }
-}
-
 extern "C" int mrcnn_rle_decode_host(const uint32_t* counts, const int64_t* run_offsets, int n_images, int slots, const int32_t* heights,
                                      const int32_t* widths, uint8_t* out, const int64_t* out_offsets)
 {
@@ -65,25 +48,26 @@ namespace {
 
 // One call on the device.  The constructor stages what the three entries share: the RLE set on the device, its prefix table, the image
 // table and the records (pass 1 of kernels_rle_draw.hip), and answers a bad RLE before anything is drawn.  The entry then draws into
-// out(), and deliver() hands the images' bytes to a host caller.
+// out.p, and deliver() hands the images' bytes to a host caller.
 struct RleDrawRun {
     const rle_draw::Set& a;
     const char* who;
     const bool dev;
     const size_t n;
     Stream st_;
-    DevBuf tc, to, td, tp, tt, ts, tout;
-    Drain drain;                                             // (declared behind the buffers: the stream drains before they are freed)
+    DevBuf tc, to, td, tp;
+    Carver sc;
+    RaggedOut out;                                           // (declared behind the buffers: the stream drains before they are freed)
     hipStream_t s;
     RleDrawJob job{};
-    std::vector<RleDrawImage> tab;
-    int64_t unit, extent;
+    const int64_t* offsets;
+    int64_t unit;
 
-    // det: the caller's detections_src (nullptr: the decode); offsets / unit_bytes: the output's layout, checked by the caller
-    RleDrawRun(const rle_draw::Set& set, const char* name, int memspace, const float* det, float min_score, const int64_t* offsets, int64_t unit_bytes,
-               int64_t out_extent)
-        : a(set), who(name), dev(memspace == MRCNN_DEVICE), n((size_t)set.n_images * set.slots), drain{st_.s}, s(st_.s), unit(unit_bytes),
-          extent(out_extent)
+    // det: the caller's detections_src (nullptr: the decode); callers / out_offsets / unit_bytes / extent: the output and its layout, checked by the caller
+    RleDrawRun(const rle_draw::Set& set, const char* name, int memspace, const float* det, float min_score, void* callers, const int64_t* out_offsets,
+               int64_t unit_bytes, int64_t extent)
+        : a(set), who(name), dev(memspace == MRCNN_DEVICE), n((size_t)set.n_images * set.slots), out(st_.s, callers, dev, extent), s(st_.s),
+          offsets(out_offsets), unit(unit_bytes)
     {
         std::vector<long long> h_off(n + 1, 0);
         if (dev) HIP_CHECK(hipMemcpy(h_off.data(), a.run_offsets, (n + 1) * 8, hipMemcpyDeviceToHost));
@@ -101,64 +85,46 @@ struct RleDrawRun {
             if (runs) HIP_CHECK(hipMemcpy(tc.p, a.counts, runs * 4, hipMemcpyHostToDevice));
             HIP_CHECK(hipMemcpy(to.p, h_off.data(), (n + 1) * 8, hipMemcpyHostToDevice));
             counts = tc.as<uint32_t>(); off = to.as<long long>();
-            if (det && n) {
-                td.alloc(n * 6 * sizeof(float));
-                HIP_CHECK(hipMemcpy(td.p, det, n * 6 * sizeof(float), hipMemcpyHostToDevice));
-                det = td.as<float>();
-            }
+            if (det && n) det = stage_rows(det, memspace, (long)n, 6, 6, td);
         }
-        tab.resize((size_t)a.n_images);
+        std::vector<ImageGeom> tab((size_t)a.n_images);
         for (int b = 0; b < a.n_images; ++b) {
-            tab[(size_t)b] = RleDrawImage{a.heights[b], a.widths[b], (long long)offsets[b]};
+            tab[(size_t)b].h = a.heights[b]; tab[(size_t)b].w = a.widths[b]; tab[(size_t)b].offset = offsets[b];
             job.max_h = std::max(job.max_h, a.heights[b]); job.max_w = std::max(job.max_w, a.widths[b]);
         }
         tp.alloc(runs * 4);
         // one scratch allocation: the image table | totals | areas | extents | records | the flag
-        size_t o = 0;
-        auto take = [&](size_t bytes) { const size_t at = o; o = up(o + bytes, 16); return at; };
-        const size_t o_tab = take(tab.size() * sizeof(RleDrawImage)), o_tot = take(n * 8), o_ar = take(n * 4), o_ext = take(n * sizeof(uint2)),
-                     o_rec = take(n * sizeof(RleDrawRec)), o_bad = take(8);
-        tt.alloc(o);
-        char* const wb = tt.as<char>();
-        if (!tab.empty()) HIP_CHECK(hipMemcpy(wb + o_tab, tab.data(), tab.size() * sizeof(RleDrawImage), hipMemcpyHostToDevice));
-        job.rec = reinterpret_cast<const RleDrawRec*>(wb + o_rec);
+        const auto s_tab = sc.take<ImageGeom>(tab.size());
+        const auto s_tot = sc.take<unsigned long long>(n);
+        const auto s_ar = sc.take<uint32_t>(n);
+        const auto s_ext = sc.take<uint2>(n);
+        const auto s_rec = sc.take<RleDrawRec>(n);
+        const auto s_bad = sc.take<unsigned long long>(1);
+        sc.alloc();
+        if (!tab.empty()) HIP_CHECK(hipMemcpy(sc[s_tab], tab.data(), tab.size() * sizeof(ImageGeom), hipMemcpyHostToDevice));
+        job.rec = sc[s_rec];
         job.pre_b = tp.as<uint32_t>();
-        job.tab = reinterpret_cast<const RleDrawImage*>(wb + o_tab);
+        job.tab = sc[s_tab];
         job.n_images = a.n_images; job.slots = a.slots;
-        unsigned long long* const totals = reinterpret_cast<unsigned long long*>(wb + o_tot);
-        unsigned long long* const bad = reinterpret_cast<unsigned long long*>(wb + o_bad);
-        rle_prefix_forward(s, counts, off, (long)n, tp.as<uint32_t>(), nullptr, totals, reinterpret_cast<uint32_t*>(wb + o_ar),
-                           reinterpret_cast<uint2*>(wb + o_ext));
-        rle_draw_prepare(s, off, totals, reinterpret_cast<const uint2*>(wb + o_ext), det, min_score, job, reinterpret_cast<RleDrawRec*>(wb + o_rec), bad);
+        rle_prefix_forward(s, counts, off, (long)n, tp.as<uint32_t>(), nullptr, sc[s_tot], sc[s_ar], sc[s_ext]);
+        rle_draw_prepare(s, off, sc[s_tot], sc[s_ext], det, min_score, job, sc[s_rec], sc[s_bad]);
         unsigned long long k = 0;
-        HIP_CHECK(hipMemcpyAsync(&k, bad, sizeof k, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(&k, sc[s_bad], sizeof k, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         if (k != ~0ull) {                                           // the one flag said no: fetch the sum for the message
             unsigned long long sum = 0;
-            HIP_CHECK(hipMemcpy(&sum, totals + k, sizeof sum, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(&sum, sc[s_tot] + k, sizeof sum, hipMemcpyDeviceToHost));
             const int b = (int)(k / (unsigned long long)a.slots);
             fail(MRCNN_ERR_SHAPE, "%s: RLE %llu (image %d, slot %d) sums to %llu pixels, its %dx%d plane has %llu", who, k, b,
                  (int)(k % (unsigned long long)a.slots), sum, a.heights[b], a.widths[b], (unsigned long long)a.heights[b] * (unsigned long long)a.widths[b]);
         }
     }
 
-    // where the kernels write: the caller's buffer, or a staging copy with the same offsets
-    uint8_t* out(void* callers)
-    {
-        if (dev) return static_cast<uint8_t*>(callers);
-        tout.alloc((size_t)extent);
-        return tout.as<uint8_t>();
-    }
-
     // the drawing is queued: only the images' own bytes go to a host caller
     void deliver(void* callers)
     {
         HIP_CHECK(hipStreamSynchronize(s));
-        if (dev) return;
-        for (int b = 0; b < a.n_images; ++b) {
-            const size_t bytes = (size_t)unit * a.heights[b] * a.widths[b];
-            if (bytes) HIP_CHECK(hipMemcpy(static_cast<uint8_t*>(callers) + tab[(size_t)b].offset, tout.as<uint8_t>() + tab[(size_t)b].offset, bytes, hipMemcpyDeviceToHost));
-        }
+        out.deliver(callers, offsets, a.heights, a.widths, a.n_images, unit);
     }
 };
 
@@ -174,11 +140,11 @@ extern "C" int mrcnn_rle_decode(const uint32_t* counts, const int64_t* run_offse
         MRCNN_REQUIRE(out, MRCNN_ERR_INVALID, "rle_decode: null out");
         MRCNN_REQUIRE(memspace == MRCNN_HOST || memspace == MRCNN_DEVICE, MRCNN_ERR_INVALID, "rle_decode: unknown memspace %d", memspace);
         int64_t extent = 0;
-        answer(rle_draw::check_offsets(a, out_offsets, slots, "rle_decode", &extent, &err), err);
+        answer(check_offsets(heights, widths, n_images, out_offsets, slots, "rle_decode", &extent, &err), err);
         require_gpu();
         if (n_images == 0 || slots == 0) return;
-        RleDrawRun r(a, "rle_decode", memspace, nullptr, 0.0f, out_offsets, slots, extent);
-        rle_decode_forward(r.s, r.job, r.out(out));
+        RleDrawRun r(a, "rle_decode", memspace, nullptr, 0.0f, out, out_offsets, slots, extent);
+        rle_decode_forward(r.s, r.job, r.out.p);
         r.deliver(out);
     });
 }
@@ -195,14 +161,14 @@ extern "C" int mrcnn_instance_map_rle(const float* detections_src, const uint32_
         MRCNN_REQUIRE(memspace == MRCNN_HOST || memspace == MRCNN_DEVICE, MRCNN_ERR_INVALID, "instance_map_rle: unknown memspace %d", memspace);
         MRCNN_REQUIRE(reinterpret_cast<uintptr_t>(map) % 2 == 0, MRCNN_ERR_INVALID, "instance_map_rle: map is not aligned for int16");
         int64_t extent = 0;
-        answer(rle_draw::check_offsets(a, map_offsets, 2, "instance_map_rle", &extent, &err), err);
+        answer(check_offsets(heights, widths, n_images, map_offsets, 2, "instance_map_rle", &extent, &err), err);
         require_gpu();
         if (n_images == 0) return;
-        RleDrawRun r(a, "instance_map_rle", memspace, detections_src, min_score, map_offsets, 2, extent);
+        RleDrawRun r(a, "instance_map_rle", memspace, detections_src, min_score, map, map_offsets, 2, extent);
         uint32_t* va = visible_areas;
         DevBuf tv;
         if (!r.dev && visible_areas) { tv.alloc(r.n * sizeof(uint32_t)); va = tv.as<uint32_t>(); }
-        instance_map_rle_forward(r.s, r.job, reinterpret_cast<int16_t*>(r.out(map)), va);
+        instance_map_rle_forward(r.s, r.job, reinterpret_cast<int16_t*>(r.out.p), va);
         r.deliver(map);
         if (!r.dev && visible_areas && r.n) HIP_CHECK(hipMemcpy(visible_areas, tv.p, r.n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     });
@@ -222,30 +188,14 @@ extern "C" int mrcnn_render_detections_rle(const mrcnn_image* images, const floa
         MRCNN_REQUIRE(memspace == MRCNN_HOST || memspace == MRCNN_DEVICE, MRCNN_ERR_INVALID, "render_detections_rle: unknown memspace %d", memspace);
         answer(rle_draw::check_render(alpha, stroke, "render_detections_rle", &err), err);
         int64_t extent = 0;
-        answer(rle_draw::check_offsets(a, out_offsets, 3, "render_detections_rle", &extent, &err), err);
+        answer(check_offsets(hs.data(), ws.data(), n_images, out_offsets, 3, "render_detections_rle", &extent, &err), err);
         require_gpu();
         if (n_images == 0) return;
-        RleDrawRun r(a, "render_detections_rle", memspace, detections_src, min_score, out_offsets, 3, extent);
-        // the sources: the caller's device pointers, or uploaded back to back, each from a 16-byte boundary
+        RleDrawRun r(a, "render_detections_rle", memspace, detections_src, min_score, out_rgb, out_offsets, 3, extent);
         DevBuf ti, tsrc;
-        std::vector<const uint8_t*> srcs((size_t)n_images);
-        if (!r.dev) {
-            size_t total = 0;
-            for (int b = 0; b < n_images; ++b) total += up((size_t)3 * hs[(size_t)b] * ws[(size_t)b], 16);
-            ti.alloc(total);
-            size_t at = 0;
-            for (int b = 0; b < n_images; ++b) {
-                const size_t bytes = (size_t)3 * hs[(size_t)b] * ws[(size_t)b];
-                HIP_CHECK(hipMemcpy(ti.as<uint8_t>() + at, images[b].rgb, bytes, hipMemcpyHostToDevice));
-                srcs[(size_t)b] = ti.as<uint8_t>() + at;
-                at += up(bytes, 16);
-            }
-        } else {
-            for (int b = 0; b < n_images; ++b) srcs[(size_t)b] = images[b].rgb;
-        }
-        tsrc.alloc(srcs.size() * sizeof(const uint8_t*));
-        HIP_CHECK(hipMemcpy(tsrc.p, srcs.data(), srcs.size() * sizeof(const uint8_t*), hipMemcpyHostToDevice));
-        render_detections_rle_forward(r.s, r.job, tsrc.as<const uint8_t*>(), alpha, stroke, r.out(out_rgb));
+        tsrc.alloc((size_t)n_images * sizeof(const uint8_t*));
+        upload_sources(images, n_images, r.dev, ti, tsrc.as<const uint8_t*>());
+        render_detections_rle_forward(r.s, r.job, tsrc.as<const uint8_t*>(), alpha, stroke, r.out.p);
         r.deliver(out_rgb);
     });
 }

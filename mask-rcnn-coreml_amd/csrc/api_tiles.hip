@@ -12,8 +12,7 @@ extern "C" int mrcnn_tile_plan(int height, int width, int tile_h, int tile_w, in
 {
     return guarded([&] {
         std::string err;
-        const int st = tiles::plan(height, width, tile_h, tile_w, overlap_y, overlap_x, image, out, capacity, count, &err);
-        if (st != MRCNN_OK) fail(st, "%s", err.c_str());
+        answer(tiles::plan(height, width, tile_h, tile_w, overlap_y, overlap_x, image, out, capacity, count, &err), err);
     });
 }
 
@@ -24,14 +23,10 @@ extern "C" int mrcnn_maskrcnn_predict_tiles(mrcnn_model* model, const mrcnn_imag
         MRCNN_REQUIRE(model && images && tiles && detections && masks, MRCNN_ERR_INVALID, "predict_tiles: null argument");
         MRCNN_REQUIRE(n_tiles >= 1, MRCNN_ERR_SHAPE, "predict_tiles: n_tiles %d < 1", n_tiles);
         MRCNN_REQUIRE(n_images >= 1, MRCNN_ERR_SHAPE, "predict_tiles: n_images %d < 1", n_images);
-        std::vector<int32_t> hs((size_t)n_images), ws((size_t)n_images);
-        for (int b = 0; b < n_images; ++b) {
-            MRCNN_REQUIRE(images[b].rgb, MRCNN_ERR_INVALID, "predict_tiles: image %d has a null rgb pointer", b);
-            hs[(size_t)b] = images[b].height; ws[(size_t)b] = images[b].width;
-        }
+        std::vector<int32_t> hs, ws;
+        image_sizes(images, n_images, "predict_tiles", hs, ws);
         std::string err;
-        const int st = tiles::check_tiles(tiles, n_tiles, hs.data(), ws.data(), n_images, "predict_tiles", &err);
-        if (st != MRCNN_OK) fail(st, "%s", err.c_str());
+        answer(tiles::check_tiles(tiles, n_tiles, hs.data(), ws.data(), n_images, "predict_tiles", &err), err);
         model->m.predict_tiles(images, n_images, tiles, n_tiles, memspace, detections, masks);
     });
 }
@@ -53,10 +48,9 @@ extern "C" int mrcnn_merge_tiles_host(const float* detections, const float* mask
 {
     return guarded([&] {
         std::string err;
-        const int st = tiles::merge_host(merge_args(detections, masks, tiles, n_tiles, rows, mask_size, heights, widths, n_images, model_h, model_w,
+        answer(tiles::merge_host(merge_args(detections, masks, tiles, n_tiles, rows, mask_size, heights, widths, n_images, model_h, model_w,
                                                     threshold, metric, match_threshold, max_out, detections_src, source, n_kept, counts, capacity,
-                                                    run_offsets, areas, bboxes_xywh), &err);
-        if (st != MRCNN_OK) fail(st, "%s", err.c_str());
+                                                    run_offsets, areas, bboxes_xywh), &err), err);
     });
 }
 
@@ -68,10 +62,9 @@ extern "C" int mrcnn_unite_tiles_host(const float* detections, const float* mask
 {
     return guarded([&] {
         std::string err;
-        const int st = tiles::unite_host(merge_args(detections, masks, tiles, n_tiles, rows, mask_size, heights, widths, n_images, model_h, model_w,
+        answer(tiles::unite_host(merge_args(detections, masks, tiles, n_tiles, rows, mask_size, heights, widths, n_images, model_h, model_w,
                                                     threshold, metric, link_threshold, max_out, detections_src, source, n_kept, counts, capacity,
-                                                    run_offsets, areas, bboxes_xywh, n_parts, group), &err);
-        if (st != MRCNN_OK) fail(st, "%s", err.c_str());
+                                                    run_offsets, areas, bboxes_xywh, n_parts, group), &err), err);
     });
 }
 
@@ -86,7 +79,8 @@ struct TilesRun {
     const bool dev, unite;
     const size_t n, slots;
     Stream st_;
-    DevBuf td, tm, tt, tw, tc, toc;
+    DevBuf td, tm, tc, toc;
+    Carver tt, tw;                                           // one allocation for the tables, one for the scratch
     Drain drain;                                             // (declared behind the buffers: the stream drains before they are freed)
     TilesMerge m{};
     hipStream_t s;
@@ -125,58 +119,56 @@ struct TilesRun {
         m.thr = a.threshold; m.metric = a.metric; m.match_thr = a.match_threshold;
         m.det = stage_rows(a.detections, memspace, (long)n, 6, 6, td);
         m.masks = stage_rows(a.masks, memspace, (long)n, (long)a.mask_size * a.mask_size, (long)a.mask_size * a.mask_size, tm);
-        // one allocation for the tables, one for the scratch
-        size_t o = 0;
-        auto take = [&](size_t bytes) { const size_t at = o; o = up(o + bytes, 16); return at; };
-        const size_t o_tab = take(tab.size() * sizeof(ImageGeom)), o_tg = take(tg.size() * sizeof(TileGeom)), o_toff = take(toff.size() * sizeof(int)),
-                     o_tl = take(tlist.size() * sizeof(int)), o_sz = take(imgsz.size() * sizeof(int2));
-        tt.alloc(o);
-        HIP_CHECK(hipMemcpyAsync(tt.as<char>() + o_tab, tab.data(), tab.size() * sizeof(ImageGeom), hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(tt.as<char>() + o_tg, tg.data(), tg.size() * sizeof(TileGeom), hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(tt.as<char>() + o_toff, toff.data(), toff.size() * sizeof(int), hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(tt.as<char>() + o_tl, tlist.data(), tlist.size() * sizeof(int), hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(tt.as<char>() + o_sz, imgsz.data(), imgsz.size() * sizeof(int2), hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipStreamSynchronize(s));                      // (the vectors above are pageable: the copies have read them now)
-        const ImageGeom* tab_tile = reinterpret_cast<const ImageGeom*>(tt.as<char>() + o_tab);
+        auto table = [&](auto slot, const auto& v) {
+            HIP_CHECK(hipMemcpyAsync(tt[slot], v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, s));
+            return tt[slot];
+        };
+        const auto s_tab = tt.take<ImageGeom>(tab.size());
+        const auto s_tg = tt.take<TileGeom>(tg.size());
+        const auto s_toff = tt.take<int>(toff.size()), s_tl = tt.take<int>(tlist.size());
+        const auto s_sz = tt.take<int2>(imgsz.size());
+        tt.alloc();
+        const ImageGeom* tab_tile = table(s_tab, tab);
         m.tab_full = tab_tile + n_tiles;
-        m.tiles = reinterpret_cast<const TileGeom*>(tt.as<char>() + o_tg);
-        m.toff = reinterpret_cast<const int*>(tt.as<char>() + o_toff);
-        m.tlist = reinterpret_cast<const int*>(tt.as<char>() + o_tl);
-        m.imgsz = reinterpret_cast<const int2*>(tt.as<char>() + o_sz);
-        o = 0;
-        const size_t w_box = take(n * sizeof(int4)), w_rows = take(n * 6 * sizeof(float)), w_tile = take(n * 6 * sizeof(float)),
-                     w_seg = take(n * RLE_SEGS * sizeof(RleSeg)), w_nr = take(n * sizeof(uint32_t)), w_ro = take((n + 1) * sizeof(long long)),
-                     w_ar = take(n * sizeof(uint32_t)), w_bb = take(n * 4 * sizeof(int32_t)), w_ord = take(n * sizeof(int)), w_pos = take(n * sizeof(int)),
-                     w_ne = take((size_t)n_images * sizeof(int)), w_sup = take(n * (size_t)m.W * sizeof(unsigned long long)),
-                     w_onr = take(slots * sizeof(uint32_t));
-        // the outputs: the caller's device arrays, or a staging copy of each
-        const size_t w_ds = take(slots * 6 * sizeof(float)), w_src = take(slots * sizeof(int32_t)), w_nk = take((size_t)n_images * sizeof(int32_t)),
-                     w_oro = take((slots + 1) * sizeof(long long)), w_oar = take(slots * sizeof(uint32_t)), w_obb = take(slots * 4 * sizeof(int32_t));
-        // the union's member lists, hulls and segments, and its two outputs
+        m.tiles = table(s_tg, tg);
+        m.toff = table(s_toff, toff);
+        m.tlist = table(s_tl, tlist);
+        m.imgsz = table(s_sz, imgsz);
+        HIP_CHECK(hipStreamSynchronize(s));                      // (the vectors above are pageable: the copies have read them now)
+        // the scratch; the outputs are the caller's device arrays, or a staging copy of each; u: the union's member lists, hulls and
+        // segments, and its two outputs
         const size_t u = unite ? 1 : 0;
-        const size_t w_mem = take(u * n * sizeof(int)), w_span = take(u * slots * sizeof(int2)), w_hull = take(u * slots * sizeof(int4)),
-                     w_oseg = take(u * slots * RLE_SEGS * sizeof(RleSeg)), w_np = take(u * slots * sizeof(int32_t)), w_grp = take(u * n * sizeof(int32_t));
-        tw.alloc(o);
-        char* const wb = tw.as<char>();
-        m.boxes = reinterpret_cast<int4*>(wb + w_box); m.rows_src = reinterpret_cast<float*>(wb + w_rows);
-        m.segs = reinterpret_cast<RleSeg*>(wb + w_seg); m.nruns = reinterpret_cast<uint32_t*>(wb + w_nr); m.ro = reinterpret_cast<long long*>(wb + w_ro);
-        m.areas = reinterpret_cast<uint32_t*>(wb + w_ar); m.bboxes = reinterpret_cast<int32_t*>(wb + w_bb);
-        m.order = reinterpret_cast<int*>(wb + w_ord); m.pos = reinterpret_cast<int*>(wb + w_pos); m.nelig = reinterpret_cast<int*>(wb + w_ne);
-        m.supp = reinterpret_cast<unsigned long long*>(wb + w_sup); m.out_nruns = reinterpret_cast<uint32_t*>(wb + w_onr);
-        m.det_src = dev ? a.detections_src : reinterpret_cast<float*>(wb + w_ds);
-        m.source = dev ? a.source : reinterpret_cast<int32_t*>(wb + w_src);
-        m.n_kept = dev ? a.n_kept : reinterpret_cast<int32_t*>(wb + w_nk);
-        m.out_ro = dev ? reinterpret_cast<long long*>(a.run_offsets) : reinterpret_cast<long long*>(wb + w_oro);
-        m.out_areas = dev && a.areas ? a.areas : reinterpret_cast<uint32_t*>(wb + w_oar);
-        m.out_bboxes = dev && a.bboxes_xywh ? a.bboxes_xywh : reinterpret_cast<int32_t*>(wb + w_obb);
+        const auto w_box = tw.take<int4>(n);
+        const auto w_rows = tw.take<float>(n * 6), w_tile = tw.take<float>(n * 6), w_ds = tw.take<float>(slots * 6);
+        const auto w_seg = tw.take<RleSeg>(n * RLE_SEGS), w_oseg = tw.take<RleSeg>(u * slots * RLE_SEGS);
+        const auto w_nr = tw.take<uint32_t>(n), w_ar = tw.take<uint32_t>(n), w_onr = tw.take<uint32_t>(slots), w_oar = tw.take<uint32_t>(slots);
+        const auto w_ro = tw.take<long long>(n + 1), w_oro = tw.take<long long>(slots + 1);
+        const auto w_bb = tw.take<int32_t>(n * 4), w_ord = tw.take<int32_t>(n), w_pos = tw.take<int32_t>(n), w_ne = tw.take<int32_t>((size_t)n_images),
+                   w_src = tw.take<int32_t>(slots), w_nk = tw.take<int32_t>((size_t)n_images), w_obb = tw.take<int32_t>(slots * 4),
+                   w_mem = tw.take<int32_t>(u * n), w_np = tw.take<int32_t>(u * slots), w_grp = tw.take<int32_t>(u * n);
+        const auto w_sup = tw.take<unsigned long long>(n * (size_t)m.W);
+        const auto w_span = tw.take<int2>(u * slots);
+        const auto w_hull = tw.take<int4>(u * slots);
+        tw.alloc();
+        m.boxes = tw[w_box]; m.rows_src = tw[w_rows];
+        m.segs = tw[w_seg]; m.nruns = tw[w_nr]; m.ro = tw[w_ro];
+        m.areas = tw[w_ar]; m.bboxes = tw[w_bb];
+        m.order = tw[w_ord]; m.pos = tw[w_pos]; m.nelig = tw[w_ne];
+        m.supp = tw[w_sup]; m.out_nruns = tw[w_onr];
+        m.det_src = dev ? a.detections_src : tw[w_ds];
+        m.source = dev ? a.source : tw[w_src];
+        m.n_kept = dev ? a.n_kept : tw[w_nk];
+        m.out_ro = dev ? reinterpret_cast<long long*>(a.run_offsets) : tw[w_oro];
+        m.out_areas = dev && a.areas ? a.areas : tw[w_oar];
+        m.out_bboxes = dev && a.bboxes_xywh ? a.bboxes_xywh : tw[w_obb];
         if (unite) {
-            m.members = reinterpret_cast<int*>(wb + w_mem); m.mspan = reinterpret_cast<int2*>(wb + w_span);
-            m.hull = reinterpret_cast<int4*>(wb + w_hull); m.out_segs = reinterpret_cast<RleSeg*>(wb + w_oseg);
-            m.n_parts = dev && a.n_parts ? a.n_parts : reinterpret_cast<int32_t*>(wb + w_np);
-            m.group = dev && a.group ? a.group : reinterpret_cast<int32_t*>(wb + w_grp);
+            m.members = tw[w_mem]; m.mspan = tw[w_span];
+            m.hull = tw[w_hull]; m.out_segs = tw[w_oseg];
+            m.n_parts = dev && a.n_parts ? a.n_parts : tw[w_np];
+            m.group = dev && a.group ? a.group : tw[w_grp];
         }
         // 1. the boxes, 2. the candidates' runs counted
-        unletterbox_boxes_forward(s, m.det, tab_tile, n_tiles, rows, a.model_h, a.model_w, reinterpret_cast<float*>(wb + w_tile), m.boxes);
+        unletterbox_boxes_forward(s, m.det, tab_tile, n_tiles, rows, a.model_h, a.model_w, tw[w_tile], m.boxes);
         tiles_rle_count_forward(s, m);
         long long need = 0;
         HIP_CHECK(hipMemcpyAsync(&need, m.ro + n, sizeof need, hipMemcpyDeviceToHost, s));
@@ -232,8 +224,7 @@ extern "C" int mrcnn_merge_tiles(const float* detections, const float* masks, co
         const tiles::MergeArgs a = merge_args(detections, masks, tiles, n_tiles, rows, mask_size, heights, widths, n_images, model_h, model_w, threshold,
                                               metric, match_threshold, max_out, detections_src, source, n_kept, counts, capacity, run_offsets, areas,
                                               bboxes_xywh);
-        const int st = tiles::check_merge(a, "merge_tiles", &err);
-        if (st != MRCNN_OK) fail(st, "%s", err.c_str());
+        answer(tiles::check_merge(a, "merge_tiles", &err), err);
         require_gpu();
         TilesRun r(a, memspace, "merge_tiles", false);
         tiles_select_forward(r.s, r.m);                          // 4., 5. suppression bits, greedy scan, the size of the output
@@ -254,8 +245,7 @@ extern "C" int mrcnn_unite_tiles(const float* detections, const float* masks, co
         const tiles::MergeArgs a = merge_args(detections, masks, tiles, n_tiles, rows, mask_size, heights, widths, n_images, model_h, model_w, threshold,
                                               metric, link_threshold, max_out, detections_src, source, n_kept, counts, capacity, run_offsets, areas,
                                               bboxes_xywh, n_parts, group);
-        const int st = tiles::check_merge(a, "unite_tiles", &err, "link_threshold");
-        if (st != MRCNN_OK) fail(st, "%s", err.c_str());
+        answer(tiles::check_merge(a, "unite_tiles", &err, "link_threshold"), err);
         require_gpu();
         TilesRun r(a, memspace, "unite_tiles", true);
         tiles_unite_forward(r.s, r.m);                           // link bits, components, the union planes counted

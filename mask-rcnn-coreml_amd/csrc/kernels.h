@@ -500,13 +500,12 @@ void rle_prefix_forward(hipStream_t s, const uint32_t* counts, const long long* 
 // ================================================================================================
 // Drawing run-length masks (kernels_rle_draw.hip): planes, instance maps and overlays of a ragged batch from an RLE set.
 // ================================================================================================
-struct RleDrawImage { int h, w; long long offset; };              // one image: its size and the byte offset of its output
 // One RLE after rle_draw_prepare: its runs, the positions of its first and last set pixel, its row's pixel box, whether it is drawn
 struct RleDrawRec { long long r0; int nruns; uint32_t first, last; int y1, x1, y2, x2; int drawn; };
 struct RleDrawJob {
     const RleDrawRec* rec;            // n_images * slots
     const uint32_t* pre_b;            // rle_prefix_forward's B, indexed like counts
-    const RleDrawImage* tab;          // n_images
+    const ImageGeom* tab;             // n_images: h, w and the byte offset of the image's output; the rest is not read
     int n_images, slots;
     int max_h, max_w;                 // the largest sides of the batch: the grid
 };

@@ -24,7 +24,9 @@
 // visible_areas: winners are counted per listed row in LDS (a lane merges runs of equal winners first), then one vector
 // atomic per (block, row) that has any.  Bytes before the first and after the last whole chunk go out one by one from block 0.
 #include "kernels.h"
+#include "draw_rule.h"
 #include "paste_device.h"
+#include "scan_device.h"
 
 namespace mrcnn {
 
@@ -35,21 +37,15 @@ struct DrawList {
     int wave_n[DRAW_ROWS / 64];
 };
 
-// the stroke of a box (y1, x1, y2, x2): inside the box grown by `grow`, outside the box shrunk by `shrink` (an empty or inverted
-// inner box contains no pixel: the ring is the whole outer box).  The image clips by itself: only its own pixels are asked.
-__device__ __forceinline__ bool in_ring(const int4 b, int grow, int shrink, int y, int x)
-{
-    const bool outer = y >= b.x - grow && y < b.z + grow && x >= b.y - grow && x < b.w + grow;
-    const bool inner = y >= b.x + shrink && y < b.z - shrink && x >= b.y + shrink && x < b.w - shrink;
-    return outer && !inner;
-}
+// draw_rule.h's stroke for a box kept as (y1, x1, y2, x2)
+__device__ __forceinline__ bool in_ring(const int4 b, int grow, int shrink, int y, int x) { return in_ring(RleDrawBox{b.x, b.y, b.z, b.w}, grow, shrink, y, x); }
 
 // One cull pass: rows [base, base + 256) of the image against the tile's rectangle (inclusive bounds).  Returns the list length.
-// Two barriers inside; the caller puts one more behind its walk before the next pass overwrites the list.
+// Two barriers inside (one of them compact_256's); the caller puts one more behind its walk before the next pass overwrites the list.
 __device__ __forceinline__ int cull_rows(DrawList& L, const int4* __restrict__ bx, const float* __restrict__ det, int rows, int base, float min_score,
                                          int grow, int ty0, int ty1, int tx0, int tx1)
 {
-    const int i = base + (int)threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = base + (int)threadIdx.x;
     bool keep = false;
     int4 b = make_int4(0, 0, 0, 0);
     if (i < rows) {
@@ -57,18 +53,9 @@ __device__ __forceinline__ int cull_rows(DrawList& L, const int4* __restrict__ b
         keep = b.z > b.x && b.w > b.y && det[(size_t)i * 6 + 5] > min_score
             && b.x - grow <= ty1 && b.z + grow > ty0 && b.y - grow <= tx1 && b.w + grow > tx0;
     }
-    const unsigned long long bal = __ballot(keep);
-    if (lane == 0) L.wave_n[wave] = __popcll(bal);
-    __syncthreads();
-    int before = 0, n = 0;
-#pragma unroll
-    for (int k = 0; k < DRAW_ROWS / 64; ++k) {
-        const int c = L.wave_n[k];
-        before += k < wave ? c : 0;
-        n += c;
-    }
+    int n;
+    const int pos = compact_256(keep, L.wave_n, &n);
     if (keep) {
-        const int pos = before + __popcll(bal & ((1ull << lane) - 1ull));
         L.box[pos] = b;
         L.row[pos] = i;
     }
@@ -216,20 +203,7 @@ __global__ __launch_bounds__(256) void k_instance_map(const ImageGeom* __restric
 // ------------------------------------------------------------------------------------------------
 // Rendered overlay: RGB8.  Algorithmic bytes: 3·h·w read + 3·h·w written per image.
 // ------------------------------------------------------------------------------------------------
-// palette[i % 4] of DetectionRenderer.swift:53 — red, blue, green, yellow — as one bit per channel (bit c: channel c is 255)
-__device__ __forceinline__ uint32_t palette_bits(int row) { return (0x3241u >> (4 * (row & 3))) & 7u; }
-// what to do with a pixel: 0 = the source, 0x10 | bits = blend the row's colour in, 0x20 | bits = the colour, opaque
-__device__ __forceinline__ uint32_t pixel_code(int win, int ring)
-{
-    return ring >= 0 ? 0x20u | palette_bits(ring) : (win >= 0 ? 0x10u | palette_bits(win) : 0u);
-}
-__device__ __forceinline__ uint32_t render_byte(uint32_t src, uint32_t code, int ch, int alpha)
-{
-    const uint32_t col = ((code >> ch) & 1u) * 255u;
-    if (code & 0x20u) return col;
-    if (code & 0x10u) return (src * (uint32_t)(256 - alpha) + col * (uint32_t)alpha + 128u) >> 8;
-    return src;
-}
+// The colours and the blend are draw_rule.h's palette_bits, pixel_code and render_byte.
 
 // One tile of 256 lanes × 48 bytes; R = (the first byte of every lane's 48) mod 3, the same for the whole image.
 template <int R, bool RING>

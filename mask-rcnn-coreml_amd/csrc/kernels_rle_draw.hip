@@ -39,7 +39,8 @@
 //                     k_rle_draw<RENDER>   3·h·w read + 3·h·w written per image
 // plus 4 bytes read per run a tile column crosses, and the records.
 #include "kernels.h"
-#include "rle_draw_box.h"
+#include "draw_rule.h"
+#include "scan_device.h"
 
 namespace mrcnn {
 namespace {
@@ -59,12 +60,12 @@ template <> struct RdTile<RD_MAP> { using type = int16_t; };
 
 __global__ __launch_bounds__(256) void k_rle_draw_prepare(const long long* __restrict__ run_offsets, const unsigned long long* __restrict__ totals,
                                                           const uint2* __restrict__ extent, const float* __restrict__ det, float min_score,
-                                                          const RleDrawImage* __restrict__ tab, long n, int slots, RleDrawRec* __restrict__ rec,
+                                                          const ImageGeom* __restrict__ tab, long n, int slots, RleDrawRec* __restrict__ rec,
                                                           unsigned long long* __restrict__ bad)
 {
     const long k = (long)blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
-    const RleDrawImage im = tab[k / slots];
+    const ImageGeom im = tab[k / slots];
     if (totals[k] != (unsigned long long)im.h * (unsigned long long)im.w) atomicMin(bad, (unsigned long long)k);
     RleDrawRec r;
     r.r0 = run_offsets[k];
@@ -83,12 +84,12 @@ __global__ __launch_bounds__(256) void k_rle_draw_prepare(const long long* __res
 }
 
 // One cull pass: slots [base, base + 256) of the image against the tile (inclusive bounds).  Returns the list length.  Two barriers
-// inside; the caller puts one more behind its walk before the next pass overwrites the list.
+// inside (one of them compact_256's); the caller puts one more behind its walk before the next pass overwrites the list.
 template <int MODE>
 __device__ __forceinline__ int rd_cull(RdList& L, const RleDrawRec* __restrict__ rec, int slots, int base, int h, int grow, bool stroke_on,
                                        int ty0, int ty1, int tx0, int tx1)
 {
-    const int i = base + (int)threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = base + (int)threadIdx.x;
     bool keep = false;
     RleDrawRec r{};
     if (i < slots) {
@@ -99,18 +100,9 @@ __device__ __forceinline__ int rd_cull(RdList& L, const RleDrawRec* __restrict__
                 keep |= r.y1 - grow <= ty1 && r.y2 + grow > ty0 && r.x1 - grow <= tx1 && r.x2 + grow > tx0;
         }
     }
-    const unsigned long long bal = __ballot(keep);
-    if (lane == 0) L.wave_n[wave] = __popcll(bal);
-    __syncthreads();
-    int before = 0, n = 0;
-#pragma unroll
-    for (int k = 0; k < RD_LIST / 64; ++k) {
-        const int c = L.wave_n[k];
-        before += k < wave ? c : 0;
-        n += c;
-    }
+    int n;
+    const int pos = compact_256(keep, L.wave_n, &n);
     if (keep) {
-        const int pos = before + __popcll(bal & ((1ull << lane) - 1ull));
         L.rec[pos] = r;
         L.row[pos] = i;
     }
@@ -133,7 +125,7 @@ __device__ __forceinline__ uint32_t rd_walk(const RleDrawRec& r, int i, const ui
         if (B[mid] <= p0) lo = mid; else hi = mid - 1;
     }
     uint32_t mine = 0, pos = p0;
-    const uint32_t code = 0x10u | rle_draw_palette(i);
+    const uint32_t code = pixel_code(i, -1);
     for (int j = lo; pos <= p1 && j < r.nruns; ++j) {
         const uint32_t end = j + 1 < r.nruns ? B[j + 1] : total;
         const uint32_t stop = end < p1 + 1u ? end : p1 + 1u;
@@ -182,7 +174,7 @@ __device__ __forceinline__ void rd_emit(const typename RdTile<MODE>::type (*tile
             uint32_t byte;
             if constexpr (MODE == RD_DECODE) byte = tile[yy][j];
             else if constexpr (MODE == RD_MAP) byte = ((uint32_t)(uint16_t)tile[yy][j >> 1] >> (8 * (j & 1))) & 0xffu;
-            else byte = rle_draw_byte((sv >> (8 * k)) & 0xffu, tile[yy][j / 3], j % 3, alpha);
+            else byte = render_byte((sv >> (8 * k)) & 0xffu, tile[yy][j / 3], j % 3, alpha);
             v |= byte << (8 * k);
         }
         if (whole) *reinterpret_cast<uint32_t*>(dst + j0) = v;
@@ -204,7 +196,7 @@ __global__ __launch_bounds__(256) void k_rle_draw(RleDrawJob job, uint8_t* __res
     const bool stroke_on = grow + shrink > 0;
     for (long u = blockIdx.y; u < units; u += gridDim.y) {
         const int b = MODE == RD_DECODE ? (int)(u / job.slots) : (int)u;
-        const RleDrawImage im = job.tab[b];
+        const ImageGeom im = job.tab[b];
         const int h = im.h, w = im.w;
         const uint32_t total = (uint32_t)h * (uint32_t)w;
         uint8_t* const o = out + im.offset + (MODE == RD_DECODE ? (size_t)(u - (long)b * job.slots) * total : (size_t)0);
@@ -239,9 +231,9 @@ __global__ __launch_bounds__(256) void k_rle_draw(RleDrawJob job, uint8_t* __res
                                 if (x >= bx.x1 - grow && x < bx.x2 + grow) {
                                     const int ya = bx.y1 - grow > ty0 ? bx.y1 - grow : ty0;
                                     const int yb = bx.y2 + grow < ty0 + th ? bx.y2 + grow : ty0 + th;
-                                    const T code = (T)(0x20u | rle_draw_palette(i));
+                                    const T code = (T)pixel_code(-1, i);
                                     for (int y = ya; y < yb; ++y)
-                                        if (!(tile[y - ty0][tid] & 0x20) && rle_draw_ring(bx, grow, shrink, y, x)) tile[y - ty0][tid] = code;
+                                        if (!(tile[y - ty0][tid] & 0x20) && in_ring(bx, grow, shrink, y, x)) tile[y - ty0][tid] = code;
                                 }
                             }
                         }

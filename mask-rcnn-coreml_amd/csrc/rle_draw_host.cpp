@@ -2,28 +2,13 @@
 // kernels_rle_draw.hip are compared with.  Decode the runs, lowest row first; a pixel keeps its first owner.
 #include "rle_draw_host.h"
 
-#include <stdarg.h>
-#include <stdio.h>
-
 #include <algorithm>
 #include <vector>
 
-#include "rle_draw_box.h"
+#include "draw_rule.h"
 
 namespace mrcnn {
 namespace rle_draw {
-
-static int bad(std::string* err, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
-static int bad(std::string* err, int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (err) *err = buf;
-    return code;
-}
 
 // ---- argument checks -----------------------------------------------------------------------------
 int check_set(const Set& s, int max_slots, const char* who, std::string* err)
@@ -32,28 +17,7 @@ int check_set(const Set& s, int max_slots, const char* who, std::string* err)
     if (s.n_images < 0 || s.slots < 0) return bad(err, MRCNN_ERR_INVALID, "%s: n_images %d, slots %d: neither may be negative", who, s.n_images, s.slots);
     if (s.slots > max_slots) return bad(err, MRCNN_ERR_SHAPE, "%s: %d slots are too many (at most %d)", who, s.slots, max_slots);
     if ((int64_t)s.n_images * s.slots >= (1LL << 31)) return bad(err, MRCNN_ERR_SHAPE, "%s: %d x %d RLEs are too many", who, s.n_images, s.slots);
-    for (int b = 0; b < s.n_images; ++b)
-        if (s.heights[b] < 1 || s.heights[b] > 32767 || s.widths[b] < 1 || s.widths[b] > 32767)
-            return bad(err, MRCNN_ERR_SHAPE, "%s: image %d is %dx%d: height and width must lie in 1..32767", who, b, s.heights[b], s.widths[b]);
-    return MRCNN_OK;
-}
-
-int check_offsets(const Set& s, const int64_t* offsets, int64_t unit, const char* who, int64_t* extent, std::string* err)
-{
-    if (!offsets) return bad(err, MRCNN_ERR_INVALID, "%s: null output offsets", who);
-    auto bytes_of = [&](int b) { return unit * s.heights[b] * s.widths[b]; };
-    int64_t end = 0;
-    for (int b = 0; b < s.n_images; ++b) {
-        if (offsets[b] < 0 || offsets[b] % 16 != 0)
-            return bad(err, MRCNN_ERR_INVALID, "%s: image %d: offset %lld is not a non-negative multiple of 16", who, b, (long long)offsets[b]);
-        end = std::max(end, offsets[b] + bytes_of(b));
-    }
-    for (int a = 0; a < s.n_images; ++a)
-        for (int b = a + 1; b < s.n_images; ++b)
-            if (!(offsets[a] + bytes_of(a) <= offsets[b] || offsets[b] + bytes_of(b) <= offsets[a]))
-                return bad(err, MRCNN_ERR_INVALID, "%s: images %d and %d overlap in the output", who, a, b);
-    if (extent) *extent = end;
-    return MRCNN_OK;
+    return check_sides(s.heights, s.widths, s.n_images, who, err);
 }
 
 int check_render(int alpha, int stroke, const char* who, std::string* err)
@@ -109,7 +73,7 @@ int decode_host(const Set& s, uint8_t* out, const int64_t* out_offsets, std::str
     int st = check_set(s, 0x7fffffff, "rle_decode_host", err);
     if (st != MRCNN_OK) return st;
     if (!out) return bad(err, MRCNN_ERR_INVALID, "rle_decode_host: null out");
-    st = check_offsets(s, out_offsets, s.slots, "rle_decode_host", nullptr, err);
+    st = check_offsets(s.heights, s.widths, s.n_images, out_offsets, s.slots, "rle_decode_host", nullptr, err);
     if (st != MRCNN_OK) return st;
     st = check_sums(s, "rle_decode_host", err);
     if (st != MRCNN_OK) return st;
@@ -149,7 +113,7 @@ int instance_map_host(const Set& s, const float* detections_src, float min_score
     if (st != MRCNN_OK) return st;
     if (!detections_src || !map) return bad(err, MRCNN_ERR_INVALID, "instance_map_rle_host: null argument");
     if (reinterpret_cast<uintptr_t>(map) % 2 != 0) return bad(err, MRCNN_ERR_INVALID, "instance_map_rle_host: map is not aligned for int16");
-    st = check_offsets(s, map_offsets, 2, "instance_map_rle_host", nullptr, err);
+    st = check_offsets(s.heights, s.widths, s.n_images, map_offsets, 2, "instance_map_rle_host", nullptr, err);
     if (st != MRCNN_OK) return st;
     st = check_sums(s, "instance_map_rle_host", err);
     if (st != MRCNN_OK) return st;
@@ -175,7 +139,7 @@ int render_host(const Set& s, const mrcnn_image* images, const float* detections
     if (!detections_src || !out_rgb) return bad(err, MRCNN_ERR_INVALID, "render_detections_rle_host: null argument");
     st = check_render(alpha, stroke, "render_detections_rle_host", err);
     if (st != MRCNN_OK) return st;
-    st = check_offsets(t, out_offsets, 3, "render_detections_rle_host", nullptr, err);
+    st = check_offsets(t.heights, t.widths, t.n_images, out_offsets, 3, "render_detections_rle_host", nullptr, err);
     if (st != MRCNN_OK) return st;
     st = check_sums(t, "render_detections_rle_host", err);
     if (st != MRCNN_OK) return st;
@@ -191,13 +155,12 @@ int render_host(const Set& s, const mrcnn_image* images, const float* detections
             if (!rle_draw_drawn(row, box, min_score)) continue;
             for (int y = std::max(0, box.y1 - grow); y < std::min(h, box.y2 + grow); ++y)
                 for (int x = std::max(0, box.x1 - grow); x < std::min(w, box.x2 + grow); ++x)
-                    if (ring[(size_t)y * w + x] < 0 && rle_draw_ring(box, grow, shrink, y, x)) ring[(size_t)y * w + x] = (int16_t)i;
+                    if (ring[(size_t)y * w + x] < 0 && in_ring(box, grow, shrink, y, x)) ring[(size_t)y * w + x] = (int16_t)i;
         }
         const uint8_t* src = images[b].rgb;
         uint8_t* out = out_rgb + out_offsets[b];
         for (size_t p = 0; p < (size_t)h * w; ++p) {
-            const unsigned code = ring[p] >= 0 ? 0x20u | rle_draw_palette(ring[p]) : (own[p] >= 0 ? 0x10u | rle_draw_palette(own[p]) : 0u);
-            for (int ch = 0; ch < 3; ++ch) out[p * 3 + ch] = (uint8_t)rle_draw_byte(src[p * 3 + ch], code, ch, alpha);
+            for (int ch = 0; ch < 3; ++ch) out[p * 3 + ch] = (uint8_t)render_byte(src[p * 3 + ch], pixel_code(own[p], ring[p]), ch, alpha);
         }
     }
     return MRCNN_OK;

@@ -1,13 +1,11 @@
 // rle_draw_host.h — drawing run-length masks, the host half: the argument checks the six entries share and the sequential code that DEFINES
 // the output of mrcnn_rle_decode, mrcnn_instance_map_rle and mrcnn_render_detections_rle (the _host entries).  Plain C++17: no HIP header,
 // builds with g++ alone.  The kernels of kernels_rle_draw.hip must give the same bytes.  The only float arithmetic is the pixel box
-// (rle_draw_box.h: products of a float and an int below 2^15, exact in double), shared with the kernels.
+// (draw_rule.h: products of a float and an int below 2^15, exact in double), shared with the kernels.
 #pragma once
 #include <stddef.h>
-#include <stdint.h>
-#include <string>
 
-#include "../../include/maskrcnn_hip.h"
+#include "ragged.h"
 
 namespace mrcnn {
 namespace rle_draw {
@@ -20,11 +18,9 @@ struct Set {
 };
 
 // What can be answered without reading counts or run_offsets (they may be device memory): null pointers and negative sizes ->
-// MRCNN_ERR_INVALID, a side outside 1..32767 or slots above max_slots -> MRCNN_ERR_SHAPE (the message names the image).
+// MRCNN_ERR_INVALID, a side outside 1..32767 (ragged.h) or slots above max_slots -> MRCNN_ERR_SHAPE (the message names the image).
+// The output offsets are checked by ragged.h's check_offsets.
 int check_set(const Set& s, int max_slots, const char* who, std::string* err);
-// Byte offsets of a ragged output of unit*h_b*w_b bytes per image: each a non-negative multiple of 16, no two ranges overlapping
-// (MRCNN_ERR_INVALID).  *extent = the end of the last range.
-int check_offsets(const Set& s, const int64_t* offsets, int64_t unit, const char* who, int64_t* extent, std::string* err);
 int check_render(int alpha, int stroke, const char* who, std::string* err);
 // run_offsets (host memory, n_images*slots + 1 entries): non-negative and not decreasing (MRCNN_ERR_SHAPE naming the RLE).
 int check_run_offsets(const int64_t* run_offsets, int64_t n, const char* who, std::string* err);

@@ -1,5 +1,7 @@
-// scan_device.h — what the encoders' scan and pack launches share (kernels_jpeg_enc.hip, kernels_png.hip): the search that maps a unit of a
-// ragged batch to its image, and the one-block prefix sums.  Device code only; every loop is bounded by an argument.
+// scan_device.h — the block-wide searches and scans more than one kernel file needs: the search that maps a unit of a ragged batch to its
+// image and the one-block prefix sums of the encoders' scan and pack launches (kernels_jpeg_enc.hip, kernels_png.hip), and the
+// compaction of the drawing kernels' cull passes (kernels_render.hip, kernels_rle_draw.hip).  Device code only; every loop is bounded
+// by an argument.
 #pragma once
 #include <stdint.h>
 
@@ -17,6 +19,26 @@ __device__ inline int last_not_above(int n, long long g, Get first)
         if (first(mid) <= g) lo = mid; else hi = mid - 1;
     }
     return lo;
+}
+
+// Compaction over the 256 threads of a block; every thread calls it.  Returns this thread's position in the list of the threads whose
+// `keep` is set, in thread order, and *n = the list's length.  wave_n: four ints of LDS, free again after the caller's next barrier
+// (one barrier inside).
+__device__ __forceinline__ int compact_256(bool keep, int* wave_n, int* n)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long bal = __ballot(keep);
+    if (lane == 0) wave_n[wave] = __popcll(bal);
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int c = wave_n[k];
+        before += k < wave ? c : 0;
+        all += c;
+    }
+    *n = all;
+    return before + __popcll(bal & ((1ull << lane) - 1ull));
 }
 
 // inclusive sum over the 1024 threads of a block; every thread calls it.  buf is free again when it returns.

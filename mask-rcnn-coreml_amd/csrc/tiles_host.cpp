@@ -2,26 +2,12 @@
 #include "tiles_host.h"
 
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include <algorithm>
 #include <vector>
 
 namespace mrcnn {
 namespace tiles {
-
-static int bad(std::string* err, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
-static int bad(std::string* err, int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (err) *err = buf;
-    return code;
-}
 
 // ---- the planner: one axis ---------------------------------------------------------------------
 static int axis_count(int L, int T, int O) { return L <= T ? 1 : (L - T + (T - O) - 1) / (T - O) + 1; }
@@ -57,9 +43,8 @@ int plan(int height, int width, int tile_h, int tile_w, int overlap_y, int overl
 // ---- argument checks -----------------------------------------------------------------------------
 int check_tiles(const mrcnn_tile* tiles, int n_tiles, const int32_t* heights, const int32_t* widths, int n_images, const char* who, std::string* err)
 {
-    for (int b = 0; b < n_images; ++b)
-        if (heights[b] < 1 || heights[b] > 32767 || widths[b] < 1 || widths[b] > 32767)
-            return bad(err, MRCNN_ERR_SHAPE, "%s: image %d is %dx%d: height and width must lie in 1..32767", who, b, heights[b], widths[b]);
+    const int sides = check_sides(heights, widths, n_images, who, err);
+    if (sides != MRCNN_OK) return sides;
     for (int t = 0; t < n_tiles; ++t) {
         const mrcnn_tile& w = tiles[t];
         if (w.image < 0 || w.image >= n_images) return bad(err, MRCNN_ERR_SHAPE, "%s: tile %d names image %d of %d", who, t, w.image, n_images);

@@ -4,10 +4,8 @@
 // operation (paste_device.h), and the translation unit is compiled without FMA contraction like the kernels.
 #pragma once
 #include <stddef.h>
-#include <stdint.h>
-#include <string>
 
-#include "../../include/maskrcnn_hip.h"
+#include "ragged.h"
 
 namespace mrcnn {
 namespace tiles {

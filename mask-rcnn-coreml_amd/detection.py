@@ -13,6 +13,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
+from ._marshal import Space, image_table, ragged_output, rle_results, sizes_of
 
 
 @dataclass
@@ -81,23 +82,18 @@ def paste_masks_source(detections: np.ndarray, masks: np.ndarray, sizes, model_h
     ``sizes`` = [(h_b, w_b)] → (det_src, [ (rows, h_b, w_b) uint8 per image ]).  det_src holds the boxes normalized in each SOURCE
     image (``mrcnn_unletterbox_boxes``' mapping, done on the GPU), the masks are pasted in each image's own pixels — any width —
     by one launch over the ragged buffer (``mrcnn_paste_masks_source``)."""
-    det = np.ascontiguousarray(detections, dtype=np.float32)
-    m = np.ascontiguousarray(masks, dtype=np.float32)
+    space = Space()
+    det, m = space.f32(detections, masks)
     B, rows = det.shape[0], det.shape[1]
     if len(sizes) != B or m.shape[0] != B or m.shape[1] != rows or det.shape[2] != 6:
         raise ValueError("paste_masks_source: detections (B,rows,6), masks (B,rows,S,S) and B sizes expected")
-    hs = np.array([int(s[0]) for s in sizes], dtype=np.int32)
-    ws = np.array([int(s[1]) for s in sizes], dtype=np.int32)
-    nbytes = rows * hs.astype(np.int64) * ws.astype(np.int64)
-    padded = (nbytes + 15) // 16 * 16                      # every image's planes start on a 16-byte boundary
-    offs = np.concatenate(([0], np.cumsum(padded)[:-1])).astype(np.int64) if B else np.zeros(0, np.int64)
-    out = np.empty(int(padded.sum()), dtype=np.uint8)
+    hs, ws = sizes_of(sizes)
+    out, offs, planes = ragged_output(space, hs, ws, np.uint8, lead=(rows,))
     det_src = np.empty_like(det)
     _lib.check(_lib.lib().mrcnn_paste_masks_source(det.ctypes.data, m.ctypes.data, B, rows, m.shape[2], hs.ctypes.data, ws.ctypes.data,
                                                    model_h, model_w, C.c_float(threshold), _lib.HOST, det_src.ctypes.data,
                                                    out.ctypes.data, offs.ctypes.data))
-    planes = [out[int(offs[b]):int(offs[b] + nbytes[b])].reshape(rows, int(hs[b]), int(ws[b])) for b in range(B)]
-    return det_src, planes
+    return det_src, planes()
 
 
 def masks_rle_source(detections, masks, sizes, model_h: int, model_w: int, threshold: float = 0.5):
@@ -108,52 +104,21 @@ def masks_rle_source(detections, masks, sizes, model_h: int, model_w: int, thres
     place, det_src / areas / bboxes stay on the device (int32 tensors) and only the run offsets and the used part of the run
     lengths come to the host.  A first attempt is sized from the image widths; if the batch needs more, one more call with the
     capacity the library reported."""
-    on_host = isinstance(detections, np.ndarray)
-    if on_host:
-        det = np.ascontiguousarray(detections, dtype=np.float32)
-        m = np.ascontiguousarray(masks, dtype=np.float32)
-    else:
-        import torch
-        det, m = detections, masks
-        assert det.is_cuda and m.is_cuda and det.dtype == torch.float32 and m.dtype == torch.float32 and det.is_contiguous() and m.is_contiguous()
+    space = Space(detections)
+    ptr = space.ptr
+    det, m = space.f32(detections, masks)
     B, rows = int(det.shape[0]), int(det.shape[1])
     if len(sizes) != B or m.shape[0] != B or m.shape[1] != rows or det.shape[2] != 6:
         raise ValueError("masks_rle_source: detections (B,rows,6), masks (B,rows,S,S) and B sizes expected")
-    hs = np.array([int(s[0]) for s in sizes], dtype=np.int32)
-    ws = np.array([int(s[1]) for s in sizes], dtype=np.int32)
-    n = B * rows
-    offsets = np.zeros(n + 1, dtype=np.int64)
-    if on_host:
-        det_src, areas, bboxes = np.empty_like(det), np.empty((B, rows), np.uint32), np.empty((B, rows, 4), np.int32)
-        ptr = lambda a: a.ctypes.data
-        new_counts = lambda k: np.empty(max(1, k), np.uint32)
-        offs_buf = offsets
-    else:
-        det_src = torch.empty_like(det)
-        areas = torch.empty((B, rows), dtype=torch.int32, device=det.device)
-        bboxes = torch.empty((B, rows, 4), dtype=torch.int32, device=det.device)
-        ptr = lambda a: a.data_ptr()
-        new_counts = lambda k: torch.empty(max(1, k), dtype=torch.int32, device=det.device)
-        offs_buf = torch.empty(n + 1, dtype=torch.int64, device=det.device)
+    hs, ws = sizes_of(sizes)
+    det_src, areas, bboxes = space.new(det.shape, np.float32), space.new((B, rows), np.uint32), space.new((B, rows, 4), np.int32)
 
-    def call(capacity):
-        counts = new_counts(capacity)
-        st = _lib.lib().mrcnn_masks_rle_source(ptr(det), ptr(m), B, rows, int(m.shape[2]), hs.ctypes.data, ws.ctypes.data, model_h, model_w,
-                                               C.c_float(threshold), _lib.HOST if on_host else _lib.DEVICE, ptr(det_src), ptr(counts), capacity,
-                                               ptr(offs_buf), ptr(areas), ptr(bboxes))
-        return st, counts
+    def call(counts, capacity, run_offsets):
+        return _lib.lib().mrcnn_masks_rle_source(ptr(det), ptr(m), B, rows, int(m.shape[2]), hs.ctypes.data, ws.ctypes.data, model_h, model_w,
+                                                 C.c_float(threshold), space.code, ptr(det_src), ptr(counts), capacity, ptr(run_offsets),
+                                                 ptr(areas), ptr(bboxes))
     # a mask with one run of ones per column of its image has 2 w + 1 runs: enough for the masks a network draws, not for noise
-    capacity = int(rows * (2 * ws.astype(np.int64) + 2).sum())
-    st, counts = call(capacity)
-    if not on_host:
-        offsets[:] = offs_buf.cpu().numpy()
-    if st == 4 and int(offsets[n]) > capacity:                 # MRCNN_ERR_SHAPE with the offsets complete: the capacity was the reason
-        st, counts = call(int(offsets[n]))
-    _lib.check(st)
-    used = int(offsets[n])
-    host = counts[:used] if on_host else counts[:used].cpu().numpy().view(np.uint32)
-    rles = [[{"size": [int(hs[b]), int(ws[b])], "counts": host[int(offsets[b * rows + i]):int(offsets[b * rows + i + 1])]}
-             for i in range(rows)] for b in range(B)]
+    rles = rle_results(space, B, rows, hs, ws, int(rows * (2 * ws.astype(np.int64) + 2).sum()), call)
     return det_src, rles, areas, bboxes
 
 
@@ -182,15 +147,10 @@ _METRICS = {"iou": _lib.MATCH_IOU, "ios": _lib.MATCH_IOS}
 
 def _merge_tiles(host_definition, detections, masks, tiles, sizes, model_h, model_w, threshold, metric, match_threshold, max_out, unite=False):
     name = "unite_tiles" if unite else "merge_tiles"
-    on_host = isinstance(detections, np.ndarray)
-    if on_host:
-        det = np.ascontiguousarray(detections, dtype=np.float32)
-        m = np.ascontiguousarray(masks, dtype=np.float32)
-    else:
-        import torch
-        det, m = detections, masks
-        assert not host_definition, f"{name}_host takes numpy arrays"
-        assert det.is_cuda and m.is_cuda and det.dtype == torch.float32 and m.dtype == torch.float32 and det.is_contiguous() and m.is_contiguous()
+    space = Space(detections)
+    ptr = space.ptr
+    assert space.on_host or not host_definition, f"{name}_host takes numpy arrays"
+    det, m = space.f32(detections, masks)
     tab = _tile_table(tiles)
     T, rows = int(det.shape[0]), int(det.shape[1])
     if tab.shape[0] != T or m.shape[0] != T or m.shape[1] != rows or det.shape[2] != 6:
@@ -198,51 +158,24 @@ def _merge_tiles(host_definition, detections, masks, tiles, sizes, model_h, mode
     if metric not in _METRICS:
         raise ValueError(f"{name}: metric {metric!r} is neither 'iou' nor 'ios'")
     B = len(sizes)
-    hs = np.array([int(s[0]) for s in sizes], dtype=np.int32)
-    ws = np.array([int(s[1]) for s in sizes], dtype=np.int32)
-    if max_out is None:
-        max_out = rows
-    max_out = int(max_out)
-    slots = max(0, B * max_out)
-    offsets = np.zeros(slots + 1, dtype=np.int64)
-    if on_host:
-        det_src, source, n_kept = np.zeros((B, max(0, max_out), 6), np.float32), np.zeros((B, max(0, max_out)), np.int32), np.zeros(B, np.int32)
-        areas, bboxes = np.zeros((B, max(0, max_out)), np.uint32), np.zeros((B, max(0, max_out), 4), np.int32)
-        n_parts, group = np.zeros((B, max(0, max_out)), np.int32), np.zeros((T, rows), np.int32)
-        ptr = lambda a: a.ctypes.data
-        new_counts = lambda k: np.empty(max(1, k), np.uint32)
-        offs_buf = offsets
-    else:
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=det.device)
-        det_src, source, n_kept = z((B, max(0, max_out), 6), torch.float32), z((B, max(0, max_out)), torch.int32), z((B,), torch.int32)
-        areas, bboxes = z((B, max(0, max_out)), torch.int32), z((B, max(0, max_out), 4), torch.int32)
-        n_parts, group = z((B, max(0, max_out)), torch.int32), z((T, rows), torch.int32)
-        ptr = lambda a: a.data_ptr()
-        new_counts = lambda k: torch.empty(max(1, k), dtype=torch.int32, device=det.device)
-        offs_buf = z((slots + 1,), torch.int64)
+    hs, ws = sizes_of(sizes)
+    max_out = int(rows if max_out is None else max_out)
+    per = max(0, max_out)
+    z = lambda shape, dt: space.new(shape, dt, zero=True)
+    det_src, source, n_kept = z((B, per, 6), np.float32), z((B, per), np.int32), z((B,), np.int32)
+    areas, bboxes = z((B, per), np.uint32), z((B, per, 4), np.int32)
+    n_parts, group = z((B, per), np.int32), z((T, rows), np.int32)
     head = (ptr(det), ptr(m), tab.ctypes.data_as(C.POINTER(_lib.Tile)), T, rows, int(m.shape[2]), hs.ctypes.data, ws.ctypes.data, B,
             int(model_h), int(model_w), C.c_float(threshold), _METRICS[metric], float(match_threshold), max_out)
 
-    def call(capacity):
-        counts = new_counts(capacity)
+    def call(counts, capacity, run_offsets):
         parts = (ptr(n_parts), ptr(group)) if unite else ()
-        tail = (ptr(det_src), ptr(source), ptr(n_kept), *parts, ptr(counts), capacity, ptr(offs_buf), ptr(areas), ptr(bboxes))
+        tail = (ptr(det_src), ptr(source), ptr(n_kept), *parts, ptr(counts), capacity, ptr(run_offsets), ptr(areas), ptr(bboxes))
         if host_definition:
-            return getattr(_lib.lib(), f"mrcnn_{name}_host")(*head, *tail), counts
-        return getattr(_lib.lib(), f"mrcnn_{name}")(*head, _lib.HOST if on_host else _lib.DEVICE, *tail), counts
-    capacity = int(max(1, max_out) * (2 * ws.astype(np.int64) + 2).sum())      # as masks_rle_source sizes its first attempt
-    st, counts = call(capacity)
-    if not on_host:
-        offsets[:] = offs_buf.cpu().numpy()
-    if st == 4 and int(offsets[slots]) > capacity:             # MRCNN_ERR_SHAPE with the offsets complete: the capacity was the reason
-        st, counts = call(int(offsets[slots]))
-        if not on_host:
-            offsets[:] = offs_buf.cpu().numpy()
-    _lib.check(st)
-    used = int(offsets[slots])
-    host = counts[:used] if on_host else counts[:used].cpu().numpy().view(np.uint32)
-    rles = [[{"size": [int(hs[b]), int(ws[b])], "counts": host[int(offsets[b * max_out + i]):int(offsets[b * max_out + i + 1])]}
-             for i in range(max_out)] for b in range(B)]
+            return getattr(_lib.lib(), f"mrcnn_{name}_host")(*head, *tail)
+        return getattr(_lib.lib(), f"mrcnn_{name}")(*head, space.code, *tail)
+    # the first attempt is sized as masks_rle_source sizes its own
+    rles = rle_results(space, B, max_out, hs, ws, int(max(1, max_out) * (2 * ws.astype(np.int64) + 2).sum()), call)
     if unite:
         return det_src, source, n_kept, rles, areas, bboxes, n_parts, group
     return det_src, source, n_kept, rles, areas, bboxes
@@ -287,29 +220,13 @@ def unite_tiles_host(detections, masks, tiles, sizes, model_h: int, model_w: int
     return _merge_tiles(True, detections, masks, tiles, sizes, model_h, model_w, threshold, metric, link_threshold, max_out, unite=True)
 
 
-def _ragged_layout(hs, ws, unit):
-    """Byte offsets of a ragged output with ``unit`` bytes per pixel: every image starts on a 16-byte boundary."""
-    nbytes = unit * hs.astype(np.int64) * ws.astype(np.int64)
-    padded = (nbytes + 15) // 16 * 16
-    offs = np.concatenate(([0], np.cumsum(padded)[:-1])).astype(np.int64) if len(hs) else np.zeros(0, np.int64)
-    return nbytes, offs, int(padded.sum())
-
-
 def _batch_inputs(name, detections, masks, B_expected):
-    """(on_host, det, masks, B, rows, ptr): numpy arrays made contiguous float32, or contiguous float32 CUDA tensors used in place."""
-    on_host = isinstance(detections, np.ndarray)
-    if on_host:
-        det = np.ascontiguousarray(detections, dtype=np.float32)
-        m = np.ascontiguousarray(masks, dtype=np.float32)
-        ptr = lambda a: a.ctypes.data
-    else:
-        import torch
-        det, m = detections, masks
-        assert det.is_cuda and m.is_cuda and det.dtype == torch.float32 and m.dtype == torch.float32 and det.is_contiguous() and m.is_contiguous()
-        ptr = lambda a: a.data_ptr()
+    """(space, det, masks, B, rows): numpy arrays made contiguous float32, or contiguous float32 CUDA tensors used in place."""
+    space = Space(detections)
+    det, m = space.f32(detections, masks)
     if det.ndim != 3 or m.ndim != 4 or det.shape[2] != 6 or m.shape[0] != det.shape[0] or m.shape[1] != det.shape[1] or B_expected != det.shape[0]:
         raise ValueError(f"{name}: detections (B,rows,6), masks (B,rows,S,S) and B images / sizes expected")
-    return on_host, det, m, int(det.shape[0]), int(det.shape[1]), ptr
+    return space, det, m, int(det.shape[0]), int(det.shape[1])
 
 
 def instance_map_source(detections, masks, sizes, model_h: int, model_w: int, threshold: float = 0.5, min_score: float = 0.0):
@@ -319,22 +236,15 @@ def instance_map_source(detections, masks, sizes, model_h: int, model_w: int, th
     pixels row i owns.  The planes are never pasted.  numpy in → numpy out; torch CUDA tensors in → the device buffers are used in
     place and torch tensors come back (visible as int32)."""
     sizes = list(sizes)
-    on_host, det, m, B, rows, ptr = _batch_inputs("instance_map_source", detections, masks, len(sizes))
-    hs = np.array([int(s[0]) for s in sizes], dtype=np.int32)
-    ws = np.array([int(s[1]) for s in sizes], dtype=np.int32)
-    nbytes, offs, total = _ragged_layout(hs, ws, 2)
-    if on_host:
-        det_src, out, visible = np.empty_like(det), np.empty(max(1, total // 2), np.int16), np.zeros((B, rows), np.uint32)
-    else:
-        import torch
-        det_src = torch.empty_like(det)
-        out = torch.empty(max(1, total // 2), dtype=torch.int16, device=det.device)
-        visible = torch.zeros((B, rows), dtype=torch.int32, device=det.device)
+    space, det, m, B, rows = _batch_inputs("instance_map_source", detections, masks, len(sizes))
+    ptr = space.ptr
+    hs, ws = sizes_of(sizes)
+    out, offs, maps = ragged_output(space, hs, ws, np.int16)
+    det_src, visible = space.new(det.shape, np.float32), space.new((B, rows), np.uint32, zero=True)
     _lib.check(_lib.lib().mrcnn_instance_map_source(ptr(det), ptr(m), B, rows, int(m.shape[2]), hs.ctypes.data, ws.ctypes.data, model_h, model_w,
-                                                    C.c_float(threshold), C.c_float(min_score), _lib.HOST if on_host else _lib.DEVICE,
+                                                    C.c_float(threshold), C.c_float(min_score), space.code,
                                                     ptr(det_src), ptr(out), offs.ctypes.data, ptr(visible)))
-    maps = [out[int(offs[b]) // 2:int(offs[b] + nbytes[b]) // 2].reshape(int(hs[b]), int(ws[b])) for b in range(B)]
-    return det_src, maps, visible
+    return det_src, maps(), visible
 
 
 def render_detections_source(images, detections, masks, model_h: int, model_w: int, threshold: float = 0.5, min_score: float = 0.7,
@@ -345,31 +255,14 @@ def render_detections_source(images, detections, masks, model_h: int, model_w: i
     the box stroked ``stroke`` pixels wide, opaque, the mask blended in with ``alpha``/256 (256 = the reference's opaque fill); the
     lowest row wins a contested pixel.  numpy in → numpy out; torch CUDA tensors in → used in place, torch tensors returned."""
     images = list(images)
-    on_host, det, m, B, rows, ptr = _batch_inputs("render_detections_source", detections, masks, len(images))
-    table = (_lib.Image * max(1, B))()
-    keep = []
-    for b, im in enumerate(images):
-        if on_host:
-            im = np.ascontiguousarray(im, dtype=np.uint8)
-        else:
-            import torch
-            assert im.is_cuda and im.dtype == torch.uint8 and im.is_contiguous()
-        if im.ndim != 3 or im.shape[2] != 3:
-            raise ValueError(f"image {b} has shape {tuple(im.shape)}, expected (h, w, 3)")
-        keep.append(im)
-        table[b].rgb, table[b].height, table[b].width = ptr(im), int(im.shape[0]), int(im.shape[1])
-    hs = np.array([int(im.shape[0]) for im in keep], dtype=np.int32)
-    ws = np.array([int(im.shape[1]) for im in keep], dtype=np.int32)
-    nbytes, offs, total = _ragged_layout(hs, ws, 3)
-    if on_host:
-        out = np.empty(max(1, total), np.uint8)
-    else:
-        import torch
-        out = torch.empty(max(1, total), dtype=torch.uint8, device=det.device)
+    space, det, m, B, rows = _batch_inputs("render_detections_source", detections, masks, len(images))
+    ptr = space.ptr
+    table, _, keep, hs, ws = image_table(images, space)
+    out, offs, drawn = ragged_output(space, hs, ws, np.uint8, trail=(3,))
     _lib.check(_lib.lib().mrcnn_render_detections_source(table, ptr(det), ptr(m), B, rows, int(m.shape[2]), model_h, model_w, C.c_float(threshold),
-                                                         C.c_float(min_score), int(alpha), int(stroke), _lib.HOST if on_host else _lib.DEVICE,
+                                                         C.c_float(min_score), int(alpha), int(stroke), space.code,
                                                          None, ptr(out), offs.ctypes.data))
-    return [out[int(offs[b]):int(offs[b] + nbytes[b])].reshape(int(hs[b]), int(ws[b]), 3) for b in range(B)]
+    return drawn()
 
 
 # ---- drawing run-length masks (mrcnn_rle_decode, mrcnn_instance_map_rle, mrcnn_render_detections_rle) ------------------------------------
@@ -420,26 +313,17 @@ def _rle_set(name, rles, sizes, device):
         offs = torch.from_numpy(offs.copy()).to(device)
     if isinstance(counts, np.ndarray) and counts.size == 0:
         counts = np.zeros(1, np.uint32)
-    hs = np.array([int(s[0]) for s in sizes], dtype=np.int32)
-    ws = np.array([int(s[1]) for s in sizes], dtype=np.int32)
-    return counts, offs, B, slots, hs, ws
+    return (counts, offs, B, slots, *sizes_of(sizes))
 
 
 def _rle_rows(name, det_src, B, slots, host_definition):
-    """(on_host, det_src, ptr) for the (B, slots, 6) source-frame rows that go with an RLE set."""
-    on_host = isinstance(det_src, np.ndarray)
-    if on_host:
-        det = np.ascontiguousarray(det_src, dtype=np.float32)
-        ptr = lambda a: a.ctypes.data
-    else:
-        import torch
-        det = det_src
-        assert not host_definition, f"{name}_host takes numpy arrays"
-        assert det.is_cuda and det.dtype == torch.float32 and det.is_contiguous()
-        ptr = lambda a: a.data_ptr()
+    """(space, det_src) for the (B, slots, 6) source-frame rows that go with an RLE set."""
+    space = Space(det_src)
+    assert space.on_host or not host_definition, f"{name}_host takes numpy arrays"
+    det, = space.f32(det_src)
     if det.ndim != 3 or det.shape[0] != B or det.shape[1] != slots or det.shape[2] != 6:
         raise ValueError(f"{name}: det_src {tuple(det.shape)} does not go with {B} images of {slots} RLEs: ({B}, {slots}, 6) expected")
-    return on_host, det, ptr
+    return space, det
 
 
 def _rle_decode_planes(host_definition, rles, sizes, device):
@@ -447,20 +331,15 @@ def _rle_decode_planes(host_definition, rles, sizes, device):
     if device is None and not host_definition and isinstance(rles, tuple) and len(rles) == 2 and hasattr(rles[0], "is_cuda"):
         device = rles[0].device                                  # a pair of CUDA tensors: used in place, tensors out
     counts, offs, B, slots, hs, ws = _rle_set(name, rles, sizes, device)
-    nbytes, out_offs, total = _ragged_layout(hs, ws, max(1, slots))
-    if device is None:
-        out = np.empty(max(1, total), np.uint8)
-        ptr = lambda a: a.ctypes.data
-    else:
-        import torch
-        out = torch.empty(max(1, total), dtype=torch.uint8, device=device)
-        ptr = lambda a: a.data_ptr()
+    space = Space(device)
+    ptr = space.ptr
+    out, out_offs, planes = ragged_output(space, hs, ws, np.uint8, lead=(slots,))
     head = (ptr(counts), ptr(offs), B, slots, hs.ctypes.data, ws.ctypes.data)
     if host_definition:
         _lib.check(_lib.lib().mrcnn_rle_decode_host(*head, ptr(out), out_offs.ctypes.data))
     else:
-        _lib.check(_lib.lib().mrcnn_rle_decode(*head, _lib.HOST if device is None else _lib.DEVICE, ptr(out), out_offs.ctypes.data))
-    return [out[int(out_offs[b]):int(out_offs[b]) + slots * int(hs[b]) * int(ws[b])].reshape(slots, int(hs[b]), int(ws[b])) for b in range(B)]
+        _lib.check(_lib.lib().mrcnn_rle_decode(*head, space.code, ptr(out), out_offs.ctypes.data))
+    return planes()
 
 
 def rle_decode_planes(rles, sizes=None, device=None):
@@ -479,24 +358,18 @@ def rle_decode_planes_host(rles, sizes=None):
 
 def _instance_map_rle(host_definition, det_src, rles, sizes, min_score):
     name = "instance_map_rle_host" if host_definition else "instance_map_rle"
-    on_host = isinstance(det_src, np.ndarray)
-    counts, offs, B, slots, hs, ws = _rle_set(name, rles, sizes, None if on_host else det_src.device)
-    on_host, det, ptr = _rle_rows(name, det_src, B, slots, host_definition)
-    nbytes, map_offs, total = _ragged_layout(hs, ws, 2)
-    if on_host:
-        out, visible = np.empty(max(1, total // 2), np.int16), np.zeros((B, slots), np.uint32)
-    else:
-        import torch
-        out = torch.empty(max(1, total // 2), dtype=torch.int16, device=det.device)
-        visible = torch.zeros((B, slots), dtype=torch.int32, device=det.device)
+    counts, offs, B, slots, hs, ws = _rle_set(name, rles, sizes, Space(det_src).device)
+    space, det = _rle_rows(name, det_src, B, slots, host_definition)
+    ptr = space.ptr
+    out, map_offs, maps = ragged_output(space, hs, ws, np.int16)
+    visible = space.new((B, slots), np.uint32, zero=True)
     head = (ptr(det), ptr(counts), ptr(offs), B, slots, hs.ctypes.data, ws.ctypes.data, C.c_float(min_score))
     tail = (ptr(out), map_offs.ctypes.data, ptr(visible))
     if host_definition:
         _lib.check(_lib.lib().mrcnn_instance_map_rle_host(*head, *tail))
     else:
-        _lib.check(_lib.lib().mrcnn_instance_map_rle(*head, _lib.HOST if on_host else _lib.DEVICE, *tail))
-    maps = [out[int(map_offs[b]) // 2:int(map_offs[b] + nbytes[b]) // 2].reshape(int(hs[b]), int(ws[b])) for b in range(B)]
-    return maps, visible
+        _lib.check(_lib.lib().mrcnn_instance_map_rle(*head, space.code, *tail))
+    return maps(), visible
 
 
 def instance_map_rle(det_src, rles, sizes=None, min_score: float = 0.0):
@@ -516,34 +389,18 @@ def instance_map_rle_host(det_src, rles, sizes=None, min_score: float = 0.0):
 def _render_detections_rle(host_definition, images, det_src, rles, min_score, alpha, stroke):
     name = "render_detections_rle_host" if host_definition else "render_detections_rle"
     images = list(images)
-    on_host = isinstance(det_src, np.ndarray)
     sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
-    counts, offs, B, slots, hs, ws = _rle_set(name, rles, sizes, None if on_host else det_src.device)
-    on_host, det, ptr = _rle_rows(name, det_src, B, slots, host_definition)
-    table = (_lib.Image * max(1, B))()
-    keep = []
-    for b, im in enumerate(images):
-        if on_host:
-            im = np.ascontiguousarray(im, dtype=np.uint8)
-        else:
-            import torch
-            assert im.is_cuda and im.dtype == torch.uint8 and im.is_contiguous()
-        if im.ndim != 3 or im.shape[2] != 3:
-            raise ValueError(f"image {b} has shape {tuple(im.shape)}, expected (h, w, 3)")
-        keep.append(im)
-        table[b].rgb, table[b].height, table[b].width = ptr(im), int(im.shape[0]), int(im.shape[1])
-    nbytes, out_offs, total = _ragged_layout(hs, ws, 3)
-    if on_host:
-        out = np.empty(max(1, total), np.uint8)
-    else:
-        import torch
-        out = torch.empty(max(1, total), dtype=torch.uint8, device=det.device)
+    counts, offs, B, slots, hs, ws = _rle_set(name, rles, sizes, Space(det_src).device)
+    space, det = _rle_rows(name, det_src, B, slots, host_definition)
+    ptr = space.ptr
+    table, _, keep, hs, ws = image_table(images, space)
+    out, out_offs, drawn = ragged_output(space, hs, ws, np.uint8, trail=(3,))
     head = (table, ptr(det), ptr(counts), ptr(offs), B, slots, C.c_float(min_score), int(alpha), int(stroke))
     if host_definition:
         _lib.check(_lib.lib().mrcnn_render_detections_rle_host(*head, ptr(out), out_offs.ctypes.data))
     else:
-        _lib.check(_lib.lib().mrcnn_render_detections_rle(*head, _lib.HOST if on_host else _lib.DEVICE, ptr(out), out_offs.ctypes.data))
-    return [out[int(out_offs[b]):int(out_offs[b] + nbytes[b])].reshape(int(hs[b]), int(ws[b]), 3) for b in range(B)]
+        _lib.check(_lib.lib().mrcnn_render_detections_rle(*head, space.code, ptr(out), out_offs.ctypes.data))
+    return drawn()
 
 
 def render_detections_rle(images, det_src, rles, min_score: float = 0.7, alpha: int = 128, stroke: int = 3):

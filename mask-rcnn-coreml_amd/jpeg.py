@@ -14,7 +14,7 @@ from typing import List, Sequence, Tuple
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _marshal
 
 
 def _view(data) -> np.ndarray:
@@ -144,25 +144,8 @@ def encode_host(rgb, quality: int = 90, sampling="420") -> bytes:
 
 def image_table(images):
     """list of (h, w, 3) uint8 numpy arrays or CUDA tensors → (mrcnn_image table, memspace, what keeps the pixels alive)."""
-    images = list(images)
-    table = (_lib.Image * max(1, len(images)))()
-    on_host = len(images) == 0 or isinstance(images[0], np.ndarray)
-    keep = []
-    for b, im in enumerate(images):
-        if on_host:
-            im = np.ascontiguousarray(im, dtype=np.uint8)
-            ptr = im.ctypes.data
-        else:
-            import torch
-            if not (im.is_cuda and im.dtype == torch.uint8):
-                raise ValueError(f"image {b}: expected a uint8 CUDA tensor")
-            im = im.contiguous()
-            ptr = im.data_ptr()
-        if im.ndim != 3 or im.shape[2] != 3:
-            raise ValueError(f"image {b} has shape {tuple(im.shape)}, expected (h, w, 3)")
-        keep.append(im)
-        table[b].rgb, table[b].height, table[b].width = ptr, int(im.shape[0]), int(im.shape[1])
-    return table, (_lib.HOST if on_host else _lib.DEVICE), keep
+    table, space, keep, _, _ = _marshal.image_table(images)
+    return table, space.code, keep
 
 
 def encode_batch(images, quality: int = 90, sampling="420") -> List[bytes]:

@@ -17,6 +17,7 @@ from typing import Dict, Optional
 import numpy as np
 
 from . import _lib
+from ._marshal import image_table
 from .config import MaskRCNNConfig
 
 # f32s / f32x3: fp32 tensors, 2- / 3-part split-fp16 MFMA.  "default" = MRCNN_DEFAULT (include/maskrcnn_hip.h): what the artefact is prepared
@@ -121,33 +122,11 @@ class MaskRCNN(_Model):
         or of uint8 CUDA tensors, in which case the results stay on the device.  Every image is letterboxed with its own geometry
         inside the one pre-processing launch; row b equals predict_scalefit(images[b][None]).  Returns (det, mask) like
         predict_scalefit: boxes normalized in the letterboxed frame (detection.paste_masks_source maps them back)."""
-        images = list(images)
-        B = len(images)
-        table = (_lib.Image * max(1, B))()
-        on_host = B == 0 or isinstance(images[0], np.ndarray)
-        keep = []
-        for b, im in enumerate(images):
-            if on_host:
-                im = np.ascontiguousarray(im, dtype=np.uint8)
-                ptr = im.ctypes.data
-            else:
-                import torch
-                assert im.is_cuda and im.dtype == torch.uint8 and im.is_contiguous()
-                ptr = im.data_ptr()
-            if im.ndim != 3 or im.shape[2] != 3:
-                raise ValueError(f"image {b} has shape {tuple(im.shape)}, expected (h, w, 3)")
-            keep.append(im)
-            table[b].rgb, table[b].height, table[b].width = ptr, int(im.shape[0]), int(im.shape[1])
-        shape_d = (B, self.max_detections, 6)
-        shape_m = (B, self.max_detections, self.mask_size, self.mask_size)
-        if on_host:
-            det, mask = np.empty(shape_d, dtype=np.float32), np.empty(shape_m, dtype=np.float32)
-            _lib.check(_lib.lib().mrcnn_maskrcnn_predict_images(self._h, table, B, _lib.HOST, det.ctypes.data, mask.ctypes.data))
-        else:
-            import torch
-            det = torch.empty(shape_d, dtype=torch.float32, device=images[0].device)
-            mask = torch.empty(shape_m, dtype=torch.float32, device=images[0].device)
-            _lib.check(_lib.lib().mrcnn_maskrcnn_predict_images(self._h, table, B, _lib.DEVICE, det.data_ptr(), mask.data_ptr()))
+        table, space, keep, _, _ = image_table(images)
+        B = len(keep)
+        det = space.new((B, self.max_detections, 6), np.float32)
+        mask = space.new((B, self.max_detections, self.mask_size, self.mask_size), np.float32)
+        _lib.check(_lib.lib().mrcnn_maskrcnn_predict_images(self._h, table, B, space.code, space.ptr(det), space.ptr(mask)))
         return det, mask
 
     def predict_tiles(self, images, tiles):
@@ -155,35 +134,12 @@ class MaskRCNN(_Model):
         int32 table of (image, y0, x0, height, width) (detection.tile_plan).  Record t equals predict_images on a contiguous copy
         of window t; every image crosses to the device once.  Any number of tiles: the call runs them max_batch at a time."""
         from .detection import _tile_table
-        images = list(images)
         tab = _tile_table(tiles)
-        B, T = len(images), int(tab.shape[0])
-        table = (_lib.Image * max(1, B))()
-        on_host = B == 0 or isinstance(images[0], np.ndarray)
-        keep = []
-        for b, im in enumerate(images):
-            if on_host:
-                im = np.ascontiguousarray(im, dtype=np.uint8)
-                ptr = im.ctypes.data
-            else:
-                import torch
-                assert im.is_cuda and im.dtype == torch.uint8 and im.is_contiguous()
-                ptr = im.data_ptr()
-            if im.ndim != 3 or im.shape[2] != 3:
-                raise ValueError(f"image {b} has shape {tuple(im.shape)}, expected (h, w, 3)")
-            keep.append(im)
-            table[b].rgb, table[b].height, table[b].width = ptr, int(im.shape[0]), int(im.shape[1])
-        shape_d = (T, self.max_detections, 6)
-        shape_m = (T, self.max_detections, self.mask_size, self.mask_size)
-        tp = tab.ctypes.data_as(C.POINTER(_lib.Tile))
-        if on_host:
-            det, mask = np.empty(shape_d, dtype=np.float32), np.empty(shape_m, dtype=np.float32)
-            _lib.check(_lib.lib().mrcnn_maskrcnn_predict_tiles(self._h, table, B, tp, T, _lib.HOST, det.ctypes.data, mask.ctypes.data))
-        else:
-            import torch
-            det = torch.empty(shape_d, dtype=torch.float32, device=images[0].device)
-            mask = torch.empty(shape_m, dtype=torch.float32, device=images[0].device)
-            _lib.check(_lib.lib().mrcnn_maskrcnn_predict_tiles(self._h, table, B, tp, T, _lib.DEVICE, det.data_ptr(), mask.data_ptr()))
+        table, space, keep, _, _ = image_table(images)
+        B, T = len(keep), int(tab.shape[0])
+        det = space.new((T, self.max_detections, 6), np.float32)
+        mask = space.new((T, self.max_detections, self.mask_size, self.mask_size), np.float32)
+        _lib.check(_lib.lib().mrcnn_maskrcnn_predict_tiles(self._h, table, B, tab.ctypes.data_as(C.POINTER(_lib.Tile)), T, space.code, space.ptr(det), space.ptr(mask)))
         return det, mask
 
     def predict_tiled(self, images, tile=None, overlap=(64, 64), metric="ios", match_threshold=0.5, max_out=None, threshold=0.5,

@@ -97,6 +97,7 @@ def test_bad_arguments():
     assert call(2, [0, 8192]) == 0
     assert call(2, [0, 8200]) == 1                      # not a multiple of 16
     assert call(2, [0, 4720]) == 1                      # 35*45*3 = 4725 bytes: the second image starts inside the first
+    assert call(2, [4800, 16]) == 1                     # 40*40*3 = 4800 bytes from 16: the second image ends inside the first
     assert call(2, [0, 8192], None) == 1                # null output
     assert call(0, [0, 8192]) == 4 and call(1025, [0, 8192]) == 4
     assert not out[8192 + 40 * 40 * 3:].any()

@@ -20,7 +20,7 @@
 #include <string>
 #include <vector>
 
-#include "rle_draw_box.h"
+#include "draw_rule.h"
 #include "rle_draw_host.h"
 
 using namespace mrcnn;
@@ -129,7 +129,7 @@ int main()
                         const RleDrawBox bx = rle_draw_box(r, h, w);
                         if (!(r[5] > min_score && r[5] > 0.0f && bx.y2 > bx.y1 && bx.x2 > bx.x1)) continue;
                         if (own < 0 && planes[(size_t)k][(size_t)y * w + x]) own = i;
-                        if (ring < 0 && stroke > 0 && rle_draw_ring(bx, grow, shrink, y, x)) ring = i;
+                        if (ring < 0 && stroke > 0 && in_ring(bx, grow, shrink, y, x)) ring = i;
                     }
                     reinterpret_cast<int16_t*>(reinterpret_cast<uint8_t*>(w_map.data()) + o_map[(size_t)b])[(size_t)y * w + x] = (int16_t)own;
                     static const int pal[4][3] = {{255, 0, 0}, {0, 0, 255}, {0, 255, 0}, {255, 255, 0}};
