@@ -289,6 +289,66 @@ extern "C" int mrcnn_bottleneck_nhwc(const float* x, int batch, int h, int w, in
     });
 }
 
+// A chained pair of the split modes on caller (host) data (kernels_conv_chain.hip): P = branch2c (t2 -> y, + residual x or the shortcut convolution
+// ws of xs, ReLU) and Q = the next block's branch2a (y -> t1, ReLU).  chained = 1: the one launch whatever the grid size; 0: the two launches.
+// tests/test_gpu_conv_chain.py compares them bit for bit.
+extern "C" int mrcnn_conv_chain_nhwc(const float* t2, int batch, int h, int w, int cmid, const float* w3, const float* s3, const float* h3, const float* x,
+                                     const float* xs, int cs, int ss, const float* ws, const float* s_s, const float* h_s,
+                                     const float* w1, const float* s1, const float* h1, int dtype, int chained, int in_place, float* y, float* t1)
+{
+    return guarded([&] {
+        require_gpu();
+        MRCNN_REQUIRE(t2 && w3 && s3 && h3 && w1 && s1 && h1 && y && t1 && batch >= 1 && h >= 1 && w >= 1 && cmid >= 32 && cmid % 32 == 0, MRCNN_ERR_INVALID, "bad conv_chain_nhwc argument");
+        MRCNN_REQUIRE((x != nullptr) != (xs != nullptr), MRCNN_ERR_INVALID, "conv_chain_nhwc: either the residual x or the shortcut's input xs");
+        MRCNN_REQUIRE(!xs || (ws && s_s && h_s && cs >= 32 && cs % 32 == 0 && ss >= 1), MRCNN_ERR_INVALID, "conv_chain_nhwc: the shortcut's operands");
+        MRCNN_REQUIRE(dtype == MRCNN_F32S || dtype == MRCNN_F32X3, MRCNN_ERR_UNSUPPORTED, "conv_chain_nhwc: dtype %d (split modes only)", dtype);
+        const int C = cmid, C4 = 4 * cmid;
+        const int wdt = dtype == MRCNN_F32X3 ? MRCNN_F32X3 : MRCNN_F16;
+        const size_t npix = (size_t)batch * h * w;
+        DevBuf dt2, dw3, ds3, dh3, dx, dxs, dws, dss, dhs, dw1, ds1, dh1, dy, dt1;
+        upload_f32(dt2, t2, npix * C);
+        upload_f16(dw3, w3, (size_t)C4 * C); upload_f32(ds3, s3, C4); upload_f32(dh3, h3, C4);
+        upload_f16(dw1, w1, (size_t)C * C4); upload_f32(ds1, s1, C); upload_f32(dh1, h1, C);
+        dx.alloc(npix * C4 * 4);          // the residual: the caller's x, or the shortcut tensor of the two-launch form
+        if (x) HIP_CHECK(hipMemcpy(dx.p, x, npix * C4 * 4, hipMemcpyHostToDevice));
+        else {
+            HIP_CHECK(hipMemset(dx.p, 0xff, npix * C4 * 4));
+            upload_f32(dxs, xs, (size_t)batch * (h * ss) * (w * ss) * cs);
+            upload_f16(dws, ws, (size_t)C4 * cs); upload_f32(dss, s_s, C4); upload_f32(dhs, h_s, C4);
+        }
+        dy.alloc(npix * C4 * 4); dt1.alloc(npix * C * 4);
+        HIP_CHECK(hipMemset(dy.p, 0xff, npix * C4 * 4));
+        HIP_CHECK(hipMemset(dt1.p, 0xff, npix * C * 4));
+        void* const yout = in_place ? dx.p : dy.p;
+        auto desc = [&](const void* in, int hh, int ww, int cin, const void* wgt, int stride, const float* sc, const float* sh, void* o, int cout, int act) {
+            ConvDesc d = dense_nhwc_desc(in, batch, hh, ww, cin, wgt, 1, stride, sc, sh, o, cout, cout, act);
+            d.dtype = MRCNN_F32; d.wdtype = wdt;
+            return d;
+        };
+        ConvDesc dP = desc(dt2.p, h, w, C, dw3.p, 1, ds3.as<float>(), dh3.as<float>(), yout, C4, ACT_RELU);
+        set_dense_residual(dP, dx.p);
+        ConvDesc dQ = desc(yout, h, w, C4, dw1.p, 1, ds1.as<float>(), dh1.as<float>(), dt1.p, C, ACT_RELU);
+        ConvDesc dS;
+        if (xs) dS = desc(dxs.p, h * ss, w * ss, cs, dws.p, ss, dss.as<float>(), dhs.as<float>(), dx.p, C4, ACT_NONE);
+        MRCNN_REQUIRE(!xs || (dS.OH == h && dS.OW == w), MRCNN_ERR_SHAPE, "conv_chain_nhwc: the shortcut's output is not %d x %d", h, w);
+        MRCNN_REQUIRE(!chained || conv_chain_fusable(dP, dQ, xs ? &dS : nullptr), MRCNN_ERR_UNSUPPORTED, "conv_chain_nhwc: C %d at %dx%d does not qualify for the chained launch", C, h, w);
+        // the policy knob for the length of the call: 3 = chained at every grid size, the shortcut riding too; 0 = the two launches
+        struct ScopedKnob {
+            std::vector<std::pair<int*, int>> saved;
+            ScopedKnob(const char* key, int v) { const auto r = knob_table().by_key.equal_range(key); for (auto it = r.first; it != r.second; ++it) { saved.emplace_back(it->second, *it->second); *it->second = v; } }
+            ~ScopedKnob() { for (auto& kv : saved) *kv.first = kv.second; }
+        } knob_scope("conv_chain", chained ? 3 : 0);
+        Stream st;
+        ScopedConvScratch scratch(true);
+        ScopedRangeFlag range(st.s, true);
+        conv_forward_chain(st.s, dP, dQ, xs ? &dS : nullptr);
+        HIP_CHECK(hipStreamSynchronize(st.s));
+        range.keep();
+        HIP_CHECK(hipMemcpy(y, yout, npix * C4 * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(t1, dt1.p, npix * C * 4, hipMemcpyDeviceToHost));
+    });
+}
+
 // The stage-entry block (res2a of the fp16 mode: x (B,H,W,C) -> (B,H,W,4C), shortcut = the 1x1 convolution ws of x) — fused = 1: one launch
 // (kernels_bneck.hip, FIRST form); 0: the four launches.  tests/test_gpu_bneck.py compares them bit for bit.
 extern "C" int mrcnn_bottleneck_first_nhwc(const float* x, int batch, int h, int w, int cmid, const float* w1, const float* w2, const float* w3, const float* ws,

@@ -12,6 +12,7 @@ namespace mrcnn {
 
 void conv_mfma_launch(hipStream_t s, const ConvArgs& a, int mode, int bn, bool wide_waves);   // kernels_conv.hip: 0 fp16, 1 exact fp32, 2 / 3 split parts
 void conv_pp_launch(hipStream_t s, const ConvArgs& a, int mode);   // kernels_conv_pp.hip: 0 fp16, 2 / 3 split parts
+void conv_chain_launch(hipStream_t s, const ConvArgs& p, const ConvArgs& q, int parts, bool wlds, int n_cus);   // kernels_conv_chain.hip: split parts 2 / 3
 
 // ---- what a layer description says about its mode and geometry --------------------------------------------------------------
 static inline int conv_wdtype(const ConvDesc& d) { return d.wdtype < 0 ? d.dtype : d.wdtype; }
@@ -165,6 +166,9 @@ static int& g_ksplit = knob("conv_ksplit", "MRCNN_KSPLIT", 1);
 static int& g_ksplit_below = knob("conv_ksplit_below", "MRCNN_KSPLIT_BELOW", 256);       // share tiles when the widest-tile grid has fewer blocks than this
 static int& g_halo = knob("conv_halo", "MRCNN_HALO", 1);        // 3x3 stride-1 layers of the split modes on the halo kernel (kernels_conv_halo.hip) when the filters come re-tiled
 bool conv_halo_enabled() { return g_halo != 0; }
+// Split modes: a bottleneck's branch2c and the NEXT block's branch2a as one launch (kernels_conv_chain.hip; bit-identical to the two launches):
+// 0 never, 1 by policy (conv_forward_chain), 2 at every grid size (tests), 3 as 2 with the entry block's shortcut riding at every grid size too (mrcnn_conv_chain_nhwc)
+static int& g_chain = knob("conv_chain", "MRCNN_CHAIN", 1);
 static int& g_tn4 = knob("conv_tn4", nullptr, -1);       // split modes, 128x128 tile as 4 waves of 32x128: -1 by policy (conv_forward), 0 never, 1 always (tests)
 
 // The 256 x 256 ping-pong kernel's policy.
@@ -257,9 +261,9 @@ static bool conv_shortcut_fusable(const ConvDesc& m, const ConvDesc& sc)
     return true;
 }
 
-void conv_forward(hipStream_t s, const ConvDesc& d_in, const ConvDesc* sc)
+// Does `sc` ride in d_in's launch (conv_forward), or run first as its own?
+static bool conv_shortcut_rides(const ConvDesc& d_in, const ConvDesc* sc)
 {
-    // a shortcut that cannot ride in this launch runs first, as its own (its output is this layer's residual)
     bool fuse = sc && g_scfuse && conv_shortcut_fusable(d_in, *sc) && conv_k_chunks(d_in) == 1 && conv_k_chunks(*sc) == 1;
     if (fuse) {
         // the fused form needs the direct fp32 epilogue (tiles of 64 columns or more)
@@ -276,6 +280,13 @@ void conv_forward(hipStream_t s, const ConvDesc& d_in, const ConvDesc* sc)
         if (g_pp_dbg) fuse = false;          // (the measurement build ablates the fused launch too)
 #endif
     }
+    return fuse;
+}
+
+void conv_forward(hipStream_t s, const ConvDesc& d_in, const ConvDesc* sc)
+{
+    // a shortcut that cannot ride in this launch runs first, as its own (its output is this layer's residual)
+    const bool fuse = conv_shortcut_rides(d_in, sc);
     if (sc && !fuse) conv_forward(s, *sc, nullptr);
     ConvDesc d = d_in;
     if (fuse) { d.res = nullptr; d.res_sB = d.res_sH = d.res_sW = 0; }
@@ -425,7 +436,72 @@ bool conv_tail_fusable(const ConvDesc& d3, const ConvDesc& d1)
     return true;
 }
 
-void conv_forward_tail(hipStream_t s, const ConvDesc& d3, const ConvDesc& d1, const ConvDesc* sc)
+// ------------------------------------------------------------------------------------------------
+// Chained pair (kernels.h: conv_forward_chain)
+// ------------------------------------------------------------------------------------------------
+bool conv_chain_fusable(const ConvDesc& dP, const ConvDesc& dQ, const ConvDesc* sc)
+{
+    if (!conv_is_split(dP) || !conv_is_split(dQ) || conv_wdtype(dP) != conv_wdtype(dQ)) return false;      // split modes, one filter dtype
+    const int C = dQ.Cout, H = dP.OH, W = dP.OW;
+    if (!(C == 64 || C == 128) || dQ.Npad != C || dP.Cin != C || dP.Cout != 4 * C || dP.Npad != 4 * C) return false;
+    if (!is_pointwise(dP) || !is_pointwise(dQ) || dP.B != dQ.B) return false;
+    if (!plain_epilogue(dP, ACT_RELU) || !plain_epilogue(dQ, ACT_RELU) || dQ.res) return false;
+    if (!dense_in(dP, H, W, C) || !dense_out(dP, H, W, 4 * C) || dQ.in != dP.out || !dense_in(dQ, H, W, 4 * C) || !dense_out(dQ, H, W, C)) return false;
+    if (conv_k_chunks(dP) != 1 || conv_k_chunks(dQ) != 1) return false;
+    auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    if (!al(dP.in) || !al(dP.out) || !al(dQ.out) || !al(dP.wgt) || !al(dQ.wgt) || !al(dP.scale) || !al(dP.shift) || !al(dQ.scale) || !al(dQ.shift)) return false;
+    if (sc) {
+        // the residual is formed from the shortcut's sums, as conv_forward does it
+        if (!g_scfuse || !conv_shortcut_fusable(dP, *sc) || conv_k_chunks(*sc) != 1 || !sc->scale || !sc->shift) return false;
+        if (C == 64 && sc->Cin != 64) return false;          // (C = 64 runs with every filter resident in LDS: the shortcut's too)
+        if (!al(sc->in) || !al(sc->wgt) || !al(sc->scale) || !al(sc->shift) || sc->in_sW % 4 || sc->in_sH % 4 || sc->in_sB % 4 || sc->Npad != 4 * C) return false;
+    } else {
+        if (!dP.res || !al(dP.res) || dP.res_sW != 4 * C || dP.res_sH != (long)W * 4 * C || dP.res_sB != (long)H * W * 4 * C) return false;
+    }
+    return true;
+}
+
+void conv_forward_chain(hipStream_t s, const ConvDesc& dP, const ConvDesc& dQ, const ConvDesc* sc)
+{
+    const long tiles = ((long)dP.B * dP.OH * dP.OW + 127) / 128;
+    // a shortcut rides in the chained launch exactly where it would ride in dP's own (conv_forward): the chain removes dQ's launch and no other
+    // ("conv_chain" 3, the test entry: the shortcut rides wherever the pair qualifies — the small shapes of tests/test_gpu_conv_chain.py reach that form)
+    const bool sc_rides = g_chain >= 3 ? sc != nullptr && conv_chain_fusable(dP, dQ, sc) : conv_shortcut_rides(dP, sc);
+    // By policy ("conv_chain" 1) a pair is chained where the grid fills the chip AND its shape pays: C = 64 (C2), whose filters stay resident in LDS.
+    // C = 128 (C3) — 256 KB of filters, fetched from L2 by every wave — measured SLOWER than its two launches: excluded by shape.
+    const int n_cus = device_cu_count();
+    bool chain = g_chain && g_direct >= 2 && conv_chain_fusable(dP, dQ, sc_rides ? sc : nullptr) && (g_chain >= 2 || (dQ.Cout == 64 && fills_chip(tiles, n_cus)));
+#ifndef MRCNN_CONV_ABLATE
+    if (g_pp_dbg) chain = false;
+#endif
+    if (!chain) {
+        conv_forward(s, dP, sc);
+        conv_forward(s, dQ);
+        return;
+    }
+    if (sc && !sc_rides) { conv_forward(s, *sc); sc = nullptr; }          // (its output is dP's residual)
+    ConvDesc d = dP;
+    if (sc) { d.res = nullptr; d.res_sB = d.res_sH = d.res_sW = 0; }
+    ConvArgs aP, aQ;
+    conv_fill_args(d, aP);
+    conv_fill_args(dQ, aQ);
+    if (sc) {
+        aP.sc_in = sc->in; aP.sc_wgt = sc->wgt; aP.sc_scale = sc->scale; aP.sc_shift = sc->shift;
+        aP.sc_in_sB = sc->in_sB; aP.sc_in_sH = sc->in_sH; aP.sc_in_sW = sc->in_sW;
+        aP.sc_H = sc->H; aP.sc_W = sc->W; aP.sc_Cin = sc->Cin; aP.sc_stride = sc->stride;
+    }
+    const ProfScope prof(s);
+    conv_chain_launch(s, aP, aQ, conv_split_parts(dP), dQ.Cout == 64, n_cus);
+    if (prof) {
+        // one launch, two layers, under the tile class P's own launch has: the flops of both, the bytes of both less Q's input read
+        const double fl = 2.0 * (double)aP.M * ((double)aP.ncols * (aP.Ktot + (sc ? sc->Cin : 0)) + (double)aQ.ncols * aQ.Ktot);
+        prof.finish(sc ? TILE_128x128_4WAVE : TILE_128x128, fl, aP.M, aP.ncols, aP.Ktot, dP.group,
+                    conv_algorithmic_bytes(d, sc) + conv_algorithmic_bytes(dQ) - (double)aP.M * dQ.Cin * 4.0);
+    }
+    HIP_CHECK(hipGetLastError());
+}
+
+void conv_forward_tail(hipStream_t s, const ConvDesc& d3, const ConvDesc& d1, const ConvDesc* sc, const ConvDesc* q)
 {
     const int n_cus = device_cu_count();
     const long tiles = ((long)d3.B * d3.OH * d3.OW + 127) / 128;
@@ -443,7 +519,8 @@ void conv_forward_tail(hipStream_t s, const ConvDesc& d3, const ConvDesc& d1, co
     }
     if (!fuse) {
         conv_forward(s, d3);
-        conv_forward(s, d1, sc);
+        if (q) conv_forward_chain(s, d1, *q, sc);
+        else conv_forward(s, d1, sc);
         return;
     }
     const ProfScope prof(s);
@@ -455,6 +532,7 @@ void conv_forward_tail(hipStream_t s, const ConvDesc& d3, const ConvDesc& d1, co
         prof.finish(TILE_HALO_TAIL, fl, a3.M, a1.ncols, a3.Ktot + a1.Ktot, d3.group, conv_algorithmic_bytes(d3n) + conv_algorithmic_bytes(d1) - (double)a3.M * d1.Cin * 4.0);
     }
     HIP_CHECK(hipGetLastError());
+    if (q) conv_forward(s, *q);          // (the fused tail stores d1's output itself: the next layer runs as its own launch)
 }
 
 // ------------------------------------------------------------------------------------------------

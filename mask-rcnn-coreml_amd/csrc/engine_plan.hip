@@ -240,23 +240,41 @@ struct PlanBuilder {
     // and while a calibration pass needs the tensor between them
     // dsc: the stage's shortcut convolution (first block) — computed inside branch2c's launch where the pair qualifies (conv_forward),
     // so that its tensor is neither written nor read back; its own launch in a calibration pass (which observes its output)
+    // chain (split modes, C2 / C3): the NEXT block's branch2a rides behind branch2c (conv_forward_chain: bit-identical to its own launch), so
+    // the op is held back until the next block has made that layer's description — tail_flush adds it, with or without one
+    struct PendingTail { ConvDesc d3, d1, dS; bool has_sc = false; int g_mid = 0, g_out = 0; size_t pm = 0, po = 0; bool open = false; } pending_tail;
     void tail_op(const std::string& n3, const std::string& n1, const Tensor4& in3, const Tensor4& mid, const Tensor4& out, const Tensor4& res,
                  int g_in, int g_mid, int g_out, const ConvDesc* dsc)
     {
-        const ConvDesc d3 = make_desc(n3, in3, mid, 1, 1, ACT_RELU, nullptr, 0, g_in, g_mid);
-        const ConvDesc d1 = make_desc(n1, mid, out, 1, 0, ACT_RELU, &res, 0, g_mid, g_out);
-        const size_t pm = (size_t)mid.sB(), po = (size_t)out.sB();
-        const bool has_sc = dsc != nullptr;
-        const ConvDesc dS = has_sc ? *dsc : ConvDesc();
+        PendingTail& t = pending_tail;
+        t.d3 = make_desc(n3, in3, mid, 1, 1, ACT_RELU, nullptr, 0, g_in, g_mid);
+        t.d1 = make_desc(n1, mid, out, 1, 0, ACT_RELU, &res, 0, g_mid, g_out);
+        t.pm = (size_t)mid.sB(); t.po = (size_t)out.sB();
+        t.has_sc = dsc != nullptr;
+        t.dS = t.has_sc ? *dsc : ConvDesc();
+        t.g_mid = g_mid; t.g_out = g_out;
+        t.open = true;
+    }
+    // dq: the chained layer (the next block's branch2a), g_q its output's group, pq its output's elements per image
+    void tail_flush(const ConvDesc* dq = nullptr, int g_q = 0, size_t pq = 0)
+    {
+        if (!pending_tail.open) return;
+        pending_tail.open = false;
+        const ConvDesc d3 = pending_tail.d3, d1 = pending_tail.d1, dS = pending_tail.dS;
+        const bool has_sc = pending_tail.has_sc, has_q = dq != nullptr;
+        const ConvDesc dQ = has_q ? *dq : ConvDesc();
+        const int g_mid = pending_tail.g_mid, g_out = pending_tail.g_out;
+        const size_t pm = pending_tail.pm, po = pending_tail.po;
         Model* const self = &m;
-        add([d3, d1, dS, has_sc, self, g_mid, g_out, pm, po](hipStream_t s, int batch) {
-            ConvDesc x3 = d3, x1 = d1, xs = dS;
-            x3.B = x1.B = xs.B = batch;
+        add([d3, d1, dS, dQ, has_sc, has_q, self, g_mid, g_out, g_q, pm, po, pq](hipStream_t s, int batch) {
+            ConvDesc x3 = d3, x1 = d1, xs = dS, xq = dQ;
+            x3.B = x1.B = xs.B = xq.B = batch;
             if (self->calib_phase) {
                 if (has_sc) { conv_forward(s, xs); self->observe_split(s, g_out, dS.out, po * batch); }
                 conv_forward(s, x3); self->observe_split(s, g_mid, d3.out, pm * batch);
                 conv_forward(s, x1); self->observe_split(s, g_out, d1.out, po * batch);
-            } else conv_forward_tail(s, x3, x1, has_sc ? &xs : nullptr);
+                if (has_q) { conv_forward(s, xq); self->observe_split(s, g_q, dQ.out, pq * batch); }
+            } else conv_forward_tail(s, x3, x1, has_sc ? &xs : nullptr, has_q ? &xq : nullptr);
         });
     }
 
@@ -363,6 +381,9 @@ struct PlanBuilder {
             const bool first = b == "a";
             const int stride = (first && st > 2) ? 2 : 1;
             const int oh = x.H / stride, ow = x.W / stride;
+            // split modes, C2 / C3: an identity block's branch2a is chained behind the previous block's branch2c (same description, same groups)
+            const bool chain_q = pending_tail.open && !first && (st == 2 || st == 3) && (m.mode == MRCNN_F32S || m.mode == MRCNN_F32X3);
+            if (!chain_q) tail_flush();
             if (first) { stage_ta = T(oh, ow, f1s[st]); stage_tb = T(oh, ow, f1s[st]); }      // the branch tensors are reused by every block of the stage
             if (first && m.mode == MRCNN_F16 && blocks[st].size() > 1 && bneck_geometry_ok(f1s[st], oh, ow)) {
                 stage_fused = true;
@@ -398,7 +419,10 @@ struct PlanBuilder {
                 g_x = g_stage;
                 continue;
             }
-            conv_op("res" + p + "_branch2a", x, ta, stride, 0, ACT_RELU, nullptr, 0, g_x, g_a);
+            if (chain_q) {
+                const ConvDesc dq = make_desc("res" + p + "_branch2a", x, ta, stride, 0, ACT_RELU, nullptr, 0, g_x, g_a);
+                tail_flush(&dq, g_a, (size_t)ta.sB());
+            } else conv_op("res" + p + "_branch2a", x, ta, stride, 0, ACT_RELU, nullptr, 0, g_x, g_a);
             Tensor4 sc = x;
             ConvDesc dsc;
             if (first) {
@@ -415,6 +439,7 @@ struct PlanBuilder {
             if (first) stage_main = to;
             g_x = g_stage;
         }
+        tail_flush();
         bneck_stage_flush((x.H / (f1s[st] == 256 ? 8 : 16)) * (x.W / 16));
         Cf[st] = x;
         g_C[st] = g_stage;

@@ -373,7 +373,14 @@ bool conv_halo_tail_geometry_ok(int H, int W);                          // ... a
 // which is what runs when the pair does not qualify, the grid would not fill the chip, or mrcnn_debug_set("conv_tail", 0).
 bool conv_tail_fusable(const ConvDesc& d3, const ConvDesc& d1);
 int conv_sel_part_cols();       // selected-class mode: output columns per partial sum the next conv_forward will leave (64: wave-private form, 128: block-staged)
-void conv_forward_tail(hipStream_t s, const ConvDesc& d3, const ConvDesc& d1, const ConvDesc* sc = nullptr);      // sc: d1's shortcut convolution (conv_forward)
+void conv_forward_tail(hipStream_t s, const ConvDesc& d3, const ConvDesc& d1, const ConvDesc* sc = nullptr, const ConvDesc* q = nullptr);      // sc: d1's shortcut convolution (conv_forward); q: the layer chained behind d1 (conv_forward_chain)
+// Chained pair of the split modes (kernels_conv_chain.hip): dP = a bottleneck's branch2c (1x1, C -> 4C, residual or fused shortcut sc, ReLU) and
+// dQ = the NEXT block's branch2a (1x1, 4C -> C, ReLU) reading dP's output, C = 64 | 128 — ONE launch: dP's output is stored and dQ is computed from
+// the tile while it is on chip.  BIT-IDENTICAL to conv_forward(dP, sc); conv_forward(dQ), which run where the pair does not qualify, the grid
+// under-fills the chip, C = 128 (measured slower: DESIGN.md section 3.1r), or behind mrcnn_debug_set("conv_chain", 0) ("conv_chain" 2: every
+// pair conv_chain_fusable accepts, at every grid size).  conv_chain_fusable says what the kernel can run, not what the policy chooses.
+bool conv_chain_fusable(const ConvDesc& dP, const ConvDesc& dQ, const ConvDesc* sc = nullptr);
+void conv_forward_chain(hipStream_t s, const ConvDesc& dP, const ConvDesc& dQ, const ConvDesc* sc = nullptr);
 
 // An identity ResNet bottleneck of the fp16 mode — da: the 1x1 `branch2a` (4C -> C, ReLU), db: the 3x3 `branch2b` reading da's output
 // (C -> C, ReLU), dc: the 1x1 `branch2c` reading db's output (C -> 4C, + shortcut = da's input, ReLU), C in {64, 128, 256} — as ONE

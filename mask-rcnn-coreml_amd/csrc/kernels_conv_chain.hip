@@ -1,0 +1,318 @@
+// kernels_conv_chain.hip — split modes: a bottleneck's `branch2c` (P: C -> 4C, + residual or fused shortcut, ReLU) and the NEXT
+// block's `branch2a` (Q: 4C -> C, ReLU) as one launch (conv_dispatch.hip: conv_forward_chain).  The tile of y = P's output that a
+// wave has just activated is exactly Q's activation operand for the same pixels: Q is computed from it while it is on chip, so
+// the 4C-wide tensor is stored (the next block's residual) but not read back by a launch of its own.
+//
+// BIT-IDENTICAL to conv_forward(P); conv_forward(Q), output for output:
+//   * a wave owns 32 pixel rows and walks ALL of P's 4C columns in ascending chunks of 64; P's sums per chunk are the 128-row
+//     kernel's (K steps of 32 channels, groups of 16 ascending, hi / mid / lo part per group, filter fragment first);
+//   * each 32 x 32 piece goes through the wave-private transpose of conv_epilogue_wave with its expressions (scale / shift,
+//     + residual — loaded, or formed from the shortcut's sums —, ReLU, fp16-range watch) and is stored;
+//   * the stored fp32 values go back through the same LDS tile into activation-fragment layout, are split by split_hi_mid_lo /
+//     split_hi_lo and multiplied into Q's accumulators: one running sum per output, channel groups ascending — Q's own order;
+//   * Q's epilogue is the same wave-private piece without a residual.
+// The waves of a block share no pixel: nothing synchronises them inside the loop.  Two forms:
+//   * C = 64 (WLDS): one persistent block of eight waves per CU with every filter of the launch resident in LDS, P's activation
+//     fragments split once per 32-row tile into registers — what conv_forward_chain runs by policy;
+//   * C = 128: P's activation tile (32 rows x C fp32 per wave) in LDS in the 128-row kernel's swizzled layout, both layers' filter
+//     fragments straight from L2 (16 B per lane) — measured slower than the two launches, kept as the tests' bit-identity anchor.
+#include "conv_device.h"
+
+namespace mrcnn {
+
+struct ChainArgs { ConvArgs p, q; };
+
+// one 32 x 32 piece: accumulators -> wave-private LDS tile (chunk c of row r at c ^ (r & 7)) -> row-wise read-back
+__device__ __forceinline__ void chain_stage_acc(float* stage, const f32x16& acc, int l31, int kk)
+{
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        *reinterpret_cast<float4*>(&stage[l31 * 32 + (((2 * q + kk) ^ (l31 & 7)) << 2)]) = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+}
+
+// the fp16 parts of eight fp32 activations: hi, (mid,) lo
+struct ChainParts { f16x8 hi, lo, lo2; };
+template <int PARTS>
+__device__ __forceinline__ ChainParts chain_split(const uint4 u0, const uint4 u1)
+{
+    ChainParts p;
+    if constexpr (PARTS == 3) split_hi_mid_lo(u0, u1, p.hi, p.lo, p.lo2);
+    else { split_hi_lo(u0, u1, p.hi, p.lo); p.lo2 = p.lo; }
+    return p;
+}
+// one 16-channel group into N column tiles: every tile's hi part, then mid, then lo — per accumulator the 128-row kernel's order
+template <int PARTS, int N>
+__device__ __forceinline__ void chain_mfma_parts(f32x16 (&acc)[N], const uint4 (&bv)[N], const ChainParts& pt)
+{
+    const f16x8 hi = pt.hi, lo = pt.lo, lo2 = pt.lo2;
+    _Pragma("unroll") for (int j = 0; j < N; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bv[j]), hi, acc[j], 0, 0, 0);
+    _Pragma("unroll") for (int j = 0; j < N; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bv[j]), lo, acc[j], 0, 0, 0);
+    if constexpr (PARTS == 3)
+        _Pragma("unroll") for (int j = 0; j < N; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bv[j]), lo2, acc[j], 0, 0, 0);
+}
+
+// C: P's input channels = Q's output columns (64: C2, 128: C3); SC: P's residual is formed from the fused shortcut convolution
+// WLDS (C = 64 only): every filter of the launch resident in LDS (W3, W1 and the shortcut's: 32 KB each, in the 128-row kernel's swizzled
+// 64-B rows per K step), ONE block of eight waves per CU walking 32-row tiles of the whole tensor (a persistent grid: the filters are staged once
+// per CU), and P's activation fragments split ONCE per tile into registers — no filter request leaves the CU inside the loop.
+template <int C, int PARTS, bool SC, bool WLDS>
+__global__ __launch_bounds__(WLDS ? 512 : 256, WLDS ? 1 : 2) void k_conv_chain(const ChainArgs ca)
+{
+    static_assert(!WLDS || C == 64, "the LDS-resident form holds C = 64's filters");
+    constexpr int NW = WLDS ? 8 : 4, C4 = 4 * C, KT = C / 32, TNP = 2, TNQ = C / 32;
+    constexpr int A_BYTES = WLDS ? 0 : KT * 32 * 128;    // a wave's activation tile: KT sub-tiles of 32 rows x 128 B
+    constexpr int W_BYTES = WLDS ? C4 * C * 2 : 0;       // one filter matrix (W3: [K step][4C rows][64 B]; W1: [K step][C rows][64 B])
+    constexpr int WF_BYTES = W_BYTES * (SC ? 3 : 2);
+    __shared__ __attribute__((aligned(16))) unsigned char smem[WF_BYTES + NW * (A_BYTES + 32 * 32 * 4)];
+    const ConvArgs& a = ca.p;
+    const ConvArgs& aq = ca.q;
+    const int t = threadIdx.x;
+    const int wave = t >> 6, lane = t & 63;
+    const int l31 = lane & 31, kk = lane >> 5;
+    unsigned char* const As = smem + WF_BYTES + wave * A_BYTES;
+    float* const stage = reinterpret_cast<float*>(smem + WF_BYTES + NW * A_BYTES) + wave * (32 * 32);
+    const float* const in = static_cast<const float*>(a.in);
+    const _Float16* const w3 = static_cast<const _Float16*>(a.wgt);
+    const _Float16* const w1 = static_cast<const _Float16*>(aq.wgt);
+    const float* const res = static_cast<const float*>(a.res);
+    float* const out = static_cast<float*>(a.out);
+    float* const outq = static_cast<float*>(aq.out);
+    const _Float16* const wsc = static_cast<const _Float16*>(a.sc_wgt);
+    const int swzb = (l31 >> 2) & 3;                     // filter rows in LDS: 16-B chunk c of row r at c ^ ((r >> 2) & 3)
+    if constexpr (WLDS) {
+        // rows x K fp16 -> [K step][row][64 B]
+        auto stage_filter = [&](unsigned char* dst, const _Float16* src, int rows, int K) {
+            const int cpr = K / 8;                       // 16-B chunks per filter row
+            for (int idx = t; idx < rows * cpr; idx += NW * 64) {
+                const int r = idx / cpr, ch = idx - r * cpr;
+                *reinterpret_cast<uint4*>(dst + ((ch >> 2) * rows + r) * 64 + (((ch & 3) ^ ((r >> 2) & 3)) << 4)) = *reinterpret_cast<const uint4*>(src + (long)r * K + ch * 8);
+            }
+        };
+        stage_filter(smem, w3, C4, C);
+        stage_filter(smem + W_BYTES, w1, C, C4);
+        if constexpr (SC) stage_filter(smem + 2 * W_BYTES, wsc, C4, C);
+        __syncthreads();                                 // (the only block barrier: the waves share nothing else)
+    }
+    bool out_of_range = false, out_of_range_q = false;
+    for (int row0 = (blockIdx.x * NW + wave) * 32; row0 < a.M; row0 += gridDim.x * NW * 32) {
+    // ---- P's activation tile: -> LDS, or (WLDS) this lane's fragments straight into registers, split once (rows beyond M: zeros) ----
+    ChainParts ap[WLDS ? 2 * KT : 1];
+    if constexpr (WLDS) {
+        const int m = row0 + l31;
+#pragma unroll
+        for (int g = 0; g < 2 * KT; ++g) {
+            uint4 u0 = make_uint4(0u, 0u, 0u, 0u), u1 = u0;
+            if (m < a.M) { u0 = *reinterpret_cast<const uint4*>(in + (long)m * C + g * 16 + 8 * kk); u1 = *reinterpret_cast<const uint4*>(in + (long)m * C + g * 16 + 8 * kk + 4); }
+            ap[g] = chain_split<PARTS>(u0, u1);
+        }
+    } else {
+#pragma unroll
+        for (int it = 0; it < C / 8; ++it) {
+            const int idx = it * 64 + lane;
+            const int r = idx / (C / 4), ch = idx - r * (C / 4);
+            const int m = row0 + r;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (m < a.M) v = *reinterpret_cast<const uint4*>(in + (long)m * C + ch * 4);
+            *reinterpret_cast<uint4*>(As + (ch >> 3) * 4096 + r * 128 + (((ch & 7) ^ ((r >> 1) & 7)) << 4)) = v;
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+
+    const int swz = (l31 >> 1) & 7;
+    const unsigned char* const la = As + l31 * 128;
+    const int ca0 = ((0 + 2 * kk) ^ swz) << 4, ca1 = ((1 + 2 * kk) ^ swz) << 4, ca2 = ((4 + 2 * kk) ^ swz) << 4, ca3 = ((5 + 2 * kk) ^ swz) << 4;
+    const int rrow = lane >> 3, c4 = (lane & 7) * 4;     // read-back: eight lanes per row, four passes of eight rows
+    const bool relu = a.act == ACT_RELU, reluq = aq.act == ACT_RELU;
+    bool ok[4];
+    long mrow[4];
+#pragma unroll
+    for (int ps = 0; ps < 4; ++ps) { const int m = row0 + 8 * ps + rrow; ok[ps] = m < a.M; mrow[ps] = m; }
+
+    // fused shortcut: this lane's pixel of the shortcut's input (a strided 1x1: no padding)
+    const float* sc_row = nullptr;
+    bool sc_ok = false;
+    if constexpr (SC) {
+        const int m = row0 + l31;
+        sc_ok = m < a.M;
+        const int ohw = a.OH * a.OW;
+        const int mm = sc_ok ? m : 0;
+        const int b = mm / ohw, rem = mm - b * ohw;
+        const int oh = rem / a.OW, ow = rem - oh * a.OW;
+        sc_row = static_cast<const float*>(a.sc_in) + (long)b * a.sc_in_sB + (long)(oh * a.sc_stride) * a.sc_in_sH + (long)(ow * a.sc_stride) * a.sc_in_sW + 8 * kk;
+    }
+    // WLDS: the lane's 64 shortcut-input channels, loaded once per tile (split again per column chunk: no registers for the parts)
+    uint4 xr[SC && WLDS ? C / 4 : 1];
+    if constexpr (SC && WLDS) {
+#pragma unroll
+        for (int i = 0; i < C / 4; ++i) {
+            xr[i] = make_uint4(0u, 0u, 0u, 0u);
+            if (sc_ok) xr[i] = *reinterpret_cast<const uint4*>(sc_row + (i >> 1) * 16 + (i & 1) * 4);
+        }
+    }
+
+    f32x16 accQ[TNQ];
+#pragma unroll
+    for (int j = 0; j < TNQ; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) accQ[j][e] = 0.0f;
+
+    for (int nc = 0; nc < C4; nc += TNP * 32) {
+        // the residual of the chunk is requested before its K loop: every element the wave will overwrite, before its first store
+        float4 rv[TNP][4];
+        if constexpr (!SC) {
+#pragma unroll
+            for (int j = 0; j < TNP; ++j)
+#pragma unroll
+                for (int ps = 0; ps < 4; ++ps) {
+                    rv[j][ps] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (res && ok[ps]) rv[j][ps] = *reinterpret_cast<const float4*>(res + mrow[ps] * C4 + nc + j * 32 + c4);
+                }
+        }
+        f32x16 accP[TNP], accS[TNP];
+#pragma unroll
+        for (int j = 0; j < TNP; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) { accP[j][e] = 0.0f; accS[j][e] = 0.0f; }
+        // ---- P: K steps of 32 channels, two groups of 16 each ------------------------------------------------------
+#pragma unroll
+        for (int kt = 0; kt < KT; ++kt) {
+#pragma unroll
+            for (int g = 0; g < 2; ++g) {
+                uint4 bv[TNP];
+                if constexpr (WLDS) {
+#pragma unroll
+                    for (int j = 0; j < TNP; ++j) bv[j] = *reinterpret_cast<const uint4*>(smem + (kt * C4 + nc + j * 32 + l31) * 64 + (((2 * g + kk) ^ swzb) << 4));
+                    chain_mfma_parts<PARTS, TNP>(accP, bv, ap[2 * kt + g]);
+                } else {
+                    const uint4 u0 = *reinterpret_cast<const uint4*>(la + kt * 4096 + (g ? ca2 : ca0));
+                    const uint4 u1 = *reinterpret_cast<const uint4*>(la + kt * 4096 + (g ? ca3 : ca1));
+#pragma unroll
+                    for (int j = 0; j < TNP; ++j) bv[j] = *reinterpret_cast<const uint4*>(w3 + (long)(nc + j * 32 + l31) * C + kt * 32 + g * 16 + 8 * kk);
+                    chain_mfma_parts<PARTS, TNP>(accP, bv, chain_split<PARTS>(u0, u1));
+                }
+            }
+        }
+        if constexpr (SC) {
+            // the shortcut's own sums, from zero: its channel groups ascending (fragments straight from memory)
+            for (int g = 0; g < (WLDS ? C / 16 : a.sc_Cin / 16); ++g) {
+                uint4 u0 = make_uint4(0u, 0u, 0u, 0u), u1 = u0;
+                if constexpr (WLDS) { u0 = xr[2 * g]; u1 = xr[2 * g + 1]; }
+                else if (sc_ok) { u0 = *reinterpret_cast<const uint4*>(sc_row + g * 16); u1 = *reinterpret_cast<const uint4*>(sc_row + g * 16 + 4); }
+                uint4 bv[TNP];
+#pragma unroll
+                for (int j = 0; j < TNP; ++j) {
+                    if constexpr (WLDS) bv[j] = *reinterpret_cast<const uint4*>(smem + 2 * W_BYTES + ((g >> 1) * C4 + nc + j * 32 + l31) * 64 + (((2 * (g & 1) + kk) ^ swzb) << 4));
+                    else bv[j] = *reinterpret_cast<const uint4*>(wsc + (long)(nc + j * 32 + l31) * a.sc_Cin + g * 16 + 8 * kk);
+                }
+                chain_mfma_parts<PARTS, TNP>(accS, bv, chain_split<PARTS>(u0, u1));
+            }
+        }
+        // ---- epilogue of the chunk, piece by piece; each piece is one K step of Q -------------------------------------
+#pragma unroll
+        for (int j = 0; j < TNP; ++j) {
+            const int n = nc + j * 32 + c4;
+            float4 rj[4];
+            if constexpr (SC) {
+                chain_stage_acc(stage, accS[j], l31, kk);
+                __builtin_amdgcn_wave_barrier();
+                const float4 sc2 = *reinterpret_cast<const float4*>(a.sc_scale + n), sh2 = *reinterpret_cast<const float4*>(a.sc_shift + n);
+#pragma unroll
+                for (int ps = 0; ps < 4; ++ps) {
+                    float4 y = *reinterpret_cast<const float4*>(&stage[(8 * ps + rrow) * 32 + (((lane & 7) ^ rrow) << 2)]);
+                    y.x = y.x * sc2.x + sh2.x; y.y = y.y * sc2.y + sh2.y; y.z = y.z * sc2.z + sh2.z; y.w = y.w * sc2.w + sh2.w;
+                    out_of_range = out_of_range || !(fabsf(y.x) < 65504.0f) || !(fabsf(y.y) < 65504.0f) || !(fabsf(y.z) < 65504.0f) || !(fabsf(y.w) < 65504.0f);
+                    rj[ps] = y;
+                }
+                __builtin_amdgcn_wave_barrier();
+            } else {
+#pragma unroll
+                for (int ps = 0; ps < 4; ++ps) rj[ps] = rv[j][ps];
+            }
+            chain_stage_acc(stage, accP[j], l31, kk);
+            __builtin_amdgcn_wave_barrier();
+            const float4 sc = *reinterpret_cast<const float4*>(a.scale + n), sh = *reinterpret_cast<const float4*>(a.shift + n);
+            float4 xs[4];
+#pragma unroll
+            for (int ps = 0; ps < 4; ++ps) {
+                float4 x = *reinterpret_cast<const float4*>(&stage[(8 * ps + rrow) * 32 + (((lane & 7) ^ rrow) << 2)]);
+                x.x = x.x * sc.x + sh.x; x.y = x.y * sc.y + sh.y; x.z = x.z * sc.z + sh.z; x.w = x.w * sc.w + sh.w;
+                if (SC || res) { x.x += rj[ps].x; x.y += rj[ps].y; x.z += rj[ps].z; x.w += rj[ps].w; }
+                if (relu) { x.x = fmaxf(x.x, 0.f); x.y = fmaxf(x.y, 0.f); x.z = fmaxf(x.z, 0.f); x.w = fmaxf(x.w, 0.f); }
+                if (ok[ps]) {
+                    out_of_range = out_of_range || !(fabsf(x.x) < 65504.0f) || !(fabsf(x.y) < 65504.0f) || !(fabsf(x.z) < 65504.0f) || !(fabsf(x.w) < 65504.0f);
+                    *reinterpret_cast<float4*>(out + mrow[ps] * C4 + n) = x;
+                }
+                xs[ps] = x;
+            }
+            __builtin_amdgcn_wave_barrier();
+            // the stored values, back in place: the tile now holds y row-major (same swizzle)
+#pragma unroll
+            for (int ps = 0; ps < 4; ++ps) *reinterpret_cast<float4*>(&stage[(8 * ps + rrow) * 32 + (((lane & 7) ^ rrow) << 2)]) = xs[ps];
+            __builtin_amdgcn_wave_barrier();
+            // ---- Q: the K step of channels nc + 32 j .. + 31 ---------------------------------------------------------
+#pragma unroll
+            for (int g = 0; g < 2; ++g) {
+                const uint4 u0 = *reinterpret_cast<const uint4*>(&stage[l31 * 32 + (((4 * g + 2 * kk) ^ (l31 & 7)) << 2)]);
+                const uint4 u1 = *reinterpret_cast<const uint4*>(&stage[l31 * 32 + (((4 * g + 2 * kk + 1) ^ (l31 & 7)) << 2)]);
+                uint4 bq[TNQ];
+#pragma unroll
+                for (int jq = 0; jq < TNQ; ++jq) {
+                    if constexpr (WLDS) bq[jq] = *reinterpret_cast<const uint4*>(smem + W_BYTES + ((nc / 32 + j) * C + jq * 32 + l31) * 64 + (((2 * g + kk) ^ swzb) << 4));
+                    else bq[jq] = *reinterpret_cast<const uint4*>(w1 + (long)(jq * 32 + l31) * C4 + nc + j * 32 + g * 16 + 8 * kk);
+                }
+                chain_mfma_parts<PARTS, TNQ>(accQ, bq, chain_split<PARTS>(u0, u1));
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    // ---- Q's epilogue: scale / shift, ReLU, watch, full-line stores ------------------------------------------------------
+#pragma unroll
+    for (int jq = 0; jq < TNQ; ++jq) {
+        const int n = jq * 32 + c4;
+        chain_stage_acc(stage, accQ[jq], l31, kk);
+        __builtin_amdgcn_wave_barrier();
+        const float4 sc = *reinterpret_cast<const float4*>(aq.scale + n), sh = *reinterpret_cast<const float4*>(aq.shift + n);
+#pragma unroll
+        for (int ps = 0; ps < 4; ++ps) {
+            float4 x = *reinterpret_cast<const float4*>(&stage[(8 * ps + rrow) * 32 + (((lane & 7) ^ rrow) << 2)]);
+            x.x = x.x * sc.x + sh.x; x.y = x.y * sc.y + sh.y; x.z = x.z * sc.z + sh.z; x.w = x.w * sc.w + sh.w;
+            if (reluq) { x.x = fmaxf(x.x, 0.f); x.y = fmaxf(x.y, 0.f); x.z = fmaxf(x.z, 0.f); x.w = fmaxf(x.w, 0.f); }
+            if (ok[ps]) {
+                out_of_range_q = out_of_range_q || !(fabsf(x.x) < 65504.0f) || !(fabsf(x.y) < 65504.0f) || !(fabsf(x.z) < 65504.0f) || !(fabsf(x.w) < 65504.0f);
+                *reinterpret_cast<float4*>(outq + mrow[ps] * C + n) = x;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    }          // (the wave's next 32-row tile)
+    if (a.range_flag && out_of_range) atomicOr(a.range_flag, 1);
+    if (aq.range_flag && out_of_range_q) atomicOr(aq.range_flag, 1);
+}
+
+// p / q: the launch arguments of the two layers (conv_dispatch.hip has checked the pair: conv_chain_fusable); parts 2 | 3
+// wlds: the LDS-resident persistent form (C = 64 with a 64-channel shortcut or none); n_cus sizes its grid
+void conv_chain_launch(hipStream_t s, const ConvArgs& p, const ConvArgs& q, int parts, bool wlds, int n_cus)
+{
+    ChainArgs ca{p, q};
+    dim3 grid((p.M + 127) / 128), block(256);
+    const bool sc = p.sc_in != nullptr;
+    const int C = q.Cout;
+    MRCNN_REQUIRE((C == 64 || C == 128) && (parts == 2 || parts == 3), MRCNN_ERR_INVALID, "conv_chain_launch: C %d, %d parts", C, parts);
+    if (wlds) {
+        MRCNN_REQUIRE(C == 64 && (!sc || p.sc_Cin == 64) && n_cus > 0, MRCNN_ERR_INVALID, "conv_chain_launch: the LDS-resident form holds C = 64's filters");
+        const int tiles256 = (p.M + 255) / 256;
+        grid = dim3(tiles256 < n_cus ? tiles256 : n_cus); block = dim3(512);
+#define MRCNN_CHAIN_W(P_, S_) hipLaunchKernelGGL((k_conv_chain<64, P_, S_, true>), grid, block, 0, s, ca)
+        if (parts == 3) { if (sc) MRCNN_CHAIN_W(3, true); else MRCNN_CHAIN_W(3, false); }
+        else { if (sc) MRCNN_CHAIN_W(2, true); else MRCNN_CHAIN_W(2, false); }
+#undef MRCNN_CHAIN_W
+        return;
+    }
+    MRCNN_REQUIRE(C == 128, MRCNN_ERR_INVALID, "conv_chain_launch: C = 64 runs the LDS-resident form");
+#define MRCNN_CHAIN(C_, P_, S_) hipLaunchKernelGGL((k_conv_chain<C_, P_, S_, false>), grid, block, 0, s, ca)
+    if (parts == 3) { if (sc) MRCNN_CHAIN(128, 3, true); else MRCNN_CHAIN(128, 3, false); }
+    else { if (sc) MRCNN_CHAIN(128, 2, true); else MRCNN_CHAIN(128, 2, false); }
+#undef MRCNN_CHAIN
+}
+
+}  // namespace mrcnn
