@@ -1,0 +1,100 @@
+/*
+ * maskrcnn_polygons.c — run-length masks handed on as geometry, in plain C99 over include/maskrcnn_hip.h: an RLE set is read from a
+ * text file, mrcnn_rle_to_polygons traces the boundary of every mask on the GPU (the size query first, then the call), and the rings
+ * are printed, one per line, with their signed areas: positive for an outline, negative for a hole.
+ *
+ *   cc -std=c99 -Iinclude examples/maskrcnn_polygons.c -Lmask-rcnn-coreml_amd -lmaskrcnn_hip \
+ *      -Wl,-rpath,$PWD/mask-rcnn-coreml_amd -Wl,-rpath-link,/opt/rocm/lib -o maskrcnn_polygons
+ *   ./maskrcnn_polygons [--host] <set.txt>
+ *
+ * <set.txt> holds whitespace-separated integers: n_images and slots; then per image its height and width and, for each of its `slots`
+ * RLEs, the number of runs followed by the runs (column-major, the first run counts zeros) — the layout mrcnn_masks_rle_source,
+ * mrcnn_merge_tiles and mrcnn_unite_tiles write.  --host calls the sequential definition, mrcnn_rle_to_polygons_host, which needs no
+ * GPU.  Exit status 0 on success; on failure the mrcnn_last_error() text goes to stderr and the status code is the exit status.
+ */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "maskrcnn_hip.h"
+
+static int trace(int host, const uint32_t* counts, const int64_t* run_offsets, int n_images, int slots, const int32_t* heights, const int32_t* widths,
+                 int64_t* rle_rings, int64_t* n_rings, int64_t* n_vertices, int64_t* ring_offsets, int64_t* ring_areas, int64_t ring_capacity,
+                 int32_t* xy, int64_t vertex_capacity)
+{
+    if (host)
+        return mrcnn_rle_to_polygons_host(counts, run_offsets, n_images, slots, heights, widths, rle_rings, n_rings, n_vertices, ring_offsets, ring_areas,
+                                          ring_capacity, xy, vertex_capacity);
+    return mrcnn_rle_to_polygons(counts, run_offsets, n_images, slots, heights, widths, MRCNN_HOST, rle_rings, n_rings, n_vertices, ring_offsets,
+                                 ring_areas, ring_capacity, xy, vertex_capacity);
+}
+
+int main(int argc, char** argv)
+{
+    const int host = argc > 1 && strcmp(argv[1], "--host") == 0;
+    if (argc != 2 + host) {
+        fprintf(stderr, "usage: %s [--host] <set.txt>\n", argv[0]);
+        return 64;
+    }
+    FILE* f = fopen(argv[1 + host], "r");
+    if (!f) { fprintf(stderr, "cannot read %s\n", argv[1 + host]); return 66; }
+    int n_images = 0, slots = 0;
+    if (fscanf(f, "%d %d", &n_images, &slots) != 2 || n_images < 0 || slots < 0 || (n_images > 0 && slots > 1000000 / n_images)) {
+        fprintf(stderr, "%s: n_images and slots expected\n", argv[1 + host]);
+        return 65;
+    }
+    const size_t n = (size_t)n_images * (size_t)slots;
+    int32_t* heights = (int32_t*)malloc(sizeof(int32_t) * (size_t)(n_images + 1));
+    int32_t* widths = (int32_t*)malloc(sizeof(int32_t) * (size_t)(n_images + 1));
+    int64_t* run_offsets = (int64_t*)malloc(sizeof(int64_t) * (n + 1));
+    int64_t* rle_rings = (int64_t*)malloc(sizeof(int64_t) * (n + 1));
+    size_t held = 1024, used = 0;
+    uint32_t* counts = (uint32_t*)malloc(sizeof(uint32_t) * held);
+    if (!heights || !widths || !run_offsets || !rle_rings || !counts) { fprintf(stderr, "out of memory\n"); return 70; }
+    run_offsets[0] = 0;
+    for (int b = 0; b < n_images; ++b) {
+        if (fscanf(f, "%d %d", &heights[b], &widths[b]) != 2) { fprintf(stderr, "image %d: height and width expected\n", b); return 65; }
+        for (int i = 0; i < slots; ++i) {
+            long long runs = 0;
+            if (fscanf(f, "%lld", &runs) != 1 || runs < 0 || runs > 0x7fffffffLL) { fprintf(stderr, "image %d, RLE %d: the number of runs expected\n", b, i); return 65; }
+            if (used + (size_t)runs > held) {
+                while (used + (size_t)runs > held) held *= 2;
+                counts = (uint32_t*)realloc(counts, sizeof(uint32_t) * held);
+                if (!counts) { fprintf(stderr, "out of memory\n"); return 70; }
+            }
+            for (long long j = 0; j < runs; ++j) {
+                unsigned long c = 0;
+                if (fscanf(f, "%lu", &c) != 1) { fprintf(stderr, "image %d, RLE %d: %lld runs expected\n", b, i, runs); return 65; }
+                counts[used++] = (uint32_t)c;
+            }
+            run_offsets[(size_t)b * (size_t)slots + (size_t)i + 1] = (int64_t)used;
+        }
+    }
+    fclose(f);
+
+    /* the size query: no buffers, both capacities 0.  MRCNN_ERR_SHAPE is its answer when there is anything to write. */
+    int64_t rings = 0, vertices = 0;
+    int st = trace(host, counts, run_offsets, n_images, slots, heights, widths, rle_rings, &rings, &vertices, NULL, NULL, 0, NULL, 0);
+    if (st != MRCNN_OK && !(st == MRCNN_ERR_SHAPE && (rings > 0 || vertices > 0))) {
+        fprintf(stderr, "the size query failed (%d): %s\n", st, mrcnn_last_error());
+        return st;
+    }
+    int64_t* ring_offsets = (int64_t*)malloc(sizeof(int64_t) * (size_t)(rings + 1));
+    int64_t* ring_areas = (int64_t*)malloc(sizeof(int64_t) * (size_t)(rings + 1));
+    int32_t* xy = (int32_t*)malloc(sizeof(int32_t) * 2 * (size_t)(vertices + 1));
+    if (!ring_offsets || !ring_areas || !xy) { fprintf(stderr, "out of memory\n"); return 70; }
+    st = trace(host, counts, run_offsets, n_images, slots, heights, widths, rle_rings, &rings, &vertices, ring_offsets, ring_areas, rings, xy, vertices);
+    if (st != MRCNN_OK) {
+        fprintf(stderr, "mrcnn_rle_to_polygons%s failed (%d): %s\n", host ? "_host" : "", st, mrcnn_last_error());
+        return st;
+    }
+    printf("%lld rings, %lld vertices in %d x %d RLEs\n", (long long)rings, (long long)vertices, n_images, slots);
+    for (size_t k = 0; k < n; ++k)
+        for (int64_t r = rle_rings[k]; r < rle_rings[k + 1]; ++r) {
+            printf("RLE %lld ring %lld area %lld:", (long long)k, (long long)(r - rle_rings[k]), (long long)ring_areas[r]);
+            for (int64_t v = ring_offsets[r]; v < ring_offsets[r + 1]; ++v) printf(" %d,%d", (int)xy[2 * v], (int)xy[2 * v + 1]);
+            printf("\n");
+        }
+    free(xy); free(ring_areas); free(ring_offsets); free(counts); free(rle_rings); free(run_offsets); free(widths); free(heights);
+    return 0;
+}

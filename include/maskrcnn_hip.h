@@ -883,6 +883,52 @@ MRCNN_API int mrcnn_rle_from_polygons_batch(const double* xy, const int64_t* pol
                                             const int32_t* heights, const int32_t* widths, int memspace, uint32_t* counts, int64_t capacity,
                                             int64_t* run_offsets, uint32_t* areas, int32_t* bboxes_xywh);
 
+/* Polygons out: the boundary of every mask of an RLE SET as closed rings of pixel corners, traced from the runs — no plane is decoded.
+ * The input is the set of the drawing entries above (counts, run_offsets, n_images, slots, heights, widths): RLE k = b*slots + i lies on
+ * the h_b x w_b plane P_k of image b; zero-length runs are legal anywhere and a run of ones that crosses a column end is two vertical
+ * intervals.
+ * Geometry.  Pixel (x, y) is the unit square [x, x+1] x [y, y+1], x to the right and y down.  A vertex (X, Y) is a pixel corner,
+ *   0 <= X <= w, 0 <= Y <= h.  The boundary of P_k is the set of unit edges between a set pixel and an unset pixel or the outside of
+ *   the plane, each directed so that the set pixel lies on its right as seen on screen: the top edge of a set pixel runs +x, its right
+ *   edge +y, its bottom edge -x, its left edge -y.  Where four boundary edges meet — two set pixels touch only diagonally — the walk
+ *   turns right: set pixels are 4-connected, unset pixels 8-connected, every directed edge has exactly one successor, and the edges fall
+ *   into closed rings.
+ * A ring keeps only its corners (collinear vertices are dropped): an even number of vertices, at least 4, horizontal and vertical
+ *   pieces in turn.  It may pass twice through a vertex, only at such a diagonal contact.  It starts at its smallest vertex, ordered by
+ *   x and then y, and goes on in walking direction; nothing of a ring lies left of that vertex, so the ring visits it once and no two
+ *   rings of a plane start at the same vertex.  The rings of one RLE are ordered by their start vertex, x then y.  A ring's signed area
+ *   is (1/2) * sum(x_i*y_{i+1} - x_{i+1}*y_i): positive for an outline, which runs clockwise on screen, negative for a hole; the areas
+ *   of an RLE's rings sum to its set pixels.  An empty mask has no rings.
+ * Outputs.
+ *   rle_rings (n + 1, n = n_images*slots)   the rings of RLE k are [rle_rings[k], rle_rings[k+1]); ALWAYS written
+ *   *n_rings, *n_vertices (host)            the totals; ALWAYS written
+ *   ring_offsets (ring_capacity + 1)        ring r owns the vertices [ring_offsets[r], ring_offsets[r+1]); n_rings + 1 entries are written
+ *   ring_areas (ring_capacity, may be NULL) the signed areas
+ *   xy (2 * vertex_capacity, int32)         x then y per vertex, all rings back to back
+ * The two capacities follow the protocol of mrcnn_masks_rle_source: if n_rings > ring_capacity or n_vertices > vertex_capacity the
+ * call returns MRCNN_ERR_SHAPE, the message names both sizes needed and none of ring_offsets, ring_areas and xy is written (both
+ * capacities 0 with NULL buffers is the size query).  memspace holds for counts, run_offsets, rle_rings, ring_offsets, ring_areas and
+ * xy; heights, widths, n_rings and n_vertices are host memory.
+ * mrcnn_rle_to_polygons_host is the definition: sequential plain C++, no GPU, host pointers; it decodes each plane and walks its edges
+ * one by one.  mrcnn_rle_to_polygons equals it bit for bit in every array.  It finds the corners of a vertex column by merging the runs
+ * of the two pixel columns beside it, pairs them along columns and rows, and orders the cycles of that permutation by pointer
+ * jumping; an RLE of at most MRCNN_POLYGON_LDS_CORNERS corners is sorted and ranked by one workgroup in LDS, a larger one in global
+ * memory.  The number of launches grows with the square of the logarithm of the largest RLE's corners, never with the number of RLEs;
+ * the host reads back one summary (is every RLE right, how many corners) before anything is traced and the number of rings after.
+ * Errors are mrcnn_rle_decode's: null pointer, negative capacity -> MRCNN_ERR_INVALID; a side outside 1..32767, decreasing
+ * run_offsets -> MRCNN_ERR_SHAPE; an RLE whose runs do not sum to h_b*w_b -> MRCNN_ERR_SHAPE, the message names k and nothing is
+ * written; all of these before a device is looked for, except the sums of a set in device memory.  No gfx950 device -> MRCNN_ERR_HIP
+ * from the device entry (no CPU fallback).
+ * Not here: simplification (Douglas-Peucker and the like), smoothing, sub-pixel contours from the 28x28 probabilities, and nesting the
+ * rings into a tree of outlines and their holes — a hole is a ring of negative area and nothing more.  examples/maskrcnn_polygons.c. */
+#define MRCNN_POLYGON_LDS_CORNERS 1024
+MRCNN_API int mrcnn_rle_to_polygons(const uint32_t* counts, const int64_t* run_offsets, int n_images, int slots, const int32_t* heights,
+                                    const int32_t* widths, int memspace, int64_t* rle_rings, int64_t* n_rings, int64_t* n_vertices,
+                                    int64_t* ring_offsets, int64_t* ring_areas, int64_t ring_capacity, int32_t* xy, int64_t vertex_capacity);
+MRCNN_API int mrcnn_rle_to_polygons_host(const uint32_t* counts, const int64_t* run_offsets, int n_images, int slots, const int32_t* heights,
+                                         const int32_t* widths, int64_t* rle_rings, int64_t* n_rings, int64_t* n_vertices,
+                                         int64_t* ring_offsets, int64_t* ring_areas, int64_t ring_capacity, int32_t* xy, int64_t vertex_capacity);
+
 #ifdef __cplusplus
 }
 #endif

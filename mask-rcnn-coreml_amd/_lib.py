@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = [
     "mrcnn_unite_tiles", "mrcnn_unite_tiles_host",
     "mrcnn_rle_decode", "mrcnn_rle_decode_host", "mrcnn_instance_map_rle", "mrcnn_instance_map_rle_host",
     "mrcnn_render_detections_rle", "mrcnn_render_detections_rle_host",
+    "mrcnn_rle_to_polygons", "mrcnn_rle_to_polygons_host",
 ]
 # declared in include/maskrcnn_hip_test.h (test / measurement entry points of the same library)
 TEST_SYMBOLS = [
@@ -109,6 +110,7 @@ class Tile(C.Structure):            # mrcnn_tile
 
 MATCH_IOU, MATCH_IOS = 0, 1
 TILES_MAX_CANDIDATES = 8192
+POLYGON_LDS_CORNERS = 1024      # MRCNN_POLYGON_LDS_CORNERS
 
 
 class PngSource(C.Structure):       # mrcnn_png_source
@@ -183,6 +185,9 @@ def lib():
     L.mrcnn_instance_map_rle_host.argtypes = [vp] + _rles + [vp, vp, C.c_float, vp, vp, vp]
     L.mrcnn_render_detections_rle.argtypes = [C.POINTER(Image), vp] + _rles + [C.c_float, C.c_int, C.c_int, C.c_int, vp, vp]
     L.mrcnn_render_detections_rle_host.argtypes = [C.POINTER(Image), vp] + _rles + [C.c_float, C.c_int, C.c_int, vp, vp]
+    _rings = [vp, i64p, i64p, vp, vp, C.c_int64, vp, C.c_int64]    # rle_rings, n_rings, n_vertices, ring_offsets, ring_areas, capacity, xy, capacity
+    L.mrcnn_rle_to_polygons.argtypes = _rles + [vp, vp, C.c_int] + _rings
+    L.mrcnn_rle_to_polygons_host.argtypes = _rles + [vp, vp] + _rings
     L.mrcnn_rle_to_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_from_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_iou.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int64]

@@ -79,10 +79,11 @@ def ragged_output(space, hs, ws, dtype, lead=(), trail=()):
     return out, np.array(starts, dtype=np.int64), views
 
 
-def rle_results(space, B, per, hs, ws, capacity, call):
+def rle_results(space, B, per, hs, ws, capacity, call, resident=None):
     """The run lengths of B images x ``per`` RLEs: call(counts, capacity, run_offsets) -> status runs with a first guess of the
     capacity and, if the library answers MRCNN_ERR_SHAPE with the offsets complete (the capacity was the reason), once more with
-    the need it reported.  Returns rles[b][i] = {"size": [h_b, w_b], "counts": uint32 runs}; only the used runs cross to the host."""
+    the need it reported.  Returns rles[b][i] = {"size": [h_b, w_b], "counts": uint32 runs}; only the used runs cross to the host.
+    resident: a list that receives the (counts, run_offsets) pair as the library wrote it, in the call's own memory space."""
     n = max(0, B * per)
     offs_buf = space.new(n + 1, np.int64, zero=True)
     for _ in range(2):
@@ -94,6 +95,8 @@ def rle_results(space, B, per, hs, ws, capacity, call):
         capacity = int(offsets[n])
     _lib.check(st)
     used = int(offsets[n])
+    if resident is not None:
+        resident.append((counts[:used], offs_buf))
     host = counts[:used] if space.on_host else counts[:used].cpu().numpy().view(np.uint32)
     return [[{"size": [int(hs[b]), int(ws[b])], "counts": host[int(offsets[b * per + i]):int(offsets[b * per + i + 1])]}
              for i in range(per)] for b in range(B)]

@@ -4,7 +4,8 @@ The scoring half of the reference's ``maskrcnn evaluate`` (``Sources/maskrcnn/Py
 ``coco_dataset.evaluate_results``) wants COCO-format results; the reference's own ``results.proto`` drops the masks.  Here the masks
 arrive already run-length encoded from the GPU (``detection.masks_rle_source`` / ``mrcnn_masks_rle_source``); this module turns them
 into COCO's compressed strings (``mrcnn_rle_to_string`` / ``mrcnn_rle_from_string``, host arithmetic of the C library) and into the
-list of result records.  ``rle_decode`` / ``rle_encode`` are numpy helpers for consumers and tests.  No GPU involved.
+list of result records.  ``rle_decode`` / ``rle_encode`` are numpy helpers for consumers and tests.  No GPU involved, unless
+``coco_results(segmentation="polygon")`` is asked to trace the rings itself.
 
 An RLE here is ``{"size": [h, w], "counts": ...}`` as in pycocotools: pixels in column-major order, ``counts[0]`` the number of
 leading zeros, then alternating run lengths of ones and zeros.  ``counts`` is a uint32 array (uncompressed) or a ``str`` (compressed).
@@ -65,12 +66,23 @@ def rle_encode(plane: np.ndarray) -> Dict:
 
 
 def coco_results(image_ids: Sequence, det_src, rles, sizes, class_to_category: Optional[Dict[int, int]] = None,
-                 score_threshold: float = 0.0) -> List[Dict]:
+                 score_threshold: float = 0.0, segmentation: str = "rle", min_area: int = 1, polygons=None) -> List[Dict]:
     """The COCO results list (``segm`` results, which carry ``bbox`` too) of a batch: image_ids (B), det_src (B, rows, 6) — boxes
     normalized in each SOURCE image, as masks_rle_source returns them —, rles[b][i], sizes = [(h_b, w_b)].  One record per row with
     score > score_threshold: ``bbox`` is the detection's box in source pixels (Matterport's denorm_boxes of the row — the box the mask
     was pasted into — as x, y, width, height), ``category_id`` = class_to_category[class id] (the class id itself without a map),
-    ``segmentation`` the RLE with its compressed string.  ``json.dumps`` takes the list as it is."""
+    ``segmentation`` the RLE with its compressed string.  ``json.dumps`` takes the list as it is.
+
+    segmentation="polygon" writes COCO's other form instead: a list of flat ``[x0, y0, x1, y1, ...]`` float lists, one per ring, in
+    pixel-corner coordinates.  COCO polygons cannot carry holes, so this mode emits only the OUTLINES (the rings of positive area)
+    of at least ``min_area`` pixels and DROPS the hole rings: a mask with a hole comes out filled, and a mask whose outlines are all
+    smaller than min_area has an empty list.  ``polygons`` = what detection.rle_to_polygons or rle_to_polygons_host returned for
+    ``rles`` (rings, areas); None traces them here with detection.rle_to_polygons, on the GPU."""
+    if segmentation not in ("rle", "polygon"):
+        raise ValueError(f"coco_results: segmentation {segmentation!r} is neither 'rle' nor 'polygon'")
+    if segmentation == "polygon" and polygons is None:
+        from .detection import rle_to_polygons
+        polygons = rle_to_polygons([[{"size": r["size"], "counts": _counts(r)} for r in row] for row in rles], sizes)
     det = np.asarray(det_src, dtype=np.float32)
     out = []
     for b, image_id in enumerate(image_ids):
@@ -85,10 +97,13 @@ def coco_results(image_ids: Sequence, det_src, rles, sizes, class_to_category: O
             cls = int(r[4])
             rle = rles[b][i]
             counts = rle["counts"]
+            if segmentation == "polygon":
+                seg = [[float(v) for v in ring.reshape(-1)] for ring, area in zip(polygons[0][b][i], polygons[1][b][i]) if area >= max(1, min_area)]
+            else:
+                seg = {"size": [int(rle["size"][0]), int(rle["size"][1])], "counts": counts if isinstance(counts, str) else rle_to_string(counts)}
             out.append({"image_id": image_id.item() if isinstance(image_id, np.generic) else image_id,
                         "category_id": int(class_to_category[cls]) if class_to_category is not None else cls,
                         "bbox": [float(x1), float(y1), float(x2 - x1), float(y2 - y1)],
                         "score": score,
-                        "segmentation": {"size": [int(rle["size"][0]), int(rle["size"][1])],
-                                         "counts": counts if isinstance(counts, str) else rle_to_string(counts)}})
+                        "segmentation": seg})
     return out

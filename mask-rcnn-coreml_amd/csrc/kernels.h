@@ -562,6 +562,45 @@ void poly_offsets_forward(hipStream_t s, const uint32_t* nruns, long n, long lon
 void poly_write_forward(hipStream_t s, const PolyAnn* anns, long n_anns, const long long* tog_off, const uint32_t* bnd, const uint32_t* nb,
                         const long long* run_offsets, uint32_t* counts);
 
+// ================================================================================================
+// Run-length masks -> polygon rings (mrcnn_rle_to_polygons; kernels_polygons.hip, the rule is polygon_rule.h).  All tables are device
+// arrays.  A UNIT is one vertex column X (0..w) of one RLE; its corners come from merging the runs of pixel columns X-1 and X.  The
+// corners of the whole set lie back to back in unit order — per RLE by (X, Y): the order that names a ring's start — and a corner is
+// polygon_rule.h's 32-bit word.  Every corner has one successor in the walk; the rings are the cycles of that permutation.
+// ================================================================================================
+constexpr int POLYGON_LDS_CORNERS = MRCNN_POLYGON_LDS_CORNERS;   // corners an RLE may have to be sorted and ranked by one block in LDS (24 KiB)
+struct PolygonImage { long long unit0; int h, w; };              // image b: its first unit (slots * (w + 1) units follow) and its sides
+struct PolygonSet {
+    const uint32_t* pre_b;            // rle_prefix_forward's B, indexed like counts
+    const long long* run_offsets;
+    const unsigned long long* totals; // rle_prefix_forward's totals: an RLE that does not sum to its plane is not walked
+    const PolygonImage* tab;
+    int n_images, slots;
+    long long units;
+    uint32_t* unit_cnt;               // units: the corners of a unit (always even)
+    unsigned long long* unit_start;   // units + 1: their exclusive prefix
+    long long* corner0;               // n + 1: the first corner of RLE k
+};
+// unit_cnt, unit_start and corner0, and summary[0..2] = the lowest k whose total is not its plane's h*w (~0: none), the corners of the
+// set, the most corners of one RLE.  The caller reads the summary back before it sizes and launches anything else.
+void polygons_count_forward(hipStream_t s, const PolygonSet& set, unsigned long long* summary);
+struct PolygonWork {                  // n_corners entries each unless said otherwise
+    uint32_t* corner;                 // polygon_rule.h's word
+    uint32_t *succ, *lead, *dist;     // the next corner of the walk, the smallest corner of its ring, the steps from here to that one
+    uint32_t *head, *len;             // 1 / the ring's length at a ring's smallest corner, else 0
+    unsigned long long *ring_id, *vertex0;   // n_corners + 1: the exclusive prefixes of head and len
+    // RLEs above POLYGON_LDS_CORNERS only: slices padded to a power of two (sort, the sum of the padded sizes <= 2 * n_corners), the
+    // padded sizes and their prefix (n, n + 1), and the two sides of the pointer jumping
+    unsigned long long* sort; uint32_t* pad_size; unsigned long long* pad_start;
+    uint32_t *next_a, *next_b; unsigned long long *md_a, *md_b;
+};
+// The walk's permutation, every ring's leader and every corner's rank, then rle_rings (n + 1, device).  n_corners and most (the summary's)
+// size the launches: with R = ceil(log2(most)), R * (R + 3) / 2 + 5 more when most > POLYGON_LDS_CORNERS; never the number of RLEs.
+void polygons_trace_forward(hipStream_t s, const PolygonSet& set, const PolygonWork& w, long long n_corners, long long most, long long* rle_rings);
+// ring_offsets (n_rings + 1), ring_areas (n_rings, may be nullptr) and xy (2 * n_corners), every vertex at its final place
+void polygons_write_forward(hipStream_t s, const PolygonWork& w, long long n_corners, long long n_rings, long long* ring_offsets, long long* ring_areas,
+                            int32_t* xy);
+
 // COCOeval.accumulate (mrcnn_coco_accumulate; kernels_coco_acc.hip).  -ffp-contract=off.  All tables are device arrays.
 // A chunk is COCO_ACC_CHUNK consecutive entries of one category's segment [seg0, seg0 + seg_len) of the flat detection list, starting
 // `at` entries into it (a multiple of the chunk); the chunks of all segments, in order, are the grid of the sort kernels.

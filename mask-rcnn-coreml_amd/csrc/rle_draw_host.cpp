@@ -36,7 +36,7 @@ int check_run_offsets(const int64_t* run_offsets, int64_t n, const char* who, st
 }
 
 // every RLE sums to its plane, or nothing is drawn
-static int check_sums(const Set& s, const char* who, std::string* err)
+int check_sums(const Set& s, const char* who, std::string* err)
 {
     const int64_t n = (int64_t)s.n_images * s.slots;
     const int st = check_run_offsets(s.run_offsets, n, who, err);

@@ -24,6 +24,8 @@ int check_set(const Set& s, int max_slots, const char* who, std::string* err);
 int check_render(int alpha, int stroke, const char* who, std::string* err);
 // run_offsets (host memory, n_images*slots + 1 entries): non-negative and not decreasing (MRCNN_ERR_SHAPE naming the RLE).
 int check_run_offsets(const int64_t* run_offsets, int64_t n, const char* who, std::string* err);
+// an RLE set in host memory: check_run_offsets, then every RLE sums to its plane (MRCNN_ERR_SHAPE naming the RLE, its image and its slot)
+int check_sums(const Set& s, const char* who, std::string* err);
 
 // The definitions.  All pointers are host memory; nothing is written unless every RLE sums to its plane.
 int decode_host(const Set& s, uint8_t* out, const int64_t* out_offsets, std::string* err);

@@ -145,7 +145,8 @@ def _tile_table(tiles):
 _METRICS = {"iou": _lib.MATCH_IOU, "ios": _lib.MATCH_IOS}
 
 
-def _merge_tiles(host_definition, detections, masks, tiles, sizes, model_h, model_w, threshold, metric, match_threshold, max_out, unite=False):
+def _merge_tiles(host_definition, detections, masks, tiles, sizes, model_h, model_w, threshold, metric, match_threshold, max_out, unite=False,
+                 resident=None):
     name = "unite_tiles" if unite else "merge_tiles"
     space = Space(detections)
     ptr = space.ptr
@@ -175,7 +176,7 @@ def _merge_tiles(host_definition, detections, masks, tiles, sizes, model_h, mode
             return getattr(_lib.lib(), f"mrcnn_{name}_host")(*head, *tail)
         return getattr(_lib.lib(), f"mrcnn_{name}")(*head, space.code, *tail)
     # the first attempt is sized as masks_rle_source sizes its own
-    rles = rle_results(space, B, max_out, hs, ws, int(max(1, max_out) * (2 * ws.astype(np.int64) + 2).sum()), call)
+    rles = rle_results(space, B, max_out, hs, ws, int(max(1, max_out) * (2 * ws.astype(np.int64) + 2).sum()), call, resident)
     if unite:
         return det_src, source, n_kept, rles, areas, bboxes, n_parts, group
     return det_src, source, n_kept, rles, areas, bboxes
@@ -415,3 +416,53 @@ def render_detections_rle(images, det_src, rles, min_score: float = 0.7, alpha: 
 def render_detections_rle_host(images, det_src, rles, min_score: float = 0.7, alpha: int = 128, stroke: int = 3):
     """The definition of render_detections_rle: the sequential host code (``mrcnn_render_detections_rle_host``), no GPU."""
     return _render_detections_rle(True, images, det_src, rles, min_score, alpha, stroke)
+
+
+# ---- polygons out (mrcnn_rle_to_polygons) -------------------------------------------------------------------------------------------
+def _rle_to_polygons(host_definition, rles, sizes, device, flat):
+    name = "rle_to_polygons_host" if host_definition else "rle_to_polygons"
+    if device is None and not host_definition and isinstance(rles, tuple) and len(rles) == 2 and hasattr(rles[0], "is_cuda"):
+        device = rles[0].device                                  # a pair of CUDA tensors: traced where they lie, tensors out
+    counts, offs, B, slots, hs, ws = _rle_set(name, rles, sizes, device)
+    space = Space(device)
+    ptr = space.ptr
+    n = B * slots
+    rle_rings = space.new(n + 1, np.int64, zero=True)
+    totals = (C.c_int64(0), C.c_int64(0))
+    head = (ptr(counts), ptr(offs), B, slots, hs.ctypes.data, ws.ctypes.data) + (() if host_definition else (space.code,))
+    entry = getattr(_lib.lib(), "mrcnn_" + name)
+    cap_r, cap_v = 4 * n + 16, 2 * int(counts.shape[0]) + 64      # a first guess; the library names what it needs
+    for _ in range(2):
+        ring_offsets, ring_areas, xy = space.new(cap_r + 1, np.int64), space.new(max(1, cap_r), np.int64), space.new(max(1, 2 * cap_v), np.int32)
+        st = entry(*head, ptr(rle_rings), C.byref(totals[0]), C.byref(totals[1]), ptr(ring_offsets), ptr(ring_areas), cap_r, ptr(xy), cap_v)
+        if st != 4 or (totals[0].value <= cap_r and totals[1].value <= cap_v):
+            break
+        cap_r, cap_v = totals[0].value, totals[1].value
+    _lib.check(st)
+    R, V = totals[0].value, totals[1].value
+    ring_offsets, ring_areas, xy = ring_offsets[:R + 1], ring_areas[:R], xy[:2 * V].reshape(V, 2)
+    if flat:
+        return {"rle_rings": rle_rings, "ring_offsets": ring_offsets, "ring_areas": ring_areas, "xy": xy, "n_rings": R, "n_vertices": V}
+    if not space.on_host:
+        rle_rings, ring_offsets, ring_areas, xy = (a.cpu().numpy() for a in (rle_rings, ring_offsets, ring_areas, xy))
+    rings = [[[xy[ring_offsets[r]:ring_offsets[r + 1]] for r in range(rle_rings[b * slots + i], rle_rings[b * slots + i + 1])]
+              for i in range(slots)] for b in range(B)]
+    areas = [[ring_areas[rle_rings[b * slots + i]:rle_rings[b * slots + i + 1]] for i in range(slots)] for b in range(B)]
+    return rings, areas
+
+
+def rle_to_polygons(rles, sizes=None, device=None, flat: bool = False):
+    """The boundary of every mask of an RLE set as closed rings of pixel corners, traced from the runs on the GPU
+    (``mrcnn_rle_to_polygons``; the geometry is defined in include/maskrcnn_hip.h).  ``rles`` as rle_decode_planes takes them: what
+    merge_tiles, unite_tiles or masks_rle_source returned, or a (counts, run_offsets) pair with ``sizes``; a pair of CUDA tensors is
+    traced where it lies.  Returns (rings, areas): rings[b][i] is the list of the (m, 2) int32 arrays of RLE i of image b — x then y
+    per vertex, every ring, outlines and holes alike, ordered by their start vertex — and areas[b][i] their signed areas as int64:
+    positive for an outline, negative for a hole.  flat=True returns the library's own arrays instead (rle_rings, ring_offsets,
+    ring_areas, xy as (V, 2), n_rings, n_vertices): numpy arrays, or tensors that stay on the device when ``device`` is given or the
+    pair is CUDA tensors."""
+    return _rle_to_polygons(False, rles, sizes, device, flat)
+
+
+def rle_to_polygons_host(rles, sizes=None, flat: bool = False):
+    """The definition of rle_to_polygons: the sequential host code (``mrcnn_rle_to_polygons_host``), no GPU; numpy out."""
+    return _rle_to_polygons(True, rles, sizes, None, flat)

@@ -143,23 +143,28 @@ class MaskRCNN(_Model):
         return det, mask
 
     def predict_tiled(self, images, tile=None, overlap=(64, 64), metric="ios", match_threshold=0.5, max_out=None, threshold=0.5,
-                      unite=False, link_threshold=0.5):
+                      unite=False, link_threshold=0.5, polygons=False):
         """Large images as overlapping windows at native resolution: detection.tile_plan per image (tile = None: the model's input
         size), predict_tiles, detection.merge_tiles.  Returns (det_src, source, n_kept, rles) in the frame of the images, in the
         form coco_results.coco_results and coco_eval.score_batch take.  By default an object is found whole only if some window
         holds it whole: choose the overlap at least as large as the largest object of interest.  unite=True replaces the third step
         by detection.unite_tiles(metric, link_threshold): the cut parts of an object larger than the overlap, and its duplicates,
-        become one mask (match_threshold is not used then)."""
-        from .detection import merge_tiles, tile_plan, unite_tiles
+        become one mask (match_threshold is not used then).  polygons=True adds a fifth result, (rings, areas) as
+        detection.rle_to_polygons returns them: the boundaries of the masks, traced from the runs where the merge or the union left
+        them — on the device when the images are CUDA tensors."""
+        from .detection import _merge_tiles, rle_to_polygons, tile_plan
         images = list(images)
         H, W = self.image_height, self.image_width
         tile = (H, W) if tile is None else tile
         sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
         tiles = np.concatenate([tile_plan(h, w, tile, overlap, b) for b, (h, w) in enumerate(sizes)])
         det, mask = self.predict_tiles(images, tiles)
-        if unite:
-            return unite_tiles(det, mask, tiles, sizes, H, W, threshold, metric, link_threshold, max_out)[:4]
-        return merge_tiles(det, mask, tiles, sizes, H, W, threshold, metric, match_threshold, max_out)[:4]
+        resident = []
+        out = _merge_tiles(False, det, mask, tiles, sizes, H, W, threshold, metric, link_threshold if unite else match_threshold, max_out, unite=unite,
+                           resident=resident)[:4]
+        if not polygons:
+            return out
+        return (*out, rle_to_polygons(resident[0], sizes))
 
     def predict_jpegs(self, files, entropy="host"):
         """predict_images straight from JPEG files (mrcnn_maskrcnn_predict_jpegs_on): a list of bytes.  The entropy decoders run on the
