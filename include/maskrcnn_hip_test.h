@@ -144,13 +144,56 @@ MRCNN_API int mrcnn_conv_chain_nhwc(const float* t2, int batch, int h, int w, in
 MRCNN_API int mrcnn_bottleneck_stage_nhwc(const float* x, int batch, int h, int w, int nlayers, const float* w1, const float* w2, const float* w3,
                                           const float* const bn[6], int form, int iters, float* out, float* avg_ms, int* status_flag);
 
-/* The fp16-range watchdog word of the calling thread's last mrcnn_conv2d_nhwc / mrcnn_conv_chain_nhwc / mrcnn_bottleneck_nhwc / mrcnn_bottleneck_first_nhwc (each of them
+/* The fp16-range watchdog word of the calling thread's last mrcnn_conv2d_nhwc / mrcnn_test_conv_form_nhwc / mrcnn_conv_chain_nhwc / mrcnn_bottleneck_nhwc / mrcnn_bottleneck_first_nhwc (each of them
  * gives its launches a zeroed 4-byte device flag, the way the engine does for a predict, and reads it back when they have finished):
  * bit 0: some stored output has !(|v| < 65504) after scale, shift, residual and activation (NaN included) — what makes MRCNN_F16 refuse a predict and
- * MRCNN_F32S / MRCNN_F32X3 recompute it.  Padded columns, rows beyond M and the on-chip lanes of no real output never set it; in the fused bottlenecks
+ * MRCNN_F32S / MRCNN_F32X3 recompute it.  Padded columns, rows beyond M, the on-chip lanes of no real output and, in the selected-class mode
+ * (where the watched value is the activated y the dot reads), ROI rows of class -1 never set it; in the fused bottlenecks
  * the two mid tensors count as stored outputs.  MRCNN_F32 (exact fp32: no fp16 hand-over) leaves the word 0; so does an entry that failed.
  * mrcnn_bottleneck_stage_nhwc returns its word through status_flag.  tests/test_gpu_range_watch.py pins every epilogue form with it. */
 MRCNN_API int mrcnn_test_last_range_flag(int* flag);
+
+/* ONE conv_forward of a form only the engine builds, on caller (host) data, in any of the four compute modes — what mrcnn_conv2d_nhwc's dense
+ * description cannot reach (tests/test_gpu_conv_forms.py; the float64 definitions: tests/conv_forms_cases.py).  The layer reads a level of
+ * batch x h x w pixels of cin channels and has cout output channels; ksize 1 | 3 ('same' padding ksize/2), stride, act 0 | 1 | 2 as mrcnn_conv2d_nhwc.
+ *   in        dense (batch, h*in_step, w*in_step, cin); in_step 1 | 2: the layer reads every in_step-th row and column through its strides
+ *             (the RPN's shared layer on P6 reads P5 this way).
+ *   filters   (cout, ksize, ksize, cin); deconv2 = 1: (2, 2, cout, cin) = (dy, dx, co, ci) of the transposed 2x2 stride-2 convolution
+ *             (ksize 1, stride 1, in_step 1), packed by the engine's own routine (csrc/conv_pack.h).  scale / shift: cout entries or NULL (1 / 0).
+ *   residual  NULL or (batch, OH, OW, cout); res_shift = 1: (batch, ceil(OH/2), ceil(OW/2), cout), read at (oh >> 1, ow >> 1) — the FPN laterals.
+ *   outputs   n_split = 0: every column goes to `out`; n_split > 0: columns [0, n_split) go to `out`, the rest to `out2` (the unfused RPN heads).
+ *             Output k is a buffer of len elements; image b starts at element offset + b * batch_stride, its pixel p at p * pitch (pitch >= the
+ *             output's columns; 0 = dense).  deconv2: the output image is 2h x 2w, pixel (y, x) at y * row_pitch + x * pitch (row_pitch 0 = 2w * pitch).
+ *             Each buffer is filled with `sentinel` before the launch and returned WHOLE in out / out2 (fp32; fp16 stores widened: pass a
+ *             sentinel fp16 holds), so a caller sees every element the launch did not address.  out_f32 = 1 (MRCNN_F16 only): fp32 stores.
+ *   sel_w     non-NULL with deconv2: the selected-class dot instead of the store (ConvDesc::sel_partial) — sel_w (nc, cout), sel_cid (batch) with
+ *             values < 0 = "row not written".  sel_partial receives batch * 4*h*w * parts floats, sentinel-filled first, *sel_parts = parts =
+ *             cout / (64 | 128 by "mask_sel_wave"); a caller sizes it for cout / 64.  Nothing goes to `out` (may be NULL).
+ * dtype = the compute mode; operands are converted on the host as in mrcnn_conv2d_nhwc, padded filter rows are zero and carry a shift far
+ * beyond the fp16 range.  The watchdog word of the call: mrcnn_test_last_range_flag.  A combination the dispatcher cannot run fails with a
+ * message (MRCNN_ERR_INVALID / _SHAPE / _UNSUPPORTED); nothing falls back. */
+typedef struct mrcnn_test_conv_output {
+    float* data;                   /* len floats, host */
+    int64_t len, offset, batch_stride, pitch, row_pitch;
+} mrcnn_test_conv_output;
+typedef struct mrcnn_test_conv_form {
+    int32_t dtype, batch, h, w, cin, cout;
+    int32_t ksize, stride, act, in_step, res_shift, n_split, deconv2, out_f32;
+    int32_t nc, reserved;
+    float sentinel;
+    int32_t reserved2;
+    const float* in;
+    const float* filters;
+    const float* scale;
+    const float* shift;
+    const float* residual;
+    const float* sel_w;
+    const int32_t* sel_cid;
+    mrcnn_test_conv_output out, out2;
+    float* sel_partial;
+    int32_t* sel_parts;
+} mrcnn_test_conv_form;
+MRCNN_API int mrcnn_test_conv_form_nhwc(const mrcnn_test_conv_form* form);
 
 /* The classifier head behind its last inner product, on caller (host) rows: logits (n rows at stride ld >= nc, the first nc entries of a row are read),
  * bbox (n, nc*4) -> probs_out (n, nc) = the row softmax, cls6_out (n, 6) = (dy, dx, dh, dw, class id, score) of the arg-max class (ties -> lowest index).

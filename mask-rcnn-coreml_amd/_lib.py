@@ -55,6 +55,7 @@ TEST_SYMBOLS = [
     "mrcnn_bench_conv", "mrcnn_bench_conv_dtype", "mrcnn_model_conv_profile_enable", "mrcnn_model_conv_profile_get",
     "mrcnn_model_conv_profile_shapes", "mrcnn_conv2d_nhwc", "mrcnn_debug_set", "mrcnn_bottleneck_nhwc", "mrcnn_bench_mfma_probe", "mrcnn_model_conv_profile_group", "mrcnn_bottleneck_first_nhwc", "mrcnn_bottleneck_stage_nhwc", "mrcnn_model_conv_profile_bytes",
     "mrcnn_jpeg_last_stage_ms", "mrcnn_jpeg_coefficients", "mrcnn_test_last_range_flag", "mrcnn_classifier_rows", "mrcnn_test_roi_align_nhwc_batch", "mrcnn_conv_chain_nhwc",
+    "mrcnn_test_conv_form_nhwc",
 ]
 
 
@@ -118,6 +119,19 @@ class PngSource(C.Structure):       # mrcnn_png_source
 
 
 _lib = None
+
+
+class ConvFormOutput(C.Structure):   # mrcnn_test_conv_output
+    _fields_ = [("data", C.c_void_p), ("len", C.c_int64), ("offset", C.c_int64), ("batch_stride", C.c_int64), ("pitch", C.c_int64),
+                ("row_pitch", C.c_int64)]
+
+
+class ConvForm(C.Structure):     # mrcnn_test_conv_form
+    _fields_ = [(k, C.c_int32) for k in ("dtype", "batch", "h", "w", "cin", "cout", "ksize", "stride", "act", "in_step", "res_shift", "n_split",
+                                         "deconv2", "out_f32", "nc", "reserved")] + \
+               [("sentinel", C.c_float), ("reserved2", C.c_int32)] + \
+               [(k, C.c_void_p) for k in ("in_", "filters", "scale", "shift", "residual", "sel_w", "sel_cid")] + \
+               [("out", ConvFormOutput), ("out2", ConvFormOutput), ("sel_partial", C.c_void_p), ("sel_parts", C.c_void_p)]
 
 
 class ConvShapeStat(C.Structure):    # mrcnn_conv_shape_stat
@@ -268,6 +282,7 @@ def lib():
                                        C.c_int, vp, vp]
     L.mrcnn_test_roi_align_nhwc_batch.argtypes = [C.POINTER(vp), ip, ip, C.c_int, C.c_int, f32p, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double,
                                                   C.c_double, vp, vp]
+    L.mrcnn_test_conv_form_nhwc.argtypes = [C.POINTER(ConvForm)]
     _lib = L
     return L
 

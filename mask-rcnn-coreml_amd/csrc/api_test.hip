@@ -5,6 +5,7 @@
 #include <random>
 
 #include "api_util.h"
+#include "conv_pack.h"
 #include "knobs.h"
 
 using namespace mrcnn;
@@ -235,6 +236,143 @@ extern "C" int mrcnn_conv2d_nhwc(const float* in, int batch, int h, int w, int c
         range.keep();
         if (adt == MRCNN_F16) download_f16_as_f32(d.out, n_out, out);
         else HIP_CHECK(hipMemcpy(out, d.out, n_out * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+// One conv_forward of a form only the engine builds (include/maskrcnn_hip_test.h: mrcnn_test_conv_form_nhwc; tests/test_gpu_conv_forms.py): the
+// strided input view, the shifted residual, the column split into two pitched outputs, the 2x2 scatter and its selected-class dot, fp32 stores
+// of fp16 tensors.  Every output buffer is sentinel-filled and returned whole.
+namespace {
+
+// one pitched output of the entry: the device copy of the caller's whole buffer, and where the layer's images sit in it
+struct FormOutput {
+    DevBuf dev;
+    long len = 0, offset = 0, sB = 0, sP = 0, sH = 0;
+    bool f32 = true;
+    void* base() const { return static_cast<char*>(dev.p) + (size_t)offset * (f32 ? 4 : 2); }
+    // cols columns per pixel of a rows x width image; every addressed element must lie inside the buffer
+    void lay_out(const mrcnn_test_conv_output& o, const char* who, int B, int rows, int width, int cols, bool deconv, bool as_f32, float sentinel)
+    {
+        MRCNN_REQUIRE(o.data && o.len > 0 && o.offset >= 0 && o.pitch >= 0 && o.row_pitch >= 0 && o.batch_stride >= 0, MRCNN_ERR_INVALID, "test_conv_form: output %s missing or negative", who);
+        MRCNN_REQUIRE(deconv || o.row_pitch == 0, MRCNN_ERR_INVALID, "test_conv_form: output %s: a row pitch goes with deconv2 only (rows of an image are contiguous)", who);
+        len = o.len; offset = o.offset; f32 = as_f32;
+        sP = o.pitch ? o.pitch : cols;
+        sH = o.row_pitch ? o.row_pitch : (long)width * sP;
+        MRCNN_REQUIRE(sP >= cols && sH >= (long)width * sP, MRCNN_ERR_SHAPE, "test_conv_form: output %s: pitch %ld under %d columns, or row pitch %ld under a row", who, sP, cols, sH);
+        const long image = (long)(rows - 1) * sH + (long)(width - 1) * sP + cols;      // the elements from an image's first to its last addressed one
+        sB = o.batch_stride ? o.batch_stride : (long)rows * sH;
+        MRCNN_REQUIRE(sB >= (long)rows * sH, MRCNN_ERR_SHAPE, "test_conv_form: output %s: batch stride %ld under an image of %ld", who, sB, (long)rows * sH);
+        MRCNN_REQUIRE(offset + (long)(B - 1) * sB + image <= len, MRCNN_ERR_SHAPE, "test_conv_form: output %s: %d images do not fit %ld elements behind offset %ld", who, B, len, offset);
+        const std::vector<float> fill((size_t)len, sentinel);
+        (f32 ? upload_f32 : upload_f16)(dev, fill.data(), fill.size(), 0);
+    }
+    void deliver(float* dst) const
+    {
+        if (f32) HIP_CHECK(hipMemcpy(dst, dev.p, (size_t)len * 4, hipMemcpyDeviceToHost));
+        else download_f16_as_f32(dev.p, (size_t)len, dst);
+    }
+};
+
+}  // namespace
+
+extern "C" int mrcnn_test_conv_form_nhwc(const mrcnn_test_conv_form* form)
+{
+    return guarded([&] {
+        require_gpu();
+        MRCNN_REQUIRE(form, MRCNN_ERR_INVALID, "test_conv_form: null form");
+        const mrcnn_test_conv_form& f = *form;
+        const int dtype = f.dtype, B = f.batch, H = f.h, W = f.w, Cin = f.cin, Cout = f.cout, K = f.ksize;
+        MRCNN_REQUIRE(f.in && f.filters && B >= 1 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 1 && (K == 1 || K == 3) && f.stride >= 1 && f.act >= 0 && f.act <= 2,
+                      MRCNN_ERR_INVALID, "bad test_conv_form argument");
+        MRCNN_REQUIRE(dtype == MRCNN_F32 || dtype == MRCNN_F16 || dtype == MRCNN_F32S || dtype == MRCNN_F32X3, MRCNN_ERR_UNSUPPORTED, "test_conv_form: dtype %d", dtype);
+        MRCNN_REQUIRE((f.in_step == 1 || f.in_step == 2) && (f.res_shift == 0 || f.res_shift == 1) && (f.deconv2 == 0 || f.deconv2 == 1) && (f.out_f32 == 0 || f.out_f32 == 1),
+                      MRCNN_ERR_INVALID, "test_conv_form: in_step 1 | 2, res_shift / deconv2 / out_f32 0 | 1");
+        const bool sel = f.sel_w != nullptr;
+        MRCNN_REQUIRE(!f.out_f32 || dtype == MRCNN_F16, MRCNN_ERR_INVALID, "test_conv_form: out_f32 is an option of MRCNN_F16 (the other modes store fp32 anyway)");
+        MRCNN_REQUIRE(f.res_shift == 0 || f.residual, MRCNN_ERR_INVALID, "test_conv_form: res_shift without a residual");
+        MRCNN_REQUIRE(f.n_split >= 0 && f.n_split < Cout, MRCNN_ERR_INVALID, "test_conv_form: n_split %d outside [0, cout %d)", f.n_split, Cout);
+        MRCNN_REQUIRE(!f.deconv2 || (K == 1 && f.stride == 1 && f.in_step == 1 && !f.residual && f.n_split == 0), MRCNN_ERR_INVALID,
+                      "test_conv_form: deconv2 is a 1x1 stride-1 GEMM over a dense input with one output and no residual");
+        MRCNN_REQUIRE(!sel || (f.deconv2 && f.sel_cid && f.sel_partial && f.sel_parts && f.nc >= 1), MRCNN_ERR_INVALID,
+                      "test_conv_form: the selected-class mode needs deconv2, sel_cid, nc >= 1 and somewhere to put the partial sums");
+        const int adt = dtype == MRCNN_F16 ? MRCNN_F16 : MRCNN_F32;
+        const int wdt = dtype == MRCNN_F32 ? MRCNN_F32 : (dtype == MRCNN_F32X3 ? MRCNN_F32X3 : MRCNN_F16);
+        MRCNN_REQUIRE(Cin % (adt == MRCNN_F16 ? 64 : 32) == 0, MRCNN_ERR_SHAPE, "test_conv_form: Cin %d not a multiple of the K tile", Cin);
+        const bool half = adt == MRCNN_F16;
+        auto* const upload_act = half ? upload_f16 : upload_f32;
+        const int ncols = f.deconv2 ? 4 * Cout : Cout;
+        const int bn = conv_n_tile(ncols), npad = (ncols + bn - 1) / bn * bn;
+        const int step = f.in_step;
+
+        // the input: dense (B, H*step, W*step, Cin), read through strides
+        DevBuf din, dw, ds, db, dres, dselw, dcid, dpartial;
+        const size_t n_in = (size_t)B * (H * step) * (W * step) * Cin;
+        upload_act(din, f.in, n_in, n_in);
+        // the filters, in conv_pack.h's layouts; the padded rows are zero ...
+        const std::vector<float> wp = f.deconv2 ? pack_deconv2_rows(Cin, Cout, npad, [&](int dy, int dx, int o, int i) { return f.filters[(((size_t)dy * 2 + dx) * Cout + o) * Cin + i]; })
+                                                : pack_filter_rows(Cout, Cin, K, K, npad, [&](int o, int y, int x, int i) { return f.filters[(((size_t)o * K + y) * K + x) * Cin + i]; });
+        (wdt != MRCNN_F32 ? upload_f16 : upload_f32)(dw, wp.data(), wp.size(), 0);
+        // ... and carry a shift far beyond the fp16 range, as in mrcnn_conv2d_nhwc: no epilogue stores them, and a watchdog that forgot to gate them reports it
+        std::vector<float> hs(npad, 0.f), hb(npad, 1.0e30f);
+        for (int q = 0; q < (f.deconv2 ? 4 : 1); ++q)
+            for (int o = 0; o < Cout; ++o) {
+                const int n = f.deconv2 ? deconv2_row(q >> 1, q & 1, o, Cout) : o;
+                hs[n] = f.scale ? f.scale[o] : 1.f; hb[n] = f.shift ? f.shift[o] : 0.f;
+            }
+        upload_f32(ds, hs.data(), npad);
+        upload_f32(db, hb.data(), npad);
+
+        ConvDesc d = dense_nhwc_desc(din.p, B, H, W, Cin, dw.p, K, f.stride, ds.as<float>(), db.as<float>(), nullptr, Cout, npad, f.act);
+        d.in_sW = (long)step * Cin; d.in_sH = (long)step * (W * step) * Cin; d.in_sB = (long)(H * step) * (W * step) * Cin;
+        d.dtype = adt; d.wdtype = wdt; d.out_f32 = f.out_f32;
+        const int OH = d.OH, OW = d.OW;
+        if (f.residual) {
+            const int RH = f.res_shift ? (OH + 1) / 2 : OH, RW = f.res_shift ? (OW + 1) / 2 : OW;
+            const size_t n_res = (size_t)B * RH * RW * Cout;
+            upload_act(dres, f.residual, n_res, n_res);
+            d.res = dres.p; d.res_sW = Cout; d.res_sH = (long)RW * Cout; d.res_sB = (long)RH * RW * Cout; d.res_shift = f.res_shift;
+        }
+        // the outputs
+        const bool st32 = !half || f.out_f32;
+        FormOutput o1, o2;
+        if (!sel) {
+            o1.lay_out(f.out, "out", B, f.deconv2 ? 2 * H : OH, f.deconv2 ? 2 * W : OW, f.n_split ? f.n_split : Cout, f.deconv2 != 0, st32, f.sentinel);
+            d.out = o1.base(); d.out_sB = o1.sB; d.out_sP = o1.sP;
+            if (f.deconv2) { d.deconv2 = 1; d.out_sH = o1.sH; d.out_sW = o1.sP; }
+        }
+        if (f.n_split) {
+            o2.lay_out(f.out2, "out2", B, OH, OW, Cout - f.n_split, false, st32, f.sentinel);
+            d.out2 = o2.base(); d.out2_sB = o2.sB; d.out2_sP = o2.sP; d.n_split = f.n_split;
+        }
+        size_t n_partial = 0;
+        if (sel) {
+            for (int b = 0; b < B; ++b) MRCNN_REQUIRE(f.sel_cid[b] < f.nc, MRCNN_ERR_INVALID, "test_conv_form: sel_cid[%d] = %d with %d classes", b, f.sel_cid[b], f.nc);
+            MRCNN_REQUIRE(Cout % conv_sel_part_cols() == 0, MRCNN_ERR_SHAPE, "test_conv_form: cout %d is not a multiple of the %d-column partial sums", Cout, conv_sel_part_cols());
+            *f.sel_parts = Cout / conv_sel_part_cols();
+            n_partial = (size_t)B * 4 * H * W * *f.sel_parts;
+            const std::vector<float> fill(n_partial, f.sentinel);
+            upload_f32(dpartial, fill.data(), n_partial);
+            upload_f32(dselw, f.sel_w, (size_t)f.nc * Cout);
+            dcid.alloc((size_t)B * 4);
+            HIP_CHECK(hipMemcpy(dcid.p, f.sel_cid, (size_t)B * 4, hipMemcpyHostToDevice));
+            // (`out` is not written in this mode; the description keeps the scatter's strides of a dense image, as the engine's does)
+            d.deconv2 = 1; d.out_sP = Cout; d.out_sW = Cout; d.out_sH = (long)2 * W * Cout; d.out_sB = (long)4 * H * W * Cout;
+            d.sel_w = dselw.as<float>(); d.sel_cid = dcid.as<int32_t>(); d.sel_partial = dpartial.as<float>();
+        }
+        Stream st;
+        DevBuf dwh;
+        if (K == 3 && wdt != MRCNN_F32 && !half && conv_halo_packable(K, K, Cin, npad)) {
+            conv_halo_pack(st.s, dw.p, npad, Cin, dwh);
+            d.wgt_halo = dwh.p;
+        }
+        ScopedConvScratch scratch(wdt != MRCNN_F32 && !half);
+        ScopedRangeFlag range(st.s, dtype != MRCNN_F32);
+        conv_forward(st.s, d);
+        HIP_CHECK(hipStreamSynchronize(st.s));
+        range.keep();
+        if (!sel) o1.deliver(f.out.data);
+        if (f.n_split) o2.deliver(f.out2.data);
+        if (sel) HIP_CHECK(hipMemcpy(f.sel_partial, dpartial.p, n_partial * 4, hipMemcpyDeviceToHost));
     });
 }
 

@@ -189,6 +189,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[T
                 if (need_bp) { b = m / ohw; pix = m - b * ohw; }
                 if (need_yx) { oh = pix / a.OW; ow = pix - oh * a.OW; }
                 float4 v[NV];
+                bool row_out_of_range = false;
 #pragma unroll
                 for (int q = 0; q < NV; ++q) {
                     float4 x = *reinterpret_cast<const float4*>(&Cs[r * CWP + c4 * CPT + 4 * q]);
@@ -199,13 +200,15 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[T
                         x.x = 1.0f / (1.0f + expf(-x.x)); x.y = 1.0f / (1.0f + expf(-x.y));
                         x.z = 1.0f / (1.0f + expf(-x.z)); x.w = 1.0f / (1.0f + expf(-x.w));
                     }
-                    out_of_range = out_of_range || !(fabsf(x.x) < 65504.0f) || !(fabsf(x.y) < 65504.0f) || !(fabsf(x.z) < 65504.0f) || !(fabsf(x.w) < 65504.0f);
+                    row_out_of_range = row_out_of_range || !(fabsf(x.x) < 65504.0f) || !(fabsf(x.y) < 65504.0f) || !(fabsf(x.z) < 65504.0f) || !(fabsf(x.w) < 65504.0f);
                     v[q] = x;
                 }
+                if (!a.sel_partial) out_of_range = out_of_range || row_out_of_range;
                 if (a.sel_partial) {
                     // selected-class dot over this thread's channels, then over the TPR threads of the row (a 128-channel part of
                     // one output pixel); fixed order: identical for every batch size
                     const int cid = a.sel_cid[b];
+                    out_of_range = out_of_range || (row_out_of_range && cid >= 0);      // (a row that is not written has no output to watch)
                     float dot = 0.f;
                     if (cid >= 0) {
                         const float* wr = a.sel_w + (size_t)cid * a.Cout + co;
@@ -425,7 +428,7 @@ __device__ __forceinline__ void conv_epilogue_sel_wave(const ConvArgs& a, f32x16
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     if (relu) x[r] = fmaxf(x[r], 0.f);
-                    out_of_range = out_of_range || (ok && !(fabsf(x[r]) < 65504.0f));
+                    out_of_range = out_of_range || (cid >= 0 && !(fabsf(x[r]) < 65504.0f));      // (cid < 0: beyond M, or a row that is not written)
                     if constexpr (sizeof(T) == 2) x[r] = (float)(_Float16)x[r];          // the value the fp16 tensor would have held
                 }
                 dot += x[0] * w.x + x[1] * w.y + x[2] * w.z + x[3] * w.w;

@@ -369,7 +369,9 @@ void conv_forward(hipStream_t s, const ConvDesc& d_in, const ConvDesc* sc)
     }
     if (pp_bn) { a.tiles_m = (a.M + 255) / 256; a.tiles_n = d.Npad / pp_bn; }
     // K >= 2048: the 3x3 layers; and every chunked layer (the 8-wave form has no registers for the second accumulator set)
-    const bool wide_waves = split && bn == 128 && (a.kchunks > 1 || fuse || (g_tn4 < 0 ? a.Ktot / bk >= 64 : g_tn4 != 0));
+    // (selected-class mode: its wave-private epilogue exists for the eight-wave tile only, and the partial-sum layout the caller sized
+    //  — conv_sel_part_cols — must not depend on K or on "conv_tn4": the four-wave form would return without a single store)
+    const bool wide_waves = split && bn == 128 && !d.sel_partial && (a.kchunks > 1 || fuse || (g_tn4 < 0 ? a.Ktot / bk >= 64 : g_tn4 != 0));
     const ProfScope prof(s);
     // 3x3 stride-1 layers of the split modes: the persistent halo kernel, whenever the layer qualifies — by its geometry and
     // mode alone, so that a layer runs in ONE summation order whatever the batch (the kernel's K order is its own).

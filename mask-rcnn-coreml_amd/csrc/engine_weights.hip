@@ -1,6 +1,7 @@
 // engine_weights.hip — the .mrcw reader, BatchNorm folding and the weight packers: everything between an artefact's bytes and a
 // PackedConv on the device.
 #include "engine_internal.h"
+#include "conv_pack.h"
 
 #include <math.h>
 #include <string.h>
@@ -221,12 +222,7 @@ PackedConv pack_conv_oihw(const MrcwFile& f, const std::string& conv, const std:
     const int O = t.dims[0], I = t.dims[1], KH = t.dims[2], KW = t.dims[3];
     const std::vector<float> k = f.floats(conv + "/kernel");
     PackedConv pc = new_pack(dtype, I, O, KH, KW);
-    std::vector<float> w((size_t)pc.Npad * KH * KW * I, 0.f);
-    for (int o = 0; o < O; ++o)
-        for (int i = 0; i < I; ++i)
-            for (int y = 0; y < KH; ++y)
-                for (int x = 0; x < KW; ++x)
-                    w[(((size_t)o * KH + y) * KW + x) * I + i] = k[(((size_t)o * I + i) * KH + y) * KW + x];
+    const std::vector<float> w = pack_filter_rows(O, I, KH, KW, pc.Npad, [&](int o, int y, int x, int i) { return k[(((size_t)o * I + i) * KH + y) * KW + x]; });
     std::vector<float> sc, sh;
     fold_bn(f, conv, bn, O, pc.Npad, sc, sh);
     finish_pack(pc, w, sc, sh);
@@ -307,12 +303,11 @@ PackedConv pack_deconv2(const MrcwFile& f, const std::string& name, int dtype)
     PackedConv pc = new_pack(dtype, I, O, 1, 1);
     pc.Npad = 4 * O;                              // (four GEMM rows per output channel: not the rounded-up Cout)
     MRCNN_REQUIRE(pc.Npad % conv_n_tile(pc.Npad) == 0, MRCNN_ERR_SHAPE, "%s: 4*O must be a multiple of the N tile", name.c_str());
-    std::vector<float> w((size_t)pc.Npad * I), sc(pc.Npad, 1.f), sh(pc.Npad);
-    for (int qd = 0; qd < 4; ++qd)
-        for (int o = 0; o < O; ++o) {
-            for (int i = 0; i < I; ++i) w[((size_t)qd * O + o) * I + i] = k[(((size_t)i * O + o) * 2 + (qd >> 1)) * 2 + (qd & 1)];
-            sh[(size_t)qd * O + o] = b[o];
-        }
+    const std::vector<float> w = pack_deconv2_rows(I, O, pc.Npad, [&](int dy, int dx, int o, int i) { return k[(((size_t)i * O + o) * 2 + dy) * 2 + dx]; });
+    std::vector<float> sc(pc.Npad, 1.f), sh(pc.Npad);
+    for (int dy = 0; dy < 2; ++dy)
+        for (int dx = 0; dx < 2; ++dx)
+            for (int o = 0; o < O; ++o) sh[(size_t)deconv2_row(dy, dx, o, O)] = b[o];
     finish_pack(pc, w, sc, sh);
     return pc;
 }
