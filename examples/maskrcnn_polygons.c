@@ -1,16 +1,17 @@
 /*
  * maskrcnn_polygons.c — run-length masks handed on as geometry, in plain C99 over include/maskrcnn_hip.h: an RLE set is read from a
  * text file, mrcnn_rle_to_polygons traces the boundary of every mask on the GPU (the size query first, then the call), and the rings
- * are printed, one per line, with their signed areas: positive for an outline, negative for a hole.
+ * are printed, one per line, with their signed areas: positive for an outline, negative for a hole.  With --tolerance T the rings are
+ * simplified first (mrcnn_polygons_simplify, Douglas-Peucker within T pixels): the areas printed stay the pixel areas.
  *
  *   cc -std=c99 -Iinclude examples/maskrcnn_polygons.c -Lmask-rcnn-coreml_amd -lmaskrcnn_hip \
  *      -Wl,-rpath,$PWD/mask-rcnn-coreml_amd -Wl,-rpath-link,/opt/rocm/lib -o maskrcnn_polygons
- *   ./maskrcnn_polygons [--host] <set.txt>
+ *   ./maskrcnn_polygons [--host] [--tolerance T] <set.txt>
  *
  * <set.txt> holds whitespace-separated integers: n_images and slots; then per image its height and width and, for each of its `slots`
  * RLEs, the number of runs followed by the runs (column-major, the first run counts zeros) — the layout mrcnn_masks_rle_source,
- * mrcnn_merge_tiles and mrcnn_unite_tiles write.  --host calls the sequential definition, mrcnn_rle_to_polygons_host, which needs no
- * GPU.  Exit status 0 on success; on failure the mrcnn_last_error() text goes to stderr and the status code is the exit status.
+ * mrcnn_merge_tiles and mrcnn_unite_tiles write.  --host calls the sequential definitions, mrcnn_rle_to_polygons_host and
+ * mrcnn_polygons_simplify_host, which need no GPU.  Exit status 0 on success; on failure the mrcnn_last_error() text goes to stderr and the status code is the exit status.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -32,15 +33,18 @@ static int trace(int host, const uint32_t* counts, const int64_t* run_offsets, i
 int main(int argc, char** argv)
 {
     const int host = argc > 1 && strcmp(argv[1], "--host") == 0;
-    if (argc != 2 + host) {
-        fprintf(stderr, "usage: %s [--host] <set.txt>\n", argv[0]);
+    const int simplify = argc > 1 + host && strcmp(argv[1 + host], "--tolerance") == 0;
+    const int file = 1 + host + 2 * simplify;
+    if (argc != file + 1) {
+        fprintf(stderr, "usage: %s [--host] [--tolerance T] <set.txt>\n", argv[0]);
         return 64;
     }
-    FILE* f = fopen(argv[1 + host], "r");
-    if (!f) { fprintf(stderr, "cannot read %s\n", argv[1 + host]); return 66; }
+    const double tolerance = simplify ? atof(argv[2 + host]) : 0.0;
+    FILE* f = fopen(argv[file], "r");
+    if (!f) { fprintf(stderr, "cannot read %s\n", argv[file]); return 66; }
     int n_images = 0, slots = 0;
     if (fscanf(f, "%d %d", &n_images, &slots) != 2 || n_images < 0 || slots < 0 || (n_images > 0 && slots > 1000000 / n_images)) {
-        fprintf(stderr, "%s: n_images and slots expected\n", argv[1 + host]);
+        fprintf(stderr, "%s: n_images and slots expected\n", argv[file]);
         return 65;
     }
     const size_t n = (size_t)n_images * (size_t)slots;
@@ -88,7 +92,25 @@ int main(int argc, char** argv)
         fprintf(stderr, "mrcnn_rle_to_polygons%s failed (%d): %s\n", host ? "_host" : "", st, mrcnn_last_error());
         return st;
     }
-    printf("%lld rings, %lld vertices in %d x %d RLEs\n", (long long)rings, (long long)vertices, n_images, slots);
+    if (simplify) {
+        /* the input's vertex count always suffices as the capacity: no size query.  The rings stay in their order, so rle_rings and the
+         * pixel areas still go with them. */
+        int64_t* simple_offsets = (int64_t*)malloc(sizeof(int64_t) * (size_t)(rings + 1));
+        int32_t* simple_xy = (int32_t*)malloc(sizeof(int32_t) * 2 * (size_t)(vertices + 1));
+        int64_t simple_vertices = 0;
+        if (!simple_offsets || !simple_xy) { fprintf(stderr, "out of memory\n"); return 70; }
+        st = host ? mrcnn_polygons_simplify_host(ring_offsets, xy, rings, tolerance, simple_offsets, NULL, simple_xy, NULL, &simple_vertices, vertices)
+                  : mrcnn_polygons_simplify(ring_offsets, xy, rings, tolerance, MRCNN_HOST, simple_offsets, NULL, simple_xy, NULL, &simple_vertices, vertices);
+        if (st != MRCNN_OK) {
+            fprintf(stderr, "mrcnn_polygons_simplify%s failed (%d): %s\n", host ? "_host" : "", st, mrcnn_last_error());
+            return st;
+        }
+        printf("%lld rings, %lld vertices, %lld simplified within %g px, in %d x %d RLEs\n", (long long)rings, (long long)vertices,
+               (long long)simple_vertices, tolerance, n_images, slots);
+        free(xy); free(ring_offsets);
+        xy = simple_xy; ring_offsets = simple_offsets;
+    } else
+        printf("%lld rings, %lld vertices in %d x %d RLEs\n", (long long)rings, (long long)vertices, n_images, slots);
     for (size_t k = 0; k < n; ++k)
         for (int64_t r = rle_rings[k]; r < rle_rings[k + 1]; ++r) {
             printf("RLE %lld ring %lld area %lld:", (long long)k, (long long)(r - rle_rings[k]), (long long)ring_areas[r]);

@@ -919,8 +919,9 @@ MRCNN_API int mrcnn_rle_from_polygons_batch(const double* xy, const int64_t* pol
  * run_offsets -> MRCNN_ERR_SHAPE; an RLE whose runs do not sum to h_b*w_b -> MRCNN_ERR_SHAPE, the message names k and nothing is
  * written; all of these before a device is looked for, except the sums of a set in device memory.  No gfx950 device -> MRCNN_ERR_HIP
  * from the device entry (no CPU fallback).
- * Not here: simplification (Douglas-Peucker and the like), smoothing, sub-pixel contours from the 28x28 probabilities, and nesting the
- * rings into a tree of outlines and their holes — a hole is a ring of negative area and nothing more.  examples/maskrcnn_polygons.c. */
+ * Simplification (Douglas-Peucker) is the next entry's, mrcnn_polygons_simplify, which takes ring_offsets and xy as they are written
+ * here.  Not here: smoothing, sub-pixel contours from the 28x28 probabilities, and nesting the rings into a tree of outlines and their
+ * holes — a hole is a ring of negative area and nothing more.  examples/maskrcnn_polygons.c. */
 #define MRCNN_POLYGON_LDS_CORNERS 1024
 MRCNN_API int mrcnn_rle_to_polygons(const uint32_t* counts, const int64_t* run_offsets, int n_images, int slots, const int32_t* heights,
                                     const int32_t* widths, int memspace, int64_t* rle_rings, int64_t* n_rings, int64_t* n_vertices,
@@ -928,6 +929,54 @@ MRCNN_API int mrcnn_rle_to_polygons(const uint32_t* counts, const int64_t* run_o
 MRCNN_API int mrcnn_rle_to_polygons_host(const uint32_t* counts, const int64_t* run_offsets, int n_images, int slots, const int32_t* heights,
                                          const int32_t* widths, int64_t* rle_rings, int64_t* n_rings, int64_t* n_vertices,
                                          int64_t* ring_offsets, int64_t* ring_areas, int64_t ring_capacity, int32_t* xy, int64_t vertex_capacity);
+
+/* Polygon rings simplified on the GPU: Douglas-Peucker with a tolerance in pixels, exact in integers.  The input is rings in the layout
+ * mrcnn_rle_to_polygons writes — ring r = the vertices [ring_offsets[r], ring_offsets[r+1]) of xy (int32 x then y) — but any integer
+ * rings are legal, not only traced ones: every coordinate in 0..32767, every ring under 2^31 vertices, offsets that start at 0 or above
+ * and do not decrease.  A ring is closed: its last vertex is joined to its first.
+ * Tolerance.  A double, finite, 0 <= tolerance <= 65535.  It becomes one integer once, on the host: E = floor(tolerance * tolerance *
+ *   65536) (the products rounded as doubles).  Nothing after that touches floating point.
+ * The ring rule.  A ring of m vertices v_0 .. v_{m-1}: if m <= 2 it is copied as it is.  Otherwise it has two anchors, which are kept:
+ *   v_0, and v_f, the vertex of largest squared Euclidean distance from v_0, the smallest index on a tie.  The two open chains
+ *   v_0 .. v_f and v_f .. v_m (v_m is v_0 again) are simplified independently by the chain rule.
+ * The chain rule.  A chain with end vertices a and b and at least one vertex strictly between them: every such vertex p has the
+ *   distance c(p) = |(b - a) x (p - a)| = |(bx - ax)*(py - ay) - (by - ay)*(px - ax)|, or, when a and b have equal coordinates (a ring
+ *   may pass twice through a vertex), c(p) = |p - a|^2.  The chosen vertex has the largest c; a tie goes to the smallest position along
+ *   the chain.  It is kept iff c*c*65536 > E*|b - a|^2 (an exact comparison of up to 79 bits), for equal a and b iff c*65536 > E: iff it
+ *   lies farther than the tolerance from the chord.  If it is kept, the chains a .. p and p .. b are handled by the same rule; if not,
+ *   every vertex strictly between a and b is dropped.
+ * What follows: the output ring is a subsequence of the input ring and starts at the same vertex; rings stay in their order, one for
+ *   one, so rle_rings of the tracer still indexes them.  Tolerance 0 returns a traced ring unchanged (horizontal and vertical pieces in
+ *   turn leave no vertex on a chord).  The kept sets are nested: a larger tolerance keeps a subset.  A ring may come out with 2 vertices
+ *   (with 1 if all its vertices are equal).  TOPOLOGY IS NOT PRESERVED: rings may touch or cross themselves and one another afterwards.
+ * Outputs.
+ *   out_ring_offsets (n_rings + 1)          ring r owns the vertices [out_ring_offsets[r], out_ring_offsets[r+1]); ALWAYS written
+ *   *n_vertices_out (host)                  the vertices of all simplified rings; ALWAYS written
+ *   out_areas2 (n_rings, may be NULL)       TWICE the signed shoelace area of each simplified ring, sum(x_i*y_{i+1} - x_{i+1}*y_i): an
+ *                                           integer where the area itself need not be one
+ *   out_xy (2 * vertex_capacity, int32)     the simplified vertices, all rings back to back
+ *   out_src_index (vertex_capacity, may be NULL)   per output vertex its index in the input xy: strictly increasing within a ring
+ * Capacity, the protocol of mrcnn_rle_to_polygons: if *n_vertices_out > vertex_capacity the call returns MRCNN_ERR_SHAPE, the message
+ * names the size needed and none of out_xy, out_areas2 and out_src_index is written (capacity 0 with NULL buffers is the size query;
+ * the input's vertex count always suffices).  memspace holds for ring_offsets, xy and the four output arrays; n_vertices_out is host memory.
+ * mrcnn_polygons_simplify_host is the definition: sequential plain C++ with an explicit stack, no GPU, host pointers.
+ * mrcnn_polygons_simplify equals it bit for bit in every array.  The chains of a ring are independent, so it runs them level by level:
+ * one workgroup owns a ring, every vertex knows its chain, a 64-bit maximum per chain picks the vertex, and the loop ends when no chain
+ * is left — in LDS for a ring of at most MRCNN_SIMPLIFY_LDS_VERTICES vertices, in global scratch above.  Three launches and a prefix
+ * sum, whatever the number of rings and the depth of the recursion; the host reads back one summary (are the rings legal, how large is
+ * the largest) before anything is written and the size needed after the count.
+ * Errors: null pointer (out_xy only with a capacity, xy only with rings), negative n_rings or capacity, a tolerance that is NaN or outside
+ * 0..65535, unknown memspace -> MRCNN_ERR_INVALID; offsets that are negative, decrease or span 2^31 vertices, or a coordinate outside
+ * 0..32767 -> MRCNN_ERR_SHAPE, the message names the ring and nothing is written; all of these before a device is looked for, except
+ * the contents of rings in device memory.  No gfx950 device -> MRCNN_ERR_HIP from the device entry (no CPU fallback).
+ * Not here: topology-preserving simplification, Visvalingam-Whyatt, smoothing.  examples/maskrcnn_polygons.c --tolerance. */
+#define MRCNN_SIMPLIFY_LDS_VERTICES 1024
+MRCNN_API int mrcnn_polygons_simplify(const int64_t* ring_offsets, const int32_t* xy, int64_t n_rings, double tolerance, int memspace,
+                                      int64_t* out_ring_offsets, int64_t* out_areas2, int32_t* out_xy, int64_t* out_src_index,
+                                      int64_t* n_vertices_out, int64_t vertex_capacity);
+MRCNN_API int mrcnn_polygons_simplify_host(const int64_t* ring_offsets, const int32_t* xy, int64_t n_rings, double tolerance,
+                                           int64_t* out_ring_offsets, int64_t* out_areas2, int32_t* out_xy, int64_t* out_src_index,
+                                           int64_t* n_vertices_out, int64_t vertex_capacity);
 
 #ifdef __cplusplus
 }

@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = [
     "mrcnn_rle_decode", "mrcnn_rle_decode_host", "mrcnn_instance_map_rle", "mrcnn_instance_map_rle_host",
     "mrcnn_render_detections_rle", "mrcnn_render_detections_rle_host",
     "mrcnn_rle_to_polygons", "mrcnn_rle_to_polygons_host",
+    "mrcnn_polygons_simplify", "mrcnn_polygons_simplify_host",
 ]
 # declared in include/maskrcnn_hip_test.h (test / measurement entry points of the same library)
 TEST_SYMBOLS = [
@@ -112,6 +113,7 @@ class Tile(C.Structure):            # mrcnn_tile
 MATCH_IOU, MATCH_IOS = 0, 1
 TILES_MAX_CANDIDATES = 8192
 POLYGON_LDS_CORNERS = 1024      # MRCNN_POLYGON_LDS_CORNERS
+SIMPLIFY_LDS_VERTICES = 1024    # MRCNN_SIMPLIFY_LDS_VERTICES
 
 
 class PngSource(C.Structure):       # mrcnn_png_source
@@ -202,6 +204,9 @@ def lib():
     _rings = [vp, i64p, i64p, vp, vp, C.c_int64, vp, C.c_int64]    # rle_rings, n_rings, n_vertices, ring_offsets, ring_areas, capacity, xy, capacity
     L.mrcnn_rle_to_polygons.argtypes = _rles + [vp, vp, C.c_int] + _rings
     L.mrcnn_rle_to_polygons_host.argtypes = _rles + [vp, vp] + _rings
+    _simple = [vp, vp, vp, vp, i64p, C.c_int64]                   # out_ring_offsets, out_areas2, out_xy, out_src_index, n_vertices_out, capacity
+    L.mrcnn_polygons_simplify.argtypes = [vp, vp, C.c_int64, C.c_double, C.c_int] + _simple
+    L.mrcnn_polygons_simplify_host.argtypes = [vp, vp, C.c_int64, C.c_double] + _simple
     L.mrcnn_rle_to_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_from_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_iou.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int64]

@@ -66,7 +66,8 @@ def rle_encode(plane: np.ndarray) -> Dict:
 
 
 def coco_results(image_ids: Sequence, det_src, rles, sizes, class_to_category: Optional[Dict[int, int]] = None,
-                 score_threshold: float = 0.0, segmentation: str = "rle", min_area: int = 1, polygons=None) -> List[Dict]:
+                 score_threshold: float = 0.0, segmentation: str = "rle", min_area: int = 1, polygons=None,
+                 tolerance: Optional[float] = None) -> List[Dict]:
     """The COCO results list (``segm`` results, which carry ``bbox`` too) of a batch: image_ids (B), det_src (B, rows, 6) — boxes
     normalized in each SOURCE image, as masks_rle_source returns them —, rles[b][i], sizes = [(h_b, w_b)].  One record per row with
     score > score_threshold: ``bbox`` is the detection's box in source pixels (Matterport's denorm_boxes of the row — the box the mask
@@ -77,12 +78,18 @@ def coco_results(image_ids: Sequence, det_src, rles, sizes, class_to_category: O
     pixel-corner coordinates.  COCO polygons cannot carry holes, so this mode emits only the OUTLINES (the rings of positive area)
     of at least ``min_area`` pixels and DROPS the hole rings: a mask with a hole comes out filled, and a mask whose outlines are all
     smaller than min_area has an empty list.  ``polygons`` = what detection.rle_to_polygons or rle_to_polygons_host returned for
-    ``rles`` (rings, areas); None traces them here with detection.rle_to_polygons, on the GPU."""
+    ``rles`` (rings, areas); None traces them here with detection.rle_to_polygons, on the GPU.  ``tolerance`` (pixels) simplifies the
+    rings (detection.simplify_polygons, on the GPU: while tracing here, or the ``polygons`` given; rings that are simplified already,
+    such as rle_to_polygons_host(..., tolerance=) returns, are passed without it).  A ring is still chosen by its ORIGINAL area, the
+    pixels it encloses; its simplified vertices are written, and a ring left with fewer than 3 vertices is dropped."""
     if segmentation not in ("rle", "polygon"):
         raise ValueError(f"coco_results: segmentation {segmentation!r} is neither 'rle' nor 'polygon'")
     if segmentation == "polygon" and polygons is None:
         from .detection import rle_to_polygons
-        polygons = rle_to_polygons([[{"size": r["size"], "counts": _counts(r)} for r in row] for row in rles], sizes)
+        polygons = rle_to_polygons([[{"size": r["size"], "counts": _counts(r)} for r in row] for row in rles], sizes, tolerance=tolerance)
+    elif segmentation == "polygon" and tolerance is not None:
+        from .detection import simplify_polygons
+        polygons = simplify_polygons(polygons, tolerance)
     det = np.asarray(det_src, dtype=np.float32)
     out = []
     for b, image_id in enumerate(image_ids):
@@ -98,7 +105,8 @@ def coco_results(image_ids: Sequence, det_src, rles, sizes, class_to_category: O
             rle = rles[b][i]
             counts = rle["counts"]
             if segmentation == "polygon":
-                seg = [[float(v) for v in ring.reshape(-1)] for ring, area in zip(polygons[0][b][i], polygons[1][b][i]) if area >= max(1, min_area)]
+                seg = [[float(v) for v in ring.reshape(-1)] for ring, area in zip(polygons[0][b][i], polygons[1][b][i])
+                       if area >= max(1, min_area) and len(ring) >= 3]
             else:
                 seg = {"size": [int(rle["size"][0]), int(rle["size"][1])], "counts": counts if isinstance(counts, str) else rle_to_string(counts)}
             out.append({"image_id": image_id.item() if isinstance(image_id, np.generic) else image_id,

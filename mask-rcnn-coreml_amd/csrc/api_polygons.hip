@@ -1,9 +1,12 @@
 // api_polygons.hip — the C ABI of include/maskrcnn_hip.h, run-length masks to polygon rings: the host definition (polygons_host.cpp
-// behind it) and the device entry (kernels_polygons.hip).  Every argument error is answered before a device is looked for.
+// behind it) and the device entry (kernels_polygons.hip); and the rings simplified: simplify_host.cpp and kernels_simplify.hip.  Every
+// argument error is answered before a device is looked for.
 #include <string.h>
 
 #include "api_util.h"
 #include "polygons_host.h"
+#include "simplify_host.h"
+#include "simplify_rule.h"
 
 using namespace mrcnn;
 
@@ -155,6 +158,113 @@ extern "C" int mrcnn_rle_to_polygons(const uint32_t* counts, const int64_t* run_
             HIP_CHECK(hipMemcpy(ring_offsets, d_offsets, (size_t)(rings + 1) * 8, hipMemcpyDeviceToHost));
             if (ring_areas) HIP_CHECK(hipMemcpy(ring_areas, d_areas, (size_t)rings * 8, hipMemcpyDeviceToHost));
             HIP_CHECK(hipMemcpy(xy, d_xy, (size_t)corners * 8, hipMemcpyDeviceToHost));
+        }
+    });
+}
+
+extern "C" int mrcnn_polygons_simplify_host(const int64_t* ring_offsets, const int32_t* xy, int64_t n_rings, double tolerance, int64_t* out_ring_offsets,
+                                            int64_t* out_areas2, int32_t* out_xy, int64_t* out_src_index, int64_t* n_vertices_out,
+                                            int64_t vertex_capacity)
+{
+    return guarded([&] {
+        const char* who = "polygons_simplify_host";
+        std::string err;
+        answer(simplify::check_arguments(ring_offsets, xy, n_rings, tolerance, out_ring_offsets, out_xy, n_vertices_out, vertex_capacity, who, &err), err);
+        int64_t most = 0;
+        answer(simplify::check_offsets(ring_offsets, n_rings, who, &err, &most), err);
+        answer(simplify::check_coordinates(ring_offsets, xy, n_rings, who, &err), err);
+        simplify::Rings r;
+        simplify::simplify_host(ring_offsets, xy, n_rings, simp_tolerance(tolerance), &r);
+        const int64_t vertices = (int64_t)(r.xy.size() / 2);
+        memcpy(out_ring_offsets, r.ring_offsets.data(), r.ring_offsets.size() * sizeof(int64_t));
+        *n_vertices_out = vertices;
+        answer(simplify::check_capacity(vertices, vertex_capacity, who, &err), err);
+        if (out_areas2 && n_rings) memcpy(out_areas2, r.areas2.data(), (size_t)n_rings * sizeof(int64_t));
+        if (vertices) memcpy(out_xy, r.xy.data(), r.xy.size() * sizeof(int32_t));
+        if (out_src_index && vertices) memcpy(out_src_index, r.src_index.data(), (size_t)vertices * sizeof(int64_t));
+    });
+}
+
+extern "C" int mrcnn_polygons_simplify(const int64_t* ring_offsets, const int32_t* xy, int64_t n_rings, double tolerance, int memspace,
+                                       int64_t* out_ring_offsets, int64_t* out_areas2, int32_t* out_xy, int64_t* out_src_index,
+                                       int64_t* n_vertices_out, int64_t vertex_capacity)
+{
+    return guarded([&] {
+        const char* who = "polygons_simplify";
+        std::string err;
+        answer(simplify::check_arguments(ring_offsets, xy, n_rings, tolerance, out_ring_offsets, out_xy, n_vertices_out, vertex_capacity, who, &err), err);
+        MRCNN_REQUIRE(memspace == MRCNN_HOST || memspace == MRCNN_DEVICE, MRCNN_ERR_INVALID, "%s: unknown memspace %d", who, memspace);
+        MRCNN_REQUIRE(n_rings < (1LL << 31), MRCNN_ERR_SHAPE, "%s: %lld rings: too many for one call", who, (long long)n_rings);
+        const bool dev = memspace == MRCNN_DEVICE;
+        const size_t n = (size_t)n_rings;
+        int64_t most = 0, v_in = 0;
+        if (!dev) {                                              // rings in host memory: a bad one needs no device to be named
+            answer(simplify::check_offsets(ring_offsets, n_rings, who, &err, &most), err);
+            answer(simplify::check_coordinates(ring_offsets, xy, n_rings, who, &err), err);
+            v_in = ring_offsets[n];
+        }
+        const uint64_t E = simp_tolerance(tolerance);
+        require_gpu();
+        const int64_t zero = 0;
+        if (n == 0) {
+            HIP_CHECK(hipMemcpy(out_ring_offsets, &zero, sizeof zero, dev ? hipMemcpyHostToDevice : hipMemcpyHostToHost));
+            *n_vertices_out = 0;
+            return;
+        }
+        Stream st;
+        hipStream_t s = st.s;
+        DevBuf t_off, t_xy, t_out_off, t_areas, t_out_xy, t_src;
+        Carver sc, wc;
+        Drain drain{s};                                          // (declared behind the buffers: the stream drains before they are freed)
+        SimplifyRings in{reinterpret_cast<const long long*>(ring_offsets), xy, (long long)n_rings};
+        if (!dev) {                                              // (all of xy up to the last ring's end: the offsets hold as they are)
+            t_off.alloc((n + 1) * 8); t_xy.alloc((size_t)v_in * 8);
+            HIP_CHECK(hipMemcpy(t_off.p, ring_offsets, (n + 1) * 8, hipMemcpyHostToDevice));
+            if (v_in) HIP_CHECK(hipMemcpy(t_xy.p, xy, (size_t)v_in * 8, hipMemcpyHostToDevice));
+            in.ring_offsets = t_off.as<long long>(); in.xy = t_xy.as<int32_t>();
+        }
+        const auto s_sum = sc.take<unsigned long long>(4);
+        const auto s_cnt = sc.take<uint32_t>(n);
+        sc.alloc();
+        if (dev) {                                               // the one read-back before anything is written: are the rings legal, how large are they
+            simplify_check_forward(s, in, sc[s_sum]);
+            unsigned long long sum[4] = {0, 0, 0, 0};
+            HIP_CHECK(hipMemcpyAsync(sum, sc[s_sum], sizeof sum, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            if (sum[0] != ~0ull) answer(simplify::bad_offsets((int64_t)sum[0], who, &err), err);
+            if (sum[1] != ~0ull) answer(simplify::bad_coordinate((int64_t)sum[1], who, &err), err);
+            most = (int64_t)sum[2]; v_in = (int64_t)sum[3];
+        }
+        const bool big = most > SIMPLIFY_LDS_VERTICES;
+        const size_t v = (size_t)v_in;
+        const auto w_keep = wc.take<uint8_t>(v);
+        const auto w_chain = wc.take<unsigned long long>(big ? v : 0), w_sa = wc.take<unsigned long long>(big ? v : 0);
+        const auto w_sb = wc.take<unsigned long long>(big ? v : 0);
+        wc.alloc();
+        const SimplifyWork w{wc[w_keep], sc[s_cnt], big ? wc[w_chain] : nullptr, big ? wc[w_sa] : nullptr, big ? wc[w_sb] : nullptr};
+        long long* d_out_off = reinterpret_cast<long long*>(out_ring_offsets);
+        if (!dev) { t_out_off.alloc((n + 1) * 8); d_out_off = t_out_off.as<long long>(); }
+        simplify_count_forward(s, in, E, w, d_out_off);
+        long long needed = 0;                                    // the second read-back: the size the capacity is checked against
+        HIP_CHECK(hipMemcpyAsync(&needed, d_out_off + n, sizeof needed, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (!dev) HIP_CHECK(hipMemcpy(out_ring_offsets, d_out_off, (n + 1) * 8, hipMemcpyDeviceToHost));
+        *n_vertices_out = needed;
+        answer(simplify::check_capacity(needed, vertex_capacity, who, &err), err);
+        long long* d_areas = reinterpret_cast<long long*>(out_areas2);
+        long long* d_src = reinterpret_cast<long long*>(out_src_index);
+        int32_t* d_xy = out_xy;
+        if (!dev) {
+            if (out_areas2) { t_areas.alloc(n * 8); d_areas = t_areas.as<long long>(); }
+            if (out_src_index) { t_src.alloc((size_t)needed * 8); d_src = t_src.as<long long>(); }
+            t_out_xy.alloc((size_t)needed * 8); d_xy = t_out_xy.as<int32_t>();
+        }
+        simplify_write_forward(s, in, w, d_out_off, needed, d_areas, d_xy, d_src);
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (!dev) {
+            if (out_areas2) HIP_CHECK(hipMemcpy(out_areas2, d_areas, n * 8, hipMemcpyDeviceToHost));
+            if (needed) HIP_CHECK(hipMemcpy(out_xy, d_xy, (size_t)needed * 8, hipMemcpyDeviceToHost));
+            if (out_src_index && needed) HIP_CHECK(hipMemcpy(out_src_index, d_src, (size_t)needed * 8, hipMemcpyDeviceToHost));
         }
     });
 }

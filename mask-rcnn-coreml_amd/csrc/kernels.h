@@ -601,6 +601,28 @@ void polygons_trace_forward(hipStream_t s, const PolygonSet& set, const PolygonW
 void polygons_write_forward(hipStream_t s, const PolygonWork& w, long long n_corners, long long n_rings, long long* ring_offsets, long long* ring_areas,
                             int32_t* xy);
 
+// ================================================================================================
+// Polygon rings simplified (mrcnn_polygons_simplify; kernels_simplify.hip, the rule is simplify_rule.h).  All tables are device arrays.
+// One workgroup owns a ring and runs its chains level by level: in LDS for a ring of at most SIMPLIFY_LDS_VERTICES vertices, in its own
+// carve of the global scratch above.  Three launches and one scan, whatever the number of rings and the depth of the recursion.
+// ================================================================================================
+constexpr int SIMPLIFY_LDS_VERTICES = MRCNN_SIMPLIFY_LDS_VERTICES;
+struct SimplifyRings { const long long* ring_offsets; const int32_t* xy; long long n_rings; };
+// summary[0..3] = the lowest ring whose offsets are negative, decrease or span 2^31 vertices (~0: none), the lowest ring with a
+// coordinate outside 0..32767 (~0: none; not looked for when summary[0] names a ring), the most vertices of one ring, ring_offsets[n_rings].
+void simplify_check_forward(hipStream_t s, const SimplifyRings& in, unsigned long long* summary);
+struct SimplifyWork {
+    uint8_t* keep;                    // per input vertex: it stays
+    uint32_t* count;                  // n_rings: the vertices a ring keeps
+    // rings above SIMPLIFY_LDS_VERTICES only, per input vertex (nullptr when there is none): the chain a vertex is in, and the two sides of the slots
+    unsigned long long *chain, *slot_a, *slot_b;
+};
+// keep and count by the rule, then out_ring_offsets (n_rings + 1) = the exclusive prefix of count; its last entry is the size needed
+void simplify_count_forward(hipStream_t s, const SimplifyRings& in, unsigned long long E, const SimplifyWork& w, long long* out_ring_offsets);
+// the kept vertices at their places: out_xy, out_src_index (may be nullptr) and out_areas2 (may be nullptr); n_out = out_ring_offsets[n_rings]
+void simplify_write_forward(hipStream_t s, const SimplifyRings& in, const SimplifyWork& w, const long long* out_ring_offsets, long long n_out,
+                            long long* out_areas2, int32_t* out_xy, long long* out_src_index);
+
 // COCOeval.accumulate (mrcnn_coco_accumulate; kernels_coco_acc.hip).  -ffp-contract=off.  All tables are device arrays.
 // A chunk is COCO_ACC_CHUNK consecutive entries of one category's segment [seg0, seg0 + seg_len) of the flat detection list, starting
 // `at` entries into it (a multiple of the chunk); the chunks of all segments, in order, are the grid of the sort kernels.

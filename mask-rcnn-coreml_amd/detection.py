@@ -419,7 +419,78 @@ def render_detections_rle_host(images, det_src, rles, min_score: float = 0.7, al
 
 
 # ---- polygons out (mrcnn_rle_to_polygons) -------------------------------------------------------------------------------------------
-def _rle_to_polygons(host_definition, rles, sizes, device, flat):
+def _simplify_flat(host_definition, space, ring_offsets, xy, tolerance):
+    """mrcnn_polygons_simplify(_host) on ring_offsets (R + 1) and xy (V, 2) of ``space`` -> (ring_offsets, areas2, xy (V', 2), src_index,
+    V').  One call: the input's vertex count always suffices as the capacity."""
+    R, V = int(ring_offsets.shape[0]) - 1, int(xy.shape[0])
+    if R < 0 or (V and tuple(xy.shape) != (V, 2)):
+        raise ValueError("simplify_polygons: ring_offsets needs an entry and xy the shape (V, 2)")
+    ptr = space.ptr
+    src_xy = xy if V else space.new(2, np.int32, zero=True)      # (an empty tensor has no address)
+    out_offsets, areas2 = space.new(R + 1, np.int64, zero=True), space.new(max(1, R), np.int64)
+    out_xy, src_index = space.new(max(2, 2 * V), np.int32), space.new(max(1, V), np.int64)
+    total = C.c_int64(0)
+    head = (ptr(ring_offsets), ptr(src_xy), R, C.c_double(float(tolerance))) + (() if host_definition else (space.code,))
+    entry = _lib.lib().mrcnn_polygons_simplify_host if host_definition else _lib.lib().mrcnn_polygons_simplify
+    _lib.check(entry(*head, ptr(out_offsets), ptr(areas2), ptr(out_xy), ptr(src_index), C.byref(total), V))
+    n = total.value
+    return out_offsets, areas2[:R], out_xy[:2 * n].reshape(n, 2), src_index[:n], n
+
+
+def _simplify_polygons(host_definition, polygons, tolerance, device, flat):
+    nested = not isinstance(polygons, dict)
+    if nested:                                                   # (rings, areas): rings[b][i] = the list of the (m, 2) arrays of RLE i of image b
+        rings, areas = polygons
+        every = [np.asarray(r, dtype=np.int32).reshape(-1, 2) for row in rings for rle in row for r in rle]
+        per_rle = [len(rle) for row in rings for rle in row]
+        P = {"rle_rings": np.concatenate(([0], np.cumsum(per_rle))).astype(np.int64),
+             "ring_offsets": np.concatenate(([0], np.cumsum([len(r) for r in every]))).astype(np.int64),
+             "ring_areas": np.concatenate([np.asarray(a, dtype=np.int64).reshape(-1) for row in areas for a in row] + [np.zeros(0, np.int64)]),
+             "xy": np.concatenate(every + [np.zeros((0, 2), np.int32)])}
+    else:
+        P = dict(polygons)
+    on_device = hasattr(P["xy"], "is_cuda")
+    if device is None and on_device and not host_definition:
+        device = P["xy"].device                                  # tensors: simplified where they lie, tensors out
+    space = Space(device)
+
+    def here(a, dtype):
+        if a is None:
+            return None
+        if space.on_host:
+            return np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "is_cuda") else a, dtype=dtype)
+        import torch
+        t = a if hasattr(a, "is_cuda") else torch.from_numpy(np.ascontiguousarray(a, dtype=dtype))
+        return t.to(device=space.device, dtype=getattr(torch, np.dtype(dtype).name)).contiguous()
+    offsets, xy = here(P["ring_offsets"], np.int64), here(P["xy"], np.int32)
+    out_offsets, areas2, out_xy, src_index, n = _simplify_flat(host_definition, space, offsets, xy, tolerance)
+    out = {"rle_rings": here(P.get("rle_rings"), np.int64), "ring_offsets": out_offsets, "ring_areas": here(P.get("ring_areas"), np.int64),
+           "areas2": areas2, "xy": out_xy, "src_index": src_index, "n_rings": int(offsets.shape[0]) - 1, "n_vertices": n}
+    if flat or not nested:
+        return out
+    ro, sxy = (out_offsets, out_xy) if space.on_host else (out_offsets.cpu().numpy(), out_xy.cpu().numpy())
+    at = iter(range(len(every)))
+    return [[[sxy[ro[r]:ro[r + 1]] for r in (next(at) for _ in rle)] for rle in row] for row in rings], areas
+
+
+def simplify_polygons(polygons, tolerance, device=None, flat: bool = False):
+    """Polygon rings simplified on the GPU by Douglas-Peucker with ``tolerance`` in pixels (``mrcnn_polygons_simplify``; the rule is
+    defined in include/maskrcnn_hip.h: exact in integers, a dropped vertex lies within the tolerance of the chord that replaces it,
+    topology is not preserved).  ``polygons`` is what rle_to_polygons returned: the flat dictionary (flat=True) — its ring_offsets and
+    xy, numpy arrays or CUDA tensors, which are simplified where they lie — or the nested (rings, areas) pair.  The flat form comes
+    back flat: rle_rings and ring_areas as they were (the ORIGINAL pixel areas), ring_offsets and xy simplified, and beside them areas2
+    (twice the signed area of each simplified ring), src_index (per vertex, its index in the input xy), n_rings, n_vertices.  The nested
+    form comes back nested, (rings, areas) with the original areas, unless flat=True.  Rings stay in their order, one for one; a ring
+    may come out with two vertices."""
+    return _simplify_polygons(False, polygons, tolerance, device, flat)
+
+
+def simplify_polygons_host(polygons, tolerance, flat: bool = False):
+    """The definition of simplify_polygons: the sequential host code (``mrcnn_polygons_simplify_host``), no GPU; numpy out."""
+    return _simplify_polygons(True, polygons, tolerance, None, flat)
+
+
+def _rle_to_polygons(host_definition, rles, sizes, device, flat, tolerance=None):
     name = "rle_to_polygons_host" if host_definition else "rle_to_polygons"
     if device is None and not host_definition and isinstance(rles, tuple) and len(rles) == 2 and hasattr(rles[0], "is_cuda"):
         device = rles[0].device                                  # a pair of CUDA tensors: traced where they lie, tensors out
@@ -441,8 +512,12 @@ def _rle_to_polygons(host_definition, rles, sizes, device, flat):
     _lib.check(st)
     R, V = totals[0].value, totals[1].value
     ring_offsets, ring_areas, xy = ring_offsets[:R + 1], ring_areas[:R], xy[:2 * V].reshape(V, 2)
+    extra = {}
+    if tolerance is not None:                                    # the same memory space: device-resident rings never leave the device
+        ring_offsets, areas2, xy, src_index, V = _simplify_flat(host_definition, space, ring_offsets, xy, tolerance)
+        extra = {"areas2": areas2, "src_index": src_index}
     if flat:
-        return {"rle_rings": rle_rings, "ring_offsets": ring_offsets, "ring_areas": ring_areas, "xy": xy, "n_rings": R, "n_vertices": V}
+        return {"rle_rings": rle_rings, "ring_offsets": ring_offsets, "ring_areas": ring_areas, "xy": xy, "n_rings": R, "n_vertices": V, **extra}
     if not space.on_host:
         rle_rings, ring_offsets, ring_areas, xy = (a.cpu().numpy() for a in (rle_rings, ring_offsets, ring_areas, xy))
     rings = [[[xy[ring_offsets[r]:ring_offsets[r + 1]] for r in range(rle_rings[b * slots + i], rle_rings[b * slots + i + 1])]
@@ -451,7 +526,7 @@ def _rle_to_polygons(host_definition, rles, sizes, device, flat):
     return rings, areas
 
 
-def rle_to_polygons(rles, sizes=None, device=None, flat: bool = False):
+def rle_to_polygons(rles, sizes=None, device=None, flat: bool = False, tolerance=None):
     """The boundary of every mask of an RLE set as closed rings of pixel corners, traced from the runs on the GPU
     (``mrcnn_rle_to_polygons``; the geometry is defined in include/maskrcnn_hip.h).  ``rles`` as rle_decode_planes takes them: what
     merge_tiles, unite_tiles or masks_rle_source returned, or a (counts, run_offsets) pair with ``sizes``; a pair of CUDA tensors is
@@ -459,10 +534,13 @@ def rle_to_polygons(rles, sizes=None, device=None, flat: bool = False):
     per vertex, every ring, outlines and holes alike, ordered by their start vertex — and areas[b][i] their signed areas as int64:
     positive for an outline, negative for a hole.  flat=True returns the library's own arrays instead (rle_rings, ring_offsets,
     ring_areas, xy as (V, 2), n_rings, n_vertices): numpy arrays, or tensors that stay on the device when ``device`` is given or the
-    pair is CUDA tensors."""
-    return _rle_to_polygons(False, rles, sizes, device, flat)
+    pair is CUDA tensors.  ``tolerance`` (pixels; None: the traced rings as they are) hands the rings on to simplify_polygons in the
+    same memory space: the rings come back simplified with the ORIGINAL pixel areas beside them, and the flat form gains areas2 and
+    src_index."""
+    return _rle_to_polygons(False, rles, sizes, device, flat, tolerance)
 
 
-def rle_to_polygons_host(rles, sizes=None, flat: bool = False):
-    """The definition of rle_to_polygons: the sequential host code (``mrcnn_rle_to_polygons_host``), no GPU; numpy out."""
-    return _rle_to_polygons(True, rles, sizes, None, flat)
+def rle_to_polygons_host(rles, sizes=None, flat: bool = False, tolerance=None):
+    """The definition of rle_to_polygons: the sequential host code (``mrcnn_rle_to_polygons_host``, and ``mrcnn_polygons_simplify_host``
+    for a tolerance), no GPU; numpy out."""
+    return _rle_to_polygons(True, rles, sizes, None, flat, tolerance)
