@@ -126,14 +126,20 @@ MRCNN_API int mrcnn_bottleneck_first_nhwc(const float* x, int batch, int h, int 
 /* A chained pair of the split modes on caller (host) data (dtype MRCNN_F32S | MRCNN_F32X3): P = a bottleneck's `branch2c`, t2 (B,H,W,C) x w3 (4C,C) with
  * folded BatchNorm s3 / h3, plus EITHER the residual x (B,H,W,4C) OR (x == NULL) the shortcut convolution ws (4C,cs) with s_s / h_s over xs
  * (B, H*ss, W*ss, cs) sampled with stride ss, then ReLU -> y (B,H,W,4C); Q = the next block's `branch2a`, y x w1 (C,4C) with s1 / h1, ReLU -> t1 (B,H,W,C).
- * chained = 1: ONE launch (kernels_conv_chain.hip; needs C in {64,128}) at whatever grid size; 0: the two launches of the convolution family.
- * in_place = 1: y is written over the residual (the engine's form).  Both outputs must agree bit for bit (tests/test_gpu_conv_chain.py); the
- * watchdog word of the call: mrcnn_test_last_range_flag.
+ * chained = 1: ONE launch (kernels_conv_chain.hip; needs C in {64,128,256}) at whatever grid size; 0: the two launches of the convolution family.
+ * C = 256 runs the identity form only (the residual x): with the shortcut's operands and chained = 1 it fails with MRCNN_ERR_UNSUPPORTED.
+ * in_place = 1: y is written over the residual (the engine's form).  Both outputs must agree bit for bit (tests/test_gpu_conv_chain.py,
+ * tests/test_gpu_conv_chain_c256.py); the watchdog word of the call: mrcnn_test_last_range_flag.
  * "conv_chain" 0|1|2 of mrcnn_debug_set: the engine's C2 / C3 pairs as two launches | C2's pairs chained where the grid fills the chip (default; C3's measured
- * slower and stay two launches) | every pair chained at every grid size (bit-identical, all three). */
+ * slower and stay two launches) | every pair chained at every grid size (bit-identical, all three).
+ * "conv_chain4" 0|1|2: the same for C4's identity pairs (C = 256), a knob of their own. */
 MRCNN_API int mrcnn_conv_chain_nhwc(const float* t2, int batch, int h, int w, int cmid, const float* w3, const float* s3, const float* h3, const float* x,
                                     const float* xs, int cs, int ss, const float* ws, const float* s_s, const float* h_s,
                                     const float* w1, const float* s1, const float* h1, int dtype, int chained, int in_place, float* y, float* t1);
+
+/* The stream image of one filter of a chainable C = 256 pair, as the engine packs it when a model is loaded (csrc/conv_pack.h; needs no GPU):
+ * w (4*cmid, cmid) with q = 0 (P, `branch2c`) or (cmid, 4*cmid) with q = 1 (Q, `branch2a`), cmid = 256; image: 4*cmid*cmid fp16 values. */
+MRCNN_API int mrcnn_test_chain_stream_image(const float* w, int cmid, int q, uint16_t* image);
 
 /* The consecutive identity blocks of a C = 256 stage (C4's 22 in ResNet-101) on caller data: x (B,H,W,1024), stacked operands w1 (n,256,1024),
  * w2 (n,256,3,3,256), w3 (n,1024,256), bn = {s1,h1,s2,h2: (n,256); s3,h3: (n,1024)}.  form 1: ONE launch in which a tile's block l waits for its

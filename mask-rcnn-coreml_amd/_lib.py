@@ -56,7 +56,7 @@ TEST_SYMBOLS = [
     "mrcnn_bench_conv", "mrcnn_bench_conv_dtype", "mrcnn_model_conv_profile_enable", "mrcnn_model_conv_profile_get",
     "mrcnn_model_conv_profile_shapes", "mrcnn_conv2d_nhwc", "mrcnn_debug_set", "mrcnn_bottleneck_nhwc", "mrcnn_bench_mfma_probe", "mrcnn_model_conv_profile_group", "mrcnn_bottleneck_first_nhwc", "mrcnn_bottleneck_stage_nhwc", "mrcnn_model_conv_profile_bytes",
     "mrcnn_jpeg_last_stage_ms", "mrcnn_jpeg_coefficients", "mrcnn_test_last_range_flag", "mrcnn_classifier_rows", "mrcnn_test_roi_align_nhwc_batch", "mrcnn_conv_chain_nhwc",
-    "mrcnn_test_conv_form_nhwc",
+    "mrcnn_test_conv_form_nhwc", "mrcnn_test_chain_stream_image",
 ]
 
 
@@ -261,6 +261,7 @@ def lib():
     L.mrcnn_bottleneck_nhwc.argtypes = [vp] + [C.c_int] * 4 + [vp] * 9 + [C.c_int, C.c_int, vp, vp]
     L.mrcnn_test_last_range_flag.argtypes = [ip]
     L.mrcnn_conv_chain_nhwc.argtypes = [vp] + [C.c_int] * 4 + [vp] * 5 + [C.c_int, C.c_int] + [vp] * 6 + [C.c_int] * 3 + [vp, vp]
+    L.mrcnn_test_chain_stream_image.argtypes = [vp, C.c_int, C.c_int, vp]
     L.mrcnn_classifier_rows.argtypes = [vp, C.c_int64, vp, C.c_int, C.c_int64, vp, vp]
     L.mrcnn_model_check_range.argtypes = [vp, ip]
     L.mrcnn_model_calibrate_split.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]

@@ -454,6 +454,19 @@ extern "C" int mrcnn_conv_chain_nhwc(const float* t2, int batch, int h, int w, i
             upload_f32(dxs, xs, (size_t)batch * (h * ss) * (w * ss) * cs);
             upload_f16(dws, ws, (size_t)C4 * cs); upload_f32(dss, s_s, C4); upload_f32(dhs, h_s, C4);
         }
+        // C = 256: both filters also as stream images, packed by the engine's own routine (csrc/conv_pack.h)
+        DevBuf dw3s, dw1s;
+        if (C == 256) {
+            auto stream = [&](DevBuf& d, const float* src, bool q) {
+                std::vector<_Float16> hw((size_t)C4 * C);
+                for (size_t i = 0; i < hw.size(); ++i) hw[i] = (_Float16)src[i];
+                const std::vector<_Float16> img = pack_chain_stream(hw.data(), C, q);
+                d.alloc(img.size() * 2);
+                HIP_CHECK(hipMemcpy(d.p, img.data(), img.size() * 2, hipMemcpyHostToDevice));
+            };
+            stream(dw3s, w3, false);
+            stream(dw1s, w1, true);
+        }
         dy.alloc(npix * C4 * 4); dt1.alloc(npix * C * 4);
         HIP_CHECK(hipMemset(dy.p, 0xff, npix * C4 * 4));
         HIP_CHECK(hipMemset(dt1.p, 0xff, npix * C * 4));
@@ -466,6 +479,7 @@ extern "C" int mrcnn_conv_chain_nhwc(const float* t2, int batch, int h, int w, i
         ConvDesc dP = desc(dt2.p, h, w, C, dw3.p, 1, ds3.as<float>(), dh3.as<float>(), yout, C4, ACT_RELU);
         set_dense_residual(dP, dx.p);
         ConvDesc dQ = desc(yout, h, w, C4, dw1.p, 1, ds1.as<float>(), dh1.as<float>(), dt1.p, C, ACT_RELU);
+        dP.wgt_stream = dw3s.p; dQ.wgt_stream = dw1s.p;
         ConvDesc dS;
         if (xs) dS = desc(dxs.p, h * ss, w * ss, cs, dws.p, ss, dss.as<float>(), dhs.as<float>(), dx.p, C4, ACT_NONE);
         MRCNN_REQUIRE(!xs || (dS.OH == h && dS.OW == w), MRCNN_ERR_SHAPE, "conv_chain_nhwc: the shortcut's output is not %d x %d", h, w);
@@ -475,7 +489,7 @@ extern "C" int mrcnn_conv_chain_nhwc(const float* t2, int batch, int h, int w, i
             std::vector<std::pair<int*, int>> saved;
             ScopedKnob(const char* key, int v) { const auto r = knob_table().by_key.equal_range(key); for (auto it = r.first; it != r.second; ++it) { saved.emplace_back(it->second, *it->second); *it->second = v; } }
             ~ScopedKnob() { for (auto& kv : saved) *kv.first = kv.second; }
-        } knob_scope("conv_chain", chained ? 3 : 0);
+        } knob_scope("conv_chain", chained ? 3 : 0), knob_scope4("conv_chain4", chained ? 2 : 0);          // (C = 256 has its own knob)
         Stream st;
         ScopedConvScratch scratch(true);
         ScopedRangeFlag range(st.s, true);
@@ -484,6 +498,18 @@ extern "C" int mrcnn_conv_chain_nhwc(const float* t2, int batch, int h, int w, i
         range.keep();
         HIP_CHECK(hipMemcpy(y, yout, npix * C4 * 4, hipMemcpyDeviceToHost));
         HIP_CHECK(hipMemcpy(t1, dt1.p, npix * C * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+// The stream image of one filter of a chainable C = 256 pair, as the engine and mrcnn_conv_chain_nhwc pack it (csrc/conv_pack.h; host only).
+extern "C" int mrcnn_test_chain_stream_image(const float* w, int cmid, int q, uint16_t* image)
+{
+    return guarded([&] {
+        MRCNN_REQUIRE(w && image && cmid == 256, MRCNN_ERR_INVALID, "bad chain_stream_image argument");
+        std::vector<_Float16> hw((size_t)4 * cmid * cmid);
+        for (size_t i = 0; i < hw.size(); ++i) hw[i] = (_Float16)w[i];
+        const std::vector<_Float16> img = pack_chain_stream(hw.data(), cmid, q != 0);
+        memcpy(image, img.data(), img.size() * 2);
     });
 }
 

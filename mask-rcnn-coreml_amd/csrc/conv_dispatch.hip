@@ -12,7 +12,7 @@ namespace mrcnn {
 
 void conv_mfma_launch(hipStream_t s, const ConvArgs& a, int mode, int bn, bool wide_waves);   // kernels_conv.hip: 0 fp16, 1 exact fp32, 2 / 3 split parts
 void conv_pp_launch(hipStream_t s, const ConvArgs& a, int mode);   // kernels_conv_pp.hip: 0 fp16, 2 / 3 split parts
-void conv_chain_launch(hipStream_t s, const ConvArgs& p, const ConvArgs& q, int parts, bool wlds, int n_cus);   // kernels_conv_chain.hip: split parts 2 / 3
+void conv_chain_launch(hipStream_t s, const ConvArgs& p, const ConvArgs& q, int parts, bool wlds, int n_cus, const void* p_stream, const void* q_stream);   // kernels_conv_chain.hip: split parts 2 / 3
 
 // ---- what a layer description says about its mode and geometry --------------------------------------------------------------
 static inline int conv_wdtype(const ConvDesc& d) { return d.wdtype < 0 ? d.dtype : d.wdtype; }
@@ -169,6 +169,8 @@ bool conv_halo_enabled() { return g_halo != 0; }
 // Split modes: a bottleneck's branch2c and the NEXT block's branch2a as one launch (kernels_conv_chain.hip; bit-identical to the two launches):
 // 0 never, 1 by policy (conv_forward_chain), 2 at every grid size (tests), 3 as 2 with the entry block's shortcut riding at every grid size too (mrcnn_conv_chain_nhwc)
 static int& g_chain = knob("conv_chain", "MRCNN_CHAIN", 1);
+// ... and the same for C = 256 (C4's identity pairs: the ring form of kernels_conv_chain.hip): 0 never, 1 by policy, 2 at every grid size
+static int& g_chain4 = knob("conv_chain4", "MRCNN_CHAIN4", 1);
 static int& g_tn4 = knob("conv_tn4", nullptr, -1);       // split modes, 128x128 tile as 4 waves of 32x128: -1 by policy (conv_forward), 0 never, 1 always (tests)
 
 // The 256 x 256 ping-pong kernel's policy.
@@ -445,13 +447,15 @@ bool conv_chain_fusable(const ConvDesc& dP, const ConvDesc& dQ, const ConvDesc* 
 {
     if (!conv_is_split(dP) || !conv_is_split(dQ) || conv_wdtype(dP) != conv_wdtype(dQ)) return false;      // split modes, one filter dtype
     const int C = dQ.Cout, H = dP.OH, W = dP.OW;
-    if (!(C == 64 || C == 128) || dQ.Npad != C || dP.Cin != C || dP.Cout != 4 * C || dP.Npad != 4 * C) return false;
+    if (!(C == 64 || C == 128 || C == 256) || dQ.Npad != C || dP.Cin != C || dP.Cout != 4 * C || dP.Npad != 4 * C) return false;
     if (!is_pointwise(dP) || !is_pointwise(dQ) || dP.B != dQ.B) return false;
     if (!plain_epilogue(dP, ACT_RELU) || !plain_epilogue(dQ, ACT_RELU) || dQ.res) return false;
     if (!dense_in(dP, H, W, C) || !dense_out(dP, H, W, 4 * C) || dQ.in != dP.out || !dense_in(dQ, H, W, 4 * C) || !dense_out(dQ, H, W, C)) return false;
     if (conv_k_chunks(dP) != 1 || conv_k_chunks(dQ) != 1) return false;
     auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     if (!al(dP.in) || !al(dP.out) || !al(dQ.out) || !al(dP.wgt) || !al(dQ.wgt) || !al(dP.scale) || !al(dP.shift) || !al(dQ.scale) || !al(dQ.shift)) return false;
+    // C = 256 (the ring form): identity pairs only, both filters as stream images
+    if (C == 256 && (sc || !dP.wgt_stream || !dQ.wgt_stream || !al(dP.wgt_stream) || !al(dQ.wgt_stream))) return false;
     if (sc) {
         // the residual is formed from the shortcut's sums, as conv_forward does it
         if (!g_scfuse || !conv_shortcut_fusable(dP, *sc) || conv_k_chunks(*sc) != 1 || !sc->scale || !sc->shift) return false;
@@ -471,8 +475,12 @@ void conv_forward_chain(hipStream_t s, const ConvDesc& dP, const ConvDesc& dQ, c
     const bool sc_rides = g_chain >= 3 ? sc != nullptr && conv_chain_fusable(dP, dQ, sc) : conv_shortcut_rides(dP, sc);
     // By policy ("conv_chain" 1) a pair is chained where the grid fills the chip AND its shape pays: C = 64 (C2), whose filters stay resident in LDS.
     // C = 128 (C3) — 256 KB of filters, fetched from L2 by every wave — measured SLOWER than its two launches: excluded by shape.
+    // C = 256 (C4) — 1 MB of filters, streamed through a block-shared LDS ring — has its own knob; a dP that carries the stage's shortcut (fused, or
+    // as the tensor it adds) is never chained there.
     const int n_cus = device_cu_count();
-    bool chain = g_chain && g_direct >= 2 && conv_chain_fusable(dP, dQ, sc_rides ? sc : nullptr) && (g_chain >= 2 || (dQ.Cout == 64 && fills_chip(tiles, n_cus)));
+    const bool c4 = dQ.Cout == 256;
+    const int g = c4 ? g_chain4 : g_chain;
+    bool chain = g && g_direct >= 2 && !(c4 && sc) && conv_chain_fusable(dP, dQ, sc_rides ? sc : nullptr) && (g >= 2 || ((c4 || dQ.Cout == 64) && fills_chip(tiles, n_cus)));
 #ifndef MRCNN_CONV_ABLATE
     if (g_pp_dbg) chain = false;
 #endif
@@ -493,7 +501,7 @@ void conv_forward_chain(hipStream_t s, const ConvDesc& dP, const ConvDesc& dQ, c
         aP.sc_H = sc->H; aP.sc_W = sc->W; aP.sc_Cin = sc->Cin; aP.sc_stride = sc->stride;
     }
     const ProfScope prof(s);
-    conv_chain_launch(s, aP, aQ, conv_split_parts(dP), dQ.Cout == 64, n_cus);
+    conv_chain_launch(s, aP, aQ, conv_split_parts(dP), dQ.Cout == 64, n_cus, dP.wgt_stream, dQ.wgt_stream);
     if (prof) {
         // one launch, two layers, under the tile class P's own launch has: the flops of both, the bytes of both less Q's input read
         const double fl = 2.0 * (double)aP.M * ((double)aP.ncols * (aP.Ktot + (sc ? sc->Cin : 0)) + (double)aQ.ncols * aQ.Ktot);

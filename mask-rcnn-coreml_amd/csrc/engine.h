@@ -48,6 +48,7 @@ struct PackedConv {
     DevBuf wgt_halo;              // 3x3 layers of the split modes: the same filters re-tiled for the halo kernel (conv_halo_pack)
     DevBuf wgt_c3h;               // fp16 mode, 3x3 layers with 256 | 512 output columns: the filters in k_conv3x3_h's stream order (conv3x3h_pack)
     DevBuf wgt_frag;              // fp16 mode, the layers of C4's identity bottlenecks: the same filters in MFMA-fragment order (bneck_pack_frag)
+    DevBuf wgt_stream;            // split modes, the 256 <-> 1024 pointwise layers of the bottlenecks: the chained pair's stream image (conv_pack.h: pack_chain_stream)
     int Cin = 0, Cout = 0, KH = 1, KW = 1, Npad = 0;
     int dtype = MRCNN_F32;        // activations
     int wdtype = MRCNN_F32;       // filters (fp16 with fp32 activations = split mode, MRCNN_F32S)

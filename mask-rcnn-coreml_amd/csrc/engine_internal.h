@@ -33,7 +33,7 @@ inline ConvView view_of(const Tensor4& t) { return dense_view(t.p, t.H, t.W, t.C
 
 // Which re-tiled copies of its filters a site hands to the dispatcher.  conv_forward reads a non-null pointer as permission to
 // run that kernel, so this is a dispatch decision of the SITE: a pack may hold a copy its site does not pass.
-enum : unsigned { RETILED_NONE = 0, RETILED_HALO = 1, RETILED_C3H = 2, RETILED_FRAG = 4, RETILED_ALL = 7 };
+enum : unsigned { RETILED_NONE = 0, RETILED_HALO = 1, RETILED_C3H = 2, RETILED_FRAG = 4, RETILED_STREAM = 8, RETILED_ALL = 15 };
 
 // Everything a ConvDesc takes from its pack, its two views and (stride, pad, act); B stays 0 (set per call).  A site then adds
 // only what is particular to it: algo_k / group, out_f32 / out2* / n_split, head_*, deconv2 / out_sH / out_sW / sel_*, res*.
@@ -48,6 +48,7 @@ inline ConvDesc make_conv_desc(const PackedConv& pc, const float* scale, const f
     if (retiled & RETILED_HALO) d.wgt_halo = pc.wgt_halo.p;
     if (retiled & RETILED_C3H) d.wgt_c3h = pc.wgt_c3h.p;
     if (retiled & RETILED_FRAG) d.wgt_frag = pc.wgt_frag.p;
+    if (retiled & RETILED_STREAM) d.wgt_stream = pc.wgt_stream.p;
     d.scale = scale; d.shift = shift;
     d.act = act;
     d.out = out.p; d.OH = out.H; d.OW = out.W; d.Cout = pc.Cout; d.Npad = pc.Npad;

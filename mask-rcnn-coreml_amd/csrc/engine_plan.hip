@@ -240,7 +240,7 @@ struct PlanBuilder {
     // and while a calibration pass needs the tensor between them
     // dsc: the stage's shortcut convolution (first block) — computed inside branch2c's launch where the pair qualifies (conv_forward),
     // so that its tensor is neither written nor read back; its own launch in a calibration pass (which observes its output)
-    // chain (split modes, C2 / C3): the NEXT block's branch2a rides behind branch2c (conv_forward_chain: bit-identical to its own launch), so
+    // chain (split modes, C2 / C3 / C4's identity pairs): the NEXT block's branch2a rides behind branch2c (conv_forward_chain: bit-identical to its own launch), so
     // the op is held back until the next block has made that layer's description — tail_flush adds it, with or without one
     struct PendingTail { ConvDesc d3, d1, dS; bool has_sc = false; int g_mid = 0, g_out = 0; size_t pm = 0, po = 0; bool open = false; } pending_tail;
     void tail_op(const std::string& n3, const std::string& n1, const Tensor4& in3, const Tensor4& mid, const Tensor4& out, const Tensor4& res,
@@ -382,7 +382,8 @@ struct PlanBuilder {
             const int stride = (first && st > 2) ? 2 : 1;
             const int oh = x.H / stride, ow = x.W / stride;
             // split modes, C2 / C3: an identity block's branch2a is chained behind the previous block's branch2c (same description, same groups)
-            const bool chain_q = pending_tail.open && !first && (st == 2 || st == 3) && (m.mode == MRCNN_F32S || m.mode == MRCNN_F32X3);
+            // C4: behind an identity block's branch2c only — the entry block's, which carries the stage's shortcut, keeps its own launch
+            const bool chain_q = pending_tail.open && !first && (st == 2 || st == 3 || (st == 4 && !pending_tail.has_sc)) && (m.mode == MRCNN_F32S || m.mode == MRCNN_F32X3);
             if (!chain_q) tail_flush();
             if (first) { stage_ta = T(oh, ow, f1s[st]); stage_tb = T(oh, ow, f1s[st]); }      // the branch tensors are reused by every block of the stage
             if (first && m.mode == MRCNN_F16 && blocks[st].size() > 1 && bneck_geometry_ok(f1s[st], oh, ow)) {

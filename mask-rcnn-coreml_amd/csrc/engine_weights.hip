@@ -233,6 +233,14 @@ PackedConv pack_conv_oihw(const MrcwFile& f, const std::string& conv, const std:
         conv_halo_pack(nullptr, pc.wgt.p, pc.Npad, I, pc.wgt_halo, 1);        // ... the 256 -> 1024 1x1 layers for the fused bottleneck tail
         HIP_CHECK(hipStreamSynchronize(nullptr));
     }
+    if (pc.wdtype != pc.dtype && pc.dtype == MRCNN_F32 && O == pc.Npad && chain_stream_wanted(KH, KW, I, O) && conv.find("_branch2") != std::string::npos) {
+        // split modes, the bottlenecks' 256 <-> 1024 pointwise layers (C4): also as the chained pair's stream image, built once here
+        std::vector<uint16_t> hw(w.size());
+        for (size_t i = 0; i < w.size(); ++i) hw[i] = float_to_half(w[i]);
+        const std::vector<uint16_t> img = pack_chain_stream(hw.data(), 256, I == 1024);
+        pc.wgt_stream.alloc(img.size() * 2);
+        HIP_CHECK(hipMemcpy(pc.wgt_stream.p, img.data(), img.size() * 2, hipMemcpyHostToDevice));
+    }
     if (pc.dtype == MRCNN_F16 && pc.wdtype == MRCNN_F16 && conv3x3h_packable(KH, KW, I, O, pc.Npad)) {
         conv3x3h_pack(nullptr, pc.wgt.p, O, I, pc.wgt_c3h);
         HIP_CHECK(hipStreamSynchronize(nullptr));

@@ -254,7 +254,9 @@ struct ConvDesc {
     const void* wgt_frag = nullptr;
     // fp16 mode, 3x3 stride-1 layers: the filters in the stream order of k_conv3x3_h (kernels_conv3x3_h.hip: conv3x3h_pack); nullptr = not available
     const void* wgt_c3h = nullptr;
-    int prefer_c3h = 0;          // run on that kernel even without a fused head (the engine's A/B of the head fusion: "conv_c3h" 3)
+    // split modes, the pointwise layers of a C = 256 stage: the filters as the chained pair's stream image (conv_pack.h: pack_chain_stream); nullptr = not available
+    const void* wgt_stream = nullptr;
+    int prefer_c3h = 0;         // run on that kernel even without a fused head (the engine's A/B of the head fusion: "conv_c3h" 3)
     int KH = 1, KW = 1, stride = 1, padH = 0, padW = 0;
     // epilogue: y = act(acc*scale[n] + shift[n] + residual)
     const float* scale = nullptr;
@@ -375,10 +377,12 @@ bool conv_tail_fusable(const ConvDesc& d3, const ConvDesc& d1);
 int conv_sel_part_cols();       // selected-class mode: output columns per partial sum the next conv_forward will leave (64: wave-private form, 128: block-staged)
 void conv_forward_tail(hipStream_t s, const ConvDesc& d3, const ConvDesc& d1, const ConvDesc* sc = nullptr, const ConvDesc* q = nullptr);      // sc: d1's shortcut convolution (conv_forward); q: the layer chained behind d1 (conv_forward_chain)
 // Chained pair of the split modes (kernels_conv_chain.hip): dP = a bottleneck's branch2c (1x1, C -> 4C, residual or fused shortcut sc, ReLU) and
-// dQ = the NEXT block's branch2a (1x1, 4C -> C, ReLU) reading dP's output, C = 64 | 128 — ONE launch: dP's output is stored and dQ is computed from
+// dQ = the NEXT block's branch2a (1x1, 4C -> C, ReLU) reading dP's output, C = 64 | 128 | 256 — ONE launch: dP's output is stored and dQ is computed from
 // the tile while it is on chip.  BIT-IDENTICAL to conv_forward(dP, sc); conv_forward(dQ), which run where the pair does not qualify, the grid
 // under-fills the chip, C = 128 (measured slower: DESIGN.md section 3.1r), or behind mrcnn_debug_set("conv_chain", 0) ("conv_chain" 2: every
 // pair conv_chain_fusable accepts, at every grid size).  conv_chain_fusable says what the kernel can run, not what the policy chooses.
+// C = 256 (C4) has a knob of its own, "conv_chain4" (0 never, 1 by policy, 2 at every grid size), runs identity pairs only — a dP that carries the
+// stage's shortcut, fused or as a tensor, is never chained — and needs both layers' stream images (ConvDesc::wgt_stream).
 bool conv_chain_fusable(const ConvDesc& dP, const ConvDesc& dQ, const ConvDesc* sc = nullptr);
 void conv_forward_chain(hipStream_t s, const ConvDesc& dP, const ConvDesc& dQ, const ConvDesc* sc = nullptr);
 

@@ -11,7 +11,8 @@
 //   * the stored fp32 values go back through the same LDS tile into activation-fragment layout, are split by split_hi_mid_lo /
 //     split_hi_lo and multiplied into Q's accumulators: one running sum per output, channel groups ascending — Q's own order;
 //   * Q's epilogue is the same wave-private piece without a residual.
-// The waves of a block share no pixel: nothing synchronises them inside the loop.  Two forms:
+// The waves of a block share no pixel: nothing synchronises them inside the loop (the ring form: but the hand-over of its filter stages).
+// Three forms (the third, k_conv_chain_ring for C = 256, is described where it stands):
 //   * C = 64 (WLDS): one persistent block of eight waves per CU with every filter of the launch resident in LDS, P's activation
 //     fragments split once per 32-row tile into registers — what conv_forward_chain runs by policy;
 //   * C = 128: P's activation tile (32 rows x C fp32 per wave) in LDS in the 128-row kernel's swizzled layout, both layers' filter
@@ -20,7 +21,7 @@
 
 namespace mrcnn {
 
-struct ChainArgs { ConvArgs p, q; };
+struct ChainArgs { ConvArgs p, q; const void *p_stream, *q_stream; };        // the stream images: the ring form (C = 256) only
 
 // one 32 x 32 piece: accumulators -> wave-private LDS tile (chunk c of row r at c ^ (r & 7)) -> row-wise read-back
 __device__ __forceinline__ void chain_stage_acc(float* stage, const f32x16& acc, int l31, int kk)
@@ -41,14 +42,15 @@ __device__ __forceinline__ ChainParts chain_split(const uint4 u0, const uint4 u1
     return p;
 }
 // one 16-channel group into N column tiles: every tile's hi part, then mid, then lo — per accumulator the 128-row kernel's order
-template <int PARTS, int N>
-__device__ __forceinline__ void chain_mfma_parts(f32x16 (&acc)[N], const uint4 (&bv)[N], const ChainParts& pt)
+// (NA, OFF: the N tiles are acc[OFF .. OFF + N) of a wider set)
+template <int PARTS, int N, int NA = N, int OFF = 0>
+__device__ __forceinline__ void chain_mfma_parts(f32x16 (&acc)[NA], const uint4 (&bv)[N], const ChainParts& pt)
 {
     const f16x8 hi = pt.hi, lo = pt.lo, lo2 = pt.lo2;
-    _Pragma("unroll") for (int j = 0; j < N; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bv[j]), hi, acc[j], 0, 0, 0);
-    _Pragma("unroll") for (int j = 0; j < N; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bv[j]), lo, acc[j], 0, 0, 0);
+    _Pragma("unroll") for (int j = 0; j < N; ++j) acc[OFF + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bv[j]), hi, acc[OFF + j], 0, 0, 0);
+    _Pragma("unroll") for (int j = 0; j < N; ++j) acc[OFF + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bv[j]), lo, acc[OFF + j], 0, 0, 0);
     if constexpr (PARTS == 3)
-        _Pragma("unroll") for (int j = 0; j < N; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bv[j]), lo2, acc[j], 0, 0, 0);
+        _Pragma("unroll") for (int j = 0; j < N; ++j) acc[OFF + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bv[j]), lo2, acc[OFF + j], 0, 0, 0);
 }
 
 // C: P's input channels = Q's output columns (64: C2, 128: C3); SC: P's residual is formed from the fused shortcut convolution
@@ -289,15 +291,253 @@ __global__ __launch_bounds__(WLDS ? 512 : 256, WLDS ? 1 : 2) void k_conv_chain(c
     if (aq.range_flag && out_of_range_q) atomicOr(aq.range_flag, 1);
 }
 
+// The ring form (C = 256: C4's identity pairs).  W3 and W1 are 512 KB each: neither LDS residency nor per-lane L2 fetches serve.  The
+// block's four waves (one per SIMD, 32 rows each, 128 rows per block) share a ring of two LDS stages; per 64-column chunk of P a stage
+// holds the chunk's 32 KB of W3 (64 rows x K 256) and its 32 KB of W1 (256 rows x 64 of Q's channels), copied by LDS-DMA from the layers'
+// stream images (conv_pack.h: pack_chain_stream — the chunk images lie in memory in their LDS layout, so the copy is straight: 16 DMAs of
+// 1 KB per wave and chunk).  One block barrier per chunk hands a stage over: behind it every wave has its share of chunk i landed
+// (vmcnt(0) in front of it) and has finished reading chunk i - 1, whose stage the DMAs of chunk i + 1 then overwrite while chunk i is
+// multiplied.  EVERY wave reaches every barrier and issues its share of every DMA: a wave whose 32 rows lie beyond M skips loads, MFMAs
+// and stores, never a ring step.  P's activation fragments are split once into registers (the C = 64 form's method: 16 groups x PARTS
+// fragments); the sums, the epilogue pieces and Q's steps are the other forms', expression for expression.  Nothing crosses blocks.
+template <int C, int PARTS>
+__global__ __launch_bounds__(256, 1) void k_conv_chain_ring(const ChainArgs ca)
+{
+    static_assert(C == 256, "the ring's stage holds C = 256's chunk images");
+    constexpr int C4 = 4 * C, KT = C / 32, TNP = 2, TNQ = C / 32, NCH = C4 / 64;
+    constexpr int WCH = 64 * C * 2;                      // one chunk image of either layer: 64 rows x C channels (W3) = C rows x 64 channels (W1)
+    constexpr int STAGE = 2 * WCH;
+    constexpr int NDMA = WCH / 4096;                     // DMAs per thread, chunk and layer: 256 lanes x 16 B each
+    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE + 4 * 32 * 32 * 4];
+    __shared__ __attribute__((aligned(16))) float s_tab[2 * C4], s_tabq[2 * C];       // scale | shift of P's and of Q's columns: one wave per SIMD hides no global load inside an epilogue
+    const ConvArgs& a = ca.p;
+    const ConvArgs& aq = ca.q;
+    const int t = threadIdx.x;
+    const int wave = t >> 6, lane = t & 63;
+    const int l31 = lane & 31, kk = lane >> 5;
+    float* const stage = reinterpret_cast<float*>(smem + 2 * STAGE) + wave * (32 * 32);
+    static_assert(C4 == 4 * 256 && C % 8 == 0 && C / 2 <= 256, "the tables are filled by 256 threads, 16 B each");
+    *reinterpret_cast<float4*>(&s_tab[4 * t]) = *reinterpret_cast<const float4*>(a.scale + 4 * t);
+    *reinterpret_cast<float4*>(&s_tab[C4 + 4 * t]) = *reinterpret_cast<const float4*>(a.shift + 4 * t);
+    if (t < C / 2) *reinterpret_cast<float4*>(&s_tabq[4 * t]) = *reinterpret_cast<const float4*>(t < C / 4 ? aq.scale + 4 * t : aq.shift + 4 * (t - C / 4));      // (read behind the first ring barrier)
+    const float* const in = static_cast<const float*>(a.in);
+    const float* const res = static_cast<const float*>(a.res);
+    float* const out = static_cast<float*>(a.out);
+    float* const outq = static_cast<float*>(aq.out);
+    const int swzb = (l31 >> 2) & 3;                     // filter rows in LDS: 16-B chunk c of row r at c ^ ((r >> 2) & 3)
+
+    // ---- the ring's DMA: buffer resources over the two images (a lane beyond them would deposit zeros), inline asm as in kernels_conv.hip ----
+    typedef unsigned srd_t __attribute__((ext_vector_type(4)));
+    srd_t srdP, srdQ;
+    {
+        const unsigned long long wp = (unsigned long long)(uintptr_t)ca.p_stream, wq = (unsigned long long)(uintptr_t)ca.q_stream;
+        srdP[0] = __builtin_amdgcn_readfirstlane((unsigned)wp);
+        srdP[1] = __builtin_amdgcn_readfirstlane((unsigned)(wp >> 32) & 0xffffu);
+        srdP[2] = (unsigned)(NCH * WCH);
+        srdP[3] = 0x00020000u;
+        srdQ[0] = __builtin_amdgcn_readfirstlane((unsigned)wq);
+        srdQ[1] = __builtin_amdgcn_readfirstlane((unsigned)(wq >> 32) & 0xffffu);
+        srdQ[2] = (unsigned)(NCH * WCH);
+        srdQ[3] = 0x00020000u;
+    }
+    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem);
+    const unsigned wdst = lds0 + (unsigned)__builtin_amdgcn_readfirstlane(wave) * 1024u;      // wave-uniform: lane i's 16 B land at M0 + 16 i
+    const unsigned voff = (unsigned)t * 16u;
+#define MRCNN_RING_DMA(SRD, SOFF, DST)                                                                         \
+    asm volatile("s_nop 4\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff), "s"(SRD), "s"(SOFF), "s"(DST) : "memory", "m0");
+    // chunk ch of both images -> stage ch & 1 (this thread's share: 16 B of each 4 KB slice)
+    auto ring_fill = [&](int ch) {
+        const unsigned src = (unsigned)__builtin_amdgcn_readfirstlane(ch) * (unsigned)WCH;
+        const unsigned dst = wdst + (unsigned)(__builtin_amdgcn_readfirstlane(ch) & 1) * (unsigned)STAGE;
+#pragma unroll
+        for (int k = 0; k < NDMA; ++k) {
+            MRCNN_RING_DMA(srdP, src + k * 4096u, dst + k * 4096u)
+            MRCNN_RING_DMA(srdQ, src + k * 4096u, dst + (unsigned)WCH + k * 4096u)
+        }
+    };
+    ring_fill(0);
+
+    const int row0 = (blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(wave)) * 32;
+    const bool live = row0 < a.M;                        // (wave-uniform) a wave without rows keeps the ring going and does nothing else
+    bool out_of_range = false, out_of_range_q = false;
+    // P's activation fragments of this lane, split once (rows beyond M: zeros)
+    // (every request leaves before the first split: a lane beyond M reads the wave's first row and zeroes what it got)
+    ChainParts ap[2 * KT];
+    if (live) {
+        const int m = row0 + l31;
+        const bool m_ok = m < a.M;
+        const float* const src = in + (long)(m_ok ? m : row0) * C + 8 * kk;
+        uint4 u[2 * KT][2];
+#pragma unroll
+        for (int g = 0; g < 2 * KT; ++g) { u[g][0] = *reinterpret_cast<const uint4*>(src + g * 16); u[g][1] = *reinterpret_cast<const uint4*>(src + g * 16 + 4); }
+#pragma unroll
+        for (int g = 0; g < 2 * KT; ++g) {
+            if (!m_ok) u[g][0] = u[g][1] = make_uint4(0u, 0u, 0u, 0u);
+            ap[g] = chain_split<PARTS>(u[g][0], u[g][1]);
+        }
+    }
+    const bool full = row0 + 32 <= a.M;                  // (wave-uniform) the wave issues every load and store of a chunk
+    const int rrow = lane >> 3, c4 = (lane & 7) * 4;     // read-back: eight lanes per row, four passes of eight rows
+    const bool relu = a.act == ACT_RELU, reluq = aq.act == ACT_RELU;
+    bool ok[4];
+    long mrow[4];
+#pragma unroll
+    for (int ps = 0; ps < 4; ++ps) { const int m = row0 + 8 * ps + rrow; ok[ps] = m < a.M; mrow[ps] = m; }
+
+    f32x16 accQ[TNQ];
+#pragma unroll
+    for (int j = 0; j < TNQ; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) accQ[j][e] = 0.0f;
+
+    for (int ch = 0; ch < NCH; ++ch) {
+        // chunk ch has landed for every wave, and every wave has left chunk ch - 1: its stage takes chunk ch + 1
+        // (the DMAs of chunk ch are older than the 8 residual loads and 8 stores a wave of 32 rows has issued since, and vector memory
+        // operations retire in order: such a wave leaves its last piece's four stores in flight across the barrier; any other wave waits for all)
+        if (full) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (ch + 1 < NCH) ring_fill(ch + 1);
+        if (!live) continue;
+        const unsigned char* const w3s = smem + (ch & 1) * STAGE;          // [K step][64 rows][64 B]
+        const unsigned char* const w1s = w3s + WCH;                        // [2 K steps][C rows][64 B]
+        const int nc = ch * 64;
+        // the residual of the chunk is requested before its K loop: every element the wave will overwrite, before its first store
+        float4 rv[TNP][4];
+#pragma unroll
+        for (int j = 0; j < TNP; ++j)
+#pragma unroll
+            for (int ps = 0; ps < 4; ++ps) {
+                rv[j][ps] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (res && ok[ps]) rv[j][ps] = *reinterpret_cast<const float4*>(res + mrow[ps] * C4 + nc + j * 32 + c4);
+            }
+        f32x16 accP[TNP];
+#pragma unroll
+        for (int j = 0; j < TNP; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) accP[j][e] = 0.0f;
+        // ---- P: K steps of 32 channels, two groups of 16 each ------------------------------------------------------
+        // (one wave per SIMD: only the wave's own stream hides an LDS read, so group i + 1's filter fragments are requested ahead of group i's MFMAs)
+        auto frag_p = [&](uint4 (&b)[TNP], int i) {
+#pragma unroll
+            for (int j = 0; j < TNP; ++j) b[j] = *reinterpret_cast<const uint4*>(w3s + ((i >> 1) * 64 + j * 32 + l31) * 64 + (((2 * (i & 1) + kk) ^ swzb) << 4));
+        };
+        {
+            uint4 bv[TNP];
+            frag_p(bv, 0);
+#pragma unroll
+            for (int i = 0; i < 2 * KT; ++i) {
+                uint4 bn[TNP];
+                if (i + 1 < 2 * KT) frag_p(bn, i + 1);
+                __builtin_amdgcn_sched_barrier(0);
+                chain_mfma_parts<PARTS, TNP>(accP, bv, ap[i]);
+                if (i + 1 < 2 * KT) {
+#pragma unroll
+                    for (int j = 0; j < TNP; ++j) bv[j] = bn[j];
+                }
+            }
+        }
+        // Q's filter fragments of half a group (four column tiles x 16 channels): half h of piece j
+        auto frag_q = [&](uint4 (&b)[TNQ / 2], int j, int h) {
+#pragma unroll
+            for (int i = 0; i < TNQ / 2; ++i) b[i] = *reinterpret_cast<const uint4*>(w1s + (j * C + ((h & 1) * (TNQ / 2) + i) * 32 + l31) * 64 + (((2 * (h >> 1) + kk) ^ swzb) << 4));
+        };
+        // ---- epilogue of the chunk, piece by piece; each piece is one K step of Q -------------------------------------
+#pragma unroll
+        for (int j = 0; j < TNP; ++j) {
+            const int n = nc + j * 32 + c4;
+            uint4 bq[TNQ / 2];
+            frag_q(bq, j, 0);                              // (independent of the epilogue: on its way meanwhile)
+            chain_stage_acc(stage, accP[j], l31, kk);
+            __builtin_amdgcn_wave_barrier();
+            const float4 sc = *reinterpret_cast<const float4*>(&s_tab[n]), sh = *reinterpret_cast<const float4*>(&s_tab[C4 + n]);
+            float4 xs[4];
+#pragma unroll
+            for (int ps = 0; ps < 4; ++ps) xs[ps] = *reinterpret_cast<const float4*>(&stage[(8 * ps + rrow) * 32 + (((lane & 7) ^ rrow) << 2)]);      // (all four reads ahead of the row tests: one LDS wait)
+#pragma unroll
+            for (int ps = 0; ps < 4; ++ps) {
+                float4 x = xs[ps];
+                x.x = x.x * sc.x + sh.x; x.y = x.y * sc.y + sh.y; x.z = x.z * sc.z + sh.z; x.w = x.w * sc.w + sh.w;
+                if (res) { x.x += rv[j][ps].x; x.y += rv[j][ps].y; x.z += rv[j][ps].z; x.w += rv[j][ps].w; }
+                if (relu) { x.x = fmaxf(x.x, 0.f); x.y = fmaxf(x.y, 0.f); x.z = fmaxf(x.z, 0.f); x.w = fmaxf(x.w, 0.f); }
+                if (ok[ps]) {
+                    out_of_range = out_of_range || !(fabsf(x.x) < 65504.0f) || !(fabsf(x.y) < 65504.0f) || !(fabsf(x.z) < 65504.0f) || !(fabsf(x.w) < 65504.0f);
+                    *reinterpret_cast<float4*>(out + mrow[ps] * C4 + n) = x;
+                }
+                xs[ps] = x;
+            }
+            __builtin_amdgcn_wave_barrier();
+            // the stored values, back in place: the tile now holds y row-major (same swizzle)
+#pragma unroll
+            for (int ps = 0; ps < 4; ++ps) *reinterpret_cast<float4*>(&stage[(8 * ps + rrow) * 32 + (((lane & 7) ^ rrow) << 2)]) = xs[ps];
+            __builtin_amdgcn_wave_barrier();
+            // ---- Q: the K step of channels nc + 32 j .. + 31 ---------------------------------------------------------
+            // (per accumulator the order is the other forms': group 0's parts, then group 1's; the halves only stagger the fragment reads)
+            ChainParts pt;
+#pragma unroll
+            for (int h = 0; h < 4; ++h) {
+                if ((h & 1) == 0) {
+                    const int g = h >> 1;
+                    const uint4 u0 = *reinterpret_cast<const uint4*>(&stage[l31 * 32 + (((4 * g + 2 * kk) ^ (l31 & 7)) << 2)]);
+                    const uint4 u1 = *reinterpret_cast<const uint4*>(&stage[l31 * 32 + (((4 * g + 2 * kk + 1) ^ (l31 & 7)) << 2)]);
+                    pt = chain_split<PARTS>(u0, u1);
+                }
+                uint4 bn[TNQ / 2];
+                if (h < 3) frag_q(bn, j, h + 1);
+                __builtin_amdgcn_sched_barrier(0);
+                if (h & 1) chain_mfma_parts<PARTS, TNQ / 2, TNQ, TNQ / 2>(accQ, bq, pt);
+                else chain_mfma_parts<PARTS, TNQ / 2, TNQ, 0>(accQ, bq, pt);
+                if (h < 3) {
+#pragma unroll
+                    for (int i = 0; i < TNQ / 2; ++i) bq[i] = bn[i];
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+#undef MRCNN_RING_DMA
+    // (no barrier follows: a wave without rows is done)
+    if (live) {
+        // ---- Q's epilogue: scale / shift, ReLU, watch, full-line stores ------------------------------------------------------
+#pragma unroll
+        for (int jq = 0; jq < TNQ; ++jq) {
+            const int n = jq * 32 + c4;
+            chain_stage_acc(stage, accQ[jq], l31, kk);
+            __builtin_amdgcn_wave_barrier();
+            const float4 sc = *reinterpret_cast<const float4*>(&s_tabq[n]), sh = *reinterpret_cast<const float4*>(&s_tabq[C + n]);
+#pragma unroll
+            for (int ps = 0; ps < 4; ++ps) {
+                float4 x = *reinterpret_cast<const float4*>(&stage[(8 * ps + rrow) * 32 + (((lane & 7) ^ rrow) << 2)]);
+                x.x = x.x * sc.x + sh.x; x.y = x.y * sc.y + sh.y; x.z = x.z * sc.z + sh.z; x.w = x.w * sc.w + sh.w;
+                if (reluq) { x.x = fmaxf(x.x, 0.f); x.y = fmaxf(x.y, 0.f); x.z = fmaxf(x.z, 0.f); x.w = fmaxf(x.w, 0.f); }
+                if (ok[ps]) {
+                    out_of_range_q = out_of_range_q || !(fabsf(x.x) < 65504.0f) || !(fabsf(x.y) < 65504.0f) || !(fabsf(x.z) < 65504.0f) || !(fabsf(x.w) < 65504.0f);
+                    *reinterpret_cast<float4*>(outq + mrow[ps] * C + n) = x;
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    if (a.range_flag && out_of_range) atomicOr(a.range_flag, 1);
+    if (aq.range_flag && out_of_range_q) atomicOr(aq.range_flag, 1);
+}
+
 // p / q: the launch arguments of the two layers (conv_dispatch.hip has checked the pair: conv_chain_fusable); parts 2 | 3
 // wlds: the LDS-resident persistent form (C = 64 with a 64-channel shortcut or none); n_cus sizes its grid
-void conv_chain_launch(hipStream_t s, const ConvArgs& p, const ConvArgs& q, int parts, bool wlds, int n_cus)
+// p_stream / q_stream: the layers' stream images (C = 256: the ring form, identity pairs only)
+void conv_chain_launch(hipStream_t s, const ConvArgs& p, const ConvArgs& q, int parts, bool wlds, int n_cus, const void* p_stream, const void* q_stream)
 {
-    ChainArgs ca{p, q};
+    ChainArgs ca{p, q, p_stream, q_stream};
     dim3 grid((p.M + 127) / 128), block(256);
     const bool sc = p.sc_in != nullptr;
     const int C = q.Cout;
-    MRCNN_REQUIRE((C == 64 || C == 128) && (parts == 2 || parts == 3), MRCNN_ERR_INVALID, "conv_chain_launch: C %d, %d parts", C, parts);
+    MRCNN_REQUIRE((C == 64 || C == 128 || C == 256) && (parts == 2 || parts == 3), MRCNN_ERR_INVALID, "conv_chain_launch: C %d, %d parts", C, parts);
+    if (C == 256) {
+        MRCNN_REQUIRE(!wlds && !sc && p.res && p_stream && q_stream, MRCNN_ERR_INVALID, "conv_chain_launch: C = 256 runs identity pairs from their stream images");
+        if (parts == 3) hipLaunchKernelGGL((k_conv_chain_ring<256, 3>), grid, block, 0, s, ca);
+        else hipLaunchKernelGGL((k_conv_chain_ring<256, 2>), grid, block, 0, s, ca);
+        return;
+    }
     if (wlds) {
         MRCNN_REQUIRE(C == 64 && (!sc || p.sc_Cin == 64) && n_cus > 0, MRCNN_ERR_INVALID, "conv_chain_launch: the LDS-resident form holds C = 64's filters");
         const int tiles256 = (p.M + 255) / 256;
