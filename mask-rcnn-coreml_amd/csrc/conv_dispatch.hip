@@ -12,7 +12,7 @@ namespace mrcnn {
 
 void conv_mfma_launch(hipStream_t s, const ConvArgs& a, int mode, int bn, bool wide_waves);   // kernels_conv.hip: 0 fp16, 1 exact fp32, 2 / 3 split parts
 void conv_pp_launch(hipStream_t s, const ConvArgs& a, int mode);   // kernels_conv_pp.hip: 0 fp16, 2 / 3 split parts
-void conv_chain_launch(hipStream_t s, const ConvArgs& p, const ConvArgs& q, int parts, bool wlds, int n_cus, const void* p_stream, const void* q_stream);   // kernels_conv_chain.hip: split parts 2 / 3
+void conv_chain_launch(hipStream_t s, const ConvArgs& p, const ConvArgs& q, int parts, int n_cus, const void* p_stream, const void* q_stream);   // kernels_conv_chain.hip: split parts 2 / 3
 
 // ---- what a layer description says about its mode and geometry --------------------------------------------------------------
 static inline int conv_wdtype(const ConvDesc& d) { return d.wdtype < 0 ? d.dtype : d.wdtype; }
@@ -501,7 +501,7 @@ void conv_forward_chain(hipStream_t s, const ConvDesc& dP, const ConvDesc& dQ, c
         aP.sc_H = sc->H; aP.sc_W = sc->W; aP.sc_Cin = sc->Cin; aP.sc_stride = sc->stride;
     }
     const ProfScope prof(s);
-    conv_chain_launch(s, aP, aQ, conv_split_parts(dP), dQ.Cout == 64, n_cus, dP.wgt_stream, dQ.wgt_stream);
+    conv_chain_launch(s, aP, aQ, conv_split_parts(dP), n_cus, dP.wgt_stream, dQ.wgt_stream);
     if (prof) {
         // one launch, two layers, under the tile class P's own launch has: the flops of both, the bytes of both less Q's input read
         const double fl = 2.0 * (double)aP.M * ((double)aP.ncols * (aP.Ktot + (sc ? sc->Cin : 0)) + (double)aQ.ncols * aQ.Ktot);

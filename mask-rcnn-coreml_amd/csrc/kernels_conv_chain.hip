@@ -3,32 +3,52 @@
 // wave has just activated is exactly Q's activation operand for the same pixels: Q is computed from it while it is on chip, so
 // the 4C-wide tensor is stored (the next block's residual) but not read back by a launch of its own.
 //
-// BIT-IDENTICAL to conv_forward(P); conv_forward(Q), output for output:
-//   * a wave owns 32 pixel rows and walks ALL of P's 4C columns in ascending chunks of 64; P's sums per chunk are the 128-row
-//     kernel's (K steps of 32 channels, groups of 16 ascending, hi / mid / lo part per group, filter fragment first);
-//   * each 32 x 32 piece goes through the wave-private transpose of conv_epilogue_wave with its expressions (scale / shift,
-//     + residual — loaded, or formed from the shortcut's sums —, ReLU, fp16-range watch) and is stored;
-//   * the stored fp32 values go back through the same LDS tile into activation-fragment layout, are split by split_hi_mid_lo /
-//     split_hi_lo and multiplied into Q's accumulators: one running sum per output, channel groups ascending — Q's own order;
-//   * Q's epilogue is the same wave-private piece without a residual.
-// The waves of a block share no pixel: nothing synchronises them inside the loop (the ring form: but the hand-over of its filter stages).
-// Three forms (the third, k_conv_chain_ring for C = 256, is described where it stands):
-//   * C = 64 (WLDS): one persistent block of eight waves per CU with every filter of the launch resident in LDS, P's activation
-//     fragments split once per 32-row tile into registers — what conv_forward_chain runs by policy;
-//   * C = 128: P's activation tile (32 rows x C fp32 per wave) in LDS in the 128-row kernel's swizzled layout, both layers' filter
-//     fragments straight from L2 (16 B per lane) — measured slower than the two launches, kept as the tests' bit-identity anchor.
+// BIT-IDENTICAL to conv_forward(P); conv_forward(Q), output for output.  A wave owns 32 pixel rows and walks ALL of P's 4C columns
+// in ascending chunks of 64.  The arithmetic is written ONCE, in the building blocks ahead of the kernels:
+//   * chain_split_row / chain_mfma_parts — P's sums per chunk are the 128-row kernel's: K steps of 32 channels, groups of 16
+//     ascending, hi / mid / lo part per group, filter fragment first;
+//   * ChainTile — the wave-private 32 x 32 LDS tile of conv_epilogue_wave: accumulators in (put), rows out and back (row_get /
+//     row_put), Q's activation fragments out (frag);
+//   * chain_scale_shift, chain_add, chain_relu, chain_beyond_fp16 — conv_epilogue_wave's expressions on four adjacent columns (scale /
+//     shift, + residual — loaded by chain_residual, or formed from the shortcut's sums —, ReLU, the fp16-range watch);
+//   * chain_piece_p — one 32 x 32 piece of P through them, stored, and left in the tile as y: the stored fp32 values, which Q's step
+//     splits by split_hi_mid_lo / split_hi_lo and multiplies into Q's accumulators: one running sum per output, channel groups
+//     ascending — Q's own order.  k_conv_chain spells the piece (and the shortcut's, which only it has) out of the same primitives in
+//     its body: called as a function it costs k_conv_chain<64, 3, SC>, which sits at its 256 registers, 12 B of scratch;
+//   * chain_epilogue_q — Q's epilogue: the same piece without a residual.
+// What a kernel body adds is where its FILTERS come from.  The waves of a block share no pixel: nothing
+// synchronises them inside the loop but, in the ring form, the hand-over of its filter stages.
+//   * k_conv_chain<64>: every filter of the launch resident in LDS, one persistent block of eight waves per CU — what
+//     conv_forward_chain runs for C2;
+//   * k_conv_chain<128>: P's activation tile (32 rows x C fp32 per wave) in LDS in the 128-row kernel's swizzled layout, both layers'
+//     filter fragments straight from L2 (16 B per lane) — measured slower than the two launches, kept as the tests' bit-identity anchor;
+//   * k_conv_chain_ring<256>: both layers' filters streamed chunk by chunk through a block-shared LDS ring — what runs for C4.
 #include "conv_device.h"
 
 namespace mrcnn {
 
 struct ChainArgs { ConvArgs p, q; const void *p_stream, *q_stream; };        // the stream images: the ring form (C = 256) only
 
-// one 32 x 32 piece: accumulators -> wave-private LDS tile (chunk c of row r at c ^ (r & 7)) -> row-wise read-back
-__device__ __forceinline__ void chain_stage_acc(float* stage, const f32x16& acc, int l31, int kk)
+// ---- four adjacent columns of one row: conv_epilogue_wave's expressions -------------------------------------------------------------
+__device__ __forceinline__ float4 chain_scale_shift(float4 x, const float4 sc, const float4 sh)
 {
+    x.x = x.x * sc.x + sh.x; x.y = x.y * sc.y + sh.y; x.z = x.z * sc.z + sh.z; x.w = x.w * sc.w + sh.w;
+    return x;
+}
+__device__ __forceinline__ float4 chain_add(float4 x, const float4 r) { x.x += r.x; x.y += r.y; x.z += r.z; x.w += r.w; return x; }
+__device__ __forceinline__ float4 chain_relu(float4 x) { x.x = fmaxf(x.x, 0.f); x.y = fmaxf(x.y, 0.f); x.z = fmaxf(x.z, 0.f); x.w = fmaxf(x.w, 0.f); return x; }
+__device__ __forceinline__ bool chain_beyond_fp16(const float4 x) { return !(fabsf(x.x) < 65504.0f) || !(fabsf(x.y) < 65504.0f) || !(fabsf(x.z) < 65504.0f) || !(fabsf(x.w) < 65504.0f); }
+__device__ __forceinline__ float4 chain_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+
+// the row-wise read-back of a wave's 32 rows: eight lanes per row (columns c4 .. c4 + 3), four passes of eight rows
+struct ChainRows { bool ok[4]; long mrow[4]; int c4; };
+__device__ __forceinline__ ChainRows chain_rows(int row0, int M, int lane)
+{
+    ChainRows rw;
+    rw.c4 = (lane & 7) * 4;
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
-        *reinterpret_cast<float4*>(&stage[l31 * 32 + (((2 * q + kk) ^ (l31 & 7)) << 2)]) = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+    for (int ps = 0; ps < 4; ++ps) { const int m = row0 + 8 * ps + (lane >> 3); rw.ok[ps] = m < M; rw.mrow[ps] = m; }
+    return rw;
 }
 
 // the fp16 parts of eight fp32 activations: hi, (mid,) lo
@@ -41,6 +61,25 @@ __device__ __forceinline__ ChainParts chain_split(const uint4 u0, const uint4 u1
     else { split_hi_lo(u0, u1, p.hi, p.lo); p.lo2 = p.lo; }
     return p;
 }
+// this lane's activation fragments of P (pixel row0 + l31, NG groups of 16 channels), split once into registers (rows beyond M: zeros)
+// AHEAD (the ring form: one wave per SIMD, nothing else hides a request): every request leaves before the first split — a lane beyond M reads
+// the wave's first row and zeroes what it got; otherwise such a lane requests nothing (measured: C = 64 without a shortcut is 0.4 % slower AHEAD)
+template <int PARTS, bool AHEAD, int NG>
+__device__ __forceinline__ void chain_split_row(ChainParts (&ap)[NG], const float* in, int row0, int M, int l31, int kk)
+{
+    const int m = row0 + l31;
+    const bool m_ok = m < M;
+    const float* const src = in + (long)(m_ok ? m : row0) * (NG * 16) + 8 * kk;
+    uint4 u[NG][2];
+    if constexpr (AHEAD)
+        _Pragma("unroll") for (int g = 0; g < NG; ++g) { u[g][0] = *reinterpret_cast<const uint4*>(src + g * 16); u[g][1] = *reinterpret_cast<const uint4*>(src + g * 16 + 4); }
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        if (!AHEAD || !m_ok) u[g][0] = u[g][1] = make_uint4(0u, 0u, 0u, 0u);
+        if (!AHEAD && m_ok) { u[g][0] = *reinterpret_cast<const uint4*>(src + g * 16); u[g][1] = *reinterpret_cast<const uint4*>(src + g * 16 + 4); }
+        ap[g] = chain_split<PARTS>(u[g][0], u[g][1]);
+    }
+}
 // one 16-channel group into N column tiles: every tile's hi part, then mid, then lo — per accumulator the 128-row kernel's order
 // (NA, OFF: the N tiles are acc[OFF .. OFF + N) of a wider set)
 template <int PARTS, int N, int NA = N, int OFF = 0>
@@ -52,15 +91,113 @@ __device__ __forceinline__ void chain_mfma_parts(f32x16 (&acc)[NA], const uint4 
     if constexpr (PARTS == 3)
         _Pragma("unroll") for (int j = 0; j < N; ++j) acc[OFF + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bv[j]), lo2, acc[OFF + j], 0, 0, 0);
 }
+template <int N>
+__device__ __forceinline__ void chain_zero(f32x16 (&acc)[N])
+{
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[j][e] = 0.0f;
+}
+
+// the wave-private 32 x 32 fp32 tile: 16-B chunk c of row r at c ^ (r & 7); one access pattern per member
+// (the wave's own barriers between the patterns are the callers')
+struct ChainTile {
+    float* s;
+    int lane;
+    __device__ __forceinline__ float4* at(int r, int c) const { return reinterpret_cast<float4*>(&s[r * 32 + ((c ^ (r & 7)) << 2)]); }
+    // an accumulator tile, transposing: lane l31 holds row l31's columns 8 q + 4 kk .. + 3
+    __device__ __forceinline__ void put(const f32x16& acc) const
+    {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) *at(lane & 31, 2 * q + (lane >> 5)) = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+    }
+    // row-wise: pass ps of ChainRows
+    __device__ __forceinline__ float4 row_get(int ps) const { return *at(8 * ps + (lane >> 3), lane & 7); }
+    __device__ __forceinline__ void row_put(int ps, const float4 v) const { *at(8 * ps + (lane >> 3), lane & 7) = v; }
+    // row l31's channels 16 g + 8 kk .. + 7 as an activation fragment, split
+    template <int PARTS>
+    __device__ __forceinline__ ChainParts frag(int g) const
+    {
+        const int c = 4 * g + 2 * (lane >> 5);
+        return chain_split<PARTS>(*reinterpret_cast<const uint4*>(at(lane & 31, c)), *reinterpret_cast<const uint4*>(at(lane & 31, c + 1)));
+    }
+};
+
+// the residual of a 64-column chunk (no residual: zeros); the callers request it before the chunk's K loop: every element the wave will
+// overwrite, before its first store
+__device__ __forceinline__ void chain_residual(float4 (&rv)[2][4], const float* res, const ChainRows& rw, int pitch, int nc)
+{
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int ps = 0; ps < 4; ++ps) {
+            rv[j][ps] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (res && rw.ok[ps]) rv[j][ps] = chain_ld4(res + rw.mrow[ps] * pitch + nc + j * 32 + rw.c4);
+        }
+}
+// one 32 x 32 piece of P: columns n .. n + 3 of this lane's four rows, scaled and shifted (scale / shift: the tables, in memory or in LDS), + r,
+// activated, watched and stored; the tile is left holding y row-major (the stored values, same swizzle) for Q's step
+// (all four tile reads ahead of the row tests: one LDS wait)
+__device__ __forceinline__ void chain_piece_p(const ChainTile& tl, const f32x16& acc, const float* scale, const float* shift, const float4 (&r)[4], bool has_res, bool relu,
+                                              const ChainRows& rw, float* out, int pitch, int n, bool& out_of_range)
+{
+    tl.put(acc);
+    __builtin_amdgcn_wave_barrier();
+    const float4 sc = chain_ld4(scale + n), sh = chain_ld4(shift + n);
+    float4 xs[4];
+#pragma unroll
+    for (int ps = 0; ps < 4; ++ps) xs[ps] = tl.row_get(ps);
+#pragma unroll
+    for (int ps = 0; ps < 4; ++ps) {
+        float4 x = chain_scale_shift(xs[ps], sc, sh);
+        if (has_res) x = chain_add(x, r[ps]);
+        if (relu) x = chain_relu(x);
+        if (rw.ok[ps]) {
+            out_of_range = out_of_range || chain_beyond_fp16(x);
+            *reinterpret_cast<float4*>(out + rw.mrow[ps] * pitch + n) = x;
+        }
+        xs[ps] = x;
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int ps = 0; ps < 4; ++ps) tl.row_put(ps, xs[ps]);
+    __builtin_amdgcn_wave_barrier();
+}
+// Q's epilogue: TNQ pieces of 32 columns — scale / shift (tables in memory or in LDS), ReLU, watch, full-line stores
+template <int TNQ>
+__device__ __forceinline__ void chain_epilogue_q(const ChainTile& tl, const f32x16 (&acc)[TNQ], const float* scale, const float* shift, bool relu,
+                                                 const ChainRows& rw, float* out, bool& out_of_range)
+{
+#pragma unroll
+    for (int jq = 0; jq < TNQ; ++jq) {
+        const int n = jq * 32 + rw.c4;
+        tl.put(acc[jq]);
+        __builtin_amdgcn_wave_barrier();
+        const float4 sc = chain_ld4(scale + n), sh = chain_ld4(shift + n);
+#pragma unroll
+        for (int ps = 0; ps < 4; ++ps) {
+            float4 x = chain_scale_shift(tl.row_get(ps), sc, sh);
+            if (relu) x = chain_relu(x);
+            if (rw.ok[ps]) {
+                out_of_range = out_of_range || chain_beyond_fp16(x);
+                *reinterpret_cast<float4*>(out + rw.mrow[ps] * (TNQ * 32) + n) = x;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
 
 // C: P's input channels = Q's output columns (64: C2, 128: C3); SC: P's residual is formed from the fused shortcut convolution
-// WLDS (C = 64 only): every filter of the launch resident in LDS (W3, W1 and the shortcut's: 32 KB each, in the 128-row kernel's swizzled
-// 64-B rows per K step), ONE block of eight waves per CU walking 32-row tiles of the whole tensor (a persistent grid: the filters are staged once
-// per CU), and P's activation fragments split ONCE per tile into registers — no filter request leaves the CU inside the loop.
-template <int C, int PARTS, bool SC, bool WLDS>
-__global__ __launch_bounds__(WLDS ? 512 : 256, WLDS ? 1 : 2) void k_conv_chain(const ChainArgs ca)
+// C = 64: every filter of the launch resident in LDS (W3, W1 and the shortcut's: 32 KB each, in the 128-row kernel's swizzled 64-B rows per
+// K step), ONE block of eight waves per CU walking 32-row tiles of the whole tensor (a persistent grid: the filters are staged once per CU),
+// and P's activation fragments split ONCE per tile into registers — no filter request leaves the CU inside the loop.
+// C = 128: four waves of one tile each; P's activation tile in LDS, split per use; every filter fragment from L2.
+template <int C, int PARTS, bool SC>
+__global__ __launch_bounds__(C == 64 ? 512 : 256, C == 64 ? 1 : 2) void k_conv_chain(const ChainArgs ca)
 {
-    static_assert(!WLDS || C == 64, "the LDS-resident form holds C = 64's filters");
+    static_assert(C == 64 || C == 128, "C = 64: filters resident in LDS; C = 128: filters from L2");
+    constexpr bool WLDS = C == 64;
     constexpr int NW = WLDS ? 8 : 4, C4 = 4 * C, KT = C / 32, TNP = 2, TNQ = C / 32;
     constexpr int A_BYTES = WLDS ? 0 : KT * 32 * 128;    // a wave's activation tile: KT sub-tiles of 32 rows x 128 B
     constexpr int W_BYTES = WLDS ? C4 * C * 2 : 0;       // one filter matrix (W3: [K step][4C rows][64 B]; W1: [K step][C rows][64 B])
@@ -72,13 +209,12 @@ __global__ __launch_bounds__(WLDS ? 512 : 256, WLDS ? 1 : 2) void k_conv_chain(c
     const int wave = t >> 6, lane = t & 63;
     const int l31 = lane & 31, kk = lane >> 5;
     unsigned char* const As = smem + WF_BYTES + wave * A_BYTES;
-    float* const stage = reinterpret_cast<float*>(smem + WF_BYTES + NW * A_BYTES) + wave * (32 * 32);
+    const ChainTile tl{reinterpret_cast<float*>(smem + WF_BYTES + NW * A_BYTES) + wave * (32 * 32), lane};
     const float* const in = static_cast<const float*>(a.in);
     const _Float16* const w3 = static_cast<const _Float16*>(a.wgt);
     const _Float16* const w1 = static_cast<const _Float16*>(aq.wgt);
     const float* const res = static_cast<const float*>(a.res);
     float* const out = static_cast<float*>(a.out);
-    float* const outq = static_cast<float*>(aq.out);
     const _Float16* const wsc = static_cast<const _Float16*>(a.sc_wgt);
     const int swzb = (l31 >> 2) & 3;                     // filter rows in LDS: 16-B chunk c of row r at c ^ ((r >> 2) & 3)
     if constexpr (WLDS) {
@@ -97,16 +233,10 @@ __global__ __launch_bounds__(WLDS ? 512 : 256, WLDS ? 1 : 2) void k_conv_chain(c
     }
     bool out_of_range = false, out_of_range_q = false;
     for (int row0 = (blockIdx.x * NW + wave) * 32; row0 < a.M; row0 += gridDim.x * NW * 32) {
-    // ---- P's activation tile: -> LDS, or (WLDS) this lane's fragments straight into registers, split once (rows beyond M: zeros) ----
+    // ---- P's activation tile: -> LDS, or (C = 64) this lane's fragments straight into registers, split once (rows beyond M: zeros) ----
     ChainParts ap[WLDS ? 2 * KT : 1];
     if constexpr (WLDS) {
-        const int m = row0 + l31;
-#pragma unroll
-        for (int g = 0; g < 2 * KT; ++g) {
-            uint4 u0 = make_uint4(0u, 0u, 0u, 0u), u1 = u0;
-            if (m < a.M) { u0 = *reinterpret_cast<const uint4*>(in + (long)m * C + g * 16 + 8 * kk); u1 = *reinterpret_cast<const uint4*>(in + (long)m * C + g * 16 + 8 * kk + 4); }
-            ap[g] = chain_split<PARTS>(u0, u1);
-        }
+        chain_split_row<PARTS, false>(ap, in, row0, a.M, l31, kk);
     } else {
 #pragma unroll
         for (int it = 0; it < C / 8; ++it) {
@@ -123,12 +253,8 @@ __global__ __launch_bounds__(WLDS ? 512 : 256, WLDS ? 1 : 2) void k_conv_chain(c
     const int swz = (l31 >> 1) & 7;
     const unsigned char* const la = As + l31 * 128;
     const int ca0 = ((0 + 2 * kk) ^ swz) << 4, ca1 = ((1 + 2 * kk) ^ swz) << 4, ca2 = ((4 + 2 * kk) ^ swz) << 4, ca3 = ((5 + 2 * kk) ^ swz) << 4;
-    const int rrow = lane >> 3, c4 = (lane & 7) * 4;     // read-back: eight lanes per row, four passes of eight rows
-    const bool relu = a.act == ACT_RELU, reluq = aq.act == ACT_RELU;
-    bool ok[4];
-    long mrow[4];
-#pragma unroll
-    for (int ps = 0; ps < 4; ++ps) { const int m = row0 + 8 * ps + rrow; ok[ps] = m < a.M; mrow[ps] = m; }
+    const ChainRows rw = chain_rows(row0, a.M, lane);
+    const bool relu = a.act == ACT_RELU;
 
     // fused shortcut: this lane's pixel of the shortcut's input (a strided 1x1: no padding)
     const float* sc_row = nullptr;
@@ -142,7 +268,7 @@ __global__ __launch_bounds__(WLDS ? 512 : 256, WLDS ? 1 : 2) void k_conv_chain(c
         const int oh = rem / a.OW, ow = rem - oh * a.OW;
         sc_row = static_cast<const float*>(a.sc_in) + (long)b * a.sc_in_sB + (long)(oh * a.sc_stride) * a.sc_in_sH + (long)(ow * a.sc_stride) * a.sc_in_sW + 8 * kk;
     }
-    // WLDS: the lane's 64 shortcut-input channels, loaded once per tile (split again per column chunk: no registers for the parts)
+    // C = 64: the lane's 64 shortcut-input channels, loaded once per tile (split again per column chunk: no registers for the parts)
     uint4 xr[SC && WLDS ? C / 4 : 1];
     if constexpr (SC && WLDS) {
 #pragma unroll
@@ -153,28 +279,13 @@ __global__ __launch_bounds__(WLDS ? 512 : 256, WLDS ? 1 : 2) void k_conv_chain(c
     }
 
     f32x16 accQ[TNQ];
-#pragma unroll
-    for (int j = 0; j < TNQ; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) accQ[j][e] = 0.0f;
-
+    chain_zero(accQ);
     for (int nc = 0; nc < C4; nc += TNP * 32) {
-        // the residual of the chunk is requested before its K loop: every element the wave will overwrite, before its first store
-        float4 rv[TNP][4];
-        if constexpr (!SC) {
-#pragma unroll
-            for (int j = 0; j < TNP; ++j)
-#pragma unroll
-                for (int ps = 0; ps < 4; ++ps) {
-                    rv[j][ps] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (res && ok[ps]) rv[j][ps] = *reinterpret_cast<const float4*>(res + mrow[ps] * C4 + nc + j * 32 + c4);
-                }
-        }
+        float4 rv[TNP][4];                               // P's residual: loaded here, or (SC) formed piece by piece from the shortcut's sums
+        if constexpr (!SC) chain_residual(rv, res, rw, C4, nc);
         f32x16 accP[TNP], accS[TNP];
-#pragma unroll
-        for (int j = 0; j < TNP; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) { accP[j][e] = 0.0f; accS[j][e] = 0.0f; }
+        chain_zero(accP);
+        chain_zero(accS);
         // ---- P: K steps of 32 channels, two groups of 16 each ------------------------------------------------------
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt) {
@@ -212,80 +323,54 @@ __global__ __launch_bounds__(WLDS ? 512 : 256, WLDS ? 1 : 2) void k_conv_chain(c
         // ---- epilogue of the chunk, piece by piece; each piece is one K step of Q -------------------------------------
 #pragma unroll
         for (int j = 0; j < TNP; ++j) {
-            const int n = nc + j * 32 + c4;
-            float4 rj[4];
+            const int n = nc + j * 32 + rw.c4;
             if constexpr (SC) {
-                chain_stage_acc(stage, accS[j], l31, kk);
+                // the shortcut's piece: its sums -> the residual values of P's piece, with their watch
+                tl.put(accS[j]);
                 __builtin_amdgcn_wave_barrier();
-                const float4 sc2 = *reinterpret_cast<const float4*>(a.sc_scale + n), sh2 = *reinterpret_cast<const float4*>(a.sc_shift + n);
+                const float4 sc2 = chain_ld4(a.sc_scale + n), sh2 = chain_ld4(a.sc_shift + n);
 #pragma unroll
                 for (int ps = 0; ps < 4; ++ps) {
-                    float4 y = *reinterpret_cast<const float4*>(&stage[(8 * ps + rrow) * 32 + (((lane & 7) ^ rrow) << 2)]);
-                    y.x = y.x * sc2.x + sh2.x; y.y = y.y * sc2.y + sh2.y; y.z = y.z * sc2.z + sh2.z; y.w = y.w * sc2.w + sh2.w;
-                    out_of_range = out_of_range || !(fabsf(y.x) < 65504.0f) || !(fabsf(y.y) < 65504.0f) || !(fabsf(y.z) < 65504.0f) || !(fabsf(y.w) < 65504.0f);
-                    rj[ps] = y;
+                    rv[j][ps] = chain_scale_shift(tl.row_get(ps), sc2, sh2);
+                    out_of_range = out_of_range || chain_beyond_fp16(rv[j][ps]);
                 }
                 __builtin_amdgcn_wave_barrier();
-            } else {
-#pragma unroll
-                for (int ps = 0; ps < 4; ++ps) rj[ps] = rv[j][ps];
             }
-            chain_stage_acc(stage, accP[j], l31, kk);
+            // P's piece: scaled, shifted, + residual, activated, watched and stored; the tile is left holding y row-major for Q's step
+            tl.put(accP[j]);
             __builtin_amdgcn_wave_barrier();
-            const float4 sc = *reinterpret_cast<const float4*>(a.scale + n), sh = *reinterpret_cast<const float4*>(a.shift + n);
+            const float4 sc = chain_ld4(a.scale + n), sh = chain_ld4(a.shift + n);
             float4 xs[4];
 #pragma unroll
             for (int ps = 0; ps < 4; ++ps) {
-                float4 x = *reinterpret_cast<const float4*>(&stage[(8 * ps + rrow) * 32 + (((lane & 7) ^ rrow) << 2)]);
-                x.x = x.x * sc.x + sh.x; x.y = x.y * sc.y + sh.y; x.z = x.z * sc.z + sh.z; x.w = x.w * sc.w + sh.w;
-                if (SC || res) { x.x += rj[ps].x; x.y += rj[ps].y; x.z += rj[ps].z; x.w += rj[ps].w; }
-                if (relu) { x.x = fmaxf(x.x, 0.f); x.y = fmaxf(x.y, 0.f); x.z = fmaxf(x.z, 0.f); x.w = fmaxf(x.w, 0.f); }
-                if (ok[ps]) {
-                    out_of_range = out_of_range || !(fabsf(x.x) < 65504.0f) || !(fabsf(x.y) < 65504.0f) || !(fabsf(x.z) < 65504.0f) || !(fabsf(x.w) < 65504.0f);
-                    *reinterpret_cast<float4*>(out + mrow[ps] * C4 + n) = x;
+                float4 x = chain_scale_shift(tl.row_get(ps), sc, sh);
+                if (SC || res) x = chain_add(x, rv[j][ps]);
+                if (relu) x = chain_relu(x);
+                if (rw.ok[ps]) {
+                    out_of_range = out_of_range || chain_beyond_fp16(x);
+                    *reinterpret_cast<float4*>(out + rw.mrow[ps] * C4 + n) = x;
                 }
                 xs[ps] = x;
             }
             __builtin_amdgcn_wave_barrier();
-            // the stored values, back in place: the tile now holds y row-major (same swizzle)
 #pragma unroll
-            for (int ps = 0; ps < 4; ++ps) *reinterpret_cast<float4*>(&stage[(8 * ps + rrow) * 32 + (((lane & 7) ^ rrow) << 2)]) = xs[ps];
+            for (int ps = 0; ps < 4; ++ps) tl.row_put(ps, xs[ps]);
             __builtin_amdgcn_wave_barrier();
             // ---- Q: the K step of channels nc + 32 j .. + 31 ---------------------------------------------------------
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
-                const uint4 u0 = *reinterpret_cast<const uint4*>(&stage[l31 * 32 + (((4 * g + 2 * kk) ^ (l31 & 7)) << 2)]);
-                const uint4 u1 = *reinterpret_cast<const uint4*>(&stage[l31 * 32 + (((4 * g + 2 * kk + 1) ^ (l31 & 7)) << 2)]);
                 uint4 bq[TNQ];
 #pragma unroll
                 for (int jq = 0; jq < TNQ; ++jq) {
                     if constexpr (WLDS) bq[jq] = *reinterpret_cast<const uint4*>(smem + W_BYTES + ((nc / 32 + j) * C + jq * 32 + l31) * 64 + (((2 * g + kk) ^ swzb) << 4));
                     else bq[jq] = *reinterpret_cast<const uint4*>(w1 + (long)(jq * 32 + l31) * C4 + nc + j * 32 + g * 16 + 8 * kk);
                 }
-                chain_mfma_parts<PARTS, TNQ>(accQ, bq, chain_split<PARTS>(u0, u1));
+                chain_mfma_parts<PARTS, TNQ>(accQ, bq, tl.template frag<PARTS>(g));
             }
             __builtin_amdgcn_wave_barrier();
         }
     }
-    // ---- Q's epilogue: scale / shift, ReLU, watch, full-line stores ------------------------------------------------------
-#pragma unroll
-    for (int jq = 0; jq < TNQ; ++jq) {
-        const int n = jq * 32 + c4;
-        chain_stage_acc(stage, accQ[jq], l31, kk);
-        __builtin_amdgcn_wave_barrier();
-        const float4 sc = *reinterpret_cast<const float4*>(aq.scale + n), sh = *reinterpret_cast<const float4*>(aq.shift + n);
-#pragma unroll
-        for (int ps = 0; ps < 4; ++ps) {
-            float4 x = *reinterpret_cast<const float4*>(&stage[(8 * ps + rrow) * 32 + (((lane & 7) ^ rrow) << 2)]);
-            x.x = x.x * sc.x + sh.x; x.y = x.y * sc.y + sh.y; x.z = x.z * sc.z + sh.z; x.w = x.w * sc.w + sh.w;
-            if (reluq) { x.x = fmaxf(x.x, 0.f); x.y = fmaxf(x.y, 0.f); x.z = fmaxf(x.z, 0.f); x.w = fmaxf(x.w, 0.f); }
-            if (ok[ps]) {
-                out_of_range_q = out_of_range_q || !(fabsf(x.x) < 65504.0f) || !(fabsf(x.y) < 65504.0f) || !(fabsf(x.z) < 65504.0f) || !(fabsf(x.w) < 65504.0f);
-                *reinterpret_cast<float4*>(outq + mrow[ps] * C + n) = x;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
+    chain_epilogue_q(tl, accQ, aq.scale, aq.shift, aq.act == ACT_RELU, rw, static_cast<float*>(aq.out), out_of_range_q);
     }          // (the wave's next 32-row tile)
     if (a.range_flag && out_of_range) atomicOr(a.range_flag, 1);
     if (aq.range_flag && out_of_range_q) atomicOr(aq.range_flag, 1);
@@ -298,8 +383,8 @@ __global__ __launch_bounds__(WLDS ? 512 : 256, WLDS ? 1 : 2) void k_conv_chain(c
 // 1 KB per wave and chunk).  One block barrier per chunk hands a stage over: behind it every wave has its share of chunk i landed
 // (vmcnt(0) in front of it) and has finished reading chunk i - 1, whose stage the DMAs of chunk i + 1 then overwrite while chunk i is
 // multiplied.  EVERY wave reaches every barrier and issues its share of every DMA: a wave whose 32 rows lie beyond M skips loads, MFMAs
-// and stores, never a ring step.  P's activation fragments are split once into registers (the C = 64 form's method: 16 groups x PARTS
-// fragments); the sums, the epilogue pieces and Q's steps are the other forms', expression for expression.  Nothing crosses blocks.
+// and stores, never a ring step.  One wave per SIMD: only the wave's own instruction stream hides a read, so the scale / shift tables
+// lie in LDS and every filter fragment is requested one group (P) or half a group (Q) ahead of the MFMAs it feeds.  Nothing crosses blocks.
 template <int C, int PARTS>
 __global__ __launch_bounds__(256, 1) void k_conv_chain_ring(const ChainArgs ca)
 {
@@ -309,21 +394,19 @@ __global__ __launch_bounds__(256, 1) void k_conv_chain_ring(const ChainArgs ca)
     constexpr int STAGE = 2 * WCH;
     constexpr int NDMA = WCH / 4096;                     // DMAs per thread, chunk and layer: 256 lanes x 16 B each
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE + 4 * 32 * 32 * 4];
-    __shared__ __attribute__((aligned(16))) float s_tab[2 * C4], s_tabq[2 * C];       // scale | shift of P's and of Q's columns: one wave per SIMD hides no global load inside an epilogue
+    __shared__ __attribute__((aligned(16))) float s_tab[2 * C4], s_tabq[2 * C];       // scale | shift of P's and of Q's columns
     const ConvArgs& a = ca.p;
     const ConvArgs& aq = ca.q;
     const int t = threadIdx.x;
     const int wave = t >> 6, lane = t & 63;
     const int l31 = lane & 31, kk = lane >> 5;
-    float* const stage = reinterpret_cast<float*>(smem + 2 * STAGE) + wave * (32 * 32);
+    const ChainTile tl{reinterpret_cast<float*>(smem + 2 * STAGE) + wave * (32 * 32), lane};
     static_assert(C4 == 4 * 256 && C % 8 == 0 && C / 2 <= 256, "the tables are filled by 256 threads, 16 B each");
-    *reinterpret_cast<float4*>(&s_tab[4 * t]) = *reinterpret_cast<const float4*>(a.scale + 4 * t);
-    *reinterpret_cast<float4*>(&s_tab[C4 + 4 * t]) = *reinterpret_cast<const float4*>(a.shift + 4 * t);
-    if (t < C / 2) *reinterpret_cast<float4*>(&s_tabq[4 * t]) = *reinterpret_cast<const float4*>(t < C / 4 ? aq.scale + 4 * t : aq.shift + 4 * (t - C / 4));      // (read behind the first ring barrier)
-    const float* const in = static_cast<const float*>(a.in);
+    *reinterpret_cast<float4*>(&s_tab[4 * t]) = chain_ld4(a.scale + 4 * t);
+    *reinterpret_cast<float4*>(&s_tab[C4 + 4 * t]) = chain_ld4(a.shift + 4 * t);
+    if (t < C / 2) *reinterpret_cast<float4*>(&s_tabq[4 * t]) = chain_ld4(t < C / 4 ? aq.scale + 4 * t : aq.shift + 4 * (t - C / 4));      // (read behind the first ring barrier)
     const float* const res = static_cast<const float*>(a.res);
     float* const out = static_cast<float*>(a.out);
-    float* const outq = static_cast<float*>(aq.out);
     const int swzb = (l31 >> 2) & 3;                     // filter rows in LDS: 16-B chunk c of row r at c ^ ((r >> 2) & 3)
 
     // ---- the ring's DMA: buffer resources over the two images (a lane beyond them would deposit zeros), inline asm as in kernels_conv.hip ----
@@ -360,35 +443,13 @@ __global__ __launch_bounds__(256, 1) void k_conv_chain_ring(const ChainArgs ca)
     const int row0 = (blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(wave)) * 32;
     const bool live = row0 < a.M;                        // (wave-uniform) a wave without rows keeps the ring going and does nothing else
     bool out_of_range = false, out_of_range_q = false;
-    // P's activation fragments of this lane, split once (rows beyond M: zeros)
-    // (every request leaves before the first split: a lane beyond M reads the wave's first row and zeroes what it got)
     ChainParts ap[2 * KT];
-    if (live) {
-        const int m = row0 + l31;
-        const bool m_ok = m < a.M;
-        const float* const src = in + (long)(m_ok ? m : row0) * C + 8 * kk;
-        uint4 u[2 * KT][2];
-#pragma unroll
-        for (int g = 0; g < 2 * KT; ++g) { u[g][0] = *reinterpret_cast<const uint4*>(src + g * 16); u[g][1] = *reinterpret_cast<const uint4*>(src + g * 16 + 4); }
-#pragma unroll
-        for (int g = 0; g < 2 * KT; ++g) {
-            if (!m_ok) u[g][0] = u[g][1] = make_uint4(0u, 0u, 0u, 0u);
-            ap[g] = chain_split<PARTS>(u[g][0], u[g][1]);
-        }
-    }
+    if (live) chain_split_row<PARTS, true>(ap, static_cast<const float*>(a.in), row0, a.M, l31, kk);
     const bool full = row0 + 32 <= a.M;                  // (wave-uniform) the wave issues every load and store of a chunk
-    const int rrow = lane >> 3, c4 = (lane & 7) * 4;     // read-back: eight lanes per row, four passes of eight rows
-    const bool relu = a.act == ACT_RELU, reluq = aq.act == ACT_RELU;
-    bool ok[4];
-    long mrow[4];
-#pragma unroll
-    for (int ps = 0; ps < 4; ++ps) { const int m = row0 + 8 * ps + rrow; ok[ps] = m < a.M; mrow[ps] = m; }
-
+    const ChainRows rw = chain_rows(row0, a.M, lane);
+    const bool relu = a.act == ACT_RELU;
     f32x16 accQ[TNQ];
-#pragma unroll
-    for (int j = 0; j < TNQ; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) accQ[j][e] = 0.0f;
+    chain_zero(accQ);
 
     for (int ch = 0; ch < NCH; ++ch) {
         // chunk ch has landed for every wave, and every wave has left chunk ch - 1: its stage takes chunk ch + 1
@@ -402,22 +463,11 @@ __global__ __launch_bounds__(256, 1) void k_conv_chain_ring(const ChainArgs ca)
         const unsigned char* const w3s = smem + (ch & 1) * STAGE;          // [K step][64 rows][64 B]
         const unsigned char* const w1s = w3s + WCH;                        // [2 K steps][C rows][64 B]
         const int nc = ch * 64;
-        // the residual of the chunk is requested before its K loop: every element the wave will overwrite, before its first store
         float4 rv[TNP][4];
-#pragma unroll
-        for (int j = 0; j < TNP; ++j)
-#pragma unroll
-            for (int ps = 0; ps < 4; ++ps) {
-                rv[j][ps] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (res && ok[ps]) rv[j][ps] = *reinterpret_cast<const float4*>(res + mrow[ps] * C4 + nc + j * 32 + c4);
-            }
+        chain_residual(rv, res, rw, C4, nc);
         f32x16 accP[TNP];
-#pragma unroll
-        for (int j = 0; j < TNP; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) accP[j][e] = 0.0f;
-        // ---- P: K steps of 32 channels, two groups of 16 each ------------------------------------------------------
-        // (one wave per SIMD: only the wave's own stream hides an LDS read, so group i + 1's filter fragments are requested ahead of group i's MFMAs)
+        chain_zero(accP);
+        // ---- P: K steps of 32 channels, two groups of 16 each; group i + 1's filter fragments are requested ahead of group i's MFMAs ----
         auto frag_p = [&](uint4 (&b)[TNP], int i) {
 #pragma unroll
             for (int j = 0; j < TNP; ++j) b[j] = *reinterpret_cast<const uint4*>(w3s + ((i >> 1) * 64 + j * 32 + l31) * 64 + (((2 * (i & 1) + kk) ^ swzb) << 4));
@@ -445,43 +495,16 @@ __global__ __launch_bounds__(256, 1) void k_conv_chain_ring(const ChainArgs ca)
         // ---- epilogue of the chunk, piece by piece; each piece is one K step of Q -------------------------------------
 #pragma unroll
         for (int j = 0; j < TNP; ++j) {
-            const int n = nc + j * 32 + c4;
+            const int n = nc + j * 32 + rw.c4;
             uint4 bq[TNQ / 2];
             frag_q(bq, j, 0);                              // (independent of the epilogue: on its way meanwhile)
-            chain_stage_acc(stage, accP[j], l31, kk);
-            __builtin_amdgcn_wave_barrier();
-            const float4 sc = *reinterpret_cast<const float4*>(&s_tab[n]), sh = *reinterpret_cast<const float4*>(&s_tab[C4 + n]);
-            float4 xs[4];
-#pragma unroll
-            for (int ps = 0; ps < 4; ++ps) xs[ps] = *reinterpret_cast<const float4*>(&stage[(8 * ps + rrow) * 32 + (((lane & 7) ^ rrow) << 2)]);      // (all four reads ahead of the row tests: one LDS wait)
-#pragma unroll
-            for (int ps = 0; ps < 4; ++ps) {
-                float4 x = xs[ps];
-                x.x = x.x * sc.x + sh.x; x.y = x.y * sc.y + sh.y; x.z = x.z * sc.z + sh.z; x.w = x.w * sc.w + sh.w;
-                if (res) { x.x += rv[j][ps].x; x.y += rv[j][ps].y; x.z += rv[j][ps].z; x.w += rv[j][ps].w; }
-                if (relu) { x.x = fmaxf(x.x, 0.f); x.y = fmaxf(x.y, 0.f); x.z = fmaxf(x.z, 0.f); x.w = fmaxf(x.w, 0.f); }
-                if (ok[ps]) {
-                    out_of_range = out_of_range || !(fabsf(x.x) < 65504.0f) || !(fabsf(x.y) < 65504.0f) || !(fabsf(x.z) < 65504.0f) || !(fabsf(x.w) < 65504.0f);
-                    *reinterpret_cast<float4*>(out + mrow[ps] * C4 + n) = x;
-                }
-                xs[ps] = x;
-            }
-            __builtin_amdgcn_wave_barrier();
-            // the stored values, back in place: the tile now holds y row-major (same swizzle)
-#pragma unroll
-            for (int ps = 0; ps < 4; ++ps) *reinterpret_cast<float4*>(&stage[(8 * ps + rrow) * 32 + (((lane & 7) ^ rrow) << 2)]) = xs[ps];
-            __builtin_amdgcn_wave_barrier();
+            chain_piece_p(tl, accP[j], s_tab, s_tab + C4, rv[j], res != nullptr, relu, rw, out, C4, n, out_of_range);
             // ---- Q: the K step of channels nc + 32 j .. + 31 ---------------------------------------------------------
             // (per accumulator the order is the other forms': group 0's parts, then group 1's; the halves only stagger the fragment reads)
             ChainParts pt;
 #pragma unroll
             for (int h = 0; h < 4; ++h) {
-                if ((h & 1) == 0) {
-                    const int g = h >> 1;
-                    const uint4 u0 = *reinterpret_cast<const uint4*>(&stage[l31 * 32 + (((4 * g + 2 * kk) ^ (l31 & 7)) << 2)]);
-                    const uint4 u1 = *reinterpret_cast<const uint4*>(&stage[l31 * 32 + (((4 * g + 2 * kk + 1) ^ (l31 & 7)) << 2)]);
-                    pt = chain_split<PARTS>(u0, u1);
-                }
+                if ((h & 1) == 0) pt = tl.template frag<PARTS>(h >> 1);
                 uint4 bn[TNQ / 2];
                 if (h < 3) frag_q(bn, j, h + 1);
                 __builtin_amdgcn_sched_barrier(0);
@@ -497,62 +520,37 @@ __global__ __launch_bounds__(256, 1) void k_conv_chain_ring(const ChainArgs ca)
     }
 #undef MRCNN_RING_DMA
     // (no barrier follows: a wave without rows is done)
-    if (live) {
-        // ---- Q's epilogue: scale / shift, ReLU, watch, full-line stores ------------------------------------------------------
-#pragma unroll
-        for (int jq = 0; jq < TNQ; ++jq) {
-            const int n = jq * 32 + c4;
-            chain_stage_acc(stage, accQ[jq], l31, kk);
-            __builtin_amdgcn_wave_barrier();
-            const float4 sc = *reinterpret_cast<const float4*>(&s_tabq[n]), sh = *reinterpret_cast<const float4*>(&s_tabq[C + n]);
-#pragma unroll
-            for (int ps = 0; ps < 4; ++ps) {
-                float4 x = *reinterpret_cast<const float4*>(&stage[(8 * ps + rrow) * 32 + (((lane & 7) ^ rrow) << 2)]);
-                x.x = x.x * sc.x + sh.x; x.y = x.y * sc.y + sh.y; x.z = x.z * sc.z + sh.z; x.w = x.w * sc.w + sh.w;
-                if (reluq) { x.x = fmaxf(x.x, 0.f); x.y = fmaxf(x.y, 0.f); x.z = fmaxf(x.z, 0.f); x.w = fmaxf(x.w, 0.f); }
-                if (ok[ps]) {
-                    out_of_range_q = out_of_range_q || !(fabsf(x.x) < 65504.0f) || !(fabsf(x.y) < 65504.0f) || !(fabsf(x.z) < 65504.0f) || !(fabsf(x.w) < 65504.0f);
-                    *reinterpret_cast<float4*>(outq + mrow[ps] * C + n) = x;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
+    if (live) chain_epilogue_q(tl, accQ, s_tabq, s_tabq + C, aq.act == ACT_RELU, rw, static_cast<float*>(aq.out), out_of_range_q);
     if (a.range_flag && out_of_range) atomicOr(a.range_flag, 1);
     if (aq.range_flag && out_of_range_q) atomicOr(aq.range_flag, 1);
 }
 
+typedef void (*chain_kernel_t)(const ChainArgs);
+template <int PARTS>
+static chain_kernel_t chain_kernel(int C, bool sc)
+{
+    if (C == 256) return k_conv_chain_ring<256, PARTS>;
+    if (C == 64) return sc ? k_conv_chain<64, PARTS, true> : k_conv_chain<64, PARTS, false>;
+    return sc ? k_conv_chain<128, PARTS, true> : k_conv_chain<128, PARTS, false>;
+}
+
 // p / q: the launch arguments of the two layers (conv_dispatch.hip has checked the pair: conv_chain_fusable); parts 2 | 3
-// wlds: the LDS-resident persistent form (C = 64 with a 64-channel shortcut or none); n_cus sizes its grid
-// p_stream / q_stream: the layers' stream images (C = 256: the ring form, identity pairs only)
-void conv_chain_launch(hipStream_t s, const ConvArgs& p, const ConvArgs& q, int parts, bool wlds, int n_cus, const void* p_stream, const void* q_stream)
+// the form follows from C = q.Cout: 64 — LDS-resident and persistent (a 64-channel shortcut or none; n_cus sizes its grid), 128 — filters from L2,
+// 256 — the ring (identity pairs only, from p_stream / q_stream: the layers' stream images)
+void conv_chain_launch(hipStream_t s, const ConvArgs& p, const ConvArgs& q, int parts, int n_cus, const void* p_stream, const void* q_stream)
 {
     ChainArgs ca{p, q, p_stream, q_stream};
     dim3 grid((p.M + 127) / 128), block(256);
     const bool sc = p.sc_in != nullptr;
     const int C = q.Cout;
     MRCNN_REQUIRE((C == 64 || C == 128 || C == 256) && (parts == 2 || parts == 3), MRCNN_ERR_INVALID, "conv_chain_launch: C %d, %d parts", C, parts);
-    if (C == 256) {
-        MRCNN_REQUIRE(!wlds && !sc && p.res && p_stream && q_stream, MRCNN_ERR_INVALID, "conv_chain_launch: C = 256 runs identity pairs from their stream images");
-        if (parts == 3) hipLaunchKernelGGL((k_conv_chain_ring<256, 3>), grid, block, 0, s, ca);
-        else hipLaunchKernelGGL((k_conv_chain_ring<256, 2>), grid, block, 0, s, ca);
-        return;
-    }
-    if (wlds) {
-        MRCNN_REQUIRE(C == 64 && (!sc || p.sc_Cin == 64) && n_cus > 0, MRCNN_ERR_INVALID, "conv_chain_launch: the LDS-resident form holds C = 64's filters");
+    if (C == 256) MRCNN_REQUIRE(!sc && p.res && p_stream && q_stream, MRCNN_ERR_INVALID, "conv_chain_launch: C = 256 runs identity pairs from their stream images");
+    if (C == 64) {
+        MRCNN_REQUIRE((!sc || p.sc_Cin == 64) && n_cus > 0, MRCNN_ERR_INVALID, "conv_chain_launch: the LDS-resident form holds C = 64's filters");
         const int tiles256 = (p.M + 255) / 256;
         grid = dim3(tiles256 < n_cus ? tiles256 : n_cus); block = dim3(512);
-#define MRCNN_CHAIN_W(P_, S_) hipLaunchKernelGGL((k_conv_chain<64, P_, S_, true>), grid, block, 0, s, ca)
-        if (parts == 3) { if (sc) MRCNN_CHAIN_W(3, true); else MRCNN_CHAIN_W(3, false); }
-        else { if (sc) MRCNN_CHAIN_W(2, true); else MRCNN_CHAIN_W(2, false); }
-#undef MRCNN_CHAIN_W
-        return;
     }
-    MRCNN_REQUIRE(C == 128, MRCNN_ERR_INVALID, "conv_chain_launch: C = 64 runs the LDS-resident form");
-#define MRCNN_CHAIN(C_, P_, S_) hipLaunchKernelGGL((k_conv_chain<C_, P_, S_, false>), grid, block, 0, s, ca)
-    if (parts == 3) { if (sc) MRCNN_CHAIN(128, 3, true); else MRCNN_CHAIN(128, 3, false); }
-    else { if (sc) MRCNN_CHAIN(128, 2, true); else MRCNN_CHAIN(128, 2, false); }
-#undef MRCNN_CHAIN
+    hipLaunchKernelGGL(parts == 3 ? chain_kernel<3>(C, sc) : chain_kernel<2>(C, sc), grid, block, 0, s, ca);
 }
 
 }  // namespace mrcnn

@@ -81,6 +81,17 @@ def ref64(case, y_gpu):
 # C, B, H, W, entry form — M = 288: two full 128-row tiles and a ragged one, a tile across the image boundary; M = 64: less than a tile;
 # the entry forms of C2 (stride-1 shortcut, 64 channels) and C3 (stride-2 shortcut from 256 channels at 24 x 24)
 CASES = [(64, 2, 12, 12, False), (128, 2, 12, 12, False), (64, 1, 8, 8, False), (128, 1, 8, 8, False), (64, 2, 12, 12, True), (128, 2, 12, 12, True)]
+# the C = 64 form is persistent: one block of eight waves per CU, a wave walks 32-row tiles 256 rows x the grid apart.  H = W = None: a square sized
+# on the device so that some waves take a SECOND tile and the last one is ragged (what a wave carries from one tile into the next: Q's sums, the LDS
+# tile, the watch); bit-identity only — the small cases hold the two launches against float64
+SECOND_TILE = (64, 1, None, None, False)
+
+
+def _second_tile_side():
+    """H = W with H * W between 256 and 1024 rows beyond one 256-row tile per CU and no multiple of 32 (256 CUs: 257 x 257 = 66049 rows)"""
+    import torch
+    rows = 256 * torch.cuda.get_device_properties(0).multi_processor_count
+    return next(s for s in range(1, 1 << 15) if rows + 256 <= s * s <= rows + 1024 and (s * s) % 32)
 
 
 @functools.lru_cache(maxsize=None)
@@ -102,8 +113,10 @@ def _same_bits(a, b, what):
 
 @pytest.mark.parametrize("in_place", [0, 1])
 @pytest.mark.parametrize("dtype", ["f32x3", "f32s"])
-@pytest.mark.parametrize("C,B,H,W,entry", CASES)
+@pytest.mark.parametrize("C,B,H,W,entry", CASES + [SECOND_TILE])
 def test_chained_equals_the_two_launches_bitwise(C, B, H, W, entry, dtype, in_place):
+    if H is None:
+        H = W = _second_tile_side()
     y0, t0, f0 = _two_launches(C, B, H, W, entry, dtype, in_place)
     y1, t1, f1 = chain(_case(C, B, H, W, entry), dtype, True, in_place)
     assert np.isfinite(y1).all() and np.isfinite(t1).all()
