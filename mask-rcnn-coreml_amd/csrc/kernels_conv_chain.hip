@@ -10,19 +10,20 @@
 //   * ChainTile — the wave-private 32 x 32 LDS tile of conv_epilogue_wave: accumulators in (put), rows out and back (row_get /
 //     row_put), Q's activation fragments out (frag);
 //   * chain_scale_shift, chain_add, chain_relu, chain_beyond_fp16 — conv_epilogue_wave's expressions on four adjacent columns (scale /
-//     shift, + residual — loaded by chain_residual, or formed from the shortcut's sums —, ReLU, the fp16-range watch);
-//   * chain_piece_p — one 32 x 32 piece of P through them, stored, and left in the tile as y: the stored fp32 values, which Q's step
+//     shift, + residual — loaded by chain_residual / chain_residual_piece, or formed from the shortcut's sums —, ReLU, the fp16-range watch);
+//   * chain_piece_p (the ring form's) — one 32 x 32 piece of P through them, stored, and left in the tile as y: the stored fp32 values, which Q's step
 //     splits by split_hi_mid_lo / split_hi_lo and multiplies into Q's accumulators: one running sum per output, channel groups
 //     ascending — Q's own order.  k_conv_chain spells the piece (and the shortcut's, which only it has) out of the same primitives in
 //     its body: called as a function it costs k_conv_chain<64, 3, SC>, which sits at its 256 registers, 12 B of scratch;
 //   * chain_epilogue_q — Q's epilogue: the same piece without a residual.
-// What a kernel body adds is where its FILTERS come from.  The waves of a block share no pixel: nothing
-// synchronises them inside the loop but, in the ring form, the hand-over of its filter stages.
+// What a kernel body adds is where its FILTERS come from.  In k_conv_chain the waves of a block share no pixel and nothing
+// synchronises them inside the loop; in the ring form two waves share 32 rows and split the work by role, and one block barrier per piece hands
+// filter stages and P's sums over.
 //   * k_conv_chain<64>: every filter of the launch resident in LDS, one persistent block of eight waves per CU — what
 //     conv_forward_chain runs for C2;
 //   * k_conv_chain<128>: P's activation tile (32 rows x C fp32 per wave) in LDS in the 128-row kernel's swizzled layout, both layers'
 //     filter fragments straight from L2 (16 B per lane) — measured slower than the two launches, kept as the tests' bit-identity anchor;
-//   * k_conv_chain_ring<256>: both layers' filters streamed chunk by chunk through a block-shared LDS ring — what runs for C4.
+//   * k_conv_chain_ring<256>: both layers' filters streamed through block-shared LDS stages, eight waves in two roles — what runs for C4.
 #include "conv_device.h"
 
 namespace mrcnn {
@@ -62,21 +63,17 @@ __device__ __forceinline__ ChainParts chain_split(const uint4 u0, const uint4 u1
     return p;
 }
 // this lane's activation fragments of P (pixel row0 + l31, NG groups of 16 channels), split once into registers (rows beyond M: zeros)
-// AHEAD (the ring form: one wave per SIMD, nothing else hides a request): every request leaves before the first split — a lane beyond M reads
-// the wave's first row and zeroes what it got; otherwise such a lane requests nothing (measured: C = 64 without a shortcut is 0.4 % slower AHEAD)
-template <int PARTS, bool AHEAD, int NG>
+template <int PARTS, int NG>
 __device__ __forceinline__ void chain_split_row(ChainParts (&ap)[NG], const float* in, int row0, int M, int l31, int kk)
 {
     const int m = row0 + l31;
     const bool m_ok = m < M;
     const float* const src = in + (long)(m_ok ? m : row0) * (NG * 16) + 8 * kk;
     uint4 u[NG][2];
-    if constexpr (AHEAD)
-        _Pragma("unroll") for (int g = 0; g < NG; ++g) { u[g][0] = *reinterpret_cast<const uint4*>(src + g * 16); u[g][1] = *reinterpret_cast<const uint4*>(src + g * 16 + 4); }
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
-        if (!AHEAD || !m_ok) u[g][0] = u[g][1] = make_uint4(0u, 0u, 0u, 0u);
-        if (!AHEAD && m_ok) { u[g][0] = *reinterpret_cast<const uint4*>(src + g * 16); u[g][1] = *reinterpret_cast<const uint4*>(src + g * 16 + 4); }
+        u[g][0] = u[g][1] = make_uint4(0u, 0u, 0u, 0u);
+        if (m_ok) { u[g][0] = *reinterpret_cast<const uint4*>(src + g * 16); u[g][1] = *reinterpret_cast<const uint4*>(src + g * 16 + 4); }
         ap[g] = chain_split<PARTS>(u[g][0], u[g][1]);
     }
 }
@@ -136,30 +133,49 @@ __device__ __forceinline__ void chain_residual(float4 (&rv)[2][4], const float* 
             if (res && rw.ok[ps]) rv[j][ps] = chain_ld4(res + rw.mrow[ps] * pitch + nc + j * 32 + rw.c4);
         }
 }
-// one 32 x 32 piece of P: columns n .. n + 3 of this lane's four rows, scaled and shifted (scale / shift: the tables, in memory or in LDS), + r,
-// activated, watched and stored; the tile is left holding y row-major (the stored values, same swizzle) for Q's step
-// (all four tile reads ahead of the row tests: one LDS wait)
-__device__ __forceinline__ void chain_piece_p(const ChainTile& tl, const f32x16& acc, const float* scale, const float* shift, const float4 (&r)[4], bool has_res, bool relu,
-                                              const ChainRows& rw, float* out, int pitch, int n, bool& out_of_range)
+// the ring form's view of the same rows, cheap in registers: the byte offset of (row, column c4) from the wave's first row in a tensor of `pitch`
+// floats per row — a wave-uniform base pointer takes the rest.  A row beyond M is pointed at the wave's first row: its requests stay inside the
+// tensor, nothing of it is stored or watched, and no other row's sums see it
+struct ChainRowOffs { bool ok[4]; unsigned off[4]; };
+__device__ __forceinline__ ChainRowOffs chain_row_offs(int row0, int M, int lane, int pitch)
 {
-    tl.put(acc);
-    __builtin_amdgcn_wave_barrier();
+    ChainRowOffs ro;
+#pragma unroll
+    for (int ps = 0; ps < 4; ++ps) {
+        const int r = 8 * ps + (lane >> 3);
+        ro.ok[ps] = row0 + r < M;
+        ro.off[ps] = (unsigned)((ro.ok[ps] ? r : 0) * pitch + (lane & 7) * 4) * 4u;
+    }
+    return ro;
+}
+// the residual of ONE 32-column piece (res: the piece's first column in the wave's first row), this lane's four rows, requested a whole piece
+// ahead: every element the wave will overwrite, before the wave's store to it.  Four unconditional requests
+__device__ __forceinline__ void chain_residual_piece(float4 (&rv)[4], const float* res, const ChainRowOffs& ro)
+{
+#pragma unroll
+    for (int ps = 0; ps < 4; ++ps) rv[ps] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(res) + ro.off[ps]);
+}
+// one 32 x 32 piece of P whose sums lie in the tile (ChainTile::put): columns n .. n + 3 of this lane's four rows, scaled and shifted (the tables in LDS), + r,
+// activated, watched and stored (out: the piece's first column in the wave's first row); the tile is left holding y row-major (the stored values, same swizzle) for Q's step.  A lane rewrites exactly the
+// elements it read.  FULL (no row lies beyond M) is straight-line code
+template <bool FULL, bool RELU>
+__device__ __forceinline__ void chain_piece_p(const ChainTile& tl, const float* scale, const float* shift, const float4 (&r)[4], const ChainRowOffs& ro, float* out, int n,
+                                              bool& out_of_range)
+{
     const float4 sc = chain_ld4(scale + n), sh = chain_ld4(shift + n);
     float4 xs[4];
 #pragma unroll
     for (int ps = 0; ps < 4; ++ps) xs[ps] = tl.row_get(ps);
 #pragma unroll
     for (int ps = 0; ps < 4; ++ps) {
-        float4 x = chain_scale_shift(xs[ps], sc, sh);
-        if (has_res) x = chain_add(x, r[ps]);
-        if (relu) x = chain_relu(x);
-        if (rw.ok[ps]) {
-            out_of_range = out_of_range || chain_beyond_fp16(x);
-            *reinterpret_cast<float4*>(out + rw.mrow[ps] * pitch + n) = x;
+        float4 x = chain_add(chain_scale_shift(xs[ps], sc, sh), r[ps]);
+        if (RELU) x = chain_relu(x);
+        if (FULL || ro.ok[ps]) {
+            out_of_range |= chain_beyond_fp16(x);
+            *reinterpret_cast<float4*>(reinterpret_cast<char*>(out) + ro.off[ps]) = x;
         }
         xs[ps] = x;
     }
-    __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int ps = 0; ps < 4; ++ps) tl.row_put(ps, xs[ps]);
     __builtin_amdgcn_wave_barrier();
@@ -236,7 +252,7 @@ __global__ __launch_bounds__(C == 64 ? 512 : 256, C == 64 ? 1 : 2) void k_conv_c
     // ---- P's activation tile: -> LDS, or (C = 64) this lane's fragments straight into registers, split once (rows beyond M: zeros) ----
     ChainParts ap[WLDS ? 2 * KT : 1];
     if constexpr (WLDS) {
-        chain_split_row<PARTS, false>(ap, in, row0, a.M, l31, kk);
+        chain_split_row<PARTS>(ap, in, row0, a.M, l31, kk);
     } else {
 #pragma unroll
         for (int it = 0; it < C / 8; ++it) {
@@ -376,154 +392,229 @@ __global__ __launch_bounds__(C == 64 ? 512 : 256, C == 64 ? 1 : 2) void k_conv_c
     if (aq.range_flag && out_of_range_q) atomicOr(aq.range_flag, 1);
 }
 
-// The ring form (C = 256: C4's identity pairs).  W3 and W1 are 512 KB each: neither LDS residency nor per-lane L2 fetches serve.  The
-// block's four waves (one per SIMD, 32 rows each, 128 rows per block) share a ring of two LDS stages; per 64-column chunk of P a stage
-// holds the chunk's 32 KB of W3 (64 rows x K 256) and its 32 KB of W1 (256 rows x 64 of Q's channels), copied by LDS-DMA from the layers'
-// stream images (conv_pack.h: pack_chain_stream — the chunk images lie in memory in their LDS layout, so the copy is straight: 16 DMAs of
-// 1 KB per wave and chunk).  One block barrier per chunk hands a stage over: behind it every wave has its share of chunk i landed
-// (vmcnt(0) in front of it) and has finished reading chunk i - 1, whose stage the DMAs of chunk i + 1 then overwrite while chunk i is
-// multiplied.  EVERY wave reaches every barrier and issues its share of every DMA: a wave whose 32 rows lie beyond M skips loads, MFMAs
-// and stores, never a ring step.  One wave per SIMD: only the wave's own instruction stream hides a read, so the scale / shift tables
-// lie in LDS and every filter fragment is requested one group (P) or half a group (Q) ahead of the MFMAs it feeds.  Nothing crosses blocks.
+// The ring form (C = 256: C4's identity pairs).  W3 and W1 are 512 KB each: neither LDS residency nor per-lane L2 fetches serve, so both
+// layers' filters are streamed through LDS by LDS-DMA from the layers' stream images (conv_pack.h: pack_chain_stream — the chunk images lie in
+// memory in their LDS layout, so every copy is straight).  A block owns 128 rows and has EIGHT waves, two per SIMD: the two waves of a SIMD
+// (a pair: waves p and p + 4) own the same 32 rows and split the work by role, so that one's epilogue runs while the other's MFMAs run.
+//   * wave A holds the rows' raw fp32 activation fragments, splits them group by group and issues P's MFMAs for a 64-column chunk (two
+//     accumulator tiles) in two half-steps of eight channel groups; it deposits the finished sums piece by piece in the pair's two LDS tiles
+//     and issues ALL of the block's DMAs, BEHIND its MFMAs of the step (measured: in front of them the matrix pipe stands idle while A issues and B is
+//     in its epilogue) — it has no other vector-memory traffic in the loop, so its vmcnt in front of a barrier counts DMAs only;
+//   * wave B requests the residual a whole piece ahead, takes a piece of P's sums from the pair's tile, runs chain_piece_p on it (scale / shift,
+//     + residual, ReLU, watch, store; y left in the tile), reads y back as fragments, splits and issues Q's MFMAs; it holds Q's sums and runs
+//     Q's epilogue at the end.
+// Time runs in steps, one block barrier in front of each (34 in all, the same for every wave whatever M is); nothing else synchronises.  In step s
+//   A multiplies half s & 1 of chunk s >> 1 from W3 stage (s >> 1) & 1 and deposits piece s - 1 (odd s: tile X; even s: tile Y, from the sums it kept);
+//   B works on piece s - 2 (tile X for an even piece, Y for an odd one) with W1 stage (s - 2) % 3;
+//   A's DMAs bring half s & 1 of W3's next chunk (into the stage nobody reads) and W1's K step of piece s (into the stage B last read in step s - 1).
+// A step's 32 KB are first read in step s + 2: in front of barrier s + 2 A waits with vmcnt(8), which leaves the eight DMAs of step s + 1 in flight
+// (vmcnt(0) where a step issued fewer).  A tile is written in one step and read in the next, and the barrier between the two steps is the hand-over.  A pair whose 32 rows lie beyond M skips loads, MFMAs and stores, never a barrier or a DMA.  Per accumulator the
+// order is the other forms': channel groups ascending, hi / mid / lo per group, filter fragment first; one running sum per output of Q.
+// LDS: W3 2 x 32 KB | W1 3 x 16 KB | tiles 4 pairs x 2 x 4 KB | the scale / shift tables 10 KB = 154 KB.  Nothing crosses blocks.
 template <int C, int PARTS>
-__global__ __launch_bounds__(256, 1) void k_conv_chain_ring(const ChainArgs ca)
+__global__ __launch_bounds__(512, 1) void k_conv_chain_ring(const ChainArgs ca)
 {
-    static_assert(C == 256, "the ring's stage holds C = 256's chunk images");
-    constexpr int C4 = 4 * C, KT = C / 32, TNP = 2, TNQ = C / 32, NCH = C4 / 64;
+    static_assert(C == 256, "the ring's stages hold C = 256's chunk images");
+    constexpr int C4 = 4 * C, KT = C / 32, TNP = 2, TNQ = C / 32, NCH = C4 / 64, NPC = 2 * NCH;
     constexpr int WCH = 64 * C * 2;                      // one chunk image of either layer: 64 rows x C channels (W3) = C rows x 64 channels (W1)
-    constexpr int STAGE = 2 * WCH;
-    constexpr int NDMA = WCH / 4096;                     // DMAs per thread, chunk and layer: 256 lanes x 16 B each
-    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE + 4 * 32 * 32 * 4];
+    constexpr int WHALF = WCH / 2;                       // four K steps of a W3 chunk image = one K step (a piece's 32 channels) of a W1 chunk image
+    constexpr int NW1 = 3;                               // W1's stages: a piece's K step lands two steps ahead of its use
+    constexpr int W1_OFF = 2 * WCH, TILE_OFF = W1_OFF + NW1 * WHALF;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[TILE_OFF + 4 * 2 * 32 * 32 * 4];
     __shared__ __attribute__((aligned(16))) float s_tab[2 * C4], s_tabq[2 * C];       // scale | shift of P's and of Q's columns
     const ConvArgs& a = ca.p;
     const ConvArgs& aq = ca.q;
-    const int t = threadIdx.x;
-    const int wave = t >> 6, lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int pair = wave & 3;                           // waves p and p + 4 share a SIMD and 32 rows
     const int l31 = lane & 31, kk = lane >> 5;
-    const ChainTile tl{reinterpret_cast<float*>(smem + 2 * STAGE) + wave * (32 * 32), lane};
-    static_assert(C4 == 4 * 256 && C % 8 == 0 && C / 2 <= 256, "the tables are filled by 256 threads, 16 B each");
-    *reinterpret_cast<float4*>(&s_tab[4 * t]) = chain_ld4(a.scale + 4 * t);
-    *reinterpret_cast<float4*>(&s_tab[C4 + 4 * t]) = chain_ld4(a.shift + 4 * t);
-    if (t < C / 2) *reinterpret_cast<float4*>(&s_tabq[4 * t]) = chain_ld4(t < C / 4 ? aq.scale + 4 * t : aq.shift + 4 * (t - C / 4));      // (read behind the first ring barrier)
-    const float* const res = static_cast<const float*>(a.res);
-    float* const out = static_cast<float*>(a.out);
+    float* const tiles = reinterpret_cast<float*>(smem + TILE_OFF) + pair * (2 * 32 * 32);
+    const ChainTile tx{tiles, lane}, ty{tiles + 32 * 32, lane};
     const int swzb = (l31 >> 2) & 3;                     // filter rows in LDS: 16-B chunk c of row r at c ^ ((r >> 2) & 3)
+    const int row0 = (blockIdx.x * 4 + pair) * 32;
+    const bool live = row0 < a.M;                        // (wave-uniform) a pair without rows keeps the barriers and the DMAs going and does nothing else
 
-    // ---- the ring's DMA: buffer resources over the two images (a lane beyond them would deposit zeros), inline asm as in kernels_conv.hip ----
-    typedef unsigned srd_t __attribute__((ext_vector_type(4)));
-    srd_t srdP, srdQ;
-    {
-        const unsigned long long wp = (unsigned long long)(uintptr_t)ca.p_stream, wq = (unsigned long long)(uintptr_t)ca.q_stream;
-        srdP[0] = __builtin_amdgcn_readfirstlane((unsigned)wp);
-        srdP[1] = __builtin_amdgcn_readfirstlane((unsigned)(wp >> 32) & 0xffffu);
-        srdP[2] = (unsigned)(NCH * WCH);
-        srdP[3] = 0x00020000u;
-        srdQ[0] = __builtin_amdgcn_readfirstlane((unsigned)wq);
-        srdQ[1] = __builtin_amdgcn_readfirstlane((unsigned)(wq >> 32) & 0xffffu);
-        srdQ[2] = (unsigned)(NCH * WCH);
-        srdQ[3] = 0x00020000u;
-    }
-    const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem);
-    const unsigned wdst = lds0 + (unsigned)__builtin_amdgcn_readfirstlane(wave) * 1024u;      // wave-uniform: lane i's 16 B land at M0 + 16 i
-    const unsigned voff = (unsigned)t * 16u;
+    if (wave < 4) {
+        // ================================================ wave A: P's sums and the block's DMAs ================================================
+        const int t = pair * 64 + lane;
+        static_assert(C4 == 4 * 256 && C % 8 == 0 && C / 2 <= 256, "the tables are filled by 256 threads, 16 B each");
+        *reinterpret_cast<float4*>(&s_tab[4 * t]) = chain_ld4(a.scale + 4 * t);
+        *reinterpret_cast<float4*>(&s_tab[C4 + 4 * t]) = chain_ld4(a.shift + 4 * t);
+        if (t < C / 2) *reinterpret_cast<float4*>(&s_tabq[4 * t]) = chain_ld4(t < C / 4 ? aq.scale + 4 * t : aq.shift + 4 * (t - C / 4));      // (read behind the barriers)
+        // ---- the DMA: buffer resources over the two images (a lane beyond them would deposit zeros), inline asm as in kernels_conv.hip ----
+        typedef unsigned srd_t __attribute__((ext_vector_type(4)));
+        srd_t srdP, srdQ;
+        {
+            const unsigned long long wp = (unsigned long long)(uintptr_t)ca.p_stream, wq = (unsigned long long)(uintptr_t)ca.q_stream;
+            srdP[0] = __builtin_amdgcn_readfirstlane((unsigned)wp);
+            srdP[1] = __builtin_amdgcn_readfirstlane((unsigned)(wp >> 32) & 0xffffu);
+            srdP[2] = (unsigned)(NCH * WCH);
+            srdP[3] = 0x00020000u;
+            srdQ[0] = __builtin_amdgcn_readfirstlane((unsigned)wq);
+            srdQ[1] = __builtin_amdgcn_readfirstlane((unsigned)(wq >> 32) & 0xffffu);
+            srdQ[2] = (unsigned)(NCH * WCH);
+            srdQ[3] = 0x00020000u;
+        }
+        const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem);
+        const unsigned wdst = lds0 + (unsigned)pair * 1024u;           // wave-uniform: lane i's 16 B land at M0 + 16 i; the four A waves copy 4 KB per round
+        const unsigned voff = (unsigned)t * 16u;
 #define MRCNN_RING_DMA(SRD, SOFF, DST)                                                                         \
     asm volatile("s_nop 4\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff), "s"(SRD), "s"(SOFF), "s"(DST) : "memory", "m0");
-    // chunk ch of both images -> stage ch & 1 (this thread's share: 16 B of each 4 KB slice)
-    auto ring_fill = [&](int ch) {
-        const unsigned src = (unsigned)__builtin_amdgcn_readfirstlane(ch) * (unsigned)WCH;
-        const unsigned dst = wdst + (unsigned)(__builtin_amdgcn_readfirstlane(ch) & 1) * (unsigned)STAGE;
+        // half h (K steps 4 h .. 4 h + 3, 16 KB contiguous) of W3's chunk c -> W3 stage c & 1
+        auto fill_w3 = [&](int c, int h) {
+            const unsigned src = (unsigned)__builtin_amdgcn_readfirstlane(c) * (unsigned)WCH + (unsigned)(h * WHALF);
+            const unsigned dst = wdst + (unsigned)(__builtin_amdgcn_readfirstlane(c) & 1) * (unsigned)WCH + (unsigned)(h * WHALF);
 #pragma unroll
-        for (int k = 0; k < NDMA; ++k) {
-            MRCNN_RING_DMA(srdP, src + k * 4096u, dst + k * 4096u)
-            MRCNN_RING_DMA(srdQ, src + k * 4096u, dst + (unsigned)WCH + k * 4096u)
-        }
-    };
-    ring_fill(0);
-
-    const int row0 = (blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(wave)) * 32;
-    const bool live = row0 < a.M;                        // (wave-uniform) a wave without rows keeps the ring going and does nothing else
-    bool out_of_range = false, out_of_range_q = false;
-    ChainParts ap[2 * KT];
-    if (live) chain_split_row<PARTS, true>(ap, static_cast<const float*>(a.in), row0, a.M, l31, kk);
-    const bool full = row0 + 32 <= a.M;                  // (wave-uniform) the wave issues every load and store of a chunk
-    const ChainRows rw = chain_rows(row0, a.M, lane);
-    const bool relu = a.act == ACT_RELU;
-    f32x16 accQ[TNQ];
-    chain_zero(accQ);
-
-    for (int ch = 0; ch < NCH; ++ch) {
-        // chunk ch has landed for every wave, and every wave has left chunk ch - 1: its stage takes chunk ch + 1
-        // (the DMAs of chunk ch are older than the 8 residual loads and 8 stores a wave of 32 rows has issued since, and vector memory
-        // operations retire in order: such a wave leaves its last piece's four stores in flight across the barrier; any other wave waits for all)
-        if (full) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (ch + 1 < NCH) ring_fill(ch + 1);
-        if (!live) continue;
-        const unsigned char* const w3s = smem + (ch & 1) * STAGE;          // [K step][64 rows][64 B]
-        const unsigned char* const w1s = w3s + WCH;                        // [2 K steps][C rows][64 B]
-        const int nc = ch * 64;
-        float4 rv[TNP][4];
-        chain_residual(rv, res, rw, C4, nc);
-        f32x16 accP[TNP];
-        chain_zero(accP);
-        // ---- P: K steps of 32 channels, two groups of 16 each; group i + 1's filter fragments are requested ahead of group i's MFMAs ----
-        auto frag_p = [&](uint4 (&b)[TNP], int i) {
-#pragma unroll
-            for (int j = 0; j < TNP; ++j) b[j] = *reinterpret_cast<const uint4*>(w3s + ((i >> 1) * 64 + j * 32 + l31) * 64 + (((2 * (i & 1) + kk) ^ swzb) << 4));
+            for (int k = 0; k < WHALF / 4096; ++k) MRCNN_RING_DMA(srdP, src + k * 4096u, dst + k * 4096u)
         };
+        // W1's K step of piece p (K step p & 1 of chunk p >> 1, 16 KB contiguous) -> W1 stage p % 3
+        auto fill_w1 = [&](int p) {
+            const unsigned off = (unsigned)(__builtin_amdgcn_readfirstlane(p) & 1) * (unsigned)WHALF;
+            const unsigned src = (unsigned)(__builtin_amdgcn_readfirstlane(p) >> 1) * (unsigned)WCH + off;
+            const unsigned dst = wdst + (unsigned)W1_OFF + ((unsigned)__builtin_amdgcn_readfirstlane(p) % (unsigned)NW1) * (unsigned)WHALF;
+#pragma unroll
+            for (int k = 0; k < WHALF / 4096; ++k) MRCNN_RING_DMA(srdQ, src + k * 4096u, dst + k * 4096u)
+        };
+        fill_w3(0, 0);
+        fill_w3(0, 1);
+        // step s = 2 c + h: half h of W3's next chunk (first read in step s + 2, its stage last read in step 2 c - 1) and W1's K step of piece s (read in
+        // step s + 2, its stage last read in step s - 1): eight DMAs per wave in every step that has a next chunk, four in the last two
+        auto ring_step = [&](int c, int h) {
+            if (c + 1 < NCH) fill_w3(c + 1, h);
+            fill_w1(2 * c + h);
+        };
+        // this lane's activation fragments (pixel row0 + l31, 16 groups of 16 channels), raw: the three parts do not fit beside a second wave
+        // (a row beyond M: zeros)
+        uint4 u[2 * KT][2];
         {
-            uint4 bv[TNP];
-            frag_p(bv, 0);
+            const int m = row0 + l31;
+            const float* const src = static_cast<const float*>(a.in) + (long)m * C + 8 * kk;
 #pragma unroll
-            for (int i = 0; i < 2 * KT; ++i) {
-                uint4 bn[TNP];
-                if (i + 1 < 2 * KT) frag_p(bn, i + 1);
-                __builtin_amdgcn_sched_barrier(0);
-                chain_mfma_parts<PARTS, TNP>(accP, bv, ap[i]);
-                if (i + 1 < 2 * KT) {
-#pragma unroll
-                    for (int j = 0; j < TNP; ++j) bv[j] = bn[j];
-                }
+            for (int g = 0; g < 2 * KT; ++g) {
+                u[g][0] = u[g][1] = make_uint4(0u, 0u, 0u, 0u);
+                if (m < a.M) { u[g][0] = *reinterpret_cast<const uint4*>(src + g * 16); u[g][1] = *reinterpret_cast<const uint4*>(src + g * 16 + 4); }
             }
         }
-        // Q's filter fragments of half a group (four column tiles x 16 channels): half h of piece j
-        auto frag_q = [&](uint4 (&b)[TNQ / 2], int j, int h) {
+        f32x16 accP[TNP];
+        chain_zero(accP);
+        for (int c = 0; c < NCH; ++c) {
+            const unsigned char* const w3s = smem + (c & 1) * WCH;     // [K step][64 rows][64 B]
+            auto frag_p = [&](uint4 (&b)[TNP], int i) {
 #pragma unroll
-            for (int i = 0; i < TNQ / 2; ++i) b[i] = *reinterpret_cast<const uint4*>(w1s + (j * C + ((h & 1) * (TNQ / 2) + i) * 32 + l31) * 64 + (((2 * (h >> 1) + kk) ^ swzb) << 4));
-        };
-        // ---- epilogue of the chunk, piece by piece; each piece is one K step of Q -------------------------------------
+                for (int j = 0; j < TNP; ++j) b[j] = *reinterpret_cast<const uint4*>(w3s + ((i >> 1) * 64 + j * 32 + l31) * 64 + (((2 * (i & 1) + kk) ^ swzb) << 4));
+            };
 #pragma unroll
-        for (int j = 0; j < TNP; ++j) {
-            const int n = nc + j * 32 + rw.c4;
-            uint4 bq[TNQ / 2];
-            frag_q(bq, j, 0);                              // (independent of the epilogue: on its way meanwhile)
-            chain_piece_p(tl, accP[j], s_tab, s_tab + C4, rv[j], res != nullptr, relu, rw, out, C4, n, out_of_range);
-            // ---- Q: the K step of channels nc + 32 j .. + 31 ---------------------------------------------------------
-            // (per accumulator the order is the other forms': group 0's parts, then group 1's; the halves only stagger the fragment reads)
+            for (int h = 0; h < 2; ++h) {
+                // the DMAs of step s - 2 (and, once, everything before the loop) have landed; the eight of step s - 1 stay in flight
+                if (2 * c + h == 0 || c + 1 >= NCH) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+                __syncthreads();                                        // step 2 c + h
+                if (!live) { ring_step(c, h); continue; }
+                if (h == 0) {
+                    if (c > 0) ty.put(accP[1]);                         // the previous chunk's second piece: B left tile Y at the barrier
+                    chain_zero(accP);
+                }
+                // eight groups of 16 channels; group i + 1's filter fragments and parts are formed ahead of group i's MFMAs
+                uint4 bv[TNP];
+                frag_p(bv, 8 * h);
+                ChainParts pt = chain_split<PARTS>(u[8 * h][0], u[8 * h][1]);
+#pragma unroll
+                for (int i = 8 * h; i < 8 * h + 8; ++i) {
+                    uint4 bn[TNP];
+                    ChainParts pn;
+                    if (i + 1 < 8 * h + 8) { frag_p(bn, i + 1); pn = chain_split<PARTS>(u[i + 1][0], u[i + 1][1]); }
+                    chain_mfma_parts<PARTS, TNP>(accP, bv, pt);
+                    if (i + 1 < 8 * h + 8) {
+#pragma unroll
+                        for (int j = 0; j < TNP; ++j) bv[j] = bn[j];
+                        pt = pn;
+                    }
+                }
+                ring_step(c, h);                                        // behind the MFMAs: B's MFMAs run beside the DMAs' issue
+                if (h == 1) tx.put(accP[0]);                            // the chunk's first piece: B left tile X at the barrier
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                                                // step NPC: the last piece's hand-over
+        if (live) ty.put(accP[1]);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                                                // step NPC + 1: B's last piece
+#undef MRCNN_RING_DMA
+        return;
+    }
+
+    // ================================================ wave B: P's epilogue, Q ================================================
+    if (!live) {
+        for (int s = 0; s < NPC + 2; ++s) __syncthreads();
+        return;
+    }
+    const float* const res = static_cast<const float*>(a.res);
+    float* const out = static_cast<float*>(a.out);
+    const bool full = row0 + 32 <= a.M;                  // (wave-uniform) no row of the pair lies beyond M
+    const ChainRowOffs ro = chain_row_offs(row0, a.M, lane, C4);
+    const float* const res0 = res + (long)row0 * C4;     // (wave-uniform) the wave's first row
+    float* const out0 = out + (long)row0 * C4;
+    const int c4 = (lane & 7) * 4;
+    const bool relu = a.act == ACT_RELU;
+    bool out_of_range = false, out_of_range_q = false;
+    f32x16 accQ[TNQ];
+    chain_zero(accQ);
+    float4 rv[2][4];                                     // the residual of this piece and of the next
+    auto residual = [&](float4 (&r)[4], int p) { chain_residual_piece(r, res0 + p * 32, ro); };
+    residual(rv[0], 0);
+    __syncthreads();                                     // steps 0 and 1: A's first chunk
+    __syncthreads();
+    for (int c = 0; c < NCH; ++c) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int p = 2 * c + j;
+            residual(rv[j ^ 1], p + 1 < NPC ? p + 1 : p);          // (unconditional: one count of requests in flight on every path; the last is unused)
+            __syncthreads();                             // step p + 2: piece p lies in the pair's tile, its K step of W1 in stage j
+            const ChainTile& tl = j ? ty : tx;
+            const unsigned char* const w1s = smem + W1_OFF + ((unsigned)p % (unsigned)NW1) * WHALF;       // [C rows][64 B]
+            // Q's filter fragments of a quarter of a group (two column tiles x 16 channels): quarter h & 3 of group h >> 2
+            auto frag_q = [&](uint4 (&b)[TNQ / 4], int h) {
+#pragma unroll
+                for (int i = 0; i < TNQ / 4; ++i) b[i] = *reinterpret_cast<const uint4*>(w1s + (((h & 3) * (TNQ / 4) + i) * 32 + l31) * 64 + (((2 * (h >> 2) + kk) ^ swzb) << 4));
+            };
+            uint4 bq[TNQ / 4];
+            frag_q(bq, 0);                               // (independent of the epilogue: on its way meanwhile)
+            const int n = p * 32 + c4;
+            if (full) {
+                if (relu) chain_piece_p<true, true>(tl, s_tab, s_tab + C4, rv[j], ro, out0 + p * 32, n, out_of_range);
+                else chain_piece_p<true, false>(tl, s_tab, s_tab + C4, rv[j], ro, out0 + p * 32, n, out_of_range);
+            } else {
+                if (relu) chain_piece_p<false, true>(tl, s_tab, s_tab + C4, rv[j], ro, out0 + p * 32, n, out_of_range);
+                else chain_piece_p<false, false>(tl, s_tab, s_tab + C4, rv[j], ro, out0 + p * 32, n, out_of_range);
+            }
+            // ---- Q: the K step of channels 32 p .. + 31 ----------------------------------------------------------------
+            // (per accumulator the order is the other forms': group 0's parts, then group 1's; the quarters only stagger the fragment reads)
             ChainParts pt;
 #pragma unroll
-            for (int h = 0; h < 4; ++h) {
-                if ((h & 1) == 0) pt = tl.template frag<PARTS>(h >> 1);
-                uint4 bn[TNQ / 2];
-                if (h < 3) frag_q(bn, j, h + 1);
+            for (int h = 0; h < 8; ++h) {
+                if ((h & 3) == 0) pt = tl.template frag<PARTS>(h >> 2);
+                uint4 bn[TNQ / 4];
+                if (h < 7) frag_q(bn, h + 1);
                 __builtin_amdgcn_sched_barrier(0);
-                if (h & 1) chain_mfma_parts<PARTS, TNQ / 2, TNQ, TNQ / 2>(accQ, bq, pt);
-                else chain_mfma_parts<PARTS, TNQ / 2, TNQ, 0>(accQ, bq, pt);
-                if (h < 3) {
+                if ((h & 3) == 0) chain_mfma_parts<PARTS, TNQ / 4, TNQ, 0>(accQ, bq, pt);
+                else if ((h & 3) == 1) chain_mfma_parts<PARTS, TNQ / 4, TNQ, TNQ / 4>(accQ, bq, pt);
+                else if ((h & 3) == 2) chain_mfma_parts<PARTS, TNQ / 4, TNQ, TNQ / 2>(accQ, bq, pt);
+                else chain_mfma_parts<PARTS, TNQ / 4, TNQ, 3 * TNQ / 4>(accQ, bq, pt);
+                if (h < 7) {
 #pragma unroll
-                    for (int i = 0; i < TNQ / 2; ++i) bq[i] = bn[i];
+                    for (int i = 0; i < TNQ / 4; ++i) bq[i] = bn[i];
                 }
             }
             __builtin_amdgcn_wave_barrier();
         }
     }
-#undef MRCNN_RING_DMA
-    // (no barrier follows: a wave without rows is done)
-    if (live) chain_epilogue_q(tl, accQ, s_tabq, s_tabq + C, aq.act == ACT_RELU, rw, static_cast<float*>(aq.out), out_of_range_q);
+    // (no barrier follows: A is done with the tiles, a pair without rows is done)
+    int lane_q = lane;
+    asm volatile("" : "+v"(lane_q));                     // Q's rows are formed here, not carried through the loop (the loop has no register to spare)
+    chain_epilogue_q(tx, accQ, s_tabq, s_tabq + C, aq.act == ACT_RELU, chain_rows(row0, a.M, lane_q), static_cast<float*>(aq.out), out_of_range_q);
     if (a.range_flag && out_of_range) atomicOr(a.range_flag, 1);
     if (aq.range_flag && out_of_range_q) atomicOr(aq.range_flag, 1);
 }
+
 
 typedef void (*chain_kernel_t)(const ChainArgs);
 template <int PARTS>
@@ -540,9 +631,9 @@ static chain_kernel_t chain_kernel(int C, bool sc)
 void conv_chain_launch(hipStream_t s, const ConvArgs& p, const ConvArgs& q, int parts, int n_cus, const void* p_stream, const void* q_stream)
 {
     ChainArgs ca{p, q, p_stream, q_stream};
-    dim3 grid((p.M + 127) / 128), block(256);
     const bool sc = p.sc_in != nullptr;
     const int C = q.Cout;
+    dim3 grid((p.M + 127) / 128), block(C == 256 ? 512 : 256);
     MRCNN_REQUIRE((C == 64 || C == 128 || C == 256) && (parts == 2 || parts == 3), MRCNN_ERR_INVALID, "conv_chain_launch: C %d, %d parts", C, parts);
     if (C == 256) MRCNN_REQUIRE(!sc && p.res && p_stream && q_stream, MRCNN_ERR_INVALID, "conv_chain_launch: C = 256 runs identity pairs from their stream images");
     if (C == 64) {
