@@ -5,6 +5,11 @@
  * convolution of the kernel family on caller data, to time a layer shape, to read the live per-kernel profile of a
  * predict, and to switch kernel-selection policy for A/B comparisons.  The switches are PROCESS-WIDE and not
  * thread-safe; a production host never calls anything declared here.
+ *
+ * mrcnn_test_proposals_batch / mrcnn_test_detections_batch run the box path (top-k select, sort and decode, suppression matrix, greedy scan,
+ * final top-k) on a batch of caller images in one launch sequence with a predict's bindings and strides: the tests' way to put adversarial
+ * content — empty and saturated neighbours, tied scores, odd anchor counts, more than 1024 regions, class ids beyond 1024 — where only
+ * whole-model predicts on random weights reached before.
  */
 #ifndef MASKRCNN_HIP_TEST_H
 #define MASKRCNN_HIP_TEST_H
@@ -217,6 +222,22 @@ MRCNN_API int mrcnn_classifier_rows(const float* logits, int64_t ld, const float
 MRCNN_API int mrcnn_test_roi_align_nhwc_batch(const float* const maps[4], const int heights[4], const int widths[4], int channels, int dtype,
                                               const float level_mul[4], const float* rois, int64_t roi_stride, int n_rois, int batch, int pool,
                                               double image_w, double image_h, float* out, int32_t* row_flags);
+
+/* The proposal path and the detection path (csrc/kernels_boxes.hip) on a BATCH of caller (host) images in one launch sequence, bound and strided
+ * exactly as a predict does it — the layer API (mrcnn_layer_evaluate) binds one image with every batch stride 0 and so never reaches the
+ * per-image state / histogram / count words, the image index of the grids or the batch-dependent column-split policy (tests/test_gpu_boxes.py;
+ * the cases and their conditions: tests/boxes_cases.py).
+ *   mrcnn_test_proposals_batch: probs (batch, n_anchors, 2), deltas (batch, n_anchors, 4), anchors (n_anchors, 4) passed in (no anchors file),
+ *     std4 = bboxStdDev; K = min(n_anchors, pre_nms) candidates, batch strides 2A / 4A.  rois (batch, max_proposals, row_stride >= 4) is IN/OUT:
+ *     the caller's buffer is staged to the device first, as the layer does, so columns >= 4 of kept rows come back as they went in and padded
+ *     rows come back zero.  keep_count (optional, batch int32): proposals kept per image.
+ *   mrcnn_test_detections_batch: rois (batch, n, 4), cls6 (batch, n, 6) = (dy, dx, dh, dw, class id, score); out (batch, max_det,
+ *     row_stride >= 6) is IN/OUT in the same way.  n <= 8192 (the greedy scan's LDS); more fails with MRCNN_ERR_UNSUPPORTED and out untouched.
+ * Bad arguments return a status; nothing falls back to per-image launches.  The box-path knobs of mrcnn_debug_set apply. */
+MRCNN_API int mrcnn_test_proposals_batch(const float* probs, const float* deltas, const float* anchors, int batch, int n_anchors, const float std4[4],
+                                         int pre_nms, int max_proposals, float nms_thr, float* rois, int64_t row_stride, int32_t* keep_count);
+MRCNN_API int mrcnn_test_detections_batch(const float* rois, const float* cls6, int batch, int n, const float std4[4], int max_det, float score_thr,
+                                          float nms_thr, float* out, int64_t row_stride);
 
 /* Measurement (tools/jpeg_ab.py): the wall time of the two stages of the calling thread's last mrcnn_jpeg_decode_batch /
  * mrcnn_maskrcnn_predict_jpegs — host_ms: header parsing + the entropy threads; device_ms: from the upload of the coefficients to the end

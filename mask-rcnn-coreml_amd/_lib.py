@@ -56,7 +56,7 @@ TEST_SYMBOLS = [
     "mrcnn_bench_conv", "mrcnn_bench_conv_dtype", "mrcnn_model_conv_profile_enable", "mrcnn_model_conv_profile_get",
     "mrcnn_model_conv_profile_shapes", "mrcnn_conv2d_nhwc", "mrcnn_debug_set", "mrcnn_bottleneck_nhwc", "mrcnn_bench_mfma_probe", "mrcnn_model_conv_profile_group", "mrcnn_bottleneck_first_nhwc", "mrcnn_bottleneck_stage_nhwc", "mrcnn_model_conv_profile_bytes",
     "mrcnn_jpeg_last_stage_ms", "mrcnn_jpeg_coefficients", "mrcnn_test_last_range_flag", "mrcnn_classifier_rows", "mrcnn_test_roi_align_nhwc_batch", "mrcnn_conv_chain_nhwc",
-    "mrcnn_test_conv_form_nhwc", "mrcnn_test_chain_stream_image",
+    "mrcnn_test_conv_form_nhwc", "mrcnn_test_chain_stream_image", "mrcnn_test_proposals_batch", "mrcnn_test_detections_batch",
 ]
 
 
@@ -289,6 +289,8 @@ def lib():
     L.mrcnn_test_roi_align_nhwc_batch.argtypes = [C.POINTER(vp), ip, ip, C.c_int, C.c_int, f32p, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double,
                                                   C.c_double, vp, vp]
     L.mrcnn_test_conv_form_nhwc.argtypes = [C.POINTER(ConvForm)]
+    L.mrcnn_test_proposals_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_float, vp, C.c_int64, vp]
+    L.mrcnn_test_detections_batch.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_float, C.c_float, vp, C.c_int64]
     _lib = L
     return L
 

@@ -684,6 +684,63 @@ extern "C" int mrcnn_test_roi_align_nhwc_batch(const float* const maps[4], const
     });
 }
 
+// proposal_forward on a BATCH of caller (host) images in ONE launch sequence, bound and strided the way MaskRCNNModel::predict does it: per-image
+// state / hist / count words, blockIdx.y / z = image, nms_col_splits(W, B) — what the layer API (B = 1, every batch stride 0) never reaches
+// (tests/test_gpu_boxes.py).  rois is IN/OUT: the caller's buffer is staged in first, as ProposalLayer.evaluate does.
+extern "C" int mrcnn_test_proposals_batch(const float* probs, const float* deltas, const float* anchors, int batch, int n_anchors, const float std4[4],
+                                          int pre_nms, int max_proposals, float nms_thr, float* rois, int64_t row_stride, int32_t* keep_count)
+{
+    return guarded([&] {
+        require_gpu();
+        MRCNN_REQUIRE(probs && deltas && anchors && std4 && rois, MRCNN_ERR_INVALID, "test_proposals_batch: null argument");
+        MRCNN_REQUIRE(batch >= 1 && n_anchors >= 1 && pre_nms >= 1 && max_proposals >= 1 && row_stride >= 4, MRCNN_ERR_INVALID,
+                      "bad test_proposals_batch argument");
+        MRCNN_REQUIRE(n_anchors < (1 << 24) / 4, MRCNN_ERR_UNSUPPORTED, "test_proposals_batch: region count exceeds the reference's float-index range");
+        const int A = n_anchors, K = A < pre_nms ? A : pre_nms;
+        const long rois_sB = (long)max_proposals * row_stride;
+        DevBuf dp, dd, da, dr, ws_buf;
+        upload_f32(dp, probs, (size_t)batch * A * 2);
+        upload_f32(dd, deltas, (size_t)batch * A * 4);
+        upload_f32(da, anchors, (size_t)A * 4);
+        upload_f32(dr, rois, (size_t)batch * rois_sB);
+        ProposalWorkspace ws;
+        ws_buf.alloc(ProposalWorkspace::bytes(batch, A, K, max_proposals));
+        ws.bind(ws_buf.p, batch, A, K, max_proposals);
+        Stream st;
+        Drain drain{st.s};
+        proposal_forward(st.s, ws, dp.as<float>(), (long)A * 2, dd.as<float>(), (long)A * 4, da.as<float>(), std4, nms_thr, dr.as<float>(), rois_sB,
+                         row_stride);
+        HIP_CHECK(hipStreamSynchronize(st.s));
+        HIP_CHECK(hipMemcpy(rois, dr.p, (size_t)batch * rois_sB * 4, hipMemcpyDeviceToHost));
+        if (keep_count) HIP_CHECK(hipMemcpy(keep_count, ws.keep_count, (size_t)batch * 4, hipMemcpyDeviceToHost));
+    });
+}
+
+// detection_forward on a batch of caller (host) images in one launch sequence, as MaskRCNNModel::predict calls it.  out is IN/OUT.
+extern "C" int mrcnn_test_detections_batch(const float* rois, const float* cls6, int batch, int n, const float std4[4], int max_det, float score_thr,
+                                           float nms_thr, float* out, int64_t row_stride)
+{
+    return guarded([&] {
+        require_gpu();
+        MRCNN_REQUIRE(rois && cls6 && std4 && out, MRCNN_ERR_INVALID, "test_detections_batch: null argument");
+        MRCNN_REQUIRE(batch >= 1 && n >= 1 && max_det >= 1 && row_stride >= 6, MRCNN_ERR_INVALID, "bad test_detections_batch argument");
+        const long out_sB = (long)max_det * row_stride;
+        DevBuf dr, dc, dout, ws_buf;
+        upload_f32(dr, rois, (size_t)batch * n * 4);
+        upload_f32(dc, cls6, (size_t)batch * n * 6);
+        upload_f32(dout, out, (size_t)batch * out_sB);
+        DetectionWorkspace ws;
+        ws_buf.alloc(DetectionWorkspace::bytes(batch, n, max_det));
+        ws.bind(ws_buf.p, batch, n, max_det);
+        Stream st;
+        Drain drain{st.s};
+        detection_forward(st.s, ws, dr.as<float>(), (long)n * 4, 4, dc.as<float>(), (long)n * 6, std4, score_thr, nms_thr, 0, dout.as<float>(), out_sB,
+                          row_stride);
+        HIP_CHECK(hipStreamSynchronize(st.s));
+        HIP_CHECK(hipMemcpy(out, dout.p, (size_t)batch * out_sB * 4, hipMemcpyDeviceToHost));
+    });
+}
+
 extern "C" int mrcnn_model_conv_profile_enable(mrcnn_model* model, int on)
 {
     return guarded([&] {

@@ -391,7 +391,7 @@ __global__ __launch_bounds__(1024) void k_sort_decode_lds(const uint64_t* __rest
 // 256 CUs whatever the batch).  A block owns 64 keys (one per lane); its four waves each count over a quarter of every
 // 2048-key chunk staged in LDS (wave-uniform addresses: broadcast reads), and wave 0 adds the four counts and writes the
 // decoded box at its rank.  Same keys, same order, same decode: the outputs are the bitonic kernel's, bit for bit
-// (tests/test_gpu_boxes.py; "proposal_rank_sort" 0 / MRCNN_RANK_SORT=0 keeps the old kernel).
+// (tests/test_gpu_boxes.py::test_bitonic_anchors_equal_rank_counting; "proposal_rank_sort" 0 / MRCNN_RANK_SORT=0 keeps the old kernel).
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_rank_decode(const uint64_t* __restrict__ cand, int K, int Kpad,
                                                      const float* __restrict__ deltas, long deltas_sB,
