@@ -9,7 +9,8 @@
  * mrcnn_test_proposals_batch / mrcnn_test_detections_batch run the box path (top-k select, sort and decode, suppression matrix, greedy scan,
  * final top-k) on a batch of caller images in one launch sequence with a predict's bindings and strides: the tests' way to put adversarial
  * content — empty and saturated neighbours, tied scores, odd anchor counts, more than 1024 regions, class ids beyond 1024 — where only
- * whole-model predicts on random weights reached before.
+ * whole-model predicts on random weights reached before.  mrcnn_test_mask_select_batch does the same for the mask head's row selection: rows
+ * dropped in the middle of an image, where compact index and row differ, in each of the three tail forms.
  */
 #ifndef MASKRCNN_HIP_TEST_H
 #define MASKRCNN_HIP_TEST_H
@@ -238,6 +239,46 @@ MRCNN_API int mrcnn_test_proposals_batch(const float* probs, const float* deltas
                                          int pre_nms, int max_proposals, float nms_thr, float* rois, int64_t row_stride, int32_t* keep_count);
 MRCNN_API int mrcnn_test_detections_batch(const float* rois, const float* cls6, int batch, int n, const float std4[4], int max_det, float score_thr,
                                           float nms_thr, float* out, int64_t row_stride);
+
+/* The mask head's row selection (TimeDistributedMaskLayer.swift:58-89 behind MultiArrayBatchProvider(removeZeros: true); csrc/kernels_elementwise.hip)
+ * on a BATCH of caller (host) images in one launch sequence, bound and strided as a predict binds it — the layer API runs one image with every batch
+ * stride 0, and the suite's predicts on random weights keep a prefix of the rows, where compact index and row coincide, but for one dropped row in
+ * one image, behind the engine's memset (tests/test_gpu_mask_select.py; the cases
+ * and the rule's plain restatement: tests/mask_select_cases.py).  The predicate of the first d rows of every image comes from
+ *   flags     (batch, d) int32, non-zero = kept: what the engine does (the ROIAlign kernel wrote them; only the compaction runs), OR
+ *   pooled    batch images of d rows: row r of image b starts at b * pooled_batch_stride + r * row_stride, its first row_len elements are tested
+ *             (row_stride >= row_len, pooled_batch_stride >= d * row_stride; the buffer holds batch * pooled_batch_stride floats), converted on the
+ *             host to `dtype` (MRCNN_F32 | MRCNN_F16, round-to-nearest) so that k_mask_row_flags<float | _Float16> runs.  Exactly one of the two.
+ * The tail then runs over det_rows >= d rows per image (the layer pads up to the detection count, the engine has det_rows == d):
+ *   form 0    mask_select_forward (k_mask_select): feat (batch, d, hw, c) converted to `dtype`, w (nc, c), bias (nc); c % 4 == 0
+ *   form 1    mask_select_classes + mask_select_from_partials: partial (batch, d, hw, parts), the layout ConvDesc::sel_partial leaves, bias (nc)
+ *   form 2    mask_select_from_full_forward: masks (batch, d, nc, hw)
+ *   det       (batch, det_rows, det_stride >= 6): column 4 is the class
+ *   out       (batch, det_rows, out_stride >= hw), IN/OUT: the caller's buffer is staged to the device first and returned whole, so a sentinel shows
+ *             every element that no launch addressed.  Nothing here zeroes it: the engine's memset in front of the tail stays the engine's.
+ *   optional  row_flags (batch, d), mapping (batch, d: only the first kept[b] entries of a row are defined, the rest come back -1), kept (batch),
+ *             sel_cid (batch, det_rows: the class table of the fused tail, -1 = row not written; computed in every form when asked for).
+ * A null required pointer, both or neither predicate source, form outside 0..2, a dtype other than the two, a count below 1, det_rows < d,
+ * parts < 1, a stride below its minimum (MRCNN_ERR_INVALID) or c % 4 != 0 (MRCNN_ERR_SHAPE) fails with a message and leaves `out` untouched;
+ * nothing falls back to per-image launches. */
+typedef struct mrcnn_test_mask_select {
+    int32_t form, dtype, batch, d, det_rows, hw, c, nc, parts, reserved;
+    int64_t row_len, row_stride, pooled_batch_stride, det_stride, out_stride;
+    const int32_t* flags;
+    const float* pooled;
+    const float* det;
+    const float* feat;
+    const float* w;
+    const float* bias;
+    const float* partial;
+    const float* masks;
+    float* out;
+    int32_t* row_flags;
+    int32_t* mapping;
+    int32_t* kept;
+    int32_t* sel_cid;
+} mrcnn_test_mask_select;
+MRCNN_API int mrcnn_test_mask_select_batch(const mrcnn_test_mask_select* sel);
 
 /* Measurement (tools/jpeg_ab.py): the wall time of the two stages of the calling thread's last mrcnn_jpeg_decode_batch /
  * mrcnn_maskrcnn_predict_jpegs — host_ms: header parsing + the entropy threads; device_ms: from the upload of the coefficients to the end

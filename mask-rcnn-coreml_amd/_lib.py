@@ -57,6 +57,7 @@ TEST_SYMBOLS = [
     "mrcnn_model_conv_profile_shapes", "mrcnn_conv2d_nhwc", "mrcnn_debug_set", "mrcnn_bottleneck_nhwc", "mrcnn_bench_mfma_probe", "mrcnn_model_conv_profile_group", "mrcnn_bottleneck_first_nhwc", "mrcnn_bottleneck_stage_nhwc", "mrcnn_model_conv_profile_bytes",
     "mrcnn_jpeg_last_stage_ms", "mrcnn_jpeg_coefficients", "mrcnn_test_last_range_flag", "mrcnn_classifier_rows", "mrcnn_test_roi_align_nhwc_batch", "mrcnn_conv_chain_nhwc",
     "mrcnn_test_conv_form_nhwc", "mrcnn_test_chain_stream_image", "mrcnn_test_proposals_batch", "mrcnn_test_detections_batch",
+    "mrcnn_test_mask_select_batch",
 ]
 
 
@@ -134,6 +135,13 @@ class ConvForm(C.Structure):     # mrcnn_test_conv_form
                [("sentinel", C.c_float), ("reserved2", C.c_int32)] + \
                [(k, C.c_void_p) for k in ("in_", "filters", "scale", "shift", "residual", "sel_w", "sel_cid")] + \
                [("out", ConvFormOutput), ("out2", ConvFormOutput), ("sel_partial", C.c_void_p), ("sel_parts", C.c_void_p)]
+
+
+class MaskSelect(C.Structure):   # mrcnn_test_mask_select
+    _fields_ = [(k, C.c_int32) for k in ("form", "dtype", "batch", "d", "det_rows", "hw", "c", "nc", "parts", "reserved")] + \
+               [(k, C.c_int64) for k in ("row_len", "row_stride", "pooled_batch_stride", "det_stride", "out_stride")] + \
+               [(k, C.c_void_p) for k in ("flags", "pooled", "det", "feat", "w", "bias", "partial", "masks", "out", "row_flags", "mapping", "kept",
+                                          "sel_cid")]
 
 
 class ConvShapeStat(C.Structure):    # mrcnn_conv_shape_stat
@@ -291,6 +299,7 @@ def lib():
     L.mrcnn_test_conv_form_nhwc.argtypes = [C.POINTER(ConvForm)]
     L.mrcnn_test_proposals_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_float, vp, C.c_int64, vp]
     L.mrcnn_test_detections_batch.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_float, C.c_float, vp, C.c_int64]
+    L.mrcnn_test_mask_select_batch.argtypes = [C.POINTER(MaskSelect)]
     _lib = L
     return L
 

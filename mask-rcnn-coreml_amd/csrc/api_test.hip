@@ -741,6 +741,92 @@ extern "C" int mrcnn_test_detections_batch(const float* rois, const float* cls6,
     });
 }
 
+// The mask head's row selection on a batch of caller (host) images in one launch sequence, as MaskRCNNModel::predict binds it (engine.hip: the
+// compaction over the row flags, then the fused or the unfused tail) or, with pooled rows and form 2, as TimeDistributedMaskLayer.evaluate does (api.hip:
+// the predicate over d feature rows, the select over det_rows detections) — the workspace's rows per image are det_rows for both.  out is IN/OUT and is
+// not zeroed here (tests/test_gpu_mask_select.py).
+extern "C" int mrcnn_test_mask_select_batch(const mrcnn_test_mask_select* sel)
+{
+    return guarded([&] {
+        require_gpu();
+        MRCNN_REQUIRE(sel, MRCNN_ERR_INVALID, "test_mask_select_batch: null descriptor");
+        const mrcnn_test_mask_select& q = *sel;
+        const int form = q.form, B = q.batch, D = q.d, R = q.det_rows, HW = q.hw, C = q.c, nc = q.nc, parts = q.parts;
+        MRCNN_REQUIRE(form >= 0 && form <= 2, MRCNN_ERR_INVALID, "test_mask_select_batch: form %d outside 0..2", form);
+        MRCNN_REQUIRE(q.dtype == MRCNN_F32 || q.dtype == MRCNN_F16, MRCNN_ERR_INVALID, "test_mask_select_batch: dtype %d", q.dtype);
+        MRCNN_REQUIRE(B >= 1 && D >= 1 && HW >= 1 && nc >= 1, MRCNN_ERR_INVALID, "test_mask_select_batch: batch %d, d %d, hw %d, nc %d: none may be below 1", B, D, HW, nc);
+        MRCNN_REQUIRE(R >= D, MRCNN_ERR_INVALID, "test_mask_select_batch: det_rows %d < d %d", R, D);
+        MRCNN_REQUIRE(q.det && q.out, MRCNN_ERR_INVALID, "test_mask_select_batch: null det or out");
+        MRCNN_REQUIRE((q.flags != nullptr) != (q.pooled != nullptr), MRCNN_ERR_INVALID, "test_mask_select_batch: exactly one of flags and pooled gives the predicate");
+        MRCNN_REQUIRE(q.det_stride >= 6 && q.out_stride >= HW, MRCNN_ERR_INVALID, "test_mask_select_batch: det_stride %ld < 6 or out_stride %ld < hw %d",
+                      (long)q.det_stride, (long)q.out_stride, HW);
+        if (q.pooled)
+            MRCNN_REQUIRE(q.row_len >= 1 && q.row_stride >= q.row_len && q.pooled_batch_stride >= (int64_t)D * q.row_stride, MRCNN_ERR_INVALID,
+                          "test_mask_select_batch: row_len %ld, row_stride %ld, pooled_batch_stride %ld", (long)q.row_len, (long)q.row_stride, (long)q.pooled_batch_stride);
+        if (form == 0) {
+            MRCNN_REQUIRE(q.feat && q.w && q.bias, MRCNN_ERR_INVALID, "test_mask_select_batch: form 0 needs feat, w and bias");
+            MRCNN_REQUIRE(C >= 4 && C % 4 == 0, MRCNN_ERR_SHAPE, "test_mask_select_batch: c %d is not a positive multiple of 4", C);
+        } else if (form == 1) {
+            MRCNN_REQUIRE(q.partial && q.bias, MRCNN_ERR_INVALID, "test_mask_select_batch: form 1 needs partial and bias");
+            MRCNN_REQUIRE(parts >= 1, MRCNN_ERR_INVALID, "test_mask_select_batch: parts %d < 1", parts);
+        } else {
+            MRCNN_REQUIRE(q.masks, MRCNN_ERR_INVALID, "test_mask_select_batch: form 2 needs masks");
+        }
+        const bool f16 = q.dtype == MRCNN_F16;
+        const long det_sB = (long)R * q.det_stride, out_sB = (long)R * q.out_stride;
+
+        // the workspace: R rows per image, -1 wherever no launch writes
+        Carver carve;
+        const auto s_flags = carve.take<int32_t>((size_t)B * R), s_map = carve.take<int32_t>((size_t)B * R), s_cid = carve.take<int32_t>((size_t)B * R);
+        const auto s_kept = carve.take<int32_t>((size_t)B);
+        carve.alloc();
+        HIP_CHECK(hipMemset(carve.buf.p, 0xff, carve.size));
+        MaskSelectWorkspace ws;
+        ws.flags = carve[s_flags]; ws.mapping = carve[s_map]; ws.sel_cid = carve[s_cid]; ws.kept = carve[s_kept]; ws.ld = R;
+        auto rows_to_host = [&](int32_t* dst, const int32_t* dev, int n) {
+            HIP_CHECK(hipMemcpy2D(dst, (size_t)n * 4, dev, (size_t)R * 4, (size_t)n * 4, (size_t)B, hipMemcpyDeviceToHost));
+        };
+
+        DevBuf dpool, ddet, dout, dfeat, dw, dbias, dpart, dmasks;
+        if (q.flags) HIP_CHECK(hipMemcpy2D(ws.flags, (size_t)R * 4, q.flags, (size_t)D * 4, (size_t)D * 4, (size_t)B, hipMemcpyHostToDevice));
+        else (f16 ? upload_f16 : upload_f32)(dpool, q.pooled, (size_t)B * q.pooled_batch_stride, 0);
+        upload_f32(ddet, q.det, (size_t)B * det_sB);
+        upload_f32(dout, q.out, (size_t)B * out_sB);
+        if (form == 0) {
+            (f16 ? upload_f16 : upload_f32)(dfeat, q.feat, (size_t)B * D * HW * C, 0);
+            upload_f32(dw, q.w, (size_t)nc * C);
+        }
+        if (form != 2) upload_f32(dbias, q.bias, (size_t)nc);
+        if (form == 1) {                               // k_mask_select_partials strides the images by the rows it pads: R rows each, zero behind the first D
+            const size_t row = (size_t)HW * parts;
+            dpart.alloc((size_t)B * R * row * 4);
+            HIP_CHECK(hipMemset(dpart.p, 0, (size_t)B * R * row * 4));
+            HIP_CHECK(hipMemcpy2D(dpart.p, (size_t)R * row * 4, q.partial, (size_t)D * row * 4, (size_t)D * row * 4, (size_t)B, hipMemcpyHostToDevice));
+        }
+        if (form == 2) upload_f32(dmasks, q.masks, (size_t)B * D * nc * HW);
+
+        Stream st;
+        Drain drain{st.s};
+        mask_valid_rows_forward(st.s, q.pooled ? dpool.p : nullptr, (long)q.pooled_batch_stride, (long)q.row_stride, (long)q.row_len, D, B, ws, q.dtype);
+        if (form == 1 || q.sel_cid) mask_select_classes(st.s, ddet.as<float>(), det_sB, (long)q.det_stride, R, B, nc, ws, ws.sel_cid);
+        if (form == 0)
+            mask_select_forward(st.s, dfeat.p, (long)D * HW * C, HW, C, dw.as<float>(), dbias.as<float>(), nc, ddet.as<float>(), det_sB, (long)q.det_stride, R, B, ws,
+                                dout.as<float>(), out_sB, (long)q.out_stride, q.dtype);
+        else if (form == 1)
+            mask_select_from_partials(st.s, dpart.as<float>(), parts, HW, dbias.as<float>(), nc, ddet.as<float>(), det_sB, (long)q.det_stride, R, B, ws,
+                                      dout.as<float>(), out_sB, (long)q.out_stride);
+        else
+            mask_select_from_full_forward(st.s, dmasks.as<float>(), (long)D * nc * HW, HW, nc, ddet.as<float>(), det_sB, (long)q.det_stride, R, B, ws,
+                                          dout.as<float>(), out_sB, (long)q.out_stride);
+        HIP_CHECK(hipStreamSynchronize(st.s));
+        HIP_CHECK(hipMemcpy(q.out, dout.p, (size_t)B * out_sB * 4, hipMemcpyDeviceToHost));
+        if (q.row_flags) rows_to_host(q.row_flags, ws.flags, D);
+        if (q.mapping) rows_to_host(q.mapping, ws.mapping, D);
+        if (q.sel_cid) rows_to_host(q.sel_cid, ws.sel_cid, R);
+        if (q.kept) HIP_CHECK(hipMemcpy(q.kept, ws.kept, (size_t)B * 4, hipMemcpyDeviceToHost));
+    });
+}
+
 extern "C" int mrcnn_model_conv_profile_enable(mrcnn_model* model, int on)
 {
     return guarded([&] {

@@ -472,6 +472,8 @@ struct MaskSelectWorkspace {
     int32_t* mapping = nullptr;    // [B][D] compact index → row
     int32_t* kept = nullptr;       // [B]
     int32_t* sel_cid = nullptr;    // [B][D] class per row for the fused tail (mask_select_classes), -1 = not written
+    int ld = 0;                    // rows per image of the three [B][D] arrays; 0 = the D of each call.  Set it where the predicate runs on
+                                   // fewer rows than the select pads (the stand-alone layer's D feature rows under det_count detections) in a batch.
 };
 // flags/mapping of MultiArrayBatchProvider(removeZeros:true): pooled (B, D, row_len) contiguous rows.
 // pooled == nullptr: ws.flags already holds the predicate (written by roi_align_forward's row_flags from the fp32

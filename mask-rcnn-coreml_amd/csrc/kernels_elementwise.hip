@@ -246,23 +246,23 @@ void copy_rows_forward(hipStream_t s, const float* src, long src_stride, long n,
 // kept iff every element is != 0.
 template <typename T>
 __global__ __launch_bounds__(256) void k_mask_row_flags(const T* __restrict__ pooled, long pooled_sB, long row_stride,
-                                                        long row_len, int D, int32_t* __restrict__ flags)
+                                                        long row_len, int ld, int32_t* __restrict__ flags)
 {
     const int d = blockIdx.x, b = blockIdx.y;
     const T* r = pooled + (size_t)b * pooled_sB + (size_t)d * row_stride;
     int ok = 1;
     for (long e = threadIdx.x; e < row_len; e += 256) ok &= ((float)r[e] != 0.0f) ? 1 : 0;
     ok = __syncthreads_and(ok);
-    if (threadIdx.x == 0) flags[(size_t)b * D + d] = ok;
+    if (threadIdx.x == 0) flags[(size_t)b * ld + d] = ok;
 }
-__global__ void k_mask_row_compact(const int32_t* __restrict__ flags, int D, int32_t* __restrict__ mapping,
+__global__ void k_mask_row_compact(const int32_t* __restrict__ flags, int D, int ld, int32_t* __restrict__ mapping,
                                    int32_t* __restrict__ kept)
 {
     const int b = blockIdx.x;
     if (threadIdx.x != 0) return;
     int k = 0;
     for (int d = 0; d < D; ++d)
-        if (flags[(size_t)b * D + d]) mapping[(size_t)b * D + k++] = d;
+        if (flags[(size_t)b * ld + d]) mapping[(size_t)b * ld + k++] = d;
     kept[b] = k;
 }
 
@@ -270,11 +270,12 @@ void mask_valid_rows_forward(hipStream_t s, const void* pooled, long pooled_sB, 
                              int B, const MaskSelectWorkspace& ws, int dtype)
 {
     if (D <= 0 || B <= 0) return;
+    const int ld = ws.ld ? ws.ld : D;
     if (!pooled) { /* flags come from the ROIAlign kernel */ }
     else if (dtype == MRCNN_F16)
-        hipLaunchKernelGGL(k_mask_row_flags<_Float16>, dim3(D, B), dim3(256), 0, s, (const _Float16*)pooled, pooled_sB, row_stride, row_len, D, ws.flags);
-    else hipLaunchKernelGGL(k_mask_row_flags<float>, dim3(D, B), dim3(256), 0, s, (const float*)pooled, pooled_sB, row_stride, row_len, D, ws.flags);
-    hipLaunchKernelGGL(k_mask_row_compact, dim3(B), dim3(64), 0, s, ws.flags, D, ws.mapping, ws.kept);
+        hipLaunchKernelGGL(k_mask_row_flags<_Float16>, dim3(D, B), dim3(256), 0, s, (const _Float16*)pooled, pooled_sB, row_stride, row_len, ld, ws.flags);
+    else hipLaunchKernelGGL(k_mask_row_flags<float>, dim3(D, B), dim3(256), 0, s, (const float*)pooled, pooled_sB, row_stride, row_len, ld, ws.flags);
+    hipLaunchKernelGGL(k_mask_row_compact, dim3(B), dim3(64), 0, s, ws.flags, D, ld, ws.mapping, ws.kept);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -285,7 +286,7 @@ void mask_valid_rows_forward(hipStream_t s, const void* pooled, long pooled_sB, 
 template <typename T>
 __global__ __launch_bounds__(256) void k_mask_select(const T* __restrict__ feat, long feat_sB, int HW, int C,
                                                      const float* __restrict__ w, const float* __restrict__ bias, int nc,
-                                                     const float* __restrict__ det, long det_sB, long det_stride, int D,
+                                                     const float* __restrict__ det, long det_sB, long det_stride, int ld,
                                                      const int32_t* __restrict__ mapping, const int32_t* __restrict__ kept,
                                                      float* __restrict__ out, long out_sB, long out_stride)
 {
@@ -297,7 +298,7 @@ __global__ __launch_bounds__(256) void k_mask_select(const T* __restrict__ feat,
         for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < out_stride; e += (long)gridDim.x * 256) ob[(size_t)i * out_stride + e] = 0.0f;
         return;
     }
-    const int actual = mapping[(size_t)b * D + i];
+    const int actual = mapping[(size_t)b * ld + i];
     if (actual >= nk) return;                       // would be overwritten by the zero padding
     int cid = (int)det[(size_t)b * det_sB + (size_t)i * det_stride + 4];
     cid = cid < 0 ? 0 : (cid >= nc ? nc - 1 : cid);
@@ -324,10 +325,10 @@ void mask_select_forward(hipStream_t s, const void* feat, long feat_sB, int HW, 
     MRCNN_REQUIRE(C % 4 == 0, MRCNN_ERR_SHAPE, "mask head: C %% 4 != 0");
     if (dtype == MRCNN_F16)
         hipLaunchKernelGGL(k_mask_select<_Float16>, dim3(49, D, B), dim3(256), 0, s, (const _Float16*)feat, feat_sB, HW, C, w, bias, nc, det,
-                           det_sB, det_stride, D, ws.mapping, ws.kept, out, out_sB, out_stride);
+                           det_sB, det_stride, ws.ld ? ws.ld : D, ws.mapping, ws.kept, out, out_sB, out_stride);
     else
         hipLaunchKernelGGL(k_mask_select<float>, dim3(49, D, B), dim3(256), 0, s, (const float*)feat, feat_sB, HW, C, w, bias, nc, det, det_sB,
-                           det_stride, D, ws.mapping, ws.kept, out, out_sB, out_stride);
+                           det_stride, ws.ld ? ws.ld : D, ws.mapping, ws.kept, out, out_sB, out_stride);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -336,32 +337,32 @@ void mask_select_forward(hipStream_t s, const void* feat, long feat_sB, int HW, 
 // class's 1x1 filter (conv_epilogue, ConvDesc::sel_partial) instead of its 256-channel fp32 output (642 MB per batch of 8
 // that this layer used to read back).  Same control flow as k_mask_select — what TimeDistributedMaskLayer.swift:58-89 writes.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(128) void k_mask_select_classes(const float* __restrict__ det, long det_sB, long det_stride, int D, int nc,
+__global__ __launch_bounds__(128) void k_mask_select_classes(const float* __restrict__ det, long det_sB, long det_stride, int D, int ld, int nc,
                                                              const int32_t* __restrict__ mapping, const int32_t* __restrict__ kept,
                                                              int32_t* __restrict__ sel_cid)
 {
     const int b = blockIdx.x;
     const int nk = kept[b];
-    for (int r = threadIdx.x; r < D; r += blockDim.x) sel_cid[(size_t)b * D + r] = -1;
+    for (int r = threadIdx.x; r < D; r += blockDim.x) sel_cid[(size_t)b * ld + r] = -1;
     __syncthreads();
     for (int i = threadIdx.x; i < nk; i += blockDim.x) {
-        const int actual = mapping[(size_t)b * D + i];
+        const int actual = mapping[(size_t)b * ld + i];
         if (actual >= nk) continue;                     // would be overwritten by the zero padding
         int cid = (int)det[(size_t)b * det_sB + (size_t)i * det_stride + 4];      // the COMPACT index's class (:71)
         cid = cid < 0 ? 0 : (cid >= nc ? nc - 1 : cid);
-        sel_cid[(size_t)b * D + actual] = cid;
+        sel_cid[(size_t)b * ld + actual] = cid;
     }
 }
 
 __global__ __launch_bounds__(256) void k_mask_select_partials(const float* __restrict__ partial, int parts, int HW,
-                                                              const float* __restrict__ bias, int D,
+                                                              const float* __restrict__ bias, int D, int ld,
                                                               const int32_t* __restrict__ sel_cid, const int32_t* __restrict__ kept,
                                                               float* __restrict__ out, long out_sB, long out_stride)
 {
     const int r = blockIdx.y, b = blockIdx.z;
     const int nk = kept[b];
     float* orow = out + (size_t)b * out_sB + (size_t)r * out_stride;
-    const int cid = sel_cid[(size_t)b * D + r];
+    const int cid = sel_cid[(size_t)b * ld + r];
     if (r >= nk) {                                       // zero padding (:87-89)
         for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < out_stride; e += (long)gridDim.x * 256) orow[e] = 0.0f;
         return;
@@ -380,7 +381,7 @@ void mask_select_classes(hipStream_t s, const float* det, long det_sB, long det_
                          const MaskSelectWorkspace& ws, int32_t* sel_cid)
 {
     if (D <= 0 || B <= 0) return;
-    hipLaunchKernelGGL(k_mask_select_classes, dim3(B), dim3(128), 0, s, det, det_sB, det_stride, D, nc, ws.mapping, ws.kept, sel_cid);
+    hipLaunchKernelGGL(k_mask_select_classes, dim3(B), dim3(128), 0, s, det, det_sB, det_stride, D, ws.ld ? ws.ld : D, nc, ws.mapping, ws.kept, sel_cid);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -390,14 +391,14 @@ void mask_select_from_partials(hipStream_t s, const float* partial, int parts, i
 {
     (void)nc; (void)det; (void)det_sB; (void)det_stride;
     if (D <= 0 || B <= 0) return;
-    hipLaunchKernelGGL(k_mask_select_partials, dim3((HW + 255) / 256, D, B), dim3(256), 0, s, partial, parts, HW, bias, D, ws.sel_cid, ws.kept,
+    hipLaunchKernelGGL(k_mask_select_partials, dim3((HW + 255) / 256, D, B), dim3(256), 0, s, partial, parts, HW, bias, D, ws.ld ? ws.ld : D, ws.sel_cid, ws.kept,
                        out, out_sB, out_stride);
     HIP_CHECK(hipGetLastError());
 }
 
 __global__ __launch_bounds__(256) void k_mask_select_full(const float* __restrict__ masks, long masks_sB, int HW, int nc,
                                                           const float* __restrict__ det, long det_sB, long det_stride,
-                                                          int D, const int32_t* __restrict__ mapping,
+                                                          int ld, const int32_t* __restrict__ mapping,
                                                           const int32_t* __restrict__ kept, float* __restrict__ out,
                                                           long out_sB, long out_stride)
 {
@@ -408,7 +409,7 @@ __global__ __launch_bounds__(256) void k_mask_select_full(const float* __restric
         for (long e = threadIdx.x; e < out_stride; e += 256) ob[(size_t)i * out_stride + e] = 0.0f;
         return;
     }
-    const int actual = mapping[(size_t)b * D + i];
+    const int actual = mapping[(size_t)b * ld + i];
     if (actual >= nk) return;
     int cid = (int)det[(size_t)b * det_sB + (size_t)i * det_stride + 4];
     cid = cid < 0 ? 0 : (cid >= nc ? nc - 1 : cid);
@@ -422,7 +423,7 @@ void mask_select_from_full_forward(hipStream_t s, const float* masks, long masks
 {
     if (D <= 0 || B <= 0) return;
     hipLaunchKernelGGL(k_mask_select_full, dim3(D, B), dim3(256), 0, s, masks, masks_sB, HW, nc, det, det_sB, det_stride,
-                       D, ws.mapping, ws.kept, out, out_sB, out_stride);
+                       ws.ld ? ws.ld : D, ws.mapping, ws.kept, out, out_sB, out_stride);
     HIP_CHECK(hipGetLastError());
 }
 
