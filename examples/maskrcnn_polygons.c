@@ -2,16 +2,19 @@
  * maskrcnn_polygons.c — run-length masks handed on as geometry, in plain C99 over include/maskrcnn_hip.h: an RLE set is read from a
  * text file, mrcnn_rle_to_polygons traces the boundary of every mask on the GPU (the size query first, then the call), and the rings
  * are printed, one per line, with their signed areas: positive for an outline, negative for a hole.  With --tolerance T the rings are
- * simplified first (mrcnn_polygons_simplify, Douglas-Peucker within T pixels): the areas printed stay the pixel areas.
+ * simplified first (mrcnn_polygons_simplify, Douglas-Peucker within T pixels): the areas printed stay the pixel areas.  With
+ * --geojson FILE the traced rings are nested into outlines and their holes (mrcnn_polygons_nest) and FILE receives a GeoJSON
+ * FeatureCollection: one Feature per mask that has a ring, a Polygon for one outline and a MultiPolygon for several, every hole with the
+ * outline it lies in.  The nesting is that of the traced rings; a tolerance only changes the vertices written.
  *
  *   cc -std=c99 -Iinclude examples/maskrcnn_polygons.c -Lmask-rcnn-coreml_amd -lmaskrcnn_hip \
  *      -Wl,-rpath,$PWD/mask-rcnn-coreml_amd -Wl,-rpath-link,/opt/rocm/lib -o maskrcnn_polygons
- *   ./maskrcnn_polygons [--host] [--tolerance T] <set.txt>
+ *   ./maskrcnn_polygons [--host] [--tolerance T] [--geojson FILE] <set.txt>
  *
  * <set.txt> holds whitespace-separated integers: n_images and slots; then per image its height and width and, for each of its `slots`
  * RLEs, the number of runs followed by the runs (column-major, the first run counts zeros) — the layout mrcnn_masks_rle_source,
  * mrcnn_merge_tiles and mrcnn_unite_tiles write.  --host calls the sequential definitions, mrcnn_rle_to_polygons_host and
- * mrcnn_polygons_simplify_host, which need no GPU.  Exit status 0 on success; on failure the mrcnn_last_error() text goes to stderr and the status code is the exit status.
+ * mrcnn_polygons_simplify_host (and mrcnn_polygons_nest_host), which need no GPU.  Exit status 0 on success; on failure the mrcnn_last_error() text goes to stderr and the status code is the exit status.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -30,13 +33,69 @@ static int trace(int host, const uint32_t* counts, const int64_t* run_offsets, i
                                  ring_areas, ring_capacity, xy, vertex_capacity);
 }
 
+/* one ring as a closed GeoJSON ring: its first vertex repeated, an exterior with positive shoelace area and a hole with negative (a
+ * traced ring has that already; a simplified one is reversed where it has not) */
+static void write_ring(FILE* g, const int32_t* xy, int64_t v0, int64_t v1, int exterior)
+{
+    int64_t twice = 0;
+    for (int64_t v = v0; v < v1; ++v) {
+        const int64_t u = v + 1 < v1 ? v + 1 : v0;
+        twice += (int64_t)xy[2 * v] * xy[2 * u + 1] - (int64_t)xy[2 * u] * xy[2 * v + 1];
+    }
+    const int reverse = twice != 0 && (twice < 0) == (exterior != 0);
+    fprintf(g, "[[%d,%d]", (int)xy[2 * v0], (int)xy[2 * v0 + 1]);
+    for (int64_t j = 1; j < v1 - v0; ++j) {
+        const int64_t v = reverse ? v1 - j : v0 + j;
+        fprintf(g, ",[%d,%d]", (int)xy[2 * v], (int)xy[2 * v + 1]);
+    }
+    fprintf(g, ",[%d,%d]]", (int)xy[2 * v0], (int)xy[2 * v0 + 1]);
+}
+
+/* The FeatureCollection of the set: polygon p owns ring_order[poly_rings[p] .. poly_rings[p+1]), its shell first; the polygons of RLE k
+ * are [rle_polys[k], rle_polys[k+1]).  A shell with fewer than 3 vertices left is dropped with its holes, such a hole alone. */
+static void write_geojson(FILE* g, size_t n, int slots, const int64_t* rle_rings, const int64_t* ring_offsets, const int64_t* ring_areas, const int32_t* xy,
+                          const int64_t* rle_polys, const int64_t* poly_rings, const int64_t* ring_order)
+{
+    int features = 0;
+    fprintf(g, "{\"type\":\"FeatureCollection\",\"features\":[");
+    for (size_t k = 0; k < n; ++k) {
+        int64_t shells = 0, area = 0;
+        for (int64_t p = rle_polys[k]; p < rle_polys[k + 1]; ++p) {
+            const int64_t s = ring_order[poly_rings[p]];
+            shells += ring_offsets[s + 1] - ring_offsets[s] >= 3;
+        }
+        if (!shells) continue;
+        for (int64_t r = rle_rings[k]; r < rle_rings[k + 1]; ++r) area += ring_areas[r];
+        fprintf(g, "%s\n{\"type\":\"Feature\",\"geometry\":{\"type\":\"%s\",\"coordinates\":%s", features++ ? "," : "", shells > 1 ? "MultiPolygon" : "Polygon",
+                shells > 1 ? "[" : "");
+        int written = 0;
+        for (int64_t p = rle_polys[k]; p < rle_polys[k + 1]; ++p) {
+            const int64_t s = ring_order[poly_rings[p]];
+            if (ring_offsets[s + 1] - ring_offsets[s] < 3) continue;
+            fprintf(g, "%s[", written++ ? "," : "");
+            write_ring(g, xy, ring_offsets[s], ring_offsets[s + 1], 1);
+            for (int64_t j = poly_rings[p] + 1; j < poly_rings[p + 1]; ++j) {
+                const int64_t h = ring_order[j];
+                if (ring_offsets[h + 1] - ring_offsets[h] < 3) continue;
+                fprintf(g, ",");
+                write_ring(g, xy, ring_offsets[h], ring_offsets[h + 1], 0);
+            }
+            fprintf(g, "]");
+        }
+        fprintf(g, "%s},\"properties\":{\"image\":%d,\"row\":%d,\"area\":%lld}}", shells > 1 ? "]" : "", (int)(k / (size_t)slots), (int)(k % (size_t)slots),
+                (long long)area);
+    }
+    fprintf(g, "\n]}\n");
+}
+
 int main(int argc, char** argv)
 {
     const int host = argc > 1 && strcmp(argv[1], "--host") == 0;
     const int simplify = argc > 1 + host && strcmp(argv[1 + host], "--tolerance") == 0;
-    const int file = 1 + host + 2 * simplify;
+    const int geo = argc > 1 + host + 2 * simplify && strcmp(argv[1 + host + 2 * simplify], "--geojson") == 0;
+    const int file = 1 + host + 2 * simplify + 2 * geo;
     if (argc != file + 1) {
-        fprintf(stderr, "usage: %s [--host] [--tolerance T] <set.txt>\n", argv[0]);
+        fprintf(stderr, "usage: %s [--host] [--tolerance T] [--geojson FILE] <set.txt>\n", argv[0]);
         return 64;
     }
     const double tolerance = simplify ? atof(argv[2 + host]) : 0.0;
@@ -92,6 +151,25 @@ int main(int argc, char** argv)
         fprintf(stderr, "mrcnn_rle_to_polygons%s failed (%d): %s\n", host ? "_host" : "", st, mrcnn_last_error());
         return st;
     }
+    int64_t *rle_polys = NULL, *poly_rings = NULL, *ring_order = NULL;
+    if (geo) {
+        /* nested where the rings are still the traced ones: simplification keeps them one for one, so the nesting indexes the simplified
+         * rings too.  n_polys <= rings: the buffers are sized by the rings, no size query. */
+        int64_t* parent = (int64_t*)malloc(sizeof(int64_t) * (size_t)(rings + 1));
+        int32_t* depth = (int32_t*)malloc(sizeof(int32_t) * (size_t)(rings + 1));
+        int64_t polys = 0;
+        rle_polys = (int64_t*)malloc(sizeof(int64_t) * (n + 1));
+        poly_rings = (int64_t*)malloc(sizeof(int64_t) * (size_t)(rings + 1));
+        ring_order = (int64_t*)malloc(sizeof(int64_t) * (size_t)(rings + 1));
+        if (!parent || !depth || !rle_polys || !poly_rings || !ring_order) { fprintf(stderr, "out of memory\n"); return 70; }
+        st = host ? mrcnn_polygons_nest_host(rle_rings, (int64_t)n, ring_offsets, xy, rings, parent, depth, rle_polys, poly_rings, ring_order, &polys)
+                  : mrcnn_polygons_nest(rle_rings, (int64_t)n, ring_offsets, xy, rings, MRCNN_HOST, parent, depth, rle_polys, poly_rings, ring_order, &polys);
+        if (st != MRCNN_OK) {
+            fprintf(stderr, "mrcnn_polygons_nest%s failed (%d): %s\n", host ? "_host" : "", st, mrcnn_last_error());
+            return st;
+        }
+        free(depth); free(parent);
+    }
     if (simplify) {
         /* the input's vertex count always suffices as the capacity: no size query.  The rings stay in their order, so rle_rings and the
          * pixel areas still go with them. */
@@ -117,6 +195,13 @@ int main(int argc, char** argv)
             for (int64_t v = ring_offsets[r]; v < ring_offsets[r + 1]; ++v) printf(" %d,%d", (int)xy[2 * v], (int)xy[2 * v + 1]);
             printf("\n");
         }
+    if (geo) {
+        FILE* g = fopen(argv[file - 1], "w");
+        if (!g) { fprintf(stderr, "cannot write %s\n", argv[file - 1]); return 73; }
+        write_geojson(g, n, slots, rle_rings, ring_offsets, ring_areas, xy, rle_polys, poly_rings, ring_order);
+        if (fclose(g) != 0) { fprintf(stderr, "cannot write %s\n", argv[file - 1]); return 74; }
+        free(ring_order); free(poly_rings); free(rle_polys);
+    }
     free(xy); free(ring_areas); free(ring_offsets); free(counts); free(rle_rings); free(run_offsets); free(widths); free(heights);
     return 0;
 }

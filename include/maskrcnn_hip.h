@@ -920,8 +920,8 @@ MRCNN_API int mrcnn_rle_from_polygons_batch(const double* xy, const int64_t* pol
  * written; all of these before a device is looked for, except the sums of a set in device memory.  No gfx950 device -> MRCNN_ERR_HIP
  * from the device entry (no CPU fallback).
  * Simplification (Douglas-Peucker) is the next entry's, mrcnn_polygons_simplify, which takes ring_offsets and xy as they are written
- * here.  Not here: smoothing, sub-pixel contours from the 28x28 probabilities, and nesting the rings into a tree of outlines and their
- * holes — a hole is a ring of negative area and nothing more.  examples/maskrcnn_polygons.c. */
+ * here; nesting the rings into outlines and their holes is mrcnn_polygons_nest's, below: here a hole is a ring of negative area and
+ * nothing more.  Not here: smoothing and sub-pixel contours from the 28x28 probabilities.  examples/maskrcnn_polygons.c. */
 #define MRCNN_POLYGON_LDS_CORNERS 1024
 MRCNN_API int mrcnn_rle_to_polygons(const uint32_t* counts, const int64_t* run_offsets, int n_images, int slots, const int32_t* heights,
                                     const int32_t* widths, int memspace, int64_t* rle_rings, int64_t* n_rings, int64_t* n_vertices,
@@ -977,6 +977,68 @@ MRCNN_API int mrcnn_polygons_simplify(const int64_t* ring_offsets, const int32_t
 MRCNN_API int mrcnn_polygons_simplify_host(const int64_t* ring_offsets, const int32_t* xy, int64_t n_rings, double tolerance,
                                            int64_t* out_ring_offsets, int64_t* out_areas2, int32_t* out_xy, int64_t* out_src_index,
                                            int64_t* n_vertices_out, int64_t vertex_capacity);
+
+/* Polygon rings nested on the GPU into outlines and their holes: which ring lies directly inside which, how deep, and the rings grouped
+ * into polygons of one shell and its holes — what GeoJSON, WKT and GIS layers take.  The input is rings in the tracer's layout: the rings
+ * of RLE k are [rle_rings[k], rle_rings[k+1]) (rle_rings has n_rles + 1 entries, starts at 0 and ends at n_rings), ring r = the vertices
+ * [ring_offsets[r], ring_offsets[r+1]) of xy (int32 x then y).  Any integer rings are legal, as for mrcnn_polygons_simplify: every
+ * coordinate in 0..32767, every ring closed and under 2^31 vertices, offsets that do not decrease.  The rule is total on all of them;
+ * only traced rings come with the geometric guarantee.  Everything is integer arithmetic; no input array of areas is trusted.  Rings are
+ * nested among the rings of their own RLE, never across RLEs; parent holds GLOBAL ring indices.
+ * area2(r).  Twice the signed shoelace area of ring r, sum(x_i*y_{i+1} - x_{i+1}*y_i), 64 bits, from xy.
+ * probe(r).  The point (X0 + 1/2, Y0 + 1/2), where (X0, Y0) is r's first vertex; a ring without vertices has no probe and no parent.
+ *   For a traced ring the probe is the centre of a pixel that r encloses, a set pixel for an outline and an unset pixel for a hole: the
+ *   ring starts at its smallest vertex and nothing of the ring lies left of its start vertex (the tracer's geometry, above), so the unit
+ *   edge (X0, Y0) - (X0, Y0 + 1) is the ring's only crossing of a ray from the probe towards -x.
+ * contains(q, r).  The ray from probe(r) towards -x crosses an odd number of q's edges, the closing edge included.  An edge a -> b
+ *   crosses iff (ay <= Y0) != (by <= Y0) and its intersection with the line y = Y0 + 1/2 lies at x < X0 + 1/2, decided in doubled
+ *   integers by the sign of (bx - ax)*(2*Y0 + 1 - 2*ay) - (by - ay)*(2*X0 + 1 - 2*ax), corrected by the sign of by - ay: no division, no
+ *   floating point; 0 — the probe on the edge's line — is not a crossing.  No vertex lies on the ray's line.  For axis-parallel rings this
+ *   counts the vertical edges with x <= X0 whose y-span holds Y0.  A ring of fewer than 3 vertices contains nothing.
+ * parent(r).  Among the rings q != r of the same RLE with contains(q, r), those that OUTRANK r: |area2(q)| > |area2(r)|, or equal with
+ *   q < r.  The parent is the one of smallest |area2|, a tie goes to the smallest index; -1 if there is none.  Outranking is a strict
+ *   total order, so the result is a forest on any input; on traced rings the parent is the innermost enclosing ring.
+ * depth(r).  The number of ancestors along the parent chain.  On traced rings even depth means outline (area > 0) and odd depth hole; a
+ *   hole's parent is the outline of the 4-connected component around it, an outline's parent the hole it is an island of.
+ * Polygons.  A ring of even depth is a shell, its children (of odd depth) are its holes.  The polygons of an RLE are ordered by their
+ *   shell's ring index; inside a polygon the shell comes first, then its holes by ring index.  An island inside a hole is a polygon of
+ *   its own.
+ * Outputs.
+ *   parent (n_rings, int64)         the global index of the ring's parent, or -1
+ *   depth (n_rings, int32)
+ *   rle_polys (n_rles + 1)          the polygons of RLE k are [rle_polys[k], rle_polys[k+1])
+ *   poly_rings (n_rings + 1)        polygon p of the whole set owns ring_order[poly_rings[p] .. poly_rings[p+1]), shell first;
+ *                                   *n_polys + 1 entries are written
+ *   ring_order (n_rings)            a permutation of the rings
+ *   *n_polys (host)                 n_polys <= n_rings: the buffers are sized by n_rings and there is no capacity protocol
+ * memspace holds for every array argument; n_polys is host memory.  n_rings = 0 is legal: rle_polys is all zeros and *n_polys = 0.
+ * Simplified rings.  mrcnn_polygons_simplify keeps the rings in their order and number, so a nesting computed on the TRACED rings
+ * indexes the simplified ones, one for one: nest first, then simplify.  Nesting simplified rings themselves is legal and yields a forest,
+ * but simplification does not preserve topology and the probe's guarantee is the traced rings' alone.
+ * mrcnn_polygons_nest_host is the definition: sequential plain C++, no GPU, host pointers; per ring it loops over the other rings of the
+ * RLE and over their edges.  mrcnn_polygons_nest equals it bit for bit in every array.  One wave per ring measures |area2|, the bounding
+ * box and the owning RLE; one workgroup per target ring finds the parent, its waves striding over the candidates — one whose bounding
+ * box does not hold the probe is skipped, which cannot change a parity — and their lanes over a candidate's edges; a thread per ring
+ * walks to the root; two prefix sums and a rank among siblings, counted by a wave, place every ring.  Eight launches and two scans,
+ * whatever the number of rings and RLEs; the host reads back one summary (are the arrays legal) before anything is written and the
+ * number of polygons at the end.
+ * Errors: null pointer, negative n_rles or n_rings, unknown memspace -> MRCNN_ERR_INVALID; rle_rings that does not start at 0, decreases
+ * or does not end at n_rings, offsets that are negative, decrease or span 2^31 vertices, a coordinate outside 0..32767 ->
+ * MRCNN_ERR_SHAPE, the message names the RLE or the ring and nothing is written; all of these before a device is looked for, except
+ * the contents of arrays in device memory, which one summary answers.  No gfx950 device -> MRCNN_ERR_HIP from the device entry (no CPU
+ * fallback).
+ * Not here: the work is O(rings x vertices) per RLE — small for detector masks (a few rings per detection; 317 rings on the README's
+ * large scene), large for a pathological plane such as a megapixel checkerboard.  The sweep that would replace the quadratic stage —
+ * per probe the nearest vertical edge to its left, then pointer jumping over "sibling of" — is not built.  The depth is one thread's walk
+ * to the root per ring, in one launch: on a deep chain such as concentric rings the lanes of a wave wait for the longest walk, which
+ * the quadratic stage before it has outweighed already; pointer jumping in rounds is not built.  Neither are WKT, topology
+ * repair of simplified rings, or nesting across RLEs.  examples/maskrcnn_polygons.c --geojson. */
+MRCNN_API int mrcnn_polygons_nest(const int64_t* rle_rings, int64_t n_rles, const int64_t* ring_offsets, const int32_t* xy, int64_t n_rings,
+                                  int memspace, int64_t* parent, int32_t* depth, int64_t* rle_polys, int64_t* poly_rings, int64_t* ring_order,
+                                  int64_t* n_polys);
+MRCNN_API int mrcnn_polygons_nest_host(const int64_t* rle_rings, int64_t n_rles, const int64_t* ring_offsets, const int32_t* xy, int64_t n_rings,
+                                       int64_t* parent, int32_t* depth, int64_t* rle_polys, int64_t* poly_rings, int64_t* ring_order,
+                                       int64_t* n_polys);
 
 #ifdef __cplusplus
 }

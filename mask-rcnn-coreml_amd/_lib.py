@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = [
     "mrcnn_render_detections_rle", "mrcnn_render_detections_rle_host",
     "mrcnn_rle_to_polygons", "mrcnn_rle_to_polygons_host",
     "mrcnn_polygons_simplify", "mrcnn_polygons_simplify_host",
+    "mrcnn_polygons_nest", "mrcnn_polygons_nest_host",
 ]
 # declared in include/maskrcnn_hip_test.h (test / measurement entry points of the same library)
 TEST_SYMBOLS = [
@@ -215,6 +216,9 @@ def lib():
     _simple = [vp, vp, vp, vp, i64p, C.c_int64]                   # out_ring_offsets, out_areas2, out_xy, out_src_index, n_vertices_out, capacity
     L.mrcnn_polygons_simplify.argtypes = [vp, vp, C.c_int64, C.c_double, C.c_int] + _simple
     L.mrcnn_polygons_simplify_host.argtypes = [vp, vp, C.c_int64, C.c_double] + _simple
+    _nest = [vp, vp, vp, vp, vp, i64p]                            # parent, depth, rle_polys, poly_rings, ring_order, n_polys
+    L.mrcnn_polygons_nest.argtypes = [vp, C.c_int64, vp, vp, C.c_int64, C.c_int] + _nest
+    L.mrcnn_polygons_nest_host.argtypes = [vp, C.c_int64, vp, vp, C.c_int64] + _nest
     L.mrcnn_rle_to_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_from_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_iou.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int64]

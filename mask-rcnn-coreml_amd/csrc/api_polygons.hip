@@ -1,9 +1,10 @@
 // api_polygons.hip — the C ABI of include/maskrcnn_hip.h, run-length masks to polygon rings: the host definition (polygons_host.cpp
-// behind it) and the device entry (kernels_polygons.hip); and the rings simplified: simplify_host.cpp and kernels_simplify.hip.  Every
-// argument error is answered before a device is looked for.
+// behind it) and the device entry (kernels_polygons.hip); the rings simplified: simplify_host.cpp and kernels_simplify.hip; and the rings
+// nested into outlines and their holes: nest_host.cpp and kernels_nest.hip.  Every argument error is answered before a device is looked for.
 #include <string.h>
 
 #include "api_util.h"
+#include "nest_host.h"
 #include "polygons_host.h"
 #include "simplify_host.h"
 #include "simplify_rule.h"
@@ -266,5 +267,111 @@ extern "C" int mrcnn_polygons_simplify(const int64_t* ring_offsets, const int32_
             if (needed) HIP_CHECK(hipMemcpy(out_xy, d_xy, (size_t)needed * 8, hipMemcpyDeviceToHost));
             if (out_src_index && needed) HIP_CHECK(hipMemcpy(out_src_index, d_src, (size_t)needed * 8, hipMemcpyDeviceToHost));
         }
+    });
+}
+
+extern "C" int mrcnn_polygons_nest_host(const int64_t* rle_rings, int64_t n_rles, const int64_t* ring_offsets, const int32_t* xy, int64_t n_rings,
+                                        int64_t* parent, int32_t* depth, int64_t* rle_polys, int64_t* poly_rings, int64_t* ring_order, int64_t* n_polys)
+{
+    return guarded([&] {
+        const char* who = "polygons_nest_host";
+        std::string err;
+        answer(nest::check_arguments(rle_rings, n_rles, ring_offsets, xy, n_rings, parent, depth, rle_polys, poly_rings, ring_order, n_polys, who, &err), err);
+        int64_t most = 0;
+        answer(nest::check_rle_rings(rle_rings, n_rles, n_rings, who, &err), err);
+        answer(simplify::check_offsets(ring_offsets, n_rings, who, &err, &most), err);
+        answer(simplify::check_coordinates(ring_offsets, xy, n_rings, who, &err), err);
+        nest::Nest t;
+        nest::nest_host(rle_rings, n_rles, ring_offsets, xy, n_rings, &t);
+        const size_t n = (size_t)n_rings;
+        if (n) {
+            memcpy(parent, t.parent.data(), n * sizeof(int64_t));
+            memcpy(depth, t.depth.data(), n * sizeof(int32_t));
+            memcpy(ring_order, t.ring_order.data(), n * sizeof(int64_t));
+        }
+        memcpy(rle_polys, t.rle_polys.data(), t.rle_polys.size() * sizeof(int64_t));
+        memcpy(poly_rings, t.poly_rings.data(), t.poly_rings.size() * sizeof(int64_t));
+        *n_polys = (int64_t)t.poly_rings.size() - 1;
+    });
+}
+
+extern "C" int mrcnn_polygons_nest(const int64_t* rle_rings, int64_t n_rles, const int64_t* ring_offsets, const int32_t* xy, int64_t n_rings, int memspace,
+                                   int64_t* parent, int32_t* depth, int64_t* rle_polys, int64_t* poly_rings, int64_t* ring_order, int64_t* n_polys)
+{
+    return guarded([&] {
+        const char* who = "polygons_nest";
+        std::string err;
+        answer(nest::check_arguments(rle_rings, n_rles, ring_offsets, xy, n_rings, parent, depth, rle_polys, poly_rings, ring_order, n_polys, who, &err), err);
+        MRCNN_REQUIRE(memspace == MRCNN_HOST || memspace == MRCNN_DEVICE, MRCNN_ERR_INVALID, "%s: unknown memspace %d", who, memspace);
+        MRCNN_REQUIRE(n_rings < (1LL << 31) && n_rles < (1LL << 31) - 1, MRCNN_ERR_SHAPE, "%s: %lld rings in %lld RLEs: too many for one call", who,
+                      (long long)n_rings, (long long)n_rles);
+        const bool dev = memspace == MRCNN_DEVICE;
+        const size_t n = (size_t)n_rings, k = (size_t)n_rles;
+        int64_t most = 0, v_in = 0;
+        if (!dev) {                                              // rings in host memory: a bad one needs no device to be named
+            answer(nest::check_rle_rings(rle_rings, n_rles, n_rings, who, &err), err);
+            answer(simplify::check_offsets(ring_offsets, n_rings, who, &err, &most), err);
+            answer(simplify::check_coordinates(ring_offsets, xy, n_rings, who, &err), err);
+            v_in = ring_offsets[n];
+        }
+        require_gpu();
+        Stream st;
+        hipStream_t s = st.s;
+        DevBuf t_rle, t_off, t_xy;
+        Carver sc, oc;
+        Drain drain{s};                                          // (declared behind the buffers: the stream drains before they are freed)
+        NestRings in{reinterpret_cast<const long long*>(rle_rings), (long long)n_rles, reinterpret_cast<const long long*>(ring_offsets), xy, (long long)n_rings};
+        if (!dev) {                                              // (all of xy up to the last ring's end: the offsets hold as they are)
+            t_rle.alloc((k + 1) * 8); t_off.alloc((n + 1) * 8); t_xy.alloc((size_t)v_in * 8);
+            HIP_CHECK(hipMemcpy(t_rle.p, rle_rings, (k + 1) * 8, hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(t_off.p, ring_offsets, (n + 1) * 8, hipMemcpyHostToDevice));
+            if (v_in) HIP_CHECK(hipMemcpy(t_xy.p, xy, (size_t)v_in * 8, hipMemcpyHostToDevice));
+            in.rle_rings = t_rle.as<long long>(); in.ring_offsets = t_off.as<long long>(); in.xy = t_xy.as<int32_t>();
+        }
+        // one scratch allocation: the summary | per ring its size, box, RLE, the three counts | the two prefix sums
+        const auto s_sum = sc.take<unsigned long long>(3);
+        const auto s_size = sc.take<unsigned long long>(n);
+        const auto s_box = sc.take<int4>(n);
+        const auto s_rle = sc.take<int32_t>(n);
+        const auto s_shell = sc.take<uint32_t>(n), s_holes = sc.take<uint32_t>(n), s_rings = sc.take<uint32_t>(n);
+        const auto s_polygon = sc.take<unsigned long long>(n + 1), s_start = sc.take<unsigned long long>(n + 1);
+        sc.alloc();
+        const NestWork w{sc[s_size], sc[s_box], sc[s_rle], sc[s_shell], sc[s_holes], sc[s_rings], sc[s_polygon], sc[s_start]};
+        nest_measure_forward(s, in, w, sc[s_sum]);
+        unsigned long long sum[3] = {0, 0, 0};                   // the one read-back before anything is written: are the rings legal
+        HIP_CHECK(hipMemcpyAsync(sum, sc[s_sum], sizeof sum, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (sum[0] != ~0ull) answer(nest::bad_rle_rings((int64_t)sum[0], n_rings, who, &err), err);
+        if (sum[1] != ~0ull) answer(simplify::bad_offsets((int64_t)sum[1], who, &err), err);
+        if (sum[2] != ~0ull) answer(simplify::bad_coordinate((int64_t)sum[2], who, &err), err);
+        if (n == 0) {                                            // no rings: no polygons in any RLE
+            if (dev) HIP_CHECK(hipMemset(rle_polys, 0, (k + 1) * 8));
+            else memset(rle_polys, 0, (k + 1) * 8);
+            HIP_CHECK(hipMemcpy(poly_rings, rle_polys, 8, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToHost));
+            *n_polys = 0;
+            return;
+        }
+        long long *d_parent = reinterpret_cast<long long*>(parent), *d_polys = reinterpret_cast<long long*>(rle_polys);
+        long long *d_rings = reinterpret_cast<long long*>(poly_rings), *d_order = reinterpret_cast<long long*>(ring_order);
+        int32_t* d_depth = depth;
+        const auto o_parent = oc.take<long long>(dev ? 0 : n), o_polys = oc.take<long long>(dev ? 0 : k + 1), o_rings = oc.take<long long>(dev ? 0 : n + 1);
+        const auto o_order = oc.take<long long>(dev ? 0 : n);
+        const auto o_depth = oc.take<int32_t>(dev ? 0 : n);
+        if (!dev) {
+            oc.alloc();
+            d_parent = oc[o_parent]; d_polys = oc[o_polys]; d_rings = oc[o_rings]; d_order = oc[o_order]; d_depth = oc[o_depth];
+        }
+        nest_forward(s, in, w, d_parent, d_depth, d_polys, d_rings, d_order);
+        unsigned long long polys = 0;                            // the second read-back: the number of polygons
+        HIP_CHECK(hipMemcpyAsync(&polys, w.polygon + n, sizeof polys, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (!dev) {
+            HIP_CHECK(hipMemcpy(parent, d_parent, n * 8, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(depth, d_depth, n * 4, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(rle_polys, d_polys, (k + 1) * 8, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(poly_rings, d_rings, (size_t)(polys + 1) * 8, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(ring_order, d_order, n * 8, hipMemcpyDeviceToHost));
+        }
+        *n_polys = (int64_t)polys;
     });
 }

@@ -629,6 +629,27 @@ void simplify_count_forward(hipStream_t s, const SimplifyRings& in, unsigned lon
 void simplify_write_forward(hipStream_t s, const SimplifyRings& in, const SimplifyWork& w, const long long* out_ring_offsets, long long n_out,
                             long long* out_areas2, int32_t* out_xy, long long* out_src_index);
 
+// ================================================================================================
+// Polygon rings nested into outlines and their holes (mrcnn_polygons_nest; kernels_nest.hip, the rule is nest_rule.h).  All tables are
+// device arrays.  One workgroup owns a target ring and its waves the candidates of the ring's RLE; eight launches and two scans, whatever
+// the number of rings and RLEs.
+// ================================================================================================
+struct NestRings { const long long* rle_rings; long long n_rles; const long long* ring_offsets; const int32_t* xy; long long n_rings; };
+struct NestWork {
+    unsigned long long* size;         // n_rings: |area2|
+    int4* box;                        // n_rings: the smallest and the largest x and y of a ring's vertices (x, y, z, w); an empty ring holds nothing
+    int32_t* rle;                     // n_rings: the RLE that owns the ring
+    uint32_t *shell, *holes, *rings;  // n_rings each: the depth is even; a shell's holes; a shell's polygon's rings (0 for a hole)
+    unsigned long long *polygon, *start;      // n_rings + 1 each: the shells before a ring; the rings of the polygons before a ring
+};
+// summary[0..2] = the lowest RLE at which rle_rings does not start at 0, decreases or does not end at n_rings, the lowest ring whose
+// offsets are negative, decrease or span 2^31 vertices, the lowest ring with a coordinate outside 0..32767 (~0: none; the last is not
+// looked for, and size, box and rle are not written, when one of the first two names something).
+void nest_measure_forward(hipStream_t s, const NestRings& in, const NestWork& w, unsigned long long* summary);
+// the five arrays of the entry from rings that passed; polygon[n_rings] is then the number of polygons
+void nest_forward(hipStream_t s, const NestRings& in, const NestWork& w, long long* parent, int32_t* depth, long long* rle_polys, long long* poly_rings,
+                  long long* ring_order);
+
 // COCOeval.accumulate (mrcnn_coco_accumulate; kernels_coco_acc.hip).  -ffp-contract=off.  All tables are device arrays.
 // A chunk is COCO_ACC_CHUNK consecutive entries of one category's segment [seg0, seg0 + seg_len) of the flat detection list, starting
 // `at` entries into it (a multiple of the chunk); the chunks of all segments, in order, are the grid of the sort kernels.

@@ -437,31 +437,39 @@ def _simplify_flat(host_definition, space, ring_offsets, xy, tolerance):
     return out_offsets, areas2[:R], out_xy[:2 * n].reshape(n, 2), src_index[:n], n
 
 
+def _flat_of_nested(rings, areas):
+    """rings[b][i] = the list of the (m, 2) arrays of RLE i of image b, areas beside them -> (the flat dictionary, every ring in order)"""
+    every = [np.asarray(r, dtype=np.int32).reshape(-1, 2) for row in rings for rle in row for r in rle]
+    per_rle = [len(rle) for row in rings for rle in row]
+    return {"rle_rings": np.concatenate(([0], np.cumsum(per_rle))).astype(np.int64),
+            "ring_offsets": np.concatenate(([0], np.cumsum([len(r) for r in every]))).astype(np.int64),
+            "ring_areas": np.concatenate([np.asarray(a, dtype=np.int64).reshape(-1) for row in areas for a in row] + [np.zeros(0, np.int64)]),
+            "xy": np.concatenate(every + [np.zeros((0, 2), np.int32)])}, every
+
+
+def _here(space, a, dtype):
+    """an array of a flat dictionary as a contiguous array of ``space``: converted or moved only where it has to be"""
+    if a is None:
+        return None
+    if space.on_host:
+        return np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "is_cuda") else a, dtype=dtype)
+    import torch
+    t = a if hasattr(a, "is_cuda") else torch.from_numpy(np.ascontiguousarray(a, dtype=dtype))
+    return t.to(device=space.device, dtype=getattr(torch, np.dtype(dtype).name)).contiguous()
+
+
 def _simplify_polygons(host_definition, polygons, tolerance, device, flat):
     nested = not isinstance(polygons, dict)
-    if nested:                                                   # (rings, areas): rings[b][i] = the list of the (m, 2) arrays of RLE i of image b
-        rings, areas = polygons
-        every = [np.asarray(r, dtype=np.int32).reshape(-1, 2) for row in rings for rle in row for r in rle]
-        per_rle = [len(rle) for row in rings for rle in row]
-        P = {"rle_rings": np.concatenate(([0], np.cumsum(per_rle))).astype(np.int64),
-             "ring_offsets": np.concatenate(([0], np.cumsum([len(r) for r in every]))).astype(np.int64),
-             "ring_areas": np.concatenate([np.asarray(a, dtype=np.int64).reshape(-1) for row in areas for a in row] + [np.zeros(0, np.int64)]),
-             "xy": np.concatenate(every + [np.zeros((0, 2), np.int32)])}
+    if nested:
+        rings, areas = polygons[0], polygons[1]
+        P, every = _flat_of_nested(rings, areas)
     else:
         P = dict(polygons)
     on_device = hasattr(P["xy"], "is_cuda")
     if device is None and on_device and not host_definition:
         device = P["xy"].device                                  # tensors: simplified where they lie, tensors out
     space = Space(device)
-
-    def here(a, dtype):
-        if a is None:
-            return None
-        if space.on_host:
-            return np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "is_cuda") else a, dtype=dtype)
-        import torch
-        t = a if hasattr(a, "is_cuda") else torch.from_numpy(np.ascontiguousarray(a, dtype=dtype))
-        return t.to(device=space.device, dtype=getattr(torch, np.dtype(dtype).name)).contiguous()
+    here = lambda a, dtype: _here(space, a, dtype)
     offsets, xy = here(P["ring_offsets"], np.int64), here(P["xy"], np.int32)
     out_offsets, areas2, out_xy, src_index, n = _simplify_flat(host_definition, space, offsets, xy, tolerance)
     out = {"rle_rings": here(P.get("rle_rings"), np.int64), "ring_offsets": out_offsets, "ring_areas": here(P.get("ring_areas"), np.int64),
@@ -481,7 +489,8 @@ def simplify_polygons(polygons, tolerance, device=None, flat: bool = False):
     back flat: rle_rings and ring_areas as they were (the ORIGINAL pixel areas), ring_offsets and xy simplified, and beside them areas2
     (twice the signed area of each simplified ring), src_index (per vertex, its index in the input xy), n_rings, n_vertices.  The nested
     form comes back nested, (rings, areas) with the original areas, unless flat=True.  Rings stay in their order, one for one; a ring
-    may come out with two vertices."""
+    may come out with two vertices.  The (rings, areas, nesting) triple of rle_to_polygons(..., nest=True) is taken too: its first two
+    entries are simplified and returned, the nesting is not touched and still indexes the rings."""
     return _simplify_polygons(False, polygons, tolerance, device, flat)
 
 
@@ -490,7 +499,82 @@ def simplify_polygons_host(polygons, tolerance, flat: bool = False):
     return _simplify_polygons(True, polygons, tolerance, None, flat)
 
 
-def _rle_to_polygons(host_definition, rles, sizes, device, flat, tolerance=None):
+def _nest_flat(host_definition, space, rle_rings, ring_offsets, xy):
+    """mrcnn_polygons_nest(_host) on rle_rings (K + 1), ring_offsets (R + 1) and xy (V, 2) of ``space`` -> the flat nesting: parent,
+    depth, rle_polys, poly_rings (n_polys + 1), ring_order, n_polys.  The buffers are sized by R: one call."""
+    K, R, V = int(rle_rings.shape[0]) - 1, int(ring_offsets.shape[0]) - 1, int(xy.shape[0])
+    if K < 0 or R < 0 or (V and tuple(xy.shape) != (V, 2)):
+        raise ValueError("nest_polygons: rle_rings and ring_offsets need an entry each and xy the shape (V, 2)")
+    ptr = space.ptr
+    src_xy = xy if V else space.new(2, np.int32, zero=True)      # (an empty tensor has no address)
+    parent, depth, ring_order = space.new(max(1, R), np.int64), space.new(max(1, R), np.int32), space.new(max(1, R), np.int64)
+    rle_polys, poly_rings = space.new(K + 1, np.int64, zero=True), space.new(R + 1, np.int64, zero=True)
+    total = C.c_int64(0)
+    head = (ptr(rle_rings), K, ptr(ring_offsets), ptr(src_xy), R) + (() if host_definition else (space.code,))
+    entry = _lib.lib().mrcnn_polygons_nest_host if host_definition else _lib.lib().mrcnn_polygons_nest
+    _lib.check(entry(*head, ptr(parent), ptr(depth), ptr(rle_polys), ptr(poly_rings), ptr(ring_order), C.byref(total)))
+    P = total.value
+    return {"parent": parent[:R], "depth": depth[:R], "rle_polys": rle_polys, "poly_rings": poly_rings[:P + 1], "ring_order": ring_order[:R], "n_polys": P}
+
+
+def _nest_nested(N, rle_rings, per_image):
+    """The flat nesting as lists: {"nest": nest[b][i] = [[shell, hole, ...], ...], "parent": parent[b][i], "depth": depth[b][i]}, all
+    indices LOCAL to rings[b][i] (parent -1: none).  per_image: the number of RLEs of each image."""
+    host = lambda a: a.cpu().numpy() if hasattr(a, "is_cuda") else np.asarray(a)
+    parent, depth, rle_polys, poly_rings, order = (host(N[k]) for k in ("parent", "depth", "rle_polys", "poly_rings", "ring_order"))
+    rr = host(rle_rings)
+    nest, par, dep, k = [], [], [], 0
+    for slots in per_image:
+        nest.append([]), par.append([]), dep.append([])
+        for _ in range(slots):
+            r0, r1 = int(rr[k]), int(rr[k + 1])
+            nest[-1].append([[int(r) - r0 for r in order[int(poly_rings[p]):int(poly_rings[p + 1])]] for p in range(int(rle_polys[k]), int(rle_polys[k + 1]))])
+            p = parent[r0:r1]
+            par[-1].append(np.where(p >= 0, p - r0, -1))
+            dep[-1].append(depth[r0:r1].copy())
+            k += 1
+    return {"nest": nest, "parent": par, "depth": dep}
+
+
+def _nest_polygons(host_definition, polygons, device, flat):
+    nested = not isinstance(polygons, dict)
+    if nested:
+        rings = polygons[0]
+        P, _ = _flat_of_nested(rings, [[np.zeros(len(rle), np.int64) for rle in row] for row in rings])      # (areas are not trusted: not needed)
+    else:
+        P = dict(polygons)
+        if P.get("rle_rings") is None:
+            raise ValueError("nest_polygons: the flat form needs rle_rings, ring_offsets and xy")
+    if device is None and hasattr(P["xy"], "is_cuda") and not host_definition:
+        device = P["xy"].device                                  # tensors: nested where they lie, tensors out
+    space = Space(device)
+    rle_rings = _here(space, P["rle_rings"], np.int64)
+    N = _nest_flat(host_definition, space, rle_rings, _here(space, P["ring_offsets"], np.int64), _here(space, P["xy"], np.int32))
+    if flat or not nested:
+        return N
+    return _nest_nested(N, rle_rings, [len(row) for row in rings])
+
+
+def nest_polygons(polygons, device=None, flat: bool = False):
+    """Polygon rings nested on the GPU into outlines and their holes (``mrcnn_polygons_nest``; the rule is defined in
+    include/maskrcnn_hip.h: a ring's parent is the closest ring of its RLE that contains the centre of the pixel at the ring's first
+    vertex, even depth is a shell, its children are its holes).  ``polygons`` is what rle_to_polygons or simplify_polygons returned:
+    the flat dictionary — rle_rings, ring_offsets and xy, numpy arrays or CUDA tensors, which are nested where they lie — or the
+    nested (rings, areas) pair.  The flat form (and flat=True) gives the library's arrays: parent (global ring indices, -1: none),
+    depth, rle_polys, poly_rings, ring_order — polygon p owns ring_order[poly_rings[p]:poly_rings[p + 1]], shell first, and RLE k the
+    polygons rle_polys[k]:rle_polys[k + 1] — and n_polys.  The nested form gives {"nest", "parent", "depth"}: nest[b][i] =
+    [[shell_ring, hole_ring, ...], ...], indices into rings[b][i], and parent[b][i], depth[b][i] per ring with local indices too.
+    Nest the TRACED rings: simplification keeps rings one for one, so the result indexes the simplified rings, whose own topology is
+    not preserved."""
+    return _nest_polygons(False, polygons, device, flat)
+
+
+def nest_polygons_host(polygons, flat: bool = False):
+    """The definition of nest_polygons: the sequential host code (``mrcnn_polygons_nest_host``), no GPU; numpy out."""
+    return _nest_polygons(True, polygons, None, flat)
+
+
+def _rle_to_polygons(host_definition, rles, sizes, device, flat, tolerance=None, nest=False):
     name = "rle_to_polygons_host" if host_definition else "rle_to_polygons"
     if device is None and not host_definition and isinstance(rles, tuple) and len(rles) == 2 and hasattr(rles[0], "is_cuda"):
         device = rles[0].device                                  # a pair of CUDA tensors: traced where they lie, tensors out
@@ -513,9 +597,11 @@ def _rle_to_polygons(host_definition, rles, sizes, device, flat, tolerance=None)
     R, V = totals[0].value, totals[1].value
     ring_offsets, ring_areas, xy = ring_offsets[:R + 1], ring_areas[:R], xy[:2 * V].reshape(V, 2)
     extra = {}
+    if nest:                                                     # on the TRACED rings, before they are simplified: the guarantee is theirs
+        extra["nest"] = _nest_flat(host_definition, space, rle_rings, ring_offsets, xy)
     if tolerance is not None:                                    # the same memory space: device-resident rings never leave the device
         ring_offsets, areas2, xy, src_index, V = _simplify_flat(host_definition, space, ring_offsets, xy, tolerance)
-        extra = {"areas2": areas2, "src_index": src_index}
+        extra.update({"areas2": areas2, "src_index": src_index})
     if flat:
         return {"rle_rings": rle_rings, "ring_offsets": ring_offsets, "ring_areas": ring_areas, "xy": xy, "n_rings": R, "n_vertices": V, **extra}
     if not space.on_host:
@@ -523,10 +609,12 @@ def _rle_to_polygons(host_definition, rles, sizes, device, flat, tolerance=None)
     rings = [[[xy[ring_offsets[r]:ring_offsets[r + 1]] for r in range(rle_rings[b * slots + i], rle_rings[b * slots + i + 1])]
               for i in range(slots)] for b in range(B)]
     areas = [[ring_areas[rle_rings[b * slots + i]:rle_rings[b * slots + i + 1]] for i in range(slots)] for b in range(B)]
+    if nest:
+        return rings, areas, _nest_nested(extra["nest"], rle_rings, [slots] * B)
     return rings, areas
 
 
-def rle_to_polygons(rles, sizes=None, device=None, flat: bool = False, tolerance=None):
+def rle_to_polygons(rles, sizes=None, device=None, flat: bool = False, tolerance=None, nest: bool = False):
     """The boundary of every mask of an RLE set as closed rings of pixel corners, traced from the runs on the GPU
     (``mrcnn_rle_to_polygons``; the geometry is defined in include/maskrcnn_hip.h).  ``rles`` as rle_decode_planes takes them: what
     merge_tiles, unite_tiles or masks_rle_source returned, or a (counts, run_offsets) pair with ``sizes``; a pair of CUDA tensors is
@@ -536,11 +624,13 @@ def rle_to_polygons(rles, sizes=None, device=None, flat: bool = False, tolerance
     ring_areas, xy as (V, 2), n_rings, n_vertices): numpy arrays, or tensors that stay on the device when ``device`` is given or the
     pair is CUDA tensors.  ``tolerance`` (pixels; None: the traced rings as they are) hands the rings on to simplify_polygons in the
     same memory space: the rings come back simplified with the ORIGINAL pixel areas beside them, and the flat form gains areas2 and
-    src_index."""
-    return _rle_to_polygons(False, rles, sizes, device, flat, tolerance)
+    src_index.  ``nest=True`` adds the nesting of the rings into outlines and their holes (nest_polygons), computed in the same memory
+    space on the traced rings before they are simplified — simplification keeps the rings one for one, so it indexes the simplified
+    rings too: a third result, as nest_polygons returns it for the nested form, or the key "nest" of the flat form."""
+    return _rle_to_polygons(False, rles, sizes, device, flat, tolerance, nest)
 
 
-def rle_to_polygons_host(rles, sizes=None, flat: bool = False, tolerance=None):
+def rle_to_polygons_host(rles, sizes=None, flat: bool = False, tolerance=None, nest: bool = False):
     """The definition of rle_to_polygons: the sequential host code (``mrcnn_rle_to_polygons_host``, and ``mrcnn_polygons_simplify_host``
-    for a tolerance), no GPU; numpy out."""
-    return _rle_to_polygons(True, rles, sizes, None, flat, tolerance)
+    for a tolerance, ``mrcnn_polygons_nest_host`` for nest=True), no GPU; numpy out."""
+    return _rle_to_polygons(True, rles, sizes, None, flat, tolerance, nest)

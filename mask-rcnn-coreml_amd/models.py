@@ -143,7 +143,7 @@ class MaskRCNN(_Model):
         return det, mask
 
     def predict_tiled(self, images, tile=None, overlap=(64, 64), metric="ios", match_threshold=0.5, max_out=None, threshold=0.5,
-                      unite=False, link_threshold=0.5, polygons=False, tolerance=None):
+                      unite=False, link_threshold=0.5, polygons=False, tolerance=None, nest=False):
         """Large images as overlapping windows at native resolution: detection.tile_plan per image (tile = None: the model's input
         size), predict_tiles, detection.merge_tiles.  Returns (det_src, source, n_kept, rles) in the frame of the images, in the
         form coco_results.coco_results and coco_eval.score_batch take.  By default an object is found whole only if some window
@@ -152,7 +152,8 @@ class MaskRCNN(_Model):
         become one mask (match_threshold is not used then).  polygons=True adds a fifth result, (rings, areas) as
         detection.rle_to_polygons returns them: the boundaries of the masks, traced from the runs where the merge or the union left
         them — on the device when the images are CUDA tensors.  tolerance (pixels) simplifies those rings there too
-        (detection.simplify_polygons); the areas stay the pixel areas."""
+        (detection.simplify_polygons); the areas stay the pixel areas.  nest=True makes that result (rings, areas, nesting): the rings
+        nested into outlines and their holes (detection.nest_polygons), in the same place, on the traced rings."""
         from .detection import _merge_tiles, rle_to_polygons, tile_plan
         images = list(images)
         H, W = self.image_height, self.image_width
@@ -165,7 +166,7 @@ class MaskRCNN(_Model):
                            resident=resident)[:4]
         if not polygons:
             return out
-        return (*out, rle_to_polygons(resident[0], sizes, tolerance=tolerance))
+        return (*out, rle_to_polygons(resident[0], sizes, tolerance=tolerance, nest=nest))
 
     def predict_jpegs(self, files, entropy="host"):
         """predict_images straight from JPEG files (mrcnn_maskrcnn_predict_jpegs_on): a list of bytes.  The entropy decoders run on the
