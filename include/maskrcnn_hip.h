@@ -1040,6 +1040,55 @@ MRCNN_API int mrcnn_polygons_nest_host(const int64_t* rle_rings, int64_t n_rles,
                                        int64_t* parent, int32_t* depth, int64_t* rle_polys, int64_t* poly_rings, int64_t* ring_order,
                                        int64_t* n_polys);
 
+/* ---- changing run-length masks: erosion, dilation and the boundary band (csrc/api_rle_morph.hip, kernels_rle_morph.hip) --------------
+ * Morphology with a square structuring element on a set of RLEs in the layout of every entry above (uint32 column-major runs, counts[0]
+ * the leading zeros, int64 run_offsets): RLE in, RLE out, no dense plane.  The set is flat: RLE k is counts[run_offsets[k] ..
+ * run_offsets[k+1]) and encodes a heights[k] x widths[k] plane; heights, widths and radii are HOST arrays of n (a detection set repeats
+ * its image's size per slot, a ground-truth set is ragged per image).  Input RLEs may hold zero-length runs anywhere.
+ * The rule (csrc/morph_rule.h).  P is the h x w {0,1} plane of an RLE, r = radii[k] >= 0; pixels outside the image are 0 for every op.
+ *   MRCNN_MORPH_ERODE     E_r(P)[y,x] = 1 iff P[y',x'] = 1 for all |y'-y| <= r, |x'-x| <= r: a mask erodes from the image border too
+ *   MRCNN_MORPH_DILATE    D_r(P)[y,x] = 1 iff some in-image P[y',x'] = 1 with |y'-y| <= r, |x'-x| <= r: clipped to the image
+ *   MRCNN_MORPH_BOUNDARY  P AND NOT E_r(P): the inner band of width r — the band of Boundary IoU (Cheng et al., CVPR 2021), whose
+ *                         published pad / iterate-3x3 / un-pad procedure with d iterations equals it at r = d
+ *   r = 0: ERODE and DILATE return P, BOUNDARY the empty mask.  E_a(E_b(P)) = E_(a+b)(P) and D_a(D_b(P)) = D_(a+b)(P).
+ * Outputs, exactly as mrcnn_masks_rle_source writes them: the canonical RLE of the result plane (counts[0] may be 0, no other run is,
+ * runs continue across column ends, an empty plane is the single run [h*w]).
+ *   out_run_offsets (n + 1)   always written
+ *   areas (n), bboxes_xywh (n, 4)   optional (NULL): the set pixels and their tight box x, y, w, h (0, 0, 0, 0 for an empty mask)
+ *   out_counts / capacity     written only when all runs fit: a smaller capacity -> MRCNN_ERR_SHAPE, the message names the capacity
+ *                             needed (= out_run_offsets[n]) and out_counts is not written; capacity = 0 with out_counts = NULL is the
+ *                             size query
+ * memspace holds for counts, run_offsets and the four outputs; the outputs must not overlap the inputs.  n = 0 is legal:
+ * out_run_offsets[0] = 0.
+ * mrcnn_rle_morph_host is the definition: sequential plain C++, no GPU, host pointers; one RLE at a time it decodes a plane, runs the
+ * two halves of the square as sliding windows over running counts, O(h*w) whatever the radius, and encodes.  mrcnn_rle_morph equals it
+ * bit for bit in every output array and never builds a plane: the prefix table of the runs; one block per RLE finds the tight box of
+ * its set pixels; the host reads the boxes (and the one flag that refuses a wrong total) back once and sizes a packed bit box per RLE,
+ * 32 rows per word — scratch that follows the masks, not the images; one thread per box column takes the vertical half on the runs of
+ * its column (an interval [a, b) becomes [a+r, b-r), or [a-r, b+r) clipped); one block per tile of a word row takes the horizontal half
+ * on the words, 2r + 1 of them combined by doubling in LDS, which MRCNN_MORPH_MAX_RADIUS bounds; the encoder of mrcnn_masks_rle_source
+ * runs on the bits.  Seven launches whatever n.
+ * mrcnn_boundary_radius: r = max(1, round_half_even(ratio * sqrt(h*h + w*w))), evaluated in double — the published
+ * int(round(dilation_ratio * img_diag)) with a floor of 1: 16 for 480x640 and 102 for 3072x4096 at ratio 0.02.
+ * Errors: null pointer, unknown memspace -> MRCNN_ERR_INVALID; n < 0, a side outside 1..32767, a radius outside
+ * 0..MRCNN_MORPH_MAX_RADIUS, an unknown op, run_offsets that decrease -> MRCNN_ERR_SHAPE; an RLE that does not sum to its h*w ->
+ * MRCNN_ERR_SHAPE, the message starts "rle_morph:" / "rle_morph_host:" and names the lowest such k, nothing is written; a ratio that is
+ * not finite or not > 0, sides outside 1..32767 -> MRCNN_ERR_SHAPE from mrcnn_boundary_radius.  Argument errors are answered before a
+ * device is looked for; no gfx950 device -> MRCNN_ERR_HIP from the device entry (no CPU fallback).
+ * Not here: structuring elements other than the square, grey-scale morphology, connected-component filtering, radii above the cap
+ * (compose two calls: the semigroup property above). */
+#define MRCNN_MORPH_ERODE 0
+#define MRCNN_MORPH_DILATE 1
+#define MRCNN_MORPH_BOUNDARY 2
+#define MRCNN_MORPH_MAX_RADIUS 1024
+MRCNN_API int mrcnn_rle_morph(const uint32_t* counts, const int64_t* run_offsets, int64_t n, const int32_t* heights, const int32_t* widths,
+                              const int32_t* radii, int op, int memspace, uint32_t* out_counts, int64_t capacity, int64_t* out_run_offsets,
+                              uint32_t* areas, int32_t* bboxes_xywh);
+MRCNN_API int mrcnn_rle_morph_host(const uint32_t* counts, const int64_t* run_offsets, int64_t n, const int32_t* heights, const int32_t* widths,
+                                   const int32_t* radii, int op, uint32_t* out_counts, int64_t capacity, int64_t* out_run_offsets,
+                                   uint32_t* areas, int32_t* bboxes_xywh);
+MRCNN_API int mrcnn_boundary_radius(int h, int w, double ratio, int32_t* radius);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ MRCNN_OK = 0
 F32, F64, F16, U8, I32, F32S, F32X3 = 0, 1, 2, 3, 4, 5, 6
 DEFAULT = -1          # MRCNN_DEFAULT of mrcnn_model_load: the mode the artefact is prepared for (stored split exponents -> F32X3, else F32)
 HOST, DEVICE = 0, 1
+MORPH_ERODE, MORPH_DILATE, MORPH_BOUNDARY, MORPH_MAX_RADIUS = 0, 1, 2, 1024
 PARAM_INT, PARAM_DOUBLE, PARAM_STRING = 0, 1, 2
 MODEL_MASKRCNN, MODEL_CLASSIFIER, MODEL_MASK = 0, 1, 2
 
@@ -51,6 +52,7 @@ EXPORTED_SYMBOLS = [
     "mrcnn_rle_to_polygons", "mrcnn_rle_to_polygons_host",
     "mrcnn_polygons_simplify", "mrcnn_polygons_simplify_host",
     "mrcnn_polygons_nest", "mrcnn_polygons_nest_host",
+    "mrcnn_rle_morph", "mrcnn_rle_morph_host", "mrcnn_boundary_radius",
 ]
 # declared in include/maskrcnn_hip_test.h (test / measurement entry points of the same library)
 TEST_SYMBOLS = [
@@ -219,6 +221,10 @@ def lib():
     _nest = [vp, vp, vp, vp, vp, i64p]                            # parent, depth, rle_polys, poly_rings, ring_order, n_polys
     L.mrcnn_polygons_nest.argtypes = [vp, C.c_int64, vp, vp, C.c_int64, C.c_int] + _nest
     L.mrcnn_polygons_nest_host.argtypes = [vp, C.c_int64, vp, vp, C.c_int64] + _nest
+    _morph = [vp, C.c_int64, vp, vp, vp]                          # out_counts, capacity, out_run_offsets, areas, bboxes_xywh
+    L.mrcnn_rle_morph.argtypes = [vp, vp, C.c_int64, vp, vp, vp, C.c_int, C.c_int] + _morph
+    L.mrcnn_rle_morph_host.argtypes = [vp, vp, C.c_int64, vp, vp, vp, C.c_int] + _morph
+    L.mrcnn_boundary_radius.argtypes = [C.c_int, C.c_int, C.c_double, vp]
     L.mrcnn_rle_to_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_from_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_iou.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int64]

@@ -217,26 +217,42 @@ class COCOGroundTruth:
             if a["area"] is None:
                 a["_area"] = float(areas_h[k])
         return DeviceGroundTruth(self, counts, run_offsets, areas, offs, {id(a): k for k, a in enumerate(order)}, ranges,
-                                 np.array([a["iscrowd"] for a in order], dtype=np.uint8))
+                                 np.array([a["iscrowd"] for a in order], dtype=np.uint8), sizes)
 
 
 class DeviceGroundTruth:
     """The masks of a COCOGroundTruth as one RLE set resident on the device, in the layout mrcnn_rle_iou reads: ``counts`` (int32),
     ``run_offsets`` (int64, n + 1) and ``areas`` (int32) are device tensors; annotation ``a`` is RLE ``index[id(a)]``, the annotations of
-    an image are the range ``image_range[image_id]``.  ``COCOGroundTruth.to_device`` makes one."""
+    an image are the range ``image_range[image_id]``; ``sizes[k]`` is the (h, w) of RLE k's image.  ``COCOGroundTruth.to_device`` makes
+    one.  ``band(ratio)`` is the same set cut down to Boundary IoU's inner bands, made once per ratio where the runs lie."""
 
-    def __init__(self, gt, counts, run_offsets, areas, host_offsets, index, image_range, iscrowd):
+    def __init__(self, gt, counts, run_offsets, areas, host_offsets, index, image_range, iscrowd, sizes=None):
         self.gt, self.counts, self.run_offsets, self.areas = gt, counts, run_offsets, areas
         self.host_offsets, self.index, self.image_range, self.iscrowd = host_offsets, index, image_range, iscrowd
         self.n = len(index)
+        self.sizes = sizes
+        self._bands: Dict = {}
 
-    def gather(self, anns):
-        """The RLEs of `anns` as a set of their own on the device (counts, run_offsets): when a filter breaks an image's range."""
+    def band(self, ratio: float = 0.02):
+        """(counts, run_offsets, host_offsets) of the BOUNDARY set of every annotation (mrcnn_rle_morph on the resident runs), device
+        tensors cached per ratio: every batch of a scoring run reads the same tensors."""
+        key = float(ratio)
+        if key not in self._bands:
+            if self.sizes is None:
+                raise ValueError("DeviceGroundTruth.band: the set was made without the sizes of its images")
+            (c, o), _, _ = _band_set((self.counts, self.run_offsets[:self.n + 1]), self.sizes, key)
+            self._bands[key] = (c, o, o.cpu().numpy())
+        return self._bands[key]
+
+    def gather(self, anns, band_ratio=None):
+        """The RLEs of `anns` as a set of their own on the device (counts, run_offsets): when a filter breaks an image's range.
+        band_ratio: their boundary bands at that ratio instead."""
         import torch
+        src, host_offsets = (self.counts, self.host_offsets) if band_ratio is None else (self.band(band_ratio)[0], self.band(band_ratio)[2])
         ks = [self.index[id(a)] for a in anns]
         offs = np.zeros(len(ks) + 1, dtype=np.int64)
-        offs[1:] = np.cumsum([self.host_offsets[k + 1] - self.host_offsets[k] for k in ks])
-        parts = [self.counts[int(self.host_offsets[k]):int(self.host_offsets[k + 1])] for k in ks]
+        offs[1:] = np.cumsum([host_offsets[k + 1] - host_offsets[k] for k in ks])
+        parts = [src[int(host_offsets[k]):int(host_offsets[k + 1])] for k in ks]
         counts = torch.cat(parts) if parts else torch.zeros(1, dtype=torch.int32, device=self.counts.device)
         return counts, torch.from_numpy(offs).to(self.counts.device)
 
@@ -251,6 +267,15 @@ class DeviceDetections:
     def __init__(self, image_ids, sizes, rows, counts, run_offsets, records):
         self.image_ids, self.sizes, self.rows = list(image_ids), list(sizes), int(rows)
         self.counts, self.run_offsets, self.records = counts, run_offsets, records
+        self._bands: Dict = {}
+
+    def band(self, ratio: float = 0.02):
+        """(counts, run_offsets) of the BOUNDARY set of every row (mrcnn_rle_morph where the runs lie), cached per ratio."""
+        key = float(ratio)
+        if key not in self._bands:
+            n = len(self.image_ids) * self.rows
+            self._bands[key] = _band_set((self.counts, self.run_offsets[:n + 1]), [s for s in self.sizes for _ in range(self.rows)], key)[0]
+        return self._bands[key]
 
 
 def device_detections(image_ids, detections, masks, sizes, model_h: int, model_w: int, threshold: float = 0.5, class_to_category=None,
@@ -300,6 +325,36 @@ def device_detections(image_ids, detections, masks, sizes, model_h: int, model_w
     return DeviceDetections(image_ids, [(int(a), int(b)) for a, b in zip(hs, ws)], rows, counts, offs, records)
 
 
+def _band_set(pair, sizes, ratio: float, host_definition: bool = False):
+    """detection.rle_morph(_host)(..., "boundary") on a flat (counts, run_offsets) pair with one (h, w) per RLE and Boundary IoU's radius
+    for each: a pair of CUDA tensors stays on the device, numpy arrays go through the host definition when asked to."""
+    from .detection import _rle_morph, boundary_radius
+    radius: Dict = {}
+    for s in sizes:
+        if tuple(s) not in radius:
+            radius[tuple(s)] = boundary_radius(int(s[0]), int(s[1]), ratio)
+    if not len(sizes):
+        return pair, None, None
+    return _rle_morph(host_definition, pair, sizes, [radius[tuple(s)] for s in sizes], "boundary", None)
+
+
+def _band_host(rles: List[np.ndarray], sizes, ratio: float) -> List[np.ndarray]:
+    """the boundary bands of host RLEs, by the host definition (mrcnn_rle_morph_host)"""
+    if not rles:
+        return []
+    (c, o), _, _ = _band_set(_concat_rles(rles), sizes, ratio, host_definition=True)
+    return [c[int(o[k]):int(o[k + 1])] for k in range(len(rles))]
+
+
+def _gt_bands(gt: "COCOGroundTruth", anns: List[dict], ratio: float) -> List[np.ndarray]:
+    """the bands of ground-truth annotations on the host, cached per annotation and ratio"""
+    todo = [a for a in anns if float(ratio) not in a.setdefault("_band", {})]
+    todo = list({id(a): a for a in todo}.values())
+    for a, b in zip(todo, _band_host([gt.counts(a) for a in todo], [gt.images[a["image_id"]] for a in todo], ratio)):
+        a["_band"][float(ratio)] = b
+    return [a["_band"][float(ratio)] for a in anns]
+
+
 def _concat_rles(rles: List[np.ndarray]):
     offs = np.zeros(len(rles) + 1, dtype=np.int64)
     if rles:
@@ -316,12 +371,15 @@ def _group_array(groups):
 
 
 def _evaluate_set(gt: COCOGroundTruth, img_order: List, per_image: Dict, iou_type: str, max_det: int, device: Optional[DeviceDetections],
-                  cat_set, area_rng, iou_thrs, resident: Optional["DeviceGroundTruth"] = None):
+                  cat_set, area_rng, iou_thrs, resident: Optional["DeviceGroundTruth"] = None, boundary_ratio: float = 0.02):
     """IoU + matching for the images of one detection set.  per_image[image_id] = list of records (with ``_local`` = the row of the
     image's IoU block, ``area``, ``score``, ``category_id`` and — host sets — ``_counts``).  Returns {(image_id, category_id): eval}."""
     L = _lib.lib()
     A, T = len(area_rng), len(iou_thrs)
     on_device = device is not None
+    band = iou_type == "boundary"                                # the mask IoU, then the bands' IoU and the smaller of the two
+    if band:
+        iou_type = "segm"
     if resident is not None and (iou_type != "segm" or resident.gt is not gt):
         resident = None                                          # boxes are host tables; another file's set is not this one's
     iou_dev = on_device or resident is not None                  # where the IoU blocks live
@@ -329,7 +387,7 @@ def _evaluate_set(gt: COCOGroundTruth, img_order: List, per_image: Dict, iou_typ
     imgs = [i for i in img_order if i in per_image]
     # --- the two sets and the IoU groups -----------------------------------------------------------------------------------------
     g_anns, groups, blocks = [], [], {}
-    d_rles, d_boxes, out_at, d_at = [], [], 0, 0
+    d_rles, d_sizes, d_boxes, out_at, d_at = [], [], [], 0, 0
     for image_id in imgs:
         recs = per_image[image_id]
         ganns = [a for a in gt.by_image.get(image_id, []) if a["category_id"] in cat_set]
@@ -341,6 +399,7 @@ def _evaluate_set(gt: COCOGroundTruth, img_order: List, per_image: Dict, iou_typ
             d_at += nd
             if iou_type == "segm":
                 d_rles += [r["_counts"] for r in recs]
+                d_sizes += [gt.images[image_id]] * nd
         if iou_type == "bbox":
             if on_device:
                 rows = np.zeros((device.rows, 4), np.float64)
@@ -396,6 +455,21 @@ def _evaluate_set(gt: COCOGroundTruth, img_order: List, per_image: Dict, iou_typ
                 do, n_d = torch.from_numpy(d_offs).to(dev_of), len(d_rles)
             _lib.check(L.mrcnn_rle_iou(dc.data_ptr(), do.data_ptr(), n_d, gc.data_ptr(), go.data_ptr(), n_g, crowd.ctypes.data, garr, len(groups),
                                        space, None, iou_ptr, n_pairs))
+            if band:                                             # the same groups over the two band sets, made where the runs lie
+                if in_place:
+                    gc, go = resident.band(boundary_ratio)[0], resident.band(boundary_ratio)[1][g_lo:g_hi + 1]
+                else:
+                    gc, go = resident.gather(g_anns, boundary_ratio)
+                if on_device:
+                    dc, do = device.band(boundary_ratio)
+                else:
+                    d_counts, d_offs = _concat_rles(_band_host(d_rles, d_sizes, boundary_ratio))
+                    dc = torch.from_numpy(d_counts.view(np.int32)).to(dev_of) if d_counts.size else torch.zeros(1, dtype=torch.int32, device=dev_of)
+                    do = torch.from_numpy(d_offs).to(dev_of)
+                iou_b = torch.zeros_like(iou)
+                _lib.check(L.mrcnn_rle_iou(dc.data_ptr(), do.data_ptr(), n_d, gc.data_ptr(), go.data_ptr(), n_g, crowd.ctypes.data, garr, len(groups),
+                                           space, None, iou_b.data_ptr(), n_pairs))
+                torch.minimum(iou, iou_b, out=iou)
         elif iou_type == "segm":
             g_counts, g_offs = _concat_rles([gt.counts(a) for a in g_anns])
             if on_device:
@@ -404,10 +478,26 @@ def _evaluate_set(gt: COCOGroundTruth, img_order: List, per_image: Dict, iou_typ
                 n_d = len(device.image_ids) * device.rows
                 _lib.check(L.mrcnn_rle_iou(device.counts.data_ptr(), device.run_offsets.data_ptr(), n_d, gc.data_ptr(), go.data_ptr(), n_g,
                                            crowd.ctypes.data, garr, len(groups), space, None, iou_ptr, n_pairs))
+                if band:                                         # the detections' bands where their runs lie, the ground truth's uploaded
+                    g_counts, g_offs = _concat_rles(_gt_bands(gt, g_anns, boundary_ratio))
+                    gc = torch.from_numpy(g_counts.view(np.int32)).to(device.counts.device)
+                    go = torch.from_numpy(g_offs).to(device.counts.device)
+                    dc, do = device.band(boundary_ratio)
+                    iou_b = torch.zeros_like(iou)
+                    _lib.check(L.mrcnn_rle_iou(dc.data_ptr(), do.data_ptr(), n_d, gc.data_ptr(), go.data_ptr(), n_g, crowd.ctypes.data, garr,
+                                               len(groups), space, None, iou_b.data_ptr(), n_pairs))
+                    torch.minimum(iou, iou_b, out=iou)
             else:
                 d_counts, d_offs = _concat_rles(d_rles)
                 _lib.check(L.mrcnn_rle_iou(d_counts.ctypes.data, d_offs.ctypes.data, len(d_rles), g_counts.ctypes.data, g_offs.ctypes.data, n_g,
                                            crowd.ctypes.data, garr, len(groups), space, None, iou_ptr, n_pairs))
+                if band:                                         # host sets: the host definition and the host memspace of mrcnn_rle_iou
+                    d_counts, d_offs = _concat_rles(_band_host(d_rles, d_sizes, boundary_ratio))
+                    g_counts, g_offs = _concat_rles(_gt_bands(gt, g_anns, boundary_ratio))
+                    iou_b = np.zeros_like(iou)
+                    _lib.check(L.mrcnn_rle_iou(d_counts.ctypes.data, d_offs.ctypes.data, len(d_rles), g_counts.ctypes.data, g_offs.ctypes.data, n_g,
+                                               crowd.ctypes.data, garr, len(groups), space, None, iou_b.ctypes.data, n_pairs))
+                    np.minimum(iou, iou_b, out=iou)
         else:
             db = np.ascontiguousarray(np.concatenate(d_boxes) if d_boxes else np.zeros((0, 4)), dtype=np.float64)
             gb = np.ascontiguousarray(np.array([a["bbox"] for a in g_anns], dtype=np.float64).reshape(-1, 4))
@@ -643,13 +733,14 @@ def summarize(precision: np.ndarray, recall: np.ndarray, max_dets=(1, 10, 100), 
 
 
 def _records(gt: COCOGroundTruth, results, iou_type: str, img_set, cat_set):
-    """The results of the scored images and categories per image, each with its area (and its run lengths for ``segm``)."""
+    """The results of the scored images and categories per image, each with its area (and its run lengths for ``segm`` and
+    ``boundary``, whose areas are the MASK areas)."""
     per_image: Dict = {}
     for r in results:
         if r["image_id"] not in img_set or r["category_id"] not in cat_set:
             continue
         rec = {"image_id": r["image_id"], "category_id": r["category_id"], "score": float(r["score"])}
-        if iou_type == "segm":
+        if iou_type in ("segm", "boundary"):
             h, w = gt.images[r["image_id"]]
             rec["_counts"] = segmentation_to_counts(r["segmentation"], h, w)
             rec["area"] = float(_area(rec["_counts"]))
@@ -682,7 +773,7 @@ def _finish(gt: COCOGroundTruth, ev: Dict, img_ids: List, cat_ids: List, max_det
 
 
 def score(gt: COCOGroundTruth, results, iou_type: str = "segm", img_ids=None, max_dets=(1, 10, 100), device_batches=None, device_gt=None,
-          accumulate_on=None) -> dict:
+          accumulate_on=None, boundary_ratio: float = 0.02) -> dict:
     """COCO's twelve numbers for `results` (the list coco_results.coco_results returns, or that list loaded from JSON) against `gt`.
     Returns ``stats`` (12, -1 where COCO prints -1), ``precision`` (T, R, K, A, M), ``recall`` (T, K, A, M) and ``summary`` (the twelve
     lines in COCOeval's wording).  img_ids: the images scored (default: all of the annotation file).
@@ -691,10 +782,17 @@ def score(gt: COCOGroundTruth, results, iou_type: str = "segm", img_ids=None, ma
     device_gt: ``gt.to_device()`` — for ``segm`` the ground truth is then read where it is resident, for every batch, and no run length
     of it crosses to the device again; the numbers are the same.
     accumulate_on: "device" — COCOeval's accumulate through mrcnn_coco_accumulate, "host" — in numpy, None — DEFAULT_ACCUMULATE_ON; the
-    arrays are identical either way."""
+    arrays are identical either way.
+    iou_type "boundary": Boundary AP (Cheng et al., CVPR 2021).  Per image r = detection.boundary_radius(h, w, boundary_ratio); the IoU
+    of a pair is the smaller of its mask IoU and the IoU of the two inner bands of width r (mrcnn_rle_morph's BOUNDARY), the crowd
+    rule applied in both; areas, matching, accumulate and summarize are those of ``segm``.  Device sets get their bands where the
+    runs lie and the minimum is taken on the device; ``device_gt`` keeps its bands per ratio for every batch; host sets go through
+    mrcnn_rle_morph_host, cached per annotation."""
     _accumulate_where(accumulate_on)
-    if iou_type not in ("segm", "bbox"):
-        raise ValueError("iou_type must be 'segm' or 'bbox'")
+    if iou_type not in ("segm", "bbox", "boundary"):
+        raise ValueError("iou_type must be 'segm', 'bbox' or 'boundary'")
+    if not (np.isfinite(boundary_ratio) and boundary_ratio > 0):
+        raise ValueError("boundary_ratio must be finite and > 0")
     if len(max_dets) != 3:
         raise ValueError("max_dets: three values, as COCO's summary reads them")
     img_ids = sorted(set(gt.img_ids() if img_ids is None else img_ids))
@@ -711,15 +809,16 @@ def score(gt: COCOGroundTruth, results, iou_type: str = "segm", img_ids=None, ma
                     if iou_type == "bbox":
                         rec["area"] = r["bbox"][2] * r["bbox"][3]
                     per_image.setdefault(r["image_id"], []).append(rec)
-            ev.update(_evaluate_set(gt, img_ids, per_image, iou_type, max_dets[-1], batch, cat_set, AREA_RNG, IOU_THRS, device_gt))
+            ev.update(_evaluate_set(gt, img_ids, per_image, iou_type, max_dets[-1], batch, cat_set, AREA_RNG, IOU_THRS, device_gt, boundary_ratio))
     else:
         per_image = _records(gt, results or [], iou_type, img_set, cat_set)
-        ev.update(_evaluate_set(gt, img_ids, per_image, iou_type, max_dets[-1], None, cat_set, AREA_RNG, IOU_THRS, device_gt))
+        ev.update(_evaluate_set(gt, img_ids, per_image, iou_type, max_dets[-1], None, cat_set, AREA_RNG, IOU_THRS, device_gt, boundary_ratio))
     return _finish(gt, ev, img_ids, cat_ids, max_dets, accumulate_on)
 
 
 def score_batch(gt: COCOGroundTruth, batches: Sequence[DeviceDetections], iou_type: str = "segm", img_ids=None, max_dets=(1, 10, 100),
-                device_gt=None, accumulate_on=None) -> dict:
+                device_gt=None, accumulate_on=None, boundary_ratio: float = 0.02) -> dict:
     """``score`` over detections that never left the device (device_detections): the same arrays as the path through strings.  With
-    device_gt = ``gt.to_device()`` neither side of the mask IoU is uploaded per batch."""
-    return score(gt, None, iou_type, img_ids, max_dets, device_batches=list(batches), device_gt=device_gt, accumulate_on=accumulate_on)
+    device_gt = ``gt.to_device()`` neither side of the mask IoU is uploaded per batch — nor, for "boundary", of the bands' IoU."""
+    return score(gt, None, iou_type, img_ids, max_dets, device_batches=list(batches), device_gt=device_gt, accumulate_on=accumulate_on,
+                 boundary_ratio=boundary_ratio)

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "common.h"
+#include "morph_rule.h"
 
 namespace mrcnn {
 
@@ -529,6 +530,33 @@ void rle_draw_prepare(hipStream_t s, const long long* run_offsets, const unsigne
 void rle_decode_forward(hipStream_t s, const RleDrawJob& job, uint8_t* out);
 void instance_map_rle_forward(hipStream_t s, const RleDrawJob& job, int16_t* map, uint32_t* visible);
 void render_detections_rle_forward(hipStream_t s, const RleDrawJob& job, const uint8_t* const* srcs, int alpha, int stroke, uint8_t* out);
+
+// ================================================================================================
+// Morphology on run-length masks (kernels_rle_morph.hip; the rule is morph_rule.h).  All tables are device arrays.
+// ================================================================================================
+constexpr int MORPH_TILE = 4096;      // words of one word row a block stages: C + 2r with C >= 2048 output columns at the largest radius
+static_assert(MORPH_TILE >= 2 * MRCNN_MORPH_MAX_RADIUS + 2048, "a tile holds its halo at the largest radius");
+// One RLE after the boxes were read back: its runs, plane and radius, the tight box of its set pixels, the box its result lies in
+// (`work`: `words` word rows of work.x2 - work.x1 words, 32 rows per word), and where its words, columns and tiles start in the call's
+struct MorphRec { long long r0, word0, col0, tile0; MorphBox tight, work; int h, w, r, nruns, words, pad; };
+struct MorphJob {
+    const MorphRec* rec; int n; int op;
+    long long cols, tiles;            // the columns of all boxes; the tiles: per RLE words * ceil(columns / (MORPH_TILE - 2r))
+    const uint32_t* counts;
+    const uint32_t* pre_b;            // rle_prefix_forward's B, indexed like counts
+    uint32_t *va, *vb;                // two bit boxes per RLE: the vertical half's result (and the mask's own bits for BOUNDARY), the result
+};
+// tight[k] from the runs and rle_prefix_forward's totals and extent; *bad (device, one word) = the lowest k whose total is not its
+// plane's h*w, ~0 if all are right: the caller reads both back before anything else is sized or launched
+void rle_morph_boxes_forward(hipStream_t s, const uint32_t* counts, const uint32_t* pre_b, const long long* run_offsets, const int32_t* heights,
+                             const int32_t* widths, const unsigned long long* totals, const uint2* extent, long n, MorphBox* tight,
+                             unsigned long long* bad);
+// the vertical and the horizontal half: job.vb holds the result's bits
+void rle_morph_forward(hipStream_t s, const MorphJob& job);
+// the encoder's two passes on those bits, as masks_rle_count_forward / masks_rle_write_forward run them (segs: n * RLE_SEGS, nruns: n)
+void rle_morph_count_forward(hipStream_t s, const MorphJob& job, RleSeg* segs, uint32_t* nruns, long long* run_offsets, uint32_t* areas, int32_t* bboxes);
+void rle_morph_write_forward(hipStream_t s, const MorphJob& job, const RleSeg* segs, const long long* run_offsets, uint32_t* counts);
+
 // inter / iou of every pair of every group.  block_starts (n_groups + 1, device): prefix of ceil(nd / 4) * ng per group = the grid.
 // The caller has checked that the two RLEs of every pair have the same total.  inter / iou may be nullptr.
 void rle_iou_forward(hipStream_t s, const uint32_t* d_b, const long long* d_off, const unsigned long long* d_total, const uint32_t* d_area,

@@ -634,3 +634,144 @@ def rle_to_polygons_host(rles, sizes=None, flat: bool = False, tolerance=None, n
     """The definition of rle_to_polygons: the sequential host code (``mrcnn_rle_to_polygons_host``, and ``mrcnn_polygons_simplify_host``
     for a tolerance, ``mrcnn_polygons_nest_host`` for nest=True), no GPU; numpy out."""
     return _rle_to_polygons(True, rles, sizes, None, flat, tolerance, nest)
+
+
+# ---- changing run-length masks (mrcnn_rle_morph, mrcnn_boundary_radius) -------------------------------------------------------------------
+MORPH_OPS = {"erode": _lib.MORPH_ERODE, "dilate": _lib.MORPH_DILATE, "boundary": _lib.MORPH_BOUNDARY}
+
+
+def boundary_radius(h: int, w: int, ratio: float = 0.02) -> int:
+    """The band width Boundary IoU takes for an h x w image (``mrcnn_boundary_radius``): max(1, round(ratio * the diagonal)), half to
+    even, in double — 16 for 480 x 640 and 102 for 3072 x 4096 at the published ratio 0.02."""
+    r = C.c_int32(0)
+    _lib.check(_lib.lib().mrcnn_boundary_radius(int(h), int(w), float(ratio), C.byref(r)))
+    return int(r.value)
+
+
+def _morph_flat(host_definition, space, counts, offs, hs, ws, radii, op):
+    """mrcnn_rle_morph(_host) on a flat set of ``space``: counts, run_offsets (n + 1), and host int32 arrays hs, ws, radii of n ->
+    (counts, run_offsets, areas (n), bboxes (n, 4)) in the same space.  A first attempt is sized from the input's runs; if the result
+    needs more, one more call with the capacity the library reported."""
+    n = int(offs.shape[0]) - 1
+    ptr = space.ptr
+    out_offs, areas, bboxes = space.new(n + 1, np.int64, zero=True), space.new(max(1, n), np.uint32), space.new((max(1, n), 4), np.int32)
+    entry = _lib.lib().mrcnn_rle_morph_host if host_definition else _lib.lib().mrcnn_rle_morph
+    head = (ptr(counts), ptr(offs), n, hs.ctypes.data, ws.ctypes.data, radii.ctypes.data, int(op)) + (() if host_definition else (space.code,))
+    capacity = int(counts.shape[0]) + 2 * n + 2
+    for _ in range(2):
+        out = space.new(max(1, capacity), np.uint32)
+        st = entry(*head, ptr(out), capacity, ptr(out_offs), ptr(areas), ptr(bboxes))
+        if st != 4 or int(out_offs[n]) <= capacity:
+            break
+        capacity = int(out_offs[n])
+    _lib.check(st)
+    return out[:int(out_offs[n])], out_offs, areas[:n], bboxes[:n]
+
+
+def rle_rows_of(pair, sizes):
+    """A (counts, run_offsets) pair of B * slots RLEs, numpy arrays or CUDA tensors, as the rows rles[b][i] = {"size": [h_b, w_b],
+    "counts": uint32 runs} on the host, for ``sizes`` = [(h_b, w_b)] per image."""
+    c, o = (a.cpu().numpy() if hasattr(a, "is_cuda") else np.asarray(a) for a in pair)
+    c, B = c.view(np.uint32), len(sizes)
+    slots = (len(o) - 1) // B if B else 0
+    return [[{"size": [int(sizes[b][0]), int(sizes[b][1])], "counts": c[int(o[b * slots + i]):int(o[b * slots + i + 1])]} for i in range(slots)]
+            for b in range(B)]
+
+
+def _rle_morph(host_definition, rle, sizes, radii, op, device):
+    name = "rle_morph_host" if host_definition else "rle_morph"
+    if op not in MORPH_OPS and op not in MORPH_OPS.values():
+        raise ValueError(f"{name}: op {op!r} is none of {sorted(MORPH_OPS)}")
+    pair = isinstance(rle, tuple) and len(rle) == 2 and not isinstance(rle[0], (list, tuple, dict))
+    if device is None and not host_definition and pair and hasattr(rle[0], "is_cuda"):
+        device = rle[0].device                                   # a pair of CUDA tensors: changed where it lies, tensors out
+    counts, offs, B, slots, hs, ws = _rle_set(name, rle, sizes, device)
+    n = B * slots
+    hs, ws = np.repeat(hs, slots).astype(np.int32), np.repeat(ws, slots).astype(np.int32)
+    r = np.asarray(radii, dtype=np.float64).reshape(-1)
+    if r.size not in (1, B, n) or r.size == 0:
+        raise ValueError(f"{name}: {r.size} radii for {n} RLEs of {B} sizes: one, one per size or one per RLE expected")
+    if (r != np.rint(r)).any() or (np.abs(r) > 2 ** 30).any():
+        raise ValueError(f"{name}: a radius is a whole number of pixels")
+    r = np.ascontiguousarray(np.broadcast_to(r, (n,)) if r.size in (1, n) else np.repeat(r, slots)).astype(np.int32)
+    space = Space(device)
+    out, out_offs, areas, bboxes = _morph_flat(host_definition, space, counts, offs, hs, ws, r, MORPH_OPS.get(op, op))
+    if pair:
+        return (out, out_offs), areas, bboxes
+    host = lambda a: a if space.on_host else a.cpu().numpy()
+    rles = rle_rows_of((out, out_offs), [(hs[b * slots], ws[b * slots]) for b in range(B)] if slots else [])
+    return rles, host(areas).view(np.uint32).reshape(B, slots), host(bboxes).reshape(B, slots, 4)
+
+
+def rle_morph(rle, sizes, radii, op, device=None):
+    """A set of run-length masks eroded, dilated or cut down to its inner boundary band on the GPU, RLE in and RLE out, no plane in
+    between (``mrcnn_rle_morph``; the rule is defined in include/maskrcnn_hip.h: a square structuring element of radius r, pixels
+    outside the image are 0).  ``rle`` is a (counts, run_offsets) pair — numpy arrays or CUDA tensors, which are changed where they lie
+    (DeviceDetections and COCOGroundTruth.to_device() hold such pairs; _merge_tiles leaves one) — with ``sizes`` = [(h, w)] per RLE or
+    per image of equally many RLEs, or the rows rles[b][i] = {"size", "counts"} that masks_rle_source, merge_tiles and unite_tiles
+    return (sizes may be None).  ``radii``: one radius, or one per size or per RLE, 0..1024.  ``op``: "erode", "dilate" or "boundary"
+    (the mask minus its erosion).  Returns (rle, areas, bboxes): the result in the form it came in — a pair in the same memory space,
+    or rows — with the set pixels and their tight boxes x, y, w, h as masks_rle_source gives them, per RLE for a pair and (B, slots)
+    for rows.  The result feeds rle_to_polygons, instance_map_rle, rle_decode_planes and coco_eval as it is."""
+    return _rle_morph(False, rle, sizes, radii, op, device)
+
+
+def rle_morph_host(rle, sizes, radii, op):
+    """The definition of rle_morph: the sequential host code (``mrcnn_rle_morph_host``), no GPU; numpy out."""
+    return _rle_morph(True, rle, sizes, radii, op, None)
+
+
+def _band_radii(name, rle, sizes, ratio, radius):
+    if radius is not None:
+        return radius
+    if sizes is None:
+        sizes = [row[0]["size"] for row in rle]
+    return [boundary_radius(int(s[0]), int(s[1]), ratio) for s in sizes]
+
+
+def rle_erode(rle, sizes, radius, device=None):
+    """rle_morph(..., "erode")[0]: the masks shrunk by ``radius`` pixels, from the image border too."""
+    return _rle_morph(False, rle, sizes, radius, "erode", device)[0]
+
+
+def rle_dilate(rle, sizes, radius, device=None):
+    """rle_morph(..., "dilate")[0]: the masks buffered by ``radius`` pixels, clipped to the image."""
+    return _rle_morph(False, rle, sizes, radius, "dilate", device)[0]
+
+
+def rle_boundary(rle, sizes=None, ratio: float = 0.02, radius=None, device=None):
+    """rle_morph(..., "boundary")[0]: the inner band of every mask — Boundary IoU's, of width boundary_radius(h, w, ratio) per image,
+    or of ``radius`` pixels when that is given."""
+    return _rle_morph(False, rle, sizes, _band_radii("rle_boundary", rle, sizes, ratio, radius), "boundary", device)[0]
+
+
+def rle_open(rle, sizes, radius, device=None):
+    """Erode, then dilate (two calls): specks and spurs thinner than 2 * radius + 1 go, the rest keeps its size."""
+    return rle_dilate(rle_erode(rle, sizes, radius, device), sizes, radius, device)
+
+
+def rle_close(rle, sizes, radius, device=None):
+    """Dilate, then erode (two calls): pinholes and gaps up to 2 * radius wide are filled.  The image border is 0 for both steps, so
+    a mask within ``radius`` of the border loses what the dilation could not grow there."""
+    return rle_erode(rle_dilate(rle, sizes, radius, device), sizes, radius, device)
+
+
+def rle_erode_host(rle, sizes, radius):
+    return _rle_morph(True, rle, sizes, radius, "erode", None)[0]
+
+
+def rle_dilate_host(rle, sizes, radius):
+    return _rle_morph(True, rle, sizes, radius, "dilate", None)[0]
+
+
+def rle_boundary_host(rle, sizes=None, ratio: float = 0.02, radius=None):
+    return _rle_morph(True, rle, sizes, _band_radii("rle_boundary_host", rle, sizes, ratio, radius), "boundary", None)[0]
+
+
+def rle_open_host(rle, sizes, radius):
+    return rle_dilate_host(rle_erode_host(rle, sizes, radius), sizes, radius)
+
+
+def rle_close_host(rle, sizes, radius):
+    """The definitions of rle_erode, rle_dilate, rle_boundary, rle_open and rle_close: ``mrcnn_rle_morph_host``, no GPU; numpy out."""
+    return rle_erode_host(rle_dilate_host(rle, sizes, radius), sizes, radius)

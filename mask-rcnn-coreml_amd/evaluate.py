@@ -282,13 +282,14 @@ def evaluate_coco(model: MaskRCNN, annotations_json: str, load_image, dataset_id
 
 def evaluate_coco_scored(model: MaskRCNN, annotations_json: str, load_image, dataset_id: str = "coco", limit: Optional[int] = 5, verbose: bool = True,
                          batch: int = 1, iou_types=("bbox", "segm"), threshold: float = 0.5, class_to_category=None, score_threshold: float = 0.0,
-                         device_gt: bool = False, accumulate_on=None, jpeg_entropy: str = "host"):
+                         device_gt: bool = False, accumulate_on=None, jpeg_entropy: str = "host", boundary_ratio: float = 0.02):
     """`maskrcnn evaluate` to its end (EvaluateCommand.swift:159-200, then COCOEval/task.py:93-98): evaluate_segm over the first `limit`
     images of the annotation file sorted by id, then coco_eval.score of those results against the same file, restricted to the images
     that were run.  Returns evaluate_segm's four values plus {iou_type: score dict} (``stats``, ``precision``, ``recall``, ``summary``);
     with verbose the twelve lines of every type are printed the way COCOeval prints them.  device_gt: encode the annotation file's masks
     once on the GPU and score against them where they are resident (COCOGroundTruth.to_device); the numbers are the same.  accumulate_on:
-    where COCOeval's accumulate runs ("host", "device", None = coco_eval.DEFAULT_ACCUMULATE_ON), as coco_eval.score takes it.  jpeg_entropy: evaluate_segm's."""
+    where COCOeval's accumulate runs ("host", "device", None = coco_eval.DEFAULT_ACCUMULATE_ON), as coco_eval.score takes it.  jpeg_entropy: evaluate_segm's.
+    iou_types may name "boundary" (Boundary AP, coco_eval.score) with boundary_ratio, the band width as a fraction of the image diagonal."""
     from .coco import COCO
     from .coco_eval import COCOGroundTruth, score
     coco = COCO(annotations_json)
@@ -300,7 +301,7 @@ def evaluate_coco_scored(model: MaskRCNN, annotations_json: str, load_image, dat
     resident = gt.to_device() if device_gt else None
     for iou_type in iou_types:
         scores[iou_type] = score(gt, results, iou_type, img_ids=[image_id for image_id, _ in items], device_gt=resident,
-                                 accumulate_on=accumulate_on)
+                                 accumulate_on=accumulate_on, boundary_ratio=boundary_ratio)
         if verbose:
             print("\n".join(scores[iou_type]["summary"]))
     return pb, secs, out, results, scores

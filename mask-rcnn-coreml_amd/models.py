@@ -143,7 +143,7 @@ class MaskRCNN(_Model):
         return det, mask
 
     def predict_tiled(self, images, tile=None, overlap=(64, 64), metric="ios", match_threshold=0.5, max_out=None, threshold=0.5,
-                      unite=False, link_threshold=0.5, polygons=False, tolerance=None, nest=False):
+                      unite=False, link_threshold=0.5, polygons=False, tolerance=None, nest=False, close=0):
         """Large images as overlapping windows at native resolution: detection.tile_plan per image (tile = None: the model's input
         size), predict_tiles, detection.merge_tiles.  Returns (det_src, source, n_kept, rles) in the frame of the images, in the
         form coco_results.coco_results and coco_eval.score_batch take.  By default an object is found whole only if some window
@@ -153,8 +153,10 @@ class MaskRCNN(_Model):
         detection.rle_to_polygons returns them: the boundaries of the masks, traced from the runs where the merge or the union left
         them — on the device when the images are CUDA tensors.  tolerance (pixels) simplifies those rings there too
         (detection.simplify_polygons); the areas stay the pixel areas.  nest=True makes that result (rings, areas, nesting): the rings
-        nested into outlines and their holes (detection.nest_polygons), in the same place, on the traced rings."""
-        from .detection import _merge_tiles, rle_to_polygons, tile_plan
+        nested into outlines and their holes (detection.nest_polygons), in the same place, on the traced rings.  close=r (pixels; 0: the
+        masks as they are) closes the kept masks first — detection.rle_close on the runs where they lie: pinholes and gaps up to 2r
+        wide are filled — and both the returned rles and the polygons are those of the closed masks."""
+        from .detection import _merge_tiles, rle_close, rle_rows_of, rle_to_polygons, tile_plan
         images = list(images)
         H, W = self.image_height, self.image_width
         tile = (H, W) if tile is None else tile
@@ -164,6 +166,9 @@ class MaskRCNN(_Model):
         resident = []
         out = _merge_tiles(False, det, mask, tiles, sizes, H, W, threshold, metric, link_threshold if unite else match_threshold, max_out, unite=unite,
                            resident=resident)[:4]
+        if close:
+            resident[0] = rle_close(resident[0], sizes, int(close))
+            out = (*out[:3], rle_rows_of(resident[0], sizes))
         if not polygons:
             return out
         return (*out, rle_to_polygons(resident[0], sizes, tolerance=tolerance, nest=nest))
