@@ -5,16 +5,20 @@
  * simplified first (mrcnn_polygons_simplify, Douglas-Peucker within T pixels): the areas printed stay the pixel areas.  With
  * --geojson FILE the traced rings are nested into outlines and their holes (mrcnn_polygons_nest) and FILE receives a GeoJSON
  * FeatureCollection: one Feature per mask that has a ring, a Polygon for one outline and a MultiPolygon for several, every hole with the
- * outline it lies in.  The nesting is that of the traced rings; a tolerance only changes the vertices written.
+ * outline it lies in.  The nesting is that of the traced rings; a tolerance only changes the vertices written.  With --fill-holes the
+ * holes of every mask are filled and with --min-area A its specks of fewer than A pixels are cleared before anything is traced, holes
+ * first (mrcnn_rle_components measures the connected components, mrcnn_rle_components_select merges the kept ones back).
  *
  *   cc -std=c99 -Iinclude examples/maskrcnn_polygons.c -Lmask-rcnn-coreml_amd -lmaskrcnn_hip \
  *      -Wl,-rpath,$PWD/mask-rcnn-coreml_amd -Wl,-rpath-link,/opt/rocm/lib -o maskrcnn_polygons
- *   ./maskrcnn_polygons [--host] [--tolerance T] [--geojson FILE] <set.txt>
+ *   ./maskrcnn_polygons [--host] [--tolerance T] [--geojson FILE] [--min-area A] [--fill-holes] <set.txt>
+ *   (the flags in this order; --min-area and --fill-holes in either)
  *
  * <set.txt> holds whitespace-separated integers: n_images and slots; then per image its height and width and, for each of its `slots`
  * RLEs, the number of runs followed by the runs (column-major, the first run counts zeros) — the layout mrcnn_masks_rle_source,
  * mrcnn_merge_tiles and mrcnn_unite_tiles write.  --host calls the sequential definitions, mrcnn_rle_to_polygons_host and
- * mrcnn_polygons_simplify_host (and mrcnn_polygons_nest_host), which need no GPU.  Exit status 0 on success; on failure the mrcnn_last_error() text goes to stderr and the status code is the exit status.
+ * mrcnn_polygons_simplify_host (and mrcnn_polygons_nest_host, mrcnn_rle_components_host,
+ * mrcnn_rle_components_select_host), which need no GPU.  Exit status 0 on success; on failure the mrcnn_last_error() text goes to stderr and the status code is the exit status.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -31,6 +35,57 @@ static int trace(int host, const uint32_t* counts, const int64_t* run_offsets, i
                                           ring_capacity, xy, vertex_capacity);
     return mrcnn_rle_to_polygons(counts, run_offsets, n_images, slots, heights, widths, MRCNN_HOST, rle_rings, n_rings, n_vertices, ring_offsets,
                                  ring_areas, ring_capacity, xy, vertex_capacity);
+}
+
+/* The set with some connected components of the value `of` merged away: those of fewer than min_area pixels (of ones), or those that do
+ * not touch the image border (of zeros: the holes).  Both entries are asked for their sizes first.  *counts and run_offsets are replaced. */
+static int filter_components(int host, int of, uint32_t** counts, int64_t* run_offsets, int64_t n, const int32_t* hs, const int32_t* ws, long long min_area)
+{
+    int64_t* comp_offsets = (int64_t*)malloc(sizeof(int64_t) * (size_t)(n + 1));
+    int64_t* out_offsets = (int64_t*)malloc(sizeof(int64_t) * (size_t)(n + 1));
+    uint32_t *areas = NULL, *out = NULL;
+    int32_t* boxes = NULL;
+    uint8_t *flags = NULL, *keep = NULL;
+    int64_t comps = 0, runs = 0, out_n = 0;
+    int st = -1;                                                 /* -1: out of memory, no library text goes with it */
+    if (!comp_offsets || !out_offsets) goto done;
+    comp_offsets[n] = 0;
+    st = host ? mrcnn_rle_components_host(*counts, run_offsets, n, hs, ws, 4, of, comp_offsets, NULL, NULL, NULL, 0)
+              : mrcnn_rle_components(*counts, run_offsets, n, hs, ws, 4, of, MRCNN_HOST, comp_offsets, NULL, NULL, NULL, 0);
+    if (st != MRCNN_OK && !(st == MRCNN_ERR_SHAPE && comp_offsets[n] > 0)) goto done;
+    comps = comp_offsets[n];
+    areas = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)(comps + 1));
+    boxes = (int32_t*)malloc(sizeof(int32_t) * 4 * (size_t)(comps + 1));
+    flags = (uint8_t*)malloc((size_t)(comps + 1));
+    keep = (uint8_t*)malloc((size_t)(comps + 1));
+    st = -1;
+    if (!areas || !boxes || !flags || !keep) goto done;
+    st = host ? mrcnn_rle_components_host(*counts, run_offsets, n, hs, ws, 4, of, comp_offsets, areas, boxes, flags, comps)
+              : mrcnn_rle_components(*counts, run_offsets, n, hs, ws, 4, of, MRCNN_HOST, comp_offsets, areas, boxes, flags, comps);
+    if (st != MRCNN_OK) goto done;
+    for (int64_t c = 0; c < comps; ++c) keep[c] = of == MRCNN_COMPONENTS_OF_ONES ? (long long)areas[c] >= min_area : (flags[c] & 1) != 0;
+    out_offsets[n] = 0;
+    st = host ? mrcnn_rle_components_select_host(*counts, run_offsets, n, hs, ws, 4, of, keep, comps, MRCNN_COMPONENTS_MERGE, NULL, 0, out_offsets, NULL, NULL,
+                                                 NULL, &out_n)
+              : mrcnn_rle_components_select(*counts, run_offsets, n, hs, ws, 4, of, keep, comps, MRCNN_COMPONENTS_MERGE, MRCNN_HOST, NULL, 0, out_offsets, NULL,
+                                            NULL, NULL, &out_n);
+    if (st != MRCNN_OK && !(st == MRCNN_ERR_SHAPE && out_offsets[n] > 0)) goto done;
+    runs = out_offsets[n];
+    out = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)(runs + 1));
+    st = -1;
+    if (!out) goto done;
+    st = host ? mrcnn_rle_components_select_host(*counts, run_offsets, n, hs, ws, 4, of, keep, comps, MRCNN_COMPONENTS_MERGE, out, runs, out_offsets, NULL, NULL,
+                                                 NULL, &out_n)
+              : mrcnn_rle_components_select(*counts, run_offsets, n, hs, ws, 4, of, keep, comps, MRCNN_COMPONENTS_MERGE, MRCNN_HOST, out, runs, out_offsets, NULL,
+                                            NULL, NULL, &out_n);
+    if (st != MRCNN_OK) goto done;
+    memcpy(run_offsets, out_offsets, sizeof(int64_t) * (size_t)(n + 1));
+    free(*counts);
+    *counts = out;
+    out = NULL;
+done:
+    free(out); free(keep); free(flags); free(boxes); free(areas); free(out_offsets); free(comp_offsets);
+    return st;
 }
 
 /* one ring as a closed GeoJSON ring: its first vertex repeated, an exterior with positive shoelace area and a hole with negative (a
@@ -93,12 +148,19 @@ int main(int argc, char** argv)
     const int host = argc > 1 && strcmp(argv[1], "--host") == 0;
     const int simplify = argc > 1 + host && strcmp(argv[1 + host], "--tolerance") == 0;
     const int geo = argc > 1 + host + 2 * simplify && strcmp(argv[1 + host + 2 * simplify], "--geojson") == 0;
-    const int file = 1 + host + 2 * simplify + 2 * geo;
-    if (argc != file + 1) {
-        fprintf(stderr, "usage: %s [--host] [--tolerance T] [--geojson FILE] <set.txt>\n", argv[0]);
+    const int geo_at = 1 + host + 2 * simplify;
+    int small = 0, fill = 0, area_at = 0, file = geo_at + 2 * geo;
+    for (int turn = 0; turn < 2; ++turn) {                       /* the two component flags, in either order, once each */
+        if (!small && argc > file + 1 && strcmp(argv[file], "--min-area") == 0) { small = 1; area_at = file + 1; file += 2; }
+        else if (!fill && argc > file && strcmp(argv[file], "--fill-holes") == 0) { fill = 1; file += 1; }
+    }
+    if (argc != file + 1 || strncmp(argv[file], "--", 2) == 0) {         /* (a flag out of place, or one without its value) */
+        fprintf(stderr, "usage: %s [--host] [--tolerance T] [--geojson FILE] [--min-area A] [--fill-holes] <set.txt>\n", argv[0]);
         return 64;
     }
     const double tolerance = simplify ? atof(argv[2 + host]) : 0.0;
+    const long long min_area = small ? atoll(argv[area_at]) : 0;
+    const char* geo_file = geo ? argv[geo_at + 1] : NULL;
     FILE* f = fopen(argv[file], "r");
     if (!f) { fprintf(stderr, "cannot read %s\n", argv[file]); return 66; }
     int n_images = 0, slots = 0;
@@ -134,6 +196,21 @@ int main(int argc, char** argv)
         }
     }
     fclose(f);
+
+    if (fill || small) {                                         /* per RLE sizes; holes first, then specks */
+        int32_t* hs = (int32_t*)malloc(sizeof(int32_t) * (n + 1));
+        int32_t* ws = (int32_t*)malloc(sizeof(int32_t) * (n + 1));
+        if (!hs || !ws) { fprintf(stderr, "out of memory\n"); return 70; }
+        for (size_t k = 0; k < n; ++k) { hs[k] = heights[k / (size_t)slots]; ws[k] = widths[k / (size_t)slots]; }
+        int st = fill ? filter_components(host, MRCNN_COMPONENTS_OF_ZEROS, &counts, run_offsets, (int64_t)n, hs, ws, 0) : MRCNN_OK;
+        if (st == MRCNN_OK && small) st = filter_components(host, MRCNN_COMPONENTS_OF_ONES, &counts, run_offsets, (int64_t)n, hs, ws, min_area);
+        if (st == -1) { fprintf(stderr, "out of memory\n"); return 70; }
+        if (st != MRCNN_OK) {
+            fprintf(stderr, "mrcnn_rle_components%s failed (%d): %s\n", host ? "_host" : "", st, mrcnn_last_error());
+            return st;
+        }
+        free(ws); free(hs);
+    }
 
     /* the size query: no buffers, both capacities 0.  MRCNN_ERR_SHAPE is its answer when there is anything to write. */
     int64_t rings = 0, vertices = 0;
@@ -196,10 +273,10 @@ int main(int argc, char** argv)
             printf("\n");
         }
     if (geo) {
-        FILE* g = fopen(argv[file - 1], "w");
-        if (!g) { fprintf(stderr, "cannot write %s\n", argv[file - 1]); return 73; }
+        FILE* g = fopen(geo_file, "w");
+        if (!g) { fprintf(stderr, "cannot write %s\n", geo_file); return 73; }
         write_geojson(g, n, slots, rle_rings, ring_offsets, ring_areas, xy, rle_polys, poly_rings, ring_order);
-        if (fclose(g) != 0) { fprintf(stderr, "cannot write %s\n", argv[file - 1]); return 74; }
+        if (fclose(g) != 0) { fprintf(stderr, "cannot write %s\n", geo_file); return 74; }
         free(ring_order); free(poly_rings); free(rle_polys);
     }
     free(xy); free(ring_areas); free(ring_offsets); free(counts); free(rle_rings); free(run_offsets); free(widths); free(heights);

@@ -1075,8 +1075,8 @@ MRCNN_API int mrcnn_polygons_nest_host(const int64_t* rle_rings, int64_t n_rles,
  * MRCNN_ERR_SHAPE, the message starts "rle_morph:" / "rle_morph_host:" and names the lowest such k, nothing is written; a ratio that is
  * not finite or not > 0, sides outside 1..32767 -> MRCNN_ERR_SHAPE from mrcnn_boundary_radius.  Argument errors are answered before a
  * device is looked for; no gfx950 device -> MRCNN_ERR_HIP from the device entry (no CPU fallback).
- * Not here: structuring elements other than the square, grey-scale morphology, connected-component filtering, radii above the cap
- * (compose two calls: the semigroup property above). */
+ * Not here: structuring elements other than the square, grey-scale morphology, radii above the cap (compose two calls: the semigroup
+ * property above). */
 #define MRCNN_MORPH_ERODE 0
 #define MRCNN_MORPH_DILATE 1
 #define MRCNN_MORPH_BOUNDARY 2
@@ -1088,6 +1088,77 @@ MRCNN_API int mrcnn_rle_morph_host(const uint32_t* counts, const int64_t* run_of
                                    const int32_t* radii, int op, uint32_t* out_counts, int64_t capacity, int64_t* out_run_offsets,
                                    uint32_t* areas, int32_t* bboxes_xywh);
 MRCNN_API int mrcnn_boundary_radius(int h, int w, double ratio, int32_t* radius);
+
+/* ---- cutting run-length masks into connected components (csrc/api_rle_components.hip, kernels_rle_components.hip) --------------------
+ * Keep the object, drop the specks, fill the holes, or cut a mask into its parts: RLE in, measures or RLE out, no dense plane.  The set
+ * is flat as mrcnn_rle_morph takes it: RLE k is counts[run_offsets[k] .. run_offsets[k+1]) and encodes a heights[k] x widths[k] plane
+ * (sides 1..32767); heights and widths are HOST arrays of n.  Zero-length runs are allowed anywhere: the result is that of the
+ * canonical RLE of the same plane.
+ * The rule (csrc/components_rule.h).  P is the h x w {0,1} plane of RLE k.  connectivity is 4 or 8; `of` chooses the value that is
+ * labelled.  Components of ones (MRCNN_COMPONENTS_OF_ONES) use `connectivity`; components of zeros (MRCNN_COMPONENTS_OF_ZEROS) use the
+ * dual, 8 where connectivity is 4 and 4 where it is 8.  At connectivity 4 the components of ones are exactly what
+ * mrcnn_rle_to_polygons traces as outlines, and the components of zeros that do not touch the border exactly what it traces as holes.
+ * Nothing continues outside the image.  The components of RLE k are numbered from 0 in rising order of their first pixel in
+ * column-major position p = x*h + y; an empty plane (for ones) or a full one (for zeros) has none.
+ * mrcnn_rle_components labels and measures — one entry per component, all components of the set back to back:
+ *   comp_offsets (n + 1, int64)   always written: RLE k owns the components comp_offsets[k] .. comp_offsets[k+1]
+ *   comp_areas (uint32)           the pixels of the component
+ *   comp_bboxes_xywh (int32 x 4)  its tight box x, y, w, h
+ *   comp_flags (uint8)            bit 0: the component holds a pixel with x == 0, x == w-1, y == 0 or y == h-1
+ * The three per-component arrays are written only when comp_offsets[n] <= comp_capacity: otherwise MRCNN_ERR_SHAPE, the message names
+ * the capacity needed and nothing else is written; comp_capacity = 0 with null arrays is the size query.
+ * mrcnn_rle_components_select labels again and writes RLEs.  keep is one uint8 per component in the order above, in `memspace`;
+ * n_comps must equal the number of components found: otherwise MRCNN_ERR_SHAPE, the message names both numbers, nothing is written.
+ *   MRCNN_COMPONENTS_MERGE  n RLEs come out: a pixel of a kept component stays as it is, a pixel of a dropped component takes the other
+ *                           value (of ONES: specks are cleared; of ZEROS: holes are filled), pixels of the value that was not labelled
+ *                           stay.  out_parent may be NULL (else out_parent[k] = k); *out_n = n.
+ *   MRCNN_COMPONENTS_SPLIT  of ONES only (else MRCNN_ERR_SHAPE): one RLE per kept component, in component order, each over its
+ *                           parent's full h x w plane; out_parent[j] is the parent's k, *out_n the number kept.  out_run_offsets
+ *                           holds *out_n + 1 entries: the caller gives room for n_comps + 1 (MERGE: n + 1), and for n_comps (MERGE: n)
+ *                           entries of out_parent, areas and bboxes_xywh.
+ * The output RLEs are canonical, exactly as mrcnn_rle_morph writes them (runs continue across column ends, an empty plane is [h*w]);
+ * areas and bboxes_xywh are optional (NULL) and the out_counts / capacity protocol with its size query is mrcnn_rle_morph's:
+ * out_run_offsets, out_parent, *out_n and the optional arrays are written whatever the capacity, out_counts only when all runs fit.
+ * memspace holds for counts, run_offsets, keep and every output array; out_n is a host word in both memory spaces.  n = 0 is legal.
+ * The _host entries are the definition: sequential plain C++, no GPU, host pointers; one RLE at a time a plane is decoded and flooded
+ * from every unlabelled pixel in rising position.  The device entries equal them bit for bit in every output array and never build a
+ * plane.  The nodes are PIECES: a run of the labelled value cut at the ends of its pixel columns, touching pieces of one column joined
+ * first.  The pieces per run are counted and scanned, a table of (RLE, [start, end) position) is written — index order is pixel order
+ * — and one thread per piece finds, with one binary search in its RLE's table and a walk, the pieces of column x + 1 that meet it:
+ * rows [a, b) and [c, d) meet if a < d && c < b (4) or a <= d && c <= b (8).  Every meeting pair is united in a parent array without
+ * locks: find both roots, hang the larger under the smaller with an integer compare-and-swap, retry from the value read.  The smaller
+ * index always wins, so a component's root is its lowest piece whatever the order of execution and every output is deterministic; no
+ * workgroup waits for another.  Root flags scanned give the rule's numbering; integer atomics give area, box and flag.  MERGE walks the
+ * pieces with their keep bits — a piece starts a run unless the piece before it is kept and ends where it starts, which joins runs
+ * across column ends — scans, and writes differences of positions; SPLIT first sorts the pieces by (component, piece) with a bitonic
+ * network and runs the same writer per component.  The parent array lives in global memory for every RLE.  The number of launches
+ * depends on neither n nor the number of components (SPLIT's sort: on the logarithm of the number of pieces).
+ * Errors: null pointer, unknown memspace -> MRCNN_ERR_INVALID; n < 0, a side outside 1..32767, a connectivity other than 4 and 8, an
+ * unknown `of` or mode, SPLIT of zeros, run_offsets that decrease, n_comps < 0 -> MRCNN_ERR_SHAPE; an RLE that does not sum to its h*w
+ * -> MRCNN_ERR_SHAPE, the message starts "rle_components:" / "rle_components_host:" / "rle_components_select:" /
+ * "rle_components_select_host:" and names the lowest such k, nothing is written.  Argument errors are answered before a device is
+ * looked for; no gfx950 device -> MRCNN_ERR_HIP from the device entries (no CPU fallback).
+ * Not here: uniting or splitting across images, cutting wrongly chained components inside mrcnn_unite_tiles, labelling instance-id
+ * or panoptic maps, filtering by shape other than area, rank and border (the measures are there to build a keep mask from),
+ * 6-connectivity, a workgroup-local path for small RLEs. */
+#define MRCNN_COMPONENTS_OF_ZEROS 0
+#define MRCNN_COMPONENTS_OF_ONES 1
+#define MRCNN_COMPONENTS_MERGE 0
+#define MRCNN_COMPONENTS_SPLIT 1
+MRCNN_API int mrcnn_rle_components(const uint32_t* counts, const int64_t* run_offsets, int64_t n, const int32_t* heights, const int32_t* widths,
+                                   int connectivity, int of, int memspace, int64_t* comp_offsets, uint32_t* comp_areas,
+                                   int32_t* comp_bboxes_xywh, uint8_t* comp_flags, int64_t comp_capacity);
+MRCNN_API int mrcnn_rle_components_host(const uint32_t* counts, const int64_t* run_offsets, int64_t n, const int32_t* heights,
+                                        const int32_t* widths, int connectivity, int of, int64_t* comp_offsets, uint32_t* comp_areas,
+                                        int32_t* comp_bboxes_xywh, uint8_t* comp_flags, int64_t comp_capacity);
+MRCNN_API int mrcnn_rle_components_select(const uint32_t* counts, const int64_t* run_offsets, int64_t n, const int32_t* heights,
+                                          const int32_t* widths, int connectivity, int of, const uint8_t* keep, int64_t n_comps, int mode,
+                                          int memspace, uint32_t* out_counts, int64_t capacity, int64_t* out_run_offsets, uint32_t* areas,
+                                          int32_t* bboxes_xywh, int64_t* out_parent, int64_t* out_n);
+MRCNN_API int mrcnn_rle_components_select_host(const uint32_t* counts, const int64_t* run_offsets, int64_t n, const int32_t* heights,
+                                               const int32_t* widths, int connectivity, int of, const uint8_t* keep, int64_t n_comps, int mode,
+                                               uint32_t* out_counts, int64_t capacity, int64_t* out_run_offsets, uint32_t* areas,
+                                               int32_t* bboxes_xywh, int64_t* out_parent, int64_t* out_n);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,7 @@ F32, F64, F16, U8, I32, F32S, F32X3 = 0, 1, 2, 3, 4, 5, 6
 DEFAULT = -1          # MRCNN_DEFAULT of mrcnn_model_load: the mode the artefact is prepared for (stored split exponents -> F32X3, else F32)
 HOST, DEVICE = 0, 1
 MORPH_ERODE, MORPH_DILATE, MORPH_BOUNDARY, MORPH_MAX_RADIUS = 0, 1, 2, 1024
+COMPONENTS_OF_ZEROS, COMPONENTS_OF_ONES, COMPONENTS_MERGE, COMPONENTS_SPLIT = 0, 1, 0, 1
 PARAM_INT, PARAM_DOUBLE, PARAM_STRING = 0, 1, 2
 MODEL_MASKRCNN, MODEL_CLASSIFIER, MODEL_MASK = 0, 1, 2
 
@@ -53,6 +54,7 @@ EXPORTED_SYMBOLS = [
     "mrcnn_polygons_simplify", "mrcnn_polygons_simplify_host",
     "mrcnn_polygons_nest", "mrcnn_polygons_nest_host",
     "mrcnn_rle_morph", "mrcnn_rle_morph_host", "mrcnn_boundary_radius",
+    "mrcnn_rle_components", "mrcnn_rle_components_host", "mrcnn_rle_components_select", "mrcnn_rle_components_select_host",
 ]
 # declared in include/maskrcnn_hip_test.h (test / measurement entry points of the same library)
 TEST_SYMBOLS = [
@@ -225,6 +227,13 @@ def lib():
     L.mrcnn_rle_morph.argtypes = [vp, vp, C.c_int64, vp, vp, vp, C.c_int, C.c_int] + _morph
     L.mrcnn_rle_morph_host.argtypes = [vp, vp, C.c_int64, vp, vp, vp, C.c_int] + _morph
     L.mrcnn_boundary_radius.argtypes = [C.c_int, C.c_int, C.c_double, vp]
+    _cset = [vp, vp, C.c_int64, vp, vp, C.c_int, C.c_int]         # counts, run_offsets, n, heights, widths, connectivity, of
+    _comps = [vp, vp, vp, vp, C.c_int64]                          # comp_offsets, comp_areas, comp_bboxes_xywh, comp_flags, comp_capacity
+    L.mrcnn_rle_components.argtypes = _cset + [C.c_int] + _comps
+    L.mrcnn_rle_components_host.argtypes = _cset + _comps
+    _csel = _morph + [vp, i64p]                                   # ... out_parent, out_n
+    L.mrcnn_rle_components_select.argtypes = _cset + [vp, C.c_int64, C.c_int, C.c_int] + _csel
+    L.mrcnn_rle_components_select_host.argtypes = _cset + [vp, C.c_int64, C.c_int] + _csel
     L.mrcnn_rle_to_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_from_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_iou.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int64]

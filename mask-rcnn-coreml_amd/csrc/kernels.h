@@ -557,6 +557,45 @@ void rle_morph_forward(hipStream_t s, const MorphJob& job);
 void rle_morph_count_forward(hipStream_t s, const MorphJob& job, RleSeg* segs, uint32_t* nruns, long long* run_offsets, uint32_t* areas, int32_t* bboxes);
 void rle_morph_write_forward(hipStream_t s, const MorphJob& job, const RleSeg* segs, const long long* run_offsets, uint32_t* counts);
 
+// ================================================================================================
+// Connected components of run-length masks (kernels_rle_components.hip; the rule is components_rule.h).  All tables are device arrays.
+// ================================================================================================
+// the set: heights, widths and rle_prefix_forward's totals per RLE, its B per run
+struct CompSet {
+    const uint32_t* counts; const uint32_t* pre_b; const long long* run_offsets;
+    const int32_t* heights; const int32_t* widths; const unsigned long long* totals;
+    int n, connectivity, of;
+};
+// The pieces, in column-major order RLE after RLE: positions [pa, pb) (x*h + y) inside one column, the RLE, the union-find parents,
+// and after the labelling the root (the component's lowest piece) and the component's number in the whole set
+struct CompPieces { long long n; uint32_t *pa, *pb; int32_t* rle; uint32_t *parent, *root, *comp; };
+struct CompAcc { uint32_t* area; int32_t *x1, *y1, *x2, *y2; uint32_t* flag; };         // per component, while it is measured
+// one group of the writer's sequence per output RLE: its places, its parent RLE, what k_cc_groups and k_cc_runs find
+struct CompGroups { long long n; long long *begin, *end; int32_t* rle; uint32_t *lead, *nruns, *area; int32_t *x1, *y1, *x2, *y2; };
+// the selection: keep per component; SPLIT adds the sorted order, the components' first places and the kept components' output index
+struct CompSelect { const uint8_t* keep; long long n_comps; const uint32_t* order; const long long* comp_first; const unsigned long long* out_index; };
+// run_cnt[j] = the pieces run run_offsets[0] + j owns, run_start = its exclusive prefix (runs + 1); *bad = the lowest RLE with a wrong total, ~0 if none
+void rle_components_count_forward(hipStream_t s, const CompSet& S, long long runs, uint32_t* run_cnt, unsigned long long* run_start, unsigned long long* bad);
+// pieces, links, roots and numbers: piece0 (n + 1), is_root (pieces), comp_start (pieces + 1), comp_rle (pieces at most), comp_offsets (n + 1)
+void rle_components_label_forward(hipStream_t s, const CompSet& S, long long runs, const unsigned long long* run_start, const CompPieces& P,
+                                  long long* piece0, uint32_t* is_root, unsigned long long* comp_start, int32_t* comp_rle, long long* comp_offsets);
+void rle_components_measure_forward(hipStream_t s, const CompSet& S, const CompPieces& P, const CompAcc& acc, long long n_comps, uint32_t* areas,
+                                    int32_t* bboxes, uint8_t* flags);
+// SPLIT's order: keys holds rle_components_sort_padded(pieces) entries, order pieces, comp_first n_comps + 1
+long long rle_components_sort_padded(long long n_pieces);
+void rle_components_sort_forward(hipStream_t s, const CompPieces& P, long long n_comps, unsigned long long* keys, uint32_t* order, long long* comp_first);
+// flag[c] = keep[c] != 0 and its exclusive prefix out_index (n_comps + 1): out_index[n_comps] components are kept
+void rle_components_keep_forward(hipStream_t s, const uint8_t* keep, long long n_comps, uint32_t* flag, unsigned long long* out_index);
+// the groups (q.order: SPLIT's, else MERGE's), the boundaries each place gives (bcnt, bpos: pieces + 1), out_parent (may be nullptr
+// for MERGE) and out_run_offsets (G.n + 1)
+void rle_components_groups_forward(hipStream_t s, const CompSet& S, const CompPieces& P, const CompSelect& q, const long long* piece0,
+                                   const int32_t* comp_rle, const CompGroups& G, uint32_t* bcnt, unsigned long long* bpos, long long* out_parent,
+                                   long long* out_run_offsets);
+// the boundaries (bnd: bpos[pieces] entries), then the runs (counts may be nullptr: only measured) and the optional areas and boxes
+void rle_components_write_forward(hipStream_t s, const CompSet& S, const CompPieces& P, const CompSelect& q, const CompGroups& G,
+                                  const unsigned long long* bpos, uint32_t* bnd, const long long* out_run_offsets, long long total_runs, uint32_t* counts,
+                                  uint32_t* areas, int32_t* bboxes);
+
 // inter / iou of every pair of every group.  block_starts (n_groups + 1, device): prefix of ceil(nd / 4) * ng per group = the grid.
 // The caller has checked that the two RLEs of every pair have the same total.  inter / iou may be nullptr.
 void rle_iou_forward(hipStream_t s, const uint32_t* d_b, const long long* d_off, const unsigned long long* d_total, const uint32_t* d_area,

@@ -775,3 +775,224 @@ def rle_open_host(rle, sizes, radius):
 def rle_close_host(rle, sizes, radius):
     """The definitions of rle_erode, rle_dilate, rle_boundary, rle_open and rle_close: ``mrcnn_rle_morph_host``, no GPU; numpy out."""
     return rle_erode_host(rle_dilate_host(rle, sizes, radius), sizes, radius)
+
+
+# ---- cutting run-length masks into connected components (mrcnn_rle_components, mrcnn_rle_components_select) -----------------------------
+COMPONENTS_OF = {"ones": _lib.COMPONENTS_OF_ONES, "zeros": _lib.COMPONENTS_OF_ZEROS}
+COMPONENTS_MODES = {"merge": _lib.COMPONENTS_MERGE, "split": _lib.COMPONENTS_SPLIT}
+
+
+class _CompSet:
+    """The RLE set of one components call: where it lies, its flat arrays and the per-RLE sizes."""
+
+    def __init__(self, name, host_definition, rle, sizes, device):
+        self.pair = isinstance(rle, tuple) and len(rle) == 2 and not isinstance(rle[0], (list, tuple, dict))
+        if device is None and not host_definition and self.pair and hasattr(rle[0], "is_cuda"):
+            device = rle[0].device                               # a pair of CUDA tensors: labelled where it lies, tensors out
+        self.counts, self.offs, self.B, self.slots, hs, ws = _rle_set(name, rle, sizes, device)
+        self.n = self.B * self.slots
+        self.image_sizes = [(int(h), int(w)) for h, w in zip(hs, ws)]
+        self.hs, self.ws = np.repeat(hs, self.slots).astype(np.int32), np.repeat(ws, self.slots).astype(np.int32)
+        self.space = Space(device)
+        self.host_definition = host_definition
+
+    def head(self, connectivity, of):
+        if of not in COMPONENTS_OF and of not in COMPONENTS_OF.values():
+            raise ValueError(f"components of {of!r}: one of {sorted(COMPONENTS_OF)} expected")
+        ptr = self.space.ptr
+        return (ptr(self.counts), ptr(self.offs), self.n, self.hs.ctypes.data, self.ws.ctypes.data, int(connectivity), int(COMPONENTS_OF.get(of, of)))
+
+    def u8(self, mask):
+        """a keep mask as contiguous uint8 of the set's memory space"""
+        if self.space.on_host:
+            return np.ascontiguousarray(mask.cpu().numpy() if hasattr(mask, "is_cuda") else mask).astype(np.uint8).reshape(-1)
+        import torch
+        if not hasattr(mask, "is_cuda"):
+            mask = torch.from_numpy(np.ascontiguousarray(mask).astype(np.uint8))
+        return mask.to(device=self.space.device, dtype=torch.uint8).contiguous().reshape(-1)
+
+
+def _components_flat(cs, connectivity, of):
+    """mrcnn_rle_components(_host) on the set: (comp_offsets (n + 1), areas, bboxes (C, 4), flags) in the set's memory space.  A first
+    attempt guesses the number of components; if there are more, one more call with the capacity the library reported."""
+    space, n = cs.space, cs.n
+    ptr = space.ptr
+    comp_offs = space.new(n + 1, np.int64, zero=True)
+    entry = _lib.lib().mrcnn_rle_components_host if cs.host_definition else _lib.lib().mrcnn_rle_components
+    head = cs.head(connectivity, of) + (() if cs.host_definition else (space.code,))
+    capacity = 4 * n + 64
+    for _ in range(2):
+        areas, bboxes, flags = space.new(capacity, np.uint32), space.new((capacity, 4), np.int32), space.new(capacity, np.uint8)
+        st = entry(*head, ptr(comp_offs), ptr(areas), ptr(bboxes), ptr(flags), capacity)
+        if st != 4 or int(comp_offs[n]) <= capacity:
+            break
+        capacity = int(comp_offs[n])
+    _lib.check(st)
+    C_ = int(comp_offs[n])
+    return comp_offs, areas[:C_], bboxes[:C_], flags[:C_]
+
+
+def _select_flat(cs, keep, connectivity, of, mode):
+    """mrcnn_rle_components_select(_host) on the set with a keep mask of its space: ((counts, run_offsets), areas, bboxes, parent)."""
+    if mode not in COMPONENTS_MODES and mode not in COMPONENTS_MODES.values():
+        raise ValueError(f"rle_select_components: mode {mode!r} is none of {sorted(COMPONENTS_MODES)}")
+    mode = int(COMPONENTS_MODES.get(mode, mode))
+    space, n = cs.space, cs.n
+    ptr = space.ptr
+    keep = cs.u8(keep)
+    n_comps = int(keep.shape[0])
+    room = n_comps if mode == _lib.COMPONENTS_SPLIT else n
+    out_offs, areas, bboxes = space.new(room + 1, np.int64, zero=True), space.new(max(1, room), np.uint32), space.new((max(1, room), 4), np.int32)
+    parent = space.new(max(1, room), np.int64)
+    out_n = C.c_int64(0)
+    entry = _lib.lib().mrcnn_rle_components_select_host if cs.host_definition else _lib.lib().mrcnn_rle_components_select
+    head = cs.head(connectivity, of) + ((ptr(keep) if n_comps else None), n_comps, mode) + (() if cs.host_definition else (space.code,))
+    capacity = int(cs.counts.shape[0]) + 2 * room + 2
+    for _ in range(2):
+        out = space.new(max(1, capacity), np.uint32)
+        st = entry(*head, ptr(out), capacity, ptr(out_offs), ptr(areas), ptr(bboxes), ptr(parent), C.byref(out_n))
+        if st != 4 or int(out_offs[out_n.value]) <= capacity:
+            break
+        capacity = int(out_offs[out_n.value])
+    _lib.check(st)
+    m = int(out_n.value)
+    return (out[:int(out_offs[m])], out_offs[:m + 1]), areas[:m], bboxes[:m], parent[:m]
+
+
+def _rle_components(host_definition, rle, sizes, connectivity, of, device):
+    cs = _CompSet("rle_components_host" if host_definition else "rle_components", host_definition, rle, sizes, device)
+    return _components_flat(cs, connectivity, of)
+
+
+def rle_components(rle, sizes=None, connectivity=4, of="ones", device=None):
+    """The connected components of every mask of an RLE set, labelled and measured on the GPU from the runs, no plane in between
+    (``mrcnn_rle_components``; the rule is defined in include/maskrcnn_hip.h).  ``rle`` in the forms rle_morph takes: a (counts,
+    run_offsets) pair — numpy arrays or CUDA tensors, labelled where they lie, tensors out — with ``sizes``, or rows.  ``of``: "ones"
+    labels the set pixels with ``connectivity`` (4 or 8), "zeros" the background with the dual connectivity, so that at connectivity 4
+    the zero components that do not touch the border are the holes rle_to_polygons traces.  Returns (comp_offsets, areas, bboxes,
+    flags): RLE k (b * slots + i for rows) owns the components comp_offsets[k]:comp_offsets[k + 1], numbered by their first pixel in
+    column-major order; per component its pixels, its tight box x, y, w, h and flags & 1 = it touches the image border."""
+    return _rle_components(False, rle, sizes, connectivity, of, device)
+
+
+def rle_components_host(rle, sizes=None, connectivity=4, of="ones"):
+    """The definition of rle_components: the sequential host code (``mrcnn_rle_components_host``), no GPU; numpy out."""
+    return _rle_components(True, rle, sizes, connectivity, of, None)
+
+
+def _rle_select(host_definition, rle, sizes, keep, connectivity, of, mode, device, cs=None):
+    cs = cs or _CompSet("rle_select_components_host" if host_definition else "rle_select_components", host_definition, rle, sizes, device)
+    pair, areas, bboxes, parent = _select_flat(cs, keep, connectivity, of, mode)
+    split = COMPONENTS_MODES.get(mode, mode) == _lib.COMPONENTS_SPLIT
+    if cs.pair:
+        return (pair, areas, bboxes, parent) if split else (pair, areas, bboxes)
+    host = lambda a: a if cs.space.on_host else a.cpu().numpy()
+    if split:                                                    # one row per kept component: no (B, slots) grid any more
+        c, o, par = host(pair[0]).view(np.uint32), host(pair[1]), host(parent)
+        rows = [{"size": [int(cs.hs[par[j]]), int(cs.ws[par[j]])], "counts": c[int(o[j]):int(o[j + 1])]} for j in range(len(par))]
+        return rows, host(areas).view(np.uint32), host(bboxes), par
+    rles = rle_rows_of(pair, cs.image_sizes if cs.slots else [])
+    return rles, host(areas).view(np.uint32).reshape(cs.B, cs.slots), host(bboxes).reshape(cs.B, cs.slots, 4)
+
+
+def rle_select_components(rle, sizes, keep, connectivity=4, of="ones", mode="merge", device=None):
+    """A set of run-length masks with some of its connected components dropped, or cut into its components, on the GPU
+    (``mrcnn_rle_components_select``).  ``keep``: one flag per component in rle_components' order (numpy or a CUDA tensor; it must
+    hold exactly as many entries as the set has components).  mode="merge": the same RLEs come back — the pixels of a dropped
+    component take the other value, so of="ones" clears specks and of="zeros" fills holes — as (rle, areas, bboxes) in the form
+    rle_morph returns.  mode="split" (of="ones" only): one RLE per kept component over its parent's plane, as ((counts, run_offsets),
+    areas, bboxes, parent) for a pair — parent[j] = the RLE it was cut from — or (rows, areas, bboxes, parent) with one row per
+    component for rows."""
+    return _rle_select(False, rle, sizes, keep, connectivity, of, mode, device)
+
+
+def rle_select_components_host(rle, sizes, keep, connectivity=4, of="ones", mode="merge"):
+    """The definition of rle_select_components: the sequential host code (``mrcnn_rle_components_select_host``), no GPU; numpy out."""
+    return _rle_select(True, rle, sizes, keep, connectivity, of, mode, None)
+
+
+def _largest_mask(comp_offs, areas, m):
+    """keep flags of the m largest components of every RLE, ties to the earlier component; numpy arrays or tensors, computed where they lie"""
+    if isinstance(areas, np.ndarray):
+        per = np.diff(comp_offs)
+        owner = np.repeat(np.arange(len(per)), per)
+        order = np.lexsort((np.arange(len(areas)), -areas.astype(np.int64), owner))
+        keep = np.zeros(len(areas), np.uint8)
+        keep[order] = (np.arange(len(areas)) - comp_offs[:-1][owner[order]]) < m
+        return keep
+    import torch
+    per = comp_offs[1:] - comp_offs[:-1]
+    owner = torch.repeat_interleave(torch.arange(per.shape[0], device=areas.device), per)
+    by_area = torch.sort(-areas.to(torch.int64), stable=True).indices          # ties keep their order
+    order = by_area[torch.sort(owner[by_area], stable=True).indices]
+    keep = torch.zeros(areas.shape[0], dtype=torch.uint8, device=areas.device)
+    keep[order] = ((torch.arange(areas.shape[0], device=areas.device) - comp_offs[:-1][owner[order]]) < m).to(torch.uint8)
+    return keep
+
+
+def _filter(host_definition, name, rle, sizes, connectivity, of, mode, device, choose):
+    """label, build the keep mask where the measures lie (choose(comp_offsets, areas, flags)), select"""
+    cs = _CompSet(name, host_definition, rle, sizes, device)
+    comp_offs, areas, _, flags = _components_flat(cs, connectivity, of)
+    if isinstance(areas, np.ndarray):
+        areas = areas.astype(np.int64)
+    return _rle_select(host_definition, rle, sizes, choose(comp_offs, areas, flags), connectivity, of, mode, device, cs=cs)
+
+
+def _remove_small(host_definition, rle, sizes, min_area, connectivity, device):
+    return _filter(host_definition, "rle_remove_small", rle, sizes, connectivity, "ones", "merge", device, lambda o, a, f: a >= int(min_area))[0]
+
+
+def _keep_largest(host_definition, rle, sizes, m, connectivity, device):
+    return _filter(host_definition, "rle_keep_largest", rle, sizes, connectivity, "ones", "merge", device, lambda o, a, f: _largest_mask(o, a, int(m)))[0]
+
+
+def _fill_holes(host_definition, rle, sizes, max_area, connectivity, device):
+    choose = (lambda o, a, f: (f & 1) != 0) if max_area is None else (lambda o, a, f: ((f & 1) != 0) | (a > int(max_area)))
+    return _filter(host_definition, "rle_fill_holes", rle, sizes, connectivity, "zeros", "merge", device, choose)[0]
+
+
+def _split_components(host_definition, rle, sizes, min_area, connectivity, device):
+    out = _filter(host_definition, "rle_split_components", rle, sizes, connectivity, "ones", "split", device, lambda o, a, f: a >= int(min_area))
+    return out[0], out[3]
+
+
+def rle_remove_small(rle, sizes, min_area, connectivity=4, device=None):
+    """The masks without their specks: the components of ones with fewer than ``min_area`` pixels are cleared, everything else keeps
+    its outline (rle_components, then rle_select_components; the keep mask is computed where the measures lie).  Returns the rle in
+    the form it came in."""
+    return _remove_small(False, rle, sizes, min_area, connectivity, device)
+
+
+def rle_keep_largest(rle, sizes, m=1, connectivity=4, device=None):
+    """The ``m`` largest components of every mask, the rest cleared; of equally large components the earlier one stays."""
+    return _keep_largest(False, rle, sizes, m, connectivity, device)
+
+
+def rle_fill_holes(rle, sizes=None, max_area=None, connectivity=4, device=None):
+    """The masks with their holes filled: the components of zeros (dual connectivity) that do not touch the image border are set —
+    all of them, or with ``max_area`` only those of at most that many pixels."""
+    return _fill_holes(False, rle, sizes, max_area, connectivity, device)
+
+
+def rle_split_components(rle, sizes, min_area=0, connectivity=4, device=None):
+    """Every mask cut into its components of at least ``min_area`` pixels: (split set, parent) — one RLE per component over its
+    parent's plane, a (counts, run_offsets) pair for a pair and one row per component for rows; parent[j] = the RLE it was cut from."""
+    return _split_components(False, rle, sizes, min_area, connectivity, device)
+
+
+def rle_remove_small_host(rle, sizes, min_area, connectivity=4):
+    return _remove_small(True, rle, sizes, min_area, connectivity, None)
+
+
+def rle_keep_largest_host(rle, sizes, m=1, connectivity=4):
+    return _keep_largest(True, rle, sizes, m, connectivity, None)
+
+
+def rle_fill_holes_host(rle, sizes=None, max_area=None, connectivity=4):
+    return _fill_holes(True, rle, sizes, max_area, connectivity, None)
+
+
+def rle_split_components_host(rle, sizes, min_area=0, connectivity=4):
+    """The definitions of rle_remove_small, rle_keep_largest, rle_fill_holes and rle_split_components: the _host entries, no GPU; numpy out."""
+    return _split_components(True, rle, sizes, min_area, connectivity, None)
