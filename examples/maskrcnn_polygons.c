@@ -7,18 +7,20 @@
  * FeatureCollection: one Feature per mask that has a ring, a Polygon for one outline and a MultiPolygon for several, every hole with the
  * outline it lies in.  The nesting is that of the traced rings; a tolerance only changes the vertices written.  With --fill-holes the
  * holes of every mask are filled and with --min-area A its specks of fewer than A pixels are cleared before anything is traced, holes
- * first (mrcnn_rle_components measures the connected components, mrcnn_rle_components_select merges the kept ones back).
+ * first (mrcnn_rle_components measures the connected components, mrcnn_rle_components_select merges the kept ones back).  With
+ * --disjoint every mask then loses the pixels of the masks before it in its image, so that no pixel belongs to two of them: one call of
+ * mrcnn_rle_combine, group k = RLE k and the RLEs of its image before it, MRCNN_RLE_DIFF.
  *
  *   cc -std=c99 -Iinclude examples/maskrcnn_polygons.c -Lmask-rcnn-coreml_amd -lmaskrcnn_hip \
  *      -Wl,-rpath,$PWD/mask-rcnn-coreml_amd -Wl,-rpath-link,/opt/rocm/lib -o maskrcnn_polygons
- *   ./maskrcnn_polygons [--host] [--tolerance T] [--geojson FILE] [--min-area A] [--fill-holes] <set.txt>
- *   (the flags in this order; --min-area and --fill-holes in either)
+ *   ./maskrcnn_polygons [--host] [--tolerance T] [--geojson FILE] [--min-area A] [--fill-holes] [--disjoint] <set.txt>
+ *   (the flags in this order; --min-area, --fill-holes and --disjoint in any)
  *
  * <set.txt> holds whitespace-separated integers: n_images and slots; then per image its height and width and, for each of its `slots`
  * RLEs, the number of runs followed by the runs (column-major, the first run counts zeros) — the layout mrcnn_masks_rle_source,
  * mrcnn_merge_tiles and mrcnn_unite_tiles write.  --host calls the sequential definitions, mrcnn_rle_to_polygons_host and
  * mrcnn_polygons_simplify_host (and mrcnn_polygons_nest_host, mrcnn_rle_components_host,
- * mrcnn_rle_components_select_host), which need no GPU.  Exit status 0 on success; on failure the mrcnn_last_error() text goes to stderr and the status code is the exit status.
+ * mrcnn_rle_components_select_host, mrcnn_rle_combine_host), which need no GPU.  Exit status 0 on success; on failure the mrcnn_last_error() text goes to stderr and the status code is the exit status.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -88,6 +90,47 @@ done:
     return st;
 }
 
+/* Every RLE minus the RLEs before it in its image: one call of mrcnn_rle_combine (after its size query) whatever the number of masks.
+ * Group k lists RLE k first and then its image's RLEs before it; MRCNN_RLE_DIFF keeps what is set in the first member alone.  *counts
+ * and run_offsets are replaced. */
+static int make_disjoint(int host, uint32_t** counts, int64_t* run_offsets, int n_images, int slots, const int32_t* hs, const int32_t* ws)
+{
+    const int64_t n = (int64_t)n_images * slots, n_members = (int64_t)n_images * ((int64_t)slots * (slots + 1) / 2);
+    int64_t* group_offsets = (int64_t*)malloc(sizeof(int64_t) * (size_t)(n + 1));
+    int64_t* members = (int64_t*)malloc(sizeof(int64_t) * (size_t)(n_members + 1));
+    int64_t* out_offsets = (int64_t*)malloc(sizeof(int64_t) * (size_t)(n + 1));
+    uint32_t* out = NULL;
+    int64_t at = 0, runs = 0;
+    int st = -1;                                                 /* -1: out of memory, no library text goes with it */
+    if (!group_offsets || !members || !out_offsets) goto done;
+    group_offsets[0] = 0;
+    for (int b = 0; b < n_images; ++b)
+        for (int i = 0; i < slots; ++i) {
+            const int64_t k = (int64_t)b * slots + i;
+            members[at++] = k;
+            for (int j = 0; j < i; ++j) members[at++] = (int64_t)b * slots + j;
+            group_offsets[k + 1] = at;
+        }
+    out_offsets[n] = 0;
+    st = host ? mrcnn_rle_combine_host(*counts, run_offsets, n, hs, ws, group_offsets, members, n, MRCNN_RLE_DIFF, NULL, 0, out_offsets, NULL, NULL)
+              : mrcnn_rle_combine(*counts, run_offsets, n, hs, ws, group_offsets, members, n, MRCNN_RLE_DIFF, MRCNN_HOST, NULL, 0, out_offsets, NULL, NULL);
+    if (st != MRCNN_OK && !(st == MRCNN_ERR_SHAPE && out_offsets[n] > 0)) goto done;
+    runs = out_offsets[n];
+    out = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)(runs + 1));
+    st = -1;
+    if (!out) goto done;
+    st = host ? mrcnn_rle_combine_host(*counts, run_offsets, n, hs, ws, group_offsets, members, n, MRCNN_RLE_DIFF, out, runs, out_offsets, NULL, NULL)
+              : mrcnn_rle_combine(*counts, run_offsets, n, hs, ws, group_offsets, members, n, MRCNN_RLE_DIFF, MRCNN_HOST, out, runs, out_offsets, NULL, NULL);
+    if (st != MRCNN_OK) goto done;
+    memcpy(run_offsets, out_offsets, sizeof(int64_t) * (size_t)(n + 1));
+    free(*counts);
+    *counts = out;
+    out = NULL;
+done:
+    free(out); free(out_offsets); free(members); free(group_offsets);
+    return st;
+}
+
 /* one ring as a closed GeoJSON ring: its first vertex repeated, an exterior with positive shoelace area and a hole with negative (a
  * traced ring has that already; a simplified one is reversed where it has not) */
 static void write_ring(FILE* g, const int32_t* xy, int64_t v0, int64_t v1, int exterior)
@@ -149,13 +192,14 @@ int main(int argc, char** argv)
     const int simplify = argc > 1 + host && strcmp(argv[1 + host], "--tolerance") == 0;
     const int geo = argc > 1 + host + 2 * simplify && strcmp(argv[1 + host + 2 * simplify], "--geojson") == 0;
     const int geo_at = 1 + host + 2 * simplify;
-    int small = 0, fill = 0, area_at = 0, file = geo_at + 2 * geo;
-    for (int turn = 0; turn < 2; ++turn) {                       /* the two component flags, in either order, once each */
+    int small = 0, fill = 0, disjoint = 0, area_at = 0, file = geo_at + 2 * geo;
+    for (int turn = 0; turn < 3; ++turn) {                       /* the two component flags and --disjoint, in any order, once each */
         if (!small && argc > file + 1 && strcmp(argv[file], "--min-area") == 0) { small = 1; area_at = file + 1; file += 2; }
         else if (!fill && argc > file && strcmp(argv[file], "--fill-holes") == 0) { fill = 1; file += 1; }
+        else if (!disjoint && argc > file && strcmp(argv[file], "--disjoint") == 0) { disjoint = 1; file += 1; }
     }
     if (argc != file + 1 || strncmp(argv[file], "--", 2) == 0) {         /* (a flag out of place, or one without its value) */
-        fprintf(stderr, "usage: %s [--host] [--tolerance T] [--geojson FILE] [--min-area A] [--fill-holes] <set.txt>\n", argv[0]);
+        fprintf(stderr, "usage: %s [--host] [--tolerance T] [--geojson FILE] [--min-area A] [--fill-holes] [--disjoint] <set.txt>\n", argv[0]);
         return 64;
     }
     const double tolerance = simplify ? atof(argv[2 + host]) : 0.0;
@@ -197,7 +241,7 @@ int main(int argc, char** argv)
     }
     fclose(f);
 
-    if (fill || small) {                                         /* per RLE sizes; holes first, then specks */
+    if (fill || small || disjoint) {                             /* per RLE sizes; holes first, then specks, then the overlaps */
         int32_t* hs = (int32_t*)malloc(sizeof(int32_t) * (n + 1));
         int32_t* ws = (int32_t*)malloc(sizeof(int32_t) * (n + 1));
         if (!hs || !ws) { fprintf(stderr, "out of memory\n"); return 70; }
@@ -207,6 +251,12 @@ int main(int argc, char** argv)
         if (st == -1) { fprintf(stderr, "out of memory\n"); return 70; }
         if (st != MRCNN_OK) {
             fprintf(stderr, "mrcnn_rle_components%s failed (%d): %s\n", host ? "_host" : "", st, mrcnn_last_error());
+            return st;
+        }
+        if (disjoint) st = make_disjoint(host, &counts, run_offsets, n_images, slots, hs, ws);
+        if (st == -1) { fprintf(stderr, "out of memory\n"); return 70; }
+        if (st != MRCNN_OK) {
+            fprintf(stderr, "mrcnn_rle_combine%s failed (%d): %s\n", host ? "_host" : "", st, mrcnn_last_error());
             return st;
         }
         free(ws); free(hs);

@@ -1160,6 +1160,53 @@ MRCNN_API int mrcnn_rle_components_select_host(const uint32_t* counts, const int
                                                uint32_t* out_counts, int64_t capacity, int64_t* out_run_offsets, uint32_t* areas,
                                                int32_t* bboxes_xywh, int64_t* out_parent, int64_t* out_n);
 
+/* ---- combining run-length masks: union, intersection, difference (csrc/api_rle_combine.hip, kernels_rle_combine.hip) ------------------
+ * The set algebra of RLEs, the counterpart of pycocotools' mask.merge: RLE in, RLE out, no dense plane.  The set is flat as
+ * mrcnn_rle_morph takes it: RLE k is counts[run_offsets[k] .. run_offsets[k+1]) and encodes a heights[k] x widths[k] plane (sides
+ * 1..32767); heights and widths are HOST arrays of n.  Zero-length runs are allowed anywhere.
+ * The groups are HOST arrays in both memory spaces, like heights: group g combines the RLEs members[group_offsets[g] ..
+ * group_offsets[g+1]) of the set, in that order, over the plane of its first member; every member must have that plane's height and
+ * width.  group_offsets holds n_groups + 1 entries from 0 and does not decrease; no group is empty.  An RLE may be a member of any
+ * number of groups, and of one group more than once.
+ * The rule (csrc/combine_rule.h), pixel by pixel:
+ *   MRCNN_RLE_OR    set in at least one member
+ *   MRCNN_RLE_AND   set in every member
+ *   MRCNN_RLE_XOR   set in an odd number of members (a member listed twice counts twice)
+ *   MRCNN_RLE_DIFF  set in the first member and in none of the others (the first member listed again empties the result)
+ * Outputs: one canonical RLE per group, exactly as mrcnn_rle_morph writes them (counts[0] may be 0, no other run is, runs continue
+ * across column ends, an empty plane is the single run [h*w]).  out_run_offsets has n_groups + 1 entries and is always written;
+ * areas (n_groups) and bboxes_xywh (n_groups, 4) are optional (NULL); the out_counts / capacity protocol with its size query is
+ * mrcnn_rle_morph's: out_counts is written only when all runs fit, a smaller capacity -> MRCNN_ERR_SHAPE, the message names the
+ * capacity needed (= out_run_offsets[n_groups]); capacity = 0 with out_counts = NULL is the size query.  memspace holds for counts,
+ * run_offsets and the four outputs; the outputs must not overlap the inputs.  n_groups = 0 and n = 0 are legal: out_run_offsets[0] = 0.
+ * mrcnn_rle_combine_host is the definition: sequential plain C++, no GPU, host pointers; one group at a time it decodes the first
+ * member into a plane, folds every further member into it pixel by pixel, and encodes.  mrcnn_rle_combine equals it bit for bit in
+ * every output array and never builds a plane: the prefix table of the runs and mrcnn_rle_morph's tight boxes (with the one flag that
+ * refuses a wrong total) are read back once; the host sizes a packed bit box per group — the first member's tight box for AND and
+ * DIFF, the hull of the members' boxes for OR and XOR; scratch that follows the masks, not the images — and uploads the member table;
+ * one thread per column of a group's box folds the runs of that column of every member (one binary search per member, then a walk)
+ * into its own column of words, kept in LDS, 1024 rows per pass: OR sets the intervals of ones, XOR toggles them, DIFF clears them, AND
+ * clears the gaps between them; the encoder of mrcnn_masks_rle_source runs on the bits.  A thread owns its column: nothing is atomic
+ * and the result does not depend on the order of execution.  The number of launches depends on neither n, n_groups nor the group sizes.
+ * Errors, answered before a device is looked for, nothing written: null pointer, unknown memspace -> MRCNN_ERR_INVALID; an unknown
+ * op, n or n_groups < 0, a side outside 1..32767, run_offsets that decrease, group_offsets[0] != 0 or decreasing group_offsets, an
+ * empty group, a member outside 0..n-1, a member whose height or width differs from its group's first member (the message names the
+ * group and the member) -> MRCNN_ERR_SHAPE.  An RLE of the set, referenced or not, that does not sum to its h*w -> MRCNN_ERR_SHAPE,
+ * the message starts "rle_combine:" / "rle_combine_host:" and names the lowest such k, nothing is written.  No gfx950 device ->
+ * MRCNN_ERR_HIP from the device entry (no CPU fallback).
+ * Not here: a vote (set in at least m of K members), combining across planes of different sizes, group tables that live on the
+ * device, the complement (it is XOR with a full mask, and a host can write the full mask [0, h*w]). */
+#define MRCNN_RLE_OR 0
+#define MRCNN_RLE_AND 1
+#define MRCNN_RLE_XOR 2
+#define MRCNN_RLE_DIFF 3
+MRCNN_API int mrcnn_rle_combine(const uint32_t* counts, const int64_t* run_offsets, int64_t n, const int32_t* heights, const int32_t* widths,
+                                const int64_t* group_offsets, const int64_t* members, int64_t n_groups, int op, int memspace,
+                                uint32_t* out_counts, int64_t capacity, int64_t* out_run_offsets, uint32_t* areas, int32_t* bboxes_xywh);
+MRCNN_API int mrcnn_rle_combine_host(const uint32_t* counts, const int64_t* run_offsets, int64_t n, const int32_t* heights,
+                                     const int32_t* widths, const int64_t* group_offsets, const int64_t* members, int64_t n_groups, int op,
+                                     uint32_t* out_counts, int64_t capacity, int64_t* out_run_offsets, uint32_t* areas, int32_t* bboxes_xywh);
+
 #ifdef __cplusplus
 }
 #endif

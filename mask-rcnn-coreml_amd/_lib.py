@@ -18,6 +18,7 @@ DEFAULT = -1          # MRCNN_DEFAULT of mrcnn_model_load: the mode the artefact
 HOST, DEVICE = 0, 1
 MORPH_ERODE, MORPH_DILATE, MORPH_BOUNDARY, MORPH_MAX_RADIUS = 0, 1, 2, 1024
 COMPONENTS_OF_ZEROS, COMPONENTS_OF_ONES, COMPONENTS_MERGE, COMPONENTS_SPLIT = 0, 1, 0, 1
+RLE_OR, RLE_AND, RLE_XOR, RLE_DIFF = 0, 1, 2, 3
 PARAM_INT, PARAM_DOUBLE, PARAM_STRING = 0, 1, 2
 MODEL_MASKRCNN, MODEL_CLASSIFIER, MODEL_MASK = 0, 1, 2
 
@@ -55,6 +56,7 @@ EXPORTED_SYMBOLS = [
     "mrcnn_polygons_nest", "mrcnn_polygons_nest_host",
     "mrcnn_rle_morph", "mrcnn_rle_morph_host", "mrcnn_boundary_radius",
     "mrcnn_rle_components", "mrcnn_rle_components_host", "mrcnn_rle_components_select", "mrcnn_rle_components_select_host",
+    "mrcnn_rle_combine", "mrcnn_rle_combine_host",
 ]
 # declared in include/maskrcnn_hip_test.h (test / measurement entry points of the same library)
 TEST_SYMBOLS = [
@@ -234,6 +236,9 @@ def lib():
     _csel = _morph + [vp, i64p]                                   # ... out_parent, out_n
     L.mrcnn_rle_components_select.argtypes = _cset + [vp, C.c_int64, C.c_int, C.c_int] + _csel
     L.mrcnn_rle_components_select_host.argtypes = _cset + [vp, C.c_int64, C.c_int] + _csel
+    _groups = [vp, vp, C.c_int64, C.c_int]                        # group_offsets, members, n_groups, op
+    L.mrcnn_rle_combine.argtypes = [vp, vp, C.c_int64, vp, vp] + _groups + [C.c_int] + _morph
+    L.mrcnn_rle_combine_host.argtypes = [vp, vp, C.c_int64, vp, vp] + _groups + _morph
     L.mrcnn_rle_to_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_from_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_iou.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int64]

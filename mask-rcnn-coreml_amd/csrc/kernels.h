@@ -558,6 +558,25 @@ void rle_morph_count_forward(hipStream_t s, const MorphJob& job, RleSeg* segs, u
 void rle_morph_write_forward(hipStream_t s, const MorphJob& job, const RleSeg* segs, const long long* run_offsets, uint32_t* counts);
 
 // ================================================================================================
+// The set algebra of run-length masks (kernels_rle_combine.hip; the rule is combine_rule.h).  All tables are device arrays.
+// ================================================================================================
+constexpr int COMBINE_PASS_WORDS = 32;                           // word rows a thread keeps in LDS: 1024 rows of a box per pass
+// one member of a group: its runs and the tight box of its set pixels (an empty mask: (0, 0, 0, 0))
+struct CombineMember { long long r0; int nruns; MorphBox tight; int pad; };
+struct CombineJob {
+    const MorphRec* rec; int n;       // one per group, laid out as mrcnn_rle_morph lays its bit boxes out: work, words, word0, col0, h and w (the rest 0)
+    const long long* member0;         // n + 1: group g owns members[member0[g] .. member0[g+1]), the first one first
+    const CombineMember* members;
+    int op;
+    long long cols;                   // the columns of all work boxes
+    const uint32_t* counts;
+    const uint32_t* pre_b;            // rle_prefix_forward's B, indexed like counts
+    uint32_t* bits;                   // the groups' bit boxes: every word of them is written
+};
+// the fold of every group's members into its bit box; rle_morph_count_forward / rle_morph_write_forward encode the boxes (MorphJob.vb = bits)
+void rle_combine_forward(hipStream_t s, const CombineJob& job);
+
+// ================================================================================================
 // Connected components of run-length masks (kernels_rle_components.hip; the rule is components_rule.h).  All tables are device arrays.
 // ================================================================================================
 // the set: heights, widths and rle_prefix_forward's totals per RLE, its B per run

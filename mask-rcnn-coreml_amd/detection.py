@@ -996,3 +996,225 @@ def rle_fill_holes_host(rle, sizes=None, max_area=None, connectivity=4):
 def rle_split_components_host(rle, sizes, min_area=0, connectivity=4):
     """The definitions of rle_remove_small, rle_keep_largest, rle_fill_holes and rle_split_components: the _host entries, no GPU; numpy out."""
     return _split_components(True, rle, sizes, min_area, connectivity, None)
+
+
+# ---- combining run-length masks (mrcnn_rle_combine) -----------------------------------------------------------------------------------------
+COMBINE_OPS = {"or": _lib.RLE_OR, "and": _lib.RLE_AND, "xor": _lib.RLE_XOR, "diff": _lib.RLE_DIFF}
+
+
+def _is_pair(rle):
+    return isinstance(rle, tuple) and len(rle) == 2 and not isinstance(rle[0], (list, tuple, dict))
+
+
+def _groups_of(name, groups):
+    """(group_offsets, members) as int64 host arrays: from a list of index lists, or from a tuple (offsets, members)"""
+    if isinstance(groups, tuple):
+        if len(groups) != 2:
+            raise ValueError(f"{name}: groups is a list of index lists or an (offsets, members) pair")
+        offs, mem = (np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "is_cuda") else a, dtype=np.int64).reshape(-1) for a in groups)
+    else:
+        rows = [np.asarray(g, dtype=np.int64).reshape(-1) for g in groups]
+        offs = np.concatenate(([0], np.cumsum([len(r) for r in rows]))).astype(np.int64)
+        mem = np.concatenate(rows).astype(np.int64) if rows else np.zeros(0, np.int64)
+    if offs.size == 0:
+        raise ValueError(f"{name}: group offsets hold one entry more than there are groups")
+    return offs, (mem if mem.size else np.zeros(1, np.int64))
+
+
+def _combine_flat(host_definition, space, counts, offs, hs, ws, goffs, mem, op):
+    """mrcnn_rle_combine(_host) on a flat set of ``space`` — counts, run_offsets (n + 1), host int32 arrays hs, ws of n — and host int64
+    group tables -> (counts, run_offsets (G + 1), areas (G), bboxes (G, 4)) in the same space.  A first attempt is sized from the
+    input's runs; if the result needs more, one more call with the capacity the library reported."""
+    n, G = int(offs.shape[0]) - 1, int(goffs.shape[0]) - 1
+    ptr = space.ptr
+    out_offs, areas, bboxes = space.new(G + 1, np.int64, zero=True), space.new(max(1, G), np.uint32), space.new((max(1, G), 4), np.int32)
+    entry = _lib.lib().mrcnn_rle_combine_host if host_definition else _lib.lib().mrcnn_rle_combine
+    head = (ptr(counts), ptr(offs), n, hs.ctypes.data, ws.ctypes.data, goffs.ctypes.data, mem.ctypes.data, G, int(op)) + (() if host_definition else (space.code,))
+    capacity = int(counts.shape[0]) + 2 * G + 2
+    for _ in range(2):
+        out = space.new(max(1, capacity), np.uint32)
+        st = entry(*head, ptr(out), capacity, ptr(out_offs), ptr(areas), ptr(bboxes))
+        if st != 4 or int(out_offs[G]) <= capacity:
+            break
+        capacity = int(out_offs[G])
+    _lib.check(st)
+    return out[:int(out_offs[G])], out_offs, areas[:G], bboxes[:G]
+
+
+def _combine_set(name, host_definition, rle, sizes, device):
+    """(pair?, space, counts, run_offsets, B, slots, hs and ws per RLE) of one combine call"""
+    pair = _is_pair(rle)
+    if device is None and not host_definition and pair and hasattr(rle[0], "is_cuda"):
+        device = rle[0].device                                   # a pair of CUDA tensors: combined where it lies, tensors out
+    counts, offs, B, slots, hs, ws = _rle_set(name, rle, sizes, device)
+    return pair, Space(device), counts, offs, B, slots, np.repeat(hs, slots).astype(np.int32), np.repeat(ws, slots).astype(np.int32)
+
+
+def _rle_combine(host_definition, rle, sizes, groups, op, device, name=None):
+    name = name or ("rle_combine_host" if host_definition else "rle_combine")
+    if op not in COMBINE_OPS and op not in COMBINE_OPS.values():
+        raise ValueError(f"{name}: op {op!r} is none of {sorted(COMBINE_OPS)}")
+    pair, space, counts, offs, _, _, hs, ws = _combine_set(name, host_definition, rle, sizes, device)
+    goffs, mem = _groups_of(name, groups)
+    out, out_offs, areas, bboxes = _combine_flat(host_definition, space, counts, offs, hs, ws, goffs, mem, COMBINE_OPS.get(op, op))
+    if pair:
+        return (out, out_offs), areas, bboxes
+    host = lambda a: a if space.on_host else a.cpu().numpy()
+    c, o = host(out).view(np.uint32), host(out_offs)
+    rows = [{"size": [int(hs[mem[goffs[g]]]), int(ws[mem[goffs[g]]])], "counts": c[int(o[g]):int(o[g + 1])]} for g in range(len(goffs) - 1)]
+    return rows, host(areas).view(np.uint32), host(bboxes)
+
+
+def rle_combine(rle, sizes, groups, op, device=None):
+    """Run-length masks combined on the GPU, RLE in and RLE out, no plane in between (``mrcnn_rle_combine``; the rule is defined in
+    include/maskrcnn_hip.h) — the counterpart of pycocotools' mask.merge.  ``rle`` in the forms rle_morph takes: a (counts,
+    run_offsets) pair — numpy arrays or CUDA tensors, combined where they lie — with ``sizes`` = [(h, w)] per RLE or per image of
+    equally many RLEs, or the rows rles[b][i] = {"size", "counts"} (RLE k = b * slots + i; sizes may be None).  ``groups``: a list of
+    index lists, or a tuple (offsets, members) of int64 arrays; group g combines the RLEs members[offsets[g]:offsets[g + 1]] in that
+    order over the plane of the first one — all of one size, none empty; an RLE may serve any number of groups, and one group more
+    than once.  ``op``: "or" (set in some member), "and" (in every member), "xor" (in an odd number; a member listed twice counts
+    twice) or "diff" (in the first and in none of the others).  Returns (rle, areas, bboxes), one canonical RLE per group: a pair in
+    the same memory space for a pair (a resident pair stays resident), else a list of rows {"size", "counts"}; with the set pixels
+    and their tight boxes x, y, w, h per group.  The result feeds rle_to_polygons, instance_map_rle, rle_decode_planes and coco_eval
+    as it is.  Not here: votes (at least m of K), planes of different sizes in one group, group tables on the device, the complement
+    (XOR with the full mask [0, h*w])."""
+    return _rle_combine(False, rle, sizes, groups, op, device)
+
+
+def rle_combine_host(rle, sizes, groups, op):
+    """The definition of rle_combine: the sequential host code (``mrcnn_rle_combine_host``), no GPU; numpy out."""
+    return _rle_combine(True, rle, sizes, groups, op, None)
+
+
+def _cat(a, b):
+    if isinstance(a, np.ndarray):
+        return np.concatenate((a, b))
+    import torch
+    return torch.cat((a, b))
+
+
+def _pairwise(host_definition, name, rle, sizes, other, op, device):
+    """A[k] op B[k] for two sets of equally many RLEs of equal sizes, in the form A came in: rows (B, slots) or a pair"""
+    if other is None:
+        raise ValueError(f"{name}: groups, or a second set ``other`` to combine pairwise, expected")
+    pair, space, ca, oa, B, slots, hs, ws = _combine_set(name, host_definition, rle, sizes, device)
+    _, _, cb, ob, B2, slots2, hs2, ws2 = _combine_set(name, host_definition, other, sizes, space.device)
+    if (B2, slots2) != (B, slots) or (hs2 != hs).any() or (ws2 != ws).any():
+        raise ValueError(f"{name}: the two sets differ in their number of RLEs or in their sizes")
+    n = B * slots
+    a0, a1, b0, b1 = int(oa[0]), int(oa[n]), int(ob[0]), int(ob[n])
+    counts = _cat(ca[a0:a1], cb[b0:b1])                          # the two sets behind each other: B's RLE k is RLE n + k
+    offs = _cat(oa - a0, ob[1:] - b0 + (a1 - a0))
+    if isinstance(counts, np.ndarray) and counts.size == 0:
+        counts = np.zeros(1, np.uint32)
+    goffs = 2 * np.arange(n + 1, dtype=np.int64)
+    mem = np.stack((np.arange(n, dtype=np.int64), n + np.arange(n, dtype=np.int64)), 1).reshape(-1)
+    out, out_offs, areas, bboxes = _combine_flat(host_definition, space, counts, offs, np.tile(hs, 2), np.tile(ws, 2), goffs,
+                                                 mem if n else np.zeros(1, np.int64), COMBINE_OPS[op])
+    if pair:
+        return (out, out_offs)
+    return rle_rows_of((out, out_offs), [(hs[b * slots], ws[b * slots]) for b in range(B)] if slots else [])
+
+
+def _algebra(host_definition, name, rle, sizes, groups, other, op, device):
+    if groups is None:
+        return _pairwise(host_definition, name, rle, sizes, other, op, device)
+    if other is not None:
+        raise ValueError(f"{name}: either groups over one set or a second set to combine pairwise, not both")
+    return _rle_combine(host_definition, rle, sizes, groups, op, device, name)[0]
+
+
+def rle_union(rle, sizes=None, groups=None, other=None, device=None):
+    """rle_combine(..., "or")[0]: per group the pixels set in at least one member.  With ``groups`` = None the sets ``rle`` and
+    ``other`` — equally many RLEs of equal sizes, in the same form — are combined pairwise, rle[k] with other[k], and the result
+    comes back in the form of ``rle`` (rows (B, slots) or a pair): masking with a region."""
+    return _algebra(False, "rle_union", rle, sizes, groups, other, "or", device)
+
+
+def rle_intersection(rle, sizes=None, groups=None, other=None, device=None):
+    """rle_combine(..., "and")[0]: the pixels set in every member; pairwise with ``other`` like rle_union."""
+    return _algebra(False, "rle_intersection", rle, sizes, groups, other, "and", device)
+
+
+def rle_xor(rle, sizes=None, groups=None, other=None, device=None):
+    """rle_combine(..., "xor")[0]: the pixels set in an odd number of members; pairwise with ``other`` like rle_union."""
+    return _algebra(False, "rle_xor", rle, sizes, groups, other, "xor", device)
+
+
+def rle_difference(rle, sizes=None, groups=None, other=None, device=None):
+    """rle_combine(..., "diff")[0]: the pixels of the first member that no other member has; pairwise (rle[k] minus other[k]) with
+    ``other`` like rle_union."""
+    return _algebra(False, "rle_difference", rle, sizes, groups, other, "diff", device)
+
+
+def rle_union_host(rle, sizes=None, groups=None, other=None):
+    return _algebra(True, "rle_union_host", rle, sizes, groups, other, "or", None)
+
+
+def rle_intersection_host(rle, sizes=None, groups=None, other=None):
+    return _algebra(True, "rle_intersection_host", rle, sizes, groups, other, "and", None)
+
+
+def rle_xor_host(rle, sizes=None, groups=None, other=None):
+    return _algebra(True, "rle_xor_host", rle, sizes, groups, other, "xor", None)
+
+
+def rle_difference_host(rle, sizes=None, groups=None, other=None):
+    """The definitions of rle_union, rle_intersection, rle_xor and rle_difference: ``mrcnn_rle_combine_host``, no GPU; numpy out."""
+    return _algebra(True, "rle_difference_host", rle, sizes, groups, other, "diff", None)
+
+
+def drawn_rows(det_src, sizes, min_score: float = 0.0) -> np.ndarray:
+    """Which rows mrcnn_instance_map_rle draws: (B, slots) bool for det_src (B, slots, 6), numpy or a CUDA tensor (read back), and
+    ``sizes`` = [(h_b, w_b)] — score > min_score, score > 0 and a non-empty pixel box, the box rounded as csrc/draw_rule.h rounds it:
+    half-to-even of y * (h - 1) in double, + 1 on the far edge, a NaN 0, held to +-2^20."""
+    det = np.asarray(det_src.cpu().numpy() if hasattr(det_src, "is_cuda") else det_src, dtype=np.float32)
+    hs, ws = sizes_of(sizes)
+    d = det.astype(np.float64)
+    h1, w1 = (hs.astype(np.float64) - 1.0)[:, None], (ws.astype(np.float64) - 1.0)[:, None]
+    with np.errstate(invalid="ignore"):
+        box = [d[..., 0] * h1, d[..., 1] * w1, d[..., 2] * h1 + 1.0, d[..., 3] * w1 + 1.0]
+    y1, x1, y2, x2 = (np.rint(np.clip(np.where(np.isnan(v), 0.0, v), -1048576.0, 1048576.0)) for v in box)
+    score = det[..., 5]
+    return (score > np.float32(min_score)) & (score > np.float32(0)) & (y2 > y1) & (x2 > x1)
+
+
+def _rle_disjoint(host_definition, det_src, rle, sizes, min_score, device):
+    name = "rle_disjoint_host" if host_definition else "rle_disjoint"
+    if device is None and not host_definition and not (_is_pair(rle) and hasattr(rle[0], "is_cuda")):
+        device = Space(det_src).device                           # the rows say where the call runs, as for instance_map_rle
+    pair, space, counts, offs, B, slots, hs, ws = _combine_set(name, host_definition, rle, sizes, device)
+    image_sizes = [(int(hs[b * slots]), int(ws[b * slots])) for b in range(B)] if slots else []
+    det = np.asarray(det_src.cpu().numpy() if hasattr(det_src, "is_cuda") else det_src, dtype=np.float32)
+    if det.ndim != 3 or det.shape[0] != B or det.shape[1] != slots or det.shape[2] != 6:
+        raise ValueError(f"{name}: det_src {tuple(det.shape)} does not go with {B} images of {slots} RLEs: ({B}, {slots}, 6) expected")
+    drawn = drawn_rows(det, image_sizes, min_score) if slots else np.zeros((B, 0), bool)
+    groups = []
+    for b in range(B):
+        above = []                                               # the drawn rows before row i
+        for i in range(slots):
+            k = b * slots + i
+            groups.append([k] + above if drawn[b, i] else [k, k])                   # an undrawn row minus itself: the empty mask
+            if drawn[b, i]:
+                above = above + [k]
+    goffs, mem = _groups_of(name, groups)
+    out, out_offs, areas, bboxes = _combine_flat(host_definition, space, counts, offs, hs, ws, goffs, mem, _lib.RLE_DIFF)
+    if pair:
+        return (out, out_offs), areas, bboxes
+    host = lambda a: a if space.on_host else a.cpu().numpy()
+    return rle_rows_of((out, out_offs), image_sizes), host(areas).view(np.uint32).reshape(B, slots), host(bboxes).reshape(B, slots, 4)
+
+
+def rle_disjoint(det_src, rle, sizes=None, min_score: float = 0.0, device=None):
+    """The masks of a detection set made disjoint on the GPU (one ``mrcnn_rle_combine`` call): per image, row i keeps the pixels no
+    drawn row j < i has — the pixels where instance_map_rle's map equals i — and an undrawn row becomes the empty mask.  "Drawn" is
+    instance_map_rle's rule (drawn_rows), evaluated from ``det_src`` (B, slots, 6) on the host (a small read-back for a CUDA tensor).
+    ``rle`` as instance_map_rle takes it: rows, or a (counts, run_offsets) pair with ``sizes``; a pair of CUDA tensors is used in
+    place.  Returns (rle, areas, bboxes) as rle_morph returns them, rows (B, slots) or a pair in the same memory space; the areas are
+    instance_map_rle's visible areas.  Footprints for a GIS layer, a GeoJSON file or a COCO result without overlaps."""
+    return _rle_disjoint(False, det_src, rle, sizes, min_score, device)
+
+
+def rle_disjoint_host(det_src, rle, sizes=None, min_score: float = 0.0):
+    """The definition of rle_disjoint: the sequential host code (``mrcnn_rle_combine_host``), no GPU; numpy out."""
+    return _rle_disjoint(True, det_src, rle, sizes, min_score, None)

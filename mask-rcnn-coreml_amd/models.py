@@ -144,7 +144,7 @@ class MaskRCNN(_Model):
 
     def predict_tiled(self, images, tile=None, overlap=(64, 64), metric="ios", match_threshold=0.5, max_out=None, threshold=0.5,
                       unite=False, link_threshold=0.5, polygons=False, tolerance=None, nest=False, close=0,
-                      min_component_area=0, fill_holes=False):
+                      min_component_area=0, fill_holes=False, disjoint=False):
         """Large images as overlapping windows at native resolution: detection.tile_plan per image (tile = None: the model's input
         size), predict_tiles, detection.merge_tiles.  Returns (det_src, source, n_kept, rles) in the frame of the images, in the
         form coco_results.coco_results and coco_eval.score_batch take.  By default an object is found whole only if some window
@@ -159,8 +159,10 @@ class MaskRCNN(_Model):
         wide are filled — and both the returned rles and the polygons are those of the closed masks.  fill_holes (True: every hole;
         an integer: holes of up to that many pixels, 0 like False) and min_component_area=a (specks of fewer than a pixels are cleared) filter the
         kept masks by their connected components after the closing, holes first, in the same place (detection.rle_fill_holes,
-        detection.rle_remove_small); the defaults change nothing."""
-        from .detection import _merge_tiles, rle_close, rle_fill_holes, rle_remove_small, rle_rows_of, rle_to_polygons, tile_plan
+        detection.rle_remove_small).  disjoint=True then takes from every kept mask the pixels of the kept masks before it in its image
+        (detection.rle_disjoint, in the same place): no pixel belongs to two masks, as detection.instance_map_rle decides it.  The
+        defaults change nothing."""
+        from .detection import _merge_tiles, rle_close, rle_disjoint, rle_fill_holes, rle_remove_small, rle_rows_of, rle_to_polygons, tile_plan
         images = list(images)
         H, W = self.image_height, self.image_width
         tile = (H, W) if tile is None else tile
@@ -177,7 +179,9 @@ class MaskRCNN(_Model):
             resident[0] = rle_fill_holes(resident[0], sizes, max_area=None if fill_holes is True else int(fill_holes))
         if min_component_area:
             resident[0] = rle_remove_small(resident[0], sizes, int(min_component_area))
-        if close or min_component_area or fill:
+        if disjoint:
+            resident[0] = rle_disjoint(out[0], resident[0], sizes)[0]
+        if close or min_component_area or fill or disjoint:
             out = (*out[:3], rle_rows_of(resident[0], sizes))
         if not polygons:
             return out
