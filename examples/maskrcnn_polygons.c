@@ -9,18 +9,20 @@
  * holes of every mask are filled and with --min-area A its specks of fewer than A pixels are cleared before anything is traced, holes
  * first (mrcnn_rle_components measures the connected components, mrcnn_rle_components_select merges the kept ones back).  With
  * --disjoint every mask then loses the pixels of the masks before it in its image, so that no pixel belongs to two of them: one call of
- * mrcnn_rle_combine, group k = RLE k and the RLEs of its image before it, MRCNN_RLE_DIFF.
+ * mrcnn_rle_combine, group k = RLE k and the RLEs of its image before it, MRCNN_RLE_DIFF.  With --props the final masks are measured
+ * (mrcnn_rle_measure, mrcnn_rle_convex_hull) and one line per mask that has a set pixel follows the rings: area, perimeter, centroid,
+ * orientation, solidity and the four corners of the minimum-area oriented box; --geojson then writes the same as properties.
  *
  *   cc -std=c99 -Iinclude examples/maskrcnn_polygons.c -Lmask-rcnn-coreml_amd -lmaskrcnn_hip \
  *      -Wl,-rpath,$PWD/mask-rcnn-coreml_amd -Wl,-rpath-link,/opt/rocm/lib -o maskrcnn_polygons
- *   ./maskrcnn_polygons [--host] [--tolerance T] [--geojson FILE] [--min-area A] [--fill-holes] [--disjoint] <set.txt>
- *   (the flags in this order; --min-area, --fill-holes and --disjoint in any)
+ *   ./maskrcnn_polygons [--host] [--tolerance T] [--geojson FILE] [--props] [--min-area A] [--fill-holes] [--disjoint] <set.txt>
+ *   (the flags in this order; --props, --min-area, --fill-holes and --disjoint in any)
  *
  * <set.txt> holds whitespace-separated integers: n_images and slots; then per image its height and width and, for each of its `slots`
  * RLEs, the number of runs followed by the runs (column-major, the first run counts zeros) — the layout mrcnn_masks_rle_source,
  * mrcnn_merge_tiles and mrcnn_unite_tiles write.  --host calls the sequential definitions, mrcnn_rle_to_polygons_host and
  * mrcnn_polygons_simplify_host (and mrcnn_polygons_nest_host, mrcnn_rle_components_host,
- * mrcnn_rle_components_select_host, mrcnn_rle_combine_host), which need no GPU.  Exit status 0 on success; on failure the mrcnn_last_error() text goes to stderr and the status code is the exit status.
+ * mrcnn_rle_components_select_host, mrcnn_rle_combine_host, mrcnn_rle_measure_host, mrcnn_rle_convex_hull_host), which need no GPU.  Exit status 0 on success; on failure the mrcnn_last_error() text goes to stderr and the status code is the exit status.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -131,6 +133,76 @@ done:
     return st;
 }
 
+/* What --props shows of one mask, in doubles made from the library's integers. */
+typedef struct { int any; long long area, perimeter; double cx, cy, orientation, solidity, obb[8]; } mask_props;
+
+/* atan2 in plain C (the example links against the library alone, not libm): the argument is brought to 0..1, then to within 1/8 of
+ * one of five tabulated tangents, and the odd series of what is left converges in ten terms. */
+static double angle_of(double y, double x)
+{
+    static const double tangent[5] = {0.0, 0.25, 0.5, 0.75, 1.0};
+    static const double angle[5] = {0.0, 0.24497866312686414, 0.4636476090008061, 0.6435011087932844, 0.7853981633974483};
+    const double pi = 3.141592653589793, ax = x < 0 ? -x : x, ay = y < 0 ? -y : y;
+    if (ax == 0 && ay == 0) return 0.0;
+    const int swap = ay > ax;
+    const double t = swap ? ax / ay : ay / ax;
+    const int c = (int)(t * 4.0 + 0.5);
+    const double u = (t - tangent[c]) / (1.0 + t * tangent[c]), u2 = u * u;
+    double sum = 0.0, term = u;
+    for (int k = 0; k < 12; ++k) { sum += term / (2 * k + 1); term = -term * u2; }
+    double a = angle[c] + sum;
+    if (swap) a = pi / 2 - a;
+    if (x < 0) a = pi - a;
+    return y < 0 ? -a : a;
+}
+
+/* Measures, hulls and oriented boxes of the set (the hulls after a size query), then the doubles.  The central moments do not fit 64
+ * bits as S1*Sxx - Sx^2: they are taken about the integer part of the mean, which is exact in int64, and corrected by the remainder. */
+static int measure_props(int host, const uint32_t* counts, const int64_t* run_offsets, int64_t n, const int32_t* hs, const int32_t* ws, mask_props* out)
+{
+    int64_t* m = (int64_t*)malloc(sizeof(int64_t) * MRCNN_MEASURE_WORDS * (size_t)(n + 1));
+    int64_t* hull_offsets = (int64_t*)malloc(sizeof(int64_t) * (size_t)(n + 1));
+    int64_t* areas2 = (int64_t*)malloc(sizeof(int64_t) * (size_t)(n + 1));
+    int64_t* obb = (int64_t*)malloc(sizeof(int64_t) * 8 * (size_t)(n + 1));
+    int32_t* xy = NULL;
+    int64_t vertices = 0;
+    int st = -1;                                                 /* -1: out of memory, no library text goes with it */
+    if (!m || !hull_offsets || !areas2 || !obb) goto done;
+    st = host ? mrcnn_rle_measure_host(counts, run_offsets, n, hs, ws, m) : mrcnn_rle_measure(counts, run_offsets, n, hs, ws, MRCNN_HOST, m);
+    if (st != MRCNN_OK) goto done;
+    st = host ? mrcnn_rle_convex_hull_host(counts, run_offsets, n, hs, ws, hull_offsets, NULL, NULL, NULL, &vertices, 0)
+              : mrcnn_rle_convex_hull(counts, run_offsets, n, hs, ws, MRCNN_HOST, hull_offsets, NULL, NULL, NULL, &vertices, 0);
+    if (st != MRCNN_OK && !(st == MRCNN_ERR_SHAPE && vertices > 0)) goto done;
+    xy = (int32_t*)malloc(sizeof(int32_t) * 2 * (size_t)(vertices + 1));
+    st = -1;
+    if (!xy) goto done;
+    st = host ? mrcnn_rle_convex_hull_host(counts, run_offsets, n, hs, ws, hull_offsets, areas2, obb, xy, &vertices, vertices)
+              : mrcnn_rle_convex_hull(counts, run_offsets, n, hs, ws, MRCNN_HOST, hull_offsets, areas2, obb, xy, &vertices, vertices);
+    if (st != MRCNN_OK) goto done;
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t *w = m + MRCNN_MEASURE_WORDS * k, *o = obb + 8 * k;
+        const int64_t s1 = w[0];
+        mask_props* p = out + k;
+        p->any = s1 > 0; p->area = (long long)s1; p->perimeter = (long long)w[6];
+        if (!p->any) continue;
+        const int64_t qx = w[1] / s1, rx = w[1] % s1, qy = w[2] / s1, ry = w[2] % s1;
+        const double about_xx = (double)(w[3] - 2 * qx * w[1] + qx * qx * s1), about_yy = (double)(w[5] - 2 * qy * w[2] + qy * qy * s1);
+        const double about_xy = (double)(w[4] - qx * w[2] - qy * w[1] + qx * qy * s1);
+        const double c20 = (about_xx - (double)rx * (double)rx / (double)s1) / (double)s1 + 1.0 / 12.0;
+        const double c02 = (about_yy - (double)ry * (double)ry / (double)s1) / (double)s1 + 1.0 / 12.0;
+        const double c11 = (about_xy - (double)rx * (double)ry / (double)s1) / (double)s1;
+        p->cx = (double)qx + (double)rx / (double)s1 + 0.5; p->cy = (double)qy + (double)ry / (double)s1 + 0.5;
+        p->orientation = 0.5 * angle_of(2.0 * c11, c20 - c02);
+        p->solidity = 2.0 * (double)s1 / (double)areas2[k];
+        const double dx = (double)o[1], dy = (double)o[2], L2 = dx * dx + dy * dy;
+        const double d[4] = {(double)o[3], (double)o[4], (double)o[4], (double)o[3]}, c[4] = {(double)o[5], (double)o[5], (double)o[6], (double)o[6]};
+        for (int j = 0; j < 4; ++j) { p->obb[2 * j] = (d[j] * dx - c[j] * dy) / L2; p->obb[2 * j + 1] = (d[j] * dy + c[j] * dx) / L2; }
+    }
+done:
+    free(xy); free(obb); free(areas2); free(hull_offsets); free(m);
+    return st;
+}
+
 /* one ring as a closed GeoJSON ring: its first vertex repeated, an exterior with positive shoelace area and a hole with negative (a
  * traced ring has that already; a simplified one is reversed where it has not) */
 static void write_ring(FILE* g, const int32_t* xy, int64_t v0, int64_t v1, int exterior)
@@ -152,7 +224,7 @@ static void write_ring(FILE* g, const int32_t* xy, int64_t v0, int64_t v1, int e
 /* The FeatureCollection of the set: polygon p owns ring_order[poly_rings[p] .. poly_rings[p+1]), its shell first; the polygons of RLE k
  * are [rle_polys[k], rle_polys[k+1]).  A shell with fewer than 3 vertices left is dropped with its holes, such a hole alone. */
 static void write_geojson(FILE* g, size_t n, int slots, const int64_t* rle_rings, const int64_t* ring_offsets, const int64_t* ring_areas, const int32_t* xy,
-                          const int64_t* rle_polys, const int64_t* poly_rings, const int64_t* ring_order)
+                          const int64_t* rle_polys, const int64_t* poly_rings, const int64_t* ring_order, const mask_props* props)
 {
     int features = 0;
     fprintf(g, "{\"type\":\"FeatureCollection\",\"features\":[");
@@ -180,8 +252,14 @@ static void write_geojson(FILE* g, size_t n, int slots, const int64_t* rle_rings
             }
             fprintf(g, "]");
         }
-        fprintf(g, "%s},\"properties\":{\"image\":%d,\"row\":%d,\"area\":%lld}}", shells > 1 ? "]" : "", (int)(k / (size_t)slots), (int)(k % (size_t)slots),
+        fprintf(g, "%s},\"properties\":{\"image\":%d,\"row\":%d,\"area\":%lld", shells > 1 ? "]" : "", (int)(k / (size_t)slots), (int)(k % (size_t)slots),
                 (long long)area);
+        if (props && props[k].any) {
+            const mask_props* p = props + k;
+            fprintf(g, ",\"centroid\":[%.17g,%.17g],\"orientation\":%.17g,\"perimeter\":%lld,\"solidity\":%.17g,\"obb\":[[%.17g,%.17g],[%.17g,%.17g],[%.17g,%.17g],[%.17g,%.17g]]",
+                    p->cx, p->cy, p->orientation, p->perimeter, p->solidity, p->obb[0], p->obb[1], p->obb[2], p->obb[3], p->obb[4], p->obb[5], p->obb[6], p->obb[7]);
+        }
+        fprintf(g, "}}");
     }
     fprintf(g, "\n]}\n");
 }
@@ -192,14 +270,15 @@ int main(int argc, char** argv)
     const int simplify = argc > 1 + host && strcmp(argv[1 + host], "--tolerance") == 0;
     const int geo = argc > 1 + host + 2 * simplify && strcmp(argv[1 + host + 2 * simplify], "--geojson") == 0;
     const int geo_at = 1 + host + 2 * simplify;
-    int small = 0, fill = 0, disjoint = 0, area_at = 0, file = geo_at + 2 * geo;
-    for (int turn = 0; turn < 3; ++turn) {                       /* the two component flags and --disjoint, in any order, once each */
+    int small = 0, fill = 0, disjoint = 0, props = 0, area_at = 0, file = geo_at + 2 * geo;
+    for (int turn = 0; turn < 4; ++turn) {                       /* the two component flags, --disjoint and --props, in any order, once each */
         if (!small && argc > file + 1 && strcmp(argv[file], "--min-area") == 0) { small = 1; area_at = file + 1; file += 2; }
         else if (!fill && argc > file && strcmp(argv[file], "--fill-holes") == 0) { fill = 1; file += 1; }
         else if (!disjoint && argc > file && strcmp(argv[file], "--disjoint") == 0) { disjoint = 1; file += 1; }
+        else if (!props && argc > file && strcmp(argv[file], "--props") == 0) { props = 1; file += 1; }
     }
     if (argc != file + 1 || strncmp(argv[file], "--", 2) == 0) {         /* (a flag out of place, or one without its value) */
-        fprintf(stderr, "usage: %s [--host] [--tolerance T] [--geojson FILE] [--min-area A] [--fill-holes] [--disjoint] <set.txt>\n", argv[0]);
+        fprintf(stderr, "usage: %s [--host] [--tolerance T] [--geojson FILE] [--props] [--min-area A] [--fill-holes] [--disjoint] <set.txt>\n", argv[0]);
         return 64;
     }
     const double tolerance = simplify ? atof(argv[2 + host]) : 0.0;
@@ -241,7 +320,8 @@ int main(int argc, char** argv)
     }
     fclose(f);
 
-    if (fill || small || disjoint) {                             /* per RLE sizes; holes first, then specks, then the overlaps */
+    mask_props* shape = NULL;
+    if (fill || small || disjoint || props) {                    /* per RLE sizes; holes first, then specks, then the overlaps, then the measures */
         int32_t* hs = (int32_t*)malloc(sizeof(int32_t) * (n + 1));
         int32_t* ws = (int32_t*)malloc(sizeof(int32_t) * (n + 1));
         if (!hs || !ws) { fprintf(stderr, "out of memory\n"); return 70; }
@@ -258,6 +338,15 @@ int main(int argc, char** argv)
         if (st != MRCNN_OK) {
             fprintf(stderr, "mrcnn_rle_combine%s failed (%d): %s\n", host ? "_host" : "", st, mrcnn_last_error());
             return st;
+        }
+        if (props) {
+            shape = (mask_props*)malloc(sizeof(mask_props) * (n + 1));
+            st = shape ? measure_props(host, counts, run_offsets, (int64_t)n, hs, ws, shape) : -1;
+            if (st == -1) { fprintf(stderr, "out of memory\n"); return 70; }
+            if (st != MRCNN_OK) {
+                fprintf(stderr, "measuring the masks failed (%d): %s\n", st, mrcnn_last_error());
+                return st;
+            }
         }
         free(ws); free(hs);
     }
@@ -322,13 +411,20 @@ int main(int argc, char** argv)
             for (int64_t v = ring_offsets[r]; v < ring_offsets[r + 1]; ++v) printf(" %d,%d", (int)xy[2 * v], (int)xy[2 * v + 1]);
             printf("\n");
         }
+    for (size_t k = 0; shape && k < n; ++k) {
+        const mask_props* p = shape + k;
+        if (!p->any) continue;
+        printf("RLE %lld props: area %lld perimeter %lld centroid %.17g %.17g orientation %.17g solidity %.17g obb %.17g,%.17g %.17g,%.17g %.17g,%.17g %.17g,%.17g\n",
+               (long long)k, p->area, p->perimeter, p->cx, p->cy, p->orientation, p->solidity, p->obb[0], p->obb[1], p->obb[2], p->obb[3], p->obb[4], p->obb[5],
+               p->obb[6], p->obb[7]);
+    }
     if (geo) {
         FILE* g = fopen(geo_file, "w");
         if (!g) { fprintf(stderr, "cannot write %s\n", geo_file); return 73; }
-        write_geojson(g, n, slots, rle_rings, ring_offsets, ring_areas, xy, rle_polys, poly_rings, ring_order);
+        write_geojson(g, n, slots, rle_rings, ring_offsets, ring_areas, xy, rle_polys, poly_rings, ring_order, shape);
         if (fclose(g) != 0) { fprintf(stderr, "cannot write %s\n", geo_file); return 74; }
         free(ring_order); free(poly_rings); free(rle_polys);
     }
-    free(xy); free(ring_areas); free(ring_offsets); free(counts); free(rle_rings); free(run_offsets); free(widths); free(heights);
+    free(shape); free(xy); free(ring_areas); free(ring_offsets); free(counts); free(rle_rings); free(run_offsets); free(widths); free(heights);
     return 0;
 }

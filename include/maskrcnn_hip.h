@@ -1207,6 +1207,70 @@ MRCNN_API int mrcnn_rle_combine_host(const uint32_t* counts, const int64_t* run_
                                      const int32_t* widths, const int64_t* group_offsets, const int64_t* members, int64_t n_groups, int op,
                                      uint32_t* out_counts, int64_t capacity, int64_t* out_run_offsets, uint32_t* areas, int32_t* bboxes_xywh);
 
+/* ---- measuring run-length masks: moments, perimeter, convex hull, oriented box (csrc/api_rle_shape.hip, kernels_rle_shape.hip) --------
+ * The shape of every mask of a flat RLE set, from the runs, no dense plane.  The set is flat as mrcnn_rle_morph takes it: RLE k is
+ * counts[run_offsets[k] .. run_offsets[k+1]) and encodes a heights[k] x widths[k] plane (sides 1..32767); heights and widths are HOST
+ * arrays of n.  Zero-length runs are allowed anywhere; n = 0 is legal.  memspace holds for counts, run_offsets and the output arrays;
+ * n_vertices is a host word in both memory spaces.  Geometry is mrcnn_rle_to_polygons': pixel (x, y) is the square [x, x+1] x [y, y+1],
+ * y points down, a vertex is a pixel corner.  Everything is integer arithmetic: no floating point in any of the four entries.
+ * mrcnn_rle_measure writes measures, n x MRCNN_MEASURE_WORDS int64 per RLE, over the set pixels with pixel INDICES (x, y):
+ *   [S1, Sx, Sy, Sxx, Sxy, Syy, perimeter]     S1 the area, Sx = sum x, Sy = sum y, Sxx = sum x^2, Sxy = sum x*y, Syy = sum y^2
+ * perimeter is the number of unit edges between a set pixel and an unset pixel or the outside of the plane: exactly the total edge
+ * length of the rings mrcnn_rle_to_polygons traces for that RLE.  An empty mask is seven zeros.  Ranges: S1 <= 32767^2 < 2^30; Sx,
+ * Sy < 32767^3 / 2 < 2^44; Sxx, Sxy, Syy < 32767^4 / 3 < 2^59 < 2^60; perimeter <= 4 * S1: every word fits int64.  Central moments
+ * (S1 * Sxx - Sx^2) do NOT fit 64 bits: a caller takes them in wider integers or in doubles from exactly reduced terms.
+ * mrcnn_rle_convex_hull.  The hull of RLE k is the convex hull of its set pixels' SQUARES, a ring in the tracer's convention: integer
+ * corner vertices, strictly convex (no vertex lies on a segment between two others), clockwise on screen with positive shoelace area,
+ * starting at its smallest vertex by x then y: the top chain from (xmin, T) to (xmax+1, T') in rising x, then the bottom chain back in
+ * falling x.  A non-empty mask has at least 4 hull vertices, an empty one none.  The hull is unique.
+ *   hull_offsets (n + 1, int64)   always written: RLE k owns the vertices hull_offsets[k] .. hull_offsets[k+1]
+ *   *n_vertices (host)            always written: hull_offsets[n]
+ *   hull_areas2 (n int64, or NULL)  twice the hull's area; written whatever the capacity
+ *   obb (n x 8 int64, or NULL)      the oriented box, below; written whatever the capacity
+ *   xy (2 x vertex_capacity int32)  x, y per vertex, under mrcnn_polygons_simplify's capacity protocol: written only when all vertices
+ *                                   fit, otherwise MRCNN_ERR_SHAPE and the message names the size needed; vertex_capacity = 0 with
+ *                                   xy = NULL is the size query.
+ * The oriented box is the minimum-area rectangle around the hull, one side on a hull edge, exact in integers.  For hull edge e from
+ * v_e to v_{e+1} (cyclic) with (dx, dy) its vector and L2 = dx^2 + dy^2, over all hull vertices (X, Y): d = dx*X + dy*Y and
+ * c = dx*Y - dy*X, D = dmax - dmin, C = cmax - cmin; the rectangle's area is D*C / L2.  The chosen edge minimises it — two edges are
+ * compared as D_i*C_i*L2_j < D_j*C_j*L2_i in 128 bits (94 are needed) — and a tie goes to the smallest e.  The row is
+ * [e, dx, dy, dmin, dmax, cmin, cmax, 0] with e local to the RLE's hull, [-1, 0, ...] for an empty mask.  The point with coordinates
+ * (d, c) is ((d*dx - c*dy) / L2, (d*dy + c*dx) / L2): a caller makes corners, centre, size and angle from that in doubles.
+ * The _host entries are the definition: sequential plain C++, no GPU, host pointers; one RLE at a time the runs are cut into column
+ * pieces (touching pieces joined), the moments are summed pixel by pixel, the perimeter is counted from the pieces of neighbouring
+ * columns, the hull is Andrew's monotone chain over the columns' first and last set rows and the box the loop over edges x vertices.
+ * The device entries equal them bit for bit in every output array and never build a plane.  Moments: one block per RLE strides over
+ * the runs of ones of rle_prefix_forward's table; a run is a head piece, a block of full columns and a tail piece, each a closed form
+ * in its ends, so a full plane costs what one pixel costs.  Perimeter: one thread per vertex column X = 0 .. w, one binary search
+ * per pixel column and the merge of columns X - 1 and X: the rows where they differ (outside the plane is empty) plus 2 per piece of
+ * column X, added to the RLE's word by 64-bit integer atomics.  Hull: one thread per pixel column finds the first and last set row;
+ * vertex column X takes the smaller first and the larger last row of its non-empty neighbours (empty columns inside a mask are
+ * skipped); one workgroup per RLE runs QuickHull level by level on both chains at once — a 64-bit maximum per chain segment of
+ * c(p) = (by-ay)(px-ax) - (bx-ax)(py-ay) picks a candidate, a tie goes to the smallest position in walking order, it is kept only if
+ * c > 0, the loop ends when no segment is left — in LDS up to MRCNN_HULL_LDS_COLUMNS vertex columns (32 bytes per column: 128 KiB),
+ * in global scratch above; the counts are scanned, the rings written with their areas, and one workgroup per RLE with one thread per
+ * hull edge finds the box by a block-wide 128-bit minimum.  The host reads back one flag before anything is written (an RLE that does
+ * not sum to its plane) and *n_vertices after the count; the number of launches depends on neither n nor the hulls' sizes.
+ * Errors, answered before a device is looked for, nothing written: null pointer, unknown memspace, negative vertex_capacity, null xy
+ * with a capacity -> MRCNN_ERR_INVALID; n < 0, a side outside 1..32767, run_offsets that decrease -> MRCNN_ERR_SHAPE.  An RLE that does
+ * not sum to its h*w -> MRCNN_ERR_SHAPE, the message starts "rle_measure:" / "rle_measure_host:" / "rle_convex_hull:" /
+ * "rle_convex_hull_host:" and names the lowest such k, nothing is written.  No gfx950 device -> MRCNN_ERR_HIP from the device entries
+ * (no CPU fallback).
+ * Not here: Feret diameters, Hu moments, hulls of rings, boxes under other criteria (smallest perimeter, axis of inertia), measures
+ * per connected component in one call (mrcnn_rle_components_select's SPLIT output feeds these entries as it is). */
+#define MRCNN_MEASURE_WORDS 7
+#define MRCNN_HULL_LDS_COLUMNS 4096
+MRCNN_API int mrcnn_rle_measure(const uint32_t* counts, const int64_t* run_offsets, int64_t n, const int32_t* heights, const int32_t* widths,
+                                int memspace, int64_t* measures);
+MRCNN_API int mrcnn_rle_measure_host(const uint32_t* counts, const int64_t* run_offsets, int64_t n, const int32_t* heights,
+                                     const int32_t* widths, int64_t* measures);
+MRCNN_API int mrcnn_rle_convex_hull(const uint32_t* counts, const int64_t* run_offsets, int64_t n, const int32_t* heights, const int32_t* widths,
+                                    int memspace, int64_t* hull_offsets, int64_t* hull_areas2, int64_t* obb, int32_t* xy, int64_t* n_vertices,
+                                    int64_t vertex_capacity);
+MRCNN_API int mrcnn_rle_convex_hull_host(const uint32_t* counts, const int64_t* run_offsets, int64_t n, const int32_t* heights,
+                                         const int32_t* widths, int64_t* hull_offsets, int64_t* hull_areas2, int64_t* obb, int32_t* xy,
+                                         int64_t* n_vertices, int64_t vertex_capacity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = [
     "mrcnn_rle_morph", "mrcnn_rle_morph_host", "mrcnn_boundary_radius",
     "mrcnn_rle_components", "mrcnn_rle_components_host", "mrcnn_rle_components_select", "mrcnn_rle_components_select_host",
     "mrcnn_rle_combine", "mrcnn_rle_combine_host",
+    "mrcnn_rle_measure", "mrcnn_rle_measure_host", "mrcnn_rle_convex_hull", "mrcnn_rle_convex_hull_host",
 ]
 # declared in include/maskrcnn_hip_test.h (test / measurement entry points of the same library)
 TEST_SYMBOLS = [
@@ -122,6 +123,8 @@ MATCH_IOU, MATCH_IOS = 0, 1
 TILES_MAX_CANDIDATES = 8192
 POLYGON_LDS_CORNERS = 1024      # MRCNN_POLYGON_LDS_CORNERS
 SIMPLIFY_LDS_VERTICES = 1024    # MRCNN_SIMPLIFY_LDS_VERTICES
+MEASURE_WORDS = 7               # MRCNN_MEASURE_WORDS
+HULL_LDS_COLUMNS = 4096         # MRCNN_HULL_LDS_COLUMNS
 
 
 class PngSource(C.Structure):       # mrcnn_png_source
@@ -239,6 +242,11 @@ def lib():
     _groups = [vp, vp, C.c_int64, C.c_int]                        # group_offsets, members, n_groups, op
     L.mrcnn_rle_combine.argtypes = [vp, vp, C.c_int64, vp, vp] + _groups + [C.c_int] + _morph
     L.mrcnn_rle_combine_host.argtypes = [vp, vp, C.c_int64, vp, vp] + _groups + _morph
+    _hull = [vp, vp, vp, vp, i64p, C.c_int64]                     # hull_offsets, hull_areas2, obb, xy, n_vertices, vertex_capacity
+    L.mrcnn_rle_measure.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int, vp]
+    L.mrcnn_rle_measure_host.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
+    L.mrcnn_rle_convex_hull.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int] + _hull
+    L.mrcnn_rle_convex_hull_host.argtypes = [vp, vp, C.c_int64, vp, vp] + _hull
     L.mrcnn_rle_to_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_from_string.argtypes = [vp, C.c_int64, vp, C.c_int64, i64p]
     L.mrcnn_rle_iou.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int64]

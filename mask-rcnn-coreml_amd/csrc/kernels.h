@@ -736,6 +736,40 @@ void nest_measure_forward(hipStream_t s, const NestRings& in, const NestWork& w,
 void nest_forward(hipStream_t s, const NestRings& in, const NestWork& w, long long* parent, int32_t* depth, long long* rle_polys, long long* poly_rings,
                   long long* ring_order);
 
+// ================================================================================================
+// Measuring run-length masks (mrcnn_rle_measure, mrcnn_rle_convex_hull; kernels_rle_shape.hip, the rules are shape_rule.h).  All tables
+// are device arrays.
+// ================================================================================================
+// A ring's candidates, segments and slots live in LDS up to this many vertex columns (w + 1 <= HULL_LDS_COLUMNS), in global scratch above.
+// Per vertex column two candidate positions (top and bottom chain), each an 8-byte slot, a 4-byte row and a 4-byte segment: 32 bytes, so
+// 4096 columns take 128 KiB of the 160 KiB a workgroup can have.
+constexpr int HULL_LDS_COLUMNS = MRCNN_HULL_LDS_COLUMNS;
+constexpr int HULL_LDS_BYTES_PER_COLUMN = 32;
+static_assert((long long)HULL_LDS_COLUMNS * HULL_LDS_BYTES_PER_COLUMN <= 159 * 1024, "MRCNN_HULL_LDS_COLUMNS: a ring's work must fit a workgroup's LDS");
+// the set: heights, widths and rle_prefix_forward's totals per RLE, its B per run; vcol0 (n + 1) = the vertex columns (w + 1 per RLE)
+// before RLE k, vcols their number
+struct ShapeSet {
+    const uint32_t* counts; const uint32_t* pre_b; const long long* run_offsets;
+    const int32_t* heights; const int32_t* widths; const unsigned long long* totals; const long long* vcol0;
+    int n; long long vcols;
+};
+// *bad (device, one word) = the lowest k whose total is not its plane's h*w, ~0 if all are right: the caller reads it back first
+void rle_shape_check_forward(hipStream_t s, const ShapeSet& S, unsigned long long* bad);
+// measures (n x 7): one fill and two launches
+void rle_shape_measure_forward(hipStream_t s, const ShapeSet& S, long long* measures);
+struct HullWork {
+    int2* ext;                        // vcols: (t, b) of a pixel column, (-1, -1) for an empty one and for the entry of vertex column w
+    uint8_t* keep;                    // 2 * vcols: per candidate position, it is a hull vertex
+    uint32_t* count;                  // n: the vertices of a hull
+    // RLEs wider than HULL_LDS_COLUMNS - 1 only, per candidate position (nullptr when there is none): the segment a candidate is in, the slots
+    uint32_t* chain; unsigned long long* slot;
+};
+// ext, keep and count by the rule, then hull_offsets (n + 1) = the exclusive prefix of count; max_w = the widest RLE.  Three launches.
+void rle_hull_count_forward(hipStream_t s, const ShapeSet& S, const HullWork& W, int max_w, long long* hull_offsets);
+// the rings at their places: xy (n_out = hull_offsets[n] vertices), areas2 and obb (either may be nullptr).  Two launches.
+void rle_hull_write_forward(hipStream_t s, const ShapeSet& S, const HullWork& W, const long long* hull_offsets, long long n_out, int32_t* xy,
+                            long long* areas2, long long* obb);
+
 // COCOeval.accumulate (mrcnn_coco_accumulate; kernels_coco_acc.hip).  -ffp-contract=off.  All tables are device arrays.
 // A chunk is COCO_ACC_CHUNK consecutive entries of one category's segment [seg0, seg0 + seg_len) of the flat detection list, starting
 // `at` entries into it (a multiple of the chunk); the chunks of all segments, in order, are the grid of the sort kernels.

@@ -1218,3 +1218,164 @@ def rle_disjoint(det_src, rle, sizes=None, min_score: float = 0.0, device=None):
 def rle_disjoint_host(det_src, rle, sizes=None, min_score: float = 0.0):
     """The definition of rle_disjoint: the sequential host code (``mrcnn_rle_combine_host``), no GPU; numpy out."""
     return _rle_disjoint(True, det_src, rle, sizes, min_score, None)
+
+
+# ---- measuring run-length masks (mrcnn_rle_measure, mrcnn_rle_convex_hull) ------------------------------------------------------------------
+MEASURE_WORDS = _lib.MEASURE_WORDS
+HULL_LDS_COLUMNS = _lib.HULL_LDS_COLUMNS          # MRCNN_HULL_LDS_COLUMNS: a hull of more vertex columns (w + 1) is built in global scratch
+
+
+def _measure_flat(host_definition, space, counts, offs, hs, ws):
+    """mrcnn_rle_measure(_host) on a flat set of ``space`` -> measures (n, 7) int64 in the same space"""
+    n = int(offs.shape[0]) - 1
+    out = space.new((max(1, n), MEASURE_WORDS), np.int64)
+    ptr = space.ptr
+    head = (ptr(counts), ptr(offs), n, hs.ctypes.data, ws.ctypes.data)
+    if host_definition:
+        _lib.check(_lib.lib().mrcnn_rle_measure_host(*head, ptr(out)))
+    else:
+        _lib.check(_lib.lib().mrcnn_rle_measure(*head, space.code, ptr(out)))
+    return out[:n]
+
+
+def _hull_flat(host_definition, space, counts, offs, hs, ws):
+    """mrcnn_rle_convex_hull(_host) on a flat set of ``space`` -> (hull_offsets (n + 1), xy (V, 2), areas2 (n), obb (n, 8)) in the same
+    space.  A first attempt guesses the number of vertices; if there are more, one more call with the capacity the library reported."""
+    n = int(offs.shape[0]) - 1
+    ptr = space.ptr
+    hull_offs, areas2, obb = space.new(n + 1, np.int64, zero=True), space.new(max(1, n), np.int64), space.new((max(1, n), 8), np.int64)
+    entry = _lib.lib().mrcnn_rle_convex_hull_host if host_definition else _lib.lib().mrcnn_rle_convex_hull
+    head = (ptr(counts), ptr(offs), n, hs.ctypes.data, ws.ctypes.data) + (() if host_definition else (space.code,))
+    nv = C.c_int64(0)
+    capacity = 32 * n + 64
+    for _ in range(2):
+        xy = space.new((max(1, capacity), 2), np.int32)
+        st = entry(*head, ptr(hull_offs), ptr(areas2), ptr(obb), ptr(xy), C.byref(nv), capacity)
+        if st != 4 or int(nv.value) <= capacity:
+            break
+        capacity = int(nv.value)
+    _lib.check(st)
+    return hull_offs, xy[:int(nv.value)], areas2[:n], obb[:n]
+
+
+def _rle_measure(host_definition, rle, sizes, device):
+    name = "rle_measure_host" if host_definition else "rle_measure"
+    _, space, counts, offs, _, _, hs, ws = _combine_set(name, host_definition, rle, sizes, device)
+    return _measure_flat(host_definition, space, counts, offs, hs, ws)
+
+
+def rle_measure(rle, sizes=None, device=None):
+    """The moments and the perimeter of every mask of an RLE set, on the GPU from the runs, no plane in between (``mrcnn_rle_measure``;
+    the rule is defined in include/maskrcnn_hip.h).  ``rle`` in the forms rle_morph takes: a (counts, run_offsets) pair — numpy arrays
+    or CUDA tensors, measured where they lie, a tensor out — with ``sizes``, or rows.  Returns measures (n, 7) int64, RLE k = b * slots
+    + i for rows: [S1, Sx, Sy, Sxx, Sxy, Syy, perimeter] over the set pixels with pixel indices (x, y); perimeter counts the unit edges
+    between a set pixel and an unset one or the outside, the total edge length of rle_to_polygons' rings.  Central moments need more
+    than 64 bits: rle_region_props takes them in Python ints."""
+    return _rle_measure(False, rle, sizes, device)
+
+
+def rle_measure_host(rle, sizes=None):
+    """The definition of rle_measure: the sequential host code (``mrcnn_rle_measure_host``), no GPU; numpy out."""
+    return _rle_measure(True, rle, sizes, None)
+
+
+def _rle_convex_hull(host_definition, rle, sizes, flat, device):
+    name = "rle_convex_hull_host" if host_definition else "rle_convex_hull"
+    _, space, counts, offs, _, _, hs, ws = _combine_set(name, host_definition, rle, sizes, device)
+    hull_offs, xy, areas2, obb = _hull_flat(host_definition, space, counts, offs, hs, ws)
+    if flat:
+        return hull_offs, xy, areas2, obb
+    o = hull_offs if space.on_host else hull_offs.cpu().numpy()
+    return [xy[int(o[k]):int(o[k + 1])] for k in range(len(o) - 1)], areas2, obb
+
+
+def rle_convex_hull(rle, sizes=None, flat=False, device=None):
+    """The convex hull and the minimum-area oriented box of every mask of an RLE set, on the GPU from the runs
+    (``mrcnn_rle_convex_hull``).  ``rle`` as rle_measure takes it; a pair of CUDA tensors gives tensors.  The hull of a mask is the
+    hull of its set pixels' squares: a ring of integer pixel corners (x, y), strictly convex, clockwise on screen, starting at its
+    smallest vertex by x then y; an empty mask has none.  flat=True returns (hull_offsets (n + 1), xy (V, 2), areas2 (n), obb (n, 8)),
+    RLE k owning xy[hull_offsets[k]:hull_offsets[k + 1]], and nothing leaves the device; flat=False returns (hulls, areas2, obb) with
+    one (m_k, 2) array per RLE (the offsets are read back).  areas2 is twice the hull's area.  obb is [e, dx, dy, dmin, dmax, cmin,
+    cmax, 0]: the hull edge e, of vector (dx, dy), whose rectangle is smallest, and the extremes of d = dx*X + dy*Y and c = dx*Y -
+    dy*X over the hull; the point (d, c) is ((d*dx - c*dy) / L2, (d*dy + c*dx) / L2) with L2 = dx^2 + dy^2; [-1, 0, ...] for an empty
+    mask.  rle_region_props makes corners, centre, size and angle from it."""
+    return _rle_convex_hull(False, rle, sizes, flat, device)
+
+
+def rle_convex_hull_host(rle, sizes=None, flat=False):
+    """The definition of rle_convex_hull: the sequential host code (``mrcnn_rle_convex_hull_host``), no GPU; numpy out."""
+    return _rle_convex_hull(True, rle, sizes, flat, None)
+
+
+REGION_PROPS = ("area", "centroid", "orientation", "major_axis", "minor_axis", "eccentricity", "perimeter", "compactness", "hull_area", "solidity",
+                "extent", "obb_corners", "obb_center", "obb_size", "obb_angle")
+
+
+def region_props_of(measures, hull_offsets, xy, areas2, obb):
+    """The fields of rle_region_props from the integer tables (host arrays), computed with Python ints where 64 bits do not suffice."""
+    import math
+    n = int(len(measures))
+    out = {"area": np.zeros(n, np.int64), "centroid": np.full((n, 2), np.nan), "orientation": np.full(n, np.nan), "major_axis": np.full(n, np.nan),
+           "minor_axis": np.full(n, np.nan), "eccentricity": np.full(n, np.nan), "perimeter": np.zeros(n, np.int64), "compactness": np.full(n, np.nan),
+           "hull_area": np.zeros(n), "solidity": np.full(n, np.nan), "extent": np.full(n, np.nan), "obb_corners": np.full((n, 4, 2), np.nan),
+           "obb_center": np.full((n, 2), np.nan), "obb_size": np.full((n, 2), np.nan), "obb_angle": np.full(n, np.nan)}
+    for k in range(n):
+        s1, sx, sy, sxx, sxy, syy, per = (int(v) for v in measures[k])
+        out["area"][k], out["perimeter"][k] = s1, per
+        if s1 == 0:
+            continue
+        out["centroid"][k] = (sx / s1 + 0.5, sy / s1 + 0.5)
+        c20 = (s1 * sxx - sx * sx) / (s1 * s1) + 1.0 / 12.0          # exact integers, one rounding each
+        c02 = (s1 * syy - sy * sy) / (s1 * s1) + 1.0 / 12.0
+        c11 = (s1 * sxy - sx * sy) / (s1 * s1)
+        mean, dev = (c20 + c02) / 2.0, math.hypot((c20 - c02) / 2.0, c11)
+        l1, l2 = mean + dev, max(mean - dev, 0.0)
+        out["major_axis"][k], out["minor_axis"][k] = 4.0 * math.sqrt(l1), 4.0 * math.sqrt(l2)
+        out["orientation"][k] = 0.5 * math.atan2(2.0 * c11, c20 - c02)
+        out["eccentricity"][k] = math.sqrt(max(0.0, 1.0 - l2 / l1))
+        out["compactness"][k] = 4.0 * math.pi * s1 / (per * per)
+        a2 = int(areas2[k])
+        out["hull_area"][k], out["solidity"][k] = a2 / 2, 2 * s1 / a2
+        v = xy[int(hull_offsets[k]):int(hull_offsets[k + 1])]
+        out["extent"][k] = s1 / ((int(v[:, 0].max()) - int(v[:, 0].min())) * (int(v[:, 1].max()) - int(v[:, 1].min())))
+        _, dx, dy, dmin, dmax, cmin, cmax, _ = (int(t) for t in obb[k])
+        L2 = dx * dx + dy * dy
+        corners = [((d * dx - c * dy) / L2, (d * dy + c * dx) / L2) for d, c in ((dmin, cmin), (dmax, cmin), (dmax, cmax), (dmin, cmax))]
+        out["obb_corners"][k] = corners
+        out["obb_center"][k] = np.mean(np.asarray(corners), axis=0)
+        out["obb_size"][k] = ((dmax - dmin) / math.sqrt(L2), (cmax - cmin) / math.sqrt(L2))
+        out["obb_angle"][k] = math.atan2(dy, dx)
+    return out
+
+
+def _rle_region_props(host_definition, rle, sizes, device):
+    name = "rle_region_props_host" if host_definition else "rle_region_props"
+    _, space, counts, offs, _, _, hs, ws = _combine_set(name, host_definition, rle, sizes, device)
+    measures = _measure_flat(host_definition, space, counts, offs, hs, ws)
+    tables = _hull_flat(host_definition, space, counts, offs, hs, ws)
+    host = lambda a: a if space.on_host else a.cpu().numpy()
+    return region_props_of(host(measures), *(host(t) for t in tables))
+
+
+def rle_region_props(rle, sizes=None, device=None):
+    """The shape of every mask of an RLE set as skimage.regionprops and cv2.minAreaRect would give it, measured on the GPU from the runs
+    (rle_measure and rle_convex_hull; only the small tables — n x 7, n x 8 and the hulls' vertices — are read back).  ``rle`` as
+    rle_measure takes it.  Returns a dictionary of numpy arrays with one
+    entry per RLE (k = b * slots + i for rows), coordinates in the tracer's corner frame (pixel (x, y) is [x, x+1] x [y, y+1], y down):
+      area          S1                                   perimeter    the unit edges of the mask's outline (int64 both)
+      centroid      (Sx / S1 + 1/2, Sy / S1 + 1/2)
+      covariance    the pixel centres' (c20, c11, c02) = central second moments / S1, plus 1/12 on the diagonal for the uniform squares
+      major_axis    4 * sqrt(l1)      minor_axis  4 * sqrt(l2)   of the covariance's eigenvalues l1 >= l2
+      orientation   1/2 * atan2(2 * c11, c20 - c02), from +x towards +y      eccentricity  sqrt(1 - l2 / l1)
+      compactness   4 * pi * S1 / perimeter^2
+      hull_area     areas2 / 2        solidity    2 * S1 / areas2           extent  S1 / (the tight box's w * h)
+      obb_corners   (4, 2): the points (dmin, cmin), (dmax, cmin), (dmax, cmax), (dmin, cmax) of the chosen edge's frame, clockwise on screen
+      obb_center    their mean        obb_size    (D, C) / sqrt(L2): along and across the edge      obb_angle  atan2(dy, dx) of the edge
+    An empty mask has area, perimeter and hull_area 0 and NaN elsewhere.  The central moments (S1 * Sxx - Sx^2) are taken in Python
+    ints: they do not fit 64 bits."""
+    return _rle_region_props(False, rle, sizes, device)
+
+
+def rle_region_props_host(rle, sizes=None):
+    """rle_region_props from the sequential host definitions (``mrcnn_rle_measure_host``, ``mrcnn_rle_convex_hull_host``), no GPU."""
+    return _rle_region_props(True, rle, sizes, None)

@@ -27,7 +27,8 @@ def _ring(ring, transform, exterior: bool) -> List[List[float]]:
     return [[x, y] for x, y in pts + pts[:1]]
 
 
-def feature_collection(det_src, polygons, nest, sizes=None, class_names=None, transform=None, min_area: int = 1, image_ids=None) -> Dict:
+def feature_collection(det_src, polygons, nest, sizes=None, class_names=None, transform=None, min_area: int = 1, image_ids=None,
+                       props=None) -> Dict:
     """A FeatureCollection of a batch: det_src (B, slots, 6) source-frame rows, ``polygons`` = the nested (rings, areas) that
     detection.rle_to_polygons returned (simplified or not; the flat dictionaries are not taken), ``nest`` = what
     detection.nest_polygons returned for the nested form (None: the third entry of ``polygons``, as rle_to_polygons(..., nest=True)
@@ -46,6 +47,12 @@ def feature_collection(det_src, polygons, nest, sizes=None, class_names=None, tr
     below ``min_area``, or that has fewer than 3 vertices left after simplification, is dropped with its holes; a hole with fewer
     than 3 vertices is dropped alone.
 
+    ``props`` = the dictionary detection.rle_region_props (or predict_tiled(props=True)) returned for the same masks, entry b * slots +
+    i for row i of image b: every Feature's properties then gain, after the keys above, ``centroid`` [x, y] and ``orientation``
+    (radians, from +x towards +y) in source pixel corners like ``bbox``, ``perimeter`` (unit pixel edges), ``solidity`` and ``obb`` —
+    the four corners of the minimum-area oriented box, which, being geometry, go through ``transform`` as the rings do.  Without
+    props nothing changes.
+
     Simplification does not preserve topology: the nesting is the traced rings'; simplified rings may cross one another."""
     rings, areas = polygons[0], polygons[1]
     if nest is None:
@@ -59,6 +66,8 @@ def feature_collection(det_src, polygons, nest, sizes=None, class_names=None, tr
     det = np.asarray(det_src.cpu() if hasattr(det_src, "is_cuda") else det_src, dtype=np.float32)
     if det.ndim != 3 or det.shape[2] != 6 or det.shape[0] != len(rings) or any(len(row) != det.shape[1] for row in rings):
         raise ValueError(f"feature_collection: det_src {tuple(det.shape)} does not go with the rings")
+    if props is not None and len(props["area"]) != det.shape[0] * det.shape[1]:
+        raise ValueError(f"feature_collection: props of {len(props['area'])} masks do not go with det_src {tuple(det.shape)}")
     features = []
     for b in range(det.shape[0]):
         for i in range(det.shape[1]):
@@ -84,12 +93,18 @@ def feature_collection(det_src, polygons, nest, sizes=None, class_names=None, tr
                 x1, y1, x2, y2 = int(every[:, 0].min()), int(every[:, 1].min()), int(every[:, 0].max()), int(every[:, 1].max())
             cls = int(row[4])
             image = b if image_ids is None else image_ids[b]
-            props = {"image": image.item() if isinstance(image, np.generic) else image, "row": i, "category_id": cls}
+            properties = {"image": image.item() if isinstance(image, np.generic) else image, "row": i, "category_id": cls}
             if class_names is not None:
-                props["category"] = str(class_names[cls])
-            props.update({"score": float(row[5]), "bbox": [float(x1), float(y1), float(x2 - x1), float(y2 - y1)], "area": int(mine_areas.sum())})
+                properties["category"] = str(class_names[cls])
+            properties.update({"score": float(row[5]), "bbox": [float(x1), float(y1), float(x2 - x1), float(y2 - y1)], "area": int(mine_areas.sum())})
+            if props is not None:
+                k = b * det.shape[1] + i
+                ta, tb, tc, td, te, tf = t
+                properties.update({"centroid": [float(v) for v in props["centroid"][k]], "orientation": float(props["orientation"][k]),
+                                   "perimeter": int(props["perimeter"][k]), "solidity": float(props["solidity"][k]),
+                                   "obb": [[ta * float(x) + tb * float(y) + tc, td * float(x) + te * float(y) + tf] for x, y in props["obb_corners"][k]]})
             geometry = {"type": "Polygon", "coordinates": polys[0]} if len(polys) == 1 else {"type": "MultiPolygon", "coordinates": polys}
-            features.append({"type": "Feature", "geometry": geometry, "properties": props})
+            features.append({"type": "Feature", "geometry": geometry, "properties": properties})
     return {"type": "FeatureCollection", "features": features}
 
 

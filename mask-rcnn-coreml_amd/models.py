@@ -144,7 +144,7 @@ class MaskRCNN(_Model):
 
     def predict_tiled(self, images, tile=None, overlap=(64, 64), metric="ios", match_threshold=0.5, max_out=None, threshold=0.5,
                       unite=False, link_threshold=0.5, polygons=False, tolerance=None, nest=False, close=0,
-                      min_component_area=0, fill_holes=False, disjoint=False):
+                      min_component_area=0, fill_holes=False, disjoint=False, props=False):
         """Large images as overlapping windows at native resolution: detection.tile_plan per image (tile = None: the model's input
         size), predict_tiles, detection.merge_tiles.  Returns (det_src, source, n_kept, rles) in the frame of the images, in the
         form coco_results.coco_results and coco_eval.score_batch take.  By default an object is found whole only if some window
@@ -160,9 +160,12 @@ class MaskRCNN(_Model):
         an integer: holes of up to that many pixels, 0 like False) and min_component_area=a (specks of fewer than a pixels are cleared) filter the
         kept masks by their connected components after the closing, holes first, in the same place (detection.rle_fill_holes,
         detection.rle_remove_small).  disjoint=True then takes from every kept mask the pixels of the kept masks before it in its image
-        (detection.rle_disjoint, in the same place): no pixel belongs to two masks, as detection.instance_map_rle decides it.  The
-        defaults change nothing."""
-        from .detection import _merge_tiles, rle_close, rle_disjoint, rle_fill_holes, rle_remove_small, rle_rows_of, rle_to_polygons, tile_plan
+        (detection.rle_disjoint, in the same place): no pixel belongs to two masks, as detection.instance_map_rle decides it.
+        props=True appends one more result, the last: the dictionary of detection.rle_region_props — centroid, orientation, perimeter,
+        hull, solidity, oriented box — of the final masks (after close, fill_holes, min_component_area and disjoint), measured from the
+        runs where they lie, entry b * max_out + i for row i of image b.  The defaults change nothing."""
+        from .detection import (_merge_tiles, rle_close, rle_disjoint, rle_fill_holes, rle_region_props, rle_remove_small, rle_rows_of, rle_to_polygons,
+                                tile_plan)
         images = list(images)
         H, W = self.image_height, self.image_width
         tile = (H, W) if tile is None else tile
@@ -183,9 +186,11 @@ class MaskRCNN(_Model):
             resident[0] = rle_disjoint(out[0], resident[0], sizes)[0]
         if close or min_component_area or fill or disjoint:
             out = (*out[:3], rle_rows_of(resident[0], sizes))
-        if not polygons:
-            return out
-        return (*out, rle_to_polygons(resident[0], sizes, tolerance=tolerance, nest=nest))
+        if polygons:
+            out = (*out, rle_to_polygons(resident[0], sizes, tolerance=tolerance, nest=nest))
+        if props:
+            out = (*out, rle_region_props(resident[0], sizes))
+        return out
 
     def predict_jpegs(self, files, entropy="host"):
         """predict_images straight from JPEG files (mrcnn_maskrcnn_predict_jpegs_on): a list of bytes.  The entropy decoders run on the
