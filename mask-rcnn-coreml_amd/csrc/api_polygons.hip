@@ -3,7 +3,7 @@
 // nested into outlines and their holes: nest_host.cpp and kernels_nest.hip.  Every argument error is answered before a device is looked for.
 #include <string.h>
 
-#include "api_util.h"
+#include "api_rle_stage.h"
 #include "nest_host.h"
 #include "polygons_host.h"
 #include "simplify_host.h"
@@ -64,29 +64,13 @@ extern "C" int mrcnn_rle_to_polygons(const uint32_t* counts, const int64_t* run_
             return;
         }
 
-        // the set on the device and its run offsets here, as the drawing entries stage them
-        std::vector<long long> h_off(n + 1, 0);
-        if (dev) HIP_CHECK(hipMemcpy(h_off.data(), run_offsets, (n + 1) * 8, hipMemcpyDeviceToHost));
-        else memcpy(h_off.data(), run_offsets, (n + 1) * 8);
-        answer(rle_draw::check_run_offsets(reinterpret_cast<const int64_t*>(h_off.data()), (int64_t)n, who, &err), err);
-        for (size_t k = 0; k < n; ++k)
-            MRCNN_REQUIRE(h_off[k + 1] - h_off[k] < (1LL << 31), MRCNN_ERR_SHAPE, "%s: RLE %lld has %lld runs: too many", who, (long long)k, h_off[k + 1] - h_off[k]);
-        const size_t runs = (size_t)h_off[n];
-        MRCNN_REQUIRE(counts || runs == 0, MRCNN_ERR_INVALID, "%s: null counts", who);
         Stream st;
         hipStream_t s = st.s;
-        DevBuf tc, to, tp, t_rings, t_offsets, t_areas, t_xy;
+        StagedRle in(counts, run_offsets, (int64_t)n, dev, who);
+        DevBuf t_rings, t_offsets, t_areas, t_xy;
         Carver sc, wc;
         Drain drain{s};                                          // (declared behind the buffers: the stream drains before they are freed)
-        const uint32_t* d_counts = counts;
-        const long long* d_off = reinterpret_cast<const long long*>(run_offsets);
-        if (!dev) {
-            tc.alloc(runs * 4); to.alloc((n + 1) * 8);
-            if (runs) HIP_CHECK(hipMemcpy(tc.p, counts, runs * 4, hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(to.p, h_off.data(), (n + 1) * 8, hipMemcpyHostToDevice));
-            d_counts = tc.as<uint32_t>(); d_off = to.as<long long>();
-        }
-        tp.alloc(runs * 4);
+        in.stage();
         // one scratch allocation: the image table | totals | areas | the units' counts and prefix | the RLEs' first corners | the summary
         const auto s_tab = sc.take<PolygonImage>(tab.size());
         const auto s_tot = sc.take<unsigned long long>(n);
@@ -97,20 +81,12 @@ extern "C" int mrcnn_rle_to_polygons(const uint32_t* counts, const int64_t* run_
         const auto s_sum = sc.take<unsigned long long>(3);
         sc.alloc();
         HIP_CHECK(hipMemcpy(sc[s_tab], tab.data(), tab.size() * sizeof(PolygonImage), hipMemcpyHostToDevice));
-        const PolygonSet set{tp.as<uint32_t>(), d_off, sc[s_tot], sc[s_tab], n_images, slots, units, sc[s_cnt], sc[s_start], sc[s_c0]};
-        rle_prefix_forward(s, d_counts, d_off, (long)n, tp.as<uint32_t>(), nullptr, sc[s_tot], sc[s_ar]);
+        const PolygonSet set{in.pre_b, in.run_offsets, sc[s_tot], sc[s_tab], n_images, slots, units, sc[s_cnt], sc[s_start], sc[s_c0]};
+        rle_prefix_forward(s, in.counts, in.run_offsets, (long)n, in.pre_b, nullptr, sc[s_tot], sc[s_ar]);
         polygons_count_forward(s, set, sc[s_sum]);
         unsigned long long sum[3] = {0, 0, 0};                   // the first of the two read-backs: is every RLE right, and how large is the work
-        HIP_CHECK(hipMemcpyAsync(sum, sc[s_sum], sizeof sum, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (sum[0] != ~0ull) {                                   // nothing has been traced and nothing is written
-            const unsigned long long k = sum[0];
-            unsigned long long total = 0;
-            HIP_CHECK(hipMemcpy(&total, sc[s_tot] + k, sizeof total, hipMemcpyDeviceToHost));
-            const int b = (int)(k / (unsigned long long)slots);
-            fail(MRCNN_ERR_SHAPE, "%s: RLE %llu (image %d, slot %d) sums to %llu pixels, its %dx%d plane has %llu", who, k, b,
-                 (int)(k % (unsigned long long)slots), total, heights[b], widths[b], (unsigned long long)heights[b] * (unsigned long long)widths[b]);
-        }
+        const Refusal r = read_refusal(s, sc[s_sum], sc[s_tot], sum, sizeof sum);
+        if (r.any) answer(rle_draw::bad_sum(a, r.k, r.sum, who, &err), err);   // nothing has been traced and nothing is written
         const long long corners = (long long)sum[1], most = (long long)sum[2];
         MRCNN_REQUIRE(corners < (1LL << 31), MRCNN_ERR_SHAPE, "%s: the set has %lld corners: too many for one call", who, corners);
 

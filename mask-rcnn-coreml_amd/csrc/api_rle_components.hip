@@ -3,9 +3,8 @@
 // that merge or split by a keep mask.  Every argument error is answered before a device is looked for.
 #include <string.h>
 
-#include "api_util.h"
+#include "api_rle_stage.h"
 #include "rle_components_host.h"
-#include "rle_draw_host.h"
 
 using namespace mrcnn;
 namespace rc = mrcnn::rle_components;
@@ -16,7 +15,7 @@ extern "C" int mrcnn_rle_components_host(const uint32_t* counts, const int64_t* 
 {
     return guarded([&] {
         std::string err;
-        answer(rc::components_host(rc::Set{counts, run_offsets, n, heights, widths, connectivity, of},
+        answer(rc::components_host(rc::Set{{counts, run_offsets, n, heights, widths}, connectivity, of},
                                    rc::Measures{comp_offsets, comp_areas, comp_bboxes_xywh, comp_flags, comp_capacity}, &err), err);
     });
 }
@@ -28,7 +27,7 @@ extern "C" int mrcnn_rle_components_select_host(const uint32_t* counts, const in
 {
     return guarded([&] {
         std::string err;
-        answer(rc::select_host(rc::Set{counts, run_offsets, n, heights, widths, connectivity, of},
+        answer(rc::select_host(rc::Set{{counts, run_offsets, n, heights, widths}, connectivity, of},
                                rc::Select{keep, n_comps, mode, out_counts, capacity, out_run_offsets, areas, bboxes_xywh, out_parent, out_n}, &err), err);
     });
 }
@@ -38,7 +37,7 @@ namespace {
 // The set on the device, labelled: what both device entries do first.  Declared before the stream's Drain in the caller: the buffers
 // outlive the queued work.
 struct Labelled {
-    DevBuf tc, to, tp;
+    StagedRle in;
     Carver sc, pc;
     CompSet S{};
     CompPieces P{};
@@ -46,33 +45,18 @@ struct Labelled {
     int32_t* comp_rle = nullptr;
     long long* comp_offsets = nullptr;       // device, n + 1
     long long n_comps = 0;
+    Labelled(const rc::Set& a, bool dev, const char* who) : in(a.counts, a.run_offsets, a.n, dev, who) {}
 };
 
-void label(hipStream_t s, const rc::Set& a, bool dev, const char* who, Labelled& L)
+void label(hipStream_t s, const rc::Set& a, const char* who, Labelled& L)
 {
     std::string err;
     const size_t N = (size_t)a.n;
-    std::vector<long long> h_off(N + 1, 0);
-    if (dev) {
-        HIP_CHECK(hipMemcpy(h_off.data(), a.run_offsets, (N + 1) * 8, hipMemcpyDeviceToHost));
-        answer(rle_draw::check_run_offsets(reinterpret_cast<const int64_t*>(h_off.data()), a.n, who, &err), err);
-    } else memcpy(h_off.data(), a.run_offsets, (N + 1) * 8);
-    for (size_t k = 0; k < N; ++k)
-        MRCNN_REQUIRE(h_off[k + 1] - h_off[k] < (1LL << 31), MRCNN_ERR_SHAPE, "%s: RLE %lld has %lld runs: too many", who, (long long)k, h_off[k + 1] - h_off[k]);
-    const size_t all = (size_t)h_off[N];                        // counts[0 .. all) is read as the other entries read it
-    const long long runs = h_off[N] - h_off[0];
+    const long long runs = L.in.runs;
     MRCNN_REQUIRE(runs < (1LL << 31), MRCNN_ERR_SHAPE, "%s: the set has %lld runs: too many for one call", who, runs);
-    MRCNN_REQUIRE(a.counts || runs == 0, MRCNN_ERR_INVALID, "%s: null counts", who);
-
-    const uint32_t* c = a.counts;
-    const long long* off = reinterpret_cast<const long long*>(a.run_offsets);
-    if (!dev) {
-        L.tc.alloc((all ? all : 1) * 4); L.to.alloc((N + 1) * 8);
-        if (all) HIP_CHECK(hipMemcpy(L.tc.p, a.counts, all * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(L.to.p, h_off.data(), (N + 1) * 8, hipMemcpyHostToDevice));
-        c = L.tc.as<uint32_t>(); off = L.to.as<long long>();
-    }
-    L.tp.alloc((all ? all : 1) * 4);
+    L.in.stage();
+    const uint32_t* c = L.in.counts;
+    const long long* off = L.in.run_offsets;
     // one scratch allocation: heights | widths | totals | areas | the flag and the number of pieces | pieces per run and their prefix | offsets
     Carver& sc = L.sc;
     const auto s_h = sc.take<int32_t>(N), s_w = sc.take<int32_t>(N);
@@ -88,20 +72,15 @@ void label(hipStream_t s, const rc::Set& a, bool dev, const char* who, Labelled&
         HIP_CHECK(hipMemcpy(sc[s_h], a.heights, N * 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(sc[s_w], a.widths, N * 4, hipMemcpyHostToDevice));
     }
-    rle_prefix_forward(s, c, off, (long)a.n, L.tp.as<uint32_t>(), nullptr, sc[s_tot], sc[s_ar]);
+    rle_prefix_forward(s, c, off, (long)a.n, L.in.pre_b, nullptr, sc[s_tot], sc[s_ar]);
     CompSet& S = L.S;
-    S.counts = c; S.pre_b = L.tp.as<uint32_t>(); S.run_offsets = off; S.heights = sc[s_h]; S.widths = sc[s_w]; S.totals = sc[s_tot];
+    S.counts = c; S.pre_b = L.in.pre_b; S.run_offsets = off; S.heights = sc[s_h]; S.widths = sc[s_w]; S.totals = sc[s_tot];
     S.n = (int)a.n; S.connectivity = a.connectivity; S.of = a.of;
     rle_components_count_forward(s, S, runs, sc[s_cnt], sc[s_start], sc[s_bad]);
-    unsigned long long k_bad = 0, n_pieces = 0;
-    HIP_CHECK(hipMemcpyAsync(&k_bad, sc[s_bad], 8, hipMemcpyDeviceToHost, s));
+    unsigned long long n_pieces = 0;                         // read back with the flag: one synchronise
     HIP_CHECK(hipMemcpyAsync(&n_pieces, sc[s_start] + runs, 8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (k_bad != ~0ull) {                                    // the one flag said no: fetch the sum for the message
-        unsigned long long sum = 0;
-        HIP_CHECK(hipMemcpy(&sum, sc[s_tot] + k_bad, sizeof sum, hipMemcpyDeviceToHost));
-        answer(rc::bad_sum(a, (int64_t)k_bad, sum, who, &err), err);
-    }
+    const Refusal r = read_refusal(s, sc[s_bad], sc[s_tot]);
+    if (r.any) answer(rle_set::bad_sum(a, r.k, r.sum, who, &err), err);
     MRCNN_REQUIRE(n_pieces < (1ull << 31), MRCNN_ERR_SHAPE, "%s: the set cuts into %llu column pieces: too many for one call", who, n_pieces);
 
     // the pieces: starts | ends | RLEs | parents | roots | numbers | root flags | their prefix | the components' RLEs
@@ -130,22 +109,19 @@ extern "C" int mrcnn_rle_components(const uint32_t* counts, const int64_t* run_o
     return guarded([&] {
         const char* who = "rle_components";
         std::string err;
-        const rc::Set a{counts, run_offsets, n, heights, widths, connectivity, of};
+        const rc::Set a{{counts, run_offsets, n, heights, widths}, connectivity, of};
         answer(rc::check_measures(a, rc::Measures{comp_offsets, comp_areas, comp_bboxes_xywh, comp_flags, comp_capacity}, who, &err), err);
         MRCNN_REQUIRE(memspace == MRCNN_HOST || memspace == MRCNN_DEVICE, MRCNN_ERR_INVALID, "rle_components: unknown memspace %d", memspace);
         const bool dev = memspace == MRCNN_DEVICE;
-        if (!dev) {                                              // the offsets can be judged here: before a device is looked for
-            answer(rle_draw::check_run_offsets(run_offsets, n, who, &err), err);
-            MRCNN_REQUIRE(counts || run_offsets[n] == run_offsets[0], MRCNN_ERR_INVALID, "rle_components: null counts");
-        }
+        if (!dev) StagedRle::check_host(counts, run_offsets, n, who);     // the offsets can be judged here: before a device is looked for
         require_gpu();
         Stream st;
-        Labelled L;
+        Labelled L(a, dev, who);
         DevBuf tar, tbb, tfl;
         Carver ac;
         Drain drain{st.s};
         hipStream_t s = st.s;
-        label(s, a, dev, who, L);
+        label(s, a, who, L);
         const size_t N = (size_t)n;
         HIP_CHECK(hipMemcpy(comp_offsets, L.comp_offsets, (N + 1) * 8, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
         // comp_offsets is written by now; the measures only when all components fit
@@ -178,22 +154,19 @@ extern "C" int mrcnn_rle_components_select(const uint32_t* counts, const int64_t
     return guarded([&] {
         const char* who = "rle_components_select";
         std::string err;
-        const rc::Set a{counts, run_offsets, n, heights, widths, connectivity, of};
+        const rc::Set a{{counts, run_offsets, n, heights, widths}, connectivity, of};
         answer(rc::check_select(a, rc::Select{keep, n_comps, mode, out_counts, capacity, out_run_offsets, areas, bboxes_xywh, out_parent, out_n}, who, &err), err);
         MRCNN_REQUIRE(memspace == MRCNN_HOST || memspace == MRCNN_DEVICE, MRCNN_ERR_INVALID, "rle_components_select: unknown memspace %d", memspace);
         const bool dev = memspace == MRCNN_DEVICE;
-        if (!dev) {
-            answer(rle_draw::check_run_offsets(run_offsets, n, who, &err), err);
-            MRCNN_REQUIRE(counts || run_offsets[n] == run_offsets[0], MRCNN_ERR_INVALID, "rle_components_select: null counts");
-        }
+        if (!dev) StagedRle::check_host(counts, run_offsets, n, who);
         require_gpu();
         Stream st;
-        Labelled L;
+        Labelled L(a, dev, who);
         DevBuf tkeep, tro, tar, tbb, tpar, tcnt, keys, bnd;
         Carver wc, gc;
         Drain drain{st.s};
         hipStream_t s = st.s;
-        label(s, a, dev, who, L);
+        label(s, a, who, L);
         if (L.n_comps != (long long)n_comps) answer(rc::bad_n_comps((long long)n_comps, L.n_comps, who, &err), err);
 
         const bool split = mode == MRCNN_COMPONENTS_SPLIT;
@@ -259,7 +232,7 @@ extern "C" int mrcnn_rle_components_select(const uint32_t* counts, const int64_t
             if (bboxes_xywh && Gn) HIP_CHECK(hipMemcpy(bboxes_xywh, tbb.p, Gn * 16, hipMemcpyDeviceToHost));
         }
         // everything but the runs is written by now; the runs only when all of them fit
-        if (!fits) answer(rc::bad_capacity(need, (long long)capacity, who, &err), err);
+        if (!fits) answer(rle_set::bad_runs_capacity(need, (long long)capacity, who, &err), err);
         if (!dev && need) HIP_CHECK(hipMemcpy(out_counts, tcnt.p, (size_t)need * 4, hipMemcpyDeviceToHost));
     });
 }

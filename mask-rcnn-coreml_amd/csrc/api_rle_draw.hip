@@ -3,22 +3,17 @@
 // staging (RleDrawRun).  Every argument error is answered before a device is looked for.
 #include <string.h>
 
-#include "api_util.h"
+#include "api_rle_stage.h"
 #include "rle_draw_host.h"
 
 using namespace mrcnn;
-
-static rle_draw::Set rle_set(const uint32_t* counts, const int64_t* run_offsets, int n_images, int slots, const int32_t* heights, const int32_t* widths)
-{
-    return rle_draw::Set{counts, run_offsets, n_images, slots, heights, widths};
-}
 
 extern "C" int mrcnn_rle_decode_host(const uint32_t* counts, const int64_t* run_offsets, int n_images, int slots, const int32_t* heights,
                                      const int32_t* widths, uint8_t* out, const int64_t* out_offsets)
 {
     return guarded([&] {
         std::string err;
-        answer(rle_draw::decode_host(rle_set(counts, run_offsets, n_images, slots, heights, widths), out, out_offsets, &err), err);
+        answer(rle_draw::decode_host(rle_draw::Set{counts, run_offsets, n_images, slots, heights, widths}, out, out_offsets, &err), err);
     });
 }
 
@@ -28,7 +23,7 @@ extern "C" int mrcnn_instance_map_rle_host(const float* detections_src, const ui
 {
     return guarded([&] {
         std::string err;
-        answer(rle_draw::instance_map_host(rle_set(counts, run_offsets, n_images, slots, heights, widths), detections_src, min_score, map, map_offsets,
+        answer(rle_draw::instance_map_host(rle_draw::Set{counts, run_offsets, n_images, slots, heights, widths}, detections_src, min_score, map, map_offsets,
                                            visible_areas, &err), err);
     });
 }
@@ -39,7 +34,7 @@ extern "C" int mrcnn_render_detections_rle_host(const mrcnn_image* images, const
 {
     return guarded([&] {
         std::string err;
-        answer(rle_draw::render_host(rle_set(counts, run_offsets, n_images, slots, nullptr, nullptr), images, detections_src, min_score, alpha, stroke,
+        answer(rle_draw::render_host(rle_draw::Set{counts, run_offsets, n_images, slots, nullptr, nullptr}, images, detections_src, min_score, alpha, stroke,
                                      out_rgb, out_offsets, &err), err);
     });
 }
@@ -55,7 +50,8 @@ struct RleDrawRun {
     const bool dev;
     const size_t n;
     Stream st_;
-    DevBuf tc, to, td, tp;
+    StagedRle in;
+    DevBuf td;
     Carver sc;
     RaggedOut out;                                           // (declared behind the buffers: the stream drains before they are freed)
     hipStream_t s;
@@ -66,33 +62,16 @@ struct RleDrawRun {
     // det: the caller's detections_src (nullptr: the decode); callers / out_offsets / unit_bytes / extent: the output and its layout, checked by the caller
     RleDrawRun(const rle_draw::Set& set, const char* name, int memspace, const float* det, float min_score, void* callers, const int64_t* out_offsets,
                int64_t unit_bytes, int64_t extent)
-        : a(set), who(name), dev(memspace == MRCNN_DEVICE), n((size_t)set.n_images * set.slots), out(st_.s, callers, dev, extent), s(st_.s),
-          offsets(out_offsets), unit(unit_bytes)
+        : a(set), who(name), dev(memspace == MRCNN_DEVICE), n((size_t)set.n_images * set.slots), in(set.counts, set.run_offsets, (int64_t)n, dev, name),
+          out(st_.s, callers, dev, extent), s(st_.s), offsets(out_offsets), unit(unit_bytes)
     {
-        std::vector<long long> h_off(n + 1, 0);
-        if (dev) HIP_CHECK(hipMemcpy(h_off.data(), a.run_offsets, (n + 1) * 8, hipMemcpyDeviceToHost));
-        else memcpy(h_off.data(), a.run_offsets, (n + 1) * 8);
-        std::string err;
-        answer(rle_draw::check_run_offsets(reinterpret_cast<const int64_t*>(h_off.data()), (int64_t)n, who, &err), err);
-        for (size_t k = 0; k < n; ++k)
-            MRCNN_REQUIRE(h_off[k + 1] - h_off[k] < (1LL << 31), MRCNN_ERR_SHAPE, "%s: RLE %lld has %lld runs: too many", who, (long long)k, h_off[k + 1] - h_off[k]);
-        const size_t runs = (size_t)h_off[n];
-        MRCNN_REQUIRE(a.counts || runs == 0, MRCNN_ERR_INVALID, "%s: null counts", who);
-        const uint32_t* counts = a.counts;
-        const long long* off = reinterpret_cast<const long long*>(a.run_offsets);
-        if (!dev) {
-            tc.alloc(runs * 4); to.alloc((n + 1) * 8);
-            if (runs) HIP_CHECK(hipMemcpy(tc.p, a.counts, runs * 4, hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(to.p, h_off.data(), (n + 1) * 8, hipMemcpyHostToDevice));
-            counts = tc.as<uint32_t>(); off = to.as<long long>();
-            if (det && n) det = stage_rows(det, memspace, (long)n, 6, 6, td);
-        }
+        in.stage();
+        if (!dev && det && n) det = stage_rows(det, memspace, (long)n, 6, 6, td);
         std::vector<ImageGeom> tab((size_t)a.n_images);
         for (int b = 0; b < a.n_images; ++b) {
             tab[(size_t)b].h = a.heights[b]; tab[(size_t)b].w = a.widths[b]; tab[(size_t)b].offset = offsets[b];
             job.max_h = std::max(job.max_h, a.heights[b]); job.max_w = std::max(job.max_w, a.widths[b]);
         }
-        tp.alloc(runs * 4);
         // one scratch allocation: the image table | totals | areas | extents | records | the flag
         const auto s_tab = sc.take<ImageGeom>(tab.size());
         const auto s_tot = sc.take<unsigned long long>(n);
@@ -103,21 +82,14 @@ struct RleDrawRun {
         sc.alloc();
         if (!tab.empty()) HIP_CHECK(hipMemcpy(sc[s_tab], tab.data(), tab.size() * sizeof(ImageGeom), hipMemcpyHostToDevice));
         job.rec = sc[s_rec];
-        job.pre_b = tp.as<uint32_t>();
+        job.pre_b = in.pre_b;
         job.tab = sc[s_tab];
         job.n_images = a.n_images; job.slots = a.slots;
-        rle_prefix_forward(s, counts, off, (long)n, tp.as<uint32_t>(), nullptr, sc[s_tot], sc[s_ar], sc[s_ext]);
-        rle_draw_prepare(s, off, sc[s_tot], sc[s_ext], det, min_score, job, sc[s_rec], sc[s_bad]);
-        unsigned long long k = 0;
-        HIP_CHECK(hipMemcpyAsync(&k, sc[s_bad], sizeof k, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (k != ~0ull) {                                           // the one flag said no: fetch the sum for the message
-            unsigned long long sum = 0;
-            HIP_CHECK(hipMemcpy(&sum, sc[s_tot] + k, sizeof sum, hipMemcpyDeviceToHost));
-            const int b = (int)(k / (unsigned long long)a.slots);
-            fail(MRCNN_ERR_SHAPE, "%s: RLE %llu (image %d, slot %d) sums to %llu pixels, its %dx%d plane has %llu", who, k, b,
-                 (int)(k % (unsigned long long)a.slots), sum, a.heights[b], a.widths[b], (unsigned long long)a.heights[b] * (unsigned long long)a.widths[b]);
-        }
+        rle_prefix_forward(s, in.counts, in.run_offsets, (long)n, in.pre_b, nullptr, sc[s_tot], sc[s_ar], sc[s_ext]);
+        rle_draw_prepare(s, in.run_offsets, sc[s_tot], sc[s_ext], det, min_score, job, sc[s_rec], sc[s_bad]);
+        const Refusal r = read_refusal(s, sc[s_bad], sc[s_tot]);
+        std::string err;
+        if (r.any) answer(rle_draw::bad_sum(a, r.k, r.sum, who, &err), err);
     }
 
     // the drawing is queued: only the images' own bytes go to a host caller
@@ -135,7 +107,7 @@ extern "C" int mrcnn_rle_decode(const uint32_t* counts, const int64_t* run_offse
 {
     return guarded([&] {
         std::string err;
-        const rle_draw::Set a = rle_set(counts, run_offsets, n_images, slots, heights, widths);
+        const rle_draw::Set a{counts, run_offsets, n_images, slots, heights, widths};
         answer(rle_draw::check_set(a, 0x7fffffff, "rle_decode", &err), err);
         MRCNN_REQUIRE(out, MRCNN_ERR_INVALID, "rle_decode: null out");
         MRCNN_REQUIRE(memspace == MRCNN_HOST || memspace == MRCNN_DEVICE, MRCNN_ERR_INVALID, "rle_decode: unknown memspace %d", memspace);
@@ -155,7 +127,7 @@ extern "C" int mrcnn_instance_map_rle(const float* detections_src, const uint32_
 {
     return guarded([&] {
         std::string err;
-        const rle_draw::Set a = rle_set(counts, run_offsets, n_images, slots, heights, widths);
+        const rle_draw::Set a{counts, run_offsets, n_images, slots, heights, widths};
         answer(rle_draw::check_set(a, 32767, "instance_map_rle", &err), err);
         MRCNN_REQUIRE(detections_src && map, MRCNN_ERR_INVALID, "instance_map_rle: null argument");
         MRCNN_REQUIRE(memspace == MRCNN_HOST || memspace == MRCNN_DEVICE, MRCNN_ERR_INVALID, "instance_map_rle: unknown memspace %d", memspace);
@@ -182,7 +154,7 @@ extern "C" int mrcnn_render_detections_rle(const mrcnn_image* images, const floa
         std::string err;
         std::vector<int32_t> hs, ws;
         image_sizes(images, n_images, "render_detections_rle", hs, ws);
-        const rle_draw::Set a = rle_set(counts, run_offsets, n_images, slots, hs.data(), ws.data());
+        const rle_draw::Set a{counts, run_offsets, n_images, slots, hs.data(), ws.data()};
         answer(rle_draw::check_set(a, 32767, "render_detections_rle", &err), err);
         MRCNN_REQUIRE(detections_src && out_rgb, MRCNN_ERR_INVALID, "render_detections_rle: null argument");
         MRCNN_REQUIRE(memspace == MRCNN_HOST || memspace == MRCNN_DEVICE, MRCNN_ERR_INVALID, "render_detections_rle: unknown memspace %d", memspace);

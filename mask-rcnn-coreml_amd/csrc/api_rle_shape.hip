@@ -3,8 +3,7 @@
 // device entries (kernels_rle_shape.hip).  Every argument error is answered before a device is looked for.
 #include <string.h>
 
-#include "api_util.h"
-#include "rle_draw_host.h"
+#include "api_rle_stage.h"
 #include "rle_shape_host.h"
 #include "shape_rule.h"
 
@@ -15,35 +14,18 @@ namespace {
 // What both device entries do first: the set staged on the device, its prefix table, and the one read-back before anything is written —
 // the flag that refuses an RLE which does not sum to its plane.
 struct ShapeCall {
-    DevBuf tc, to, tp;
+    StagedRle in;
     Carver sc;
     ShapeSet S{};
     int max_w = 0;
 
-    void stage(hipStream_t s, const rle_shape::Set& a, bool dev, const char* who)
+    ShapeCall(const rle_shape::Set& a, bool dev, const char* who) : in(a.counts, a.run_offsets, a.n, dev, who) {}
+
+    void stage(hipStream_t s, const rle_shape::Set& a, const char* who)
     {
         std::string err;
         const size_t N = (size_t)a.n;
-        std::vector<long long> h_off(N + 1, 0);
-        if (dev) {
-            HIP_CHECK(hipMemcpy(h_off.data(), a.run_offsets, (N + 1) * 8, hipMemcpyDeviceToHost));
-            answer(rle_draw::check_run_offsets(reinterpret_cast<const int64_t*>(h_off.data()), a.n, who, &err), err);
-        } else memcpy(h_off.data(), a.run_offsets, (N + 1) * 8);
-        for (size_t k = 0; k < N; ++k)
-            MRCNN_REQUIRE(h_off[k + 1] - h_off[k] < (1LL << 31), MRCNN_ERR_SHAPE, "%s: RLE %lld has %lld runs: too many", who, (long long)k, h_off[k + 1] - h_off[k]);
-        const size_t runs = (size_t)(h_off[N] - h_off[0]);
-        MRCNN_REQUIRE(a.counts || runs == 0, MRCNN_ERR_INVALID, "%s: null counts", who);
-        const uint32_t* c = a.counts;
-        const long long* off = reinterpret_cast<const long long*>(a.run_offsets);
-        if (!dev) {                                              // (all of counts up to the last RLE's end: the offsets hold as they are)
-            const size_t upto = (size_t)h_off[N];
-            tc.alloc((upto ? upto : 1) * 4); to.alloc((N + 1) * 8);
-            if (upto) HIP_CHECK(hipMemcpy(tc.p, a.counts, upto * 4, hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(to.p, h_off.data(), (N + 1) * 8, hipMemcpyHostToDevice));
-            c = tc.as<uint32_t>(); off = to.as<long long>();
-        }
-        const size_t table = (size_t)h_off[N];
-        tp.alloc((table ? table : 1) * 4);
+        in.stage();
         std::vector<long long> vcol0(N + 1, 0);
         for (size_t k = 0; k < N; ++k) {
             vcol0[k + 1] = vcol0[k] + a.widths[k] + 1;
@@ -59,17 +41,11 @@ struct ShapeCall {
         HIP_CHECK(hipMemcpy(sc[s_h], a.heights, N * 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(sc[s_w], a.widths, N * 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(sc[s_v], vcol0.data(), (N + 1) * 8, hipMemcpyHostToDevice));
-        rle_prefix_forward(s, c, off, (long)a.n, tp.as<uint32_t>(), nullptr, sc[s_tot], sc[s_ar]);
-        S = ShapeSet{c, tp.as<uint32_t>(), off, sc[s_h], sc[s_w], sc[s_tot], sc[s_v], (int)a.n, vcol0[N]};
+        rle_prefix_forward(s, in.counts, in.run_offsets, (long)a.n, in.pre_b, nullptr, sc[s_tot], sc[s_ar]);
+        S = ShapeSet{in.counts, in.pre_b, in.run_offsets, sc[s_h], sc[s_w], sc[s_tot], sc[s_v], (int)a.n, vcol0[N]};
         rle_shape_check_forward(s, S, sc[s_bad]);
-        unsigned long long k_bad = ~0ull;
-        HIP_CHECK(hipMemcpyAsync(&k_bad, sc[s_bad], sizeof k_bad, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (k_bad != ~0ull) {                                    // the one flag said no: fetch the sum for the message
-            unsigned long long sum = 0;
-            HIP_CHECK(hipMemcpy(&sum, sc[s_tot] + k_bad, sizeof sum, hipMemcpyDeviceToHost));
-            answer(rle_shape::bad_sum(a, (int64_t)k_bad, sum, who, &err), err);
-        }
+        const Refusal r = read_refusal(s, sc[s_bad], sc[s_tot]);
+        if (r.any) answer(rle_set::bad_sum(a, r.k, r.sum, who, &err), err);
     }
 };
 
@@ -91,21 +67,18 @@ extern "C" int mrcnn_rle_measure(const uint32_t* counts, const int64_t* run_offs
         const char* who = "rle_measure";
         std::string err;
         const rle_shape::Set a{counts, run_offsets, n, heights, widths};
-        answer(rle_shape::check_set(a, who, &err), err);
+        answer(rle_set::check_flat(a, who, &err), err);
         MRCNN_REQUIRE(measures || n == 0, MRCNN_ERR_INVALID, "%s: null measures", who);
         MRCNN_REQUIRE(memspace == MRCNN_HOST || memspace == MRCNN_DEVICE, MRCNN_ERR_INVALID, "%s: unknown memspace %d", who, memspace);
         const bool dev = memspace == MRCNN_DEVICE;
-        if (!dev) {                                              // the offsets can be judged here: before a device is looked for
-            answer(rle_draw::check_run_offsets(run_offsets, n, who, &err), err);
-            MRCNN_REQUIRE(counts || run_offsets[n] == run_offsets[0], MRCNN_ERR_INVALID, "%s: null counts", who);
-        }
+        if (!dev) StagedRle::check_host(counts, run_offsets, n, who);     // the offsets can be judged here: before a device is looked for
         require_gpu();
         if (n == 0) return;
         Stream st;
-        ShapeCall call;
+        ShapeCall call(a, dev, who);
         DevBuf tm;
         Drain drain{st.s};
-        call.stage(st.s, a, dev, who);
+        call.stage(st.s, a, who);
         const size_t bytes = (size_t)n * SHAPE_MEASURE_WORDS * sizeof(long long);
         long long* m = reinterpret_cast<long long*>(measures);
         if (!dev) { tm.alloc(bytes); m = tm.as<long long>(); }
@@ -134,14 +107,11 @@ extern "C" int mrcnn_rle_convex_hull(const uint32_t* counts, const int64_t* run_
         const char* who = "rle_convex_hull";
         std::string err;
         const rle_shape::Set a{counts, run_offsets, n, heights, widths};
-        answer(rle_shape::check_set(a, who, &err), err);
+        answer(rle_set::check_flat(a, who, &err), err);
         answer(rle_shape::check_hull_arguments(hull_offsets, xy, n_vertices, vertex_capacity, who, &err), err);
         MRCNN_REQUIRE(memspace == MRCNN_HOST || memspace == MRCNN_DEVICE, MRCNN_ERR_INVALID, "%s: unknown memspace %d", who, memspace);
         const bool dev = memspace == MRCNN_DEVICE;
-        if (!dev) {
-            answer(rle_draw::check_run_offsets(run_offsets, n, who, &err), err);
-            MRCNN_REQUIRE(counts || run_offsets[n] == run_offsets[0], MRCNN_ERR_INVALID, "%s: null counts", who);
-        }
+        if (!dev) StagedRle::check_host(counts, run_offsets, n, who);
         require_gpu();
         const size_t N = (size_t)n;
         if (n == 0) {
@@ -152,11 +122,11 @@ extern "C" int mrcnn_rle_convex_hull(const uint32_t* counts, const int64_t* run_
         }
         Stream st;
         hipStream_t s = st.s;
-        ShapeCall call;
+        ShapeCall call(a, dev, who);
         DevBuf t_off, t_areas, t_obb, t_xy;
         Carver wc;
         Drain drain{s};                                          // (declared behind the buffers: the stream drains before they are freed)
-        call.stage(s, a, dev, who);
+        call.stage(s, a, who);
         const ShapeSet& S = call.S;
         const bool big = call.max_w + 1 > HULL_LDS_COLUMNS;
         const size_t v = (size_t)S.vcols;

@@ -5,30 +5,23 @@
 #include <algorithm>
 
 #include "combine_rule.h"
-#include "rle_draw_host.h"
-#include "rle_morph_host.h"
 
 namespace mrcnn {
 namespace rle_combine {
 
-namespace {
-rle_morph::Set flat(const Set& s) { return rle_morph::Set{s.counts, s.run_offsets, s.n, s.heights, s.widths, nullptr, 0}; }
-}  // namespace
-
 int check_arguments(const Set& s, const uint32_t* out_counts, int64_t capacity, const int64_t* out_run_offsets, const char* who, std::string* err)
 {
-    if (s.n < 0) return bad(err, MRCNN_ERR_SHAPE, "%s: n %lld is negative", who, (long long)s.n);
-    if (s.n_groups < 0) return bad(err, MRCNN_ERR_SHAPE, "%s: n_groups %lld is negative", who, (long long)s.n_groups);
-    if (!s.run_offsets || !out_run_offsets || !s.group_offsets || ((!s.heights || !s.widths) && s.n > 0))
-        return bad(err, MRCNN_ERR_INVALID, "%s: null argument", who);
+    if (s.n >= 0 && s.n_groups < 0) return bad(err, MRCNN_ERR_SHAPE, "%s: n_groups %lld is negative", who, (long long)s.n_groups);      // (n is judged first)
+    int st = rle_set::check_flat_pointers(s, who, err);
+    if (st != MRCNN_OK) return st;
+    if (!out_run_offsets || !s.group_offsets) return bad(err, MRCNN_ERR_INVALID, "%s: null argument", who);
     if (capacity < 0 || (!out_counts && capacity != 0))
         return bad(err, MRCNN_ERR_INVALID, "%s: null out_counts with capacity %lld", who, (long long)capacity);
     if (!combine_known(s.op)) return bad(err, MRCNN_ERR_SHAPE, "%s: unknown op %d", who, s.op);
     if (s.n >= (1LL << 31) || s.n_groups >= (1LL << 31))
         return bad(err, MRCNN_ERR_SHAPE, "%s: %lld RLEs in %lld groups are too many", who, (long long)s.n, (long long)s.n_groups);
-    for (int64_t k = 0; k < s.n; ++k)
-        if (s.heights[k] < 1 || s.heights[k] > 32767 || s.widths[k] < 1 || s.widths[k] > 32767)
-            return bad(err, MRCNN_ERR_SHAPE, "%s: RLE %lld is %dx%d: height and width must lie in 1..32767", who, (long long)k, s.heights[k], s.widths[k]);
+    st = rle_set::check_flat_sides(s, who, err);
+    if (st != MRCNN_OK) return st;
     if (s.group_offsets[0] != 0) return bad(err, MRCNN_ERR_SHAPE, "%s: group_offsets[0] is %lld, not 0", who, (long long)s.group_offsets[0]);
     for (int64_t g = 0; g < s.n_groups; ++g) {
         if (s.group_offsets[g + 1] < s.group_offsets[g])
@@ -52,10 +45,6 @@ int check_arguments(const Set& s, const uint32_t* out_counts, int64_t capacity, 
     return MRCNN_OK;
 }
 
-int bad_sum(const Set& s, int64_t k, unsigned long long sum, const char* who, std::string* err) { return rle_morph::bad_sum(flat(s), k, sum, who, err); }
-
-int bad_capacity(long long need, long long capacity, const char* who, std::string* err) { return rle_morph::bad_capacity(need, capacity, who, err); }
-
 namespace {
 struct Encoded { std::vector<uint32_t> runs; uint32_t area; int32_t box[4]; };
 }  // namespace
@@ -65,7 +54,7 @@ int combine_host(const Set& s, uint32_t* out_counts, int64_t capacity, int64_t* 
     const char* who = "rle_combine_host";
     int st = check_arguments(s, out_counts, capacity, out_run_offsets, who, err);
     if (st != MRCNN_OK) return st;
-    st = rle_morph::check_sums(flat(s), who, err);
+    st = rle_set::check_sums(s, who, err);
     if (st != MRCNN_OK) return st;
 
     std::vector<Encoded> done((size_t)s.n_groups);
@@ -115,7 +104,7 @@ int combine_host(const Set& s, uint32_t* out_counts, int64_t capacity, int64_t* 
         if (areas) areas[g] = done[(size_t)g].area;
         if (bboxes_xywh) std::copy(done[(size_t)g].box, done[(size_t)g].box + 4, bboxes_xywh + 4 * g);
     }
-    if (need > (long long)capacity) return bad_capacity(need, (long long)capacity, who, err);
+    if (need > (long long)capacity) return rle_set::bad_runs_capacity(need, (long long)capacity, who, err);
     for (int64_t g = 0; g < s.n_groups; ++g) std::copy(done[(size_t)g].runs.begin(), done[(size_t)g].runs.end(), out_counts + out_run_offsets[g]);
     return MRCNN_OK;
 }

@@ -6,16 +6,14 @@
 #include <string>
 #include <vector>
 
-#include "ragged.h"
+#include "rle_set_host.h"
 
 namespace mrcnn {
 namespace rle_combine {
 
-// A flat RLE set as rle_morph_host.h takes it, and the groups over it: group g combines the RLEs members[group_offsets[g] ..
-// group_offsets[g+1]) in that order.  heights, widths, group_offsets and members are host arrays.
-struct Set {
-    const uint32_t* counts; const int64_t* run_offsets; int64_t n;
-    const int32_t* heights; const int32_t* widths;
+// A flat RLE set (rle_set_host.h) and the groups over it: group g combines the RLEs members[group_offsets[g] ..
+// group_offsets[g+1]) in that order.  group_offsets and members are host arrays.
+struct Set : rle_set::Flat {
     const int64_t* group_offsets; const int64_t* members; int64_t n_groups; int op;
 };
 
@@ -23,10 +21,6 @@ struct Set {
 // n_groups < 0, an unknown op, a side outside 1..32767, group_offsets that do not start at 0 or decrease, an empty group, a member
 // outside 0..n-1 or of another size than its group's first -> MRCNN_ERR_SHAPE (the message names the group and the member).
 int check_arguments(const Set& s, const uint32_t* out_counts, int64_t capacity, const int64_t* out_run_offsets, const char* who, std::string* err);
-// the answer to an RLE that does not sum to its plane, shared with the device entry, which finds the RLE on the device
-int bad_sum(const Set& s, int64_t k, unsigned long long sum, const char* who, std::string* err);
-// the answer to a capacity below the runs of the result
-int bad_capacity(long long need, long long capacity, const char* who, std::string* err);
 
 // The definition.  All pointers are host memory; nothing is written unless every RLE of the set sums to its plane, out_counts only when
 // all runs fit.

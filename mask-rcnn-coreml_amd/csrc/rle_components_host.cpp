@@ -5,22 +5,17 @@
 #include <algorithm>
 
 #include "components_rule.h"
-#include "rle_draw_host.h"
 
 namespace mrcnn {
 namespace rle_components {
 
 int check_set(const Set& s, const char* who, std::string* err)
 {
-    if (s.n < 0) return bad(err, MRCNN_ERR_SHAPE, "%s: n %lld is negative", who, (long long)s.n);
-    if (!s.run_offsets || ((!s.heights || !s.widths) && s.n > 0)) return bad(err, MRCNN_ERR_INVALID, "%s: null argument", who);
+    const int st = rle_set::check_flat_pointers(s, who, err);
+    if (st != MRCNN_OK) return st;
     if (s.connectivity != 4 && s.connectivity != 8) return bad(err, MRCNN_ERR_SHAPE, "%s: connectivity %d is neither 4 nor 8", who, s.connectivity);
     if (s.of != MRCNN_COMPONENTS_OF_ONES && s.of != MRCNN_COMPONENTS_OF_ZEROS) return bad(err, MRCNN_ERR_SHAPE, "%s: unknown of %d", who, s.of);
-    if (s.n >= (1LL << 31)) return bad(err, MRCNN_ERR_SHAPE, "%s: %lld RLEs are too many", who, (long long)s.n);
-    for (int64_t k = 0; k < s.n; ++k)
-        if (s.heights[k] < 1 || s.heights[k] > 32767 || s.widths[k] < 1 || s.widths[k] > 32767)
-            return bad(err, MRCNN_ERR_SHAPE, "%s: RLE %lld is %dx%d: height and width must lie in 1..32767", who, (long long)k, s.heights[k], s.widths[k]);
-    return MRCNN_OK;
+    return rle_set::check_flat_sides(s, who, err);
 }
 
 int check_measures(const Set& s, const Measures& m, const char* who, std::string* err)
@@ -48,12 +43,6 @@ int check_select(const Set& s, const Select& q, const char* who, std::string* er
     return MRCNN_OK;
 }
 
-int bad_sum(const Set& s, int64_t k, unsigned long long sum, const char* who, std::string* err)
-{
-    return bad(err, MRCNN_ERR_SHAPE, "%s: RLE %lld sums to %llu pixels, its %dx%d plane has %llu", who, (long long)k, sum, s.heights[k], s.widths[k],
-               (unsigned long long)s.heights[k] * (unsigned long long)s.widths[k]);
-}
-
 int bad_comp_capacity(long long need, long long capacity, const char* who, std::string* err)
 {
     return bad(err, MRCNN_ERR_SHAPE, "%s: the set has %lld components, the component arrays hold %lld: call again with comp_capacity >= %lld", who, need,
@@ -63,24 +52,6 @@ int bad_comp_capacity(long long need, long long capacity, const char* who, std::
 int bad_n_comps(long long given, long long found, const char* who, std::string* err)
 {
     return bad(err, MRCNN_ERR_SHAPE, "%s: keep holds n_comps = %lld entries, the set has %lld components", who, given, found);
-}
-
-int bad_capacity(long long need, long long capacity, const char* who, std::string* err)
-{
-    return bad(err, MRCNN_ERR_SHAPE, "%s: the set encodes to %lld runs, out_counts holds %lld: call again with capacity >= %lld", who, need, capacity, need);
-}
-
-int check_sums(const Set& s, const char* who, std::string* err)
-{
-    const int st = rle_draw::check_run_offsets(s.run_offsets, s.n, who, err);
-    if (st != MRCNN_OK) return st;
-    if (!s.counts && s.run_offsets[s.n] > s.run_offsets[0]) return bad(err, MRCNN_ERR_INVALID, "%s: null counts", who);
-    for (int64_t k = 0; k < s.n; ++k) {
-        uint64_t sum = 0;
-        for (int64_t j = s.run_offsets[k]; j < s.run_offsets[k + 1]; ++j) sum += s.counts[j];
-        if (sum != (uint64_t)s.heights[k] * (uint64_t)s.widths[k]) return bad_sum(s, k, sum, who, err);
-    }
-    return MRCNN_OK;
 }
 
 namespace {
@@ -170,7 +141,7 @@ int components_host(const Set& s, const Measures& m, std::string* err)
     const char* who = "rle_components_host";
     int st = check_measures(s, m, who, err);
     if (st != MRCNN_OK) return st;
-    st = check_sums(s, who, err);
+    st = rle_set::check_sums(s, who, err);
     if (st != MRCNN_OK) return st;
 
     std::vector<uint32_t> areas;
@@ -206,7 +177,7 @@ int select_host(const Set& s, const Select& q, std::string* err)
     const char* who = "rle_components_select_host";
     int st = check_select(s, q, who, err);
     if (st != MRCNN_OK) return st;
-    st = check_sums(s, who, err);
+    st = rle_set::check_sums(s, who, err);
     if (st != MRCNN_OK) return st;
 
     // pass 1 only counts, so that n_comps is judged before anything is written; pass 2 labels again: one plane at a time is held
@@ -259,7 +230,7 @@ int select_host(const Set& s, const Select& q, std::string* err)
         if (q.out_parent) q.out_parent[j] = parent[j];
     }
     *q.out_n = (int64_t)m;
-    if (need > (long long)q.capacity) return bad_capacity(need, (long long)q.capacity, who, err);
+    if (need > (long long)q.capacity) return rle_set::bad_runs_capacity(need, (long long)q.capacity, who, err);
     for (size_t j = 0; j < m; ++j) std::copy(done[j].runs.begin(), done[j].runs.end(), q.out_counts + q.out_run_offsets[j]);
     return MRCNN_OK;
 }

@@ -7,16 +7,14 @@
 #include <string>
 #include <vector>
 
-#include "ragged.h"
+#include "rle_set_host.h"
 
 namespace mrcnn {
 namespace rle_components {
 
-// A flat RLE set: RLE k is counts[run_offsets[k] .. run_offsets[k+1]) and encodes a heights[k] x widths[k] plane, column-major.
-// heights and widths are host arrays of n.
-struct Set {
-    const uint32_t* counts; const int64_t* run_offsets; int64_t n;
-    const int32_t* heights; const int32_t* widths; int connectivity; int of;
+// A flat RLE set (rle_set_host.h) and how it is cut: the connectivity, and whether the ones or the zeros are labelled.
+struct Set : rle_set::Flat {
+    int connectivity; int of;
 };
 // the outputs of mrcnn_rle_components
 struct Measures { int64_t* comp_offsets; uint32_t* comp_areas; int32_t* comp_bboxes_xywh; uint8_t* comp_flags; int64_t comp_capacity; };
@@ -32,12 +30,8 @@ int check_set(const Set& s, const char* who, std::string* err);
 int check_measures(const Set& s, const Measures& m, const char* who, std::string* err);
 int check_select(const Set& s, const Select& q, const char* who, std::string* err);
 // the answers both entries give in the same words
-int bad_sum(const Set& s, int64_t k, unsigned long long sum, const char* who, std::string* err);
 int bad_comp_capacity(long long need, long long capacity, const char* who, std::string* err);
 int bad_n_comps(long long given, long long found, const char* who, std::string* err);
-int bad_capacity(long long need, long long capacity, const char* who, std::string* err);
-// an RLE set in host memory: run_offsets do not decrease, every RLE sums to its plane (the lowest k that does not is named)
-int check_sums(const Set& s, const char* who, std::string* err);
 
 // The definitions.  All pointers are host memory.
 int components_host(const Set& s, const Measures& m, std::string* err);

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "draw_rule.h"
+#include "rle_set_host.h"
 
 namespace mrcnn {
 namespace rle_draw {
@@ -27,29 +28,25 @@ int check_render(int alpha, int stroke, const char* who, std::string* err)
     return MRCNN_OK;
 }
 
-int check_run_offsets(const int64_t* run_offsets, int64_t n, const char* who, std::string* err)
+int bad_sum(const Set& s, int64_t k, unsigned long long sum, const char* who, std::string* err)
 {
-    if (run_offsets[0] < 0) return bad(err, MRCNN_ERR_SHAPE, "%s: run_offsets[0] = %lld is negative", who, (long long)run_offsets[0]);
-    for (int64_t k = 0; k < n; ++k)
-        if (run_offsets[k + 1] < run_offsets[k]) return bad(err, MRCNN_ERR_SHAPE, "%s: run_offsets decrease at RLE %lld", who, (long long)k);
-    return MRCNN_OK;
+    const int b = (int)(k / s.slots);
+    return bad(err, MRCNN_ERR_SHAPE, "%s: RLE %lld (image %d, slot %d) sums to %llu pixels, its %dx%d plane has %llu", who, (long long)k, b, (int)(k % s.slots),
+               sum, s.heights[b], s.widths[b], (unsigned long long)s.heights[b] * (unsigned long long)s.widths[b]);
 }
 
 // every RLE sums to its plane, or nothing is drawn
 int check_sums(const Set& s, const char* who, std::string* err)
 {
     const int64_t n = (int64_t)s.n_images * s.slots;
-    const int st = check_run_offsets(s.run_offsets, n, who, err);
+    int st = rle_set::check_run_offsets(s.run_offsets, n, who, err);
+    if (st == MRCNN_OK) st = rle_set::check_counts(s.counts, s.run_offsets, n, who, err);
     if (st != MRCNN_OK) return st;
-    if (!s.counts && s.run_offsets[n] > s.run_offsets[0]) return bad(err, MRCNN_ERR_INVALID, "%s: null counts", who);
     for (int64_t k = 0; k < n; ++k) {
         const int b = (int)(k / s.slots);
-        const uint64_t want = (uint64_t)s.heights[b] * (uint64_t)s.widths[b];
         uint64_t sum = 0;
         for (int64_t j = s.run_offsets[k]; j < s.run_offsets[k + 1]; ++j) sum += s.counts[j];
-        if (sum != want)
-            return bad(err, MRCNN_ERR_SHAPE, "%s: RLE %lld (image %d, slot %d) sums to %llu pixels, its %dx%d plane has %llu", who, (long long)k, b,
-                       (int)(k % s.slots), (unsigned long long)sum, s.heights[b], s.widths[b], (unsigned long long)want);
+        if (sum != (uint64_t)s.heights[b] * (uint64_t)s.widths[b]) return bad_sum(s, k, sum, who, err);
     }
     return MRCNN_OK;
 }

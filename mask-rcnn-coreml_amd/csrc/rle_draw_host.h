@@ -1,4 +1,5 @@
-// rle_draw_host.h — drawing run-length masks, the host half: the argument checks the six entries share and the sequential code that DEFINES
+// rle_draw_host.h — drawing run-length masks, the host half: the argument checks the six entries share (the run offsets'
+// and the counts' rule is rle_set_host.h's) and the sequential code that DEFINES
 // the output of mrcnn_rle_decode, mrcnn_instance_map_rle and mrcnn_render_detections_rle (the _host entries).  Plain C++17: no HIP header,
 // builds with g++ alone.  The kernels of kernels_rle_draw.hip must give the same bytes.  The only float arithmetic is the pixel box
 // (draw_rule.h: products of a float and an int below 2^15, exact in double), shared with the kernels.
@@ -22,9 +23,10 @@ struct Set {
 // The output offsets are checked by ragged.h's check_offsets.
 int check_set(const Set& s, int max_slots, const char* who, std::string* err);
 int check_render(int alpha, int stroke, const char* who, std::string* err);
-// run_offsets (host memory, n_images*slots + 1 entries): non-negative and not decreasing (MRCNN_ERR_SHAPE naming the RLE).
-int check_run_offsets(const int64_t* run_offsets, int64_t n, const char* who, std::string* err);
-// an RLE set in host memory: check_run_offsets, then every RLE sums to its plane (MRCNN_ERR_SHAPE naming the RLE, its image and its slot)
+// the answer to an RLE that does not sum to its plane (MRCNN_ERR_SHAPE naming the RLE, its image and its slot), shared with the device
+// entries, which find the RLE on the device
+int bad_sum(const Set& s, int64_t k, unsigned long long sum, const char* who, std::string* err);
+// an RLE set in host memory: run_offsets and counts by rle_set_host.h's rule, then every RLE sums to its plane
 int check_sums(const Set& s, const char* who, std::string* err);
 
 // The definitions.  All pointers are host memory; nothing is written unless every RLE sums to its plane.

@@ -5,52 +5,29 @@
 #include <algorithm>
 
 #include "morph_rule.h"
-#include "rle_draw_host.h"
 
 namespace mrcnn {
 namespace rle_morph {
 
 int check_arguments(const Set& s, const uint32_t* out_counts, int64_t capacity, const int64_t* out_run_offsets, const char* who, std::string* err)
 {
-    if (s.n < 0) return bad(err, MRCNN_ERR_SHAPE, "%s: n %lld is negative", who, (long long)s.n);
-    if (!s.run_offsets || !out_run_offsets || ((!s.heights || !s.widths || !s.radii) && s.n > 0)) return bad(err, MRCNN_ERR_INVALID, "%s: null argument", who);
+    int st = rle_set::check_flat_pointers(s, who, err);
+    if (st != MRCNN_OK) return st;
+    if (!out_run_offsets || (!s.radii && s.n > 0)) return bad(err, MRCNN_ERR_INVALID, "%s: null argument", who);
     if (capacity < 0 || (!out_counts && capacity != 0))
         return bad(err, MRCNN_ERR_INVALID, "%s: null out_counts with capacity %lld", who, (long long)capacity);
     if (s.op != MRCNN_MORPH_ERODE && s.op != MRCNN_MORPH_DILATE && s.op != MRCNN_MORPH_BOUNDARY)
         return bad(err, MRCNN_ERR_SHAPE, "%s: unknown op %d", who, s.op);
-    if (s.n >= (1LL << 31)) return bad(err, MRCNN_ERR_SHAPE, "%s: %lld RLEs are too many", who, (long long)s.n);
-    for (int64_t k = 0; k < s.n; ++k) {
-        if (s.heights[k] < 1 || s.heights[k] > 32767 || s.widths[k] < 1 || s.widths[k] > 32767)
-            return bad(err, MRCNN_ERR_SHAPE, "%s: RLE %lld is %dx%d: height and width must lie in 1..32767", who, (long long)k, s.heights[k], s.widths[k]);
-        if (s.radii[k] < 0 || s.radii[k] > MRCNN_MORPH_MAX_RADIUS)
-            return bad(err, MRCNN_ERR_SHAPE, "%s: RLE %lld has radius %d: a radius must lie in 0..MRCNN_MORPH_MAX_RADIUS = %d", who, (long long)k, s.radii[k],
-                       MRCNN_MORPH_MAX_RADIUS);
-    }
-    return MRCNN_OK;
-}
-
-int bad_sum(const Set& s, int64_t k, unsigned long long sum, const char* who, std::string* err)
-{
-    return bad(err, MRCNN_ERR_SHAPE, "%s: RLE %lld sums to %llu pixels, its %dx%d plane has %llu", who, (long long)k, sum, s.heights[k], s.widths[k],
-               (unsigned long long)s.heights[k] * (unsigned long long)s.widths[k]);
-}
-
-int bad_capacity(long long need, long long capacity, const char* who, std::string* err)
-{
-    return bad(err, MRCNN_ERR_SHAPE, "%s: the set encodes to %lld runs, out_counts holds %lld: call again with capacity >= %lld", who, need, capacity, need);
-}
-
-int check_sums(const Set& s, const char* who, std::string* err)
-{
-    const int st = rle_draw::check_run_offsets(s.run_offsets, s.n, who, err);
-    if (st != MRCNN_OK) return st;
-    if (!s.counts && s.run_offsets[s.n] > s.run_offsets[0]) return bad(err, MRCNN_ERR_INVALID, "%s: null counts", who);
-    for (int64_t k = 0; k < s.n; ++k) {
-        uint64_t sum = 0;
-        for (int64_t j = s.run_offsets[k]; j < s.run_offsets[k + 1]; ++j) sum += s.counts[j];
-        if (sum != (uint64_t)s.heights[k] * (uint64_t)s.widths[k]) return bad_sum(s, k, sum, who, err);
-    }
-    return MRCNN_OK;
+    // The lowest RLE that fails is named, its sides before its radius: so the sides are judged as far as the first bad radius, k.
+    const bool countable = s.n < (1LL << 31);                    // (too many RLEs are refused before any is read)
+    int64_t k = 0;
+    while (countable && k < s.n && s.radii[k] >= 0 && s.radii[k] <= MRCNN_MORPH_MAX_RADIUS) ++k;
+    rle_set::Flat judged = s;
+    if (countable && k < s.n) judged.n = k + 1;
+    st = rle_set::check_flat_sides(judged, who, err);
+    if (st != MRCNN_OK || k == s.n) return st;
+    return bad(err, MRCNN_ERR_SHAPE, "%s: RLE %lld has radius %d: a radius must lie in 0..MRCNN_MORPH_MAX_RADIUS = %d", who, (long long)k, s.radii[k],
+               MRCNN_MORPH_MAX_RADIUS);
 }
 
 namespace {
@@ -82,7 +59,7 @@ int morph_host(const Set& s, uint32_t* out_counts, int64_t capacity, int64_t* ou
     const char* who = "rle_morph_host";
     int st = check_arguments(s, out_counts, capacity, out_run_offsets, who, err);
     if (st != MRCNN_OK) return st;
-    st = check_sums(s, who, err);
+    st = rle_set::check_sums(s, who, err);
     if (st != MRCNN_OK) return st;
 
     std::vector<Encoded> done((size_t)s.n);
@@ -130,7 +107,7 @@ int morph_host(const Set& s, uint32_t* out_counts, int64_t capacity, int64_t* ou
         if (areas) areas[k] = done[(size_t)k].area;
         if (bboxes_xywh) std::copy(done[(size_t)k].box, done[(size_t)k].box + 4, bboxes_xywh + 4 * k);
     }
-    if (need > (long long)capacity) return bad_capacity(need, (long long)capacity, who, err);
+    if (need > (long long)capacity) return rle_set::bad_runs_capacity(need, (long long)capacity, who, err);
     for (int64_t k = 0; k < s.n; ++k) std::copy(done[(size_t)k].runs.begin(), done[(size_t)k].runs.end(), out_counts + out_run_offsets[k]);
     return MRCNN_OK;
 }

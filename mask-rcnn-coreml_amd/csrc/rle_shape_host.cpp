@@ -4,22 +4,10 @@
 
 #include <algorithm>
 
-#include "rle_draw_host.h"
 #include "shape_rule.h"
 
 namespace mrcnn {
 namespace rle_shape {
-
-int check_set(const Set& s, const char* who, std::string* err)
-{
-    if (s.n < 0) return bad(err, MRCNN_ERR_SHAPE, "%s: n %lld is negative", who, (long long)s.n);
-    if (!s.run_offsets || ((!s.heights || !s.widths) && s.n > 0)) return bad(err, MRCNN_ERR_INVALID, "%s: null argument", who);
-    if (s.n >= (1LL << 31)) return bad(err, MRCNN_ERR_SHAPE, "%s: %lld RLEs are too many", who, (long long)s.n);
-    for (int64_t k = 0; k < s.n; ++k)
-        if (s.heights[k] < 1 || s.heights[k] > 32767 || s.widths[k] < 1 || s.widths[k] > 32767)
-            return bad(err, MRCNN_ERR_SHAPE, "%s: RLE %lld is %dx%d: height and width must lie in 1..32767", who, (long long)k, s.heights[k], s.widths[k]);
-    return MRCNN_OK;
-}
 
 int check_hull_arguments(const int64_t* hull_offsets, const int32_t* xy, const int64_t* n_vertices, int64_t vertex_capacity, const char* who,
                          std::string* err)
@@ -30,28 +18,9 @@ int check_hull_arguments(const int64_t* hull_offsets, const int32_t* xy, const i
     return MRCNN_OK;
 }
 
-int bad_sum(const Set& s, int64_t k, unsigned long long sum, const char* who, std::string* err)
-{
-    return bad(err, MRCNN_ERR_SHAPE, "%s: RLE %lld sums to %llu pixels, its %dx%d plane has %llu", who, (long long)k, sum, s.heights[k], s.widths[k],
-               (unsigned long long)s.heights[k] * (unsigned long long)s.widths[k]);
-}
-
 int bad_capacity(long long need, long long capacity, const char* who, std::string* err)
 {
     return bad(err, MRCNN_ERR_SHAPE, "%s: the hulls have %lld vertices, xy holds %lld: call again with vertex_capacity >= %lld", who, need, capacity, need);
-}
-
-int check_sums(const Set& s, const char* who, std::string* err)
-{
-    const int st = rle_draw::check_run_offsets(s.run_offsets, s.n, who, err);
-    if (st != MRCNN_OK) return st;
-    if (!s.counts && s.run_offsets[s.n] > s.run_offsets[0]) return bad(err, MRCNN_ERR_INVALID, "%s: null counts", who);
-    for (int64_t k = 0; k < s.n; ++k) {
-        uint64_t sum = 0;
-        for (int64_t j = s.run_offsets[k]; j < s.run_offsets[k + 1]; ++j) sum += s.counts[j];
-        if (sum != (uint64_t)s.heights[k] * (uint64_t)s.widths[k]) return bad_sum(s, k, sum, who, err);
-    }
-    return MRCNN_OK;
 }
 
 namespace {
@@ -107,10 +76,10 @@ int64_t differ(const Piece* A, size_t na, const Piece* B, size_t nb)
 int measure_host(const Set& s, int64_t* measures, std::string* err)
 {
     const char* who = "rle_measure_host";
-    int st = check_set(s, who, err);
+    int st = rle_set::check_flat(s, who, err);
     if (st != MRCNN_OK) return st;
     if (!measures && s.n > 0) return bad(err, MRCNN_ERR_INVALID, "%s: null measures", who);
-    st = check_sums(s, who, err);
+    st = rle_set::check_sums(s, who, err);
     if (st != MRCNN_OK) return st;
     Pieces P;
     for (int64_t k = 0; k < s.n; ++k) {
@@ -138,11 +107,11 @@ int convex_hull_host(const Set& s, int64_t* hull_offsets, int64_t* hull_areas2, 
                      std::string* err)
 {
     const char* who = "rle_convex_hull_host";
-    int st = check_set(s, who, err);
+    int st = rle_set::check_flat(s, who, err);
     if (st != MRCNN_OK) return st;
     st = check_hull_arguments(hull_offsets, xy, n_vertices, vertex_capacity, who, err);
     if (st != MRCNN_OK) return st;
-    st = check_sums(s, who, err);
+    st = rle_set::check_sums(s, who, err);
     if (st != MRCNN_OK) return st;
 
     Pieces P;

@@ -1,7 +1,8 @@
 // polygons_check.cpp — the host definition of mrcnn_rle_to_polygons (csrc/polygons_host.cpp) under the sanitizers, as a program of its own:
 //
 //   g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -I mask-rcnn-coreml_amd/csrc tools/polygons_check.cpp
-//       mask-rcnn-coreml_amd/csrc/polygons_host.cpp mask-rcnn-coreml_amd/csrc/rle_draw_host.cpp -o polygons_check       (one command line)
+//       mask-rcnn-coreml_amd/csrc/polygons_host.cpp mask-rcnn-coreml_amd/csrc/rle_draw_host.cpp mask-rcnn-coreml_amd/csrc/rle_set_host.cpp
+//       -o polygons_check                                                                            (one command line)
 //   ./polygons_check
 //
 // Host code only: no GPU, no HIP, no Python.  3 000 seeded sets — one to three images of 1x1 .. 17x17, one to four slots, random runs

@@ -2,7 +2,8 @@
 // its own:
 //
 //   g++ -std=c++17 -g -O1 -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -I mask-rcnn-coreml_amd/csrc
-//       tools/rle_draw_check.cpp mask-rcnn-coreml_amd/csrc/rle_draw_host.cpp -o rle_draw_check       (one command line)
+//       tools/rle_draw_check.cpp mask-rcnn-coreml_amd/csrc/rle_draw_host.cpp mask-rcnn-coreml_amd/csrc/rle_set_host.cpp -o rle_draw_check
+//                                                                                                    (one command line)
 //   ./rle_draw_check
 //
 // Host code only: no GPU, no HIP, no Python.  Seeded scenes — one to three images of 1x1 .. 40x40, 0..5 slots, planes of noise encoded
