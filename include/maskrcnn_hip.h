@@ -1194,8 +1194,9 @@ MRCNN_API int mrcnn_rle_components_select_host(const uint32_t* counts, const int
  * group and the member) -> MRCNN_ERR_SHAPE.  An RLE of the set, referenced or not, that does not sum to its h*w -> MRCNN_ERR_SHAPE,
  * the message starts "rle_combine:" / "rle_combine_host:" and names the lowest such k, nothing is written.  No gfx950 device ->
  * MRCNN_ERR_HIP from the device entry (no CPU fallback).
- * Not here: a vote (set in at least m of K members), combining across planes of different sizes, group tables that live on the
- * device, the complement (it is XOR with a full mask, and a host can write the full mask [0, h*w]). */
+ * Not here: a vote (set in at least m of K members), combining across planes of different sizes (mrcnn_rle_transform brings them
+ * into one frame first: a = 1, d = 1, b = (-x0, -y0); rle_place in Python), group tables that live on the device, the complement (it
+ * is XOR with a full mask, and a host can write the full mask [0, h*w]). */
 #define MRCNN_RLE_OR 0
 #define MRCNN_RLE_AND 1
 #define MRCNN_RLE_XOR 2
@@ -1206,6 +1207,61 @@ MRCNN_API int mrcnn_rle_combine(const uint32_t* counts, const int64_t* run_offse
 MRCNN_API int mrcnn_rle_combine_host(const uint32_t* counts, const int64_t* run_offsets, int64_t n, const int32_t* heights,
                                      const int32_t* widths, const int64_t* group_offsets, const int64_t* members, int64_t n_groups, int op,
                                      uint32_t* out_counts, int64_t capacity, int64_t* out_run_offsets, uint32_t* areas, int32_t* bboxes_xywh);
+
+/* ---- moving run-length masks: crop, place, flip, rotate, resize (csrc/api_rle_transform.hip, kernels_rle_transform.hip) ---------------
+ * A mask brought to another pixel grid: RLE in, RLE out, no dense plane.  The set is flat as mrcnn_rle_morph takes it: RLE k is
+ * counts[run_offsets[k] .. run_offsets[k+1]) and encodes a heights[k] x widths[k] plane P (sides 1..32767); heights and widths are
+ * HOST arrays of n.  Zero-length runs are allowed anywhere.
+ * Per RLE the caller gives an output plane and one record, all three HOST arrays in both memory spaces, like heights:
+ *   out_heights[k], out_widths[k]     sides 1..32767
+ *   xf[k] = [flags, ax, bx, dx, ay, by, dy, 0]     eight int64
+ * The rule (csrc/transform_rule.h), for the output pixel (X, Y), column X and row Y:
+ *   u = floor((ax*X + bx) / dx)        v = floor((ay*Y + by) / dy)        (floor towards -infinity, also for negatives)
+ *   (sx, sy) = (u, v)                  or (v, u) when flags has MRCNN_XF_TRANSPOSE
+ *   Out[Y, X] = P[sy, sx] if 0 <= sx < w and 0 <= sy < h, else 0
+ * Limits: 1 <= dx, dy <= 2^31-1, 1 <= |ax|, |ay| <= 2^31-1, |bx|, |by| <= 2^46 — every product then stays inside int64.  Bits of
+ * flags other than bit 0 must be 0; word 7 must be 0.  What the one rule covers:
+ *   crop / window at (x0, y0)            a = 1, d = 1, b = (x0, y0); the window may reach outside the plane, and that part is 0
+ *   place / pad / translate              a = 1, d = 1, b = (-x0, -y0) into a larger frame
+ *   horizontal or vertical flip          a = -1, b = w-1 or h-1
+ *   transpose, the four rotations        MRCNN_XF_TRANSPOSE with flips: the eight symmetries of the rectangle
+ *   nearest resize, pixel-centre rule    src = floor((2X+1)*w / (2W')):  a = 2w, b = w, d = 2W'
+ *   nearest resize, floor rule           src = floor(X*w / W'):  a = w, b = 0, d = W'
+ *   any of these combined                one record: "crop this window and deliver it at half size, mirrored"
+ * Outputs: one canonical RLE per input over its output plane, exactly as mrcnn_rle_morph writes them (counts[0] may be 0, no other
+ * run is, runs continue across column ends, an empty plane is the single run [H'*W']).  out_run_offsets has n + 1 entries and is
+ * always written; areas (n) and bboxes_xywh (n, 4) are optional (NULL); the out_counts / capacity protocol with its size query is
+ * mrcnn_rle_morph's: out_counts is written only when all runs fit, a smaller capacity -> MRCNN_ERR_SHAPE, the message names the
+ * capacity needed (= out_run_offsets[n]); capacity = 0 with out_counts = NULL is the size query.  memspace holds for counts,
+ * run_offsets and the four outputs; the outputs must not overlap the inputs.  n = 0 is legal: out_run_offsets[0] = 0.
+ * mrcnn_rle_transform_host is the definition: sequential plain C++, no GPU, host pointers; one RLE at a time it decodes the plane,
+ * evaluates the forward rule above for every pixel of the output plane, and encodes.  mrcnn_rle_transform equals it bit for bit in
+ * every output array and never builds a plane: the prefix table of the runs and mrcnn_rle_morph's tight boxes (with the one flag that
+ * refuses a wrong total) are read back once; the host takes the preimage of every tight box under its record, clipped to the output
+ * plane — the range of X with u(X) in [a, b) is [ceil((a*dx - bx)/ax), ceil((b*dx - bx)/ax)) for ax > 0 and
+ * [floor((bx - b*dx)/(-ax)) + 1, floor((bx - a*dx)/(-ax)) + 1) for ax < 0 — and sizes a packed bit box per RLE from it: scratch that
+ * follows the masks, not the images.  One thread per column of a box fills its own column of words, kept in LDS, 1024 rows per pass:
+ * for a plain record it walks the runs of source column u(X) and sets the Y range of every interval of ones by the same inverse, a
+ * run costs O(1) whatever the scale; for a transposed record column X is a source ROW, and the thread asks the prefix table one point
+ * query (a binary search) per distinct source column along Y.  The encoder of mrcnn_masks_rle_source runs on the bits.  A thread
+ * owns its column: nothing is atomic and the result does not depend on the order of execution.  The number of launches depends on
+ * neither n nor the records.  A call whose boxes together pass MRCNN_XF_MAX_BOX_WORDS words of bits -> MRCNN_ERR_SHAPE naming the
+ * number (device entry only): split the set.
+ * Errors, answered before a device is looked for, nothing written: null pointer, unknown memspace -> MRCNN_ERR_INVALID; n < 0, a
+ * side of a source or an output plane outside 1..32767, run_offsets that decrease, a record with an unknown flag bit, a coefficient
+ * outside its limits or a non-zero word 7 (the message names the RLE) -> MRCNN_ERR_SHAPE.  An RLE that does not sum to its h*w ->
+ * MRCNN_ERR_SHAPE, the message starts "rle_transform:" / "rle_transform_host:" and names the lowest such k, nothing is written.  No
+ * gfx950 device -> MRCNN_ERR_HIP from the device entry (no CPU fallback).
+ * Not here: rotation by other angles and general affine or projective warps, anti-aliased or area-weighted resampling (nearest
+ * only), mapping of detection boxes, composing two records into one. */
+#define MRCNN_XF_TRANSPOSE 1
+#define MRCNN_XF_MAX_BOX_WORDS (1LL << 30)
+MRCNN_API int mrcnn_rle_transform(const uint32_t* counts, const int64_t* run_offsets, int64_t n, const int32_t* heights, const int32_t* widths,
+                                  const int32_t* out_heights, const int32_t* out_widths, const int64_t* xf, int memspace,
+                                  uint32_t* out_counts, int64_t capacity, int64_t* out_run_offsets, uint32_t* areas, int32_t* bboxes_xywh);
+MRCNN_API int mrcnn_rle_transform_host(const uint32_t* counts, const int64_t* run_offsets, int64_t n, const int32_t* heights,
+                                       const int32_t* widths, const int32_t* out_heights, const int32_t* out_widths, const int64_t* xf,
+                                       uint32_t* out_counts, int64_t capacity, int64_t* out_run_offsets, uint32_t* areas, int32_t* bboxes_xywh);
 
 /* ---- measuring run-length masks: moments, perimeter, convex hull, oriented box (csrc/api_rle_shape.hip, kernels_rle_shape.hip) --------
  * The shape of every mask of a flat RLE set, from the runs, no dense plane.  The set is flat as mrcnn_rle_morph takes it: RLE k is

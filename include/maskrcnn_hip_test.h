@@ -301,6 +301,12 @@ MRCNN_API int mrcnn_jpeg_last_stage_ms(float* host_ms, float* device_ms);
 MRCNN_API int mrcnn_jpeg_coefficients(const mrcnn_jpeg* files, int batch, int entropy, int unit_bytes, int max_rounds, int16_t* coef,
                                       int64_t capacity, int64_t* block0, int32_t* stats);
 
+/* The inverse that mrcnn_rle_transform's device entry works from (csrc/transform_rule.h), evaluated on the host, no GPU: [*lo, *hi) =
+ * every integer X with a <= floor((A*X + B) / D) < b, not clipped; empty as *lo >= *hi.  a <= b within +-32768, A, B and D within the
+ * limits of a record (else MRCNN_ERR_SHAPE); null lo or hi -> MRCNN_ERR_INVALID.  tests/test_rle_transform_host.py pins the closed form
+ * against brute force with it. */
+MRCNN_API int mrcnn_test_xf_preimage(int64_t a, int64_t b, int64_t A, int64_t B, int64_t D, int64_t* lo, int64_t* hi);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ HOST, DEVICE = 0, 1
 MORPH_ERODE, MORPH_DILATE, MORPH_BOUNDARY, MORPH_MAX_RADIUS = 0, 1, 2, 1024
 COMPONENTS_OF_ZEROS, COMPONENTS_OF_ONES, COMPONENTS_MERGE, COMPONENTS_SPLIT = 0, 1, 0, 1
 RLE_OR, RLE_AND, RLE_XOR, RLE_DIFF = 0, 1, 2, 3
+XF_TRANSPOSE, XF_MAX_BOX_WORDS = 1, 1 << 30
 PARAM_INT, PARAM_DOUBLE, PARAM_STRING = 0, 1, 2
 MODEL_MASKRCNN, MODEL_CLASSIFIER, MODEL_MASK = 0, 1, 2
 
@@ -57,6 +58,7 @@ EXPORTED_SYMBOLS = [
     "mrcnn_rle_morph", "mrcnn_rle_morph_host", "mrcnn_boundary_radius",
     "mrcnn_rle_components", "mrcnn_rle_components_host", "mrcnn_rle_components_select", "mrcnn_rle_components_select_host",
     "mrcnn_rle_combine", "mrcnn_rle_combine_host",
+    "mrcnn_rle_transform", "mrcnn_rle_transform_host",
     "mrcnn_rle_measure", "mrcnn_rle_measure_host", "mrcnn_rle_convex_hull", "mrcnn_rle_convex_hull_host",
 ]
 # declared in include/maskrcnn_hip_test.h (test / measurement entry points of the same library)
@@ -65,7 +67,7 @@ TEST_SYMBOLS = [
     "mrcnn_model_conv_profile_shapes", "mrcnn_conv2d_nhwc", "mrcnn_debug_set", "mrcnn_bottleneck_nhwc", "mrcnn_bench_mfma_probe", "mrcnn_model_conv_profile_group", "mrcnn_bottleneck_first_nhwc", "mrcnn_bottleneck_stage_nhwc", "mrcnn_model_conv_profile_bytes",
     "mrcnn_jpeg_last_stage_ms", "mrcnn_jpeg_coefficients", "mrcnn_test_last_range_flag", "mrcnn_classifier_rows", "mrcnn_test_roi_align_nhwc_batch", "mrcnn_conv_chain_nhwc",
     "mrcnn_test_conv_form_nhwc", "mrcnn_test_chain_stream_image", "mrcnn_test_proposals_batch", "mrcnn_test_detections_batch",
-    "mrcnn_test_mask_select_batch",
+    "mrcnn_test_mask_select_batch", "mrcnn_test_xf_preimage",
 ]
 
 
@@ -242,6 +244,9 @@ def lib():
     _groups = [vp, vp, C.c_int64, C.c_int]                        # group_offsets, members, n_groups, op
     L.mrcnn_rle_combine.argtypes = [vp, vp, C.c_int64, vp, vp] + _groups + [C.c_int] + _morph
     L.mrcnn_rle_combine_host.argtypes = [vp, vp, C.c_int64, vp, vp] + _groups + _morph
+    _xf = [vp, vp, vp]                                            # out_heights, out_widths, xf
+    L.mrcnn_rle_transform.argtypes = [vp, vp, C.c_int64, vp, vp] + _xf + [C.c_int] + _morph
+    L.mrcnn_rle_transform_host.argtypes = [vp, vp, C.c_int64, vp, vp] + _xf + _morph
     _hull = [vp, vp, vp, vp, i64p, C.c_int64]                     # hull_offsets, hull_areas2, obb, xy, n_vertices, vertex_capacity
     L.mrcnn_rle_measure.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int, vp]
     L.mrcnn_rle_measure_host.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
@@ -332,6 +337,7 @@ def lib():
     L.mrcnn_test_proposals_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_float, vp, C.c_int64, vp]
     L.mrcnn_test_detections_batch.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_float, C.c_float, vp, C.c_int64]
     L.mrcnn_test_mask_select_batch.argtypes = [C.POINTER(MaskSelect)]
+    L.mrcnn_test_xf_preimage.argtypes = [C.c_int64] * 5 + [i64p, i64p]
     _lib = L
     return L
 

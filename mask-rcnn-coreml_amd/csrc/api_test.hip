@@ -888,3 +888,19 @@ extern "C" int mrcnn_model_conv_profile_shapes(mrcnn_model* model, mrcnn_conv_sh
         }
     });
 }
+
+// The inverse mrcnn_rle_transform's device entry works from (transform_rule.h's xf_preimage), on the host: the closed form can be pinned
+// against brute force without a GPU (tests/test_rle_transform_host.py).
+extern "C" int mrcnn_test_xf_preimage(int64_t a, int64_t b, int64_t A, int64_t B, int64_t D, int64_t* lo, int64_t* hi)
+{
+    return guarded([&] {
+        MRCNN_REQUIRE(lo && hi, MRCNN_ERR_INVALID, "test_xf_preimage: null output");
+        MRCNN_REQUIRE(a <= b && a >= -32768 && b <= 32768, MRCNN_ERR_SHAPE, "test_xf_preimage: the source range [%lld, %lld) must be ordered and lie within +-32768",
+                      (long long)a, (long long)b);
+        MRCNN_REQUIRE(xf_axis_known(A, B, D), MRCNN_ERR_SHAPE, "test_xf_preimage: A, B, D = %lld, %lld, %lld: 1 <= |A|, D <= 2^31-1 and |B| <= 2^46 expected",
+                      (long long)A, (long long)B, (long long)D);
+        long long l, h;
+        xf_preimage(XfAxis{(long long)A, (long long)B, (long long)D}, a, b, &l, &h);
+        *lo = l; *hi = h;
+    });
+}

@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "morph_rule.h"
+#include "transform_rule.h"
 
 namespace mrcnn {
 
@@ -575,6 +576,23 @@ struct CombineJob {
 };
 // the fold of every group's members into its bit box; rle_morph_count_forward / rle_morph_write_forward encode the boxes (MorphJob.vb = bits)
 void rle_combine_forward(hipStream_t s, const CombineJob& job);
+
+// ================================================================================================
+// Moving run-length masks to another pixel grid (kernels_rle_transform.hip; the rule is transform_rule.h).  All tables are device arrays.
+// ================================================================================================
+constexpr int XF_PASS_WORDS = 32;                                // word rows a thread keeps in LDS: 1024 rows of a box per pass
+// the source of one output RLE: its runs, its plane, the tight box of its set pixels (an empty mask: (0, 0, 0, 0)) and the record
+struct XfSource { long long r0; int nruns, h, w, pad; MorphBox tight; XfMap map; };
+struct XfJob {
+    const MorphRec* rec; int n;       // one per RLE, laid out as mrcnn_rle_morph lays its bit boxes out: work, words, word0, col0, and h and w of the OUTPUT plane
+    const XfSource* src;              // n
+    long long cols;                   // the columns of all work boxes
+    const uint32_t* counts;
+    const uint32_t* pre_b;            // rle_prefix_forward's B, indexed like counts
+    uint32_t* bits;                   // the bit boxes: every word of them is written
+};
+// every source read through its record into its bit box; rle_morph_count_forward / rle_morph_write_forward encode the boxes (MorphJob.vb = bits)
+void rle_transform_forward(hipStream_t s, const XfJob& job);
 
 // ================================================================================================
 // Connected components of run-length masks (kernels_rle_components.hip; the rule is components_rule.h).  All tables are device arrays.

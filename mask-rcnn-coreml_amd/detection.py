@@ -1076,8 +1076,8 @@ def rle_combine(rle, sizes, groups, op, device=None):
     twice) or "diff" (in the first and in none of the others).  Returns (rle, areas, bboxes), one canonical RLE per group: a pair in
     the same memory space for a pair (a resident pair stays resident), else a list of rows {"size", "counts"}; with the set pixels
     and their tight boxes x, y, w, h per group.  The result feeds rle_to_polygons, instance_map_rle, rle_decode_planes and coco_eval
-    as it is.  Not here: votes (at least m of K), planes of different sizes in one group, group tables on the device, the complement
-    (XOR with the full mask [0, h*w])."""
+    as it is.  Not here: votes (at least m of K), planes of different sizes in one group (rle_place brings them into one frame
+    first), group tables on the device, the complement (XOR with the full mask [0, h*w])."""
     return _rle_combine(False, rle, sizes, groups, op, device)
 
 
@@ -1218,6 +1218,212 @@ def rle_disjoint(det_src, rle, sizes=None, min_score: float = 0.0, device=None):
 def rle_disjoint_host(det_src, rle, sizes=None, min_score: float = 0.0):
     """The definition of rle_disjoint: the sequential host code (``mrcnn_rle_combine_host``), no GPU; numpy out."""
     return _rle_disjoint(True, det_src, rle, sizes, min_score, None)
+
+
+# ---- moving run-length masks to another pixel grid (mrcnn_rle_transform) ------------------------------------------------------------------
+XF_TRANSPOSE = _lib.XF_TRANSPOSE
+
+
+def _transform_flat(host_definition, space, counts, offs, hs, ws, ohs, ows, xf):
+    """mrcnn_rle_transform(_host) on a flat set of ``space`` — counts, run_offsets (n + 1), host int32 arrays hs, ws, ohs, ows of n and
+    the host int64 records xf (n, 8) -> (counts, run_offsets, areas (n), bboxes (n, 4)) in the same space.  A first attempt is sized
+    from the input's runs; if the result needs more, one more call with the capacity the library reported."""
+    n = int(offs.shape[0]) - 1
+    ptr = space.ptr
+    out_offs, areas, bboxes = space.new(n + 1, np.int64, zero=True), space.new(max(1, n), np.uint32), space.new((max(1, n), 4), np.int32)
+    entry = _lib.lib().mrcnn_rle_transform_host if host_definition else _lib.lib().mrcnn_rle_transform
+    head = (ptr(counts), ptr(offs), n, hs.ctypes.data, ws.ctypes.data, ohs.ctypes.data, ows.ctypes.data, xf.ctypes.data) + (() if host_definition else (space.code,))
+    capacity = int(counts.shape[0]) + 2 * n + 2
+    for _ in range(2):
+        out = space.new(max(1, capacity), np.uint32)
+        st = entry(*head, ptr(out), capacity, ptr(out_offs), ptr(areas), ptr(bboxes))
+        if st != 4 or int(out_offs[n]) <= capacity:
+            break
+        capacity = int(out_offs[n])
+    _lib.check(st)
+    return out[:int(out_offs[n])], out_offs, areas[:n], bboxes[:n]
+
+
+def _per_rle(name, what, a, width, B, slots, dtype=np.int64):
+    """``a`` — one row of ``width`` whole numbers, one per size or one per RLE — as an (n, width) array, one row per RLE"""
+    n = B * slots
+    v = np.asarray(a.cpu().numpy() if hasattr(a, "is_cuda") else a, dtype=np.float64)
+    if v.size == 0 or v.size % width or v.size // width not in (1, B, n):
+        raise ValueError(f"{name}: {what} holds {v.size} numbers for {n} RLEs of {B} sizes: {width} each for all, per size or per RLE expected")
+    if (v != np.rint(v)).any() or (np.abs(v) > 2.0 ** 62).any():
+        raise ValueError(f"{name}: {what} holds whole numbers")
+    v = v.reshape(-1, width)
+    v = np.repeat(v, slots, 0) if (len(v) == B and B != n) else np.broadcast_to(v, (n, width))
+    return np.ascontiguousarray(v).astype(dtype)
+
+
+def _xf_call(host_definition, name, rle, sizes, device, make):
+    """One transform call: ``make(hs, ws, per)`` -> (xf (n, 8), out sizes (n, 2) as (h, w)) from the planes' sides per RLE, with
+    per(what, a, width) = _per_rle of this set.  Returns (rle, areas, boxes, sizes) in the form ``rle`` came in."""
+    pair, space, counts, offs, B, slots, hs, ws = _combine_set(name, host_definition, rle, sizes, device)
+    n = B * slots
+    xf, osz = np.zeros((1, 8), np.int64), np.ones((1, 2), np.int64)          # (no RLE: nothing is read)
+    if n:
+        xf, osz = make(hs.astype(np.int64), ws.astype(np.int64), lambda what, a, width: _per_rle(name, what, a, width, B, slots))
+        xf, osz = np.ascontiguousarray(xf, dtype=np.int64).reshape(n, 8), np.asarray(osz, dtype=np.int64).reshape(n, 2)
+    if n and ((osz < 1).any() or (osz > 32767).any()):
+        raise ValueError(f"{name}: an output plane of {osz[((osz < 1) | (osz > 32767)).any(1)][0].tolist()}: height and width must lie in 1..32767")
+    ohs, ows = np.ascontiguousarray(osz[:, 0], dtype=np.int32), np.ascontiguousarray(osz[:, 1], dtype=np.int32)
+    out, out_offs, areas, bboxes = _transform_flat(host_definition, space, counts, offs, hs, ws, ohs, ows, xf)
+    per = [(int(h), int(w)) for h, w in zip(ohs[:n], ows[:n])]
+    uniform = slots > 0 and all(per[b * slots + i] == per[b * slots] for b in range(B) for i in range(slots))
+    new_sizes = [per[b * slots] for b in range(B)] if uniform else per      # per image where every RLE of an image got the same plane
+    if pair:
+        return (out, out_offs), areas, bboxes, new_sizes
+    host = lambda a: a if space.on_host else a.cpu().numpy()
+    c, o = host(out).view(np.uint32), host(out_offs)
+    rows = [[{"size": list(per[b * slots + i]), "counts": c[int(o[b * slots + i]):int(o[b * slots + i + 1])]} for i in range(slots)] for b in range(B)]
+    return rows, host(areas).view(np.uint32).reshape(B, slots), host(bboxes).reshape(B, slots, 4), new_sizes
+
+
+def _records(flags, ax, bx, dx, ay, by, dy):
+    """(n, 8) int64 records from per-RLE columns (scalars broadcast)"""
+    n = max(np.size(v) for v in (flags, ax, bx, dx, ay, by, dy))
+    return np.stack([np.broadcast_to(np.asarray(v, dtype=np.int64), (n,)) for v in (flags, ax, bx, dx, ay, by, dy, 0)], 1)
+
+
+def _rle_transform(host_definition, rle, sizes, xf, out_sizes, device, name=None):
+    name = name or ("rle_transform_host" if host_definition else "rle_transform")
+    return _xf_call(host_definition, name, rle, sizes, device, lambda hs, ws, per: (per("xf", xf, 8), per("out_sizes", out_sizes, 2)))
+
+
+def rle_transform(rle, sizes, xf, out_sizes, device=None):
+    """Run-length masks moved to another pixel grid on the GPU, RLE in and RLE out, no plane in between (``mrcnn_rle_transform``; the
+    rule is defined in include/maskrcnn_hip.h).  ``rle`` in the forms rle_morph takes: a (counts, run_offsets) pair — numpy arrays or
+    CUDA tensors, moved where they lie — with ``sizes`` = [(h, w)] per RLE or per image of equally many RLEs, or the rows rles[b][i] =
+    {"size", "counts"} (sizes may be None).  ``xf``: records [flags, ax, bx, dx, ay, by, dy, 0], one for all, one per size or one per
+    RLE; the output pixel (X, Y) is the source pixel (floor((ax*X + bx)/dx), floor((ay*Y + by)/dy)) — the two swapped when flags is
+    XF_TRANSPOSE — and 0 where that lies outside the plane.  ``out_sizes``: the output planes (h, w), given the same three ways.
+    Returns (rle, areas, boxes, sizes): one canonical RLE per input in the form it came in — a pair in the same memory space (a
+    resident pair stays resident), or rows — the set pixels and their tight boxes x, y, w, h (per RLE for a pair, (B, slots) for rows),
+    and the new sizes to pass on with a pair: per image where every RLE of an image got the same plane, else per RLE.  rle_crop,
+    rle_place, rle_flip, rle_transpose, rle_rot90 and rle_resize write the records for the usual cases.  Not here: rotation by other
+    angles, affine or projective warps, anti-aliased resampling, moving the detection boxes along, composing two records."""
+    return _rle_transform(False, rle, sizes, xf, out_sizes, device)
+
+
+def rle_transform_host(rle, sizes, xf, out_sizes):
+    """The definition of rle_transform: the sequential host code (``mrcnn_rle_transform_host``), no GPU; numpy out."""
+    return _rle_transform(True, rle, sizes, xf, out_sizes, None)
+
+
+def _rle_crop(host_definition, rle, sizes, windows, device):
+    def make(hs, ws, per):
+        win = per("windows", windows, 4)
+        return _records(0, 1, win[:, 0], 1, 1, win[:, 1], 1), win[:, [3, 2]]
+    return _xf_call(host_definition, "rle_crop_host" if host_definition else "rle_crop", rle, sizes, device, make)
+
+
+def _rle_place(host_definition, rle, sizes, origins, frame_sizes, device):
+    def make(hs, ws, per):
+        at = per("origins", origins, 2)
+        return _records(0, 1, -at[:, 0], 1, 1, -at[:, 1], 1), per("frame_sizes", frame_sizes, 2)
+    return _xf_call(host_definition, "rle_place_host" if host_definition else "rle_place", rle, sizes, device, make)
+
+
+def _rle_flip(host_definition, rle, sizes, horizontal, vertical, device):
+    def make(hs, ws, per):
+        fx, fy = bool(horizontal), bool(vertical)
+        return _records(0, -1 if fx else 1, (ws - 1) if fx else 0 * ws, 1, -1 if fy else 1, (hs - 1) if fy else 0 * hs, 1), np.stack((hs, ws), 1)
+    return _xf_call(host_definition, "rle_flip_host" if host_definition else "rle_flip", rle, sizes, device, make)
+
+
+def _rle_rot90(host_definition, rle, sizes, k, device, name):
+    def make(hs, ws, per):
+        turn = int(k) % 4
+        if turn == 0 and name.startswith("rle_rot90"):
+            return _records(0, 1, 0 * ws, 1, 1, 0, 1), np.stack((hs, ws), 1)
+        if turn == 0:                                            # rle_transpose: Out[Y, X] = P[X, Y]
+            return _records(XF_TRANSPOSE, 1, 0 * ws, 1, 1, 0, 1), np.stack((ws, hs), 1)
+        if turn == 1:                                            # Out[Y, X] = P[X, w-1-Y]
+            return _records(XF_TRANSPOSE, 1, 0 * ws, 1, -1, ws - 1, 1), np.stack((ws, hs), 1)
+        if turn == 2:                                            # Out[Y, X] = P[h-1-Y, w-1-X]
+            return _records(0, -1, ws - 1, 1, -1, hs - 1, 1), np.stack((hs, ws), 1)
+        return _records(XF_TRANSPOSE, -1, hs - 1, 1, 1, 0, 1), np.stack((ws, hs), 1)       # Out[Y, X] = P[h-1-X, Y]
+    return _xf_call(host_definition, name, rle, sizes, device, make)
+
+
+RESIZE_RULES = ("center", "floor")
+
+
+def _rle_resize(host_definition, rle, sizes, out_sizes, rule, device):
+    name = "rle_resize_host" if host_definition else "rle_resize"
+    if rule not in RESIZE_RULES:
+        raise ValueError(f"{name}: rule {rule!r} is none of {list(RESIZE_RULES)}")
+
+    def make(hs, ws, per):
+        osz = per("out_sizes", out_sizes, 2)
+        oh, ow = np.maximum(osz[:, 0], 1), np.maximum(osz[:, 1], 1)          # (a side below 1 is refused by its own message)
+        if rule == "center":                                     # src = floor((2X + 1) * w / (2W'))
+            return _records(0, 2 * ws, ws, 2 * ow, 2 * hs, hs, 2 * oh), osz
+        return _records(0, ws, 0, ow, hs, 0, oh), osz            # src = floor(X * w / W')
+    return _xf_call(host_definition, name, rle, sizes, device, make)
+
+
+def rle_crop(rle, sizes, windows, device=None):
+    """The masks cut down to a window (rle_transform with a = 1, d = 1, b = (x, y)).  ``windows``: (x, y, w, h), one for all, one per
+    size or one per RLE; a window may reach outside the plane, and that part is 0.  Returns (rle, areas, boxes, sizes) as
+    rle_transform does; the new planes are the windows'."""
+    return _rle_crop(False, rle, sizes, windows, device)
+
+
+def rle_place(rle, sizes, origins, frame_sizes, device=None):
+    """The masks put into a larger (or any other) frame with their plane's corner at ``origins`` = (x0, y0) — the inverse of rle_crop,
+    and what brings sets from planes of different sizes into one frame for rle_combine.  ``frame_sizes``: (h, w); both one for all,
+    one per size or one per RLE.  What falls outside the frame is cut.  Returns (rle, areas, boxes, sizes) as rle_transform does."""
+    return _rle_place(False, rle, sizes, origins, frame_sizes, device)
+
+
+def rle_flip(rle, sizes=None, horizontal=False, vertical=False, device=None):
+    """The masks mirrored left-right (``horizontal``), top-bottom (``vertical``) or both: np.flip along axis 1 / axis 0."""
+    return _rle_flip(False, rle, sizes, horizontal, vertical, device)
+
+
+def rle_transpose(rle, sizes=None, device=None):
+    """The masks transposed: plane.T, an h x w plane becomes w x h."""
+    return _rle_rot90(False, rle, sizes, 0, device, "rle_transpose")
+
+
+def rle_rot90(rle, sizes=None, k=1, device=None):
+    """The masks rotated by k quarter turns in np.rot90's sense (k = 1: counterclockwise on the screen)."""
+    return _rle_rot90(False, rle, sizes, k, device, "rle_rot90")
+
+
+def rle_resize(rle, sizes, out_sizes, rule="center", device=None):
+    """The masks resized to ``out_sizes`` = (h, w) — one for all, one per size or one per RLE — by nearest neighbour: ``rule`` =
+    "center" reads src = floor((2X + 1) * w / (2W')), the pixel under the output pixel's centre; "floor" reads floor(X * w / W')."""
+    return _rle_resize(False, rle, sizes, out_sizes, rule, device)
+
+
+def rle_crop_host(rle, sizes, windows):
+    return _rle_crop(True, rle, sizes, windows, None)
+
+
+def rle_place_host(rle, sizes, origins, frame_sizes):
+    return _rle_place(True, rle, sizes, origins, frame_sizes, None)
+
+
+def rle_flip_host(rle, sizes=None, horizontal=False, vertical=False):
+    return _rle_flip(True, rle, sizes, horizontal, vertical, None)
+
+
+def rle_transpose_host(rle, sizes=None):
+    return _rle_rot90(True, rle, sizes, 0, None, "rle_transpose_host")
+
+
+def rle_rot90_host(rle, sizes=None, k=1):
+    return _rle_rot90(True, rle, sizes, k, None, "rle_rot90_host")
+
+
+def rle_resize_host(rle, sizes, out_sizes, rule="center"):
+    """The definitions of rle_crop, rle_place, rle_flip, rle_transpose, rle_rot90 and rle_resize: ``mrcnn_rle_transform_host``, no GPU;
+    numpy out."""
+    return _rle_resize(True, rle, sizes, out_sizes, rule, None)
 
 
 # ---- measuring run-length masks (mrcnn_rle_measure, mrcnn_rle_convex_hull) ------------------------------------------------------------------
