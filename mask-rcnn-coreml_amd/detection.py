@@ -12,7 +12,7 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _marshal
 from ._marshal import Space, image_table, ragged_output, rle_results, sizes_of
 
 
@@ -267,75 +267,23 @@ def render_detections_source(images, detections, masks, model_h: int, model_w: i
 
 
 # ---- drawing run-length masks (mrcnn_rle_decode, mrcnn_instance_map_rle, mrcnn_render_detections_rle) ------------------------------------
-def _rle_set(name, rles, sizes, device):
-    """An RLE set for the library: (counts, run_offsets, B, slots, hs, ws).  ``rles`` is either what merge_tiles, unite_tiles and
-    masks_rle_source return — rles[b][i] = {"size": [h_b, w_b], "counts": uint32 runs}, the same number of slots for every image —
-    or a (counts, run_offsets) pair holding B*slots RLEs, numpy arrays or CUDA tensors, which then needs ``sizes`` = [(h_b, w_b)].
-    device = None: numpy arrays (a pair of tensors is copied to the host); else CUDA tensors on that device — a pair of CUDA tensors
-    is used in place, anything else is uploaded (a few MB)."""
-    if isinstance(rles, tuple) and len(rles) == 2 and not isinstance(rles[0], (list, tuple, dict)):
-        counts, offs = rles
-        if sizes is None:
-            raise ValueError(f"{name}: a (counts, run_offsets) pair needs sizes = [(h_b, w_b)]")
-        B = len(sizes)
-        n = int(offs.shape[0]) - 1
-        slots = n // B if B else 0
-        if n != B * slots or n < 0:
-            raise ValueError(f"{name}: run_offsets holds {n} RLEs, not a multiple of the {B} images")
-        if not isinstance(counts, np.ndarray):
-            import torch
-            assert counts.is_cuda and offs.is_cuda and counts.element_size() == 4 and offs.dtype == torch.int64 and counts.is_contiguous() and offs.is_contiguous()
-            if device is None:
-                counts, offs = counts.cpu().numpy().view(np.uint32), offs.cpu().numpy()
-        else:
-            counts, offs = np.ascontiguousarray(counts, dtype=np.uint32), np.ascontiguousarray(offs, dtype=np.int64)
-    else:
-        rows = [list(r) for r in rles]
-        B = len(rows)
-        slots = len(rows[0]) if B else 0
-        if any(len(r) != slots for r in rows):
-            raise ValueError(f"{name}: every image needs the same number of RLEs (pad with empty masks)")
-        if sizes is None:
-            if B and not slots:
-                raise ValueError(f"{name}: images without RLEs need sizes = [(h_b, w_b)]")
-            sizes = [r[0]["size"] for r in rows]
-        if len(sizes) != B:
-            raise ValueError(f"{name}: {len(sizes)} sizes for {B} images")
-        for b, r in enumerate(rows):
-            for i, e in enumerate(r):
-                if [int(e["size"][0]), int(e["size"][1])] != [int(sizes[b][0]), int(sizes[b][1])]:
-                    raise ValueError(f"{name}: RLE {i} of image {b} has size {list(e['size'])}, its image {list(sizes[b])}")
-        runs = [np.ascontiguousarray(e["counts"], dtype=np.uint32).ravel() for r in rows for e in r]
-        counts = np.concatenate(runs) if runs else np.zeros(0, np.uint32)
-        offs = np.concatenate(([0], np.cumsum([len(c) for c in runs]))).astype(np.int64)
-    if device is not None and isinstance(counts, np.ndarray):
-        import torch
-        counts = torch.from_numpy(np.ascontiguousarray(counts).view(np.int32).copy()).to(device)
-        offs = torch.from_numpy(offs.copy()).to(device)
-    if isinstance(counts, np.ndarray) and counts.size == 0:
-        counts = np.zeros(1, np.uint32)
-    return (counts, offs, B, slots, *sizes_of(sizes))
-
-
-def _rle_rows(name, det_src, B, slots, host_definition):
-    """(space, det_src) for the (B, slots, 6) source-frame rows that go with an RLE set."""
+def _rle_rows(name, host_definition, det_src, rles, sizes):
+    """(set, space, det_src) of a drawing call: the (B, slots, 6) source-frame rows say where it runs, and the RLE set goes there."""
     space = Space(det_src)
+    s = _marshal.RleSet(name, rles, sizes, space.device, host_definition, in_place=False)
     assert space.on_host or not host_definition, f"{name}_host takes numpy arrays"
     det, = space.f32(det_src)
-    if det.ndim != 3 or det.shape[0] != B or det.shape[1] != slots or det.shape[2] != 6:
-        raise ValueError(f"{name}: det_src {tuple(det.shape)} does not go with {B} images of {slots} RLEs: ({B}, {slots}, 6) expected")
-    return space, det
+    if det.ndim != 3 or det.shape[0] != s.B or det.shape[1] != s.slots or det.shape[2] != 6:
+        raise ValueError(f"{name}: det_src {tuple(det.shape)} does not go with {s.B} images of {s.slots} RLEs: ({s.B}, {s.slots}, 6) expected")
+    return s, space, det
 
 
 def _rle_decode_planes(host_definition, rles, sizes, device):
-    name = "rle_decode_planes_host" if host_definition else "rle_decode_planes"
-    if device is None and not host_definition and isinstance(rles, tuple) and len(rles) == 2 and hasattr(rles[0], "is_cuda"):
-        device = rles[0].device                                  # a pair of CUDA tensors: used in place, tensors out
-    counts, offs, B, slots, hs, ws = _rle_set(name, rles, sizes, device)
-    space = Space(device)
+    s = _marshal.RleSet("rle_decode_planes_host" if host_definition else "rle_decode_planes", rles, sizes, device, host_definition)
+    space = s.space
     ptr = space.ptr
-    out, out_offs, planes = ragged_output(space, hs, ws, np.uint8, lead=(slots,))
-    head = (ptr(counts), ptr(offs), B, slots, hs.ctypes.data, ws.ctypes.data)
+    out, out_offs, planes = ragged_output(space, s.image_hs, s.image_ws, np.uint8, lead=(s.slots,))
+    head = (ptr(s.counts), ptr(s.offs), s.B, s.slots, s.image_hs.ctypes.data, s.image_ws.ctypes.data)
     if host_definition:
         _lib.check(_lib.lib().mrcnn_rle_decode_host(*head, ptr(out), out_offs.ctypes.data))
     else:
@@ -359,12 +307,11 @@ def rle_decode_planes_host(rles, sizes=None):
 
 def _instance_map_rle(host_definition, det_src, rles, sizes, min_score):
     name = "instance_map_rle_host" if host_definition else "instance_map_rle"
-    counts, offs, B, slots, hs, ws = _rle_set(name, rles, sizes, Space(det_src).device)
-    space, det = _rle_rows(name, det_src, B, slots, host_definition)
+    s, space, det = _rle_rows(name, host_definition, det_src, rles, sizes)
     ptr = space.ptr
-    out, map_offs, maps = ragged_output(space, hs, ws, np.int16)
-    visible = space.new((B, slots), np.uint32, zero=True)
-    head = (ptr(det), ptr(counts), ptr(offs), B, slots, hs.ctypes.data, ws.ctypes.data, C.c_float(min_score))
+    out, map_offs, maps = ragged_output(space, s.image_hs, s.image_ws, np.int16)
+    visible = space.new((s.B, s.slots), np.uint32, zero=True)
+    head = (ptr(det), ptr(s.counts), ptr(s.offs), s.B, s.slots, s.image_hs.ctypes.data, s.image_ws.ctypes.data, C.c_float(min_score))
     tail = (ptr(out), map_offs.ctypes.data, ptr(visible))
     if host_definition:
         _lib.check(_lib.lib().mrcnn_instance_map_rle_host(*head, *tail))
@@ -391,12 +338,11 @@ def _render_detections_rle(host_definition, images, det_src, rles, min_score, al
     name = "render_detections_rle_host" if host_definition else "render_detections_rle"
     images = list(images)
     sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
-    counts, offs, B, slots, hs, ws = _rle_set(name, rles, sizes, Space(det_src).device)
-    space, det = _rle_rows(name, det_src, B, slots, host_definition)
+    s, space, det = _rle_rows(name, host_definition, det_src, rles, sizes)
     ptr = space.ptr
     table, _, keep, hs, ws = image_table(images, space)
     out, out_offs, drawn = ragged_output(space, hs, ws, np.uint8, trail=(3,))
-    head = (table, ptr(det), ptr(counts), ptr(offs), B, slots, C.c_float(min_score), int(alpha), int(stroke))
+    head = (table, ptr(det), ptr(s.counts), ptr(s.offs), s.B, s.slots, C.c_float(min_score), int(alpha), int(stroke))
     if host_definition:
         _lib.check(_lib.lib().mrcnn_render_detections_rle_host(*head, ptr(out), out_offs.ctypes.data))
     else:
@@ -447,17 +393,6 @@ def _flat_of_nested(rings, areas):
             "xy": np.concatenate(every + [np.zeros((0, 2), np.int32)])}, every
 
 
-def _here(space, a, dtype):
-    """an array of a flat dictionary as a contiguous array of ``space``: converted or moved only where it has to be"""
-    if a is None:
-        return None
-    if space.on_host:
-        return np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "is_cuda") else a, dtype=dtype)
-    import torch
-    t = a if hasattr(a, "is_cuda") else torch.from_numpy(np.ascontiguousarray(a, dtype=dtype))
-    return t.to(device=space.device, dtype=getattr(torch, np.dtype(dtype).name)).contiguous()
-
-
 def _simplify_polygons(host_definition, polygons, tolerance, device, flat):
     nested = not isinstance(polygons, dict)
     if nested:
@@ -469,14 +404,14 @@ def _simplify_polygons(host_definition, polygons, tolerance, device, flat):
     if device is None and on_device and not host_definition:
         device = P["xy"].device                                  # tensors: simplified where they lie, tensors out
     space = Space(device)
-    here = lambda a, dtype: _here(space, a, dtype)
+    here = space.take
     offsets, xy = here(P["ring_offsets"], np.int64), here(P["xy"], np.int32)
     out_offsets, areas2, out_xy, src_index, n = _simplify_flat(host_definition, space, offsets, xy, tolerance)
     out = {"rle_rings": here(P.get("rle_rings"), np.int64), "ring_offsets": out_offsets, "ring_areas": here(P.get("ring_areas"), np.int64),
            "areas2": areas2, "xy": out_xy, "src_index": src_index, "n_rings": int(offsets.shape[0]) - 1, "n_vertices": n}
     if flat or not nested:
         return out
-    ro, sxy = (out_offsets, out_xy) if space.on_host else (out_offsets.cpu().numpy(), out_xy.cpu().numpy())
+    ro, sxy = space.host(out_offsets), space.host(out_xy)
     at = iter(range(len(every)))
     return [[[sxy[ro[r]:ro[r + 1]] for r in (next(at) for _ in rle)] for rle in row] for row in rings], areas
 
@@ -548,8 +483,8 @@ def _nest_polygons(host_definition, polygons, device, flat):
     if device is None and hasattr(P["xy"], "is_cuda") and not host_definition:
         device = P["xy"].device                                  # tensors: nested where they lie, tensors out
     space = Space(device)
-    rle_rings = _here(space, P["rle_rings"], np.int64)
-    N = _nest_flat(host_definition, space, rle_rings, _here(space, P["ring_offsets"], np.int64), _here(space, P["xy"], np.int32))
+    rle_rings = space.take(P["rle_rings"], np.int64)
+    N = _nest_flat(host_definition, space, rle_rings, space.take(P["ring_offsets"], np.int64), space.take(P["xy"], np.int32))
     if flat or not nested:
         return N
     return _nest_nested(N, rle_rings, [len(row) for row in rings])
@@ -576,24 +511,21 @@ def nest_polygons_host(polygons, flat: bool = False):
 
 def _rle_to_polygons(host_definition, rles, sizes, device, flat, tolerance=None, nest=False):
     name = "rle_to_polygons_host" if host_definition else "rle_to_polygons"
-    if device is None and not host_definition and isinstance(rles, tuple) and len(rles) == 2 and hasattr(rles[0], "is_cuda"):
-        device = rles[0].device                                  # a pair of CUDA tensors: traced where they lie, tensors out
-    counts, offs, B, slots, hs, ws = _rle_set(name, rles, sizes, device)
-    space = Space(device)
+    s = _marshal.RleSet(name, rles, sizes, device, host_definition)
+    space, B, slots, n = s.space, s.B, s.slots, s.n
     ptr = space.ptr
-    n = B * slots
     rle_rings = space.new(n + 1, np.int64, zero=True)
     totals = (C.c_int64(0), C.c_int64(0))
-    head = (ptr(counts), ptr(offs), B, slots, hs.ctypes.data, ws.ctypes.data) + (() if host_definition else (space.code,))
+    head = (ptr(s.counts), ptr(s.offs), B, slots, s.image_hs.ctypes.data, s.image_ws.ctypes.data) + (() if host_definition else (space.code,))
     entry = getattr(_lib.lib(), "mrcnn_" + name)
-    cap_r, cap_v = 4 * n + 16, 2 * int(counts.shape[0]) + 64      # a first guess; the library names what it needs
-    for _ in range(2):
+
+    def attempt(capacity):                                       # rings and vertices grow together
+        cap_r, cap_v = capacity
         ring_offsets, ring_areas, xy = space.new(cap_r + 1, np.int64), space.new(max(1, cap_r), np.int64), space.new(max(1, 2 * cap_v), np.int32)
         st = entry(*head, ptr(rle_rings), C.byref(totals[0]), C.byref(totals[1]), ptr(ring_offsets), ptr(ring_areas), cap_r, ptr(xy), cap_v)
-        if st != 4 or (totals[0].value <= cap_r and totals[1].value <= cap_v):
-            break
-        cap_r, cap_v = totals[0].value, totals[1].value
-    _lib.check(st)
+        return st, (totals[0].value, totals[1].value), (ring_offsets, ring_areas, xy)
+    # a first guess; the library names what it needs
+    ring_offsets, ring_areas, xy = _marshal.with_capacity((4 * n + 16, 2 * int(s.counts.shape[0]) + 64), attempt)
     R, V = totals[0].value, totals[1].value
     ring_offsets, ring_areas, xy = ring_offsets[:R + 1], ring_areas[:R], xy[:2 * V].reshape(V, 2)
     extra = {}
@@ -604,8 +536,7 @@ def _rle_to_polygons(host_definition, rles, sizes, device, flat, tolerance=None,
         extra.update({"areas2": areas2, "src_index": src_index})
     if flat:
         return {"rle_rings": rle_rings, "ring_offsets": ring_offsets, "ring_areas": ring_areas, "xy": xy, "n_rings": R, "n_vertices": V, **extra}
-    if not space.on_host:
-        rle_rings, ring_offsets, ring_areas, xy = (a.cpu().numpy() for a in (rle_rings, ring_offsets, ring_areas, xy))
+    rle_rings, ring_offsets, ring_areas, xy = (space.host(a) for a in (rle_rings, ring_offsets, ring_areas, xy))
     rings = [[[xy[ring_offsets[r]:ring_offsets[r + 1]] for r in range(rle_rings[b * slots + i], rle_rings[b * slots + i + 1])]
               for i in range(slots)] for b in range(B)]
     areas = [[ring_areas[rle_rings[b * slots + i]:rle_rings[b * slots + i + 1]] for i in range(slots)] for b in range(B)]
@@ -654,18 +585,9 @@ def _morph_flat(host_definition, space, counts, offs, hs, ws, radii, op):
     needs more, one more call with the capacity the library reported."""
     n = int(offs.shape[0]) - 1
     ptr = space.ptr
-    out_offs, areas, bboxes = space.new(n + 1, np.int64, zero=True), space.new(max(1, n), np.uint32), space.new((max(1, n), 4), np.int32)
     entry = _lib.lib().mrcnn_rle_morph_host if host_definition else _lib.lib().mrcnn_rle_morph
     head = (ptr(counts), ptr(offs), n, hs.ctypes.data, ws.ctypes.data, radii.ctypes.data, int(op)) + (() if host_definition else (space.code,))
-    capacity = int(counts.shape[0]) + 2 * n + 2
-    for _ in range(2):
-        out = space.new(max(1, capacity), np.uint32)
-        st = entry(*head, ptr(out), capacity, ptr(out_offs), ptr(areas), ptr(bboxes))
-        if st != 4 or int(out_offs[n]) <= capacity:
-            break
-        capacity = int(out_offs[n])
-    _lib.check(st)
-    return out[:int(out_offs[n])], out_offs, areas[:n], bboxes[:n]
+    return _marshal.rle_out(space, n, int(counts.shape[0]) + 2 * n + 2, lambda *tail: entry(*head, *tail))
 
 
 def rle_rows_of(pair, sizes):
@@ -678,29 +600,40 @@ def rle_rows_of(pair, sizes):
             for b in range(B)]
 
 
+def _rle_back(s, pair_out, areas, bboxes, sizes=None):
+    """(rle, areas, bboxes) of a call that returns one RLE per RLE of the set ``s``, in the form the set came in: the pair as it is, or
+    host rows with areas (B, slots) and bboxes (B, slots, 4).  sizes: the (h, w) of every output plane where they are not the input's."""
+    if s.pair:
+        return pair_out, areas, bboxes
+    host, B, slots = s.space.host, s.B, s.slots
+    if sizes is None:
+        rles = rle_rows_of(pair_out, s.image_sizes() if slots else [])
+    else:
+        c, o = host(pair_out[0]).view(np.uint32), host(pair_out[1])
+        rles = [[{"size": list(sizes[k]), "counts": c[int(o[k]):int(o[k + 1])]} for k in range(b * slots, (b + 1) * slots)] for b in range(B)]
+    return rles, host(areas).view(np.uint32).reshape(B, slots), host(bboxes).reshape(B, slots, 4)
+
+
+def _rows_flat(s, pair_out, owner):
+    """One host row per result where there is no (B, slots) grid any more: result j lies over the plane of the set's RLE owner[j]."""
+    c, o = s.space.host(pair_out[0]).view(np.uint32), s.space.host(pair_out[1])
+    hs, ws = s.sides()
+    return [{"size": [int(hs[k]), int(ws[k])], "counts": c[int(o[j]):int(o[j + 1])]} for j, k in enumerate(owner)]
+
+
 def _rle_morph(host_definition, rle, sizes, radii, op, device):
     name = "rle_morph_host" if host_definition else "rle_morph"
-    if op not in MORPH_OPS and op not in MORPH_OPS.values():
-        raise ValueError(f"{name}: op {op!r} is none of {sorted(MORPH_OPS)}")
-    pair = isinstance(rle, tuple) and len(rle) == 2 and not isinstance(rle[0], (list, tuple, dict))
-    if device is None and not host_definition and pair and hasattr(rle[0], "is_cuda"):
-        device = rle[0].device                                   # a pair of CUDA tensors: changed where it lies, tensors out
-    counts, offs, B, slots, hs, ws = _rle_set(name, rle, sizes, device)
-    n = B * slots
-    hs, ws = np.repeat(hs, slots).astype(np.int32), np.repeat(ws, slots).astype(np.int32)
+    op = _marshal.choice(MORPH_OPS, op, f"{name}: op {op!r} is none of {sorted(MORPH_OPS)}")
+    s = _marshal.RleSet(name, rle, sizes, device, host_definition)
+    B, slots, n = s.B, s.slots, s.n
     r = np.asarray(radii, dtype=np.float64).reshape(-1)
     if r.size not in (1, B, n) or r.size == 0:
         raise ValueError(f"{name}: {r.size} radii for {n} RLEs of {B} sizes: one, one per size or one per RLE expected")
     if (r != np.rint(r)).any() or (np.abs(r) > 2 ** 30).any():
         raise ValueError(f"{name}: a radius is a whole number of pixels")
     r = np.ascontiguousarray(np.broadcast_to(r, (n,)) if r.size in (1, n) else np.repeat(r, slots)).astype(np.int32)
-    space = Space(device)
-    out, out_offs, areas, bboxes = _morph_flat(host_definition, space, counts, offs, hs, ws, r, MORPH_OPS.get(op, op))
-    if pair:
-        return (out, out_offs), areas, bboxes
-    host = lambda a: a if space.on_host else a.cpu().numpy()
-    rles = rle_rows_of((out, out_offs), [(hs[b * slots], ws[b * slots]) for b in range(B)] if slots else [])
-    return rles, host(areas).view(np.uint32).reshape(B, slots), host(bboxes).reshape(B, slots, 4)
+    out, out_offs, areas, bboxes = _morph_flat(host_definition, s.space, s.counts, s.offs, *s.sides(), r, op)
+    return _rle_back(s, (out, out_offs), areas, bboxes)
 
 
 def rle_morph(rle, sizes, radii, op, device=None):
@@ -782,86 +715,50 @@ COMPONENTS_OF = {"ones": _lib.COMPONENTS_OF_ONES, "zeros": _lib.COMPONENTS_OF_ZE
 COMPONENTS_MODES = {"merge": _lib.COMPONENTS_MERGE, "split": _lib.COMPONENTS_SPLIT}
 
 
-class _CompSet:
-    """The RLE set of one components call: where it lies, its flat arrays and the per-RLE sizes."""
-
-    def __init__(self, name, host_definition, rle, sizes, device):
-        self.pair = isinstance(rle, tuple) and len(rle) == 2 and not isinstance(rle[0], (list, tuple, dict))
-        if device is None and not host_definition and self.pair and hasattr(rle[0], "is_cuda"):
-            device = rle[0].device                               # a pair of CUDA tensors: labelled where it lies, tensors out
-        self.counts, self.offs, self.B, self.slots, hs, ws = _rle_set(name, rle, sizes, device)
-        self.n = self.B * self.slots
-        self.image_sizes = [(int(h), int(w)) for h, w in zip(hs, ws)]
-        self.hs, self.ws = np.repeat(hs, self.slots).astype(np.int32), np.repeat(ws, self.slots).astype(np.int32)
-        self.space = Space(device)
-        self.host_definition = host_definition
-
-    def head(self, connectivity, of):
-        if of not in COMPONENTS_OF and of not in COMPONENTS_OF.values():
-            raise ValueError(f"components of {of!r}: one of {sorted(COMPONENTS_OF)} expected")
-        ptr = self.space.ptr
-        return (ptr(self.counts), ptr(self.offs), self.n, self.hs.ctypes.data, self.ws.ctypes.data, int(connectivity), int(COMPONENTS_OF.get(of, of)))
-
-    def u8(self, mask):
-        """a keep mask as contiguous uint8 of the set's memory space"""
-        if self.space.on_host:
-            return np.ascontiguousarray(mask.cpu().numpy() if hasattr(mask, "is_cuda") else mask).astype(np.uint8).reshape(-1)
-        import torch
-        if not hasattr(mask, "is_cuda"):
-            mask = torch.from_numpy(np.ascontiguousarray(mask).astype(np.uint8))
-        return mask.to(device=self.space.device, dtype=torch.uint8).contiguous().reshape(-1)
+def _components_head(s, connectivity, of):
+    """the arguments the two components entries begin on"""
+    of = _marshal.choice(COMPONENTS_OF, of, f"components of {of!r}: one of {sorted(COMPONENTS_OF)} expected")
+    ptr, (hs, ws) = s.space.ptr, s.sides()
+    return (ptr(s.counts), ptr(s.offs), s.n, hs.ctypes.data, ws.ctypes.data, int(connectivity), int(of))
 
 
-def _components_flat(cs, connectivity, of):
+def _components_flat(s, connectivity, of):
     """mrcnn_rle_components(_host) on the set: (comp_offsets (n + 1), areas, bboxes (C, 4), flags) in the set's memory space.  A first
     attempt guesses the number of components; if there are more, one more call with the capacity the library reported."""
-    space, n = cs.space, cs.n
+    space, n = s.space, s.n
     ptr = space.ptr
     comp_offs = space.new(n + 1, np.int64, zero=True)
-    entry = _lib.lib().mrcnn_rle_components_host if cs.host_definition else _lib.lib().mrcnn_rle_components
-    head = cs.head(connectivity, of) + (() if cs.host_definition else (space.code,))
-    capacity = 4 * n + 64
-    for _ in range(2):
+    entry = _lib.lib().mrcnn_rle_components_host if s.host_definition else _lib.lib().mrcnn_rle_components
+    head = _components_head(s, connectivity, of) + (() if s.host_definition else (space.code,))
+
+    def attempt(capacity):
         areas, bboxes, flags = space.new(capacity, np.uint32), space.new((capacity, 4), np.int32), space.new(capacity, np.uint8)
         st = entry(*head, ptr(comp_offs), ptr(areas), ptr(bboxes), ptr(flags), capacity)
-        if st != 4 or int(comp_offs[n]) <= capacity:
-            break
-        capacity = int(comp_offs[n])
-    _lib.check(st)
-    C_ = int(comp_offs[n])
-    return comp_offs, areas[:C_], bboxes[:C_], flags[:C_]
+        C_ = int(comp_offs[n])
+        return st, C_, (comp_offs, areas[:C_], bboxes[:C_], flags[:C_])
+    return _marshal.with_capacity(4 * n + 64, attempt)
 
 
-def _select_flat(cs, keep, connectivity, of, mode):
+def _select_flat(s, keep, connectivity, of, mode):
     """mrcnn_rle_components_select(_host) on the set with a keep mask of its space: ((counts, run_offsets), areas, bboxes, parent)."""
-    if mode not in COMPONENTS_MODES and mode not in COMPONENTS_MODES.values():
-        raise ValueError(f"rle_select_components: mode {mode!r} is none of {sorted(COMPONENTS_MODES)}")
-    mode = int(COMPONENTS_MODES.get(mode, mode))
-    space, n = cs.space, cs.n
+    mode = int(_marshal.choice(COMPONENTS_MODES, mode, f"rle_select_components: mode {mode!r} is none of {sorted(COMPONENTS_MODES)}"))
+    space = s.space
     ptr = space.ptr
-    keep = cs.u8(keep)
+    keep = space.take(keep, np.uint8).reshape(-1)
     n_comps = int(keep.shape[0])
-    room = n_comps if mode == _lib.COMPONENTS_SPLIT else n
-    out_offs, areas, bboxes = space.new(room + 1, np.int64, zero=True), space.new(max(1, room), np.uint32), space.new((max(1, room), 4), np.int32)
+    room = n_comps if mode == _lib.COMPONENTS_SPLIT else s.n
     parent = space.new(max(1, room), np.int64)
     out_n = C.c_int64(0)
-    entry = _lib.lib().mrcnn_rle_components_select_host if cs.host_definition else _lib.lib().mrcnn_rle_components_select
-    head = cs.head(connectivity, of) + ((ptr(keep) if n_comps else None), n_comps, mode) + (() if cs.host_definition else (space.code,))
-    capacity = int(cs.counts.shape[0]) + 2 * room + 2
-    for _ in range(2):
-        out = space.new(max(1, capacity), np.uint32)
-        st = entry(*head, ptr(out), capacity, ptr(out_offs), ptr(areas), ptr(bboxes), ptr(parent), C.byref(out_n))
-        if st != 4 or int(out_offs[out_n.value]) <= capacity:
-            break
-        capacity = int(out_offs[out_n.value])
-    _lib.check(st)
-    m = int(out_n.value)
-    return (out[:int(out_offs[m])], out_offs[:m + 1]), areas[:m], bboxes[:m], parent[:m]
+    entry = _lib.lib().mrcnn_rle_components_select_host if s.host_definition else _lib.lib().mrcnn_rle_components_select
+    head = _components_head(s, connectivity, of) + ((ptr(keep) if n_comps else None), n_comps, mode) + (() if s.host_definition else (space.code,))
+    out, out_offs, areas, bboxes = _marshal.rle_out(space, room, int(s.counts.shape[0]) + 2 * room + 2,
+                                                    lambda *tail: entry(*head, *tail, ptr(parent), C.byref(out_n)), written=lambda: int(out_n.value))
+    return (out, out_offs), areas, bboxes, parent[:int(out_n.value)]
 
 
 def _rle_components(host_definition, rle, sizes, connectivity, of, device):
-    cs = _CompSet("rle_components_host" if host_definition else "rle_components", host_definition, rle, sizes, device)
-    return _components_flat(cs, connectivity, of)
+    s = _marshal.RleSet("rle_components_host" if host_definition else "rle_components", rle, sizes, device, host_definition)
+    return _components_flat(s, connectivity, of)
 
 
 def rle_components(rle, sizes=None, connectivity=4, of="ones", device=None):
@@ -880,19 +777,16 @@ def rle_components_host(rle, sizes=None, connectivity=4, of="ones"):
     return _rle_components(True, rle, sizes, connectivity, of, None)
 
 
-def _rle_select(host_definition, rle, sizes, keep, connectivity, of, mode, device, cs=None):
-    cs = cs or _CompSet("rle_select_components_host" if host_definition else "rle_select_components", host_definition, rle, sizes, device)
-    pair, areas, bboxes, parent = _select_flat(cs, keep, connectivity, of, mode)
-    split = COMPONENTS_MODES.get(mode, mode) == _lib.COMPONENTS_SPLIT
-    if cs.pair:
-        return (pair, areas, bboxes, parent) if split else (pair, areas, bboxes)
-    host = lambda a: a if cs.space.on_host else a.cpu().numpy()
-    if split:                                                    # one row per kept component: no (B, slots) grid any more
-        c, o, par = host(pair[0]).view(np.uint32), host(pair[1]), host(parent)
-        rows = [{"size": [int(cs.hs[par[j]]), int(cs.ws[par[j]])], "counts": c[int(o[j]):int(o[j + 1])]} for j in range(len(par))]
-        return rows, host(areas).view(np.uint32), host(bboxes), par
-    rles = rle_rows_of(pair, cs.image_sizes if cs.slots else [])
-    return rles, host(areas).view(np.uint32).reshape(cs.B, cs.slots), host(bboxes).reshape(cs.B, cs.slots, 4)
+def _rle_select(host_definition, rle, sizes, keep, connectivity, of, mode, device, s=None):
+    s = s or _marshal.RleSet("rle_select_components_host" if host_definition else "rle_select_components", rle, sizes, device, host_definition)
+    pair, areas, bboxes, parent = _select_flat(s, keep, connectivity, of, mode)
+    if COMPONENTS_MODES.get(mode, mode) != _lib.COMPONENTS_SPLIT:
+        return _rle_back(s, pair, areas, bboxes)
+    if s.pair:
+        return pair, areas, bboxes, parent
+    host = s.space.host
+    par = host(parent)
+    return _rows_flat(s, pair, par), host(areas).view(np.uint32), host(bboxes), par
 
 
 def rle_select_components(rle, sizes, keep, connectivity=4, of="ones", mode="merge", device=None):
@@ -932,11 +826,11 @@ def _largest_mask(comp_offs, areas, m):
 
 def _filter(host_definition, name, rle, sizes, connectivity, of, mode, device, choose):
     """label, build the keep mask where the measures lie (choose(comp_offsets, areas, flags)), select"""
-    cs = _CompSet(name, host_definition, rle, sizes, device)
-    comp_offs, areas, _, flags = _components_flat(cs, connectivity, of)
+    s = _marshal.RleSet(name, rle, sizes, device, host_definition)
+    comp_offs, areas, _, flags = _components_flat(s, connectivity, of)
     if isinstance(areas, np.ndarray):
         areas = areas.astype(np.int64)
-    return _rle_select(host_definition, rle, sizes, choose(comp_offs, areas, flags), connectivity, of, mode, device, cs=cs)
+    return _rle_select(host_definition, rle, sizes, choose(comp_offs, areas, flags), connectivity, of, mode, device, s=s)
 
 
 def _remove_small(host_definition, rle, sizes, min_area, connectivity, device):
@@ -1002,16 +896,12 @@ def rle_split_components_host(rle, sizes, min_area=0, connectivity=4):
 COMBINE_OPS = {"or": _lib.RLE_OR, "and": _lib.RLE_AND, "xor": _lib.RLE_XOR, "diff": _lib.RLE_DIFF}
 
 
-def _is_pair(rle):
-    return isinstance(rle, tuple) and len(rle) == 2 and not isinstance(rle[0], (list, tuple, dict))
-
-
 def _groups_of(name, groups):
     """(group_offsets, members) as int64 host arrays: from a list of index lists, or from a tuple (offsets, members)"""
     if isinstance(groups, tuple):
         if len(groups) != 2:
             raise ValueError(f"{name}: groups is a list of index lists or an (offsets, members) pair")
-        offs, mem = (np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "is_cuda") else a, dtype=np.int64).reshape(-1) for a in groups)
+        offs, mem = (_marshal.HOST.take(a, np.int64).reshape(-1) for a in groups)
     else:
         rows = [np.asarray(g, dtype=np.int64).reshape(-1) for g in groups]
         offs = np.concatenate(([0], np.cumsum([len(r) for r in rows]))).astype(np.int64)
@@ -1027,42 +917,20 @@ def _combine_flat(host_definition, space, counts, offs, hs, ws, goffs, mem, op):
     input's runs; if the result needs more, one more call with the capacity the library reported."""
     n, G = int(offs.shape[0]) - 1, int(goffs.shape[0]) - 1
     ptr = space.ptr
-    out_offs, areas, bboxes = space.new(G + 1, np.int64, zero=True), space.new(max(1, G), np.uint32), space.new((max(1, G), 4), np.int32)
     entry = _lib.lib().mrcnn_rle_combine_host if host_definition else _lib.lib().mrcnn_rle_combine
     head = (ptr(counts), ptr(offs), n, hs.ctypes.data, ws.ctypes.data, goffs.ctypes.data, mem.ctypes.data, G, int(op)) + (() if host_definition else (space.code,))
-    capacity = int(counts.shape[0]) + 2 * G + 2
-    for _ in range(2):
-        out = space.new(max(1, capacity), np.uint32)
-        st = entry(*head, ptr(out), capacity, ptr(out_offs), ptr(areas), ptr(bboxes))
-        if st != 4 or int(out_offs[G]) <= capacity:
-            break
-        capacity = int(out_offs[G])
-    _lib.check(st)
-    return out[:int(out_offs[G])], out_offs, areas[:G], bboxes[:G]
-
-
-def _combine_set(name, host_definition, rle, sizes, device):
-    """(pair?, space, counts, run_offsets, B, slots, hs and ws per RLE) of one combine call"""
-    pair = _is_pair(rle)
-    if device is None and not host_definition and pair and hasattr(rle[0], "is_cuda"):
-        device = rle[0].device                                   # a pair of CUDA tensors: combined where it lies, tensors out
-    counts, offs, B, slots, hs, ws = _rle_set(name, rle, sizes, device)
-    return pair, Space(device), counts, offs, B, slots, np.repeat(hs, slots).astype(np.int32), np.repeat(ws, slots).astype(np.int32)
+    return _marshal.rle_out(space, G, int(counts.shape[0]) + 2 * G + 2, lambda *tail: entry(*head, *tail))
 
 
 def _rle_combine(host_definition, rle, sizes, groups, op, device, name=None):
     name = name or ("rle_combine_host" if host_definition else "rle_combine")
-    if op not in COMBINE_OPS and op not in COMBINE_OPS.values():
-        raise ValueError(f"{name}: op {op!r} is none of {sorted(COMBINE_OPS)}")
-    pair, space, counts, offs, _, _, hs, ws = _combine_set(name, host_definition, rle, sizes, device)
+    op = _marshal.choice(COMBINE_OPS, op, f"{name}: op {op!r} is none of {sorted(COMBINE_OPS)}")
+    s = _marshal.RleSet(name, rle, sizes, device, host_definition)
     goffs, mem = _groups_of(name, groups)
-    out, out_offs, areas, bboxes = _combine_flat(host_definition, space, counts, offs, hs, ws, goffs, mem, COMBINE_OPS.get(op, op))
-    if pair:
+    out, out_offs, areas, bboxes = _combine_flat(host_definition, s.space, s.counts, s.offs, *s.sides(), goffs, mem, op)
+    if s.pair:
         return (out, out_offs), areas, bboxes
-    host = lambda a: a if space.on_host else a.cpu().numpy()
-    c, o = host(out).view(np.uint32), host(out_offs)
-    rows = [{"size": [int(hs[mem[goffs[g]]]), int(ws[mem[goffs[g]]])], "counts": c[int(o[g]):int(o[g + 1])]} for g in range(len(goffs) - 1)]
-    return rows, host(areas).view(np.uint32), host(bboxes)
+    return _rows_flat(s, (out, out_offs), mem[goffs[:-1]]), s.space.host(areas).view(np.uint32), s.space.host(bboxes)
 
 
 def rle_combine(rle, sizes, groups, op, device=None):
@@ -1097,23 +965,22 @@ def _pairwise(host_definition, name, rle, sizes, other, op, device):
     """A[k] op B[k] for two sets of equally many RLEs of equal sizes, in the form A came in: rows (B, slots) or a pair"""
     if other is None:
         raise ValueError(f"{name}: groups, or a second set ``other`` to combine pairwise, expected")
-    pair, space, ca, oa, B, slots, hs, ws = _combine_set(name, host_definition, rle, sizes, device)
-    _, _, cb, ob, B2, slots2, hs2, ws2 = _combine_set(name, host_definition, other, sizes, space.device)
-    if (B2, slots2) != (B, slots) or (hs2 != hs).any() or (ws2 != ws).any():
+    A = _marshal.RleSet(name, rle, sizes, device, host_definition)
+    O = _marshal.RleSet(name, other, sizes, A.space.device, host_definition)
+    (hs, ws), (hs2, ws2) = A.sides(), O.sides()
+    if (O.B, O.slots) != (A.B, A.slots) or (hs2 != hs).any() or (ws2 != ws).any():
         raise ValueError(f"{name}: the two sets differ in their number of RLEs or in their sizes")
-    n = B * slots
+    n, (ca, oa), (cb, ob) = A.n, (A.counts, A.offs), (O.counts, O.offs)
     a0, a1, b0, b1 = int(oa[0]), int(oa[n]), int(ob[0]), int(ob[n])
-    counts = _cat(ca[a0:a1], cb[b0:b1])                          # the two sets behind each other: B's RLE k is RLE n + k
+    counts = _marshal.addressable(_cat(ca[a0:a1], cb[b0:b1]))             # the two sets behind each other: B's RLE k is RLE n + k
     offs = _cat(oa - a0, ob[1:] - b0 + (a1 - a0))
-    if isinstance(counts, np.ndarray) and counts.size == 0:
-        counts = np.zeros(1, np.uint32)
     goffs = 2 * np.arange(n + 1, dtype=np.int64)
     mem = np.stack((np.arange(n, dtype=np.int64), n + np.arange(n, dtype=np.int64)), 1).reshape(-1)
-    out, out_offs, areas, bboxes = _combine_flat(host_definition, space, counts, offs, np.tile(hs, 2), np.tile(ws, 2), goffs,
-                                                 mem if n else np.zeros(1, np.int64), COMBINE_OPS[op])
-    if pair:
+    out, out_offs, _, _ = _combine_flat(host_definition, A.space, counts, offs, np.tile(hs, 2), np.tile(ws, 2), goffs,
+                                        mem if n else np.zeros(1, np.int64), COMBINE_OPS[op])
+    if A.pair:
         return (out, out_offs)
-    return rle_rows_of((out, out_offs), [(hs[b * slots], ws[b * slots]) for b in range(B)] if slots else [])
+    return rle_rows_of((out, out_offs), A.image_sizes() if A.slots else [])      # (areas and boxes are not asked for: not read back)
 
 
 def _algebra(host_definition, name, rle, sizes, groups, other, op, device):
@@ -1181,14 +1048,14 @@ def drawn_rows(det_src, sizes, min_score: float = 0.0) -> np.ndarray:
 
 def _rle_disjoint(host_definition, det_src, rle, sizes, min_score, device):
     name = "rle_disjoint_host" if host_definition else "rle_disjoint"
-    if device is None and not host_definition and not (_is_pair(rle) and hasattr(rle[0], "is_cuda")):
+    if device is None and not host_definition and _marshal.pair_device(rle) is None:
         device = Space(det_src).device                           # the rows say where the call runs, as for instance_map_rle
-    pair, space, counts, offs, B, slots, hs, ws = _combine_set(name, host_definition, rle, sizes, device)
-    image_sizes = [(int(hs[b * slots]), int(ws[b * slots])) for b in range(B)] if slots else []
+    s = _marshal.RleSet(name, rle, sizes, device, host_definition)
+    B, slots = s.B, s.slots
     det = np.asarray(det_src.cpu().numpy() if hasattr(det_src, "is_cuda") else det_src, dtype=np.float32)
     if det.ndim != 3 or det.shape[0] != B or det.shape[1] != slots or det.shape[2] != 6:
         raise ValueError(f"{name}: det_src {tuple(det.shape)} does not go with {B} images of {slots} RLEs: ({B}, {slots}, 6) expected")
-    drawn = drawn_rows(det, image_sizes, min_score) if slots else np.zeros((B, 0), bool)
+    drawn = drawn_rows(det, s.image_sizes(), min_score) if slots else np.zeros((B, 0), bool)
     groups = []
     for b in range(B):
         above = []                                               # the drawn rows before row i
@@ -1198,11 +1065,8 @@ def _rle_disjoint(host_definition, det_src, rle, sizes, min_score, device):
             if drawn[b, i]:
                 above = above + [k]
     goffs, mem = _groups_of(name, groups)
-    out, out_offs, areas, bboxes = _combine_flat(host_definition, space, counts, offs, hs, ws, goffs, mem, _lib.RLE_DIFF)
-    if pair:
-        return (out, out_offs), areas, bboxes
-    host = lambda a: a if space.on_host else a.cpu().numpy()
-    return rle_rows_of((out, out_offs), image_sizes), host(areas).view(np.uint32).reshape(B, slots), host(bboxes).reshape(B, slots, 4)
+    out, out_offs, areas, bboxes = _combine_flat(host_definition, s.space, s.counts, s.offs, *s.sides(), goffs, mem, _lib.RLE_DIFF)
+    return _rle_back(s, (out, out_offs), areas, bboxes)
 
 
 def rle_disjoint(det_src, rle, sizes=None, min_score: float = 0.0, device=None):
@@ -1230,18 +1094,9 @@ def _transform_flat(host_definition, space, counts, offs, hs, ws, ohs, ows, xf):
     from the input's runs; if the result needs more, one more call with the capacity the library reported."""
     n = int(offs.shape[0]) - 1
     ptr = space.ptr
-    out_offs, areas, bboxes = space.new(n + 1, np.int64, zero=True), space.new(max(1, n), np.uint32), space.new((max(1, n), 4), np.int32)
     entry = _lib.lib().mrcnn_rle_transform_host if host_definition else _lib.lib().mrcnn_rle_transform
     head = (ptr(counts), ptr(offs), n, hs.ctypes.data, ws.ctypes.data, ohs.ctypes.data, ows.ctypes.data, xf.ctypes.data) + (() if host_definition else (space.code,))
-    capacity = int(counts.shape[0]) + 2 * n + 2
-    for _ in range(2):
-        out = space.new(max(1, capacity), np.uint32)
-        st = entry(*head, ptr(out), capacity, ptr(out_offs), ptr(areas), ptr(bboxes))
-        if st != 4 or int(out_offs[n]) <= capacity:
-            break
-        capacity = int(out_offs[n])
-    _lib.check(st)
-    return out[:int(out_offs[n])], out_offs, areas[:n], bboxes[:n]
+    return _marshal.rle_out(space, n, int(counts.shape[0]) + 2 * n + 2, lambda *tail: entry(*head, *tail))
 
 
 def _per_rle(name, what, a, width, B, slots, dtype=np.int64):
@@ -1260,25 +1115,21 @@ def _per_rle(name, what, a, width, B, slots, dtype=np.int64):
 def _xf_call(host_definition, name, rle, sizes, device, make):
     """One transform call: ``make(hs, ws, per)`` -> (xf (n, 8), out sizes (n, 2) as (h, w)) from the planes' sides per RLE, with
     per(what, a, width) = _per_rle of this set.  Returns (rle, areas, boxes, sizes) in the form ``rle`` came in."""
-    pair, space, counts, offs, B, slots, hs, ws = _combine_set(name, host_definition, rle, sizes, device)
-    n = B * slots
+    s = _marshal.RleSet(name, rle, sizes, device, host_definition)
+    B, slots, n = s.B, s.slots, s.n
     xf, osz = np.zeros((1, 8), np.int64), np.ones((1, 2), np.int64)          # (no RLE: nothing is read)
     if n:
+        hs, ws = s.sides()
         xf, osz = make(hs.astype(np.int64), ws.astype(np.int64), lambda what, a, width: _per_rle(name, what, a, width, B, slots))
         xf, osz = np.ascontiguousarray(xf, dtype=np.int64).reshape(n, 8), np.asarray(osz, dtype=np.int64).reshape(n, 2)
     if n and ((osz < 1).any() or (osz > 32767).any()):
         raise ValueError(f"{name}: an output plane of {osz[((osz < 1) | (osz > 32767)).any(1)][0].tolist()}: height and width must lie in 1..32767")
     ohs, ows = np.ascontiguousarray(osz[:, 0], dtype=np.int32), np.ascontiguousarray(osz[:, 1], dtype=np.int32)
-    out, out_offs, areas, bboxes = _transform_flat(host_definition, space, counts, offs, hs, ws, ohs, ows, xf)
+    out, out_offs, areas, bboxes = _transform_flat(host_definition, s.space, s.counts, s.offs, *s.sides(), ohs, ows, xf)
     per = [(int(h), int(w)) for h, w in zip(ohs[:n], ows[:n])]
     uniform = slots > 0 and all(per[b * slots + i] == per[b * slots] for b in range(B) for i in range(slots))
     new_sizes = [per[b * slots] for b in range(B)] if uniform else per      # per image where every RLE of an image got the same plane
-    if pair:
-        return (out, out_offs), areas, bboxes, new_sizes
-    host = lambda a: a if space.on_host else a.cpu().numpy()
-    c, o = host(out).view(np.uint32), host(out_offs)
-    rows = [[{"size": list(per[b * slots + i]), "counts": c[int(o[b * slots + i]):int(o[b * slots + i + 1])]} for i in range(slots)] for b in range(B)]
-    return rows, host(areas).view(np.uint32).reshape(B, slots), host(bboxes).reshape(B, slots, 4), new_sizes
+    return (*_rle_back(s, (out, out_offs), areas, bboxes, sizes=per), new_sizes)
 
 
 def _records(flags, ax, bx, dx, ay, by, dy):
@@ -1453,21 +1304,17 @@ def _hull_flat(host_definition, space, counts, offs, hs, ws):
     entry = _lib.lib().mrcnn_rle_convex_hull_host if host_definition else _lib.lib().mrcnn_rle_convex_hull
     head = (ptr(counts), ptr(offs), n, hs.ctypes.data, ws.ctypes.data) + (() if host_definition else (space.code,))
     nv = C.c_int64(0)
-    capacity = 32 * n + 64
-    for _ in range(2):
+
+    def attempt(capacity):
         xy = space.new((max(1, capacity), 2), np.int32)
         st = entry(*head, ptr(hull_offs), ptr(areas2), ptr(obb), ptr(xy), C.byref(nv), capacity)
-        if st != 4 or int(nv.value) <= capacity:
-            break
-        capacity = int(nv.value)
-    _lib.check(st)
-    return hull_offs, xy[:int(nv.value)], areas2[:n], obb[:n]
+        return st, int(nv.value), xy[:int(nv.value)]
+    return hull_offs, _marshal.with_capacity(32 * n + 64, attempt), areas2[:n], obb[:n]
 
 
 def _rle_measure(host_definition, rle, sizes, device):
-    name = "rle_measure_host" if host_definition else "rle_measure"
-    _, space, counts, offs, _, _, hs, ws = _combine_set(name, host_definition, rle, sizes, device)
-    return _measure_flat(host_definition, space, counts, offs, hs, ws)
+    s = _marshal.RleSet("rle_measure_host" if host_definition else "rle_measure", rle, sizes, device, host_definition)
+    return _measure_flat(host_definition, s.space, s.counts, s.offs, *s.sides())
 
 
 def rle_measure(rle, sizes=None, device=None):
@@ -1486,12 +1333,11 @@ def rle_measure_host(rle, sizes=None):
 
 
 def _rle_convex_hull(host_definition, rle, sizes, flat, device):
-    name = "rle_convex_hull_host" if host_definition else "rle_convex_hull"
-    _, space, counts, offs, _, _, hs, ws = _combine_set(name, host_definition, rle, sizes, device)
-    hull_offs, xy, areas2, obb = _hull_flat(host_definition, space, counts, offs, hs, ws)
+    s = _marshal.RleSet("rle_convex_hull_host" if host_definition else "rle_convex_hull", rle, sizes, device, host_definition)
+    hull_offs, xy, areas2, obb = _hull_flat(host_definition, s.space, s.counts, s.offs, *s.sides())
     if flat:
         return hull_offs, xy, areas2, obb
-    o = hull_offs if space.on_host else hull_offs.cpu().numpy()
+    o = s.space.host(hull_offs)
     return [xy[int(o[k]):int(o[k + 1])] for k in range(len(o) - 1)], areas2, obb
 
 
@@ -1555,12 +1401,10 @@ def region_props_of(measures, hull_offsets, xy, areas2, obb):
 
 
 def _rle_region_props(host_definition, rle, sizes, device):
-    name = "rle_region_props_host" if host_definition else "rle_region_props"
-    _, space, counts, offs, _, _, hs, ws = _combine_set(name, host_definition, rle, sizes, device)
-    measures = _measure_flat(host_definition, space, counts, offs, hs, ws)
-    tables = _hull_flat(host_definition, space, counts, offs, hs, ws)
-    host = lambda a: a if space.on_host else a.cpu().numpy()
-    return region_props_of(host(measures), *(host(t) for t in tables))
+    s = _marshal.RleSet("rle_region_props_host" if host_definition else "rle_region_props", rle, sizes, device, host_definition)
+    measures = _measure_flat(host_definition, s.space, s.counts, s.offs, *s.sides())
+    tables = _hull_flat(host_definition, s.space, s.counts, s.offs, *s.sides())
+    return region_props_of(s.space.host(measures), *(s.space.host(t) for t in tables))
 
 
 def rle_region_props(rle, sizes=None, device=None):

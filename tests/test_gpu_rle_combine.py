@@ -66,6 +66,18 @@ def test_single_groups(cases, name):
         assert want[0].view(np.uint32).tolist() == CC.encode(CC.reference([planes[k] for k in groups[0]], op)).tolist()
 
 
+def test_a_result_past_the_first_guess_takes_the_wrappers_second_attempt(pkg, monkeypatch):
+    """one 4 x 4 checkerboard of 13 runs, four groups of it alone: the wrapper guesses 13 + 2 * 4 + 2 = 23 runs, the result holds 52"""
+    L = _mod("_lib").lib()
+    yy, xx = np.mgrid[0:4, 0:4]
+    runs = CC.encode(((xx + yy) % 2).astype(np.uint8))
+    entry, capacities = L.mrcnn_rle_combine, []
+    monkeypatch.setattr(L, "mrcnn_rle_combine", lambda *a: capacities.append(a[11]) or entry(*a))
+    want = _both_memspaces_equal_the_definition([runs], [4], [4], [[0], [0], [0], [0]], CC.OR, "four copies of a checkerboard")
+    assert capacities == [23, 52, 23, 52]                        # from host memory, then from device tensors
+    assert want[0].tolist() == runs.tolist() * 4 and want[1].tolist() == [0, 13, 26, 39, 52] and want[2].tolist() == [8] * 4
+
+
 # ---- 2. errors ---------------------------------------------------------------------------------------------------------------------------
 def _device_call(counts, offs, hs, ws, groups, op, capacity, fill=77, out=True):
     """mrcnn_rle_combine on device tensors with pre-filled outputs -> (status, message, [out_counts, out_run_offsets, areas, bboxes])"""

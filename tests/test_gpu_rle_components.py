@@ -288,6 +288,20 @@ def test_the_selection_capacity_its_size_query_and_n_comps(pkg):
     assert st == 0 and out_n == 0 and bufs[1][0] == 0, msg
 
 
+def test_a_split_past_the_first_guess_takes_the_wrappers_second_attempt(pkg, monkeypatch):
+    """the top and the bottom row of a 3 x 8 plane (tests/test_rle_components_host.py says why): 18 runs and two components, a first
+    guess of 18 + 2 * 2 + 2 = 24 and a result of 33 runs, from host memory and from device tensors"""
+    L = _mod("_lib").lib()
+    plane = np.zeros((3, 8), np.uint8)
+    plane[[0, 2]] = 1
+    runs = MC.encode(plane)
+    entry, capacities = L.mrcnn_rle_components_select, []
+    monkeypatch.setattr(L, "mrcnn_rle_components_select", lambda *a: capacities.append(a[12]) or entry(*a))
+    want = _selection_in_both_memspaces(runs, np.array([0, 18], np.int64), [3], [8], 4, "ones", np.ones(2, np.uint8), "split", "two rows, split")
+    assert capacities == [24, 33, 24, 33]                        # from host memory, then from device tensors
+    assert want[1].tolist() == [0, 17, 33] and want[4].tolist() == [0, 0]
+
+
 # ---- 3. the helpers on a resident pair -----------------------------------------------------------------------------------------------------
 def test_the_helpers_change_a_resident_pair_where_it_lies(pkg):
     import tiles_cases as TC

@@ -197,6 +197,20 @@ def test_size_query_small_capacity_and_no_groups():
     assert one.tolist() == [0]
 
 
+def test_a_result_past_the_first_guess_takes_the_wrappers_second_attempt(monkeypatch):
+    """one 4 x 4 checkerboard of 13 runs, four groups of it alone: the wrapper guesses 13 + 2 * 4 + 2 = 23 runs, the result holds 52"""
+    D, L = _mod("detection"), _mod("_lib").lib()
+    yy, xx = np.mgrid[0:4, 0:4]
+    runs = CC.encode(((xx + yy) % 2).astype(np.uint8))
+    assert len(runs) == 13
+    entry, capacities = L.mrcnn_rle_combine_host, []
+    monkeypatch.setattr(L, "mrcnn_rle_combine_host", lambda *a: capacities.append(a[10]) or entry(*a))
+    (counts, offs), areas, boxes = D.rle_combine_host((runs, np.array([0, 13], np.int64)), [(4, 4)], [[0], [0], [0], [0]], "or")
+    assert capacities == [23, 52]
+    assert counts.tolist() == runs.tolist() * 4 and offs.tolist() == [0, 13, 26, 39, 52]
+    assert areas.tolist() == [8] * 4 and boxes.tolist() == [[0, 0, 4, 4]] * 4
+
+
 # ---- 3. the helpers ------------------------------------------------------------------------------------------------------------------------
 def disjoint_batch():
     """three images of different sizes, 7 rows each: overlapping ellipses, and rows that are not drawn — a score of 0, a score below

@@ -218,6 +218,24 @@ def test_the_helpers_on_the_host(cases, labelled):
         D.rle_select_components_host(pair, sizes, np.ones(len(areas), np.uint8), mode="cut")
 
 
+def test_a_split_past_the_first_guess_takes_the_wrappers_second_attempt(pkg, monkeypatch):
+    """A run of ones that wraps from the bottom of a column into the top of the next is one run of the input and a run each of two
+    components.  The top and the bottom row of a 3 x 8 plane: 18 runs and two components, so the wrapper guesses 18 + 2 * 2 + 2 = 24,
+    and the two rows, a run per column each, hold 17 + 16 = 33."""
+    D, L = _mod("detection"), _mod("_lib").lib()
+    plane = np.zeros((3, 8), np.uint8)
+    plane[[0, 2]] = 1
+    runs = MC.encode(plane)
+    assert len(runs) == 18
+    entry, capacities = L.mrcnn_rle_components_select_host, []
+    monkeypatch.setattr(L, "mrcnn_rle_components_select_host", lambda *a: capacities.append(a[11]) or entry(*a))
+    (counts, offs), parent = D.rle_split_components_host((runs, np.array([0, 18], np.int64)), [(3, 8)])
+    assert capacities == [24, 33]
+    top, bottom = plane.copy(), plane.copy()
+    top[2], bottom[0] = 0, 0
+    assert counts.tolist() == MC.encode(top).tolist() + MC.encode(bottom).tolist() and offs.tolist() == [0, 17, 33] and parent.tolist() == [0, 0]
+
+
 # ---- errors and capacities ---------------------------------------------------------------------------------------------------------------
 def _three():
     planes = [MC.ellipse(20, 30, 10, 15, 6, 9), np.ones((7, 5), np.uint8), CC.rings(16)]
